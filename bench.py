@@ -18,6 +18,12 @@ script starts `python -m torch.distributed.run --nproc-per-node N` on itself as 
 and exits with the child's code; under the driver's launcher it finds WORLD_SIZE set and runs as a rank.  A run whose world
 size is not `--gpus` is an error, never a silent 1-GPU bench.  Prints ONE JSON line on rank 0.
 
+A plain run does what the headline needs: set-up, burn-in and settling sweeps, the W warm-up steps, the K timed steps (`value`,
+`ms_per_step`, the roofline of the sweep as the timed launches measured it, `comm` counts), the line.  `--dump-outputs DIR` writes what
+the last timed step computed (see dump_outputs).  `--full` adds every other measurement below: the events block of the statistics
+launches (`lean_kernel_ms`, `launches_ms`, `stats_kernels_ms`, all-reduce times), the extra blocks, the dense sweep, the growth run,
+the host-master leg, the legs and the CPU baseline (each `--no-*` option drops one of them from a full run).
+
 Besides the contract fields the JSON line carries
   roofline      the NIW sweep (for 33 <= D <= 64 two launches: niw_lean_kernel, which finishes the tiles its screens settle and
                 dominates, and niw_sweep_direct_kernel<LSTORE,LIST> on the spans it hands on; `launches_ms` splits the time)
@@ -83,6 +89,11 @@ def parse_args():
     ap.add_argument("--comm-timeout", type=float, default=300.0, help="seconds a rank waits in a collective before it gives up (dead peer)")
     ap.add_argument("--share-gpu", action="store_true",
                     help="development: all ranks on device 0 over gloo + the library's host transport (boxes with one GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline block: extra blocks, dense sweep, growth run, host-master leg, "
+                         "other-shape legs, CPU baseline (a plain run sets up, warms up, times --steps steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float32 / float64, < 64 MB in all)")
     return ap.parse_args()
 
 
@@ -107,6 +118,52 @@ def visible_gpus():
         if v is not None:
             n = min(n, len([x for x in v.split(",") if x.strip() != ""]))
     return n
+
+
+def gaussian_mixture_shard_threaded(host, N, D, K, mixture_var, seed, lo, hi, threads=None, part=500000):
+    """host.gaussian_mixture_shard(N, D, K, mixture_var, seed, lo, hi), the row range cut into parts generated on threads (numpy's
+    generators and matrix products release the GIL).  Every chunk of the generator has a seed of its own, so the rows are bit-identical
+    to the one-call result."""
+    threads = threads or min(16, os.cpu_count() or 1)
+    X = np.empty((hi - lo, D), np.float32)
+    y = np.empty(hi - lo, np.int64)
+    edges = list(range(lo, hi, part)) + [hi]
+
+    def gen(i):
+        a, b = edges[i], edges[i + 1]
+        X[a - lo:b - lo], y[a - lo:b - lo] = host.gaussian_mixture_shard(N, D, K, mixture_var, seed, a, b)
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(threads) as ex:
+        list(ex.map(gen, range(len(edges) - 1)))
+    return X, y
+
+
+DUMP_LIMIT = 64 << 20         # bytes of all files --dump-outputs writes
+DUMP_POINTS = 1 << 20         # labels of at most this many points (a fixed, seeded sample of the shard)
+DUMP_ENTRIES = 1 << 19        # entries of each parameter array (a fixed, seeded sample of larger ones: big D / K runs)
+DUMP_SEED = 20240611
+
+
+def dump_outputs(path, s, wk):
+    """What a caller of the timed path (group_step) receives after its last step: labels and sub-labels of a fixed sample of the
+    shard's points (their indices in `point_index`), the cluster parameters, weights, counts and K; DIR/<name>.npy, float32 / float64."""
+    lab, sub = wk.get_labels()
+    n = len(lab)
+    idx = np.arange(n) if n <= DUMP_POINTS else np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_POINTS, replace=False))
+    out = {"labels": lab[idx].astype(np.float32), "sub_labels": sub[idx].astype(np.float32), "point_index": idx.astype(np.float64)}
+    arrays = dict(s.params)
+    arrays.update(weights=s.weights, lr_weights=s.lr_weights, counts=s.N, K=np.array([s.K]))
+    for name, a in arrays.items():
+        a = np.asarray(a, np.float64)
+        if a.size > DUMP_ENTRIES:
+            a = a.ravel()[np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, DUMP_ENTRIES, replace=False))]
+        out[name] = a
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_LIMIT, total
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return sorted(out)
 
 
 def relaunch_as_ranks(args):
@@ -605,7 +662,7 @@ def main():
     N, D, K = int(args.points), args.dim, args.clusters
     comm = TorchDistComm(device=local_rank) if world > 1 else host.LocalComm()
     lo, hi = (N * rank) // world, (N * (rank + 1)) // world
-    X, y = host.gaussian_mixture_shard(N, D, K, 100.0, DATA_SEED, lo, hi)
+    X, y = gaussian_mixture_shard_threaded(host, N, D, K, 100.0, DATA_SEED, lo, hi)
 
     prior = host.niw_hyperparams(1.0, np.zeros(D), D + 3, np.eye(D))      # default prior, dp-parallel-sampling.jl:272-274
     wk = pkg.Worker(pkg.PRIOR_NIW, D, hi - lo, first_index=lo, device=local_rank, seed=SAMPLER_SEED)
@@ -692,15 +749,19 @@ def main():
         wk.last_kernel_ms()
     elapsed = timed_block(args.steps, collect)
     ci1 = wk.comm_info()
-    work.append(wk.last_sweep_work())     # per-launch averages over exactly the timed launches
+    work.append(wk.last_sweep_work())     # per-launch averages over the warm-up + timed launches
     t_after = dict(s.timers)
-    wk.set_timing(15)
-    timed_block(args.steps, collect_all)
-    wk.set_timing(1)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, s, wk)
+    # everything below the headline block measures something else: only with --full
     block_rates = []
-    for _ in range(max(0, args.blocks)):
-        block_rates.append(args.steps / timed_block(args.steps))
-    wk.set_timing(7)
+    if args.full:
+        wk.set_timing(15)
+        timed_block(args.steps, collect_all)
+        wk.set_timing(1)
+        for _ in range(max(0, args.blocks)):
+            block_rates.append(args.steps / timed_block(args.steps))
+        wk.set_timing(7)
 
     k_mean = float(np.mean(ks))
     flops_alg = 2.0 * n_local * D * D * (k_mean + 2)       # likelihood vs K clusters + own left/right (per point x points)
@@ -734,7 +795,7 @@ def main():
                             "niw_sweep_direct_kernel<LSTORE,LIST> (labels and sub-labels of the spans handed on)": float(pm[1]),
                             "niw_sub_kernel (every tile's sub-labels: only in sweeps without the lean launch)": float(pm[2]),
                             "note": "HIP events between the launches of one sweep, recorded in the second block (timing bit 8); "
-                                    "avg_launch_ms is the sweep's events of the headline block"},
+                                    "avg_launch_ms is the sweep's events of the headline block"} if parts_ms else None,
             "algorithmic_flops_per_launch": flops_alg, "executed_flops_per_launch": exe,
             "executed_tflops": exe / (avg_sweep_ms * 1e-3) / 1e12, "pruning_factor": flops_alg / exe if exe else None,
             "algorithmic_tflops": achieved, "algorithmic_mfma_frac": achieved / PEAK_F32_MFMA_TFLOPS,
@@ -747,12 +808,12 @@ def main():
                                "(= (SQ_INSTS_VALU_MFMA_MOPS_F32 / peak_f32 + ..._BF16 / peak_bf16) x 512: `pmc_frac`); `algorithmic_tflops` = the "
                                "sweep's algorithmic Float32 flops (SURVEY 8d) over the same duration: above the Float32 peak because exact screening "
                                "skips clusters; `dense_*` = the same sweep with screening off",
-            "stats_kernels_ms": float(np.mean(stats_ms)), "kernel_source_tag": kernel_source_tag()}
+            "stats_kernels_ms": float(np.mean(stats_ms)) if stats_ms else None, "kernel_source_tag": kernel_source_tag()}
     if headline_shape:
         roof.update(pmc_matrix_pipe("bench", sweep_kernels, avg_sweep_ms))
 
     # same kernel, same process, screening off: every cluster is evaluated in full (labels are bit-identical by construction)
-    if not args.no_dense:
+    if args.full and not args.no_dense:
         wk.set_option(binding.OPT_SCREEN_MARGIN, 0.0)
         dm, dw = [], []
         for _ in range(3):
@@ -797,15 +858,15 @@ def main():
                  "occupancy_allreduce_ms": float(np.mean([c[0] for c in comm_ms])) if comm_ms else None,
                  "rows_allreduce_ms": float(np.mean([c[1] for c in comm_ms])) if comm_ms else None,
                  "note": "HIP events on the ctx stream around each all-reduce of the timed steps (rank 0); they include waiting for the slowest rank"},
-        "blocks": {"it_per_s": block_rates, "min": float(np.min(block_rates)) if block_rates else None,
-                   "median": float(np.median(block_rates)) if block_rates else None, "max": float(np.max(block_rates)) if block_rates else None},
         "host_ms_per_step": {k: 1e3 * (t_after[k] - t_before[k]) / (args.steps + args.warmup) for k in t_after},
     }
-
-    final_params = (s.params, np.log(s.weights), np.log(s.lr_weights))   # before the growth run re-uses the context's staging
+    if args.full:
+        out["blocks"] = {"it_per_s": block_rates, "min": float(np.min(block_rates)) if block_rates else None,
+                         "median": float(np.median(block_rates)) if block_rates else None, "max": float(np.max(block_rates)) if block_rates else None}
+        final_params = (s.params, np.log(s.weights), np.log(s.lr_weights))   # before the growth run re-uses the context's staging
 
     # growth trajectory (each NIW config also from init_clusters=1): same data, same context, fresh model
-    if not args.no_growth:
+    if args.full and not args.no_growth:
         g = host.DPMMSampler(wk, prior, ALPHA, N, SAMPLER_SEED, burnout=BURNOUT, comm=comm)
         g.init_first_clusters(1)
         fence()
@@ -826,7 +887,7 @@ def main():
 
     # the configuration north_star words: posterior parameter draws and split / merge steps on the HOST (DPMMH_OPT_DEVICE_MASTER = 0) --
     # same data, same context, same steady state; the headline runs the engine's default for D >= 64 (device master, dpmm_hip_master.h)
-    if not args.no_host_master:
+    if args.full and not args.no_host_master:
         engine = importlib.import_module("dpmmsubclusters_jl_amd.host.engine")
         hm = host.DPMMSampler(wk, prior, ALPHA, N, SAMPLER_SEED, burnout=BURNOUT, comm=comm)
         hm.model.set_option(engine.OPT_DEVICE_MASTER, 0)
@@ -849,10 +910,10 @@ def main():
                               "note": "DPMMH_OPT_DEVICE_MASTER = 0: posteriors, factorisations, parameter draws and every Metropolis step on the host "
                                       "(src/shared_actions.jl:41-66, src/priors/niw.jl:20-40), parameters through dpmm_params_staging / dpmm_commit_params"}
 
-    if rank == 0 and world == 1 and not args.no_legs:
+    if args.full and rank == 0 and world == 1 and not args.no_legs:
         out["legs"] = run_legs(args, pkg, host, torch, out["ms_per_step"])
 
-    if rank == 0 and not args.no_cpu_baseline and world == 1:
+    if args.full and rank == 0 and not args.no_cpu_baseline and world == 1:
         from oracle import cpu_baseline
         p, logw, loglr = final_params
         inv, _ = host.native.niw_expand(p["R"], want_sigma=False)

@@ -8,7 +8,7 @@ OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd $GRAFT_REPO_ROOT
 python -m pytest tests -m gpu -q > $OUT/gpu_suite.log 2>&1; tail -2 $OUT/gpu_suite.log
-python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; cut -c1-300 $OUT/bench_default.json
+python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; cut -c1-300 $OUT/bench_default.json
 for what in bench shard mult d256; do
   bash scripts/collect_profiles.sh ${TAG}_prof_$what $what > /dev/null 2>&1
   P=$GRAFT_REPO_ROOT/gpurun_out/${TAG}_prof_$what

@@ -3,6 +3,9 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -146,3 +149,94 @@ def test_the_committed_counter_summaries_parse_for_the_kernels_the_bench_quotes(
     assert t is not None and t > 1e9
     t, _ = bench.pmc_traffic("mult", "mult_sweep", allow_stale=True)
     assert t is not None and t > 1e8
+
+
+def test_options_default_to_a_plain_run(monkeypatch):
+    bench = _bench_module()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse_args()
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse_args()
+    assert a.full and a.dump_outputs == "out"
+
+
+def test_threaded_generation_is_bit_identical_to_the_one_call_generator():
+    import importlib
+    sys.path.insert(0, ROOT)
+    from __graft_entry__ import load_package
+    load_package()
+    host = importlib.import_module("dpmmsubclusters_jl_amd.host")
+    bench = _bench_module()
+    N, D, K, lo, hi = 230000, 8, 4, 12345, 230000
+    X0, y0 = host.gaussian_mixture_shard(N, D, K, 100.0, bench.DATA_SEED, lo, hi)
+    X1, y1 = bench.gaussian_mixture_shard_threaded(host, N, D, K, 100.0, bench.DATA_SEED, lo, hi, threads=4, part=50000)
+    assert np.array_equal(X0, X1) and np.array_equal(y0, y1)
+
+
+class _FakeWorker:
+    def __init__(self, n):
+        rng = np.random.default_rng(3)
+        self.lab, self.sub = rng.integers(1, 33, n), rng.integers(1, 3, n)
+
+    def get_labels(self):
+        return self.lab.copy(), self.sub.copy()
+
+
+class _FakeSampler:
+    def __init__(self, K, D, big):
+        rng = np.random.default_rng(4)
+        self.params = {"mu": rng.normal(size=(3 * K, D)), "R": rng.normal(size=(3 * K, D, big)), "logdet": rng.normal(size=3 * K)}
+        self.weights, self.lr_weights = np.full(K, 1.0 / K), np.full((K, 2), 0.5)
+        self.N = rng.integers(0, 1000, (K, 3)).astype(np.float64)
+        self.K = K
+
+
+def test_dump_outputs_are_float_arrays_within_the_limit_and_repeatable(tmp_path):
+    """--dump-outputs: float32 / float64 .npy files, at most 64 MB in all, the same files for the same state (fixed, seeded samples)."""
+    bench = _bench_module()
+    n = 3 * bench.DUMP_POINTS
+    wk, s = _FakeWorker(n), _FakeSampler(32, 64, 1000)          # R has 6.1 M entries: sampled
+    names = bench.dump_outputs(str(tmp_path / "a"), s, wk)
+    bench.dump_outputs(str(tmp_path / "b"), s, wk)
+    assert {"labels", "sub_labels", "point_index", "mu", "R", "logdet", "weights", "lr_weights", "counts", "K"} <= set(names)
+    total = 0
+    for name in names:
+        a = np.load(tmp_path / "a" / (name + ".npy"))
+        assert a.dtype in (np.float32, np.float64), name
+        assert np.array_equal(a, np.load(tmp_path / "b" / (name + ".npy"))), name
+        total += (tmp_path / "a" / (name + ".npy")).stat().st_size
+    assert total <= 64 << 20
+    idx = np.load(tmp_path / "a" / "point_index.npy").astype(np.int64)
+    assert len(idx) == bench.DUMP_POINTS and np.all(np.diff(idx) > 0)
+    assert np.array_equal(np.load(tmp_path / "a" / "labels.npy"), wk.lab[idx].astype(np.float32))
+    assert np.array_equal(np.load(tmp_path / "a" / "mu.npy"), s.params["mu"])
+    assert np.load(tmp_path / "a" / "R.npy").size == bench.DUMP_ENTRIES and float(np.load(tmp_path / "a" / "K.npy")[0]) == 32
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(900)
+def test_plain_run_times_the_steps_and_dumps_the_last_ones_outputs(tmp_path):
+    """A plain run (no --full) prints the contract line for exactly --steps timed steps, measures nothing beside the headline block,
+    and --dump-outputs writes the state of its last step."""
+    import json
+    n = 200000
+    r = _run(["--gpus", "1", "--points", str(n), "--steps", "7", "--warmup", "2", "--settle", "5", "--dump-outputs", str(tmp_path / "out")])
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads(r.stdout.splitlines()[-1])
+    assert line["steps"] == 7 and line["warmup"] == 2 and line["n_gpus"] == 1 and line["value"] > 0
+    assert abs(line["ms_per_step"] * line["value"] - 1e3) < 1e-6 * 1e3
+    for k in ("metric", "unit", "higher_is_better", "dtype"):
+        assert k in line, k
+    d = json.loads([ln for ln in r.stderr.splitlines() if ln.startswith("bench.py details: ")][-1][len("bench.py details: "):])
+    for k in ("blocks", "growth", "host_master", "legs", "cpu_baseline"):
+        assert k not in d, k
+    out = tmp_path / "out"
+    files = sorted(out.iterdir())
+    assert sum(f.stat().st_size for f in files) <= 64 << 20
+    arrs = {f.stem: np.load(f) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+    K = int(arrs["K"][0])
+    assert K >= 1 and len(arrs["labels"]) == n and len(arrs["sub_labels"]) == n
+    assert arrs["labels"].min() >= 0 and arrs["labels"].max() <= K and np.isfinite(arrs["mu"]).all()
+    assert int(arrs["counts"].reshape(-1, 3)[:K, 0].sum()) == n

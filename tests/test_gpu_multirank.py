@@ -206,7 +206,7 @@ def test_bench_starts_its_own_ranks_and_reports_the_collective(tmp_path):
     share = [] if torch.cuda.device_count() >= 2 else ["--share-gpu"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--points", "400000", "--steps", "5", "--warmup", "1",
-                        "--settle", "5", "--blocks", "1", "--no-legs", "--no-cpu-baseline", "--no-dense", "--growth-iters", "40"] + share,
+                        "--settle", "5", "--full", "--blocks", "1", "--no-legs", "--no-cpu-baseline", "--no-dense", "--growth-iters", "40"] + share,
                        env=env, capture_output=True, text=True, timeout=800)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
@@ -231,7 +231,7 @@ def test_bench_with_eight_ranks_on_one_gpu(tmp_path):
         pytest.skip("no GPU")
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--share-gpu", "--points", "800000", "--steps", "5", "--warmup", "1",
-                        "--settle", "5", "--blocks", "1", "--no-legs", "--no-cpu-baseline", "--no-dense", "--growth-iters", "40"],
+                        "--settle", "5", "--full", "--blocks", "1", "--no-legs", "--no-cpu-baseline", "--no-dense", "--growth-iters", "40"],
                        env=env, capture_output=True, text=True, timeout=1400)
     assert r.returncode == 0, r.stderr[-2000:]
     short = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
