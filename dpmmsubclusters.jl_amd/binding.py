@@ -23,6 +23,7 @@ ABI = [
     ("dpmm_upload_points", ctypes.c_int, [ctypes.c_void_p, _c_f32p, ctypes.c_int64]),
     ("dpmm_upload_points_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]),
     ("dpmm_upload_points_npy", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int]),
+    ("dpmm_upload_points_csc", ctypes.c_int, [ctypes.c_void_p, _c_i64p, _c_i64p, _c_f32p, ctypes.c_int]),
     ("dpmm_init_labels", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32]),
     ("dpmm_set_labels", ctypes.c_int, [ctypes.c_void_p, _c_i64p, _c_i64p]),
     ("dpmm_get_labels", ctypes.c_int, [ctypes.c_void_p, _c_i64p, _c_i64p]),
@@ -261,6 +262,14 @@ class Worker:
         assert rows.ndim == 2 and rows.shape[0] == self.n and rows.shape[1] >= self.D
         self._chk(self._lib.dpmm_upload_points_npy(self._h, ctypes.c_void_p(rows.ctypes.data), int(rows.dtype == np.float64),
                                                    rows.shape[1], int(bool(nan_to_zero))))
+
+    def upload_points_csc(self, colptr, rowval, nzval, index_base=0):
+        """The shard as compressed sparse columns, one column per point (Multinomial): colptr (n_local + 1,), rowval / nzval the entries
+        [colptr[i] - colptr[0], colptr[i+1] - colptr[0]) of point i; canonical (rows strictly increasing inside a column)."""
+        colptr, rowval, nzval = _i64(colptr), _i64(rowval), _f32(nzval)
+        assert colptr.ndim == 1 and colptr.size == self.n + 1 and rowval.size == nzval.size
+        assert colptr.size == 0 or rowval.size >= colptr[-1] - colptr[0]
+        self._chk(self._lib.dpmm_upload_points_csc(self._h, _p(colptr, _c_i64p), _p(rowval, _c_i64p), _p(nzval, _c_f32p), int(index_base)))
 
     def upload_points_device(self, ptr, ldx):
         self._chk(self._lib.dpmm_upload_points_device(self._h, ctypes.c_void_p(ptr), ldx))

@@ -112,6 +112,15 @@ struct dpmm_ctx {
     int64_t ld8 = 0;
     int x_u8 = 0;
     int opt_no_u8 = 0;
+    // MULT: the points as compressed sparse columns (dpmm_upload_points_csc; mult_sparse.hip) -- then dX / dX8 are not allocated, and d_Rp / d_Rp2
+    // hold the TRANSPOSED parameter image [D][3K] the sparse sweep reads (rp_current stays false: the Float32 fragment image is not kept)
+    int x_sparse = 0;
+    int64_t *d_cp = nullptr;
+    uint16_t *d_ri = nullptr;
+    float *d_val = nullptr;
+    int64_t nnz = 0;
+    int chunk_dense = 512;            // points per statistics item while the points are dense (`chunk` is the one in use: set_points_chunk)
+    bool repack_pending = false;      // a dense upload replaced sparse points: the dense kernels' parameter images are made from the raw rows
     float *d_scratch = nullptr;
     int64_t scratch_stride = 0;
     bool have_params = false;
@@ -616,8 +625,10 @@ int dpmm_create(dpmm_ctx **out, int prior_kind, int D, int64_t n_local, int64_t 
     const int64_t min_chunk = (c->prior == DPMM_PRIOR_NIW && c->D <= 64) ? 32 : 256;
     const int64_t target_items2 = (c->prior == DPMM_PRIOR_NIW && c->D <= 64) ? 65536 : target_items;
     c->chunk = (int)std::max<int64_t>(min_chunk, ((n_local + target_items2 - 1) / target_items2 + 3) / 4 * 4);
+    c->chunk_dense = c->chunk;
     const size_t nalloc = (size_t)std::max<int64_t>(n_local, 1);
-    CHK_CREATE(hipMalloc(&c->dX, sizeof(float) * nalloc * (size_t)c->ldx));
+    // (Multinomial: the dense matrix is allocated by the first dense upload -- ensure_points_buffer -- a context that is given sparse points never holds one)
+    if (prior_kind == DPMM_PRIOR_NIW) CHK_CREATE(hipMalloc(&c->dX, sizeof(float) * nalloc * (size_t)c->ldx));
     CHK_CREATE(hipMalloc(&c->dbins, sizeof(int32_t) * nalloc));
     // sort tiles: 512 points per sorting wave below 4e6 points (the tile kernels are one-wave latency chains: at the 8-GPU shard size four
     // times as many waves of a quarter of the trips each), 2048 above; the tables are sized for whichever is in use (DPMM_OPT_SORT_TILE
@@ -680,7 +691,7 @@ int dpmm_destroy(dpmm_ctx *c) {
     hipSetDevice(c->device);
     if (c->stream && !c->comm_aborted.load()) hipStreamSynchronize(c->stream);
     free_params(c);
-    hipFree(c->dX); hipFree(c->dX8); hipFree(c->dbins); hipFree(c->d_gt); hipFree(c->d_cont);
+    hipFree(c->dX); hipFree(c->dX8); hipFree(c->d_cp); hipFree(c->d_ri); hipFree(c->d_val); hipFree(c->dbins); hipFree(c->d_gt); hipFree(c->d_cont);
     hipFree(c->sb.tile_hist); hipFree(c->sb.tile_cnt); hipFree(c->sb.tile_spec); hipFree(c->sb.spec_bins); hipFree(c->sb.fast_total); hipFree(c->sb.ticket); hipFree(c->sb.prev_lab); hipFree(c->sb.cdirty); hipFree(c->sb.cmode); hipFree(c->sb.bin_total); hipFree(c->sb.bin_start); hipFree(c->sb.item_start);
     hipFree(c->sb.perm); hipFree(c->sb.bin_sel); hipFree(c->sb.perm_total); hipFree(c->d_small); hipFree(c->d_proj); hipFree(c->d_vals); hipFree(c->d_smart);
     hipFree(c->d_m0); hipFree(c->d_psi_lo); hipFree(c->d_pairs);
@@ -748,13 +759,14 @@ static int finish_upload(dpmm_ctx *c) {
         }
         // parameters that stay in place across the upload were packed for the OLD points' sweep kernel (byte planes / bf16 planes / Float32
         // fragments): when the new points take another kernel, the images it reads are made from the raw rows now
-        if (c->have_params && c->d_raw && (was_u8 != c->x_u8 || was_bf16 != c->x_bf16_exact)) {
+        if (c->have_params && c->d_raw && (was_u8 != c->x_u8 || was_bf16 != c->x_bf16_exact || c->repack_pending)) {
             HIPCHK(c, launch_mult_pack(c->d_raw, c->d_Rp, 3 * c->K, c->ldx, c->stream));
             c->rp_current = true;
             if (c->x_u8) HIPCHK(c, launch_mult_pack_u8(c->d_raw, c->d_Lp16, 3 * c->K, c->ldx, c->ld8, c->stream));
             else if (c->x_bf16_exact) HIPCHK(c, launch_mult_pack_bf16(c->d_raw, c->d_Lp16, 3 * c->K, c->ldx, c->stream));
             c->mspec_valid = false;
         }
+        c->repack_pending = false;
     }
     HIPCHK(c, sync_stream(c, c->stream));
     // new points: the cached cluster-level statistics (derive_rows_kernel) and the rows a device master would draw from belong to the old ones
@@ -763,7 +775,37 @@ static int finish_upload(dpmm_ctx *c) {
     return DPMM_OK;
 }
 
-static int ensure_points_buffer(dpmm_ctx *c) {       // (a byte-path Multinomial context gave its Float32 matrix back)
+// Points per statistics item for the kind of points in force.  Dense: as ever.  Sparse: a slab is D doubles in global memory (512 KB at
+// D = 65536), so the items that cover the points are sized to keep their slabs within 256 MB (at least 64 items; never finer than the dense
+// items: unchanged up to D = 4096).  The 2 Kcap slabs for the bins' ragged ends come on top, whatever the chunk.
+static int set_points_chunk(dpmm_ctx *c, bool sparse) {
+    int want = c->chunk_dense;
+    if (sparse) {
+        const int64_t items = std::max<int64_t>(64, std::min<int64_t>(8192, ((int64_t)256 << 20) / (8 * (int64_t)c->D)));
+        want = std::max(want, (int)std::max<int64_t>(256, ((c->n + items - 1) / items + 3) / 4 * 4));
+    }
+    if (want == c->chunk) return DPMM_OK;
+    HIPCHK(c, sync_stream(c, c->stream));
+    c->chunk = want;
+    if (c->Kcap > 0) {      // the slabs are allocated per item (ensure_capacity)
+        hipFree(c->d_slabs); c->d_slabs = nullptr;
+        c->max_items = (int)((c->n + c->chunk - 1) / c->chunk) + 2 * c->Kcap;
+        HIPCHK(c, hipMalloc(&c->d_slabs, sizeof(double) * (size_t)c->max_items * (size_t)c->slab_stride));
+    }
+    return DPMM_OK;
+}
+static void free_sparse_points(dpmm_ctx *c) {
+    hipFree(c->d_cp); hipFree(c->d_ri); hipFree(c->d_val);
+    c->d_cp = nullptr; c->d_ri = nullptr; c->d_val = nullptr; c->nnz = 0;
+}
+static int ensure_points_buffer(dpmm_ctx *c) {       // (a byte-path Multinomial context gave its Float32 matrix back; one with sparse points never had it)
+    if (c->x_sparse) {
+        HIPCHK(c, sync_stream(c, c->stream));
+        free_sparse_points(c);
+        c->x_sparse = 0;
+        c->repack_pending = true;
+        if (int rc = set_points_chunk(c, false)) return rc;
+    }
     if (!c->dX) HIPCHK(c, hipMalloc(&c->dX, sizeof(float) * (size_t)std::max<int64_t>(c->n, 1) * (size_t)c->ldx));
     return DPMM_OK;
 }
@@ -810,6 +852,97 @@ int dpmm_upload_points_npy(dpmm_ctx *c, const void *rows, int is_f64, int64_t ld
         hipFree(tmp);
         if (rc != DPMM_OK) return rc;
         if (int rc2 = finish_upload(c)) return rc2;
+    }
+    c->have_points = true;
+    c->cache_force = true;
+    c->rows_full_K = -1;
+    return DPMM_OK;
+}
+
+// the image the sparse sweep reads, into the buffer the dense Float32 kernel's fragment image lives in otherwise
+static int pack_sparse_image(dpmm_ctx *c, const float *raw, float *Rp, int K) {
+    HIPCHK(c, launch_mult_pack_sparse(raw, Rp, K, c->D, c->ldx, c->stream));
+    return DPMM_OK;
+}
+static MultSparse sparse_args(const dpmm_ctx *c) {
+    MultSparse sp{};
+    sp.cp = c->d_cp; sp.ri = c->d_ri; sp.val = c->d_val; sp.T = c->d_Rp; sp.ticket = c->sb.ticket;
+    return sp;
+}
+
+int dpmm_upload_points_csc(dpmm_ctx *c, const int64_t *colptr, const int64_t *rowval, const float *nzval, int index_base) {
+    if (!c) return DPMM_EINVAL;
+    if (c->prior != DPMM_PRIOR_MULT) return fail(c, DPMM_EINVAL, "dpmm_upload_points_csc: sparse points are for Multinomial contexts");
+    if (c->D > DPMM_MAX_DIM_MULT_SPARSE) return fail(c, DPMM_ELIMIT, "dpmm_upload_points_csc: D > DPMM_MAX_DIM_MULT_SPARSE");
+    if (index_base != 0 && index_base != 1) return fail(c, DPMM_EINVAL, "dpmm_upload_points_csc: index_base must be 0 or 1");
+    if (!colptr) return fail(c, DPMM_EINVAL, "dpmm_upload_points_csc: colptr is null");
+    const int64_t n = c->n;
+    for (int64_t i = 0; i < n; ++i)
+        if (colptr[i + 1] < colptr[i]) return fail(c, DPMM_EINVAL, "dpmm_upload_points_csc: colptr decreases at point " + std::to_string(i));
+    const int64_t total = colptr[n] - colptr[0];
+    if (total > 0 && (!rowval || !nzval)) return fail(c, DPMM_EINVAL, "dpmm_upload_points_csc: rowval / nzval is null");
+    HIPCHK(c, hipSetDevice(c->device));
+    // everything is built beside the points in force; they are replaced only when the new ones have passed the checks
+    int64_t *t_cp = nullptr, *t_rv = nullptr, *n_cp = nullptr;
+    float *t_nz = nullptr, *n_val = nullptr;
+    uint16_t *n_ri = nullptr;
+    int32_t *t_cnt = nullptr;
+    unsigned long long *t_bad = nullptr;
+    std::vector<int32_t> cnt((size_t)n);
+    std::vector<int64_t> ncp((size_t)n + 1, 0);
+    unsigned long long bad = ~0ull;
+    std::string msg;
+    int rc = DPMM_OK;
+    hipError_t e = hipMalloc(&n_cp, sizeof(int64_t) * ((size_t)n + 1));
+    if (e == hipSuccess && n > 0) {
+        const size_t tt = (size_t)std::max<int64_t>(total, 1);
+        e = hipMalloc(&t_cp, sizeof(int64_t) * ((size_t)n + 1));
+        if (e == hipSuccess) e = hipMalloc(&t_rv, sizeof(int64_t) * tt);
+        if (e == hipSuccess) e = hipMalloc(&t_nz, sizeof(float) * tt);
+        if (e == hipSuccess) e = hipMalloc(&t_cnt, sizeof(int32_t) * (size_t)n);
+        if (e == hipSuccess) e = hipMalloc(&t_bad, sizeof(unsigned long long));
+        if (e == hipSuccess) e = hipMemcpyAsync(t_cp, colptr, sizeof(int64_t) * ((size_t)n + 1), hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess && total > 0) e = hipMemcpyAsync(t_rv, rowval, sizeof(int64_t) * (size_t)total, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess && total > 0) e = hipMemcpyAsync(t_nz, nzval, sizeof(float) * (size_t)total, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(t_bad, 0xFF, sizeof(unsigned long long), c->stream);
+        if (e == hipSuccess) e = launch_csc_check(t_cp, t_rv, t_nz, n, total, c->D, index_base, t_cnt, t_bad, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(&bad, t_bad, sizeof(bad), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(cnt.data(), t_cnt, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = sync_stream(c, c->stream);
+        if (e == hipSuccess && bad != ~0ull) {
+            rc = DPMM_EINVAL;
+            msg = "dpmm_upload_points_csc: point " + std::to_string((long long)(bad >> 2)) +
+                  ((bad & 3) == 1 ? ": row index out of range" : ": row indices are not strictly increasing (unsorted or duplicate)");
+        }
+        if (e == hipSuccess && rc == DPMM_OK) {
+            for (int64_t i = 0; i < n; ++i) ncp[i + 1] = ncp[i] + cnt[i];      // explicit zeros are dropped
+            const size_t nn = (size_t)std::max<int64_t>(ncp[n], 1);
+            e = hipMalloc(&n_ri, sizeof(uint16_t) * nn);
+            if (e == hipSuccess) e = hipMalloc(&n_val, sizeof(float) * nn);
+            if (e == hipSuccess) e = hipMemcpyAsync(n_cp, ncp.data(), sizeof(int64_t) * ((size_t)n + 1), hipMemcpyHostToDevice, c->stream);
+            if (e == hipSuccess) e = launch_csc_compact(t_cp, t_rv, t_nz, n, index_base, n_cp, n_ri, n_val, c->stream);
+            if (e == hipSuccess) e = sync_stream(c, c->stream);
+        }
+    } else if (e == hipSuccess) {
+        e = hipMemsetAsync(n_cp, 0, sizeof(int64_t), c->stream);
+        if (e == hipSuccess) e = sync_stream(c, c->stream);
+    }
+    hipFree(t_cp); hipFree(t_rv); hipFree(t_nz); hipFree(t_cnt); hipFree(t_bad);
+    if (e != hipSuccess || rc != DPMM_OK) {
+        hipFree(n_cp); hipFree(n_ri); hipFree(n_val);
+        if (e != hipSuccess) return fail(c, DPMM_EHIP, std::string("dpmm_upload_points_csc: ") + hipGetErrorString(e));
+        return fail(c, rc, msg);
+    }
+    free_sparse_points(c);
+    hipFree(c->dX); hipFree(c->dX8); c->dX = nullptr; c->dX8 = nullptr;
+    c->d_cp = n_cp; c->d_ri = n_ri; c->d_val = n_val; c->nnz = ncp[n];
+    c->x_sparse = 1; c->x_u8 = 0; c->x_bf16_exact = 0; c->repack_pending = false;
+    if (int rc2 = set_points_chunk(c, true)) return rc2;
+    if (c->have_params && c->d_raw) {       // parameters stay in force across an upload: the image the sparse sweep reads, from the raw rows
+        if (int rc2 = pack_sparse_image(c, c->d_raw, c->d_Rp, c->K)) return rc2;
+        c->rp_current = false;
+        c->mspec_valid = false;
+        HIPCHK(c, sync_stream(c, c->stream));
     }
     c->have_points = true;
     c->cache_force = true;
@@ -1011,8 +1144,9 @@ int dpmm_commit_params(dpmm_ctx *c, int K) {
     } else {
         HIPCHK(c, launch_copy_bytes(c->d_cst, hcst, sizeof(float) * 3 * K, c->stream));
         HIPCHK(c, launch_gather_rows(c->d_raw, c->ldx, hmat, c->D, hslot, 3 * K, c->D, c->stream));
-        HIPCHK(c, launch_mult_pack(c->d_raw, c->d_Rp, 3 * K, c->ldx, c->stream));
-        c->rp_current = true;
+        if (c->x_sparse) { if (int rc = pack_sparse_image(c, c->d_raw, c->d_Rp, K)) return rc; }
+        else HIPCHK(c, launch_mult_pack(c->d_raw, c->d_Rp, 3 * K, c->ldx, c->stream));
+        c->rp_current = !c->x_sparse;
         if (c->x_u8) HIPCHK(c, launch_mult_pack_u8(c->d_raw, c->d_Lp16, 3 * K, c->ldx, c->ld8, c->stream));
         else if (c->x_bf16_exact) HIPCHK(c, launch_mult_pack_bf16(c->d_raw, c->d_Lp16, 3 * K, c->ldx, c->stream));
     }
@@ -1299,7 +1433,8 @@ static int run_sweep(dpmm_ctx *c, uint32_t epoch, int final_argmax, float *table
         a.use_prev = c->have_labels ? 1 : 0;
         a.order = (!table && c->have_perm && c->opt_ordered) ? c->sb.perm : nullptr;
         a.order_total = c->sb.perm_total;
-        if (c->x_u8) HIPCHK(c, launch_mult_sweep_u8(a, c->dX8, c->ld8, c->d_Lp16, c->sweep_grid, c->stream));
+        if (c->x_sparse) HIPCHK(c, launch_mult_sweep_sparse(a, sparse_args(c), c->sweep_grid, c->stream));
+        else if (c->x_u8) HIPCHK(c, launch_mult_sweep_u8(a, c->dX8, c->ld8, c->d_Lp16, c->sweep_grid, c->stream));
         else if (c->x_bf16_exact) HIPCHK(c, launch_mult_sweep_bf16(a, c->d_Lp16, c->sweep_grid, c->stream));
         else {
             if (!c->rp_current) { HIPCHK(c, launch_mult_pack(c->d_raw, c->d_Rp, 3 * c->K, c->ldx, c->stream)); c->rp_current = true; }      // (skipped by a device-master draw)
@@ -1560,7 +1695,8 @@ static int run_stats(dpmm_ctx *c, const int64_t *idx, int n_idx, bool with_reset
             HIPCHK(c, launch_niw_stats(a, c->stream));
         } else if (c->n > 0) {
             // Multinomial: the usual statistics + derivation of the speculatively reset labels into d_out, then the travelling rows from them
-            if (c->x_u8) HIPCHK(c, launch_mult_stats_u8(a, c->dX8, c->ld8, c->stream));
+            if (c->x_sparse) HIPCHK(c, launch_mult_stats_sparse(a, sparse_args(c), c->stream));
+            else if (c->x_u8) HIPCHK(c, launch_mult_stats_u8(a, c->dX8, c->ld8, c->stream));
             else HIPCHK(c, launch_mult_stats(a, c->stream));
             if (derive) HIPCHK(c, launch_derive_rows(c->d_out, c->d_ccache, c->sb.cmode, c->sb.cdirty, c->packed_stride, c->K, flags, nullptr, c->stream));
             HIPCHK(c, launch_onecoll_rows(c->d_out, c->d_red, c->packed_stride, c->K, c->d_cside, flags, c->stream));
@@ -1593,7 +1729,8 @@ static int run_stats(dpmm_ctx *c, const int64_t *idx, int n_idx, bool with_reset
         }
         HIPCHK(c, launch_niw_stats(a, c->stream));
     } else {
-        if (c->x_u8) HIPCHK(c, launch_mult_stats_u8(a, c->dX8, c->ld8, c->stream));
+        if (c->x_sparse) HIPCHK(c, launch_mult_stats_sparse(a, sparse_args(c), c->stream));
+        else if (c->x_u8) HIPCHK(c, launch_mult_stats_u8(a, c->dX8, c->ld8, c->stream));
         else HIPCHK(c, launch_mult_stats(a, c->stream));
         if (derive) HIPCHK(c, launch_derive_rows(c->d_out, c->d_ccache, c->sb.cmode, c->sb.cdirty, c->packed_stride, c->K, fsrc, ride ? flags_to : nullptr, c->stream));
     }
@@ -1671,8 +1808,9 @@ int dpmm_step_stats(dpmm_ctx *c, uint32_t reset_epoch, const double **packed, co
         const uint32_t epoch = c->mdraw_epoch + 1;
         HIPCHK(c, launch_mult_dirichlet(c->d_out, c->packed_stride, c->d_malpha, c->mult_has_alpha1 ? c->d_malpha + c->ldx : nullptr, c->marg_req_outlier, c->D, c->ldx,
                                         K, c->seed, epoch, c->d_raw2, c->stream));
-        c->rp2_current = !(c->x_u8 || c->x_bf16_exact);                 // (only the Float32 sweep kernel reads that image)
+        c->rp2_current = !(c->x_u8 || c->x_bf16_exact || c->x_sparse);                 // (only the Float32 sweep kernel reads that image)
         if (c->rp2_current) HIPCHK(c, launch_mult_pack(c->d_raw2, c->d_Rp2, 3 * K, c->ldx, c->stream));
+        if (c->x_sparse) if (int rc = pack_sparse_image(c, c->d_raw2, c->d_Rp2, K)) return rc;
         if (c->x_u8) HIPCHK(c, launch_mult_pack_u8(c->d_raw2, c->d_Lp16_2, 3 * K, c->ldx, c->ld8, c->stream));
         else if (c->x_bf16_exact) HIPCHK(c, launch_mult_pack_bf16(c->d_raw2, c->d_Lp16_2, 3 * K, c->ldx, c->stream));
         c->mspec_valid = true; c->mspec_epoch = epoch; c->mspec_K = K; c->mspec_outlier = c->marg_req_outlier;
@@ -2367,8 +2505,9 @@ int dpmm_mult_master_draw(dpmm_ctx *c, uint32_t epoch, int K, int outlier_first,
     } else {
         HIPCHK(c, launch_mult_dirichlet(c->d_out, c->packed_stride, c->d_malpha, c->mult_has_alpha1 ? c->d_malpha + c->ldx : nullptr, outlier_first, c->D, c->ldx,
                                         K, c->seed, epoch, c->d_raw, c->stream));
-        c->rp_current = !(c->x_u8 || c->x_bf16_exact);
+        c->rp_current = !(c->x_u8 || c->x_bf16_exact || c->x_sparse);
         if (c->rp_current) HIPCHK(c, launch_mult_pack(c->d_raw, c->d_Rp, 3 * K, c->ldx, c->stream));
+        if (c->x_sparse) if (int rc = pack_sparse_image(c, c->d_raw, c->d_Rp, K)) return rc;
         if (c->x_u8) HIPCHK(c, launch_mult_pack_u8(c->d_raw, c->d_Lp16, 3 * K, c->ldx, c->ld8, c->stream));
         else if (c->x_bf16_exact) HIPCHK(c, launch_mult_pack_bf16(c->d_raw, c->d_Lp16, 3 * K, c->ldx, c->stream));
     }
@@ -2719,7 +2858,8 @@ int dpmm_set_option(dpmm_ctx *c, int option, double value) {
             c->opt_force_f32 = value != 0; return DPMM_OK;
         case DPMM_OPT_STATS_ITEMS:
             if (c->Kcap > 0) return fail(c, DPMM_ESTATE, "DPMM_OPT_STATS_ITEMS must be set before the first parameters / K");
-            if (value >= 1) c->chunk = (int)std::max<int64_t>((c->prior == DPMM_PRIOR_NIW && c->D <= 64) ? 32 : 256, ((c->n + (int64_t)value - 1) / (int64_t)value + 3) / 4 * 4);
+            if (value >= 1) c->chunk_dense = c->chunk = (int)std::max<int64_t>((c->prior == DPMM_PRIOR_NIW && c->D <= 64) ? 32 : 256, ((c->n + (int64_t)value - 1) / (int64_t)value + 3) / 4 * 4);
+            if (c->x_sparse) return set_points_chunk(c, true);
             return DPMM_OK;
         case DPMM_OPT_STATS_GROUPS: c->opt_stats_groups = value > 0 ? (int)value : 0; return DPMM_OK;
         case DPMM_OPT_TRACE_SLOW: c->opt_trace = value != 0; return DPMM_OK;
@@ -2942,6 +3082,20 @@ int dpmm_debug_subloglik(dpmm_ctx *c, float *out) {
         hipFree(tab);
         if (e != hipSuccess) { c->err = std::string("dpmm_debug_subloglik: ") + hipGetErrorString(e); return DPMM_EHIP; }
         return DPMM_OK;
+    }
+    if (c->prior == DPMM_PRIOR_MULT && c->x_sparse) {
+        // the sparse sweep's table mode evaluates all 3K rows with the arithmetic of its sub-label phase: rows 3k + 1 + s are the answer
+        const int64_t stride = c->ntiles * c->tile;
+        float *table = nullptr;
+        HIPCHK(c, hipMalloc(&table, sizeof(float) * (size_t)(3 * K) * (size_t)stride));
+        int rc = run_sweep(c, 0, 0, table, stride);
+        hipError_t e = hipSuccess;
+        for (int j = 0; j < K2 && rc == DPMM_OK && e == hipSuccess; ++j)
+            e = hipMemcpyAsync(out + (size_t)j * c->n, table + (size_t)(3 * (j / 2) + 1 + (j % 2)) * stride, sizeof(float) * (size_t)c->n, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = sync_stream(c, c->stream);
+        hipFree(table);
+        if (e != hipSuccess) { c->err = std::string("dpmm_debug_subloglik: ") + hipGetErrorString(e); return DPMM_EHIP; }
+        return rc;
     }
     if (K2 > DPMM_MAX_CLUSTERS) return fail(c, DPMM_ELIMIT, "debug_subloglik: 2K > DPMM_MAX_CLUSTERS");
     const int64_t stride = c->ntiles * c->tile;

@@ -82,6 +82,47 @@ __device__ __forceinline__ int draw2(float b0, float b1, float u) {
     return (cw < t) ? 1 : 0;
 }
 
+// Label draw of the Multinomial sweep kernels (sample_log_cat_array!, src/utils.jl:19-31, on the column of one point): `col[k * cs]`, k < K,
+// are the point's cluster-level values.  NaN -> -Inf, max-shifted exponentials, inverse-CDF scan with one uniform; a column of all -Inf
+// gives cluster 0; final_argmax: the first NaN if there is one (Julia's argmax), else the first maximum.  Returns the 0-based cluster.
+__device__ __forceinline__ int mult_draw_label(const float *col, int64_t cs, int K, int final_argmax, float u) {
+    float m = -INFINITY;
+    int best = 0;
+    bool nan_seen = false;
+    for (int k = 0; k < K; ++k) {
+        const float a = col[k * cs];
+        if (a != a) {
+            if (!nan_seen) { nan_seen = true; best = k; }
+        } else if (a > m) {
+            m = a;
+            if (!nan_seen) best = k;
+        }
+    }
+    if (final_argmax) return best;
+    if (m == -INFINITY) return 0;
+    float s = 0.f;
+    for (int k = 0; k < K; ++k) s += exp_det(nan_to_ninf(col[k * cs]) - m);
+    const float t = u * s;
+    float cw = 0.f;
+    for (int k = 0; k < K; ++k) {
+        cw += exp_det(nan_to_ninf(col[k * cs]) - m);
+        if (!(cw < t)) return k;
+    }
+    return K - 1;
+}
+
+// work item -> bin of the sorted order: the largest b with item_start[b] <= item (and item < item_start[b + 1])
+__device__ __forceinline__ int find_bin(const int32_t *__restrict__ item_start, int nbins, int item) {
+    int lo = 0, hi = nbins;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (item_start[mid] <= item) lo = mid; else hi = mid;
+    }
+    // skip empty bins that share the same start
+    while (lo + 1 < nbins && item_start[lo + 1] <= item) ++lo;
+    return lo;
+}
+
 // Certified upper bound of the spectral norm of an upper-triangular 4x4 matrix T = {T00 T01 T02 T03 | T11 T12 T13 | T22 T23 | T33}:
 // ||T||_2^2 = lambda_max(G), G = T'T (symmetric positive semi-definite), and lambda_max(G) <= tr(G^4)^(1/4) <= 4^(1/4) lambda_max(G):
 // within 19 % of the norm, where the Frobenius norm can be twice it.  Used by the ball test of the NIW sweeps (the pack kernels).

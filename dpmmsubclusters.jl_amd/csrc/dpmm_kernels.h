@@ -143,6 +143,25 @@ size_t mult_pack_u8_words(int rows, int64_t ld8);
 hipError_t launch_mult_pack_u8(const float *logp, uint32_t *Lp8, int rows, int64_t ldx, int64_t ld8, hipStream_t s);
 hipError_t launch_mult_sweep_u8(const MultSweepArgs &a, const uint8_t *X8, int64_t ld8, const uint32_t *Lp8, int grid, hipStream_t s);
 
+// ---- points stored as compressed sparse columns (mult_sparse.hip): cp [n + 1] offsets, ri [nnz] feature indices (strictly increasing inside
+// a column), val [nnz] values (none zero); T [D][3K] the transposed parameter image: columns [0, K) = rows 3k, column K + 2k + s = row 3k + 1 + s
+struct MultSparse {
+    const int64_t *cp;
+    const uint16_t *ri;
+    const float *val;
+    const float *T;
+    unsigned *ticket;    // [1] tile counter of the sweep kernel (cleared by its launcher)
+};
+hipError_t launch_csc_check(const int64_t *cp, const int64_t *rv, const float *nz, int64_t n, int64_t total, int D, int base, int32_t *cnt,
+                            unsigned long long *bad, hipStream_t s);
+hipError_t launch_csc_compact(const int64_t *cp, const int64_t *rv, const float *nz, int64_t n, int base, const int64_t *cp_out, uint16_t *ri, float *val,
+                              hipStream_t s);
+hipError_t launch_mult_pack_sparse(const float *logp, float *T, int K, int D, int64_t ldx, hipStream_t s);
+hipError_t launch_mult_sweep_sparse(const MultSweepArgs &a, const MultSparse &sp, int grid, hipStream_t s);      // a.X, a.logp, a.order are not read
+struct StatsArgs;
+hipError_t launch_mult_stats_sparse(const StatsArgs &a, const MultSparse &sp, hipStream_t s);                    // a.X is not read
+hipError_t launch_mult_reduce(const StatsArgs &a, hipStream_t s);
+
 // ---- label bookkeeping (labels.hip)
 // dst/src: device or pinned-host pointers, 4-byte aligned; bytes rounded up to a multiple of 4
 hipError_t launch_smart_project(const int32_t *bins, const float *X, int64_t ldx, int64_t n, int D, int k, const double *v, const double *mu,

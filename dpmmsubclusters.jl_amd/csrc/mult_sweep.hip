@@ -91,34 +91,7 @@ __global__ __launch_bounds__(256) void mult_sweep_kernel(MultSweepArgs A, const 
         if (valid && !A.labels_only) {
             const float *col = scr + lane;
             const Philox4 rr = philox4x32_10(A.seed, (uint64_t)(A.first_index + myp), A.epoch, STREAM_SWEEP);
-            int z = 0;
-            float m = -INFINITY;
-            int best = 0;
-            bool nan_seen = false;
-            for (int k = 0; k < K; ++k) {
-                const float a = col[(int64_t)(3 * k) * sstride];
-                if (a != a) {
-                    if (!nan_seen) { nan_seen = true; best = k; }
-                } else if (a > m) {
-                    m = a;
-                    if (!nan_seen) best = k;
-                }
-            }
-            if (A.final_argmax) {
-                z = best;
-            } else if (m == -INFINITY) {
-                z = 0;
-            } else {
-                float s = 0.f;
-                for (int k = 0; k < K; ++k) s += exp_det(nan_to_ninf(col[(int64_t)(3 * k) * sstride]) - m);
-                const float t = u01(rr.v[0]) * s;
-                float cw = 0.f;
-                z = K - 1;
-                for (int k = 0; k < K; ++k) {
-                    cw += exp_det(nan_to_ninf(col[(int64_t)(3 * k) * sstride]) - m);
-                    if (!(cw < t)) { z = k; break; }
-                }
-            }
+            const int z = mult_draw_label(col, 3 * sstride, K, A.final_argmax, u01(rr.v[0]));
             const float b0 = col[(int64_t)(3 * z + 1) * sstride], b1 = col[(int64_t)(3 * z + 2) * sstride];
             A.bins[myp] = 2 * z + draw2(b0, b1, u01(rr.v[1]));
         }
@@ -596,34 +569,7 @@ __global__ __launch_bounds__(256, (B_RBP <= 6 ? 2 : 1)) void mult_sweep_bf16_ker
         if (valid && !A.labels_only) {
             const float *col = scr + lane;
             const Philox4 rr = philox4x32_10(A.seed, (uint64_t)(A.first_index + myp), A.epoch, STREAM_SWEEP);
-            int z = 0;
-            float m = -INFINITY;
-            int best = 0;
-            bool nan_seen = false;
-            for (int k = 0; k < K; ++k) {
-                const float a = col[(int64_t)(3 * k) * sstride];
-                if (a != a) {
-                    if (!nan_seen) { nan_seen = true; best = k; }
-                } else if (a > m) {
-                    m = a;
-                    if (!nan_seen) best = k;
-                }
-            }
-            if (A.final_argmax) {
-                z = best;
-            } else if (m == -INFINITY) {
-                z = 0;
-            } else {
-                float s = 0.f;
-                for (int k = 0; k < K; ++k) s += exp_det(nan_to_ninf(col[(int64_t)(3 * k) * sstride]) - m);
-                const float t = u01(rr.v[0]) * s;
-                float cw = 0.f;
-                z = K - 1;
-                for (int k = 0; k < K; ++k) {
-                    cw += exp_det(nan_to_ninf(col[(int64_t)(3 * k) * sstride]) - m);
-                    if (!(cw < t)) { z = k; break; }
-                }
-            }
+            const int z = mult_draw_label(col, 3 * sstride, K, A.final_argmax, u01(rr.v[0]));
             const float b0 = col[(int64_t)(3 * z + 1) * sstride], b1 = col[(int64_t)(3 * z + 2) * sstride];
             A.bins[myp] = 2 * z + draw2(b0, b1, u01(rr.v[1]));
         }

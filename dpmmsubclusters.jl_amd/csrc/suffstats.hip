@@ -660,17 +660,6 @@ hipError_t launch_step_reset(int32_t *bins, int64_t n, int64_t first, int nbins,
 }
 
 // ------------------------------------------------------------------------------------ items
-__device__ __forceinline__ int find_bin(const int32_t *__restrict__ item_start, int nbins, int item) {
-    int lo = 0, hi = nbins;  // largest b with item_start[b] <= item and item < item_start[b+1]
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (item_start[mid] <= item) lo = mid; else hi = mid;
-    }
-    // skip empty bins that share the same start
-    while (lo + 1 < nbins && item_start[lo + 1] <= item) ++lo;
-    return lo;
-}
-
 // ------------------------------------------------------------------------------------ NIW statistics
 #ifndef DPMM_STATS16_SB
 #define DPMM_STATS16_SB 4       // k-steps per LDS batch of the D > 128 kernel (two buffers: 64 KiB of LDS; 2: 1.5 % slower)
@@ -1363,6 +1352,11 @@ hipError_t launch_mult_stats_u8(const StatsArgs &a, const uint8_t *X8, int64_t l
 }
 
 int64_t mult_slab_stride(int D) { return D; }
+
+hipError_t launch_mult_reduce(const StatsArgs &a, hipStream_t s) {      // behind a kernel of another file that filled the slabs (mult_sparse.hip)
+    DPMM_LAUNCH(mult_reduce_kernel, dim3((unsigned)((a.packed_stride + 255) / 256), a.nbins), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
 
 hipError_t launch_mult_stats(const StatsArgs &a, hipStream_t s) {
     const int grid = a.max_items < 1 ? 1 : a.max_items;

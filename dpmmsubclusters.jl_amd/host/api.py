@@ -8,7 +8,9 @@
 
 Argument meaning, defaults, coercions (Float32 data / Int64 iters, :279-293), the default NIW prior
 (kappa=1, m=0, nu=D+3, psi=I, :272-274) and the 9-tuple / 5-tuple results follow the reference.
-`all_data` is Dimensions x Samples (D x N) as in the reference.  Checkpoints (`save_model`), the advanced
+`all_data` is Dimensions x Samples (D x N) as in the reference.  Beyond the reference (whose points are a dense Matrix{Float32}), count
+data for the Multinomial prior may be given sparse: a scipy.sparse CSC matrix of shape (D, N) (or `csr.T`), or a tuple
+(colptr, rowval, nzval, (D, N)) -- host/sparse.py; the GPU then holds memory proportional to the stored entries.  Checkpoints (`save_model`), the advanced
 parameter-file mode `dp_parallel(model_params::String)` and `run_model_from_checkpoint` live in host/checkpoint.py.
 Smart splits (`smart_splits=True`, Gaussian prior) are driven by DPMMSampler.smart_cluster_init; the outlier component
 (`outlier_weight`, `outlier_params`) is cluster 1 of the model with a constant weight, never split, merged or re-drawn.
@@ -24,6 +26,7 @@ import numpy as np
 from .. import binding
 from . import priors as _priors
 from . import checkpoint as _ckpt
+from . import sparse as _sparse
 from .priors import multinomial_hyper, niw_hyperparams
 from .sampler import DPMMSampler, LocalComm
 
@@ -53,8 +56,13 @@ def _make_sampler(all_data, hyper, alpha, seed, burnout, max_clusters, comm, dev
                   rows=None, **sampler_kw):
     """`all_data`: Dimensions x Samples (basic mode), or `rows`: Samples x Dimensions as stored in a .npy file (advanced
     mode; cleaned and converted on the GPU by dpmm_upload_points_npy)."""
+    csc = None if rows is not None else _sparse.as_csc(all_data)
     if rows is not None:
         N, D = rows.shape
+    elif csc is not None:
+        if hyper.kind != _priors.PRIOR_MULT:
+            raise TypeError("sparse data is for the Multinomial prior (multinomial_hyper); the Gaussian prior takes a dense array")
+        D, N = csc.shape
     else:
         X = np.asarray(all_data)
         if X.ndim != 2:
@@ -73,6 +81,8 @@ def _make_sampler(all_data, hyper, alpha, seed, burnout, max_clusters, comm, dev
             wk.upload_points_npy(rows[lo:hi])
         else:
             wk.upload_points(np.nan_to_num(np.asarray(rows[lo:hi], dtype=np.float32), nan=0.0, posinf=np.inf, neginf=-np.inf))
+    elif csc is not None:
+        _sparse.upload_columns(wk, csc, lo, hi)       # columns [lo, hi): no rank touches another rank's entries
     else:
         wk.upload_points(np.ascontiguousarray(X[:, lo:hi].T, dtype=np.float32))  # (n_local, D): row = point
     return DPMMSampler(wk, hyper, alpha, N, int(seed), burnout=burnout, max_clusters=max_clusters, comm=comm, nthreads=nthreads,
@@ -207,6 +217,8 @@ def fit(all_data, *args, iters=100, init_clusters=1, seed=None, verbose=True, sa
     Returns the reference's 9-tuple: (labels, clusters, weights, iter_count, nmi_score_history,
     likelihood_history, cluster_count_history, sub_labels, dp_model)."""
     if len(args) == 1:
+        if _sparse.as_csc(all_data) is not None:
+            raise TypeError("sparse data is for the Multinomial prior: fit(all_data, multinomial_hyper(...), alpha)")
         D = np.asarray(all_data).shape[0]
         hyper = niw_hyperparams(1.0, np.zeros(D), D + 3, np.eye(D))   # dp-parallel-sampling.jl:272-274
         alpha = args[0]
@@ -226,11 +238,18 @@ def predict(dp_model, data, device=None, worker_factory=None):
     """predict(dp_model, data) -- src/dp-parallel-sampling.jl:532-537 with predict_points
     (src/local_clusters_actions.jl:23-40): weights = (points_count + alpha) / sum; per cluster the posterior predictive
     log-density (GPU), labels = row-wise argmax, probabilities = normalised exponentials (NaN -> -Inf).
-    `data` is Dimensions x Samples.  Returns (labels (n,) Int64 1-based, probs (n, K) Float32)."""
+    `data` is Dimensions x Samples, an array or (Multinomial prior) sparse columns as `fit` takes them.
+    Returns (labels (n,) Int64 1-based, probs (n, K) Float32)."""
     s = dp_model.sampler
     post = s.post
-    X = np.ascontiguousarray(np.asarray(data, dtype=np.float32).T)
-    n, D = X.shape
+    csc = _sparse.as_csc(data)
+    if csc is not None:
+        if s.prior.kind != _priors.PRIOR_MULT:
+            raise TypeError("sparse data is for the Multinomial prior")
+        D, n = csc.shape
+    else:
+        X = np.ascontiguousarray(np.asarray(data, dtype=np.float32).T)
+        n, D = X.shape
     if D != s.prior.dim:
         raise ValueError("data dimension does not match the model")
     w = s.points_count.astype(np.float64) + s.alpha
@@ -238,7 +257,10 @@ def predict(dp_model, data, device=None, worker_factory=None):
     dev = getattr(s.wk, "device", 0) if device is None else device
     wk = (worker_factory or binding.Worker)(s.prior.kind, D, n, first_index=0, device=dev, seed=0)
     try:
-        wk.upload_points(X)
+        if csc is not None:
+            _sparse.upload_columns(wk, csc, 0, n)
+        else:
+            wk.upload_points(X)
         if getattr(wk, "supports_predict_points", False):     # argmax + normalisation on the device as well
             return s.prior.predictive_table(wk, post, [3 * k for k in range(s.K)], w, points=True)
         parr = s.prior.predictive_table(wk, post, [3 * k for k in range(s.K)], w).T.astype(np.float32)   # (n, K)
@@ -310,8 +332,10 @@ def generate_gaussian_data(N, D, K, MixtureVar, seed=None):
     return np.ascontiguousarray(X.T), lab.astype(np.float32), means.T.astype(np.float32), covs.astype(np.float32)
 
 
-def generate_mnmm_data(N, D, K, trials, seed=None):
-    """Recipe of data_generators.jl:59-72. Returns (x D x N f32 counts, labels, clusters D x K)."""
+def generate_mnmm_data(N, D, K, trials, seed=None, sparse=False):
+    """Recipe of data_generators.jl:59-72. Returns (x D x N f32 counts, labels, clusters D x K).
+    sparse=True: the same draws with x as the tuple (colptr, rowval, nzval, (D, N)) of its compressed sparse columns (0-based, canonical),
+    built in blocks of points -- the dense D x N array is never made: the peak beside the result is one Int64 block of at most 32 MB."""
     rng = np.random.default_rng(seed)
     clusters = np.zeros((D, K))
     labels = rng.integers(1, K + 1, N)
@@ -319,8 +343,28 @@ def generate_mnmm_data(N, D, K, trials, seed=None):
         alphas = rng.integers(1, 21, D).astype(float)
         alphas[i % D] = rng.integers(30, 101)
         clusters[:, i] = rng.dirichlet(alphas)
-    x = np.empty((D, N), np.float32)
+    if not sparse:
+        x = np.empty((D, N), np.float32)
+        for i in range(K):
+            m = labels == i + 1
+            x[:, m] = rng.multinomial(trials, clusters[:, i], size=int(m.sum())).T
+        return x, labels, clusters
+    # a cluster's points are drawn in consecutive calls of rng.multinomial: the samples of one call are drawn one after the other, so the
+    # generator's stream -- and every count -- is the dense recipe's; a call's (points x D) Int64 block is the only dense piece
+    step = max(1, (32 << 20) // (8 * int(D)))
+    counts = np.zeros(N, np.int64)
+    parts = []
     for i in range(K):
-        m = labels == i + 1
-        x[:, m] = rng.multinomial(trials, clusters[:, i], size=int(m.sum())).T
-    return x, labels, clusters
+        members = np.nonzero(labels == i + 1)[0]
+        for a in range(0, members.size, step):
+            idx = members[a:a + step]
+            blk = rng.multinomial(trials, clusters[:, i], size=idx.size)
+            r, c = np.nonzero(blk)                           # row-major: by point, then by feature (increasing)
+            counts[idx] = np.bincount(r, minlength=idx.size)
+            parts.append((idx[r], c, blk[r, c].astype(np.float32)))
+            del blk
+    colptr = np.zeros(N + 1, np.int64)
+    np.cumsum(counts, out=colptr[1:])
+    pt = np.concatenate([p[0] for p in parts]); rv = np.concatenate([p[1] for p in parts]); nz = np.concatenate([p[2] for p in parts])
+    order = np.argsort(pt, kind="stable")                     # entries of a point stay in feature order
+    return (colptr, rv[order].astype(np.int64), nz[order], (int(D), int(N))), labels, clusters

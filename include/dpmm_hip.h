@@ -148,6 +148,7 @@ enum {
 
 #define DPMM_MAX_CLUSTERS 1024
 #define DPMM_MAX_DIM_NIW 256
+#define DPMM_MAX_DIM_MULT_SPARSE 65536   /* sparse points carry 16-bit feature indices on the device */
 
 int dpmm_abi_version(void);
 
@@ -172,6 +173,16 @@ int dpmm_upload_points_device(dpmm_ctx *ctx, const float *dX, int64_t ldx);
  * (is_f64 = 1), row r at rows + r*ld elements, host memory.  Conversion to Float32, the NaN -> 0 replacement (when
  * nan_to_zero != 0) and the re-layout happen on the device. */
 int dpmm_upload_points_npy(dpmm_ctx *ctx, const void *rows, int is_f64, int64_t ld, int nan_to_zero);
+/* Sparse points (Multinomial contexts; beyond the reference, whose points are a dense Matrix{Float32}): the shard as compressed sparse
+ * columns, one column per point -- Julia's SparseMatrixCSC (index_base = 1), scipy.sparse.csc_matrix of shape (D, n) (index_base = 0).
+ * colptr has n_local + 1 entries; the entries of point i are rowval / nzval [colptr[i] - colptr[0], colptr[i+1] - colptr[0]), so a slice
+ * of a larger matrix's colptr goes with pointers to the slice's first entry; index_base applies to colptr and rowval alike.  Host memory.
+ * Canonical input only: colptr non-decreasing, row indices in range and strictly increasing inside a column (checked on the device;
+ * DPMM_EINVAL names the first offending point and the points in force before the call stay in force).  Explicit zeros are dropped.
+ * D <= DPMM_MAX_DIM_MULT_SPARSE (DPMM_ELIMIT).  Device memory is proportional to the stored entries; every call that reads the points
+ * (sweep, statistics, predict, debug tables) works as after a dense upload, and dense and sparse uploads may follow each other.
+ * Convention: a feature a point does not store contributes nothing, also where its log-probability is -Inf (0 * log 0 = 0). */
+int dpmm_upload_points_csc(dpmm_ctx *ctx, const int64_t *colptr, const int64_t *rowval, const float *nzval, int index_base);
 
 /* labels = rand(1:init_clusters), sub-labels = rand(1:2) (dp-parallel-sampling.jl:49-50).
  * _from: labels = first_label - 1 + rand(1:init_clusters) -- `.+ 1` when cluster 1 is the outlier component (:49). */

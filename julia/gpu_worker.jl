@@ -9,6 +9,7 @@
 # array comprehensions of set_params! are emulated and compared with the ABI's memory layouts, every symbol is checked against the
 # header, every ccall's argument count against its C prototype.
 const libdpmm = "libdpmmhip.so"          # on LD_LIBRARY_PATH / dlopen path
+using SparseArrays                        # SparseMatrixCSC points of the Multinomial prior (dpmm_upload_points_csc)
 
 mutable struct GpuWorker
     h::Ptr{Cvoid}; D::Int; n::Int; K::Int; stride::Int
@@ -23,19 +24,32 @@ end
 prior_kind(::niw_hyperparams) = Cint(0)
 prior_kind(::multinomial_hyper) = Cint(1)
 
-function GpuWorker(hyper::distribution_hyper_params, pts::AbstractArray{Float32,2}, first_index::Int, device::Int, seed)
-    D, n = size(pts)
+# create the ctx, hand the points over with `upload(w)` (returns the call's status), read the packed-row stride
+function make_worker(upload, hyper::distribution_hyper_params, D::Int, n::Int, first_index::Int, device::Int, seed)
     ref = Ref{Ptr{Cvoid}}(C_NULL)
     rc = ccall((:dpmm_create, libdpmm), Cint, (Ref{Ptr{Cvoid}}, Cint, Cint, Int64, Int64, Cint, UInt64),
                ref, prior_kind(hyper), D, n, first_index, device, UInt64(seed))
     dpmm_check(rc, nothing)
     w = GpuWorker(ref[], D, n, 0, 0)
     finalizer(x -> ccall((:dpmm_destroy, libdpmm), Cint, (Ptr{Cvoid},), x.h), w)
-    # points are D x n column-major Float32 == the ABI's layout with ldx = D
-    dpmm_check(ccall((:dpmm_upload_points, libdpmm), Cint, (Ptr{Cvoid}, Ptr{Float32}, Int64), w.h, pts, D), w)
+    dpmm_check(upload(w), w)
     w.stride = ccall((:dpmm_packed_stride, libdpmm), Int64, (Ptr{Cvoid},), w.h)
     return w
 end
+
+# points are D x n column-major Float32 == the ABI's layout with ldx = D
+GpuWorker(hyper::distribution_hyper_params, pts::AbstractArray{Float32,2}, first_index::Int, device::Int, seed) =
+    make_worker(hyper, size(pts, 1), size(pts, 2), first_index, device, seed) do w
+        ccall((:dpmm_upload_points, libdpmm), Cint, (Ptr{Cvoid}, Ptr{Float32}, Int64), w.h, pts, size(pts, 1))
+    end
+
+# Sparse count data (Multinomial prior): the D x n SparseMatrixCSC goes over as it is -- colptr / rowval are 1-based (index_base = 1) and
+# the device keeps memory proportional to the stored entries; everything behind the upload is the same worker.
+GpuWorker(hyper::multinomial_hyper, pts::SparseMatrixCSC{Float32,Int64}, first_index::Int, device::Int, seed) =
+    make_worker(hyper, size(pts, 1), size(pts, 2), first_index, device, seed) do w
+        ccall((:dpmm_upload_points_csc, libdpmm), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}, Ptr{Float32}, Cint),
+              w.h, pts.colptr, pts.rowval, pts.nzval, 1)
+    end
 
 # replaces broadcast_cluster_params(params_vector, weights) for mv_gaussian clusters
 function set_params!(w::GpuWorker, params::Vector{thin_cluster_params{mv_gaussian}}, weights::Vector{Float32})
