@@ -101,6 +101,16 @@ ABI = [
     ("dpmm_comm_allgather_host", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
 ]
 
+# include/dpmm_hip_tensor.h: caller-owned device memory in and out (additive; bound next to ABI)
+ABI_TENSOR = [
+    ("dpmm_upload_points_strided_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int]),
+    ("dpmm_get_points_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]),
+    ("dpmm_get_labels_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    ("dpmm_set_labels_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    ("dpmm_predict_points_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+]
+DT_F16, DT_BF16, DT_F32, DT_F64, DT_U8, DT_I16, DT_I32, DT_I64 = range(8)      # DPMM_DT_* (include/dpmm_hip_tensor.h)
+
 HOST_ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int)   # dpmm_host_allreduce_fn
 
 # dpmm_set_option keys (include/dpmm_hip.h)
@@ -164,7 +174,7 @@ def load_library():
         except Exception:  # pragma: no cover  (torch is optional for single-GPU use)
             pass
         lib = ctypes.CDLL(p)
-        for name, res, args in ABI:
+        for name, res, args in ABI + ABI_TENSOR:
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -274,6 +284,39 @@ class Worker:
     def upload_points_device(self, ptr, ldx):
         self._chk(self._lib.dpmm_upload_points_device(self._h, ctypes.c_void_p(ptr), ldx))
 
+    # ---- caller-owned device memory (include/dpmm_hip_tensor.h); pointers are plain integers (tensor.data_ptr())
+    def upload_points_strided_device(self, ptr, dtype, stride_point, stride_feature, nan_to_zero=False):
+        """Element (point i, feature d) at ptr + (i * stride_point + d * stride_feature) elements of the DT_* type `dtype`, device memory."""
+        self._chk(self._lib.dpmm_upload_points_strided_device(self._h, ctypes.c_void_p(ptr), int(dtype), int(stride_point), int(stride_feature),
+                                                              int(bool(nan_to_zero))))
+
+    def upload_points_tensor(self, desc, lo, hi):
+        """The points [lo, hi) of a device tensor described by host/tensors.py: no copy, no slicing on the host -- the shard starts
+        lo * stride_point elements into the tensor's storage."""
+        assert hi - lo == self.n and desc.D == self.D
+        self.results_device = desc.torch_device            # labels and predictions follow the input (get_labels_tensor, _predict_points)
+        self.upload_points_strided_device(desc.shard_ptr(lo), desc.dtype, desc.stride_point, desc.stride_feature, False)
+
+    def get_points_device(self, ptr, ld_out):
+        self._chk(self._lib.dpmm_get_points_device(self._h, ctypes.c_void_p(ptr), int(ld_out)))
+
+    def get_labels_device(self, labels_ptr, sub_ptr):
+        self._chk(self._lib.dpmm_get_labels_device(self._h, ctypes.c_void_p(labels_ptr or None), ctypes.c_void_p(sub_ptr or None)))
+
+    def set_labels_device(self, labels_ptr, sub_ptr):
+        self._chk(self._lib.dpmm_set_labels_device(self._h, ctypes.c_void_p(labels_ptr or None), ctypes.c_void_p(sub_ptr or None)))
+
+    def predict_points_device(self, labels_ptr, probs_ptr):
+        self._chk(self._lib.dpmm_predict_points_device(self._h, ctypes.c_void_p(labels_ptr), ctypes.c_void_p(probs_ptr or None)))
+
+    def get_labels_tensor(self, device):
+        """(labels, sub_labels) as int64 tensors on `device` (this worker's GPU), written there by the library."""
+        import torch
+        lab = torch.empty(self.n, dtype=torch.int64, device=device); sub = torch.empty(self.n, dtype=torch.int64, device=device)
+        torch.cuda.current_stream(device).synchronize()
+        self.get_labels_device(lab.data_ptr(), sub.data_ptr())
+        return lab, sub
+
     def init_labels(self, init_clusters, epoch):
         self._chk(self._lib.dpmm_init_labels(self._h, init_clusters, epoch))
 
@@ -374,6 +417,13 @@ class Worker:
     supports_predict_points = True
 
     def _predict_points(self, K):
+        dev = getattr(self, "results_device", None)
+        if dev is not None:                  # the points came from a device tensor: the (n, K) table stays on that device
+            import torch
+            lab = torch.empty(self.n, dtype=torch.int64, device=dev); probs = torch.empty((self.n, K), dtype=torch.float32, device=dev)
+            torch.cuda.current_stream(dev).synchronize()
+            self.predict_points_device(lab.data_ptr(), probs.data_ptr())
+            return lab, probs
         lab = np.empty(self.n, np.int64); probs = np.empty((self.n, K), np.float32)
         self._chk(self._lib.dpmm_predict_points(self._h, _p(lab, _c_i64p), _p(probs, _c_f32p)))
         return lab, probs

@@ -6,6 +6,7 @@
 #include "../../include/dpmm_hip.h"
 #include "../../include/dpmm_hip_master.h"
 #include "../../include/dpmm_hip_debug.h"
+#include "../../include/dpmm_hip_tensor.h"
 
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -3238,6 +3239,153 @@ int dpmm_last_kernel_ms(dpmm_ctx *c, float *sweep_ms, float *stats_ms) {
     if (sweep_ms) { *sweep_ms = 0.f; if (c->have_sweep_ev) { HIPCHK(c, hipEventSynchronize(c->ev[1])); HIPCHK(c, hipEventElapsedTime(sweep_ms, c->ev[0], c->ev[1])); } }
     if (stats_ms) { *stats_ms = 0.f; if (c->have_stats_ev) { HIPCHK(c, hipEventSynchronize(c->ev[3])); HIPCHK(c, hipEventElapsedTime(stats_ms, c->ev[2], c->ev[3])); } }
     return DPMM_OK;
+}
+
+// ---- include/dpmm_hip_tensor.h: caller-owned device memory in and out --------------------------------------------------------------
+// Without a context there is nothing to work on: DPMM_ENODEVICE where no device exists (no CPU fallback), else a plain bad argument.
+static int tensor_no_ctx(const char *fn) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        (void)hipGetLastError();
+        return fail(nullptr, DPMM_ENODEVICE, std::string(fn) + ": no HIP device available (this library has no CPU fallback)");
+    }
+    return fail(nullptr, DPMM_EINVAL, std::string(fn) + ": ctx is null");
+}
+
+// `bytes` from `p` must be device memory of the ctx's device, inside one allocation, aligned to `align`: checked with the two runtime queries
+// before any launch (a bad pointer is a DPMM_EINVAL, never a GPU fault).  bytes == 0: nothing will be addressed, nothing to check.
+static int check_device_extent(dpmm_ctx *c, const char *fn, const char *arg, const void *p, uint64_t bytes, size_t align) {
+    const std::string who = std::string(fn) + ": " + arg;
+    if (bytes == 0) return DPMM_OK;
+    if (!p) return fail(c, DPMM_EINVAL, who + " is null");
+    if (reinterpret_cast<uintptr_t>(p) % align) return fail(c, DPMM_EINVAL, who + " is not aligned to its element size (" + std::to_string(align) + " bytes)");
+    hipPointerAttribute_t at{};
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(c, DPMM_EINVAL, who + " is not a device pointer (unknown to the HIP runtime)");
+    }
+    if (at.type != hipMemoryTypeDevice) return fail(c, DPMM_EINVAL, who + " is not device memory (host, managed or unregistered memory)");
+    if (at.device != c->device) return fail(c, DPMM_EINVAL, who + " lives on device " + std::to_string(at.device) + ", the context on device " + std::to_string(c->device));
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, const_cast<void *>(p)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(c, DPMM_EINVAL, who + ": the allocation it belongs to cannot be determined");
+    }
+    const uintptr_t b = reinterpret_cast<uintptr_t>(base), a = reinterpret_cast<uintptr_t>(p);
+    if (a < b || a - b > size || bytes > size - (a - b))
+        return fail(c, DPMM_EINVAL, who + ": the call addresses " + std::to_string((unsigned long long)bytes) + " bytes from it, its allocation holds " +
+                                        std::to_string((unsigned long long)(a >= b && a - b <= size ? size - (a - b) : 0)));
+    return DPMM_OK;
+}
+
+// a * b + ... in elements, refusing what does not fit 62 bits (the byte count must fit a uint64_t)
+static bool extent_elems(int64_t n, int64_t sp, int D, int64_t sf, uint64_t *out) {
+    const unsigned __int128 e = (unsigned __int128)(uint64_t)(n - 1) * (uint64_t)sp + (unsigned __int128)(uint64_t)(D - 1) * (uint64_t)sf + 1;
+    if (e >> 58) return false;
+    *out = (uint64_t)e;
+    return true;
+}
+
+int dpmm_upload_points_strided_device(dpmm_ctx *c, const void *d_src, int dtype, int64_t stride_point, int64_t stride_feature, int nan_to_zero) {
+    static const char *fn = "dpmm_upload_points_strided_device";
+    if (!c) return tensor_no_ctx(fn);
+    const size_t es = ingest_elem_size(dtype);
+    if (es == 0) return fail(c, DPMM_EINVAL, std::string(fn) + ": dtype " + std::to_string(dtype) + " is not a DPMM_DT_* code");
+    if (stride_point < 0 || stride_feature < 0) return fail(c, DPMM_EINVAL, std::string(fn) + ": stride_point / stride_feature is negative");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (c->n > 0) {
+        uint64_t elems = 0;
+        if (!extent_elems(c->n, stride_point, c->D, stride_feature, &elems)) return fail(c, DPMM_EINVAL, std::string(fn) + ": the strides address more than 2^58 elements");
+        if (int rc = check_device_extent(c, fn, "d_src", d_src, elems * es, es)) return rc;
+    }
+    // from here on as upload_common: the ctx-owned image, then what a Multinomial context derives from it
+    if (int rc = ensure_points_buffer(c)) return rc;
+    if (c->n > 0) {
+        HIPCHK(c, launch_ingest_strided(c->dX, c->ldx, d_src, dtype, stride_point, stride_feature, c->n, c->D, nan_to_zero, c->stream));
+        if (int rc = finish_upload(c)) return rc;
+    }
+    c->have_points = true;
+    c->cache_force = true;
+    c->rows_full_K = -1;
+    return DPMM_OK;
+}
+
+int dpmm_get_points_device(dpmm_ctx *c, float *d_out, int64_t ld_out) {
+    static const char *fn = "dpmm_get_points_device";
+    if (!c) return tensor_no_ctx(fn);
+    if (!c->have_points) return fail(c, DPMM_ESTATE, std::string(fn) + ": no points uploaded");
+    if (ld_out < c->D) return fail(c, DPMM_EINVAL, std::string(fn) + ": ld_out < D");
+    if (ld_out >> 40) return fail(c, DPMM_EINVAL, std::string(fn) + ": ld_out out of range");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (c->n == 0) return DPMM_OK;
+    if (int rc = check_device_extent(c, fn, "d_out", d_out, (uint64_t)c->n * (uint64_t)ld_out * sizeof(float), sizeof(float))) return rc;
+    if (c->x_sparse) {
+        HIPCHK(c, launch_points_readback(d_out, ld_out, nullptr, 0, nullptr, 0, c->n, c->D, c->stream));
+        HIPCHK(c, launch_sparse_readback(d_out, ld_out, c->d_cp, c->d_ri, c->d_val, c->n, c->stream));
+    } else if (c->dX) {
+        HIPCHK(c, launch_points_readback(d_out, ld_out, c->dX, c->ldx, nullptr, 0, c->n, c->D, c->stream));
+    } else if (c->x_u8 && c->dX8) {
+        HIPCHK(c, launch_points_readback(d_out, ld_out, nullptr, 0, c->dX8, c->ld8, c->n, c->D, c->stream));
+    } else return fail(c, DPMM_ESTATE, std::string(fn) + ": the context holds no point storage");
+    HIPCHK(c, sync_stream(c, c->stream));
+    return DPMM_OK;
+}
+
+int dpmm_get_labels_device(dpmm_ctx *c, int64_t *d_labels, int64_t *d_sub) {
+    static const char *fn = "dpmm_get_labels_device";
+    if (!c) return tensor_no_ctx(fn);
+    if (!c->have_labels) return fail(c, DPMM_ESTATE, "labels not initialised");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (c->n == 0 || (!d_labels && !d_sub)) return DPMM_OK;
+    const uint64_t bytes = sizeof(int64_t) * (uint64_t)c->n;
+    if (d_labels) if (int rc = check_device_extent(c, fn, "d_labels", d_labels, bytes, sizeof(int64_t))) return rc;
+    if (d_sub) if (int rc = check_device_extent(c, fn, "d_sub", d_sub, bytes, sizeof(int64_t))) return rc;
+    HIPCHK(c, launch_bins_to_i64(c->dbins, d_labels, d_sub, c->n, c->stream));      // (writes only the vectors that are given)
+    HIPCHK(c, sync_stream(c, c->stream));
+    return DPMM_OK;
+}
+
+int dpmm_set_labels_device(dpmm_ctx *c, const int64_t *d_labels, const int64_t *d_sub) {
+    static const char *fn = "dpmm_set_labels_device";
+    if (!c) return tensor_no_ctx(fn);
+    if (!c->have_labels && (!d_labels || !d_sub)) return fail(c, DPMM_ESTATE, "first dpmm_set_labels_device must provide both vectors");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (c->n == 0) { c->have_labels = true; return DPMM_OK; }
+    const uint64_t bytes = sizeof(int64_t) * (uint64_t)c->n;
+    if (d_labels) if (int rc = check_device_extent(c, fn, "d_labels", d_labels, bytes, sizeof(int64_t))) return rc;
+    if (d_sub) if (int rc = check_device_extent(c, fn, "d_sub", d_sub, bytes, sizeof(int64_t))) return rc;
+    if (d_labels || d_sub) {
+        HIPCHK(c, launch_bins_from_i64(c->dbins, d_labels, d_sub, c->n, c->stream));
+        HIPCHK(c, sync_stream(c, c->stream));
+    }
+    c->have_labels = true;
+    c->rows_full_K = -1;
+    return DPMM_OK;
+}
+
+int dpmm_predict_points_device(dpmm_ctx *c, int64_t *d_labels, float *d_probs) {
+    static const char *fn = "dpmm_predict_points_device";
+    if (!c) return tensor_no_ctx(fn);
+    if (!c->predictive) return fail(c, DPMM_ESTATE, "dpmm_predict_points_device needs dpmm_set_predictive_* first");
+    if (!c->have_points || !c->have_params) return fail(c, DPMM_ESTATE, "predict needs points and parameters");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (c->n == 0) return DPMM_OK;
+    if (!d_labels) return fail(c, DPMM_EINVAL, std::string(fn) + ": d_labels is null");
+    if (int rc = check_device_extent(c, fn, "d_labels", d_labels, sizeof(int64_t) * (uint64_t)c->n, sizeof(int64_t))) return rc;
+    if (d_probs) if (int rc = check_device_extent(c, fn, "d_probs", d_probs, sizeof(float) * (uint64_t)c->n * (uint64_t)c->K, sizeof(float))) return rc;
+    const int64_t stride = c->ntiles * c->tile;
+    const int rstep = (c->prior == DPMM_PRIOR_NIW) ? 1 : 3;       // Multinomial: rows 3k are the cluster-level rows
+    float *table = nullptr;
+    HIPCHK(c, hipMalloc(&table, sizeof(float) * (size_t)(rstep * c->K) * (size_t)stride));
+    int rc = run_sweep(c, 0, 0, table, stride);
+    if (rc == DPMM_OK) {
+        hipError_t e = launch_predict_finish(table, stride, rstep, c->n, c->K, d_labels, d_probs, c->stream);
+        if (e == hipSuccess) e = sync_stream(c, c->stream);
+        if (e != hipSuccess) { c->err = std::string(fn) + ": " + hipGetErrorString(e); rc = DPMM_EHIP; }
+    }
+    hipFree(table);
+    return rc;
 }
 
 }  // extern "C"

@@ -194,6 +194,19 @@ hipError_t launch_remap(int32_t *bins, int64_t n, const int32_t *map, hipStream_
 hipError_t launch_reset_sub(int32_t *bins, int64_t n, int64_t first_index, const int32_t *idx, int m, uint64_t seed,
                             uint32_t epoch, hipStream_t s);
 
+// ---- points in and out of caller-owned device memory (tensor_io.hip; include/dpmm_hip_tensor.h)
+// dtype: the DPMM_DT_* code; source element (point i, feature d) at src + (i * stride_point + d * stride_feature) elements, strides >= 0.
+// Writes dst [n][ldx] whole, pad columns [D, ldx) included (ldx a multiple of 4, dst 16-byte aligned).
+enum { INGEST_POINT_MAJOR = 0, INGEST_FEATURE_MAJOR = 1, INGEST_GENERAL = 2 };
+size_t ingest_elem_size(int dtype);      // 0: unknown code
+int ingest_mode(const void *src, int dtype, int64_t stride_point, int64_t stride_feature, int64_t n, int D);      // the access pattern the launcher takes
+hipError_t launch_ingest_strided(float *dst, int64_t ldx, const void *src, int dtype, int64_t stride_point, int64_t stride_feature, int64_t n, int D,
+                                 int nan_to_zero, hipStream_t s);
+// out [n][ld_out] (ld_out >= D, columns [D, ld_out) = 0) from the Float32 image X, else from the byte copy X8, else zeros
+hipError_t launch_points_readback(float *out, int64_t ld_out, const float *X, int64_t ldx, const uint8_t *X8, int64_t ld8, int64_t n, int D,
+                                  hipStream_t s);
+hipError_t launch_sparse_readback(float *out, int64_t ld_out, const int64_t *cp, const uint16_t *ri, const float *val, int64_t n, hipStream_t s);
+
 // ---- stable counting sort of the points by bin + segmented statistics (suffstats.hip)
 constexpr int SORT_TILE = 2048;  // points per sorting wave of big shards (SortBufs::tile: 2048 or SORT_TILE_SMALL)
 constexpr int SORT_TILE_SMALL = 512;

@@ -10,7 +10,9 @@ Argument meaning, defaults, coercions (Float32 data / Int64 iters, :279-293), th
 (kappa=1, m=0, nu=D+3, psi=I, :272-274) and the 9-tuple / 5-tuple results follow the reference.
 `all_data` is Dimensions x Samples (D x N) as in the reference.  Beyond the reference (whose points are a dense Matrix{Float32}), count
 data for the Multinomial prior may be given sparse: a scipy.sparse CSC matrix of shape (D, N) (or `csr.T`), or a tuple
-(colptr, rowval, nzval, (D, N)) -- host/sparse.py; the GPU then holds memory proportional to the stored entries.  Checkpoints (`save_model`), the advanced
+(colptr, rowval, nzval, (D, N)) -- host/sparse.py; the GPU then holds memory proportional to the stored entries.  A torch tensor (D, N) of
+any of eight element types and any strides is taken as it is -- host/tensors.py: one in device memory is read in place by the GPU (an (N, D)
+tensor of embeddings comes in as `emb.T`, a view) and `labels` / `sub_labels` / the results of `predict` are tensors on that device.  Checkpoints (`save_model`), the advanced
 parameter-file mode `dp_parallel(model_params::String)` and `run_model_from_checkpoint` live in host/checkpoint.py.
 Smart splits (`smart_splits=True`, Gaussian prior) are driven by DPMMSampler.smart_cluster_init; the outlier component
 (`outlier_weight`, `outlier_params`) is cluster 1 of the model with a constant weight, never split, merged or re-drawn.
@@ -27,6 +29,7 @@ from .. import binding
 from . import priors as _priors
 from . import checkpoint as _ckpt
 from . import sparse as _sparse
+from . import tensors as _tensors
 from .priors import multinomial_hyper, niw_hyperparams
 from .sampler import DPMMSampler, LocalComm
 
@@ -57,14 +60,17 @@ def _make_sampler(all_data, hyper, alpha, seed, burnout, max_clusters, comm, dev
     """`all_data`: Dimensions x Samples (basic mode), or `rows`: Samples x Dimensions as stored in a .npy file (advanced
     mode; cleaned and converted on the GPU by dpmm_upload_points_npy)."""
     csc = None if rows is not None else _sparse.as_csc(all_data)
+    desc = None if rows is not None or csc is not None else _tensors.as_device_points(all_data)
     if rows is not None:
         N, D = rows.shape
+    elif desc is not None:
+        D, N = desc.shape
     elif csc is not None:
         if hyper.kind != _priors.PRIOR_MULT:
             raise TypeError("sparse data is for the Multinomial prior (multinomial_hyper); the Gaussian prior takes a dense array")
         D, N = csc.shape
     else:
-        X = np.asarray(all_data)
+        X = np.asarray(_tensors.as_host_array(all_data))
         if X.ndim != 2:
             raise ValueError("all_data must be Dimensions x Samples")
         D, N = X.shape
@@ -81,12 +87,43 @@ def _make_sampler(all_data, hyper, alpha, seed, burnout, max_clusters, comm, dev
             wk.upload_points_npy(rows[lo:hi])
         else:
             wk.upload_points(np.nan_to_num(np.asarray(rows[lo:hi], dtype=np.float32), nan=0.0, posinf=np.inf, neginf=-np.inf))
+    elif desc is not None:
+        if hasattr(wk, "upload_points_tensor"):
+            desc.synchronize()                        # the tensor is complete before the library reads it on its own stream
+            wk.upload_points_tensor(desc, lo, hi)     # points [lo, hi) where they are: an address, no copy and no slicing on the host
+        else:                                         # (test stand-ins, third-party worker factories -- as the sparse path falls back)
+            wk.upload_points(np.ascontiguousarray(desc.tensor[:, lo:hi].T.float().cpu().numpy()))
     elif csc is not None:
         _sparse.upload_columns(wk, csc, lo, hi)       # columns [lo, hi): no rank touches another rank's entries
     else:
         wk.upload_points(np.ascontiguousarray(X[:, lo:hi].T, dtype=np.float32))  # (n_local, D): row = point
-    return DPMMSampler(wk, hyper, alpha, N, int(seed), burnout=burnout, max_clusters=max_clusters, comm=comm, nthreads=nthreads,
-                       **sampler_kw)
+    s = DPMMSampler(wk, hyper, alpha, N, int(seed), burnout=burnout, max_clusters=max_clusters, comm=comm, nthreads=nthreads,
+                    **sampler_kw)
+    s.data_tensor = desc                               # results follow the input (_final_labels)
+    return s
+
+
+def _final_labels(s, comm):
+    """(labels, sub_labels) of the whole data set.  numpy, as ever -- unless the points came from a device tensor: then int64 tensors on
+    that device, written there by the library when one rank holds all points, else gathered as ever and moved."""
+    desc = getattr(s, "data_tensor", None)
+    if desc is None:
+        return comm.gather_labels(s.wk)
+    if getattr(comm, "world", 1) == 1 and hasattr(s.wk, "get_labels_tensor"):
+        return s.wk.get_labels_tensor(desc.torch_device)
+    import torch
+    labels, sub = comm.gather_labels(s.wk)
+    return (torch.from_numpy(np.ascontiguousarray(labels, np.int64)).to(desc.torch_device),
+            torch.from_numpy(np.ascontiguousarray(sub, np.int64)).to(desc.torch_device))
+
+
+def _data_device(all_data, device):
+    """The `device` argument, or -- for a tensor in device memory -- that tensor's device (an explicit `device` must agree)."""
+    if _sparse.as_csc(all_data) is None:
+        desc = _tensors.as_device_points(all_data)
+        if desc is not None:
+            return _tensors.resolve_device(desc, device)
+    return device
 
 
 def _check_next_rows(outlier_weight, outlier_params, smart_splits, hyper=None):
@@ -124,7 +161,8 @@ def dp_parallel(all_data, local_hyper_params=None, alpha_param=None, iters=100, 
     if not isinstance(local_hyper_params, _priors.distribution_hyper_params):
         raise TypeError("local_hyper_params must be a distribution_hyper_params (niw_hyperparams / multinomial_hyper)")
     _check_next_rows(outlier_weight, outlier_params, smart_splits, local_hyper_params)
-    comm, device = _comm_device(comm, device)
+    comm, device = _comm_device(comm, _data_device(all_data, device))
+    gt = _tensors.host_int64(gt)
     s = _make_sampler(all_data, local_hyper_params, np.float32(alpha_param), seed, int(burnout), max_clusters, comm, device,
                       nthreads, worker_factory)
     s.smart_splits = bool(smart_splits)
@@ -133,7 +171,7 @@ def dp_parallel(all_data, local_hyper_params=None, alpha_param=None, iters=100, 
     s.init_first_clusters(int(init_clusters))
     hook = _ckpt.SaveHook(save_path, save_file_prefix, model_save_interval, "none", 0.0, verbose) if save_model else None
     iter_count, nmi, lik, kh = s.run_model(int(iters), 1, verbose=verbose, gt=gt, on_iteration=hook)
-    labels, sub = comm.gather_labels(s.wk)
+    labels, sub = _final_labels(s, comm)
     model = dp_parallel_sampling(s, labels, sub)
     model.checkpoints = hook.files if hook else []
     return model, iter_count, nmi, lik, kh
@@ -197,14 +235,15 @@ def resume_from_checkpoint(filename, all_data, iters, verbose=True, gt=None, bur
     """Basic-mode counterpart of run_model_from_checkpoint: the caller supplies the data array again (D x N) and the
     total number of iterations; the chain continues at iter+1 exactly where the checkpoint left it."""
     ck = _ckpt.load_checkpoint(filename)
-    comm, device = _comm_device(comm, device)
+    comm, device = _comm_device(comm, _data_device(all_data, device))
+    gt = _tensors.host_int64(gt)
     hyper = _ckpt._prior_from_dict(ck)
     s = _make_sampler(all_data, hyper, np.float32(ck["alpha"]), int(ck["seed"]), int(ck["burnout"] if burnout is None else burnout),
                       max_clusters, comm, device, nthreads, worker_factory)
     _ckpt.restore_sampler(s, ck)
     hook = _ckpt.SaveHook(save_path, save_file_prefix, model_save_interval, "none", float(ck["total_time"]), verbose) if save_model else None
     iter_count, nmi, lik, kh = s.run_model(int(iters), int(ck["iter"]) + 1, verbose=verbose, gt=gt, on_iteration=hook)
-    labels, sub = comm.gather_labels(s.wk)
+    labels, sub = _final_labels(s, comm)
     model = dp_parallel_sampling(s, labels, sub)
     model.checkpoints = hook.files if hook else []
     return model, iter_count, nmi, lik, kh
@@ -219,7 +258,7 @@ def fit(all_data, *args, iters=100, init_clusters=1, seed=None, verbose=True, sa
     if len(args) == 1:
         if _sparse.as_csc(all_data) is not None:
             raise TypeError("sparse data is for the Multinomial prior: fit(all_data, multinomial_hyper(...), alpha)")
-        D = np.asarray(all_data).shape[0]
+        D = all_data.shape[0] if _tensors.is_tensor(all_data) else np.asarray(all_data).shape[0]
         hyper = niw_hyperparams(1.0, np.zeros(D), D + 3, np.eye(D))   # dp-parallel-sampling.jl:272-274
         alpha = args[0]
     elif len(args) == 2:
@@ -238,17 +277,24 @@ def predict(dp_model, data, device=None, worker_factory=None):
     """predict(dp_model, data) -- src/dp-parallel-sampling.jl:532-537 with predict_points
     (src/local_clusters_actions.jl:23-40): weights = (points_count + alpha) / sum; per cluster the posterior predictive
     log-density (GPU), labels = row-wise argmax, probabilities = normalised exponentials (NaN -> -Inf).
-    `data` is Dimensions x Samples, an array or (Multinomial prior) sparse columns as `fit` takes them.
-    Returns (labels (n,) Int64 1-based, probs (n, K) Float32)."""
+    `data` is Dimensions x Samples, an array, a tensor or (Multinomial prior) sparse columns as `fit` takes them.
+    Returns (labels (n,) Int64 1-based, probs (n, K) Float32) -- for a tensor in device memory as tensors on its device: the library
+    writes them there, the table never crosses the host link."""
     s = dp_model.sampler
     post = s.post
     csc = _sparse.as_csc(data)
+    desc = None if csc is not None else _tensors.as_device_points(data)
+    if desc is not None and not hasattr(worker_factory or binding.Worker, "upload_points_tensor"):
+        data, desc = desc.tensor.float().cpu().numpy(), None          # (a stand-in worker without the device entry points)
     if csc is not None:
         if s.prior.kind != _priors.PRIOR_MULT:
             raise TypeError("sparse data is for the Multinomial prior")
         D, n = csc.shape
+    elif desc is not None:
+        D, n = desc.shape
+        device = _tensors.resolve_device(desc, device)
     else:
-        X = np.ascontiguousarray(np.asarray(data, dtype=np.float32).T)
+        X = np.ascontiguousarray(np.asarray(_tensors.as_host_array(data), dtype=np.float32).T)
         n, D = X.shape
     if D != s.prior.dim:
         raise ValueError("data dimension does not match the model")
@@ -259,6 +305,9 @@ def predict(dp_model, data, device=None, worker_factory=None):
     try:
         if csc is not None:
             _sparse.upload_columns(wk, csc, 0, n)
+        elif desc is not None:
+            desc.synchronize()
+            wk.upload_points_tensor(desc, 0, n)
         else:
             wk.upload_points(X)
         if getattr(wk, "supports_predict_points", False):     # argmax + normalisation on the device as well
