@@ -111,6 +111,21 @@ ABI_TENSOR = [
 ]
 DT_F16, DT_BF16, DT_F32, DT_F64, DT_U8, DT_I16, DT_I32, DT_I64 = range(8)      # DPMM_DT_* (include/dpmm_hip_tensor.h)
 
+
+class ScoreOut(ctypes.Structure):
+    """dpmm_score_out (include/dpmm_hip_score.h): host or device addresses, 0 / None = not asked for."""
+    _fields_ = [("labels", ctypes.c_void_p), ("logdens", ctypes.c_void_p), ("m", ctypes.c_int), ("top_idx", ctypes.c_void_p),
+                ("top_prob", ctypes.c_void_p), ("probs", ctypes.c_void_p)]
+
+
+# include/dpmm_hip_score.h: scoring new points (additive; bound next to ABI)
+ABI_SCORE = [
+    ("dpmm_score_points", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ScoreOut)]),
+    ("dpmm_score_points_device", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ScoreOut)]),
+]
+OPT_SCORE_TABLE_MB = 32      # DPMM_OPT_SCORE_TABLE_MB
+SCORE_MAX_TOP = 16           # DPMM_SCORE_MAX_TOP
+
 HOST_ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int)   # dpmm_host_allreduce_fn
 
 # dpmm_set_option keys (include/dpmm_hip.h)
@@ -174,7 +189,7 @@ def load_library():
         except Exception:  # pragma: no cover  (torch is optional for single-GPU use)
             pass
         lib = ctypes.CDLL(p)
-        for name, res, args in ABI + ABI_TENSOR:
+        for name, res, args in ABI + ABI_TENSOR + ABI_SCORE:
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -427,6 +442,60 @@ class Worker:
         lab = np.empty(self.n, np.int64); probs = np.empty((self.n, K), np.float32)
         self._chk(self._lib.dpmm_predict_points(self._h, _p(lab, _c_i64p), _p(probs, _c_f32p)))
         return lab, probs
+
+    # ---- scoring (include/dpmm_hip_score.h)
+    def set_predictive_niw(self, m, R, logdet, df, weights):
+        """dpmm_set_predictive_niw alone: the parameters stay in force for every later predict / score call."""
+        K = len(weights)
+        m, R, logdet, df, weights = map(_f32, (m, R, logdet, df, weights))
+        assert m.shape == (K, self.D) and R.size == K * self.D * self.D
+        self._chk(self._lib.dpmm_set_predictive_niw(self._h, K, _p(m, _c_f32p), _p(R, _c_f32p), _p(logdet, _c_f32p), _p(df, _c_f32p), _p(weights, _c_f32p)))
+
+    def set_predictive_mult(self, logp, weights):
+        K = len(weights)
+        logp, weights = _f32(logp), _f32(weights)
+        assert logp.shape == (K, self.D)
+        self._chk(self._lib.dpmm_set_predictive_mult(self._h, K, _p(logp, _c_f32p), _p(weights, _c_f32p)))
+
+    def score_points_raw(self, device, labels=0, logdens=0, m=0, top_idx=0, top_prob=0, probs=0):
+        """dpmm_score_points[_device] on plain addresses (integers; 0 = not asked for)."""
+        out = ScoreOut(labels or None, logdens or None, int(m), top_idx or None, top_prob or None, probs or None)
+        fn = self._lib.dpmm_score_points_device if device else self._lib.dpmm_score_points
+        self._chk(fn(self._h, ctypes.byref(out)))
+
+    def score_points_into(self, outs, m=0):
+        """dpmm_score_points[_device] into storage the caller made: `outs` maps `labels` / `logdens` / `top_idx` / `top_prob` / `probs` to
+        contiguous numpy arrays (host variant) or torch tensors on this worker's GPU (device variant) with n rows each."""
+        ptr, on_device = {}, None
+        for name, a in outs.items():
+            dev = hasattr(a, "data_ptr")
+            if on_device is None:
+                on_device = dev
+            assert dev == on_device, "score_points_into: numpy arrays or tensors, not both"
+            assert a.is_contiguous() if dev else a.flags.c_contiguous, name
+            ptr[name] = (a.data_ptr() if a.numel() else 0) if dev else (a.ctypes.data if a.size else 0)
+        if on_device:
+            import torch
+            torch.cuda.current_stream(next(iter(outs.values())).device).synchronize()
+        self.score_points_raw(bool(on_device), m=int(m), **ptr)
+
+    def score_points(self, labels=False, logdens=False, m=0, top_idx=None, top_prob=None, probs=False, device=None):
+        """The outputs asked for, of the ctx's n points: a dict with `labels` (n,) int64, `logdens` (n,) float32, `top_idx` (n, m) int64,
+        `top_prob` (n, m) float32, `probs` (n, K) float32.  m > 0 asks for both top_* unless one is switched off with False.
+        device: a torch device -- the results are tensors there, written by the library; None: numpy arrays."""
+        n, K, m = self.n, self.K, int(m)
+        spec = [("labels", labels, (n,), "int64"), ("logdens", logdens, (n,), "float32"), ("top_idx", m > 0 and top_idx is not False, (n, m), "int64"),
+                ("top_prob", m > 0 and top_prob is not False, (n, m), "float32"), ("probs", probs, (n, K), "float32")]
+        if device is not None:
+            import torch
+            res = {name: torch.empty(shape, dtype=getattr(torch, dt), device=device) for name, want, shape, dt in spec if want}
+        else:
+            res = {name: np.empty(shape, dt) for name, want, shape, dt in spec if want}
+        if not res:
+            raise ValueError("score_points: no output asked for")
+        if n > 0:
+            self.score_points_into(res, m=m)
+        return res
 
     def predict_table_mult(self, logp, weights, points=False):
         K = len(weights)

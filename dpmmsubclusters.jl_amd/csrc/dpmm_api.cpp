@@ -7,6 +7,7 @@
 #include "../../include/dpmm_hip_master.h"
 #include "../../include/dpmm_hip_debug.h"
 #include "../../include/dpmm_hip_tensor.h"
+#include "../../include/dpmm_hip_score.h"
 
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -129,6 +130,10 @@ struct dpmm_ctx {
     bool have_screen_prep = false, have_tail = false;
     float *d_tdf = nullptr;   // Student-t constants of the predictive mode ([3K][2]) or null
     bool predictive = false;
+    // scoring (include/dpmm_hip_score.h): one slab of the table and, for the host variant, the slab's outputs; allocated on first use, grown on demand
+    float *d_score_table = nullptr; size_t score_table_bytes = 0;
+    char *d_score_out = nullptr; size_t score_out_bytes = 0;
+    double opt_score_mb = 128.0;       // DPMM_OPT_SCORE_TABLE_MB
 
     // sort + stats
     SortBufs sb{};
@@ -696,6 +701,7 @@ int dpmm_destroy(dpmm_ctx *c) {
     hipFree(c->sb.tile_hist); hipFree(c->sb.tile_cnt); hipFree(c->sb.tile_spec); hipFree(c->sb.spec_bins); hipFree(c->sb.fast_total); hipFree(c->sb.ticket); hipFree(c->sb.prev_lab); hipFree(c->sb.cdirty); hipFree(c->sb.cmode); hipFree(c->sb.bin_total); hipFree(c->sb.bin_start); hipFree(c->sb.item_start);
     hipFree(c->sb.perm); hipFree(c->sb.bin_sel); hipFree(c->sb.perm_total); hipFree(c->d_small); hipFree(c->d_proj); hipFree(c->d_vals); hipFree(c->d_smart);
     hipFree(c->d_m0); hipFree(c->d_psi_lo); hipFree(c->d_pairs);
+    hipFree(c->d_score_table); hipFree(c->d_score_out);
     for (int i = 0; i < 2; ++i) { hipFree(c->d_Y[i]); hipFree(c->d_ld_sigma[i]); hipFree(c->d_mu_draw[i]); }
     hipFree(c->ma.fac); hipFree(c->ma.mean); hipFree(c->ma.kap); hipFree(c->ma.nu); hipFree(c->ma.rows_store);
     if (c->stream2) { hipStreamSynchronize(c->stream2); hipStreamDestroy(c->stream2); }
@@ -1314,10 +1320,20 @@ int dpmm_numa_node(dpmm_ctx *c) {
 }
 
 static int noise_flush(dpmm_ctx *c);
-static int run_sweep(dpmm_ctx *c, uint32_t epoch, int final_argmax, float *table, int64_t table_stride) {
+// Table mode takes a range of the points, [p0, p0 + np) with p0 a multiple of the tile (np < 0: all of them, the launch every caller but the
+// scoring entry points makes): the kernels see shifted base pointers, n = np and the range's tiles, and write table column 0 for point p0.
+// Table mode draws nothing and visits in storage order; the sparse columns' offsets are absolute, so shifting cp is enough.  What stays
+// unshifted is not per point or not read: mdist, tail and the parameter images are per cluster; bins (the previous labels: a prefetch /
+// row-block hint outside table mode) is switched off for a range with use_prev = 0; the table kernels write no label.
+static int run_sweep(dpmm_ctx *c, uint32_t epoch, int final_argmax, float *table, int64_t table_stride, int64_t p0 = 0, int64_t np = -1) {
     if (!c->have_points || !c->have_params) return fail(c, DPMM_ESTATE, "sweep needs points and parameters");
     HIPCHK(c, hipSetDevice(c->device));
     if (c->n == 0) return DPMM_OK;
+    const bool ranged = np >= 0;
+    if (ranged && (!table || p0 < 0 || p0 % c->tile != 0 || np == 0 || p0 + np > c->n)) return fail(c, DPMM_EINVAL, "run_sweep: bad point range");
+    const int64_t rn = ranged ? np : c->n;
+    const int64_t rtiles = ranged ? (np + c->tile - 1) / c->tile : c->ntiles;
+    const int rgrid = ranged ? (int)std::min<int64_t>(c->sweep_grid, rtiles) : c->sweep_grid;
     if (c->prior == DPMM_PRIOR_NIW && !table) {
         if (!c->work_zeroed) HIPCHK(c, hipMemsetAsync(c->d_work, 0, sizeof(unsigned long long) * DPMM_WORK_SLOTS, c->stream));   // usually done by the pack kernel
         c->work_zeroed = false;
@@ -1325,7 +1341,7 @@ static int run_sweep(dpmm_ctx *c, uint32_t epoch, int final_argmax, float *table
     if (!table && (c->opt_timing & 1)) HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
     if (c->prior == DPMM_PRIOR_NIW) {
         NiwSweepArgs a{};
-        a.X = c->dX; a.ldx = c->ldx; a.n = c->n; a.first_index = c->first; a.ntiles = c->ntiles; a.K = c->K;
+        a.X = (ranged && c->dX) ? c->dX + p0 * c->ldx : c->dX; a.ldx = c->ldx; a.n = rn; a.first_index = c->first + p0; a.ntiles = rtiles; a.K = c->K;
         a.Rp = c->d_Rp; a.mup = c->d_mup; a.cst = c->d_cst;
         a.tdf = c->predictive ? c->d_tdf : nullptr;
         a.scratch = table ? table : c->d_scratch;
@@ -1336,7 +1352,7 @@ static int run_sweep(dpmm_ctx *c, uint32_t epoch, int final_argmax, float *table
         {
             const bool no_order = !c->opt_ordered;
             a.screen_margin = table ? 0.f : c->opt_margin;
-            a.use_prev = c->have_labels ? 1 : 0;
+            a.use_prev = (c->have_labels && !ranged) ? 1 : 0;      // (a range: bins stays unshifted and must not be read, not even as a prefetch hint)
             a.lam = (c->have_screen_prep && !c->predictive) ? c->d_lam : nullptr;
             a.mdist = c->d_mdist;
             a.tail = (c->have_tail && !c->predictive) ? c->d_tail : nullptr;
@@ -1419,27 +1435,27 @@ static int run_sweep(dpmm_ctx *c, uint32_t epoch, int final_argmax, float *table
             a.tdf = nullptr;
             if (!list) HIPCHK(c, launch_niw_sub(a, nullptr, nullptr, c->sweep_grid, c->stream));      // (every tile; a list's spans were finished by the LIST launch)
         } else {
-            HIPCHK(c, launch_niw_sweep(c->NB, a, c->sweep_grid, c->stream));
+            HIPCHK(c, launch_niw_sweep(c->NB, a, rgrid, c->stream));
             if (!table) c->have_parts = 0;          // (a one-launch sweep records no part events: dpmm_last_sweep_parts_ms must not mix its ev[0] / ev[1] with an older sweep's)
         }
     } else {
         MultSweepArgs a{};
-        a.X = c->dX; a.ldx = c->ldx; a.n = c->n; a.first_index = c->first; a.D = c->D; a.K = c->K;
+        a.X = (ranged && c->dX) ? c->dX + p0 * c->ldx : c->dX; a.ldx = c->ldx; a.n = rn; a.first_index = c->first + p0; a.D = c->D; a.K = c->K;
         a.logp = c->d_Rp; a.cst = c->d_cst;
         a.scratch = table ? table : c->d_scratch;
         a.scratch_stride = table ? table_stride : c->scratch_stride;
         a.scratch_by_tile = table ? 1 : 0;
         a.labels_only = table ? 1 : 0;
         a.bins = c->dbins; a.seed = c->seed; a.epoch = epoch; a.final_argmax = final_argmax;
-        a.use_prev = c->have_labels ? 1 : 0;
+        a.use_prev = (c->have_labels && !ranged) ? 1 : 0;
         a.order = (!table && c->have_perm && c->opt_ordered) ? c->sb.perm : nullptr;
         a.order_total = c->sb.perm_total;
-        if (c->x_sparse) HIPCHK(c, launch_mult_sweep_sparse(a, sparse_args(c), c->sweep_grid, c->stream));
-        else if (c->x_u8) HIPCHK(c, launch_mult_sweep_u8(a, c->dX8, c->ld8, c->d_Lp16, c->sweep_grid, c->stream));
-        else if (c->x_bf16_exact) HIPCHK(c, launch_mult_sweep_bf16(a, c->d_Lp16, c->sweep_grid, c->stream));
+        if (c->x_sparse) { MultSparse sp = sparse_args(c); sp.cp += p0; HIPCHK(c, launch_mult_sweep_sparse(a, sp, rgrid, c->stream)); }
+        else if (c->x_u8) HIPCHK(c, launch_mult_sweep_u8(a, c->dX8 + p0 * c->ld8, c->ld8, c->d_Lp16, rgrid, c->stream));
+        else if (c->x_bf16_exact) HIPCHK(c, launch_mult_sweep_bf16(a, c->d_Lp16, rgrid, c->stream));
         else {
             if (!c->rp_current) { HIPCHK(c, launch_mult_pack(c->d_raw, c->d_Rp, 3 * c->K, c->ldx, c->stream)); c->rp_current = true; }      // (skipped by a device-master draw)
-            HIPCHK(c, launch_mult_sweep(a, c->sweep_grid, c->stream));
+            HIPCHK(c, launch_mult_sweep(a, rgrid, c->stream));
         }
     }
     if (!table) {
@@ -2916,6 +2932,7 @@ int dpmm_set_option(dpmm_ctx *c, int option, double value) {
         case DPMM_OPT_MULT_NO_U8:
             if (c->have_points) return fail(c, DPMM_ESTATE, "DPMM_OPT_MULT_NO_U8 must be set before the points are uploaded");
             c->opt_no_u8 = value != 0; return DPMM_OK;
+        case DPMM_OPT_SCORE_TABLE_MB: c->opt_score_mb = (value < 0 || value != value) ? 128.0 : value; return DPMM_OK;
         default: return fail(c, DPMM_EINVAL, "unknown option");
     }
 }
@@ -3387,6 +3404,100 @@ int dpmm_predict_points_device(dpmm_ctx *c, int64_t *d_labels, float *d_probs) {
     hipFree(table);
     return rc;
 }
+
+// ---- include/dpmm_hip_score.h: log-density, top-m, labels and probabilities, slab by slab ----------------------------------------------
+static int ensure_score_buffer(dpmm_ctx *c, void **buf, size_t *have, size_t need, const char *what) {
+    if (need <= *have) return DPMM_OK;
+    HIPCHK(c, sync_stream(c, c->stream));
+    hipFree(*buf); *buf = nullptr; *have = 0;
+    if (hipMalloc(buf, need) != hipSuccess) {
+        (void)hipGetLastError();
+        *buf = nullptr;
+        return fail(c, DPMM_EHIP, std::string("dpmm_score_points: out of device memory for the ") + what + " (" + std::to_string((unsigned long long)need) + " bytes)");
+    }
+    *have = need;
+    return DPMM_OK;
+}
+
+static int score_points(dpmm_ctx *c, const dpmm_score_out *o, bool device, const char *fn) {
+    if (!c) return tensor_no_ctx(fn);
+    const std::string who = std::string(fn) + ": ";
+    if (!o) return fail(c, DPMM_EINVAL, who + "out is null");
+    if (o->m < 0 || o->m > DPMM_SCORE_MAX_TOP) return fail(c, DPMM_EINVAL, who + "m must be in 0.." + std::to_string(DPMM_SCORE_MAX_TOP));
+    if (o->m == 0 && (o->top_idx || o->top_prob)) return fail(c, DPMM_EINVAL, who + "top_idx / top_prob given with m = 0");
+    if (o->m > 0 && !o->top_idx && !o->top_prob) return fail(c, DPMM_EINVAL, who + "m > 0 needs top_idx or top_prob");
+    if (!o->labels && !o->logdens && !o->top_idx && !o->top_prob && !o->probs) return fail(c, DPMM_EINVAL, who + "every output pointer is null");
+    if (!c->predictive) return fail(c, DPMM_ESTATE, who + "needs dpmm_set_predictive_* first");
+    if (o->m > c->K) return fail(c, DPMM_EINVAL, who + "m exceeds the number of clusters");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (c->n == 0) return DPMM_OK;
+    if (!c->have_points || !c->have_params) return fail(c, DPMM_ESTATE, who + "needs points and parameters");
+    const uint64_t n = (uint64_t)c->n, K = (uint64_t)c->K, m = (uint64_t)o->m;
+    if (device) {
+        if (o->labels) if (int rc = check_device_extent(c, fn, "labels", o->labels, sizeof(int64_t) * n, sizeof(int64_t))) return rc;
+        if (o->logdens) if (int rc = check_device_extent(c, fn, "logdens", o->logdens, sizeof(float) * n, sizeof(float))) return rc;
+        if (o->top_idx) if (int rc = check_device_extent(c, fn, "top_idx", o->top_idx, sizeof(int64_t) * n * m, sizeof(int64_t))) return rc;
+        if (o->top_prob) if (int rc = check_device_extent(c, fn, "top_prob", o->top_prob, sizeof(float) * n * m, sizeof(float))) return rc;
+        if (o->probs) if (int rc = check_device_extent(c, fn, "probs", o->probs, sizeof(float) * n * K, sizeof(float))) return rc;
+    }
+    // slabs of whole tiles: as many as the budget holds, one at least
+    const int rstep = (c->prior == DPMM_PRIOR_NIW) ? 1 : 3;       // Multinomial: rows 3k are the cluster-level rows
+    const size_t rows = (size_t)rstep * (size_t)c->K;
+    const double tile_bytes = (double)rows * (double)c->tile * sizeof(float);
+    int64_t slab_tiles = (int64_t)std::min<double>(std::floor(c->opt_score_mb * 1048576.0 / tile_bytes), (double)c->ntiles);
+    if (slab_tiles < 1) slab_tiles = 1;
+    const int64_t P = slab_tiles * c->tile;                        // points of a slab = floats between two rows of the table
+    if (int rc = ensure_score_buffer(c, reinterpret_cast<void **>(&c->d_score_table), &c->score_table_bytes, sizeof(float) * rows * (size_t)P, "table")) return rc;
+    // host variant: the slab's outputs on the device, one block per output (each 8-byte aligned)
+    size_t off_lab = 0, off_ld = 0, off_ti = 0, off_tp = 0, off_pr = 0, total = 0;
+    if (!device) {
+        auto take = [&](bool want, size_t bytes_per_point) { const size_t at = total; if (want) total += ((size_t)P * bytes_per_point + 7) & ~(size_t)7; return at; };
+        off_lab = take(o->labels != nullptr, sizeof(int64_t));
+        off_ld = take(o->logdens != nullptr, sizeof(float));
+        off_ti = take(o->top_idx != nullptr, sizeof(int64_t) * m);
+        off_tp = take(o->top_prob != nullptr, sizeof(float) * m);
+        off_pr = take(o->probs != nullptr, sizeof(float) * K);
+        if (int rc = ensure_score_buffer(c, reinterpret_cast<void **>(&c->d_score_out), &c->score_out_bytes, total, "staging of the outputs")) return rc;
+    }
+    for (int64_t p0 = 0; p0 < c->n; p0 += P) {
+        const int64_t np = std::min<int64_t>(P, c->n - p0);
+        if (int rc = run_sweep(c, 0, 0, c->d_score_table, P, p0, np)) return rc;
+        ScoreArgs a{};
+        a.table = c->d_score_table; a.stride = P; a.rstep = rstep; a.n = np; a.K = c->K; a.m = o->m;
+        if (device) {
+            a.labels = o->labels ? o->labels + p0 : nullptr;
+            a.logdens = o->logdens ? o->logdens + p0 : nullptr;
+            a.top_idx = o->top_idx ? o->top_idx + p0 * o->m : nullptr;
+            a.top_prob = o->top_prob ? o->top_prob + p0 * o->m : nullptr;
+            a.probs = o->probs ? o->probs + p0 * (int64_t)c->K : nullptr;
+        } else {
+            a.labels = o->labels ? reinterpret_cast<int64_t *>(c->d_score_out + off_lab) : nullptr;
+            a.logdens = o->logdens ? reinterpret_cast<float *>(c->d_score_out + off_ld) : nullptr;
+            a.top_idx = o->top_idx ? reinterpret_cast<int64_t *>(c->d_score_out + off_ti) : nullptr;
+            a.top_prob = o->top_prob ? reinterpret_cast<float *>(c->d_score_out + off_tp) : nullptr;
+            a.probs = o->probs ? reinterpret_cast<float *>(c->d_score_out + off_pr) : nullptr;
+        }
+        hipError_t e = launch_score_finish(a, c->stream);
+        if (e == hipSuccess && !device) {
+            const size_t q = (size_t)np;
+            if (o->labels) e = hipMemcpyAsync(o->labels + p0, a.labels, sizeof(int64_t) * q, hipMemcpyDeviceToHost, c->stream);
+            if (e == hipSuccess && o->logdens) e = hipMemcpyAsync(o->logdens + p0, a.logdens, sizeof(float) * q, hipMemcpyDeviceToHost, c->stream);
+            if (e == hipSuccess && o->top_idx) e = hipMemcpyAsync(o->top_idx + p0 * o->m, a.top_idx, sizeof(int64_t) * q * m, hipMemcpyDeviceToHost, c->stream);
+            if (e == hipSuccess && o->top_prob) e = hipMemcpyAsync(o->top_prob + p0 * o->m, a.top_prob, sizeof(float) * q * m, hipMemcpyDeviceToHost, c->stream);
+            if (e == hipSuccess && o->probs) e = hipMemcpyAsync(o->probs + p0 * (int64_t)c->K, a.probs, sizeof(float) * q * K, hipMemcpyDeviceToHost, c->stream);
+            if (e == hipSuccess) e = sync_stream(c, c->stream);      // the staging block is rewritten by the next slab
+        }
+        if (e != hipSuccess) { c->err = who + hipGetErrorString(e); return DPMM_EHIP; }
+    }
+    if (device) {
+        hipError_t e = sync_stream(c, c->stream);
+        if (e != hipSuccess) { c->err = who + hipGetErrorString(e); return DPMM_EHIP; }
+    }
+    return DPMM_OK;
+}
+
+int dpmm_score_points(dpmm_ctx *c, const dpmm_score_out *out) { return score_points(c, out, false, "dpmm_score_points"); }
+int dpmm_score_points_device(dpmm_ctx *c, const dpmm_score_out *out) { return score_points(c, out, true, "dpmm_score_points_device"); }
 
 }  // extern "C"
 #pragma GCC visibility pop

@@ -171,6 +171,22 @@ hipError_t launch_smart_kmeans(const int32_t *bins, const double *proj, int64_t 
 hipError_t launch_smart_assign(int32_t *bins, const double *proj, int64_t n, int k, double m_lo, double m_hi, hipStream_t s);
 int smart_groups();
 hipError_t launch_predict_finish(const float *table, int64_t stride, int rstep, int64_t n, int K, int64_t *labels, float *probs, hipStream_t s);
+// ---- scoring (score.hip; include/dpmm_hip_score.h): the fused finish over one slab of the table, n points from table column 0; every
+// output pointer is that of the slab's first point and may be null (top_idx / top_prob: [n][m], m <= 16; probs: [n][K])
+struct ScoreArgs {
+    const float *table;
+    int64_t stride;      // floats between two rows of the table
+    int rstep;           // cluster k is row k * rstep
+    int64_t n;
+    int K;
+    int64_t *labels;
+    float *logdens;
+    int m;
+    int64_t *top_idx;
+    float *top_prob;
+    float *probs;
+};
+hipError_t launch_score_finish(const ScoreArgs &a, hipStream_t s);
 hipError_t launch_ingest_rows(float *dst, int64_t ldx, const void *src, int is_f64, int64_t ld, int64_t rows, int D, int nan_to_zero,
                               hipStream_t s);
 hipError_t launch_copy_bytes(void *dst, const void *src, size_t bytes, hipStream_t s);

@@ -1,0 +1,252 @@
+"""Scoring new points with a fitted model, at any n: a reusable `Predictor` over include/dpmm_hip_score.h.
+
+`predict(dp_model, data)` creates a worker, loads the K posterior predictives, allocates an n-sized table and frees everything -- per
+call.  A `Predictor` does the fixed part ONCE (one worker of `capacity` points, the predictive parameters loaded once) and then scores
+data of any n in slabs of `capacity` points: labels, probabilities, the best m clusters, and the mixture's log-density (the outlier score).
+
+  * `data` is what `predict` takes: an array, a torch tensor on the CPU or a GPU (eight element types, any strides), sparse columns for
+    the Multinomial prior; Dimensions x Samples.
+  * a full slab of a device tensor is read in place (its address is the tensor's plus lo * stride_point); the last, short slab goes
+    through a staging buffer of `capacity` points that the Predictor keeps, and its outputs are cut to length: the worker always sees
+    `capacity` points.
+  * results for a device tensor are tensors on its device, written there by the library; otherwise numpy arrays.
+  * a Predictor belongs to one GPU; for several GPUs open one each.
+
+The values are those of `predict` (same kernels, same arithmetic per point).  Two caveats, both for dense Multinomial data: the worker
+picks its storage path (Float32 / bf16-exact / bytes) per upload, here per slab, `predict` for the whole data.  For data of one kind
+throughout (all counts, all bf16-exact, all other fractions) the two agree bit for bit whatever the capacity; for mixed data the last
+bits can depend on `capacity`.  And on the byte path every upload re-allocates the worker's Float32 image (it is freed once the byte copy
+exists): the scoring calls allocate nothing, the uploads of count data do.
+"""
+import numpy as np
+
+from .. import binding
+from . import priors as _priors
+from . import sparse as _sparse
+from . import tensors as _tensors
+
+
+class _Capture:
+    """Receives what prior.predictive_table would hand a worker."""
+
+    def predict_table_niw(self, m, R, logdet, df, weights, points=False):
+        self.args = ("niw", (m, R, logdet, df, weights))
+
+    def predict_table_mult(self, logp, weights, points=False):
+        self.args = ("mult", (logp, weights))
+
+
+def _device_index(device):
+    if device is None or isinstance(device, (int, np.integer)):
+        return device
+    if isinstance(device, str):
+        import torch
+        device = torch.device(device)
+    return device.index
+
+
+class Predictor:
+    """Predictor(dp_model, capacity=65536, device=None, worker_factory=None): see the module's description.  Use as a context manager or close()."""
+
+    def __init__(self, dp_model, capacity=65536, device=None, worker_factory=None):
+        s = dp_model.sampler
+        rows = [3 * k for k in range(s.K)]
+        post = {k: np.asarray(v)[rows] for k, v in s.post.items()}
+        if device is None:
+            device = getattr(getattr(s, "wk", None), "device", 0)
+        self._setup(s.prior.kind, s.prior.dim, s.alpha, np.asarray(s.points_count), post, capacity, device, worker_factory)
+
+    def _setup(self, kind, D, alpha, points_count, post, capacity, device, worker_factory):
+        self.kind, self.D, self.alpha = int(kind), int(D), float(alpha)
+        self.points_count = np.asarray(points_count, np.float64).copy()
+        self.post = {k: np.array(v) for k, v in post.items()}
+        self.K = len(self.points_count)
+        self.capacity = int(capacity)
+        if self.capacity < 1:
+            raise ValueError("capacity must be at least 1")
+        self._device_arg = device
+        idx = _device_index(device)
+        self.device = 0 if idx is None else int(idx)
+        w = self.points_count + self.alpha                                   # weights as predict forms them
+        self.weights = (w / w.sum()).astype(np.float32)
+        prior = (_priors.niw_hyperparams(1.0, np.zeros(self.D), self.D + 3.0, np.eye(self.D)) if self.kind == _priors.PRIOR_NIW
+                 else _priors.multinomial_hyper(np.ones(self.D)))
+        cap = _Capture()
+        prior.predictive_table(cap, self.post, list(range(self.K)), self.weights)
+        factory = worker_factory or binding.Worker
+        self._wk = factory(self.kind, self.D, self.capacity, first_index=0, device=self.device, seed=0)
+        try:
+            which, args = cap.args
+            (self._wk.set_predictive_niw if which == "niw" else self._wk.set_predictive_mult)(*args)      # ONCE
+        except Exception:
+            self._wk.close()
+            self._wk = None
+            raise
+        self._host_stage = None          # (capacity, D) float32, the short slab of host data
+        self._dev_stage = None           # the same on the device, for the short slab of a device tensor
+        self._out_stage = {}             # outputs of a short slab: name -> array / tensor of `capacity` rows
+
+    # ---- life
+    def close(self):
+        if getattr(self, "_wk", None) is not None:
+            self._wk.close()
+            self._wk = None
+        self._host_stage = self._dev_stage = None
+        self._out_stage = {}
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # ---- a model to serve, without the training data or the sampler
+    def save(self, path):
+        """One .npz: prior kind, D, alpha, points_count and the posterior arrays of the K clusters."""
+        np.savez(path, kind=np.int64(self.kind), D=np.int64(self.D), alpha=np.float64(self.alpha), points_count=self.points_count,
+                 **{"post_" + k: v for k, v in self.post.items()})
+
+    @classmethod
+    def load(cls, path, device=None, capacity=65536, worker_factory=None):
+        with np.load(path) as z:
+            post = {k[5:]: z[k] for k in z.files if k.startswith("post_")}
+            self = cls.__new__(cls)
+            self._setup(int(z["kind"]), int(z["D"]), float(z["alpha"]), z["points_count"], post, capacity, 0 if device is None else device, worker_factory)
+        return self
+
+    # ---- the public methods
+    def predict(self, data):
+        """(labels (n,) int64 1-based, probs (n, K) float32): what `predict(dp_model, data)` returns."""
+        r = self._run(data, labels=True, probs=True)
+        return r["labels"], r["probs"]
+
+    def predict_labels(self, data):
+        return self._run(data, labels=True)["labels"]
+
+    def predict_topk(self, data, m):
+        """(labels, idx (n, m) int64 1-based, best first, probs (n, m)): the m most probable clusters of every point, 1 <= m <= min(K, 16)."""
+        m = int(m)
+        if not 1 <= m <= min(self.K, binding.SCORE_MAX_TOP):
+            raise ValueError(f"m must be in 1..{min(self.K, binding.SCORE_MAX_TOP)}")
+        r = self._run(data, labels=True, m=m)
+        return r["labels"], r["top_idx"], r["top_prob"]
+
+    def score_samples(self, data):
+        """(n,) float32: log of the mixture's posterior predictive density at every point."""
+        return self._run(data, logdens=True)["logdens"]
+
+    # ---- slabs
+    def _spec(self, labels, logdens, m, probs):
+        spec = []
+        if labels:
+            spec.append(("labels", (), "int64"))
+        if logdens:
+            spec.append(("logdens", (), "float32"))
+        if m:
+            spec += [("top_idx", (m,), "int64"), ("top_prob", (m,), "float32")]
+        if probs:
+            spec.append(("probs", (self.K,), "float32"))
+        return spec
+
+    def _run(self, data, labels=False, logdens=False, m=0, probs=False):
+        if self._wk is None:
+            raise RuntimeError("this Predictor is closed")
+        wk, cap = self._wk, self.capacity
+        csc = _sparse.as_csc(data)
+        desc = None if csc is not None else _tensors.as_device_points(data)
+        if desc is not None:
+            if _tensors.resolve_device(desc, self._device_arg) != self.device:
+                raise ValueError(f"the data tensor lives on {desc.torch_device}, this Predictor on device {self.device}: open one Predictor per GPU")
+            if not hasattr(wk, "upload_points_strided_device"):
+                data, desc = desc.tensor.float().cpu().numpy(), None      # (a stand-in worker without the device entry points)
+        if csc is not None:
+            if self.kind != _priors.PRIOR_MULT:
+                raise TypeError("sparse data is for the Multinomial prior")
+            D, n = csc.shape
+        elif desc is not None:
+            D, n = desc.shape
+        else:
+            X = np.asarray(_tensors.as_host_array(data))
+            if X.ndim != 2:
+                raise ValueError("data must be 2-D, Dimensions x Samples")
+            D, n = X.shape
+        if D != self.D:
+            raise ValueError("data dimension does not match the model")
+        spec = self._spec(labels, logdens, m, probs)
+        if desc is not None:
+            import torch
+            dev = desc.torch_device
+            new = lambda rows, tail, dt: torch.empty((rows,) + tail, dtype=getattr(torch, dt), device=dev)      # noqa: E731
+            desc.synchronize()
+        else:
+            dev = None
+            new = lambda rows, tail, dt: np.empty((rows,) + tail, dt)      # noqa: E731
+        out = {name: new(n, tail, dt) for name, tail, dt in spec}
+        for lo in range(0, n, cap):
+            hi = min(n, lo + cap)
+            full = hi - lo == cap
+            # -- the slab's points
+            if csc is not None:
+                cp, rv, nz = csc.columns(lo, hi, check=not hasattr(wk, "upload_points_csc"))
+                if not full:                                              # empty columns behind the last point
+                    cp = np.concatenate([cp, np.full(cap - (hi - lo), cp[-1], np.int64)])
+                if hasattr(wk, "upload_points_csc"):
+                    wk.upload_points_csc(cp, rv, nz, index_base=0)
+                else:
+                    Xs = np.zeros((cap, D), np.float32)
+                    Xs[np.repeat(np.arange(cap), np.diff(cp)), rv] = nz
+                    wk.upload_points(Xs)
+            elif desc is not None:
+                if full:
+                    wk.upload_points_strided_device(desc.shard_ptr(lo), desc.dtype, desc.stride_point, desc.stride_feature, False)
+                else:
+                    st = self._dev_stage
+                    if st is None or st.device != dev:
+                        st = self._dev_stage = torch.zeros((cap, D), dtype=torch.float32, device=dev)
+                    st[:hi - lo].copy_(desc.tensor[:, lo:hi].T)           # (rounds to Float32 to nearest even, as the library's own read does)
+                    st[hi - lo:].zero_()
+                    torch.cuda.current_stream(dev).synchronize()
+                    wk.upload_points_strided_device(st.data_ptr(), _tensors.DT_F32, D, 1, False)
+            else:
+                if full:
+                    wk.upload_points(np.ascontiguousarray(X[:, lo:hi].T, dtype=np.float32))
+                else:
+                    if self._host_stage is None:
+                        self._host_stage = np.zeros((cap, D), np.float32)
+                    self._host_stage[:hi - lo] = X[:, lo:hi].T
+                    self._host_stage[hi - lo:] = 0
+                    wk.upload_points(self._host_stage)
+            # -- its outputs: straight into the result for a full slab, through the staging outputs for the short one
+            if full:
+                views = {name: out[name][lo:hi] for name, _, _ in spec}
+            else:
+                key = "dev" if dev is not None else "host"
+                views = {}
+                for name, tail, dt in spec:
+                    b = self._out_stage.get((key, name))
+                    if b is None or tuple(b.shape[1:]) != tail or (dev is not None and b.device != dev):
+                        b = self._out_stage[(key, name)] = new(cap, tail, dt)
+                    views[name] = b
+            wk.score_points_into(views, m=m)
+            if not full:
+                for name, _, _ in spec:
+                    out[name][lo:hi] = views[name][:hi - lo]
+        return out
+
+
+def score_samples(dp_model, data, **kw):
+    """Log-density of every point under the fitted mixture (opens a Predictor, runs, closes); kw: capacity, device, worker_factory."""
+    with Predictor(dp_model, **kw) as p:
+        return p.score_samples(data)
+
+
+def predict_topk(dp_model, data, m, **kw):
+    """(labels, idx (n, m), probs (n, m)) of the m most probable clusters (opens a Predictor, runs, closes)."""
+    with Predictor(dp_model, **kw) as p:
+        return p.predict_topk(data, m)
