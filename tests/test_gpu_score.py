@@ -4,7 +4,8 @@ The reference of every case is the context's OWN dpmm_predict table and dpmm_pre
 numpy: labels, probabilities and the top-m are compared bit for bit; the log-density against the Float64 log-sum-exp of the Float32
 table within 2^-23 (K + 16) + 2^-23 |ref| -- K terms of at most 1 from a few-ulp expf, K - 1 Float32 additions, one logf, one final
 addition; about a factor of two of margin.  Shapes: 3 tiles + 5 points of the path's tile, the smallest that has whole tiles, a ragged
-end and more than one slab at the small budgets."""
+end and more than one slab at the small budgets.
+The NIW table these cases bootstrap from has its independent anchor in tests/test_gpu_predictive.py (a Float64 closed form, a derived bound)."""
 import ctypes
 import importlib
 import os
