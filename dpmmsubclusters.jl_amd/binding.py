@@ -123,6 +123,11 @@ ABI_SCORE = [
     ("dpmm_score_points", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ScoreOut)]),
     ("dpmm_score_points_device", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ScoreOut)]),
 ]
+# include/dpmm_hip_csc.h: sparse points out of caller-owned device memory (additive; bound next to ABI)
+ABI_CSC = [
+    ("dpmm_upload_points_csc_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                                     ctypes.c_int64, ctypes.c_int]),
+]
 OPT_SCORE_TABLE_MB = 32      # DPMM_OPT_SCORE_TABLE_MB
 SCORE_MAX_TOP = 16           # DPMM_SCORE_MAX_TOP
 
@@ -189,7 +194,7 @@ def load_library():
         except Exception:  # pragma: no cover  (torch is optional for single-GPU use)
             pass
         lib = ctypes.CDLL(p)
-        for name, res, args in ABI + ABI_TENSOR + ABI_SCORE:
+        for name, res, args in ABI + ABI_TENSOR + ABI_SCORE + ABI_CSC:
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -311,6 +316,20 @@ class Worker:
         assert hi - lo == self.n and desc.D == self.D
         self.results_device = desc.torch_device            # labels and predictions follow the input (get_labels_tensor, _predict_points)
         self.upload_points_strided_device(desc.shard_ptr(lo), desc.dtype, desc.stride_point, desc.stride_feature, False)
+
+    # ---- sparse points in caller-owned device memory (include/dpmm_hip_csc.h)
+    def upload_points_csc_device(self, colptr_ptr, index_dtype, rowval_ptr, nzval_ptr, value_dtype, nnz_extent, index_base=0):
+        """The shard as compressed sparse columns in device memory: colptr_ptr addresses the shard's first of n + 1 offsets (DT_I32 or
+        DT_I64, as rowval), ABSOLUTE into rowval / nzval (`nnz_extent` entries of the DT_* type `value_dtype` behind nzval_ptr)."""
+        self._chk(self._lib.dpmm_upload_points_csc_device(self._h, ctypes.c_void_p(colptr_ptr or None), int(index_dtype), ctypes.c_void_p(rowval_ptr or None),
+                                                          ctypes.c_void_p(nzval_ptr or None), int(value_dtype), int(nnz_extent), int(index_base)))
+
+    def upload_points_csc_tensor(self, desc, lo, hi):
+        """The columns [lo, hi) of a sparse_csc tensor in device memory described by host/sparse.py (DeviceCSC): its offsets from `lo` on,
+        the same two entry arrays -- no copy and no slicing on the host."""
+        assert hi - lo == self.n and desc.D == self.D
+        self.results_device = desc.torch_device            # labels and predictions follow the input, as for a dense tensor
+        self.upload_points_csc_device(desc.colptr_ptr(lo), desc.index_dtype, desc.rowval_ptr, desc.nzval_ptr, desc.value_dtype, desc.nnz_extent, 0)
 
     def get_points_device(self, ptr, ld_out):
         self._chk(self._lib.dpmm_get_points_device(self._h, ctypes.c_void_p(ptr), int(ld_out)))

@@ -7,6 +7,7 @@
 #include "../../include/dpmm_hip_master.h"
 #include "../../include/dpmm_hip_debug.h"
 #include "../../include/dpmm_hip_tensor.h"
+#include "../../include/dpmm_hip_csc.h"
 #include "../../include/dpmm_hip_score.h"
 
 #include <hip/hip_runtime.h>
@@ -3321,6 +3322,95 @@ int dpmm_upload_points_strided_device(dpmm_ctx *c, const void *d_src, int dtype,
     if (c->n > 0) {
         HIPCHK(c, launch_ingest_strided(c->dX, c->ldx, d_src, dtype, stride_point, stride_feature, c->n, c->D, nan_to_zero, c->stream));
         if (int rc = finish_upload(c)) return rc;
+    }
+    c->have_points = true;
+    c->cache_force = true;
+    c->rows_full_K = -1;
+    return DPMM_OK;
+}
+
+// ---- include/dpmm_hip_csc.h: sparse points out of caller-owned device memory (csc_io.hip).  Between the phases the host reads the
+// 8-byte word of the first offender and the 8-byte number of entries kept; temporary memory is cnt [n] and the scan's tile totals.
+int dpmm_upload_points_csc_device(dpmm_ctx *c, const void *d_colptr, int index_dtype, const void *d_rowval, const void *d_nzval, int value_dtype,
+                                  int64_t nnz_extent, int index_base) {
+    static const char *fn = "dpmm_upload_points_csc_device";
+    const std::string who = std::string(fn) + ": ";
+    if (!c) return tensor_no_ctx(fn);
+    if (c->prior != DPMM_PRIOR_MULT) return fail(c, DPMM_EINVAL, who + "sparse points are for Multinomial contexts");
+    if (c->D > DPMM_MAX_DIM_MULT_SPARSE) return fail(c, DPMM_ELIMIT, who + "D > DPMM_MAX_DIM_MULT_SPARSE");
+    if (index_dtype != DPMM_DT_I32 && index_dtype != DPMM_DT_I64)
+        return fail(c, DPMM_EINVAL, who + "index_dtype " + std::to_string(index_dtype) + " is neither DPMM_DT_I32 nor DPMM_DT_I64");
+    const size_t is = ingest_elem_size(index_dtype), vs = ingest_elem_size(value_dtype);
+    if (vs == 0) return fail(c, DPMM_EINVAL, who + "value_dtype " + std::to_string(value_dtype) + " is not a DPMM_DT_* code");
+    if (index_base != 0 && index_base != 1) return fail(c, DPMM_EINVAL, who + "index_base must be 0 or 1");
+    if (nnz_extent < 0 || (nnz_extent >> 58)) return fail(c, DPMM_EINVAL, who + "nnz_extent out of range");
+    if (index_dtype == DPMM_DT_I32 && nnz_extent + index_base > INT32_MAX) return fail(c, DPMM_EINVAL, who + "nnz_extent does not fit Int32 offsets");
+    HIPCHK(c, hipSetDevice(c->device));
+    const int64_t n = c->n;
+    if (n > 0) {
+        if (int rc = check_device_extent(c, fn, "d_colptr", d_colptr, ((uint64_t)n + 1) * is, is)) return rc;
+        if (int rc = check_device_extent(c, fn, "d_rowval", d_rowval, (uint64_t)nnz_extent * is, is)) return rc;
+        if (int rc = check_device_extent(c, fn, "d_nzval", d_nzval, (uint64_t)nnz_extent * vs, vs)) return rc;
+    }
+    // everything is built beside the points in force; they are replaced only when the new ones have passed the checks
+    int64_t *n_cp = nullptr, *t_bt = nullptr;
+    float *n_val = nullptr;
+    uint16_t *n_ri = nullptr;
+    int32_t *t_cnt = nullptr;
+    const int64_t ntiles = csc_scan_tiles(n);
+    unsigned long long bad = ~0ull;
+    int64_t kept = 0;
+    hipError_t e = hipMalloc(&n_cp, sizeof(int64_t) * ((size_t)n + 1));
+    if (e == hipSuccess && n > 0) {
+        unsigned long long *t_bad = nullptr;
+        e = hipMalloc(&t_cnt, sizeof(int32_t) * (size_t)n);
+        if (e == hipSuccess) e = hipMalloc(&t_bt, sizeof(int64_t) * ((size_t)ntiles + 2));       // tile totals, the sum of all, the first offender
+        if (e == hipSuccess) {
+            t_bad = reinterpret_cast<unsigned long long *>(t_bt + ntiles + 1);
+            e = hipMemsetAsync(t_bad, 0xFF, sizeof(unsigned long long), c->stream);
+        }
+        if (e == hipSuccess) e = launch_csc_dev_check(d_colptr, d_rowval, d_nzval, index_dtype == DPMM_DT_I64, value_dtype, n, nnz_extent, c->D, index_base,
+                                                      t_cnt, t_bad, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(&bad, t_bad, sizeof(bad), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = sync_stream(c, c->stream);
+        if (e == hipSuccess && bad == ~0ull) {
+            e = launch_csc_scan(t_cnt, n, t_bt, n_cp, c->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(&kept, t_bt + ntiles, sizeof(kept), hipMemcpyDeviceToHost, c->stream);
+            if (e == hipSuccess) e = sync_stream(c, c->stream);
+            const size_t nn = (size_t)std::max<int64_t>(kept, 1);
+            if (e == hipSuccess) e = hipMalloc(&n_ri, sizeof(uint16_t) * nn);
+            if (e == hipSuccess) e = hipMalloc(&n_val, sizeof(float) * nn);
+            if (e == hipSuccess) e = launch_csc_dev_compact(d_colptr, d_rowval, d_nzval, index_dtype == DPMM_DT_I64, value_dtype, n, index_base, n_cp, n_ri,
+                                                            n_val, c->stream);
+            if (e == hipSuccess) e = sync_stream(c, c->stream);
+        }
+    } else if (e == hipSuccess) {
+        e = hipMemsetAsync(n_cp, 0, sizeof(int64_t), c->stream);
+        if (e == hipSuccess) e = sync_stream(c, c->stream);
+    }
+    hipFree(t_cnt); hipFree(t_bt);
+    if (e != hipSuccess || bad != ~0ull) {
+        hipFree(n_cp); hipFree(n_ri); hipFree(n_val);
+        if (e != hipSuccess) return fail(c, DPMM_EHIP, who + hipGetErrorString(e));
+        const std::string pt = std::to_string((long long)(bad >> 20));
+        switch ((int)(bad & 7)) {
+            case CSC_BAD_RANGE: return fail(c, DPMM_EINVAL, who + "point " + pt + ": row index out of range");
+            case CSC_BAD_ORDER: return fail(c, DPMM_EINVAL, who + "point " + pt + ": row indices are not strictly increasing (unsorted or duplicate)");
+            case CSC_BAD_DECREASES: return fail(c, DPMM_EINVAL, who + "colptr decreases at point " + pt);
+            default: return fail(c, DPMM_EINVAL, who + "colptr points outside rowval / nzval at point " + pt);
+        }
+    }
+    // from here on as dpmm_upload_points_csc
+    free_sparse_points(c);
+    hipFree(c->dX); hipFree(c->dX8); c->dX = nullptr; c->dX8 = nullptr;
+    c->d_cp = n_cp; c->d_ri = n_ri; c->d_val = n_val; c->nnz = kept;
+    c->x_sparse = 1; c->x_u8 = 0; c->x_bf16_exact = 0; c->repack_pending = false;
+    if (int rc2 = set_points_chunk(c, true)) return rc2;
+    if (c->have_params && c->d_raw) {
+        if (int rc2 = pack_sparse_image(c, c->d_raw, c->d_Rp, c->K)) return rc2;
+        c->rp_current = false;
+        c->mspec_valid = false;
+        HIPCHK(c, sync_stream(c, c->stream));
     }
     c->have_points = true;
     c->cache_force = true;

@@ -223,6 +223,18 @@ hipError_t launch_points_readback(float *out, int64_t ld_out, const float *X, in
                                   hipStream_t s);
 hipError_t launch_sparse_readback(float *out, int64_t ld_out, const int64_t *cp, const uint16_t *ri, const float *val, int64_t n, hipStream_t s);
 
+// ---- sparse points out of caller-owned device memory (csc_io.hip; include/dpmm_hip_csc.h)
+// cp: n + 1 ABSOLUTE offsets (minus base) into rv / nz, Int32 or Int64 as rv; nz of the DPMM_DT_* type value_dtype; extent: entries behind rv / nz.
+// bad[0] (preset to ~0): min over the offenders of point << 20 | (position in the column + 1) << 3 | reason
+enum { CSC_BAD_RANGE = 1, CSC_BAD_ORDER = 2, CSC_BAD_DECREASES = 3, CSC_BAD_OUTSIDE = 4 };
+constexpr int CSC_SCAN_TILE = 2048;      // points per workgroup and pass of the offsets' scan
+inline int64_t csc_scan_tiles(int64_t n) { return (n + CSC_SCAN_TILE - 1) / CSC_SCAN_TILE; }
+hipError_t launch_csc_dev_check(const void *cp, const void *rv, const void *nz, int index_i64, int value_dtype, int64_t n, int64_t extent, int D, int base,
+                                int32_t *cnt, unsigned long long *bad, hipStream_t s);
+hipError_t launch_csc_scan(const int32_t *cnt, int64_t n, int64_t *bt /* [csc_scan_tiles(n) + 1] */, int64_t *cp_out /* [n + 1] */, hipStream_t s);
+hipError_t launch_csc_dev_compact(const void *cp, const void *rv, const void *nz, int index_i64, int value_dtype, int64_t n, int base, const int64_t *cp_out,
+                                  uint16_t *ri, float *val, hipStream_t s);
+
 // ---- stable counting sort of the points by bin + segmented statistics (suffstats.hip)
 constexpr int SORT_TILE = 2048;  // points per sorting wave of big shards (SortBufs::tile: 2048 or SORT_TILE_SMALL)
 constexpr int SORT_TILE_SMALL = 512;

@@ -99,6 +99,8 @@ def _make_sampler(all_data, hyper, alpha, seed, burnout, max_clusters, comm, dev
         wk.upload_points(np.ascontiguousarray(X[:, lo:hi].T, dtype=np.float32))  # (n_local, D): row = point
     s = DPMMSampler(wk, hyper, alpha, N, int(seed), burnout=burnout, max_clusters=max_clusters, comm=comm, nthreads=nthreads,
                     **sampler_kw)
+    if desc is None and isinstance(csc, _sparse.DeviceCSC):
+        desc = csc                                     # (a sparse tensor in device memory: the same three attributes are read of it)
     s.data_tensor = desc                               # results follow the input (_final_labels)
     return s
 
@@ -119,7 +121,10 @@ def _final_labels(s, comm):
 
 def _data_device(all_data, device):
     """The `device` argument, or -- for a tensor in device memory -- that tensor's device (an explicit `device` must agree)."""
-    if _sparse.as_csc(all_data) is None:
+    csc = _sparse.as_csc(all_data)
+    if isinstance(csc, _sparse.DeviceCSC):
+        return _tensors.resolve_device(csc, device)
+    if csc is None:
         desc = _tensors.as_device_points(all_data)
         if desc is not None:
             return _tensors.resolve_device(desc, device)
@@ -290,6 +295,8 @@ def predict(dp_model, data, device=None, worker_factory=None):
         if s.prior.kind != _priors.PRIOR_MULT:
             raise TypeError("sparse data is for the Multinomial prior")
         D, n = csc.shape
+        if isinstance(csc, _sparse.DeviceCSC):
+            device = _tensors.resolve_device(csc, device)
     elif desc is not None:
         D, n = desc.shape
         device = _tensors.resolve_device(desc, device)

@@ -84,6 +84,7 @@ class Predictor:
             raise
         self._host_stage = None          # (capacity, D) float32, the short slab of host data
         self._dev_stage = None           # the same on the device, for the short slab of a device tensor
+        self._csc_stage = None           # capacity + 1 offsets on the device, for the short slab of a sparse_csc tensor
         self._out_stage = {}             # outputs of a short slab: name -> array / tensor of `capacity` rows
 
     # ---- life
@@ -91,7 +92,7 @@ class Predictor:
         if getattr(self, "_wk", None) is not None:
             self._wk.close()
             self._wk = None
-        self._host_stage = self._dev_stage = None
+        self._host_stage = self._dev_stage = self._csc_stage = None
         self._out_stage = {}
 
     def __enter__(self):
@@ -159,6 +160,12 @@ class Predictor:
             raise RuntimeError("this Predictor is closed")
         wk, cap = self._wk, self.capacity
         csc = _sparse.as_csc(data)
+        dcsc = csc if isinstance(csc, _sparse.DeviceCSC) else None
+        if dcsc is not None:
+            if _tensors.resolve_device(dcsc, self._device_arg) != self.device:
+                raise ValueError(f"the data tensor lives on {dcsc.torch_device}, this Predictor on device {self.device}: open one Predictor per GPU")
+            if not hasattr(wk, "upload_points_csc_device"):
+                csc, dcsc = dcsc.to_host(), None                          # (a stand-in worker without the device entry points)
         desc = None if csc is not None else _tensors.as_device_points(data)
         if desc is not None:
             if _tensors.resolve_device(desc, self._device_arg) != self.device:
@@ -179,11 +186,11 @@ class Predictor:
         if D != self.D:
             raise ValueError("data dimension does not match the model")
         spec = self._spec(labels, logdens, m, probs)
-        if desc is not None:
+        if desc is not None or dcsc is not None:
             import torch
-            dev = desc.torch_device
+            dev = (desc or dcsc).torch_device
             new = lambda rows, tail, dt: torch.empty((rows,) + tail, dtype=getattr(torch, dt), device=dev)      # noqa: E731
-            desc.synchronize()
+            (desc or dcsc).synchronize()
         else:
             dev = None
             new = lambda rows, tail, dt: np.empty((rows,) + tail, dt)      # noqa: E731
@@ -192,7 +199,19 @@ class Predictor:
             hi = min(n, lo + cap)
             full = hi - lo == cap
             # -- the slab's points
-            if csc is not None:
+            if dcsc is not None:
+                if full:                                                  # the slab's offsets where they are, the same entry arrays
+                    cp_ptr = dcsc.colptr_ptr(lo)
+                else:                                                     # the slice, then empty columns behind the last point
+                    st = self._csc_stage
+                    if st is None or st.device != dev or st.dtype != dcsc.colptr.dtype:
+                        st = self._csc_stage = torch.empty(cap + 1, dtype=dcsc.colptr.dtype, device=dev)
+                    st[:hi - lo + 1].copy_(dcsc.colptr[lo:hi + 1])
+                    st[hi - lo + 1:].copy_(dcsc.colptr[hi:hi + 1].expand(cap - (hi - lo)))
+                    torch.cuda.current_stream(dev).synchronize()
+                    cp_ptr = st.data_ptr()
+                wk.upload_points_csc_device(cp_ptr, dcsc.index_dtype, dcsc.rowval_ptr, dcsc.nzval_ptr, dcsc.value_dtype, dcsc.nnz_extent, 0)
+            elif csc is not None:
                 cp, rv, nz = csc.columns(lo, hi, check=not hasattr(wk, "upload_points_csc"))
                 if not full:                                              # empty columns behind the last point
                     cp = np.concatenate([cp, np.full(cap - (hi - lo), cp[-1], np.int64)])

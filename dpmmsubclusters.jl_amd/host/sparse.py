@@ -4,9 +4,20 @@ reference as Julia's SparseMatrixCSC / scipy.sparse.csc_matrix of shape (D, N) h
 Accepted wherever `fit` / `dp_parallel` / `resume_from_checkpoint` / `predict` take the data array:
   * an object with `indptr`, `indices`, `data` and `shape == (D, N)` (csc_matrix / csc_array; a CSR matrix of shape (N, D) is the
     same memory and comes in through `.T`).  Made canonical on a copy when it offers `sum_duplicates()` / `sort_indices()`;
-  * a tuple `(colptr, rowval, nzval, (D, N))`, 0-based, which must be canonical already (rows strictly increasing inside a column).
+  * a tuple `(colptr, rowval, nzval, (D, N))`, 0-based, which must be canonical already (rows strictly increasing inside a column);
+  * a torch tensor of layout `torch.sparse_csc` and shape (D, N): int32 or int64 indices, values of one of the eight element types of
+    host/tensors.py, 2-D, no batch or dense dimensions, not requiring grad.  A bag-of-words matrix held as `torch.sparse_csr` of shape
+    (N, D) is the same memory and comes in through `.t()` (`.T` is not implemented for that layout).  Canonical already, as a tuple: a
+    tensor that is not is refused by the upload, which names the point.  On a ROCm device it is described by a `DeviceCSC` and read in
+    place (include/dpmm_hip_csc.h: checked, counted and compacted on the device), labels / predictions come back as tensors on that
+    device; on the CPU it is the `CSC` over numpy views of its three arrays.  Other sparse layouts (COO, CSR, BSR, BSC) raise TypeError:
+    `.to_sparse_csc()` converts them.  torch is never imported here: a tensor cannot exist unless the caller has done so.
 """
+import sys
+
 import numpy as np
+
+from . import tensors as _tensors
 
 
 class CSC:
@@ -55,8 +66,75 @@ class CSC:
         return X
 
 
+class DeviceCSC:
+    """A (D, N) torch.sparse_csc tensor in device memory: the addresses of its three arrays, their element types and how many entries lie
+    behind rowval / nzval.  The offsets are absolute into the entries, so the columns [lo, hi) are `colptr_ptr(lo)` with the same two
+    entry addresses."""
+
+    def __init__(self, tensor, index_dtype, value_dtype):
+        self.tensor = tensor                       # keeps the memory alive for as long as the description is
+        self.shape = (int(tensor.shape[0]), int(tensor.shape[1]))
+        self.D, self.N = self.shape
+        self.colptr, self.rowval, self.nzval = tensor.ccol_indices(), tensor.row_indices(), tensor.values()
+        if not (self.colptr.is_contiguous() and self.rowval.is_contiguous() and self.nzval.is_contiguous()):
+            raise TypeError("sparse tensor data: the index and value arrays must be contiguous")
+        self.index_dtype, self.value_dtype = index_dtype, value_dtype
+        self.index_itemsize = _tensors.ITEMSIZE[index_dtype]
+        self.nnz_extent = int(self.rowval.numel())
+        self.rowval_ptr = int(self.rowval.data_ptr()) if self.nnz_extent else 0
+        self.nzval_ptr = int(self.nzval.data_ptr()) if self.nnz_extent else 0
+        self.torch_device = tensor.device
+        self.device_index = tensor.device.index if tensor.device.index is not None else 0
+
+    def colptr_ptr(self, lo):
+        """Address of point `lo`'s offset: the first of hi - lo + 1 offsets of the columns [lo, hi)."""
+        return int(self.colptr.data_ptr()) + int(lo) * self.index_itemsize
+
+    def synchronize(self):
+        """The tensor's arrays must be complete before the library reads them on its own stream."""
+        import torch
+        torch.cuda.current_stream(self.torch_device).synchronize()
+
+    def to_host(self):
+        """The same matrix as a host `CSC` (workers without the device entry point)."""
+        return _torch_csc_host(self.tensor.cpu(), self.value_dtype)
+
+
+def _torch_csc_host(t, value_dtype):
+    vals = t.values()
+    return CSC(t.ccol_indices().numpy(), t.row_indices().numpy(), (vals.float() if value_dtype == _tensors.DT_BF16 else vals).numpy(), t.shape)
+
+
+def _torch_sparse(data):
+    """`data` as CSC / DeviceCSC when it is a torch tensor of a sparse layout (TypeError where it cannot be taken); None otherwise."""
+    torch = sys.modules.get("torch")
+    if torch is None or not isinstance(data, torch.Tensor) or data.layout == torch.strided:
+        return None
+    if data.layout != torch.sparse_csc:
+        raise TypeError(f"sparse tensor data must be of layout torch.sparse_csc and shape (D, N); got {data.layout} -- "
+                        "tensor.to_sparse_csc() converts it (a sparse_csr tensor of shape (N, D) comes in as tensor.t())")
+    if data.requires_grad:
+        raise TypeError("tensor data requires grad: pass tensor.detach()")
+    vals = data.values()
+    if data.ndim != 2 or vals.ndim != 1 or data.ccol_indices().ndim != 1:
+        raise TypeError("sparse tensor data must be 2-D, Dimensions x Samples, without batch or dense dimensions")
+    value_dtype = _tensors._dtype_code(torch, vals.dtype)
+    index_dtype = _tensors._dtype_code(torch, data.ccol_indices().dtype)
+    if index_dtype not in (_tensors.DT_I32, _tensors.DT_I64):
+        raise TypeError("sparse tensor data: indices must be int32 or int64")
+    if data.device.type == "cpu":
+        return _torch_csc_host(data, value_dtype)
+    if data.device.type != "cuda":
+        raise TypeError(f"tensor data lives on device {data.device}: a ROCm device or the CPU is needed")
+    return DeviceCSC(data, index_dtype, value_dtype)
+
+
 def as_csc(data):
-    """CSC view of `data`, or None when it is not sparse input (an array goes the dense way)."""
+    """CSC view of `data` (a DeviceCSC for a sparse_csc tensor in device memory), or None when it is not sparse input (an array goes the
+    dense way)."""
+    t = _torch_sparse(data)
+    if t is not None:
+        return t
     if isinstance(data, tuple) and len(data) == 4 and isinstance(data[3], (tuple, list)) and len(data[3]) == 2:
         return CSC(data[0], data[1], data[2], data[3])
     if all(hasattr(data, a) for a in ("indptr", "indices", "data", "shape")) and not isinstance(data, np.ndarray):
@@ -78,7 +156,13 @@ def as_csc(data):
 
 def upload_columns(wk, csc, lo, hi):
     """The shard [lo, hi) into a worker: sparse where the worker can take it, else made dense on the host (test stand-ins, third-party
-    worker factories) -- as the .npy path falls back."""
+    worker factories) -- as the .npy path falls back.  A DeviceCSC is read where it is by a worker that can, else brought to the host."""
+    if isinstance(csc, DeviceCSC):
+        if hasattr(wk, "upload_points_csc_tensor"):
+            csc.synchronize()                                  # the tensor is complete before the library reads it on its own stream
+            wk.upload_points_csc_tensor(csc, lo, hi)           # the offsets from `lo` on: an address, no copy and no slicing on the host
+            return
+        csc = csc.to_host()
     if hasattr(wk, "upload_points_csc"):
         cp, rv, nz = csc.columns(lo, hi, check=False)          # (the device checks what it is given and names the point)
         wk.upload_points_csc(cp, rv, nz, index_base=0)

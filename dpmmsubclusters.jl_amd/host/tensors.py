@@ -57,7 +57,7 @@ class DeviceTensor:
 
 def _check(torch, t):
     if t.layout != torch.strided:
-        raise TypeError(f"tensor data must be dense (strided); got layout {t.layout} -- sparse count data comes in as scipy CSC or a tuple")
+        raise TypeError(f"tensor data must be dense (strided); got layout {t.layout} -- sparse count data comes in as scipy CSC, a tuple or a torch.sparse_csc tensor (tensor.to_sparse_csc())")
     if t.is_quantized:
         raise TypeError(f"tensor data of dtype {t.dtype} (quantised) is not supported")
     code = _dtype_code(torch, t.dtype)
