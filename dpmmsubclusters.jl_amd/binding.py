@@ -128,6 +128,23 @@ ABI_CSC = [
     ("dpmm_upload_points_csc_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                                                      ctypes.c_int64, ctypes.c_int]),
 ]
+
+
+class SampleRequest(ctypes.Structure):
+    """dpmm_sample_request (include/dpmm_hip_sample.h)."""
+    _fields_ = [("i0", ctypes.c_int64), ("n", ctypes.c_int64), ("cluster_start", _c_i64p), ("seed", ctypes.c_uint64), ("trials", ctypes.c_int64),
+                ("x", ctypes.c_void_p), ("ld", ctypes.c_int64), ("labels", ctypes.c_void_p), ("colptr", ctypes.c_void_p), ("nnz0", ctypes.c_int64),
+                ("rowval", ctypes.c_void_p), ("nzval", ctypes.c_void_p), ("nnz_extent", ctypes.c_int64), ("nnz_out", _c_i64p)]
+
+
+# include/dpmm_hip_sample.h: drawing points from a fitted model (additive; bound next to ABI)
+ABI_SAMPLE = [
+    ("dpmm_set_sampler_niw", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _c_f32p, _c_f32p, _c_f32p]),
+    ("dpmm_set_sampler_mult", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_int32)]),
+    ("dpmm_sample_points_device", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(SampleRequest)]),
+]
+SAMPLE_MAX_TRIALS_SPARSE = 4096        # DPMM_SAMPLE_MAX_TRIALS_SPARSE
+SAMPLE_MAX_TRIALS_DENSE = 1 << 24      # DPMM_SAMPLE_MAX_TRIALS_DENSE
 OPT_SCORE_TABLE_MB = 32      # DPMM_OPT_SCORE_TABLE_MB
 SCORE_MAX_TOP = 16           # DPMM_SCORE_MAX_TOP
 
@@ -194,7 +211,7 @@ def load_library():
         except Exception:  # pragma: no cover  (torch is optional for single-GPU use)
             pass
         lib = ctypes.CDLL(p)
-        for name, res, args in ABI + ABI_TENSOR + ABI_SCORE + ABI_CSC:
+        for name, res, args in ABI + ABI_TENSOR + ABI_SCORE + ABI_CSC + ABI_SAMPLE:
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -475,6 +492,31 @@ class Worker:
         logp, weights = _f32(logp), _f32(weights)
         assert logp.shape == (K, self.D)
         self._chk(self._lib.dpmm_set_predictive_mult(self._h, K, _p(logp, _c_f32p), _p(weights, _c_f32p)))
+
+    # ---- drawing points (include/dpmm_hip_sample.h)
+    def set_sampler_niw(self, m, A, df):
+        """dpmm_set_sampler_niw: m (K, D), A (K, D, D) upper triangular, df (K,)."""
+        m, A, df = map(_f32, (m, A, df))
+        K = len(df)
+        assert m.shape == (K, self.D) and A.size == K * self.D * self.D
+        self._chk(self._lib.dpmm_set_sampler_niw(self._h, K, _p(m, _c_f32p), _p(A, _c_f32p), _p(df, _c_f32p)))
+
+    def set_sampler_mult(self, thr, alias):
+        """dpmm_set_sampler_mult: the alias tables, thr (K, D) uint32 and alias (K, D) int32."""
+        thr, alias = np.ascontiguousarray(thr, np.uint32), np.ascontiguousarray(alias, np.int32)
+        assert thr.ndim == 2 and thr.shape == alias.shape and thr.shape[1] == self.D
+        self._chk(self._lib.dpmm_set_sampler_mult(self._h, thr.shape[0], _p(thr, ctypes.POINTER(ctypes.c_uint32)), _p(alias, ctypes.POINTER(ctypes.c_int32))))
+
+    def sample_points_raw(self, i0, n, cluster_start, seed, trials=0, x=0, ld=0, labels=0, colptr=0, nnz0=0, rowval=0, nzval=0, nnz_extent=0):
+        """dpmm_sample_points_device on plain device addresses (integers; 0 = not asked for); returns the entries counted by a sparse
+        first call, else None."""
+        cs = _i64(cluster_start)
+        nnz = ctypes.c_int64(0)
+        first = bool(colptr) and not (rowval or nzval)
+        req = SampleRequest(int(i0), int(n), _p(cs, _c_i64p), ctypes.c_uint64(int(seed)), int(trials), x or None, int(ld), labels or None, colptr or None,
+                            int(nnz0), rowval or None, nzval or None, int(nnz_extent), ctypes.pointer(nnz) if first else None)
+        self._chk(self._lib.dpmm_sample_points_device(self._h, ctypes.byref(req)))
+        return int(nnz.value) if first else None
 
     def score_points_raw(self, device, labels=0, logdens=0, m=0, top_idx=0, top_prob=0, probs=0):
         """dpmm_score_points[_device] on plain addresses (integers; 0 = not asked for)."""

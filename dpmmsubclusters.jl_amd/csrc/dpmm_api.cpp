@@ -9,6 +9,7 @@
 #include "../../include/dpmm_hip_tensor.h"
 #include "../../include/dpmm_hip_csc.h"
 #include "../../include/dpmm_hip_score.h"
+#include "../../include/dpmm_hip_sample.h"
 
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -135,6 +136,14 @@ struct dpmm_ctx {
     float *d_score_table = nullptr; size_t score_table_bytes = 0;
     char *d_score_out = nullptr; size_t score_out_bytes = 0;
     double opt_score_mb = 128.0;       // DPMM_OPT_SCORE_TABLE_MB
+    // drawing points (include/dpmm_hip_sample.h): the sampler's tables (dpmm_set_sampler_*) and what a call needs beside its outputs
+    // (cluster and tile starts; sparse: 4 bytes per point of counts and the scan's tile totals), allocated on first use
+    float *d_sm_m = nullptr, *d_sm_At = nullptr, *d_sm_df = nullptr;
+    uint32_t *d_sm_thr = nullptr;
+    int32_t *d_sm_alias = nullptr;
+    int sm_K = 0;
+    int64_t *d_sm_cstart = nullptr; int32_t *d_sm_tstart = nullptr; int sm_start_cap = 0;
+    int32_t *d_sm_cnt = nullptr; int64_t *d_sm_bt = nullptr;
 
     // sort + stats
     SortBufs sb{};
@@ -703,6 +712,8 @@ int dpmm_destroy(dpmm_ctx *c) {
     hipFree(c->sb.perm); hipFree(c->sb.bin_sel); hipFree(c->sb.perm_total); hipFree(c->d_small); hipFree(c->d_proj); hipFree(c->d_vals); hipFree(c->d_smart);
     hipFree(c->d_m0); hipFree(c->d_psi_lo); hipFree(c->d_pairs);
     hipFree(c->d_score_table); hipFree(c->d_score_out);
+    hipFree(c->d_sm_m); hipFree(c->d_sm_At); hipFree(c->d_sm_df); hipFree(c->d_sm_thr); hipFree(c->d_sm_alias);
+    hipFree(c->d_sm_cstart); hipFree(c->d_sm_tstart); hipFree(c->d_sm_cnt); hipFree(c->d_sm_bt);
     for (int i = 0; i < 2; ++i) { hipFree(c->d_Y[i]); hipFree(c->d_ld_sigma[i]); hipFree(c->d_mu_draw[i]); }
     hipFree(c->ma.fac); hipFree(c->ma.mean); hipFree(c->ma.kap); hipFree(c->ma.nu); hipFree(c->ma.rows_store);
     if (c->stream2) { hipStreamSynchronize(c->stream2); hipStreamDestroy(c->stream2); }
@@ -3588,6 +3599,159 @@ static int score_points(dpmm_ctx *c, const dpmm_score_out *o, bool device, const
 
 int dpmm_score_points(dpmm_ctx *c, const dpmm_score_out *out) { return score_points(c, out, false, "dpmm_score_points"); }
 int dpmm_score_points_device(dpmm_ctx *c, const dpmm_score_out *out) { return score_points(c, out, true, "dpmm_score_points_device"); }
+
+// ---- include/dpmm_hip_sample.h: drawing points from a fitted model (sample.hip) -------------------------------------------------------
+static int sampler_table(dpmm_ctx *c, void **dst, const void *src, size_t bytes) {
+    hipFree(*dst); *dst = nullptr;
+    HIPCHK(c, hipMalloc(dst, bytes));
+    HIPCHK(c, hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
+    return DPMM_OK;
+}
+
+int dpmm_set_sampler_niw(dpmm_ctx *c, int K, const float *m, const float *A, const float *df) {
+    static const std::string who = "dpmm_set_sampler_niw: ";
+    if (!c) return tensor_no_ctx("dpmm_set_sampler_niw");
+    if (c->prior != DPMM_PRIOR_NIW) return fail(c, DPMM_EINVAL, who + "the context is not an NIW one");
+    if (K < 1 || K > DPMM_MAX_CLUSTERS) return fail(c, DPMM_EINVAL, who + "K must be in 1..DPMM_MAX_CLUSTERS");
+    if (!m || !A || !df) return fail(c, DPMM_EINVAL, who + "m, A or df is null");
+    const int D = c->D;
+    for (int k = 0; k < K; ++k)
+        if (!(df[k] > 0.f) || !std::isfinite(df[k])) return fail(c, DPMM_EINVAL, who + "df[" + std::to_string(k) + "] is not a positive finite number");
+    // the kernel reads the factor transposed (its lanes run along the rows of A), with exact zeros below the diagonal
+    std::vector<float> At((size_t)K * D * D, 0.f);
+    for (int k = 0; k < K; ++k)
+        for (int a = 0; a < D; ++a)
+            for (int b = a; b < D; ++b) At[((size_t)k * D + b) * D + a] = A[((size_t)k * D + a) * D + b];
+    HIPCHK(c, hipSetDevice(c->device));
+    c->sm_K = 0;
+    if (int rc = sampler_table(c, reinterpret_cast<void **>(&c->d_sm_m), m, sizeof(float) * (size_t)K * D)) return rc;
+    if (int rc = sampler_table(c, reinterpret_cast<void **>(&c->d_sm_At), At.data(), sizeof(float) * At.size())) return rc;
+    if (int rc = sampler_table(c, reinterpret_cast<void **>(&c->d_sm_df), df, sizeof(float) * (size_t)K)) return rc;
+    c->sm_K = K;
+    return DPMM_OK;
+}
+
+int dpmm_set_sampler_mult(dpmm_ctx *c, int K, const uint32_t *thr, const int32_t *alias) {
+    static const std::string who = "dpmm_set_sampler_mult: ";
+    if (!c) return tensor_no_ctx("dpmm_set_sampler_mult");
+    if (c->prior != DPMM_PRIOR_MULT) return fail(c, DPMM_EINVAL, who + "the context is not a Multinomial one");
+    if (K < 1 || K > DPMM_MAX_CLUSTERS) return fail(c, DPMM_EINVAL, who + "K must be in 1..DPMM_MAX_CLUSTERS");
+    if (!thr || !alias) return fail(c, DPMM_EINVAL, who + "thr or alias is null");
+    const size_t cnt = (size_t)K * c->D;
+    for (size_t e = 0; e < cnt; ++e)
+        if (alias[e] < 0 || alias[e] >= c->D) return fail(c, DPMM_EINVAL, who + "alias[" + std::to_string(e) + "] is outside [0, D)");
+    HIPCHK(c, hipSetDevice(c->device));
+    c->sm_K = 0;
+    if (int rc = sampler_table(c, reinterpret_cast<void **>(&c->d_sm_thr), thr, sizeof(uint32_t) * cnt)) return rc;
+    if (int rc = sampler_table(c, reinterpret_cast<void **>(&c->d_sm_alias), alias, sizeof(int32_t) * cnt)) return rc;
+    c->sm_K = K;
+    return DPMM_OK;
+}
+
+int dpmm_sample_points_device(dpmm_ctx *c, const dpmm_sample_request *q) {
+    static const char *fn = "dpmm_sample_points_device";
+    const std::string who = std::string(fn) + ": ";
+    if (!c) return tensor_no_ctx(fn);
+    if (!q) return fail(c, DPMM_EINVAL, who + "the request is null");
+    if (c->sm_K < 1) return fail(c, DPMM_ESTATE, who + "no sampler set (dpmm_set_sampler_niw / _mult)");
+    const int K = c->sm_K, D = c->D;
+    const bool mult = c->prior == DPMM_PRIOR_MULT;
+    const bool sparse = q->colptr != nullptr;
+    if (q->n < 0 || q->n > c->n) return fail(c, DPMM_EINVAL, who + "n must be in 0..n_local (" + std::to_string((long long)c->n) + ")");
+    if (q->i0 < 0 || q->i0 > INT64_MAX - q->n) return fail(c, DPMM_EINVAL, who + "i0 out of range");
+    if (!q->cluster_start) return fail(c, DPMM_EINVAL, who + "cluster_start is null");
+    for (int k = 0; k < K; ++k)
+        if (q->cluster_start[k] < 0 || q->cluster_start[k + 1] < q->cluster_start[k]) return fail(c, DPMM_EINVAL, who + "cluster_start is negative or decreases");
+    if (q->n > 0 && (q->i0 < q->cluster_start[0] || q->i0 + q->n > q->cluster_start[K]))
+        return fail(c, DPMM_EINVAL, who + "[i0, i0 + n) is not inside [cluster_start[0], cluster_start[K])");
+    if (mult) {
+        if (q->trials < 1) return fail(c, DPMM_EINVAL, who + "trials must be at least 1 for a Multinomial context");
+        if (sparse && q->trials > DPMM_SAMPLE_MAX_TRIALS_SPARSE) return fail(c, DPMM_EINVAL, who + "trials > DPMM_SAMPLE_MAX_TRIALS_SPARSE");
+        if (q->trials > DPMM_SAMPLE_MAX_TRIALS_DENSE) return fail(c, DPMM_EINVAL, who + "trials > DPMM_SAMPLE_MAX_TRIALS_DENSE");
+    } else {
+        if (q->trials != 0) return fail(c, DPMM_EINVAL, who + "trials must be 0 for an NIW context");
+        if (sparse) return fail(c, DPMM_EINVAL, who + "sparse output is for Multinomial contexts");
+    }
+    const bool fill = sparse && (q->rowval || q->nzval);
+    if (sparse) {
+        if (q->x) return fail(c, DPMM_EINVAL, who + "x and colptr are both set");
+        if (D > DPMM_MAX_DIM_MULT_SPARSE) return fail(c, DPMM_ELIMIT, who + "D > DPMM_MAX_DIM_MULT_SPARSE");
+        if (q->nnz0 < 0 || (q->nnz0 >> 58)) return fail(c, DPMM_EINVAL, who + "nnz0 out of range");
+        if (fill && (q->nnz_extent < 0 || (q->nnz_extent >> 58))) return fail(c, DPMM_EINVAL, who + "nnz_extent out of range");
+        if (!fill && !q->nnz_out) return fail(c, DPMM_EINVAL, who + "nnz_out is null");
+    } else {
+        if (q->ld < D || (q->ld >> 40)) return fail(c, DPMM_EINVAL, who + "ld < D or out of range");
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    if (q->n == 0) {
+        if (sparse && !fill) {
+            if (int rc = check_device_extent(c, fn, "colptr", q->colptr, sizeof(int64_t), sizeof(int64_t))) return rc;
+            HIPCHK(c, hipMemcpy(q->colptr, &q->nnz0, sizeof(int64_t), hipMemcpyHostToDevice));
+            *q->nnz_out = 0;
+        }
+        return DPMM_OK;
+    }
+    const uint64_t n = (uint64_t)q->n;
+    if (sparse) {
+        if (int rc = check_device_extent(c, fn, "colptr", q->colptr, sizeof(int64_t) * (n + 1), sizeof(int64_t))) return rc;
+        if (fill) {
+            if (int rc = check_device_extent(c, fn, "rowval", q->rowval, sizeof(int64_t) * (uint64_t)q->nnz_extent, sizeof(int64_t))) return rc;
+            if (int rc = check_device_extent(c, fn, "nzval", q->nzval, sizeof(float) * (uint64_t)q->nnz_extent, sizeof(float))) return rc;
+            if (q->nnz_extent > 0 && (!q->rowval || !q->nzval)) return fail(c, DPMM_EINVAL, who + "rowval or nzval is null");
+        }
+    } else {
+        if (int rc = check_device_extent(c, fn, "x", q->x, sizeof(float) * ((n - 1) * (uint64_t)q->ld + (uint64_t)D), sizeof(float))) return rc;
+    }
+    if (q->labels) if (int rc = check_device_extent(c, fn, "labels", q->labels, sizeof(int64_t) * n, sizeof(int64_t))) return rc;
+    // cluster (and, NIW, 64-point tile) starts relative to the call
+    std::vector<int64_t> cs((size_t)K + 1);
+    std::vector<int32_t> ts((size_t)K + 1);
+    int64_t tiles = 0;
+    for (int k = 0; k <= K; ++k) {
+        cs[k] = std::min<int64_t>(std::max<int64_t>(q->cluster_start[k] - q->i0, 0), q->n);
+        if (k > 0) tiles += (cs[k] - cs[k - 1] + 63) / 64;
+        ts[k] = (int32_t)tiles;
+    }
+    cs[0] = 0;
+    if (c->sm_start_cap < K + 1) {
+        hipFree(c->d_sm_cstart); hipFree(c->d_sm_tstart); c->d_sm_cstart = nullptr; c->d_sm_tstart = nullptr; c->sm_start_cap = 0;
+        HIPCHK(c, hipMalloc(&c->d_sm_cstart, sizeof(int64_t) * (DPMM_MAX_CLUSTERS + 1)));
+        HIPCHK(c, hipMalloc(&c->d_sm_tstart, sizeof(int32_t) * (DPMM_MAX_CLUSTERS + 1)));
+        c->sm_start_cap = DPMM_MAX_CLUSTERS + 1;
+    }
+    HIPCHK(c, hipMemcpyAsync(c->d_sm_cstart, cs.data(), sizeof(int64_t) * cs.size(), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->d_sm_tstart, ts.data(), sizeof(int32_t) * ts.size(), hipMemcpyHostToDevice, c->stream));
+    SampleArgs a{};
+    a.i0 = q->i0; a.n = q->n; a.cstart = c->d_sm_cstart; a.tstart = c->d_sm_tstart; a.K = K; a.D = D; a.seed = q->seed;
+    a.m = c->d_sm_m; a.At = c->d_sm_At; a.df = c->d_sm_df; a.thr = c->d_sm_thr; a.alias = c->d_sm_alias; a.trials = q->trials;
+    a.x = q->x; a.ld = q->ld; a.labels = q->labels;
+    if (!mult) {
+        HIPCHK(c, launch_sample_niw(a, (int)tiles, c->cus, c->stream));
+    } else if (!sparse) {
+        HIPCHK(c, launch_sample_mult_dense(a, c->stream));
+    } else if (!fill) {
+        if (!c->d_sm_cnt) {
+            HIPCHK(c, hipMalloc(&c->d_sm_cnt, sizeof(int32_t) * (size_t)c->n));
+            HIPCHK(c, hipMalloc(&c->d_sm_bt, sizeof(int64_t) * ((size_t)csc_scan_tiles(c->n) + 1)));
+        }
+        a.cnt = c->d_sm_cnt;
+        a.labels = nullptr;
+        HIPCHK(c, launch_sample_mult_sparse(a, false, c->stream));
+        HIPCHK(c, launch_csc_scan(c->d_sm_cnt, q->n, c->d_sm_bt, q->colptr, c->stream));
+        HIPCHK(c, launch_sample_add_i64(q->colptr, q->n + 1, q->nnz0, c->stream));
+        int64_t kept = 0;
+        HIPCHK(c, hipMemcpyAsync(&kept, c->d_sm_bt + csc_scan_tiles(q->n), sizeof(kept), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, sync_stream(c, c->stream));
+        *q->nnz_out = kept;
+        return DPMM_OK;
+    } else {
+        a.colptr = q->colptr; a.rowval = q->rowval; a.nzval = q->nzval; a.extent = q->nnz_extent;
+        a.labels = nullptr;
+        HIPCHK(c, launch_sample_mult_sparse(a, true, c->stream));
+    }
+    HIPCHK(c, sync_stream(c, c->stream));
+    return DPMM_OK;
+}
 
 }  // extern "C"
 #pragma GCC visibility pop

@@ -14,6 +14,9 @@ namespace dpmm {
 constexpr int WAVE = 64;
 
 enum : uint32_t { STREAM_SWEEP = 0, STREAM_INIT = 1, STREAM_SPLIT = 2, STREAM_RESET = 3 };
+// Drawing points from a fitted model (sample.hip; include/dpmm_hip_sample.h states the keying).  The masters' streams are 32..34
+// (niw_master.hip) and 35 (mult_master.hip): these stay clear of them.
+enum : uint32_t { STREAM_SAMPLE_NORMAL = 40, STREAM_SAMPLE_CHI = 41, STREAM_SAMPLE_MULT = 42 };
 
 struct Philox4 {
     uint32_t v[4];

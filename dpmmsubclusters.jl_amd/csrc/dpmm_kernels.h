@@ -187,6 +187,33 @@ struct ScoreArgs {
     float *probs;
 };
 hipError_t launch_score_finish(const ScoreArgs &a, hipStream_t s);
+// ---- drawing points (sample.hip; include/dpmm_hip_sample.h): n samples from global index i0; every output pointer is that of the call's
+// first sample
+struct SampleArgs {
+    int64_t i0, n;
+    const int64_t *cstart;    // [K + 1] device: first sample of every cluster relative to the call, clipped to [0, n]
+    const int32_t *tstart;    // [K + 1] device, NIW: first 64-point tile of every cluster
+    int K, D;
+    uint64_t seed;
+    const float *m;           // NIW [K][D]
+    const float *At;          // NIW [K][D][D] TRANSPOSED: At[b][a] = A[a][b], zero where b < a
+    const float *df;          // NIW [K]
+    const uint32_t *thr;      // Multinomial [K][D]
+    const int32_t *alias;     // Multinomial [K][D]
+    int64_t trials;
+    float *x;                 // dense [n][ld]
+    int64_t ld;
+    int64_t *labels;          // [n] or null
+    int32_t *cnt;             // sparse, first pass: [n] stored entries of every sample
+    const int64_t *colptr;    // sparse, second pass: [n + 1] absolute offsets
+    int64_t *rowval;
+    float *nzval;
+    int64_t extent;           // entries behind rowval / nzval
+};
+hipError_t launch_sample_niw(const SampleArgs &a, int ntiles, int cus, hipStream_t s);
+hipError_t launch_sample_mult_dense(const SampleArgs &a, hipStream_t s);
+hipError_t launch_sample_mult_sparse(const SampleArgs &a, bool fill, hipStream_t s);
+hipError_t launch_sample_add_i64(int64_t *p, int64_t n, int64_t v, hipStream_t s);
 hipError_t launch_ingest_rows(float *dst, int64_t ldx, const void *src, int is_f64, int64_t ld, int64_t rows, int D, int nan_to_zero,
                               hipStream_t s);
 hipError_t launch_copy_bytes(void *dst, const void *src, size_t bytes, hipStream_t s);

@@ -36,6 +36,36 @@ class _Capture:
         self.args = ("mult", (logp, weights))
 
 
+def alias_tables(theta):
+    """Walker / Vose alias tables of the rows of `theta` (K, D), probabilities summing to 1 per row, built in Float64:
+    (thr (K, D) uint32, alias (K, D) int32).  A draw takes bucket j uniformly and returns j when a uniform 32-bit word is below thr[j],
+    else alias[j]: category d has probability (thr[d] + sum over the buckets j with alias[j] = d of (2^32 - thr[j])) / (2^32 D), which is
+    theta[d] to within 2^-32 (a threshold is rounded down to a multiple of 2^-32, and at most D buckets of weight 1 / D point at d).  A
+    full bucket is its own alias, so its threshold decides nothing; a category of probability 0 has threshold 0 and is nobody's alias."""
+    theta = np.atleast_2d(np.asarray(theta, np.float64))
+    K, D = theta.shape
+    thr = np.zeros((K, D), np.uint32)
+    alias = np.zeros((K, D), np.int32)
+    for k in range(K):
+        p = (theta[k] * D).tolist()
+        small = [j for j in range(D) if p[j] < 1.0]
+        large = [j for j in range(D) if p[j] >= 1.0]
+        prob = [1.0] * D
+        al = list(range(D))
+        while small and large:
+            s, g = small.pop(), large.pop()
+            prob[s], al[s] = p[s], g
+            p[g] = (p[g] + p[s]) - 1.0
+            (small if p[g] < 1.0 else large).append(g)
+        for j in small:                           # what rounding left over: buckets that are full to within the rounding of the sums
+            if theta[k, j] <= 0.0:
+                raise ValueError("alias_tables: the probabilities of a row do not sum to 1")
+        t = np.floor(np.asarray(prob) * 4294967296.0)
+        thr[k] = np.minimum(t, 4294967295.0).astype(np.uint32)
+        alias[k] = al
+    return thr, alias
+
+
 def _device_index(device):
     if device is None or isinstance(device, (int, np.integer)):
         return device
@@ -86,6 +116,7 @@ class Predictor:
         self._dev_stage = None           # the same on the device, for the short slab of a device tensor
         self._csc_stage = None           # capacity + 1 offsets on the device, for the short slab of a sparse_csc tensor
         self._out_stage = {}             # outputs of a short slab: name -> array / tensor of `capacity` rows
+        self._sampler_set = False        # the sampler's tables are formed and uploaded by the first sample()
 
     # ---- life
     def close(self):
@@ -141,6 +172,98 @@ class Predictor:
     def score_samples(self, data):
         """(n,) float32: log of the mixture's posterior predictive density at every point."""
         return self._run(data, logdens=True)["logdens"]
+
+    # ---- drawing points (include/dpmm_hip_sample.h)
+    def sampler_tables(self):
+        """What the sampler uploads, formed in Float64: NIW ("niw", m (K, D), A (K, D, D) = sqrt(c) U, df (K,)) -- the posterior
+        predictive MvT(df, m, A A') that `predict` scores with -- or ("mult", theta (K, D), thr, alias)."""
+        if self.kind == _priors.PRIOR_NIW:
+            kap, nu, U = (np.asarray(self.post[k], np.float64) for k in ("kappa", "nu", "U"))
+            df = nu - self.D + 1
+            c = (kap + 1) / (kap * df)
+            return "niw", np.asarray(self.post["m"], np.float64), np.sqrt(c)[:, None, None] * np.triu(U), df
+        a = np.asarray(self.post["alpha"], np.float64)
+        theta = a / a.sum(1, keepdims=True)
+        return ("mult", theta) + alias_tables(theta)
+
+    def cluster_sizes(self, n, seed=0):
+        """n_k ~ Multinomial(n, weights) from numpy's Philox generator: a function of (seed, n) and the model alone."""
+        w = self.points_count + self.alpha
+        return np.random.Generator(np.random.Philox(int(seed))).multinomial(int(n), w / w.sum()).astype(np.int64)
+
+    def sample(self, n, seed=0, trials=None, sparse=False):
+        """(data, labels): n new points from the fitted mixture, drawn on the GPU.
+
+        data     (D, n), Dimensions x Samples, on this Predictor's device: a Float32 tensor whose memory is point-major (the `.T` view of
+                 an (n, D) tensor: what `fit` and `predict` read in place), or with sparse=True (Multinomial) a torch.sparse_csc tensor
+                 with Int64 indices and Float32 counts, rows strictly increasing inside a column, no stored zero.
+        labels   (n,) int64 tensor, 1-based and NON-DECREASING: the points come grouped by cluster, as scikit-learn's
+                 GaussianMixture.sample returns them (torch.randperm shuffles them).  The cluster sizes are one Multinomial(n, weights) draw
+                 on the host (`cluster_sizes`).
+        NIW: the posterior predictive Student-t that `predict` scores with.  Multinomial: Multinomial(trials, alpha' / sum(alpha')) -- `trials`
+        per point is required (and refused for NIW); sparse=True allows at most binding.SAMPLE_MAX_TRIALS_SPARSE trials.
+        Point i depends on (seed, i, its cluster, the model) only: the same seed gives the same bits whatever `capacity` is, and a
+        Predictor restored by `load` draws what the saved one drew."""
+        if self._wk is None:
+            raise RuntimeError("this Predictor is closed")
+        n, seed = int(n), int(seed)
+        if n < 0:
+            raise ValueError("n must not be negative")
+        if seed < 0 or seed >> 64:
+            raise ValueError("seed must be in 0..2^64 - 1")
+        mult = self.kind == _priors.PRIOR_MULT
+        if mult:
+            if trials is None:
+                raise ValueError("the Multinomial prior needs `trials`, the number of trials per point")
+            trials = int(trials)
+            if trials < 1:
+                raise ValueError("trials must be at least 1")
+            limit = binding.SAMPLE_MAX_TRIALS_SPARSE if sparse else binding.SAMPLE_MAX_TRIALS_DENSE
+            if trials > limit:
+                raise ValueError(f"trials must not exceed {limit}" + (" for sparse output (DPMM_SAMPLE_MAX_TRIALS_SPARSE)" if sparse else ""))
+            if sparse and self.D > 65536:
+                raise ValueError("sparse output needs D <= 65536")
+        else:
+            if trials is not None:
+                raise ValueError("`trials` is for the Multinomial prior")
+            if sparse:
+                raise ValueError("sparse output is for the Multinomial prior")
+        wk, cap, D = self._wk, self.capacity, self.D
+        if not hasattr(wk, "sample_points_raw"):
+            raise RuntimeError("this Predictor's worker cannot draw points (no dpmm_sample_points_device)")
+        import torch
+        if not self._sampler_set:
+            t = self.sampler_tables()
+            if t[0] == "niw":
+                wk.set_sampler_niw(t[1], t[2], t[3])
+            else:
+                wk.set_sampler_mult(t[2], t[3])
+            self._sampler_set = True
+        dev = torch.device("cuda", self.device)
+        n_k = self.cluster_sizes(n, seed)
+        starts = np.concatenate([[0], np.cumsum(n_k)]).astype(np.int64)
+        tr = trials if mult else 0
+        if not sparse:
+            x = torch.empty((n, D), dtype=torch.float32, device=dev)
+            labels = torch.empty((n,), dtype=torch.int64, device=dev)
+            torch.cuda.current_stream(dev).synchronize()       # nothing queued on torch's stream still uses this memory
+            for lo in range(0, n, cap):
+                wk.sample_points_raw(lo, min(cap, n - lo), starts, seed, tr, x=x.data_ptr() + 4 * lo * D, ld=D, labels=labels.data_ptr() + 8 * lo)
+            return x.T, labels
+        colptr = torch.zeros((n + 1,), dtype=torch.int64, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        nnz = 0
+        for lo in range(0, n, cap):                             # pass 1: the offsets, slab by slab, each from the entries in front
+            nnz += wk.sample_points_raw(lo, min(cap, n - lo), starts, seed, tr, colptr=colptr.data_ptr() + 8 * lo, nnz0=nnz)
+        rowval = torch.empty((nnz,), dtype=torch.int64, device=dev)
+        nzval = torch.empty((nnz,), dtype=torch.float32, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        if nnz:
+            for lo in range(0, n, cap):                         # pass 2: the same draws, run-length encoded
+                wk.sample_points_raw(lo, min(cap, n - lo), starts, seed, tr, colptr=colptr.data_ptr() + 8 * lo, rowval=rowval.data_ptr(),
+                                     nzval=nzval.data_ptr(), nnz_extent=nnz)
+        labels = torch.repeat_interleave(torch.arange(1, self.K + 1, dtype=torch.int64, device=dev), torch.as_tensor(n_k, device=dev), output_size=n)
+        return torch.sparse_csc_tensor(colptr, rowval, nzval, size=(D, n)), labels
 
     # ---- slabs
     def _spec(self, labels, logdens, m, probs):
@@ -269,3 +392,9 @@ def predict_topk(dp_model, data, m, **kw):
     """(labels, idx (n, m), probs (n, m)) of the m most probable clusters (opens a Predictor, runs, closes)."""
     with Predictor(dp_model, **kw) as p:
         return p.predict_topk(data, m)
+
+
+def sample(dp_model, n, seed=0, trials=None, sparse=False, **kw):
+    """(data, labels): n new points from the fitted mixture (opens a Predictor, draws, closes); kw: capacity, device, worker_factory."""
+    with Predictor(dp_model, **kw) as p:
+        return p.sample(n, seed=seed, trials=trials, sparse=sparse)
