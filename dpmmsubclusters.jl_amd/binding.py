@@ -123,6 +123,23 @@ ABI_SCORE = [
     ("dpmm_score_points", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ScoreOut)]),
     ("dpmm_score_points_device", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ScoreOut)]),
 ]
+
+
+class RankOut(ctypes.Structure):
+    """dpmm_rank_out (include/dpmm_hip_rank.h): host or device addresses, 0 / None = not asked for."""
+    _fields_ = [("typ_idx", ctypes.c_void_p), ("typ_score", ctypes.c_void_p), ("fringe_idx", ctypes.c_void_p), ("fringe_score", ctypes.c_void_p),
+                ("count", ctypes.c_void_p), ("skipped", ctypes.c_void_p)]
+
+
+# include/dpmm_hip_rank.h: exemplars, the m most and least typical points of every cluster (additive; bound next to ABI)
+ABI_RANK = [
+    ("dpmm_rank_begin", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]),
+    ("dpmm_rank_accumulate", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64]),
+    ("dpmm_rank_read", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(RankOut)]),
+    ("dpmm_rank_read_device", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(RankOut)]),
+]
+RANK_MAX_M = 64                        # DPMM_RANK_MAX_M
+RANK_TYPICAL, RANK_FRINGE = 1, 2       # DPMM_RANK_TYPICAL, DPMM_RANK_FRINGE
 # include/dpmm_hip_csc.h: sparse points out of caller-owned device memory (additive; bound next to ABI)
 ABI_CSC = [
     ("dpmm_upload_points_csc_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
@@ -211,7 +228,7 @@ def load_library():
         except Exception:  # pragma: no cover  (torch is optional for single-GPU use)
             pass
         lib = ctypes.CDLL(p)
-        for name, res, args in ABI + ABI_TENSOR + ABI_SCORE + ABI_CSC + ABI_SAMPLE:
+        for name, res, args in ABI + ABI_TENSOR + ABI_SCORE + ABI_RANK + ABI_CSC + ABI_SAMPLE:
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -556,6 +573,43 @@ class Worker:
             raise ValueError("score_points: no output asked for")
         if n > 0:
             self.score_points_into(res, m=m)
+        return res
+
+    # ---- exemplars (include/dpmm_hip_rank.h)
+    def rank_begin(self, m, which=RANK_TYPICAL | RANK_FRINGE):
+        """dpmm_rank_begin: a new ranking of width m over the lists in `which` (RANK_TYPICAL | RANK_FRINGE)."""
+        self._chk(self._lib.dpmm_rank_begin(self._h, int(m), int(which)))
+        self._rank_shape = (self.K, int(m))
+
+    def rank_accumulate(self, index_base, n_valid):
+        """dpmm_rank_accumulate: ranks the points 0..n_valid-1 of the current upload as global indices index_base + i."""
+        self._chk(self._lib.dpmm_rank_accumulate(self._h, int(index_base), int(n_valid)))
+
+    def rank_read_raw(self, device, typ_idx=0, typ_score=0, fringe_idx=0, fringe_score=0, count=0, skipped=0):
+        """dpmm_rank_read[_device] on plain addresses (integers; 0 = not asked for)."""
+        out = RankOut(typ_idx or None, typ_score or None, fringe_idx or None, fringe_score or None, count or None, skipped or None)
+        fn = self._lib.dpmm_rank_read_device if device else self._lib.dpmm_rank_read
+        self._chk(fn(self._h, ctypes.byref(out)))
+
+    def rank_read(self, device=None):
+        """The lists as they stand: a dict with `typ_idx`, `fringe_idx` (K, m) int64 (0-based global indices, -1 = unused slot),
+        `typ_score`, `fringe_score` (K, m) float32 (NaN = unused slot), `count` (K,) int64 and `skipped` (1,) int64.
+        device: a torch device -- the results are tensors there, written by the library; None: numpy arrays."""
+        shape = getattr(self, "_rank_shape", None)
+        if shape is None:
+            self.rank_read_raw(False)          # (DPMM_ESTATE: no dpmm_rank_begin yet)
+            raise RuntimeError("rank_read needs rank_begin first")
+        K = shape[0]
+        spec = [("typ_idx", shape, "int64"), ("typ_score", shape, "float32"), ("fringe_idx", shape, "int64"), ("fringe_score", shape, "float32"),
+                ("count", (K,), "int64"), ("skipped", (1,), "int64")]
+        if device is not None:
+            import torch
+            res = {name: torch.empty(sh, dtype=getattr(torch, dt), device=device) for name, sh, dt in spec}
+            torch.cuda.current_stream(res["count"].device).synchronize()
+            self.rank_read_raw(True, **{k: v.data_ptr() for k, v in res.items()})
+        else:
+            res = {name: np.empty(sh, dt) for name, sh, dt in spec}
+            self.rank_read_raw(False, **{k: v.ctypes.data for k, v in res.items()})
         return res
 
     def predict_table_mult(self, logp, weights, points=False):

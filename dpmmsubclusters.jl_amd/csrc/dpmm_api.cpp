@@ -9,6 +9,7 @@
 #include "../../include/dpmm_hip_tensor.h"
 #include "../../include/dpmm_hip_csc.h"
 #include "../../include/dpmm_hip_score.h"
+#include "../../include/dpmm_hip_rank.h"
 #include "../../include/dpmm_hip_sample.h"
 
 #include <hip/hip_runtime.h>
@@ -136,6 +137,13 @@ struct dpmm_ctx {
     float *d_score_table = nullptr; size_t score_table_bytes = 0;
     char *d_score_out = nullptr; size_t score_out_bytes = 0;
     double opt_score_mb = 128.0;       // DPMM_OPT_SCORE_TABLE_MB
+    // exemplars (include/dpmm_hip_rank.h): running lists | counters | candidate counters; the candidate buffers; the staging of dpmm_rank_read
+    unsigned long long *d_rank_state = nullptr; size_t rank_state_bytes = 0;
+    char *d_rank_cand = nullptr; size_t rank_cand_bytes = 0;
+    char *d_rank_out = nullptr; size_t rank_out_bytes = 0;
+    bool rank_active = false;
+    int rank_m = 0, rank_which = 0, rank_K = 0, rank_parity = 0;
+    int64_t rank_cap = 0;
     // drawing points (include/dpmm_hip_sample.h): the sampler's tables (dpmm_set_sampler_*) and what a call needs beside its outputs
     // (cluster and tile starts; sparse: 4 bytes per point of counts and the scan's tile totals), allocated on first use
     float *d_sm_m = nullptr, *d_sm_At = nullptr, *d_sm_df = nullptr;
@@ -712,6 +720,7 @@ int dpmm_destroy(dpmm_ctx *c) {
     hipFree(c->sb.perm); hipFree(c->sb.bin_sel); hipFree(c->sb.perm_total); hipFree(c->d_small); hipFree(c->d_proj); hipFree(c->d_vals); hipFree(c->d_smart);
     hipFree(c->d_m0); hipFree(c->d_psi_lo); hipFree(c->d_pairs);
     hipFree(c->d_score_table); hipFree(c->d_score_out);
+    hipFree(c->d_rank_state); hipFree(c->d_rank_cand); hipFree(c->d_rank_out);
     hipFree(c->d_sm_m); hipFree(c->d_sm_At); hipFree(c->d_sm_df); hipFree(c->d_sm_thr); hipFree(c->d_sm_alias);
     hipFree(c->d_sm_cstart); hipFree(c->d_sm_tstart); hipFree(c->d_sm_cnt); hipFree(c->d_sm_bt);
     for (int i = 0; i < 2; ++i) { hipFree(c->d_Y[i]); hipFree(c->d_ld_sigma[i]); hipFree(c->d_mu_draw[i]); }
@@ -3520,6 +3529,19 @@ static int ensure_score_buffer(dpmm_ctx *c, void **buf, size_t *have, size_t nee
     return DPMM_OK;
 }
 
+// slabs of whole tiles: as many as the budget holds, one at least; the ctx's table is grown to one slab.  rstep: cluster k is row k * rstep;
+// P: points of a slab = floats between two rows of the table
+static int score_table_slab(dpmm_ctx *c, int *rstep_out, int64_t *P_out) {
+    const int rstep = (c->prior == DPMM_PRIOR_NIW) ? 1 : 3;       // Multinomial: rows 3k are the cluster-level rows
+    const size_t rows = (size_t)rstep * (size_t)c->K;
+    const double tile_bytes = (double)rows * (double)c->tile * sizeof(float);
+    int64_t slab_tiles = (int64_t)std::min<double>(std::floor(c->opt_score_mb * 1048576.0 / tile_bytes), (double)c->ntiles);
+    if (slab_tiles < 1) slab_tiles = 1;
+    const int64_t P = slab_tiles * c->tile;
+    *rstep_out = rstep; *P_out = P;
+    return ensure_score_buffer(c, reinterpret_cast<void **>(&c->d_score_table), &c->score_table_bytes, sizeof(float) * rows * (size_t)P, "table");
+}
+
 static int score_points(dpmm_ctx *c, const dpmm_score_out *o, bool device, const char *fn) {
     if (!c) return tensor_no_ctx(fn);
     const std::string who = std::string(fn) + ": ";
@@ -3541,14 +3563,9 @@ static int score_points(dpmm_ctx *c, const dpmm_score_out *o, bool device, const
         if (o->top_prob) if (int rc = check_device_extent(c, fn, "top_prob", o->top_prob, sizeof(float) * n * m, sizeof(float))) return rc;
         if (o->probs) if (int rc = check_device_extent(c, fn, "probs", o->probs, sizeof(float) * n * K, sizeof(float))) return rc;
     }
-    // slabs of whole tiles: as many as the budget holds, one at least
-    const int rstep = (c->prior == DPMM_PRIOR_NIW) ? 1 : 3;       // Multinomial: rows 3k are the cluster-level rows
-    const size_t rows = (size_t)rstep * (size_t)c->K;
-    const double tile_bytes = (double)rows * (double)c->tile * sizeof(float);
-    int64_t slab_tiles = (int64_t)std::min<double>(std::floor(c->opt_score_mb * 1048576.0 / tile_bytes), (double)c->ntiles);
-    if (slab_tiles < 1) slab_tiles = 1;
-    const int64_t P = slab_tiles * c->tile;                        // points of a slab = floats between two rows of the table
-    if (int rc = ensure_score_buffer(c, reinterpret_cast<void **>(&c->d_score_table), &c->score_table_bytes, sizeof(float) * rows * (size_t)P, "table")) return rc;
+    int rstep = 0;
+    int64_t P = 0;
+    if (int rc = score_table_slab(c, &rstep, &P)) return rc;
     // host variant: the slab's outputs on the device, one block per output (each 8-byte aligned)
     size_t off_lab = 0, off_ld = 0, off_ti = 0, off_tp = 0, off_pr = 0, total = 0;
     if (!device) {
@@ -3599,6 +3616,116 @@ static int score_points(dpmm_ctx *c, const dpmm_score_out *o, bool device, const
 
 int dpmm_score_points(dpmm_ctx *c, const dpmm_score_out *out) { return score_points(c, out, false, "dpmm_score_points"); }
 int dpmm_score_points_device(dpmm_ctx *c, const dpmm_score_out *out) { return score_points(c, out, true, "dpmm_score_points_device"); }
+
+// ---- include/dpmm_hip_rank.h: exemplars, the m most and least typical points of every cluster (rank.hip) -----------------------------------
+static size_t rank_keys_words(int K) { return (size_t)2 * (size_t)K * RANK_SLOTS; }
+static size_t rank_count_words(int K) { return (size_t)RANK_REPL * (size_t)(K + 1); }
+
+int dpmm_rank_begin(dpmm_ctx *c, int m, int which) {
+    static const char *fn = "dpmm_rank_begin";
+    if (!c) return tensor_no_ctx(fn);
+    const std::string who = std::string(fn) + ": ";
+    if (m < 1 || m > DPMM_RANK_MAX_M) return fail(c, DPMM_EINVAL, who + "m must be in 1.." + std::to_string(DPMM_RANK_MAX_M));
+    if (which < 1 || which > (DPMM_RANK_TYPICAL | DPMM_RANK_FRINGE)) return fail(c, DPMM_EINVAL, who + "which must be DPMM_RANK_TYPICAL, DPMM_RANK_FRINGE or both");
+    if (!c->predictive) return fail(c, DPMM_ESTATE, who + "needs dpmm_set_predictive_* first");
+    HIPCHK(c, hipSetDevice(c->device));
+    c->rank_active = false;
+    const int K = c->K;
+    const int64_t cap = std::max<int64_t>(1, std::min<int64_t>(RANK_CHUNK, c->n));
+    const size_t state = sizeof(unsigned long long) * (rank_keys_words(K) + rank_count_words(K) + 2);      // (2 words: the four candidate counters)
+    const size_t cand = (size_t)2 * (size_t)cap * (sizeof(unsigned long long) + sizeof(uint16_t));
+    const size_t km = (size_t)K * (size_t)m;
+    const size_t out = 2 * km * sizeof(int64_t) + 2 * ((km * sizeof(float) + 7) & ~(size_t)7) + (size_t)(K + 1) * sizeof(int64_t);
+    if (int rc = ensure_score_buffer(c, reinterpret_cast<void **>(&c->d_rank_state), &c->rank_state_bytes, state, "running lists of dpmm_rank_begin")) return rc;
+    if (int rc = ensure_score_buffer(c, reinterpret_cast<void **>(&c->d_rank_cand), &c->rank_cand_bytes, cand, "candidate buffers of dpmm_rank_begin")) return rc;
+    if (int rc = ensure_score_buffer(c, reinterpret_cast<void **>(&c->d_rank_out), &c->rank_out_bytes, out, "staging of dpmm_rank_read")) return rc;
+    HIPCHK(c, hipMemsetAsync(c->d_rank_state, 0, state, c->stream));
+    c->rank_m = m; c->rank_which = which; c->rank_K = K; c->rank_cap = cap; c->rank_parity = 0;
+    c->rank_active = true;
+    return DPMM_OK;
+}
+
+int dpmm_rank_accumulate(dpmm_ctx *c, int64_t index_base, int64_t n_valid) {
+    static const char *fn = "dpmm_rank_accumulate";
+    if (!c) return tensor_no_ctx(fn);
+    const std::string who = std::string(fn) + ": ";
+    if (!c->rank_active) return fail(c, DPMM_ESTATE, who + "needs dpmm_rank_begin first");
+    if (!c->predictive || c->K != c->rank_K) return fail(c, DPMM_ESTATE, who + "the predictive parameters changed since dpmm_rank_begin");
+    if (n_valid < 0 || n_valid > c->n) return fail(c, DPMM_EINVAL, who + "n_valid must be in 0..n_local");
+    if (index_base < 0 || index_base > ((int64_t)1 << 32) - n_valid) return fail(c, DPMM_EINVAL, who + "global indices must lie in 0..2^32 - 1");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (n_valid == 0) return DPMM_OK;
+    if (!c->have_points || !c->have_params) return fail(c, DPMM_ESTATE, who + "needs points and parameters");
+    if (c->rank_cap < std::min<int64_t>(RANK_CHUNK, c->n)) return fail(c, DPMM_ESTATE, who + "the context's points changed since dpmm_rank_begin");
+    int rstep = 0;
+    int64_t P = 0;
+    if (int rc = score_table_slab(c, &rstep, &P)) return rc;
+    const int K = c->K;
+    unsigned long long *keys = c->d_rank_state, *count = keys + rank_keys_words(K);
+    unsigned *cand_n = reinterpret_cast<unsigned *>(count + rank_count_words(K));
+    unsigned long long *cand_key = reinterpret_cast<unsigned long long *>(c->d_rank_cand);
+    uint16_t *cand_k = reinterpret_cast<uint16_t *>(cand_key + 2 * c->rank_cap);
+    for (int64_t p0 = 0; p0 < n_valid; p0 += P) {
+        const int64_t np = std::min<int64_t>(P, c->n - p0);              // the range dpmm_score_points evaluates
+        if (int rc = run_sweep(c, 0, 0, c->d_score_table, P, p0, np)) return rc;
+        const int64_t nv = std::min<int64_t>(np, n_valid - p0);          // what of it is ranked
+        for (int64_t q0 = 0; q0 < nv; q0 += c->rank_cap) {
+            RankArgs a{};
+            a.table = c->d_score_table + q0; a.stride = P; a.rstep = rstep; a.n = std::min<int64_t>(c->rank_cap, nv - q0); a.K = K;
+            a.index0 = index_base + p0 + q0; a.m = c->rank_m; a.which = c->rank_which;
+            a.keys = keys; a.count = count; a.cand_key = cand_key; a.cand_k = cand_k; a.cand_n = cand_n; a.cap = c->rank_cap; a.parity = c->rank_parity;
+            hipError_t e = launch_rank_chunk(a, c->stream);
+            if (e != hipSuccess) { c->err = who + hipGetErrorString(e); return DPMM_EHIP; }
+            c->rank_parity ^= 1;
+        }
+    }
+    return DPMM_OK;
+}
+
+static int rank_read(dpmm_ctx *c, const dpmm_rank_out *o, bool device, const char *fn) {
+    if (!c) return tensor_no_ctx(fn);
+    const std::string who = std::string(fn) + ": ";
+    if (!o) return fail(c, DPMM_EINVAL, who + "out is null");
+    if (!c->rank_active) return fail(c, DPMM_ESTATE, who + "needs dpmm_rank_begin first");
+    HIPCHK(c, hipSetDevice(c->device));
+    const int K = c->rank_K, m = c->rank_m;
+    const uint64_t km = (uint64_t)K * (uint64_t)m;
+    RankOut r{};
+    if (device) {
+        if (o->typ_idx) if (int rc = check_device_extent(c, fn, "typ_idx", o->typ_idx, sizeof(int64_t) * km, sizeof(int64_t))) return rc;
+        if (o->typ_score) if (int rc = check_device_extent(c, fn, "typ_score", o->typ_score, sizeof(float) * km, sizeof(float))) return rc;
+        if (o->fringe_idx) if (int rc = check_device_extent(c, fn, "fringe_idx", o->fringe_idx, sizeof(int64_t) * km, sizeof(int64_t))) return rc;
+        if (o->fringe_score) if (int rc = check_device_extent(c, fn, "fringe_score", o->fringe_score, sizeof(float) * km, sizeof(float))) return rc;
+        if (o->count) if (int rc = check_device_extent(c, fn, "count", o->count, sizeof(int64_t) * (uint64_t)K, sizeof(int64_t))) return rc;
+        if (o->skipped) if (int rc = check_device_extent(c, fn, "skipped", o->skipped, sizeof(int64_t), sizeof(int64_t))) return rc;
+        r = RankOut{o->typ_idx, o->typ_score, o->fringe_idx, o->fringe_score, o->count, o->skipped};
+    } else {      // the staging block dpmm_rank_begin sized: idx | idx | score | score | count | skipped, each 8-byte aligned
+        const size_t sb = ((size_t)km * sizeof(float) + 7) & ~(size_t)7;
+        char *p = c->d_rank_out;
+        r.typ_idx = reinterpret_cast<int64_t *>(p); p += km * sizeof(int64_t);
+        r.fringe_idx = reinterpret_cast<int64_t *>(p); p += km * sizeof(int64_t);
+        r.typ_score = reinterpret_cast<float *>(p); p += sb;
+        r.fringe_score = reinterpret_cast<float *>(p); p += sb;
+        r.count = reinterpret_cast<int64_t *>(p); p += (size_t)K * sizeof(int64_t);
+        r.skipped = reinterpret_cast<int64_t *>(p);
+    }
+    const unsigned long long *keys = c->d_rank_state, *count = keys + rank_keys_words(K);
+    hipError_t e = launch_rank_read(keys, count, K, m, c->rank_which, r, c->stream);
+    if (e == hipSuccess && !device) {
+        if (o->typ_idx) e = hipMemcpyAsync(o->typ_idx, r.typ_idx, sizeof(int64_t) * km, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess && o->fringe_idx) e = hipMemcpyAsync(o->fringe_idx, r.fringe_idx, sizeof(int64_t) * km, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess && o->typ_score) e = hipMemcpyAsync(o->typ_score, r.typ_score, sizeof(float) * km, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess && o->fringe_score) e = hipMemcpyAsync(o->fringe_score, r.fringe_score, sizeof(float) * km, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess && o->count) e = hipMemcpyAsync(o->count, r.count, sizeof(int64_t) * (size_t)K, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess && o->skipped) e = hipMemcpyAsync(o->skipped, r.skipped, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream);
+    }
+    if (e == hipSuccess) e = sync_stream(c, c->stream);
+    if (e != hipSuccess) { c->err = who + hipGetErrorString(e); return DPMM_EHIP; }
+    return DPMM_OK;
+}
+
+int dpmm_rank_read(dpmm_ctx *c, const dpmm_rank_out *out) { return rank_read(c, out, false, "dpmm_rank_read"); }
+int dpmm_rank_read_device(dpmm_ctx *c, const dpmm_rank_out *out) { return rank_read(c, out, true, "dpmm_rank_read_device"); }
 
 // ---- include/dpmm_hip_sample.h: drawing points from a fitted model (sample.hip) -------------------------------------------------------
 static int sampler_table(dpmm_ctx *c, void **dst, const void *src, size_t bytes) {

@@ -187,6 +187,30 @@ struct ScoreArgs {
     float *probs;
 };
 hipError_t launch_score_finish(const ScoreArgs &a, hipStream_t s);
+// ---- exemplars (rank.hip; include/dpmm_hip_rank.h): one chunk of at most `cap` points of a slab of the table, from table column 0, against
+// the running lists; then the lists decoded for the caller
+constexpr int RANK_SLOTS = 64;            // keys of a running list (DPMM_RANK_MAX_M), one per lane of the merging wave
+constexpr int RANK_REPL = 8;              // replicas of the counters [K + 1] (count | skipped); a workgroup adds to replica blockIdx % 8
+constexpr int64_t RANK_CHUNK = 262144;    // points per filter launch at most = entries of a candidate buffer
+struct RankArgs {
+    const float *table;
+    int64_t stride;      // floats between two rows of the table
+    int rstep;           // cluster k is row k * rstep
+    int64_t n;           // points of this chunk, n <= cap
+    int K;
+    int64_t index0;      // global index of the chunk's first point; index0 + n <= 2^32
+    int m, which;        // which bit 0: typical list, bit 1: fringe list
+    unsigned long long *keys;       // [2][K][RANK_SLOTS] the running lists, typical | fringe, largest key first, 0 = empty
+    unsigned long long *count;      // [RANK_REPL][K + 1]
+    unsigned long long *cand_key;   // [2][cap]
+    uint16_t *cand_k;               // [2][cap] 0-based cluster of the candidate
+    unsigned *cand_n;               // [2][2] candidates of (parity, list); the launch clears those of parity ^ 1
+    int64_t cap;
+    int parity;
+};
+struct RankOut { int64_t *typ_idx; float *typ_score; int64_t *fringe_idx; float *fringe_score; int64_t *count; int64_t *skipped; };      // = dpmm_rank_out
+hipError_t launch_rank_chunk(const RankArgs &a, hipStream_t s);
+hipError_t launch_rank_read(const unsigned long long *keys, const unsigned long long *count, int K, int m, int which, const RankOut &o, hipStream_t s);
 // ---- drawing points (sample.hip; include/dpmm_hip_sample.h): n samples from global index i0; every output pointer is that of the call's
 // first sample
 struct SampleArgs {

@@ -18,12 +18,19 @@ throughout (all counts, all bf16-exact, all other fractions) the two agree bit f
 bits can depend on `capacity`.  And on the byte path every upload re-allocates the worker's Float32 image (it is freed once the byte copy
 exists): the scoring calls allocate nothing, the uploads of count data do.
 """
+import collections
+
 import numpy as np
 
 from .. import binding
 from . import priors as _priors
 from . import sparse as _sparse
 from . import tensors as _tensors
+
+
+Exemplars = collections.namedtuple("Exemplars", "typical_idx typical_score fringe_idx fringe_score count skipped")
+Exemplars.__doc__ = """What `Predictor.exemplars` returns: typical_idx, typical_score, fringe_idx, fringe_score (K, m) -- a list that was not asked
+for is None -- count (K,) and skipped, an int."""
 
 
 class _Capture:
@@ -173,6 +180,44 @@ class Predictor:
         """(n,) float32: log of the mixture's posterior predictive density at every point."""
         return self._run(data, logdens=True)["logdens"]
 
+    # ---- exemplars (include/dpmm_hip_rank.h)
+    def exemplars(self, data, m, which="both"):
+        """The m most and the m least typical points of every cluster, selected on the GPU: an `Exemplars` tuple.
+
+        Every point is labelled as `predict_labels` labels it and scored by s = the log predictive density of its OWN cluster plus
+        log w_k (the largest entry of its row of the table `predict` normalises).  Points whose row holds a NaN or whose s is not finite
+        are counted in `skipped` and appear nowhere else.  For cluster k (row k of every array, k = 0 .. K-1, the cluster `predict`
+        calls k + 1):
+          typical_idx[k]   the m points of the cluster with the largest s, best first; typical_score[k] their s, non-increasing;
+          fringe_idx[k]    the m points with the smallest s, worst first; fringe_score[k] non-decreasing;
+          count[k]         the points of the cluster that take part.
+        Equal scores go to the lower index in both lists.  Slots j >= count[k] hold index -1 and score NaN.
+        Indices are 0-BASED positions along the Samples axis of `data` -- `data[:, idx]` are the points -- while labels are 1-based.
+        which: "typical", "fringe" or "both"; the list not asked for is None.  1 <= m <= binding.RANK_MAX_M.
+        `data` is what `predict` takes; for a device tensor the arrays are tensors on its device, else numpy arrays.  Nothing of size n
+        is allocated or copied to the host; the result does not depend on `capacity`."""
+        if self._wk is None:
+            raise RuntimeError("this Predictor is closed")
+        m = int(m)
+        if not 1 <= m <= binding.RANK_MAX_M:
+            raise ValueError(f"m must be in 1..{binding.RANK_MAX_M}")
+        mask = {"typical": binding.RANK_TYPICAL, "fringe": binding.RANK_FRINGE, "both": binding.RANK_TYPICAL | binding.RANK_FRINGE}.get(which)
+        if mask is None:
+            raise ValueError('which must be "typical", "fringe" or "both"')
+        wk, cap = self._wk, self.capacity
+        if not hasattr(wk, "rank_begin"):
+            raise RuntimeError("this Predictor's worker cannot rank points (no dpmm_rank_begin)")
+        n, dev, _, upload = self._open(data)
+        wk.rank_begin(m, mask)
+        for lo in range(0, n, cap):
+            hi = min(n, lo + cap)
+            upload(lo, hi)
+            wk.rank_accumulate(lo, hi - lo)
+        r = wk.rank_read(device=dev)
+        typ, fr = mask & binding.RANK_TYPICAL, mask & binding.RANK_FRINGE
+        return Exemplars(r["typ_idx"] if typ else None, r["typ_score"] if typ else None, r["fringe_idx"] if fr else None,
+                         r["fringe_score"] if fr else None, r["count"], int(r["skipped"][0]))
+
     # ---- drawing points (include/dpmm_hip_sample.h)
     def sampler_tables(self):
         """What the sampler uploads, formed in Float64: NIW ("niw", m (K, D), A (K, D, D) = sqrt(c) U, df (K,)) -- the posterior
@@ -278,7 +323,10 @@ class Predictor:
             spec.append(("probs", (self.K,), "float32"))
         return spec
 
-    def _run(self, data, labels=False, logdens=False, m=0, probs=False):
+    def _open(self, data):
+        """What every walk over `data` in slabs of `capacity` points needs: (n, dev, new, upload).  dev: the torch device of device data,
+        else None; new(rows, tail, dtype name): an empty result array / tensor where the results go; upload(lo, hi): the worker's points
+        become the points lo..hi-1, zero padded (empty columns for sparse data) to `capacity`."""
         if self._wk is None:
             raise RuntimeError("this Predictor is closed")
         wk, cap = self._wk, self.capacity
@@ -308,7 +356,6 @@ class Predictor:
             D, n = X.shape
         if D != self.D:
             raise ValueError("data dimension does not match the model")
-        spec = self._spec(labels, logdens, m, probs)
         if desc is not None or dcsc is not None:
             import torch
             dev = (desc or dcsc).torch_device
@@ -317,11 +364,9 @@ class Predictor:
         else:
             dev = None
             new = lambda rows, tail, dt: np.empty((rows,) + tail, dt)      # noqa: E731
-        out = {name: new(n, tail, dt) for name, tail, dt in spec}
-        for lo in range(0, n, cap):
-            hi = min(n, lo + cap)
+
+        def upload(lo, hi):
             full = hi - lo == cap
-            # -- the slab's points
             if dcsc is not None:
                 if full:                                                  # the slab's offsets where they are, the same entry arrays
                     cp_ptr = dcsc.colptr_ptr(lo)
@@ -364,6 +409,17 @@ class Predictor:
                     self._host_stage[:hi - lo] = X[:, lo:hi].T
                     self._host_stage[hi - lo:] = 0
                     wk.upload_points(self._host_stage)
+        return n, dev, new, upload
+
+    def _run(self, data, labels=False, logdens=False, m=0, probs=False):
+        n, dev, new, upload = self._open(data)
+        wk, cap = self._wk, self.capacity
+        spec = self._spec(labels, logdens, m, probs)
+        out = {name: new(n, tail, dt) for name, tail, dt in spec}
+        for lo in range(0, n, cap):
+            hi = min(n, lo + cap)
+            full = hi - lo == cap
+            upload(lo, hi)
             # -- its outputs: straight into the result for a full slab, through the staging outputs for the short one
             if full:
                 views = {name: out[name][lo:hi] for name, _, _ in spec}
@@ -392,6 +448,14 @@ def predict_topk(dp_model, data, m, **kw):
     """(labels, idx (n, m), probs (n, m)) of the m most probable clusters (opens a Predictor, runs, closes)."""
     with Predictor(dp_model, **kw) as p:
         return p.predict_topk(data, m)
+
+
+def exemplars(dp_model, data, m, **kw):
+    """The m most and least typical points of every cluster (opens a Predictor, runs, closes): see `Predictor.exemplars`;
+    kw: which, capacity, device, worker_factory."""
+    which = kw.pop("which", "both")
+    with Predictor(dp_model, **kw) as p:
+        return p.exemplars(data, m, which=which)
 
 
 def sample(dp_model, n, seed=0, trials=None, sparse=False, **kw):
