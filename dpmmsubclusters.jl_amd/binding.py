@@ -109,6 +109,14 @@ ABI_TENSOR = [
     ("dpmm_set_labels_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     ("dpmm_predict_points_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
 ]
+# include/dpmm_hip_project.h: wide points projected to the ctx's dimension while they are read (additive)
+_c_f64p_in = ctypes.POINTER(ctypes.c_double)
+ABI_PROJECT = [
+    ("dpmm_set_projection", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _c_f64p_in, _c_f64p_in]),
+    ("dpmm_upload_points_projected_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64]),
+    ("dpmm_upload_points_projected", ctypes.c_int, [ctypes.c_void_p, _c_f32p, ctypes.c_int64]),
+]
+MAX_DIM_PROJECT_IN = 4096      # DPMM_MAX_DIM_PROJECT_IN
 DT_F16, DT_BF16, DT_F32, DT_F64, DT_U8, DT_I16, DT_I32, DT_I64 = range(8)      # DPMM_DT_* (include/dpmm_hip_tensor.h)
 
 
@@ -228,7 +236,7 @@ def load_library():
         except Exception:  # pragma: no cover  (torch is optional for single-GPU use)
             pass
         lib = ctypes.CDLL(p)
-        for name, res, args in ABI + ABI_TENSOR + ABI_SCORE + ABI_RANK + ABI_CSC + ABI_SAMPLE:
+        for name, res, args in ABI + ABI_TENSOR + ABI_SCORE + ABI_RANK + ABI_CSC + ABI_SAMPLE + ABI_PROJECT:
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -364,6 +372,35 @@ class Worker:
         assert hi - lo == self.n and desc.D == self.D
         self.results_device = desc.torch_device            # labels and predictions follow the input, as for a dense tensor
         self.upload_points_csc_device(desc.colptr_ptr(lo), desc.index_dtype, desc.rowval_ptr, desc.nzval_ptr, desc.value_dtype, desc.nnz_extent, 0)
+
+    # ---- projection (include/dpmm_hip_project.h): points wider than D, projected while they are read
+    def set_projection(self, W, mu=None):
+        """W: (D_in, D) Float64, mu: (D_in,) or None.  Afterwards the projected uploads read D_in-wide points: y = (x - mu)' W."""
+        W = np.ascontiguousarray(W, dtype=np.float64)
+        assert W.ndim == 2 and W.shape[1] == self.D
+        mu = None if mu is None else np.ascontiguousarray(mu, dtype=np.float64)
+        assert mu is None or mu.shape == (W.shape[0],)
+        self._chk(self._lib.dpmm_set_projection(self._h, int(W.shape[0]), _p(W, _c_f64p_in), _p(mu, _c_f64p_in)))
+        self.D_in = int(W.shape[0])
+
+    def clear_projection(self):
+        self._chk(self._lib.dpmm_set_projection(self._h, 0, None, None))
+        self.D_in = 0
+
+    def upload_points_projected(self, X):
+        """X: (n_local, ld >= D_in) float32 C-contiguous host rows, row i = point i."""
+        X = _f32(X)
+        assert X.ndim == 2 and X.shape[0] == self.n
+        self._chk(self._lib.dpmm_upload_points_projected(self._h, _p(X, _c_f32p), X.shape[1]))
+
+    def upload_points_projected_strided_device(self, ptr, dtype, stride_point, stride_feature):
+        self._chk(self._lib.dpmm_upload_points_projected_device(self._h, ctypes.c_void_p(ptr), int(dtype), int(stride_point), int(stride_feature)))
+
+    def upload_points_projected_tensor(self, desc, lo, hi):
+        """The points [lo, hi) of a D_in-wide device tensor described by host/tensors.py, projected on the way in."""
+        assert hi - lo == self.n and desc.D == getattr(self, "D_in", 0)
+        self.results_device = desc.torch_device
+        self.upload_points_projected_strided_device(desc.shard_ptr(lo), desc.dtype, desc.stride_point, desc.stride_feature)
 
     def get_points_device(self, ptr, ld_out):
         self._chk(self._lib.dpmm_get_points_device(self._h, ctypes.c_void_p(ptr), int(ld_out)))

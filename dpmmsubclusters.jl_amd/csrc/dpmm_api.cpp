@@ -11,6 +11,7 @@
 #include "../../include/dpmm_hip_score.h"
 #include "../../include/dpmm_hip_rank.h"
 #include "../../include/dpmm_hip_sample.h"
+#include "../../include/dpmm_hip_project.h"
 
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -31,6 +32,7 @@
 #include <vector>
 
 #include "dpmm_kernels.h"
+#include "project_image.h"
 
 namespace dpmm {      // test hook in front of every kernel launch (dpmm_kernels.h DPMM_LAUNCH, dpmm_debug_set_prelaunch_hook)
 void (*g_prelaunch)(void *) = nullptr;
@@ -152,6 +154,11 @@ struct dpmm_ctx {
     int sm_K = 0;
     int64_t *d_sm_cstart = nullptr; int32_t *d_sm_tstart = nullptr; int sm_start_cap = 0;
     int32_t *d_sm_cnt = nullptr; int64_t *d_sm_bt = nullptr;
+    // projection (include/dpmm_hip_project.h): D_in (0: none), the plane image of W and -b as project.hip reads them, the host call's staging rows
+    int proj_Din = 0;
+    void *d_proj_W = nullptr;
+    float *d_proj_bias = nullptr;
+    float *d_proj_stage = nullptr; size_t proj_stage_bytes = 0;
 
     // sort + stats
     SortBufs sb{};
@@ -723,6 +730,7 @@ int dpmm_destroy(dpmm_ctx *c) {
     hipFree(c->d_rank_state); hipFree(c->d_rank_cand); hipFree(c->d_rank_out);
     hipFree(c->d_sm_m); hipFree(c->d_sm_At); hipFree(c->d_sm_df); hipFree(c->d_sm_thr); hipFree(c->d_sm_alias);
     hipFree(c->d_sm_cstart); hipFree(c->d_sm_tstart); hipFree(c->d_sm_cnt); hipFree(c->d_sm_bt);
+    hipFree(c->d_proj_W); hipFree(c->d_proj_bias); hipFree(c->d_proj_stage);
     for (int i = 0; i < 2; ++i) { hipFree(c->d_Y[i]); hipFree(c->d_ld_sigma[i]); hipFree(c->d_mu_draw[i]); }
     hipFree(c->ma.fac); hipFree(c->ma.mean); hipFree(c->ma.kap); hipFree(c->ma.nu); hipFree(c->ma.rows_store);
     if (c->stream2) { hipStreamSynchronize(c->stream2); hipStreamDestroy(c->stream2); }
@@ -3341,6 +3349,108 @@ int dpmm_upload_points_strided_device(dpmm_ctx *c, const void *d_src, int dtype,
     if (int rc = ensure_points_buffer(c)) return rc;
     if (c->n > 0) {
         HIPCHK(c, launch_ingest_strided(c->dX, c->ldx, d_src, dtype, stride_point, stride_feature, c->n, c->D, nan_to_zero, c->stream));
+        if (int rc = finish_upload(c)) return rc;
+    }
+    c->have_points = true;
+    c->cache_force = true;
+    c->rows_full_K = -1;
+    return DPMM_OK;
+}
+
+// ---- include/dpmm_hip_project.h: wide points projected to the ctx's dimension while they are read (project.hip) --------------------
+int dpmm_set_projection(dpmm_ctx *c, int D_in, const double *W, const double *mu) {
+    static const char *fn = "dpmm_set_projection";
+    if (!c) return tensor_no_ctx(fn);
+    if (c->prior != DPMM_PRIOR_NIW) return fail(c, DPMM_EINVAL, std::string(fn) + ": ctx is not a NIW context (projections are for the NIW prior only)");
+    if (D_in < 0) return fail(c, DPMM_EINVAL, std::string(fn) + ": D_in is negative");
+    if (D_in > DPMM_MAX_DIM_PROJECT_IN) return fail(c, DPMM_ELIMIT, std::string(fn) + ": D_in > DPMM_MAX_DIM_PROJECT_IN");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (D_in == 0) {
+        HIPCHK(c, sync_stream(c, c->stream));
+        hipFree(c->d_proj_W); hipFree(c->d_proj_bias);
+        c->d_proj_W = nullptr; c->d_proj_bias = nullptr; c->proj_Din = 0;
+        return DPMM_OK;
+    }
+    if (!W) return fail(c, DPMM_EINVAL, std::string(fn) + ": W is null");
+    std::vector<uint16_t> img;
+    std::vector<float> bias;
+    int64_t where = 0;
+    if (const int bad = proj_build_image(D_in, c->D, proj_njb(c->D), W, mu, img, bias, &where)) {
+        if (bad == 1) return fail(c, DPMM_EINVAL, std::string(fn) + ": W has a non-finite entry (or one beyond the Float32 / bf16 range) at [" + std::to_string(where / c->D) + "][" + std::to_string(where % c->D) + "]");
+        if (bad == 2) return fail(c, DPMM_EINVAL, std::string(fn) + ": mu has a non-finite entry at [" + std::to_string(where) + "]");
+        return fail(c, DPMM_EINVAL, std::string(fn) + ": mu' W overflows Float32 in column " + std::to_string(where));
+    }
+    void *dW = nullptr;
+    float *db = nullptr;
+    hipError_t e = hipMalloc(&dW, img.size() * sizeof(uint16_t));
+    if (e == hipSuccess) e = hipMalloc(&db, bias.size() * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpyAsync(dW, img.data(), img.size() * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(db, bias.data(), bias.size() * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = sync_stream(c, c->stream);
+    if (e != hipSuccess) { hipFree(dW); hipFree(db); return fail(c, DPMM_EHIP, std::string(fn) + ": " + hipGetErrorString(e)); }
+    hipFree(c->d_proj_W); hipFree(c->d_proj_bias);
+    c->d_proj_W = dW; c->d_proj_bias = db; c->proj_Din = D_in;
+    return DPMM_OK;
+}
+
+// the points in force become the projection of n_local points read from (device memory) src; everything was checked by the caller
+static int upload_projected(dpmm_ctx *c, const void *src, int dtype, int64_t sp, int64_t sf, int64_t r0, int64_t nr) {
+    HIPCHK(c, launch_project(c->dX + (size_t)r0 * c->ldx, c->ldx, c->D, src, dtype, sp, sf, nr, c->proj_Din, c->d_proj_W, c->d_proj_bias, c->stream));
+    return DPMM_OK;
+}
+
+int dpmm_upload_points_projected_device(dpmm_ctx *c, const void *d_src, int dtype, int64_t stride_point, int64_t stride_feature) {
+    static const char *fn = "dpmm_upload_points_projected_device";
+    if (!c) return tensor_no_ctx(fn);
+    if (c->prior != DPMM_PRIOR_NIW) return fail(c, DPMM_EINVAL, std::string(fn) + ": ctx is not a NIW context");
+    if (c->proj_Din <= 0) return fail(c, DPMM_EINVAL, std::string(fn) + ": ctx has no projection (dpmm_set_projection)");
+    const size_t es = ingest_elem_size(dtype);
+    if (es == 0) return fail(c, DPMM_EINVAL, std::string(fn) + ": dtype " + std::to_string(dtype) + " is not a DPMM_DT_* code");
+    if (stride_point < 0 || stride_feature < 0) return fail(c, DPMM_EINVAL, std::string(fn) + ": stride_point / stride_feature is negative");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (c->n > 0) {
+        uint64_t elems = 0;
+        if (!extent_elems(c->n, stride_point, c->proj_Din, stride_feature, &elems)) return fail(c, DPMM_EINVAL, std::string(fn) + ": the strides address more than 2^58 elements");
+        if (int rc = check_device_extent(c, fn, "d_src", d_src, elems * es, es)) return rc;
+    }
+    if (int rc = ensure_points_buffer(c)) return rc;
+    if (c->n > 0) {
+        if (int rc = upload_projected(c, d_src, dtype, stride_point, stride_feature, 0, c->n)) return rc;
+        if (int rc = finish_upload(c)) return rc;
+    }
+    c->have_points = true;
+    c->cache_force = true;
+    c->rows_full_K = -1;
+    return DPMM_OK;
+}
+
+int dpmm_upload_points_projected(dpmm_ctx *c, const float *h_src, int64_t ld_src) {
+    static const char *fn = "dpmm_upload_points_projected";
+    if (!c) return tensor_no_ctx(fn);
+    if (c->prior != DPMM_PRIOR_NIW) return fail(c, DPMM_EINVAL, std::string(fn) + ": ctx is not a NIW context");
+    if (c->proj_Din <= 0) return fail(c, DPMM_EINVAL, std::string(fn) + ": ctx has no projection (dpmm_set_projection)");
+    if (!h_src && c->n > 0) return fail(c, DPMM_EINVAL, std::string(fn) + ": h_src is null");
+    if (ld_src < c->proj_Din) return fail(c, DPMM_EINVAL, std::string(fn) + ": ld_src < D_in");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = ensure_points_buffer(c)) return rc;
+    if (c->n > 0) {
+        // compact rows [chunk][D_in] in one buffer of at most 64 MiB, kept for the next call
+        const size_t row_bytes = sizeof(float) * (size_t)c->proj_Din;
+        const int64_t chunk_rows = std::max<int64_t>(1, std::min<int64_t>(c->n, (int64_t)(((size_t)64 << 20) / row_bytes)));
+        const size_t need = row_bytes * (size_t)chunk_rows;
+        if (c->proj_stage_bytes < need) {
+            HIPCHK(c, sync_stream(c, c->stream));
+            hipFree(c->d_proj_stage); c->d_proj_stage = nullptr; c->proj_stage_bytes = 0;
+            HIPCHK(c, hipMalloc(&c->d_proj_stage, need));
+            c->proj_stage_bytes = need;
+        }
+        for (int64_t r0 = 0; r0 < c->n; r0 += chunk_rows) {
+            const int64_t nr = std::min(chunk_rows, c->n - r0);
+            HIPCHK(c, hipMemcpy2DAsync(c->d_proj_stage, row_bytes, h_src + (size_t)r0 * (size_t)ld_src, sizeof(float) * (size_t)ld_src, row_bytes, (size_t)nr,
+                                       hipMemcpyHostToDevice, c->stream));
+            if (int rc = upload_projected(c, c->d_proj_stage, DPMM_DT_F32, c->proj_Din, 1, r0, nr)) return rc;
+            HIPCHK(c, sync_stream(c, c->stream));          // the staging rows are reused by the next chunk
+        }
         if (int rc = finish_upload(c)) return rc;
     }
     c->have_points = true;

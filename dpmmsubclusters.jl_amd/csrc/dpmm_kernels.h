@@ -274,6 +274,15 @@ hipError_t launch_points_readback(float *out, int64_t ld_out, const float *X, in
                                   hipStream_t s);
 hipError_t launch_sparse_readback(float *out, int64_t ld_out, const int64_t *cp, const uint16_t *ri, const float *val, int64_t n, hipStream_t s);
 
+// ---- wide points projected to the ctx's dimension while they are read (project.hip; include/dpmm_hip_project.h)
+// Wimg: [ceil(D_in / 32)][proj_njb(D)][3 planes][64 lanes] 16-byte words -- lane l: the bf16 W[32 s + 8 (l >> 4) + e][16 jb + (l & 15)], e < 8, zero
+// outside [D_in][D]; bias: [16 proj_njb(D)] Float32, b[j] (+0 for j >= D).  Writes dst [n][ldx] whole; the source as launch_ingest_strided's.
+constexpr int PROJ_BLOCK = 256;
+int proj_njb(int D);               // blocks of 16 output columns a workgroup carries: 4, 8 or 16
+int proj_tile_points(int D);       // points per workgroup: 512, 256 or 128
+hipError_t launch_project(float *dst, int64_t ldx, int D, const void *src, int dtype, int64_t stride_point, int64_t stride_feature, int64_t n, int D_in,
+                          const void *Wimg, const float *bias, hipStream_t s);
+
 // ---- sparse points out of caller-owned device memory (csc_io.hip; include/dpmm_hip_csc.h)
 // cp: n + 1 ABSOLUTE offsets (minus base) into rv / nz, Int32 or Int64 as rv; nz of the DPMM_DT_* type value_dtype; extent: entries behind rv / nz.
 // bad[0] (preset to ~0): min over the offenders of point << 20 | (position in the column + 1) << 3 | reason

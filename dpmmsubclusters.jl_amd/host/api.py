@@ -30,6 +30,7 @@ from . import priors as _priors
 from . import checkpoint as _ckpt
 from . import sparse as _sparse
 from . import tensors as _tensors
+from . import project as _project
 from .priors import multinomial_hyper, niw_hyperparams
 from .sampler import DPMMSampler, LocalComm
 
@@ -43,6 +44,7 @@ class dp_parallel_sampling:
         self.model_hyperparams = dict(distribution_hyper_params=sampler.prior, alpha=sampler.alpha, total_dim=sampler.n_total)
         self.labels = labels
         self.labels_subcluster = sub_labels
+        self.projection = getattr(sampler, "projection", None)      # host/project.py: the model was fitted on projected coordinates
 
     @property
     def num_clusters(self):
@@ -56,10 +58,15 @@ def _shard(N, comm):
 
 
 def _make_sampler(all_data, hyper, alpha, seed, burnout, max_clusters, comm, device, nthreads=None, worker_factory=None,
-                  rows=None, **sampler_kw):
+                  rows=None, projection=None, **sampler_kw):
     """`all_data`: Dimensions x Samples (basic mode), or `rows`: Samples x Dimensions as stored in a .npy file (advanced
     mode; cleaned and converted on the GPU by dpmm_upload_points_npy)."""
     csc = None if rows is not None else _sparse.as_csc(all_data)
+    if projection is not None:
+        if hyper.kind != _priors.PRIOR_NIW:
+            raise TypeError("project= is for the Gaussian (niw_hyperparams) prior only")
+        if csc is not None or rows is not None:
+            raise TypeError("project= takes dense data (an array or a tensor), Dimensions x Samples")
     desc = None if rows is not None or csc is not None else _tensors.as_device_points(all_data)
     if rows is not None:
         N, D = rows.shape
@@ -74,6 +81,10 @@ def _make_sampler(all_data, hyper, alpha, seed, burnout, max_clusters, comm, dev
         if X.ndim != 2:
             raise ValueError("all_data must be Dimensions x Samples")
         D, N = X.shape
+    if projection is not None:
+        if D != projection.D_in:
+            raise ValueError(f"data dimension {D} != the projection's input dimension {projection.D_in}")
+        D = projection.d                               # the worker, the prior and everything downstream live in the projected space
     if hyper.dim != D:
         raise ValueError(f"prior dimension {hyper.dim} != data dimension {D}")
     lo, hi = _shard(N, comm)
@@ -82,7 +93,16 @@ def _make_sampler(all_data, hyper, alpha, seed, burnout, max_clusters, comm, dev
         seed = comm.broadcast_int(seed) if hasattr(comm, "broadcast_int") else seed
     kw = dict(timing=False) if worker_factory is None else {}      # the product path records no timing events (~5 us each, four per step)
     wk = (worker_factory or binding.Worker)(hyper.kind, D, hi - lo, first_index=lo, device=device, seed=int(seed), **kw)
-    if rows is not None:
+    if projection is not None:
+        projection.apply(wk)
+        if desc is not None and hasattr(wk, "upload_points_projected_tensor"):
+            desc.synchronize()
+            wk.upload_points_projected_tensor(desc, lo, hi)
+        elif desc is not None:
+            wk.upload_points_projected(np.ascontiguousarray(desc.tensor[:, lo:hi].T.float().cpu().numpy()))
+        else:
+            wk.upload_points_projected(np.ascontiguousarray(X[:, lo:hi].T, dtype=np.float32))
+    elif rows is not None:
         if hasattr(wk, "upload_points_npy"):
             wk.upload_points_npy(rows[lo:hi])
         else:
@@ -102,6 +122,7 @@ def _make_sampler(all_data, hyper, alpha, seed, burnout, max_clusters, comm, dev
     if desc is None and isinstance(csc, _sparse.DeviceCSC):
         desc = csc                                     # (a sparse tensor in device memory: the same three attributes are read of it)
     s.data_tensor = desc                               # results follow the input (_final_labels)
+    s.projection = projection
     return s
 
 
@@ -155,21 +176,28 @@ def _comm_device(comm, device):
 def dp_parallel(all_data, local_hyper_params=None, alpha_param=None, iters=100, init_clusters=1, seed=None, verbose=True,
                 save_model=False, burnout=15, gt=None, max_clusters=np.inf, outlier_weight=0, outlier_params=None,
                 smart_splits=False, comm=None, device=None, nthreads=None, worker_factory=None, save_path="./",
-                save_file_prefix="checkpoint_", model_save_interval=1000):
+                save_file_prefix="checkpoint_", model_save_interval=1000, project=None):
     """dp_parallel(all_data, hyper_params, alpha, ...) -- basic mode (dp-parallel-sampling.jl:121-157), or
     dp_parallel(model_params::String; verbose, gt) -- advanced mode driven by a parameter file (:178-196).
     Returns (dp_model, iter_count, nmi_score_history, likelihood_history, cluster_count_history).
-    `save_model=True` writes a checkpoint every `model_save_interval` iterations (global_params.jl:36-41 defaults)."""
+    `save_model=True` writes a checkpoint every `model_save_interval` iterations (global_params.jl:36-41 defaults).
+    `project`: a host/project.py Projection, or an int d (= fit_projection(all_data, d, seed=seed or 0); one rank only): `all_data` then
+    has D_in rows, the prior dimension d, and the GPU projects the points while it reads them (Gaussian prior, dense data)."""
     if isinstance(all_data, (str, bytes)) or hasattr(all_data, "__fspath__"):
+        if project is not None:
+            raise TypeError("project= is for the basic mode (arrays and tensors), not for a parameter file")
         return _dp_parallel_from_params(str(all_data), verbose=verbose, gt=gt, comm=comm, device=device, nthreads=nthreads,
                                         worker_factory=worker_factory)
     if not isinstance(local_hyper_params, _priors.distribution_hyper_params):
         raise TypeError("local_hyper_params must be a distribution_hyper_params (niw_hyperparams / multinomial_hyper)")
     _check_next_rows(outlier_weight, outlier_params, smart_splits, local_hyper_params)
+    if project is not None and local_hyper_params.kind != _priors.PRIOR_NIW:
+        raise TypeError("project= is for the Gaussian (niw_hyperparams) prior only")
     comm, device = _comm_device(comm, _data_device(all_data, device))
     gt = _tensors.host_int64(gt)
+    project = _project.resolve(project, all_data, seed, comm)
     s = _make_sampler(all_data, local_hyper_params, np.float32(alpha_param), seed, int(burnout), max_clusters, comm, device,
-                      nthreads, worker_factory)
+                      nthreads, worker_factory, projection=project)
     s.smart_splits = bool(smart_splits)
     if outlier_weight and outlier_weight > 0:
         s.outlier_weight, s.outlier_prior = float(outlier_weight), outlier_params
@@ -236,15 +264,17 @@ def run_model_from_checkpoint(filename, verbose=True, gt=None, comm=None, device
 
 def resume_from_checkpoint(filename, all_data, iters, verbose=True, gt=None, burnout=None, max_clusters=np.inf, comm=None,
                            device=None, nthreads=None, worker_factory=None, save_model=False, save_path="./",
-                           save_file_prefix="checkpoint_", model_save_interval=1000):
+                           save_file_prefix="checkpoint_", model_save_interval=1000, project=None):
     """Basic-mode counterpart of run_model_from_checkpoint: the caller supplies the data array again (D x N) and the
-    total number of iterations; the chain continues at iter+1 exactly where the checkpoint left it."""
+    total number of iterations; the chain continues at iter+1 exactly where the checkpoint left it.  A model fitted with `project`
+    is given the same projection again (the checkpoint file does not hold it)."""
     ck = _ckpt.load_checkpoint(filename)
     comm, device = _comm_device(comm, _data_device(all_data, device))
     gt = _tensors.host_int64(gt)
     hyper = _ckpt._prior_from_dict(ck)
+    project = _project.resolve(project, all_data, int(ck["seed"]), comm)
     s = _make_sampler(all_data, hyper, np.float32(ck["alpha"]), int(ck["seed"]), int(ck["burnout"] if burnout is None else burnout),
-                      max_clusters, comm, device, nthreads, worker_factory)
+                      max_clusters, comm, device, nthreads, worker_factory, projection=project)
     _ckpt.restore_sampler(s, ck)
     hook = _ckpt.SaveHook(save_path, save_file_prefix, model_save_interval, "none", float(ck["total_time"]), verbose) if save_model else None
     iter_count, nmi, lik, kh = s.run_model(int(iters), int(ck["iter"]) + 1, verbose=verbose, gt=gt, on_iteration=hook)
@@ -264,6 +294,13 @@ def fit(all_data, *args, iters=100, init_clusters=1, seed=None, verbose=True, sa
         if _sparse.as_csc(all_data) is not None:
             raise TypeError("sparse data is for the Multinomial prior: fit(all_data, multinomial_hyper(...), alpha)")
         D = all_data.shape[0] if _tensors.is_tensor(all_data) else np.asarray(all_data).shape[0]
+        project = kw.get("project")
+        if project is not None:                   # the default prior is built for the projected space
+            if isinstance(project, _project.Projection):
+                D = project.d
+            else:
+                _project._check_dims(D, project)
+                D = int(project)
         hyper = niw_hyperparams(1.0, np.zeros(D), D + 3, np.eye(D))   # dp-parallel-sampling.jl:272-274
         alpha = args[0]
     elif len(args) == 2:
@@ -291,6 +328,7 @@ def predict(dp_model, data, device=None, worker_factory=None):
     desc = None if csc is not None else _tensors.as_device_points(data)
     if desc is not None and not hasattr(worker_factory or binding.Worker, "upload_points_tensor"):
         data, desc = desc.tensor.float().cpu().numpy(), None          # (a stand-in worker without the device entry points)
+    proj = getattr(dp_model, "projection", None)
     if csc is not None:
         if s.prior.kind != _priors.PRIOR_MULT:
             raise TypeError("sparse data is for the Multinomial prior")
@@ -303,6 +341,9 @@ def predict(dp_model, data, device=None, worker_factory=None):
     else:
         X = np.ascontiguousarray(np.asarray(_tensors.as_host_array(data), dtype=np.float32).T)
         n, D = X.shape
+    proj = proj if proj is not None and csc is None and D == proj.D_in else None      # d-row data is taken as already projected
+    if proj is not None:
+        D = proj.d
     if D != s.prior.dim:
         raise ValueError("data dimension does not match the model")
     w = s.points_count.astype(np.float64) + s.alpha
@@ -310,7 +351,16 @@ def predict(dp_model, data, device=None, worker_factory=None):
     dev = getattr(s.wk, "device", 0) if device is None else device
     wk = (worker_factory or binding.Worker)(s.prior.kind, D, n, first_index=0, device=dev, seed=0)
     try:
-        if csc is not None:
+        if proj is not None:
+            proj.apply(wk)
+            if desc is not None and hasattr(wk, "upload_points_projected_tensor"):
+                desc.synchronize()
+                wk.upload_points_projected_tensor(desc, 0, n)
+            elif desc is not None:
+                wk.upload_points_projected(np.ascontiguousarray(desc.tensor.T.float().cpu().numpy()))
+            else:
+                wk.upload_points_projected(X)
+        elif csc is not None:
             _sparse.upload_columns(wk, csc, 0, n)
         elif desc is not None:
             desc.synchronize()

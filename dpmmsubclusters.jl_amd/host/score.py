@@ -26,6 +26,7 @@ from .. import binding
 from . import priors as _priors
 from . import sparse as _sparse
 from . import tensors as _tensors
+from . import project as _project
 
 
 Exemplars = collections.namedtuple("Exemplars", "typical_idx typical_score fringe_idx fringe_score count skipped")
@@ -91,9 +92,11 @@ class Predictor:
         post = {k: np.asarray(v)[rows] for k, v in s.post.items()}
         if device is None:
             device = getattr(getattr(s, "wk", None), "device", 0)
-        self._setup(s.prior.kind, s.prior.dim, s.alpha, np.asarray(s.points_count), post, capacity, device, worker_factory)
+        self._setup(s.prior.kind, s.prior.dim, s.alpha, np.asarray(s.points_count), post, capacity, device, worker_factory,
+                    projection=getattr(dp_model, "projection", None))
 
-    def _setup(self, kind, D, alpha, points_count, post, capacity, device, worker_factory):
+    def _setup(self, kind, D, alpha, points_count, post, capacity, device, worker_factory, projection=None):
+        self.projection = projection     # host/project.py: D_in-row data is projected on the way in (the worker holds the map)
         self.kind, self.D, self.alpha = int(kind), int(D), float(alpha)
         self.points_count = np.asarray(points_count, np.float64).copy()
         self.post = {k: np.array(v) for k, v in post.items()}
@@ -115,11 +118,14 @@ class Predictor:
         try:
             which, args = cap.args
             (self._wk.set_predictive_niw if which == "niw" else self._wk.set_predictive_mult)(*args)      # ONCE
+            if projection is not None:
+                projection.apply(self._wk)                                                                # ... as well
         except Exception:
             self._wk.close()
             self._wk = None
             raise
         self._host_stage = None          # (capacity, D) float32, the short slab of host data
+        self._host_stage_in = self._dev_stage_in = None      # the same, D_in wide, for data that is projected on the way in
         self._dev_stage = None           # the same on the device, for the short slab of a device tensor
         self._csc_stage = None           # capacity + 1 offsets on the device, for the short slab of a sparse_csc tensor
         self._out_stage = {}             # outputs of a short slab: name -> array / tensor of `capacity` rows
@@ -130,7 +136,7 @@ class Predictor:
         if getattr(self, "_wk", None) is not None:
             self._wk.close()
             self._wk = None
-        self._host_stage = self._dev_stage = self._csc_stage = None
+        self._host_stage = self._dev_stage = self._csc_stage = self._host_stage_in = self._dev_stage_in = None
         self._out_stage = {}
 
     def __enter__(self):
@@ -147,16 +153,17 @@ class Predictor:
 
     # ---- a model to serve, without the training data or the sampler
     def save(self, path):
-        """One .npz: prior kind, D, alpha, points_count and the posterior arrays of the K clusters."""
+        """One .npz: prior kind, D, alpha, points_count, the posterior arrays of the K clusters and the projection, if the model has one."""
         np.savez(path, kind=np.int64(self.kind), D=np.int64(self.D), alpha=np.float64(self.alpha), points_count=self.points_count,
-                 **{"post_" + k: v for k, v in self.post.items()})
+                 **{"post_" + k: v for k, v in self.post.items()}, **(self.projection.arrays("proj_") if self.projection is not None else {}))
 
     @classmethod
     def load(cls, path, device=None, capacity=65536, worker_factory=None):
         with np.load(path) as z:
             post = {k[5:]: z[k] for k in z.files if k.startswith("post_")}
             self = cls.__new__(cls)
-            self._setup(int(z["kind"]), int(z["D"]), float(z["alpha"]), z["points_count"], post, capacity, 0 if device is None else device, worker_factory)
+            self._setup(int(z["kind"]), int(z["D"]), float(z["alpha"]), z["points_count"], post, capacity, 0 if device is None else device, worker_factory,
+                        projection=_project.Projection.from_arrays(z, "proj_"))
         return self
 
     # ---- the public methods
@@ -248,7 +255,8 @@ class Predictor:
         NIW: the posterior predictive Student-t that `predict` scores with.  Multinomial: Multinomial(trials, alpha' / sum(alpha')) -- `trials`
         per point is required (and refused for NIW); sparse=True allows at most binding.SAMPLE_MAX_TRIALS_SPARSE trials.
         Point i depends on (seed, i, its cluster, the model) only: the same seed gives the same bits whatever `capacity` is, and a
-        Predictor restored by `load` draws what the saved one drew."""
+        Predictor restored by `load` draws what the saved one drew.  A model fitted with a projection draws in the PROJECTED space: the
+        points have d rows, the coordinates `Projection.transform` gives, not the D_in of the original data."""
         if self._wk is None:
             raise RuntimeError("this Predictor is closed")
         n, seed = int(n), int(seed)
@@ -354,8 +362,12 @@ class Predictor:
             if X.ndim != 2:
                 raise ValueError("data must be 2-D, Dimensions x Samples")
             D, n = X.shape
-        if D != self.D:
+        proj = self.projection if self.projection is not None and csc is None and D == self.projection.D_in else None
+        if proj is None and D != self.D:               # (d-row data is taken as already projected)
             raise ValueError("data dimension does not match the model")
+        if proj is not None and desc is not None and not hasattr(wk, "upload_points_projected_strided_device"):
+            data, desc = desc.tensor.float().cpu().numpy(), None
+            X = np.asarray(data)
         if desc is not None or dcsc is not None:
             import torch
             dev = (desc or dcsc).torch_device
@@ -364,6 +376,28 @@ class Predictor:
         else:
             dev = None
             new = lambda rows, tail, dt: np.empty((rows,) + tail, dt)      # noqa: E731
+
+        def upload_projected(lo, hi):                  # as the branches below, D_in wide, through the projected calls
+            full = hi - lo == cap
+            if desc is not None:
+                if full:
+                    wk.upload_points_projected_strided_device(desc.shard_ptr(lo), desc.dtype, desc.stride_point, desc.stride_feature)
+                else:
+                    st = self._dev_stage_in
+                    if st is None or st.device != dev:
+                        st = self._dev_stage_in = torch.zeros((cap, D), dtype=torch.float32, device=dev)
+                    st[:hi - lo].copy_(desc.tensor[:, lo:hi].T)
+                    st[hi - lo:].zero_()
+                    torch.cuda.current_stream(dev).synchronize()
+                    wk.upload_points_projected_strided_device(st.data_ptr(), _tensors.DT_F32, D, 1)
+            elif full:
+                wk.upload_points_projected(np.ascontiguousarray(X[:, lo:hi].T, dtype=np.float32))
+            else:
+                if self._host_stage_in is None:
+                    self._host_stage_in = np.zeros((cap, D), np.float32)
+                self._host_stage_in[:hi - lo] = X[:, lo:hi].T
+                self._host_stage_in[hi - lo:] = 0
+                wk.upload_points_projected(self._host_stage_in)
 
         def upload(lo, hi):
             full = hi - lo == cap
@@ -409,7 +443,7 @@ class Predictor:
                     self._host_stage[:hi - lo] = X[:, lo:hi].T
                     self._host_stage[hi - lo:] = 0
                     wk.upload_points(self._host_stage)
-        return n, dev, new, upload
+        return n, dev, new, (upload_projected if proj is not None else upload)
 
     def _run(self, data, labels=False, logdens=False, m=0, probs=False):
         n, dev, new, upload = self._open(data)
