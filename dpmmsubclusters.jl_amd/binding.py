@@ -172,6 +172,14 @@ SAMPLE_MAX_TRIALS_SPARSE = 4096        # DPMM_SAMPLE_MAX_TRIALS_SPARSE
 SAMPLE_MAX_TRIALS_DENSE = 1 << 24      # DPMM_SAMPLE_MAX_TRIALS_DENSE
 OPT_SCORE_TABLE_MB = 32      # DPMM_OPT_SCORE_TABLE_MB
 SCORE_MAX_TOP = 16           # DPMM_SCORE_MAX_TOP
+# include/dpmm_hip_missing.h: points with missing (NaN) features, marginalised and imputed (additive; bound next to ABI)
+ABI_MISSING = [
+    ("dpmm_score_missing_counts", ctypes.c_int, [ctypes.c_void_p, _c_i64p]),
+    ("dpmm_impute_points", ctypes.c_int, [ctypes.c_void_p, _c_f32p, ctypes.c_int64]),
+    ("dpmm_impute_points_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]),
+]
+OPT_SCORE_MISSING = 33       # DPMM_OPT_SCORE_MISSING
+SCORE_MAX_MISSING = 16       # DPMM_SCORE_MAX_MISSING
 
 HOST_ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int)   # dpmm_host_allreduce_fn
 
@@ -236,7 +244,7 @@ def load_library():
         except Exception:  # pragma: no cover  (torch is optional for single-GPU use)
             pass
         lib = ctypes.CDLL(p)
-        for name, res, args in ABI + ABI_TENSOR + ABI_SCORE + ABI_RANK + ABI_CSC + ABI_SAMPLE + ABI_PROJECT:
+        for name, res, args in ABI + ABI_TENSOR + ABI_SCORE + ABI_RANK + ABI_MISSING + ABI_CSC + ABI_SAMPLE + ABI_PROJECT:
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -611,6 +619,29 @@ class Worker:
         if n > 0:
             self.score_points_into(res, m=m)
         return res
+
+    # ---- missing features (include/dpmm_hip_missing.h)
+    def score_missing_counts(self):
+        """dpmm_score_missing_counts: (marginalised, over the cap) among the points the last score / rank / impute call evaluated."""
+        out = np.zeros(2, np.int64)
+        self._chk(self._lib.dpmm_score_missing_counts(self._h, _p(out, _c_i64p)))
+        return int(out[0]), int(out[1])
+
+    def impute_points_into(self, out):
+        """dpmm_impute_points[_device] into storage the caller made: a C-contiguous (n, ld >= D) float32 numpy array (host variant) or
+        torch tensor on this worker's GPU (device variant)."""
+        dev = hasattr(out, "data_ptr")
+        assert tuple(out.shape)[0] == self.n and out.shape[1] >= self.D and (out.is_contiguous() if dev else out.flags.c_contiguous)
+        if self.n == 0:
+            return
+        if dev:
+            import torch
+            assert out.dtype == torch.float32
+            torch.cuda.current_stream(out.device).synchronize()
+            self._chk(self._lib.dpmm_impute_points_device(self._h, ctypes.c_void_p(out.data_ptr()), int(out.shape[1])))
+        else:
+            assert out.dtype == np.float32
+            self._chk(self._lib.dpmm_impute_points(self._h, _p(out, _c_f32p), int(out.shape[1])))
 
     # ---- exemplars (include/dpmm_hip_rank.h)
     def rank_begin(self, m, which=RANK_TYPICAL | RANK_FRINGE):

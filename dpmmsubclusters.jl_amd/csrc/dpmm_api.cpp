@@ -10,6 +10,7 @@
 #include "../../include/dpmm_hip_csc.h"
 #include "../../include/dpmm_hip_score.h"
 #include "../../include/dpmm_hip_rank.h"
+#include "../../include/dpmm_hip_missing.h"
 #include "../../include/dpmm_hip_sample.h"
 #include "../../include/dpmm_hip_project.h"
 
@@ -146,6 +147,17 @@ struct dpmm_ctx {
     bool rank_active = false;
     int rank_m = 0, rank_which = 0, rank_K = 0, rank_parity = 0;
     int64_t rank_cap = 0;
+    // missing features (include/dpmm_hip_missing.h): the constants of the marginals on the host (formed by dpmm_set_predictive_niw); on the
+    // device, allocated by the first call that marginalises: their copy, the transposed factors, a range's list and the three counters
+    int opt_score_missing = 0;         // DPMM_OPT_SCORE_MISSING
+    std::vector<double> h_miss_cst;    // [K][MISS_CST]
+    int miss_slots = 0;                // slots of the parameter staging when the predictive parameters were committed (their layout in d_par)
+    unsigned long long pred_gen = 0, miss_gen = 0;      // parameter set in force / the one the device copies were made from (0: none)
+    float *d_miss_rt = nullptr; size_t miss_rt_bytes = 0;
+    double *d_miss_cst = nullptr; size_t miss_cst_bytes = 0;
+    uint32_t *d_miss_list = nullptr; size_t miss_list_bytes = 0;
+    unsigned long long *d_miss_cnt = nullptr; size_t miss_cnt_bytes = 0;
+    bool miss_counted = false;         // the last table call marginalised: the counters hold its counts
     // drawing points (include/dpmm_hip_sample.h): the sampler's tables (dpmm_set_sampler_*) and what a call needs beside its outputs
     // (cluster and tile starts; sparse: 4 bytes per point of counts and the scan's tile totals), allocated on first use
     float *d_sm_m = nullptr, *d_sm_At = nullptr, *d_sm_df = nullptr;
@@ -728,6 +740,7 @@ int dpmm_destroy(dpmm_ctx *c) {
     hipFree(c->d_m0); hipFree(c->d_psi_lo); hipFree(c->d_pairs);
     hipFree(c->d_score_table); hipFree(c->d_score_out);
     hipFree(c->d_rank_state); hipFree(c->d_rank_cand); hipFree(c->d_rank_out);
+    hipFree(c->d_miss_rt); hipFree(c->d_miss_cst); hipFree(c->d_miss_list); hipFree(c->d_miss_cnt);
     hipFree(c->d_sm_m); hipFree(c->d_sm_At); hipFree(c->d_sm_df); hipFree(c->d_sm_thr); hipFree(c->d_sm_alias);
     hipFree(c->d_sm_cstart); hipFree(c->d_sm_tstart); hipFree(c->d_sm_cnt); hipFree(c->d_sm_bt);
     hipFree(c->d_proj_W); hipFree(c->d_proj_bias); hipFree(c->d_proj_stage);
@@ -1531,6 +1544,20 @@ int dpmm_set_predictive_niw(dpmm_ctx *c, int K, const float *m, const float *R, 
     HIPCHK(c, launch_copy_bytes(c->d_tdf, c->h_pin + sizeof(float) * 3 * K, sizeof(float) * 6 * K, c->stream));
     HIPCHK(c, sync_stream(c, c->stream));
     c->predictive = true;
+    // include/dpmm_hip_missing.h: the constant of the marginal over D - r features, r = 1 .. DPMM_SCORE_MAX_MISSING (host memory only: the device
+    // copies are made by the first call that marginalises)
+    c->h_miss_cst.assign((size_t)K * MISS_CST, 0.0);
+    for (int k = 0; k < K; ++k) {
+        const double v = df[k];
+        double *ck = &c->h_miss_cst[(size_t)k * MISS_CST];
+        ck[0] = v;
+        for (int r = 1; r <= MISS_MAX && r < (int)D; ++r) {
+            const double Do = (double)((int)D - r);
+            ck[r] = lgamma(0.5 * (v + Do)) - lgamma(0.5 * v) - 0.5 * Do * log(v * M_PI) - 0.5 * logdet[k] + log((double)w[k]);
+        }
+    }
+    c->miss_slots = c->par_slots;
+    c->pred_gen += 1;
     return DPMM_OK;
 }
 
@@ -2962,6 +2989,9 @@ int dpmm_set_option(dpmm_ctx *c, int option, double value) {
             if (c->have_points) return fail(c, DPMM_ESTATE, "DPMM_OPT_MULT_NO_U8 must be set before the points are uploaded");
             c->opt_no_u8 = value != 0; return DPMM_OK;
         case DPMM_OPT_SCORE_TABLE_MB: c->opt_score_mb = (value < 0 || value != value) ? 128.0 : value; return DPMM_OK;
+        case DPMM_OPT_SCORE_MISSING:
+            if (value != 0 && c->prior != DPMM_PRIOR_NIW) return fail(c, DPMM_EINVAL, "DPMM_OPT_SCORE_MISSING: the Multinomial prior has no missing features");
+            c->opt_score_missing = value != 0; return DPMM_OK;
         default: return fail(c, DPMM_EINVAL, "unknown option");
     }
 }
@@ -3652,8 +3682,54 @@ static int score_table_slab(dpmm_ctx *c, int *rstep_out, int64_t *P_out) {
     return ensure_score_buffer(c, reinterpret_cast<void **>(&c->d_score_table), &c->score_table_bytes, sizeof(float) * rows * (size_t)P, "table");
 }
 
+
+// ---- include/dpmm_hip_missing.h: the marginal entries of points with NaN features, range by range (missing.hip) ---------------------------
+// Called once per table call, behind score_table_slab.  on: the call marginalises -- the device buffers exist afterwards (the list sized for
+// one range of P points), the copies of the parameters are those of the predictive set in force, the per-call counters are cleared.
+static int miss_begin(dpmm_ctx *c, bool on, int64_t P, const char *fn) {
+    c->miss_counted = false;
+    if (!on) return DPMM_OK;
+    const std::string who = std::string(fn) + ": ";
+    if (c->prior != DPMM_PRIOR_NIW || c->h_miss_cst.size() != (size_t)c->K * MISS_CST || !c->d_par)
+        return fail(c, DPMM_ESTATE, who + "missing features need dpmm_set_predictive_niw");
+    const size_t K = (size_t)c->K, D = (size_t)c->D;
+    if (int rc = ensure_score_buffer(c, reinterpret_cast<void **>(&c->d_miss_cnt), &c->miss_cnt_bytes, 3 * sizeof(unsigned long long), "counters of the missing-feature pass")) return rc;
+    if (int rc = ensure_score_buffer(c, reinterpret_cast<void **>(&c->d_miss_list), &c->miss_list_bytes, sizeof(uint32_t) * (size_t)P, "list of the missing-feature pass")) return rc;
+    if (c->miss_gen != c->pred_gen) {
+        if (int rc = ensure_score_buffer(c, reinterpret_cast<void **>(&c->d_miss_rt), &c->miss_rt_bytes, sizeof(float) * K * D * (size_t)miss_pitch(c->D), "transposed factors of the missing-feature pass")) return rc;
+        if (int rc = ensure_score_buffer(c, reinterpret_cast<void **>(&c->d_miss_cst), &c->miss_cst_bytes, sizeof(double) * K * MISS_CST, "constants of the missing-feature pass")) return rc;
+        HIPCHK(c, sync_stream(c, c->stream));
+        HIPCHK(c, hipMemcpy(c->d_miss_cst, c->h_miss_cst.data(), sizeof(double) * K * MISS_CST, hipMemcpyHostToDevice));
+        const ParLayout L = par_layout(c, c->miss_slots);
+        const float *Rpk = reinterpret_cast<const float *>(c->d_par + (L.mat - L.cst));      // cluster k: row 3k of the staging image (identity slot map)
+        HIPCHK(c, launch_miss_transpose(Rpk, 3 * (int64_t)(D * (D + 1) / 2), c->d_miss_rt, c->K, c->D, c->stream));
+        c->miss_gen = c->pred_gen;
+    }
+    HIPCHK(c, hipMemsetAsync(c->d_miss_cnt, 0, 3 * sizeof(unsigned long long), c->stream));
+    c->miss_counted = true;
+    return DPMM_OK;
+}
+
+// One range of the table (np points from point p0, rows P floats apart), just evaluated on the ctx stream: list, then patch.  out != null
+// (rows of the range's points, ld floats apart): the imputation behind them.
+static int miss_range(dpmm_ctx *c, int64_t P, int64_t p0, int64_t np, float *out, int64_t ld, const char *fn) {
+    const ParLayout L = par_layout(c, c->miss_slots);
+    MissArgs a{};
+    a.table = c->d_score_table; a.stride = P; a.n = np; a.K = c->K; a.D = c->D;
+    a.X = c->dX + p0 * c->ldx; a.ldx = c->ldx;
+    a.Rt = c->d_miss_rt; a.mu = reinterpret_cast<const float *>(c->d_par + (L.mu - L.cst)); a.mu_step = 3 * (int64_t)c->D;
+    a.cst = c->d_miss_cst; a.list = c->d_miss_list; a.cnt = c->d_miss_cnt; a.out = out; a.ld_out = ld;
+    hipError_t e = hipMemsetAsync(c->d_miss_cnt, 0, sizeof(unsigned long long), c->stream);
+    if (e == hipSuccess) e = launch_miss_list(a, c->stream);
+    if (e == hipSuccess) e = launch_miss_patch(a, false, 8 * c->cus, c->stream);
+    if (e == hipSuccess && out) e = launch_miss_patch(a, true, 8 * c->cus, c->stream);
+    if (e != hipSuccess) { c->err = std::string(fn) + ": " + hipGetErrorString(e); return DPMM_EHIP; }
+    return DPMM_OK;
+}
+
 static int score_points(dpmm_ctx *c, const dpmm_score_out *o, bool device, const char *fn) {
     if (!c) return tensor_no_ctx(fn);
+    c->miss_counted = false;      // (dpmm_score_missing_counts speaks of THIS call from here on, also where it returns early)
     const std::string who = std::string(fn) + ": ";
     if (!o) return fail(c, DPMM_EINVAL, who + "out is null");
     if (o->m < 0 || o->m > DPMM_SCORE_MAX_TOP) return fail(c, DPMM_EINVAL, who + "m must be in 0.." + std::to_string(DPMM_SCORE_MAX_TOP));
@@ -3676,6 +3752,8 @@ static int score_points(dpmm_ctx *c, const dpmm_score_out *o, bool device, const
     int rstep = 0;
     int64_t P = 0;
     if (int rc = score_table_slab(c, &rstep, &P)) return rc;
+    const bool miss = c->opt_score_missing != 0;
+    if (int rc = miss_begin(c, miss, P, fn)) return rc;
     // host variant: the slab's outputs on the device, one block per output (each 8-byte aligned)
     size_t off_lab = 0, off_ld = 0, off_ti = 0, off_tp = 0, off_pr = 0, total = 0;
     if (!device) {
@@ -3690,6 +3768,7 @@ static int score_points(dpmm_ctx *c, const dpmm_score_out *o, bool device, const
     for (int64_t p0 = 0; p0 < c->n; p0 += P) {
         const int64_t np = std::min<int64_t>(P, c->n - p0);
         if (int rc = run_sweep(c, 0, 0, c->d_score_table, P, p0, np)) return rc;
+        if (miss) if (int rc = miss_range(c, P, p0, np, nullptr, 0, fn)) return rc;
         ScoreArgs a{};
         a.table = c->d_score_table; a.stride = P; a.rstep = rstep; a.n = np; a.K = c->K; a.m = o->m;
         if (device) {
@@ -3727,6 +3806,59 @@ static int score_points(dpmm_ctx *c, const dpmm_score_out *o, bool device, const
 int dpmm_score_points(dpmm_ctx *c, const dpmm_score_out *out) { return score_points(c, out, false, "dpmm_score_points"); }
 int dpmm_score_points_device(dpmm_ctx *c, const dpmm_score_out *out) { return score_points(c, out, true, "dpmm_score_points_device"); }
 
+int dpmm_score_missing_counts(dpmm_ctx *c, int64_t out[2]) {
+    static const char *fn = "dpmm_score_missing_counts";
+    if (!c) return tensor_no_ctx(fn);
+    if (!out) return fail(c, DPMM_EINVAL, std::string(fn) + ": out is null");
+    out[0] = out[1] = 0;
+    if (!c->miss_counted) return DPMM_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, sync_stream(c, c->stream));
+    unsigned long long h[3] = {0, 0, 0};
+    HIPCHK(c, hipMemcpy(h, c->d_miss_cnt, sizeof(h), hipMemcpyDeviceToHost));
+    out[0] = (int64_t)h[1]; out[1] = (int64_t)h[2];
+    return DPMM_OK;
+}
+
+static int impute_points(dpmm_ctx *c, float *out, int64_t ld, bool device, const char *fn) {
+    if (!c) return tensor_no_ctx(fn);
+    c->miss_counted = false;      // (as score_points)
+    const std::string who = std::string(fn) + ": ";
+    if (c->prior != DPMM_PRIOR_NIW) return fail(c, DPMM_EINVAL, who + "the Multinomial prior has no missing features");
+    if (!c->predictive) return fail(c, DPMM_ESTATE, who + "needs dpmm_set_predictive_niw first");
+    if (ld < c->D) return fail(c, DPMM_EINVAL, who + "ld < D");
+    if (ld >> 40) return fail(c, DPMM_EINVAL, who + "ld out of range");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (c->n == 0) return DPMM_OK;
+    if (!c->have_points || !c->have_params || !c->dX) return fail(c, DPMM_ESTATE, who + "needs points and parameters");
+    if (!out) return fail(c, DPMM_EINVAL, who + "out is null");
+    if (device) if (int rc = check_device_extent(c, fn, "d_out", out, (uint64_t)c->n * (uint64_t)ld * sizeof(float), sizeof(float))) return rc;
+    int rstep = 0;
+    int64_t P = 0;
+    if (int rc = score_table_slab(c, &rstep, &P)) return rc;
+    if (int rc = miss_begin(c, true, P, fn)) return rc;
+    const int64_t D = c->D;
+    if (!device) if (int rc = ensure_score_buffer(c, reinterpret_cast<void **>(&c->d_score_out), &c->score_out_bytes, sizeof(float) * (size_t)P * (size_t)D, "staging of the outputs")) return rc;
+    for (int64_t p0 = 0; p0 < c->n; p0 += P) {
+        const int64_t np = std::min<int64_t>(P, c->n - p0);
+        if (int rc = run_sweep(c, 0, 0, c->d_score_table, P, p0, np)) return rc;
+        float *rows = device ? out + p0 * ld : reinterpret_cast<float *>(c->d_score_out);
+        const int64_t ldr = device ? ld : D;
+        HIPCHK(c, launch_points_readback(rows, ldr, c->dX + p0 * c->ldx, c->ldx, nullptr, 0, np, c->D, c->stream));
+        if (int rc = miss_range(c, P, p0, np, rows, ldr, fn)) return rc;
+        if (!device) {
+            HIPCHK(c, hipMemcpy2DAsync(out + p0 * ld, sizeof(float) * (size_t)ld, rows, sizeof(float) * (size_t)D, sizeof(float) * (size_t)D, (size_t)np, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, sync_stream(c, c->stream));      // the staging block is rewritten by the next range
+            if (ld > D) for (int64_t i = p0; i < p0 + np; ++i) memset(out + i * ld + D, 0, sizeof(float) * (size_t)(ld - D));
+        }
+    }
+    HIPCHK(c, sync_stream(c, c->stream));
+    return DPMM_OK;
+}
+
+int dpmm_impute_points(dpmm_ctx *c, float *out, int64_t ld) { return impute_points(c, out, ld, false, "dpmm_impute_points"); }
+int dpmm_impute_points_device(dpmm_ctx *c, float *d_out, int64_t ld) { return impute_points(c, d_out, ld, true, "dpmm_impute_points_device"); }
+
 // ---- include/dpmm_hip_rank.h: exemplars, the m most and least typical points of every cluster (rank.hip) -----------------------------------
 static size_t rank_keys_words(int K) { return (size_t)2 * (size_t)K * RANK_SLOTS; }
 static size_t rank_count_words(int K) { return (size_t)RANK_REPL * (size_t)(K + 1); }
@@ -3758,6 +3890,7 @@ int dpmm_rank_begin(dpmm_ctx *c, int m, int which) {
 int dpmm_rank_accumulate(dpmm_ctx *c, int64_t index_base, int64_t n_valid) {
     static const char *fn = "dpmm_rank_accumulate";
     if (!c) return tensor_no_ctx(fn);
+    c->miss_counted = false;      // (as score_points)
     const std::string who = std::string(fn) + ": ";
     if (!c->rank_active) return fail(c, DPMM_ESTATE, who + "needs dpmm_rank_begin first");
     if (!c->predictive || c->K != c->rank_K) return fail(c, DPMM_ESTATE, who + "the predictive parameters changed since dpmm_rank_begin");
@@ -3770,6 +3903,8 @@ int dpmm_rank_accumulate(dpmm_ctx *c, int64_t index_base, int64_t n_valid) {
     int rstep = 0;
     int64_t P = 0;
     if (int rc = score_table_slab(c, &rstep, &P)) return rc;
+    const bool miss = c->opt_score_missing != 0;
+    if (int rc = miss_begin(c, miss, P, fn)) return rc;
     const int K = c->K;
     unsigned long long *keys = c->d_rank_state, *count = keys + rank_keys_words(K);
     unsigned *cand_n = reinterpret_cast<unsigned *>(count + rank_count_words(K));
@@ -3778,6 +3913,7 @@ int dpmm_rank_accumulate(dpmm_ctx *c, int64_t index_base, int64_t n_valid) {
     for (int64_t p0 = 0; p0 < n_valid; p0 += P) {
         const int64_t np = std::min<int64_t>(P, c->n - p0);              // the range dpmm_score_points evaluates
         if (int rc = run_sweep(c, 0, 0, c->d_score_table, P, p0, np)) return rc;
+        if (miss) if (int rc = miss_range(c, P, p0, np, nullptr, 0, fn)) return rc;
         const int64_t nv = std::min<int64_t>(np, n_valid - p0);          // what of it is ranked
         for (int64_t q0 = 0; q0 < nv; q0 += c->rank_cap) {
             RankArgs a{};

@@ -211,6 +211,29 @@ struct RankArgs {
 struct RankOut { int64_t *typ_idx; float *typ_score; int64_t *fringe_idx; float *fringe_score; int64_t *count; int64_t *skipped; };      // = dpmm_rank_out
 hipError_t launch_rank_chunk(const RankArgs &a, hipStream_t s);
 hipError_t launch_rank_read(const unsigned long long *keys, const unsigned long long *count, int K, int m, int which, const RankOut &o, hipStream_t s);
+// ---- missing features (missing.hip; include/dpmm_hip_missing.h): one range of the score table, n points from table column 0 and from X
+constexpr int MISS_MAX = 16;              // DPMM_SCORE_MAX_MISSING
+constexpr int MISS_CST = MISS_MAX + 2;    // doubles per cluster in MissArgs::cst
+inline int miss_pitch(int D) { return 64 * ((D + 63) / 64); }
+struct MissArgs {
+    float *table;                // entry (k, i) at table[k * stride + i]; the patch kernel rewrites the listed points' entries
+    int64_t stride;
+    int64_t n;
+    int K, D;
+    const float *X;              // [n][ldx], the range's first point
+    int64_t ldx;
+    const float *Rt;             // [K][D][miss_pitch(D)]: Rt[k][j][i] = R_k[i][j], zero below the diagonal (i > j) and in the pad (i >= D)
+    const float *mu;             // cluster k's mean: mu + k * mu_step
+    int64_t mu_step;
+    const double *cst;           // [K][MISS_CST]: [0] = df, [r], 1 <= r <= MISS_MAX: lgamma((df + D - r) / 2) - lgamma(df / 2) - (D - r) / 2 log(df pi) - logdet / 2 + log w
+    uint32_t *list;              // [n] positions of the range's points with 1 .. min(MISS_MAX, D - 1) NaN features, in no particular order
+    unsigned long long *cnt;     // [0] entries of list (cleared per range), [1] marginalised, [2] over-the-cap points (cleared per call)
+    float *out;                  // impute: [n][ld_out] rows the points were copied to; the NaN words of listed points are rewritten
+    int64_t ld_out;
+};
+hipError_t launch_miss_transpose(const float *Rpk, int64_t step, float *Rt, int K, int D, hipStream_t s);      // Rpk: packed upper triangles, cluster k at Rpk + k * step
+hipError_t launch_miss_list(const MissArgs &a, hipStream_t s);
+hipError_t launch_miss_patch(const MissArgs &a, bool impute, int max_grid, hipStream_t s);
 // ---- drawing points (sample.hip; include/dpmm_hip_sample.h): n samples from global index i0; every output pointer is that of the call's
 // first sample
 struct SampleArgs {

@@ -1,0 +1,265 @@
+// missing.hip -- points with missing (NaN) features under the Student-t predictive (include/dpmm_hip_missing.h, which states the
+// mathematics): between the evaluation of a range of the score table and its finish pass,
+//   miss_list_kernel    compacts the positions of the range's points that have 1 .. min(16, D - 1) NaN features and counts those with more.
+//                       A NaN feature makes the point's entry NaN under every cluster, so row 0 of the table (n floats, just written)
+//                       names the candidates and only their x is looked at; an entry that is NaN for another reason (an Inf feature
+//                       against a zero of R) has no NaN feature and is left alone.  One atomic per wave and counter.
+//   miss_patch_kernel   one wave per listed point, looping over the clusters; no workgroup barrier anywhere (the list's length is read
+//                       from device memory, waves leave when they please).  Lane l carries features / rows l, l + 64, .. (NT = ceil(D / 64)
+//                       of them).  Per cluster:
+//                         z = x - m on O, 0 on M; y = R z in Float32: column j of R is one coalesced row of the transposed copy Rt
+//                         (zero below the diagonal and in the pad), z_j goes round with v_readlane;
+//                         g = C'y, A = C'C (C = R[:, M]): columns of Rt again, products and wave sums in Float64; A goes to r x r words of
+//                         wave-private LDS, where lane a factors row a (Cholesky, column by column) and the two triangular solves leave t_a
+//                         in lane a;
+//                         q_o = |y - C t|^2 as the squared norm of the residual; the entry in Float64, rounded once.
+//                       The IMPUTE instantiation runs behind it on the patched table: M, S and p_k = e_k / S as score_finish_kernel forms
+//                       them (same operations, same bits), t_k by the same steps, and lane a < r accumulates sum_k p_k (m[M_a] - t_a) in
+//                       Float64 for the one output word it owns.
+//   miss_transpose_kernel   Rt[k][j][i] = R_k[i][j] from the packed upper triangles of the parameter staging, once per parameter set.
+// The missing set is not stored: the wave that reads x gets it from a ballot per 64 features.
+#include "dpmm_device.h"
+#include "dpmm_kernels.h"
+
+namespace dpmm {
+
+constexpr int MISS_WAVES = 4;                  // waves per workgroup of the patch kernel (they share nothing)
+constexpr int MISS_LDA = MISS_MAX + 1;         // doubles per row of a wave's A (odd: the lanes of a column fall into different banks)
+
+__device__ __forceinline__ float miss_rl_f(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
+__device__ __forceinline__ double miss_rl_d(double v, int l) {
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
+}
+__device__ __forceinline__ double miss_wave_sum(double v) {      // (a butterfly: every lane ends with the same bits)
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+__device__ __forceinline__ void miss_lds_fence() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); }
+
+__global__ __launch_bounds__(256) void miss_transpose_kernel(const float *__restrict__ Rpk, int64_t step, float *__restrict__ Rt, int K, int D, int Dp) {
+    const int64_t total = (int64_t)K * D * Dp;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
+        const int i = (int)(e % Dp);
+        const int j = (int)((e / Dp) % D);
+        const int k = (int)(e / ((int64_t)Dp * D));
+        // packed upper triangle: row i holds the columns i .. D - 1 from word i D - i (i - 1) / 2
+        Rt[e] = (i <= j) ? Rpk[(int64_t)k * step + (int64_t)i * D - (int64_t)i * (i - 1) / 2 + (j - i)] : 0.f;
+    }
+}
+
+__global__ __launch_bounds__(256) void miss_list_kernel(MissArgs A) {
+    const int lane = threadIdx.x & 63;
+    const int cap = A.D - 1 < MISS_MAX ? A.D - 1 : MISS_MAX;
+    // (the 64 points of a trip belong to one wave: its trip count is uniform, the ballots see whole waves)
+    for (int64_t base = (int64_t)blockIdx.x * 256 + (threadIdx.x & ~63); base < A.n; base += (int64_t)gridDim.x * 256) {
+        const int64_t i = base + lane;
+        int r = 0;
+        if (i < A.n) {
+            const float a = A.table[i];
+            if (a != a) {
+                const float *x = A.X + i * A.ldx;
+                for (int j = 0; j < A.D; ++j) r += (x[j] != x[j]) ? 1 : 0;
+            }
+        }
+        const bool lst = r >= 1 && r <= cap, over = r > cap;
+        const unsigned long long ml = __ballot(lst), mo = __ballot(over);
+        if (ml) {
+            int at = 0;      // (the list holds at most n < 2^32 entries; `ml` is wave-uniform, so lane 0 is active here)
+            if (lane == 0) {
+                at = (int)(unsigned)atomicAdd(&A.cnt[0], (unsigned long long)__popcll(ml));
+                atomicAdd(&A.cnt[1], (unsigned long long)__popcll(ml));
+            }
+            const unsigned at0 = (unsigned)__builtin_amdgcn_readfirstlane(at);
+            if (lst) A.list[(uint64_t)at0 + (uint64_t)__popcll(ml & ((1ull << lane) - 1ull))] = (uint32_t)i;
+        }
+        if (mo && lane == 0) atomicAdd(&A.cnt[2], (unsigned long long)__popcll(mo));
+    }
+}
+
+template <int NT, bool IMPUTE>
+__global__ __launch_bounds__(64 * MISS_WAVES) void miss_patch_kernel(MissArgs A) {
+    __shared__ double sA[MISS_WAVES][MISS_MAX * MISS_LDA];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    double *const Am = sA[wave];
+    const int D = A.D, K = A.K;
+    constexpr int Dp = 64 * NT;
+    const unsigned long long total = A.cnt[0];
+    const unsigned long long nw = (unsigned long long)gridDim.x * MISS_WAVES;
+    for (unsigned long long e = (unsigned long long)blockIdx.x * MISS_WAVES + wave; e < total; e += nw) {
+        const int64_t i = A.list[e];
+        const float *x = A.X + i * A.ldx;
+        float xv[NT];
+        unsigned long long nm[NT];
+        int r = 0;
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            const int j = 64 * t + lane;
+            xv[t] = j < D ? x[j] : 0.f;
+            nm[t] = __ballot(xv[t] != xv[t]);
+            r += __popcll(nm[t]);
+        }
+        // lane a < r learns M_a, the a-th missing feature
+        int myM = 0;
+        {
+            int a = 0;
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+                unsigned long long mk = nm[t];
+                while (mk) {
+                    const int b = __ffsll((long long)mk) - 1;
+                    mk &= mk - 1;
+                    if (lane == a) myM = 64 * t + b;
+                    ++a;
+                }
+            }
+        }
+        float *const col_i = A.table + i;
+        float mx = -INFINITY, ssum = 0.f;
+        double acc = 0.0;
+        if constexpr (IMPUTE) {      // M and S of score_finish_kernel, from the patched column
+            for (int k = 0; k < K; ++k) {
+                const float a = col_i[(int64_t)k * A.stride];
+                if (a == a && a > mx) mx = a;
+            }
+            for (int k = 0; k < K; ++k) {
+                float a = col_i[(int64_t)k * A.stride];
+                if (a != a) a = -INFINITY;
+                ssum += expf(a - mx);
+            }
+        }
+        for (int k = 0; k < K; ++k) {
+            const float *const Rk = A.Rt + (int64_t)k * D * Dp;
+            const float *const mk = A.mu + (int64_t)k * A.mu_step;
+            float z[NT], y[NT];
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+                const int j = 64 * t + lane;
+                const bool miss = (nm[t] >> lane) & 1ull;
+                z[t] = (j < D && !miss) ? xv[t] - mk[j] : 0.f;
+                y[t] = 0.f;
+            }
+            // ---- y = R z: column j of R scaled by z_j; rows above 64 (tj + 1) hold zeros of the triangle and are skipped
+#pragma unroll
+            for (int tj = 0; tj < NT; ++tj) {
+                const int jn = D - 64 * tj < 64 ? D - 64 * tj : 64;
+#pragma unroll 4
+                for (int jj = 0; jj < jn; ++jj) {
+                    const float zj = miss_rl_f(z[tj], jj);
+                    const float *c = Rk + (int64_t)(64 * tj + jj) * Dp + lane;
+#pragma unroll
+                    for (int tr = 0; tr <= tj; ++tr) y[tr] = fmaf(c[64 * tr], zj, y[tr]);
+                }
+            }
+            // ---- g = C'y into lane b, A = C'C (lower triangle) into the wave's LDS
+            double gl = 0.0;
+            for (int b = 0; b < r; ++b) {
+                const float *cb = Rk + (int64_t)__builtin_amdgcn_readlane(myM, b) * Dp + lane;
+                float colb[NT];
+                double p = 0.0;
+#pragma unroll
+                for (int t = 0; t < NT; ++t) { colb[t] = cb[64 * t]; p += (double)colb[t] * (double)y[t]; }
+                p = miss_wave_sum(p);
+                if (lane == b) gl = p;
+                for (int a = 0; a <= b; ++a) {
+                    const float *ca = Rk + (int64_t)__builtin_amdgcn_readlane(myM, a) * Dp + lane;
+                    double s = 0.0;
+#pragma unroll
+                    for (int t = 0; t < NT; ++t) s += (double)ca[64 * t] * (double)colb[t];
+                    s = miss_wave_sum(s);
+                    if (lane == 0) Am[b * MISS_LDA + a] = s;
+                }
+            }
+            miss_lds_fence();
+            // ---- A = L L': lane a owns row a; column j is finished by the lanes j .. r - 1 at once
+            double half_logdet = 0.0;      // sum_j log L_jj = logdet A / 2
+            for (int j = 0; j < r; ++j) {
+                const bool act = lane >= j && lane < r;
+                const int row = act ? lane : j;
+                double s = Am[row * MISS_LDA + j];
+                for (int t2 = 0; t2 < j; ++t2) s -= Am[row * MISS_LDA + t2] * Am[j * MISS_LDA + t2];
+                const double dj = sqrt(miss_rl_d(s, j));
+                half_logdet += log(dj);
+                if (act) Am[lane * MISS_LDA + j] = (lane == j) ? dj : s / dj;
+                miss_lds_fence();
+            }
+            // ---- t = A^-1 g: L u = g, then L't = u; lane a ends with t_a
+            for (int j = 0; j < r; ++j) {
+                if (lane == j) gl = gl / Am[j * MISS_LDA + j];
+                const double uj = miss_rl_d(gl, j);
+                if (lane > j && lane < r) gl -= Am[lane * MISS_LDA + j] * uj;
+            }
+            for (int j = r - 1; j >= 0; --j) {
+                if (lane == j) gl = gl / Am[j * MISS_LDA + j];
+                const double tj = miss_rl_d(gl, j);
+                if (lane < j) gl -= Am[j * MISS_LDA + lane] * tj;
+            }
+            miss_lds_fence();      // (the next cluster overwrites A)
+            if constexpr (IMPUTE) {
+                float a = col_i[(int64_t)k * A.stride];
+                if (a != a) a = -INFINITY;
+                const float pk = expf(a - mx) / ssum;
+                if (lane < r) acc += (double)pk * ((double)mk[myM] - gl);
+            } else {
+                // ---- q_o = |y - C t|^2, the residual itself
+                double res[NT];
+#pragma unroll
+                for (int t = 0; t < NT; ++t) res[t] = (double)y[t];
+                for (int a = 0; a < r; ++a) {
+                    const float *ca = Rk + (int64_t)__builtin_amdgcn_readlane(myM, a) * Dp + lane;
+                    const double ta = miss_rl_d(gl, a);
+#pragma unroll
+                    for (int t = 0; t < NT; ++t) res[t] -= (double)ca[64 * t] * ta;
+                }
+                double q = 0.0;
+#pragma unroll
+                for (int t = 0; t < NT; ++t) q += res[t] * res[t];
+                q = miss_wave_sum(q);
+                const double *ck = A.cst + (int64_t)k * MISS_CST;
+                const double df = ck[0];
+                const double val = ck[r] - half_logdet - 0.5 * (df + (double)(D - r)) * log1p(q / df);
+                if (lane == 0) col_i[(int64_t)k * A.stride] = (float)val;
+            }
+        }
+        if constexpr (IMPUTE) {
+            if (lane < r) A.out[i * A.ld_out + myM] = (float)acc;
+        }
+    }
+}
+
+template <bool IMPUTE>
+static void launch_patch_nt(const MissArgs &a, int grid, hipStream_t s) {
+    const int nt = (a.D + 63) / 64;
+    if (nt == 1) DPMM_LAUNCH((miss_patch_kernel<1, IMPUTE>), dim3(grid), dim3(64 * MISS_WAVES), 0, s, a);
+    else if (nt == 2) DPMM_LAUNCH((miss_patch_kernel<2, IMPUTE>), dim3(grid), dim3(64 * MISS_WAVES), 0, s, a);
+    else if (nt == 3) DPMM_LAUNCH((miss_patch_kernel<3, IMPUTE>), dim3(grid), dim3(64 * MISS_WAVES), 0, s, a);
+    else DPMM_LAUNCH((miss_patch_kernel<4, IMPUTE>), dim3(grid), dim3(64 * MISS_WAVES), 0, s, a);
+}
+
+static bool miss_args_ok(const MissArgs &a) { return a.K >= 1 && a.D >= 1 && a.D <= 256 && a.n <= a.stride && a.n <= (int64_t)0xffffffffll; }
+
+hipError_t launch_miss_transpose(const float *Rpk, int64_t step, float *Rt, int K, int D, hipStream_t s) {
+    if (K < 1 || D < 1 || D > 256) return hipErrorInvalidValue;
+    const int Dp = miss_pitch(D);
+    const int64_t total = (int64_t)K * D * Dp;
+    DPMM_LAUNCH(miss_transpose_kernel, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 4096)), dim3(256), 0, s, Rpk, step, Rt, K, D, Dp);
+    return hipGetLastError();
+}
+
+hipError_t launch_miss_list(const MissArgs &a, hipStream_t s) {
+    if (a.n <= 0) return hipSuccess;
+    if (!miss_args_ok(a)) return hipErrorInvalidValue;
+    DPMM_LAUNCH(miss_list_kernel, dim3((unsigned)std::min<int64_t>((a.n + 255) / 256, 2048)), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_miss_patch(const MissArgs &a, bool impute, int max_grid, hipStream_t s) {
+    if (a.n <= 0) return hipSuccess;
+    if (!miss_args_ok(a) || (impute && (!a.out || a.ld_out < a.D))) return hipErrorInvalidValue;
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((a.n + MISS_WAVES - 1) / MISS_WAVES, max_grid));
+    if (impute) launch_patch_nt<true>(a, grid, s);
+    else launch_patch_nt<false>(a, grid, s);
+    return hipGetLastError();
+}
+
+}  // namespace dpmm

@@ -83,19 +83,34 @@ def _device_index(device):
     return device.index
 
 
-class Predictor:
-    """Predictor(dp_model, capacity=65536, device=None, worker_factory=None): see the module's description.  Use as a context manager or close()."""
+MISSING_MODES = ("propagate", "marginalize")
 
-    def __init__(self, dp_model, capacity=65536, device=None, worker_factory=None):
+
+class Predictor:
+    """Predictor(dp_model, capacity=65536, device=None, worker_factory=None, missing="propagate"): see the module's description.  Use as a
+    context manager or close().
+
+    missing="propagate": a NaN feature makes every result of its point NaN / "cluster 1", as the reference's dense matrix would.
+    missing="marginalize" (NIW only): a NaN feature is a MISSING one.  A point with 1 .. min(16, D - 1) of them is scored by the marginal
+    of every cluster's Student-t over the features it has (include/dpmm_hip_missing.h) -- labels, probabilities, top-m, log-density and
+    exemplars all follow; a point with more keeps its NaN results.  `missing_counts` holds (marginalised, over the cap) of the last call,
+    (0, 0) under "propagate".  `impute` fills the gaps under either setting."""
+
+    def __init__(self, dp_model, capacity=65536, device=None, worker_factory=None, missing="propagate"):
         s = dp_model.sampler
         rows = [3 * k for k in range(s.K)]
         post = {k: np.asarray(v)[rows] for k, v in s.post.items()}
         if device is None:
             device = getattr(getattr(s, "wk", None), "device", 0)
         self._setup(s.prior.kind, s.prior.dim, s.alpha, np.asarray(s.points_count), post, capacity, device, worker_factory,
-                    projection=getattr(dp_model, "projection", None))
+                    projection=getattr(dp_model, "projection", None), missing=missing)
 
-    def _setup(self, kind, D, alpha, points_count, post, capacity, device, worker_factory, projection=None):
+    def _setup(self, kind, D, alpha, points_count, post, capacity, device, worker_factory, projection=None, missing="propagate"):
+        if missing not in MISSING_MODES:
+            raise ValueError('missing must be "propagate" or "marginalize"')
+        if missing == "marginalize" and int(kind) != _priors.PRIOR_NIW:
+            raise ValueError('missing="marginalize" is for the NIW prior: the Multinomial prior has no missing features')
+        self.missing, self.missing_counts = missing, (0, 0)
         self.projection = projection     # host/project.py: D_in-row data is projected on the way in (the worker holds the map)
         self.kind, self.D, self.alpha = int(kind), int(D), float(alpha)
         self.points_count = np.asarray(points_count, np.float64).copy()
@@ -120,6 +135,8 @@ class Predictor:
             (self._wk.set_predictive_niw if which == "niw" else self._wk.set_predictive_mult)(*args)      # ONCE
             if projection is not None:
                 projection.apply(self._wk)                                                                # ... as well
+            if missing == "marginalize":
+                self._wk.set_option(binding.OPT_SCORE_MISSING, 1)                                         # ... and this
         except Exception:
             self._wk.close()
             self._wk = None
@@ -158,12 +175,12 @@ class Predictor:
                  **{"post_" + k: v for k, v in self.post.items()}, **(self.projection.arrays("proj_") if self.projection is not None else {}))
 
     @classmethod
-    def load(cls, path, device=None, capacity=65536, worker_factory=None):
+    def load(cls, path, device=None, capacity=65536, worker_factory=None, missing="propagate"):
         with np.load(path) as z:
             post = {k[5:]: z[k] for k in z.files if k.startswith("post_")}
             self = cls.__new__(cls)
             self._setup(int(z["kind"]), int(z["D"]), float(z["alpha"]), z["points_count"], post, capacity, 0 if device is None else device, worker_factory,
-                        projection=_project.Projection.from_arrays(z, "proj_"))
+                        projection=_project.Projection.from_arrays(z, "proj_"), missing=missing)
         return self
 
     # ---- the public methods
@@ -216,14 +233,55 @@ class Predictor:
             raise RuntimeError("this Predictor's worker cannot rank points (no dpmm_rank_begin)")
         n, dev, _, upload = self._open(data)
         wk.rank_begin(m, mask)
+        counts = np.zeros(2, np.int64)
         for lo in range(0, n, cap):
             hi = min(n, lo + cap)
             upload(lo, hi)
             wk.rank_accumulate(lo, hi - lo)
+            counts += self._slab_counts()
+        self.missing_counts = (int(counts[0]), int(counts[1]))
         r = wk.rank_read(device=dev)
         typ, fr = mask & binding.RANK_TYPICAL, mask & binding.RANK_FRINGE
         return Exemplars(r["typ_idx"] if typ else None, r["typ_score"] if typ else None, r["fringe_idx"] if fr else None,
                          r["fringe_score"] if fr else None, r["count"], int(r["skipped"][0]))
+
+    # ---- missing features (include/dpmm_hip_missing.h)
+    def _slab_counts(self):
+        """(marginalised, over the cap) of the slab the worker has just evaluated; zeros under "propagate" (the worker is not asked)."""
+        return np.asarray(self._wk.score_missing_counts() if self.missing == "marginalize" else (0, 0), np.int64)
+
+    def impute(self, data):
+        """(D, n) float32: `data` converted to Float32 with the NaN features of every point that has 1 .. min(16, D - 1) of them replaced
+        by sum_k p_k E[x_M | x_O, k] -- the conditional means of the clusters' Student-t predictives, mixed with the probabilities
+        `predict` gives the point under missing="marginalize".  Everything else -- observed features, complete points, points with more NaN
+        features than that -- is copied bit for bit.  NIW only; works under either `missing` setting and sets `missing_counts`.
+        A numpy array for host data; for a device tensor a tensor on its device (point-major memory: the `.T` view of an (n, D) tensor),
+        written there by the library, nothing of size n crossing the host link.  Integer data has no NaN and comes back converted."""
+        if self._wk is None:
+            raise RuntimeError("this Predictor is closed")
+        if self.kind != _priors.PRIOR_NIW:
+            raise ValueError("impute is for the NIW prior: the Multinomial prior has no missing features")
+        wk, cap, D = self._wk, self.capacity, self.D
+        if not hasattr(wk, "impute_points_into"):
+            raise RuntimeError("this Predictor's worker cannot impute points (no dpmm_impute_points)")
+        n, dev, new, upload = self._open(data, refuse_projected="impute")
+        out = new(n, (D,), "float32")
+        counts = np.zeros(2, np.int64)
+        for lo in range(0, n, cap):
+            hi = min(n, lo + cap)
+            upload(lo, hi)
+            if hi - lo == cap:
+                wk.impute_points_into(out[lo:hi])
+            else:
+                key = ("dev" if dev is not None else "host", "impute")
+                b = self._out_stage.get(key)
+                if b is None or (dev is not None and b.device != dev):
+                    b = self._out_stage[key] = new(cap, (D,), "float32")
+                wk.impute_points_into(b)
+                out[lo:hi] = b[:hi - lo]
+            counts += np.asarray(wk.score_missing_counts(), np.int64)
+        self.missing_counts = (int(counts[0]), int(counts[1]))
+        return out.T
 
     # ---- drawing points (include/dpmm_hip_sample.h)
     def sampler_tables(self):
@@ -331,7 +389,7 @@ class Predictor:
             spec.append(("probs", (self.K,), "float32"))
         return spec
 
-    def _open(self, data):
+    def _open(self, data, refuse_projected=None):
         """What every walk over `data` in slabs of `capacity` points needs: (n, dev, new, upload).  dev: the torch device of device data,
         else None; new(rows, tail, dtype name): an empty result array / tensor where the results go; upload(lo, hi): the worker's points
         become the points lo..hi-1, zero padded (empty columns for sparse data) to `capacity`."""
@@ -365,6 +423,10 @@ class Predictor:
         proj = self.projection if self.projection is not None and csc is None and D == self.projection.D_in else None
         if proj is None and D != self.D:               # (d-row data is taken as already projected)
             raise ValueError("data dimension does not match the model")
+        if proj is not None and (refuse_projected or self.missing == "marginalize"):
+            # one NaN source feature poisons all d projected coordinates: nothing is left to marginalise over
+            what = refuse_projected or 'missing="marginalize"'
+            raise ValueError(f"{what} takes data in the model's {self.D} projected coordinates, not the {D} source features of the projection")
         if proj is not None and desc is not None and not hasattr(wk, "upload_points_projected_strided_device"):
             data, desc = desc.tensor.float().cpu().numpy(), None
             X = np.asarray(data)
@@ -450,6 +512,7 @@ class Predictor:
         wk, cap = self._wk, self.capacity
         spec = self._spec(labels, logdens, m, probs)
         out = {name: new(n, tail, dt) for name, tail, dt in spec}
+        counts = np.zeros(2, np.int64)
         for lo in range(0, n, cap):
             hi = min(n, lo + cap)
             full = hi - lo == cap
@@ -466,9 +529,11 @@ class Predictor:
                         b = self._out_stage[(key, name)] = new(cap, tail, dt)
                     views[name] = b
             wk.score_points_into(views, m=m)
+            counts += self._slab_counts()
             if not full:
                 for name, _, _ in spec:
                     out[name][lo:hi] = views[name][:hi - lo]
+        self.missing_counts = (int(counts[0]), int(counts[1]))
         return out
 
 
@@ -490,6 +555,13 @@ def exemplars(dp_model, data, m, **kw):
     which = kw.pop("which", "both")
     with Predictor(dp_model, **kw) as p:
         return p.exemplars(data, m, which=which)
+
+
+def impute(dp_model, data, **kw):
+    """`data` with its missing (NaN) features filled in (opens a Predictor, runs, closes): see `Predictor.impute`;
+    kw: capacity, device, worker_factory, missing."""
+    with Predictor(dp_model, **kw) as p:
+        return p.impute(data)
 
 
 def sample(dp_model, n, seed=0, trials=None, sparse=False, **kw):
