@@ -148,6 +148,16 @@ ABI_RANK = [
 ]
 RANK_MAX_M = 64                        # DPMM_RANK_MAX_M
 RANK_TYPICAL, RANK_FRINGE = 1, 2       # DPMM_RANK_TYPICAL, DPMM_RANK_FRINGE
+# include/dpmm_hip_trace.h: label samples kept on the GPU, their pairwise contingency tables and the per-point confidence (additive)
+ABI_TRACE = [
+    ("dpmm_trace_open", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    ("dpmm_trace_close", ctypes.c_int, [ctypes.c_void_p]),
+    ("dpmm_trace_record", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]),
+    ("dpmm_trace_tables", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32), ctypes.c_int, _c_i64p]),
+    ("dpmm_trace_confidence", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int32), ctypes.c_int, _c_f32p, _c_f32p, ctypes.c_void_p]),
+    ("dpmm_trace_read", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _c_i64p, ctypes.c_void_p]),
+]
+TRACE_MAX_SLOTS = 4096                 # DPMM_TRACE_MAX_SLOTS
 # include/dpmm_hip_csc.h: sparse points out of caller-owned device memory (additive; bound next to ABI)
 ABI_CSC = [
     ("dpmm_upload_points_csc_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
@@ -244,7 +254,7 @@ def load_library():
         except Exception:  # pragma: no cover  (torch is optional for single-GPU use)
             pass
         lib = ctypes.CDLL(p)
-        for name, res, args in ABI + ABI_TENSOR + ABI_SCORE + ABI_RANK + ABI_MISSING + ABI_CSC + ABI_SAMPLE + ABI_PROJECT:
+        for name, res, args in ABI + ABI_TENSOR + ABI_SCORE + ABI_RANK + ABI_TRACE + ABI_MISSING + ABI_CSC + ABI_SAMPLE + ABI_PROJECT:
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -679,6 +689,68 @@ class Worker:
             res = {name: np.empty(sh, dt) for name, sh, dt in spec}
             self.rank_read_raw(False, **{k: v.ctypes.data for k, v in res.items()})
         return res
+
+    # ---- label trace (include/dpmm_hip_trace.h)
+    def trace_open(self, slots):
+        """dpmm_trace_open: room for `slots` labellings of the shard (16-bit cluster ids) on the GPU; an open trace is replaced."""
+        self._chk(self._lib.dpmm_trace_open(self._h, int(slots)))
+        self._trace_K = {}
+
+    def trace_close(self):
+        self._chk(self._lib.dpmm_trace_close(self._h))
+        self._trace_K = {}
+
+    def trace_record(self, slot, K):
+        """dpmm_trace_record: the labels in force into `slot`, with K clusters; returns without waiting for the GPU."""
+        self._chk(self._lib.dpmm_trace_record(self._h, int(slot), int(K)))
+        self._trace_K[int(slot)] = int(K)
+
+    def trace_tables(self, pairs):
+        """dpmm_trace_tables: for every (s, t) of `pairs` the (K[s], K[t]) int64 contingency table of the two recorded labellings of this
+        shard, a list in the order of `pairs`."""
+        pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        known = getattr(self, "_trace_K", {})
+        shapes = [(known.get(int(s), 0), known.get(int(t), 0)) for s, t in pairs]
+        counts = np.zeros(max(1, sum(a * b for a, b in shapes)), np.int64)
+        self._chk(self._lib.dpmm_trace_tables(self._h, pairs.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), len(pairs), _p(counts, _c_i64p)))
+        out, off = [], 0
+        for a, b in shapes:
+            out.append(counts[off:off + a * b].reshape(a, b))
+            off += a * b
+        return out
+
+    def trace_confidence(self, anchor, slots, ratio, device=None):
+        """dpmm_trace_confidence: per local point the mean over `slots` of ratio[j][z_anchor, z_slots[j]], Float32 (n,).  ratio: one
+        (K[anchor], K[s]) table per listed slot.  device: a torch device -- the result is a tensor there; None: a numpy array."""
+        slots = np.ascontiguousarray(slots, dtype=np.int32).ravel()
+        flat = np.concatenate([_f32(r).ravel() for r in ratio]) if len(ratio) else np.zeros(0, np.float32)
+        known = getattr(self, "_trace_K", {})
+        assert len(ratio) == len(slots) and flat.size == sum(known.get(int(anchor), 0) * known.get(int(s), 0) for s in slots)
+        flat = _f32(flat) if flat.size else np.zeros(1, np.float32)
+        sp = slots.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+        if device is not None:
+            import torch
+            out = torch.empty(self.n, dtype=torch.float32, device=device)
+            torch.cuda.current_stream(out.device).synchronize()
+            if self.n:                 # (an empty tensor has no address to hand over)
+                self._chk(self._lib.dpmm_trace_confidence(self._h, int(anchor), sp, len(slots), _p(flat, _c_f32p), None, ctypes.c_void_p(out.data_ptr())))
+            return out
+        out = np.empty(self.n, np.float32)
+        self._chk(self._lib.dpmm_trace_confidence(self._h, int(anchor), sp, len(slots), _p(flat, _c_f32p), _p(out, _c_f32p), None))
+        return out
+
+    def trace_read(self, slot, device=None):
+        """dpmm_trace_read: the labels of `slot`, 1-based int64 (n,): a tensor on `device`, or a numpy array."""
+        if device is not None:
+            import torch
+            out = torch.empty(self.n, dtype=torch.int64, device=device)
+            torch.cuda.current_stream(out.device).synchronize()
+            if self.n:
+                self._chk(self._lib.dpmm_trace_read(self._h, int(slot), None, ctypes.c_void_p(out.data_ptr())))
+            return out
+        out = np.empty(self.n, np.int64)
+        self._chk(self._lib.dpmm_trace_read(self._h, int(slot), _p(out, _c_i64p), None))
+        return out
 
     def predict_table_mult(self, logp, weights, points=False):
         K = len(weights)

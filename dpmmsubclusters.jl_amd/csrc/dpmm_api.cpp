@@ -10,6 +10,7 @@
 #include "../../include/dpmm_hip_csc.h"
 #include "../../include/dpmm_hip_score.h"
 #include "../../include/dpmm_hip_rank.h"
+#include "../../include/dpmm_hip_trace.h"
 #include "../../include/dpmm_hip_missing.h"
 #include "../../include/dpmm_hip_sample.h"
 #include "../../include/dpmm_hip_project.h"
@@ -147,6 +148,16 @@ struct dpmm_ctx {
     bool rank_active = false;
     int rank_m = 0, rank_which = 0, rank_K = 0, rank_parity = 0;
     int64_t rank_cap = 0;
+    // label trace (include/dpmm_hip_trace.h): slots rows of trace_nvec 16-byte vectors of ids; K per slot (0: never recorded); the device
+    // images of a call's tables, descriptors, ratio tables and confidence
+    uint16_t *d_trace = nullptr;
+    int trace_slots = 0;
+    int64_t trace_nvec = 0;
+    std::vector<int> trace_K;
+    unsigned long long *d_trace_counts = nullptr; size_t trace_counts_bytes = 0;
+    char *d_trace_desc = nullptr; size_t trace_desc_bytes = 0;
+    float *d_trace_ratio = nullptr; size_t trace_ratio_bytes = 0;
+    float *d_trace_conf = nullptr; size_t trace_conf_bytes = 0;
     // missing features (include/dpmm_hip_missing.h): the constants of the marginals on the host (formed by dpmm_set_predictive_niw); on the
     // device, allocated by the first call that marginalises: their copy, the transposed factors, a range's list and the three counters
     int opt_score_missing = 0;         // DPMM_OPT_SCORE_MISSING
@@ -740,6 +751,7 @@ int dpmm_destroy(dpmm_ctx *c) {
     hipFree(c->d_m0); hipFree(c->d_psi_lo); hipFree(c->d_pairs);
     hipFree(c->d_score_table); hipFree(c->d_score_out);
     hipFree(c->d_rank_state); hipFree(c->d_rank_cand); hipFree(c->d_rank_out);
+    hipFree(c->d_trace); hipFree(c->d_trace_counts); hipFree(c->d_trace_desc); hipFree(c->d_trace_ratio); hipFree(c->d_trace_conf);
     hipFree(c->d_miss_rt); hipFree(c->d_miss_cst); hipFree(c->d_miss_list); hipFree(c->d_miss_cnt);
     hipFree(c->d_sm_m); hipFree(c->d_sm_At); hipFree(c->d_sm_df); hipFree(c->d_sm_thr); hipFree(c->d_sm_alias);
     hipFree(c->d_sm_cstart); hipFree(c->d_sm_tstart); hipFree(c->d_sm_cnt); hipFree(c->d_sm_bt);
@@ -3972,6 +3984,189 @@ static int rank_read(dpmm_ctx *c, const dpmm_rank_out *o, bool device, const cha
 
 int dpmm_rank_read(dpmm_ctx *c, const dpmm_rank_out *out) { return rank_read(c, out, false, "dpmm_rank_read"); }
 int dpmm_rank_read_device(dpmm_ctx *c, const dpmm_rank_out *out) { return rank_read(c, out, true, "dpmm_rank_read_device"); }
+
+// ---- include/dpmm_hip_trace.h: label samples kept on the device, their contingency tables and the per-point confidence (trace.hip) ----------
+static int trace_buffer(dpmm_ctx *c, void **buf, size_t *have, size_t need, const char *fn, const char *what) {
+    if (need <= *have) return DPMM_OK;
+    HIPCHK(c, sync_stream(c, c->stream));
+    hipFree(*buf); *buf = nullptr; *have = 0;
+    if (hipMalloc(buf, need) != hipSuccess) {
+        (void)hipGetLastError();
+        *buf = nullptr;
+        return fail(c, DPMM_EHIP, std::string(fn) + ": out of device memory for the " + what + " (" + std::to_string((unsigned long long)need) + " bytes)");
+    }
+    *have = need;
+    return DPMM_OK;
+}
+static uint16_t *trace_row(dpmm_ctx *c, int slot) { return c->d_trace + (size_t)slot * (size_t)c->trace_nvec * 8; }
+// a slot a call names: inside the trace (DPMM_EINVAL) and recorded (DPMM_ESTATE)
+static int trace_slot_ok(dpmm_ctx *c, const std::string &who, int slot) {
+    if (slot < 0 || slot >= c->trace_slots) return fail(c, DPMM_EINVAL, who + "slot " + std::to_string(slot) + " is outside 0.." + std::to_string(c->trace_slots - 1));
+    if (c->trace_K[slot] == 0) return fail(c, DPMM_ESTATE, who + "slot " + std::to_string(slot) + " was never recorded");
+    return DPMM_OK;
+}
+
+int dpmm_trace_close(dpmm_ctx *c) {
+    static const char *fn = "dpmm_trace_close";
+    if (!c) return tensor_no_ctx(fn);
+    if (!c->d_trace) return DPMM_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, sync_stream(c, c->stream));
+    hipFree(c->d_trace); c->d_trace = nullptr;
+    c->trace_slots = 0; c->trace_nvec = 0; c->trace_K.clear();
+    return DPMM_OK;
+}
+
+int dpmm_trace_open(dpmm_ctx *c, int slots) {
+    static const char *fn = "dpmm_trace_open";
+    if (!c) return tensor_no_ctx(fn);
+    const std::string who = std::string(fn) + ": ";
+    if (slots < 1 || slots > DPMM_TRACE_MAX_SLOTS) return fail(c, DPMM_EINVAL, who + "slots must be in 1.." + std::to_string(DPMM_TRACE_MAX_SLOTS));
+    if (int rc = dpmm_trace_close(c)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    const int64_t nvec = (c->n + 7) / 8;                           // a row: n ids of 2 bytes, padded to 16 bytes
+    const size_t bytes = std::max<size_t>(16, (size_t)slots * (size_t)nvec * 16);
+    if (hipMalloc(&c->d_trace, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        c->d_trace = nullptr;
+        return fail(c, DPMM_EHIP, who + "out of device memory for the trace (" + std::to_string((unsigned long long)bytes) + " bytes)");
+    }
+    c->trace_slots = slots; c->trace_nvec = nvec; c->trace_K.assign((size_t)slots, 0);
+    return DPMM_OK;
+}
+
+int dpmm_trace_record(dpmm_ctx *c, int slot, int K) {
+    static const char *fn = "dpmm_trace_record";
+    if (!c) return tensor_no_ctx(fn);
+    const std::string who = std::string(fn) + ": ";
+    if (!c->d_trace) return fail(c, DPMM_ESTATE, who + "needs dpmm_trace_open first");
+    if (!c->have_labels) return fail(c, DPMM_ESTATE, who + "labels not initialised");
+    if (slot < 0 || slot >= c->trace_slots) return fail(c, DPMM_EINVAL, who + "slot " + std::to_string(slot) + " is outside 0.." + std::to_string(c->trace_slots - 1));
+    if (K < 1 || K > DPMM_MAX_CLUSTERS) return fail(c, DPMM_EINVAL, who + "K must be in 1..DPMM_MAX_CLUSTERS");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, launch_trace_record(c->dbins, c->n, trace_row(c, slot), c->trace_nvec, c->stream));
+    c->trace_K[slot] = K;
+    return DPMM_OK;
+}
+
+int dpmm_trace_tables(dpmm_ctx *c, const int32_t *pairs, int npairs, int64_t *counts) {
+    static const char *fn = "dpmm_trace_tables";
+    if (!c) return tensor_no_ctx(fn);
+    const std::string who = std::string(fn) + ": ";
+    if (npairs < 0 || (npairs > 0 && (!pairs || !counts))) return fail(c, DPMM_EINVAL, who + "npairs < 0 or a null pointer");
+    if (!c->d_trace) return fail(c, DPMM_ESTATE, who + "needs dpmm_trace_open first");
+    std::vector<size_t> off((size_t)npairs + 1, 0);
+    for (int p = 0; p < npairs; ++p) {
+        if (int rc = trace_slot_ok(c, who, pairs[2 * p])) return rc;
+        if (int rc = trace_slot_ok(c, who, pairs[2 * p + 1])) return rc;
+        off[p + 1] = off[p] + (size_t)c->trace_K[pairs[2 * p]] * (size_t)c->trace_K[pairs[2 * p + 1]];
+    }
+    const size_t total = off[npairs];
+    if (total == 0) return DPMM_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (c->n == 0) { memset(counts, 0, sizeof(int64_t) * total); return DPMM_OK; }
+    if (int rc = trace_buffer(c, reinterpret_cast<void **>(&c->d_trace_counts), &c->trace_counts_bytes, sizeof(unsigned long long) * total, fn, "tables")) return rc;
+    HIPCHK(c, hipMemsetAsync(c->d_trace_counts, 0, sizeof(unsigned long long) * total, c->stream));
+    // pairs by row slot (stable: a row's pairs keep their order), then consecutive pairs of a row into groups within the LDS budget
+    std::vector<int> order((size_t)npairs);
+    for (int p = 0; p < npairs; ++p) order[p] = p;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return pairs[2 * a] < pairs[2 * b]; });
+    std::vector<TraceGroup> groups;
+    std::vector<TracePair> tp;
+    std::vector<int> big;
+    int max_cells = 0;
+    for (int q = 0; q < npairs; ++q) {
+        const int p = order[q], s = pairs[2 * p], t = pairs[2 * p + 1];
+        const int Ks = c->trace_K[s], Kt = c->trace_K[t], cells = Ks * Kt;      // (at most 1024 * 1024)
+        if (cells > TRACE_LDS_CELLS) { big.push_back(p); continue; }
+        if (groups.empty() || groups.back().zs != trace_row(c, s) || groups.back().cells + cells > TRACE_LDS_CELLS) {
+            TraceGroup g{};
+            g.zs = trace_row(c, s); g.Ks = Ks; g.pair0 = (int)tp.size(); g.npairs = 0; g.cells = 0;
+            groups.push_back(g);
+        }
+        TraceGroup &g = groups.back();
+        TracePair e{};
+        e.zt = trace_row(c, t); e.Kt = Kt; e.cell0 = (unsigned)g.cells; e.out = c->d_trace_counts + off[p];
+        tp.push_back(e);
+        g.npairs += 1; g.cells += cells;
+        max_cells = std::max(max_cells, g.cells);
+    }
+    if (!groups.empty()) {
+        const size_t gb = (sizeof(TraceGroup) * groups.size() + 15) & ~(size_t)15, pb = sizeof(TracePair) * tp.size();
+        if (int rc = trace_buffer(c, reinterpret_cast<void **>(&c->d_trace_desc), &c->trace_desc_bytes, gb + pb, fn, "pair lists")) return rc;
+        HIPCHK(c, hipMemcpy(c->d_trace_desc, groups.data(), sizeof(TraceGroup) * groups.size(), hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(c->d_trace_desc + gb, tp.data(), pb, hipMemcpyHostToDevice));
+        HIPCHK(c, launch_trace_tables(reinterpret_cast<const TraceGroup *>(c->d_trace_desc), (int)groups.size(),
+                                      reinterpret_cast<const TracePair *>(c->d_trace_desc + gb), max_cells, c->trace_nvec, c->stream));
+    }
+    for (int p : big) {
+        const int s = pairs[2 * p], t = pairs[2 * p + 1];
+        HIPCHK(c, launch_trace_pair_global(trace_row(c, s), trace_row(c, t), c->trace_K[s], c->trace_K[t], c->trace_nvec, c->d_trace_counts + off[p], c->stream));
+    }
+    HIPCHK(c, hipMemcpyAsync(counts, c->d_trace_counts, sizeof(unsigned long long) * total, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, sync_stream(c, c->stream));
+    return DPMM_OK;
+}
+
+int dpmm_trace_confidence(dpmm_ctx *c, int anchor, const int32_t *slots, int nslots, const float *ratio, float *out_host, void *out_device) {
+    static const char *fn = "dpmm_trace_confidence";
+    if (!c) return tensor_no_ctx(fn);
+    const std::string who = std::string(fn) + ": ";
+    if (nslots < 1 || nslots > DPMM_TRACE_MAX_SLOTS) return fail(c, DPMM_EINVAL, who + "nslots must be in 1.." + std::to_string(DPMM_TRACE_MAX_SLOTS));
+    if (!slots || !ratio) return fail(c, DPMM_EINVAL, who + "slots or ratio is null");
+    if (!out_host && !out_device) return fail(c, DPMM_EINVAL, who + "no output given");
+    if (!c->d_trace) return fail(c, DPMM_ESTATE, who + "needs dpmm_trace_open first");
+    if (int rc = trace_slot_ok(c, who, anchor)) return rc;
+    const int Ka = c->trace_K[anchor];
+    std::vector<TraceConfSlot> cs((size_t)nslots);
+    uint64_t total = 0;
+    for (int j = 0; j < nslots; ++j) {
+        if (int rc = trace_slot_ok(c, who, slots[j])) return rc;
+        cs[j].z = trace_row(c, slots[j]); cs[j].K = c->trace_K[slots[j]]; cs[j].off = (unsigned)total;
+        total += (uint64_t)Ka * (uint64_t)cs[j].K;
+        if (total >> 32) return fail(c, DPMM_EINVAL, who + "the ratio tables hold 2^32 entries or more");
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    if (c->n == 0) return DPMM_OK;
+    if (out_device) if (int rc = check_device_extent(c, fn, "out_device", out_device, sizeof(float) * (uint64_t)c->n, sizeof(float))) return rc;
+    if (int rc = trace_buffer(c, reinterpret_cast<void **>(&c->d_trace_ratio), &c->trace_ratio_bytes, sizeof(float) * (size_t)total, fn, "ratio tables")) return rc;
+    if (int rc = trace_buffer(c, reinterpret_cast<void **>(&c->d_trace_desc), &c->trace_desc_bytes, sizeof(TraceConfSlot) * cs.size(), fn, "slot list")) return rc;
+    float *target = static_cast<float *>(out_device);
+    if (!target) {
+        if (int rc = trace_buffer(c, reinterpret_cast<void **>(&c->d_trace_conf), &c->trace_conf_bytes, sizeof(float) * (size_t)c->n, fn, "result")) return rc;
+        target = c->d_trace_conf;
+    }
+    HIPCHK(c, hipMemcpy(c->d_trace_ratio, ratio, sizeof(float) * (size_t)total, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->d_trace_desc, cs.data(), sizeof(TraceConfSlot) * cs.size(), hipMemcpyHostToDevice));
+    HIPCHK(c, launch_trace_confidence(trace_row(c, anchor), Ka, reinterpret_cast<const TraceConfSlot *>(c->d_trace_desc), nslots, c->d_trace_ratio, c->n,
+                                      c->trace_nvec, target, c->stream));
+    if (out_host) HIPCHK(c, hipMemcpyAsync(out_host, target, sizeof(float) * (size_t)c->n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, sync_stream(c, c->stream));
+    return DPMM_OK;
+}
+
+int dpmm_trace_read(dpmm_ctx *c, int slot, int64_t *labels_host, void *labels_device) {
+    static const char *fn = "dpmm_trace_read";
+    if (!c) return tensor_no_ctx(fn);
+    const std::string who = std::string(fn) + ": ";
+    if (!labels_host && !labels_device) return fail(c, DPMM_EINVAL, who + "no output given");
+    if (!c->d_trace) return fail(c, DPMM_ESTATE, who + "needs dpmm_trace_open first");
+    if (int rc = trace_slot_ok(c, who, slot)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (c->n == 0) return DPMM_OK;
+    if (labels_device) if (int rc = check_device_extent(c, fn, "labels_device", labels_device, sizeof(int64_t) * (uint64_t)c->n, sizeof(int64_t))) return rc;
+    int64_t *tmp = nullptr, *target = static_cast<int64_t *>(labels_device);
+    if (!target) {
+        HIPCHK(c, hipMalloc(&tmp, sizeof(int64_t) * (size_t)c->n));
+        target = tmp;
+    }
+    hipError_t e = launch_trace_read(trace_row(c, slot), c->n, target, c->stream);
+    if (e == hipSuccess && labels_host) e = hipMemcpyAsync(labels_host, target, sizeof(int64_t) * (size_t)c->n, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = sync_stream(c, c->stream);
+    hipFree(tmp);
+    if (e != hipSuccess) { c->err = who + hipGetErrorString(e); return DPMM_EHIP; }
+    return DPMM_OK;
+}
 
 // ---- include/dpmm_hip_sample.h: drawing points from a fitted model (sample.hip) -------------------------------------------------------
 static int sampler_table(dpmm_ctx *c, void **dst, const void *src, size_t bytes) {

@@ -234,6 +234,25 @@ struct MissArgs {
 hipError_t launch_miss_transpose(const float *Rpk, int64_t step, float *Rt, int K, int D, hipStream_t s);      // Rpk: packed upper triangles, cluster k at Rpk + k * step
 hipError_t launch_miss_list(const MissArgs &a, hipStream_t s);
 hipError_t launch_miss_patch(const MissArgs &a, bool impute, int max_grid, hipStream_t s);
+// ---- label trace (trace.hip; include/dpmm_hip_trace.h).  A row holds nvec 16-byte vectors of 8 ids, padded with 0xFFFF.
+constexpr int TRACE_LDS_CELLS = 16384;    // 32-bit counters of a group of tables in LDS (64 KiB)
+struct TracePair {                        // one table of a group
+    const uint16_t *zt;                   // the column slot's row
+    int Kt;
+    unsigned cell0;                       // first cell of the table inside the group's LDS image
+    unsigned long long *out;              // the table [Ks][Kt] in the device image of the result
+};
+struct TraceGroup {                       // consecutive pairs of one row slot, cells <= TRACE_LDS_CELLS
+    const uint16_t *zs;
+    int Ks, pair0, npairs, cells;         // pairs [pair0, pair0 + npairs) of the TracePair array
+};
+struct TraceConfSlot { const uint16_t *z; int K; unsigned off; };      // a listed slot of dpmm_trace_confidence: row, K, first float of its ratio table
+hipError_t launch_trace_record(const int32_t *bins, int64_t n, uint16_t *row, int64_t nvec, hipStream_t s);
+hipError_t launch_trace_tables(const TraceGroup *groups, int ngroups, const TracePair *pairs, int max_cells, int64_t nvec, hipStream_t s);
+hipError_t launch_trace_pair_global(const uint16_t *zs, const uint16_t *zt, int Ks, int Kt, int64_t nvec, unsigned long long *out, hipStream_t s);
+hipError_t launch_trace_confidence(const uint16_t *za, int Ka, const TraceConfSlot *slots, int ns, const float *ratio, int64_t n, int64_t nvec,
+                                   float *out, hipStream_t s);
+hipError_t launch_trace_read(const uint16_t *row, int64_t n, int64_t *labels, hipStream_t s);
 // ---- drawing points (sample.hip; include/dpmm_hip_sample.h): n samples from global index i0; every output pointer is that of the call's
 // first sample
 struct SampleArgs {

@@ -10,4 +10,5 @@ from .api import fit, dp_parallel, predict, run_model_from_checkpoint, resume_fr
 from .sampler import DPMMSampler, LocalComm  # noqa: E402,F401
 from .score import Predictor, Exemplars, score_samples, predict_topk, exemplars, sample, impute  # noqa: E402,F401
 from .project import Projection, fit_projection, random_projection  # noqa: E402,F401
+from .summary import PosteriorSummary  # noqa: E402,F401
 from .checkpoint import load_data, save_model, load_checkpoint  # noqa: E402,F401

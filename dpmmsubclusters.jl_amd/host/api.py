@@ -31,7 +31,9 @@ from . import checkpoint as _ckpt
 from . import sparse as _sparse
 from . import tensors as _tensors
 from . import project as _project
+from . import summary as _summary
 from .priors import multinomial_hyper, niw_hyperparams
+from . import sampler as _sampler_mod
 from .sampler import DPMMSampler, LocalComm
 
 
@@ -45,6 +47,7 @@ class dp_parallel_sampling:
         self.labels = labels
         self.labels_subcluster = sub_labels
         self.projection = getattr(sampler, "projection", None)      # host/project.py: the model was fitted on projected coordinates
+        self.summary = None                                         # host/summary.py: a PosteriorSummary when keep_samples > 0
 
     @property
     def num_clusters(self):
@@ -173,24 +176,48 @@ def _comm_device(comm, device):
     return comm, device
 
 
+def _run_and_wrap(s, comm, iters, first_iter, verbose, gt, hook, keep_samples, thin, loss):
+    """run_model, the final labels and the result handle; with keep_samples > 0 the label trace around them (host/summary.py)."""
+    trace = None
+    if keep_samples:
+        its = _summary.schedule(iters, first_iter, s.argmax_sample_stop, keep_samples, thin)
+        trace = _summary.TraceRecorder(s, its, inner=hook)
+    iter_count, nmi, lik, kh = s.run_model(int(iters), first_iter, verbose=verbose, gt=gt, on_iteration=trace or hook)
+    labels, sub = _final_labels(s, comm)
+    model = dp_parallel_sampling(s, labels, sub)
+    model.checkpoints = hook.files if hook else []
+    if trace is not None:
+        trace.finish(iters)
+        model.summary = _summary.PosteriorSummary(trace, loss)
+    return model, iter_count, nmi, lik, kh
+
+
 def dp_parallel(all_data, local_hyper_params=None, alpha_param=None, iters=100, init_clusters=1, seed=None, verbose=True,
                 save_model=False, burnout=15, gt=None, max_clusters=np.inf, outlier_weight=0, outlier_params=None,
                 smart_splits=False, comm=None, device=None, nthreads=None, worker_factory=None, save_path="./",
-                save_file_prefix="checkpoint_", model_save_interval=1000, project=None):
+                save_file_prefix="checkpoint_", model_save_interval=1000, project=None, keep_samples=0, thin=1, loss="vi"):
     """dp_parallel(all_data, hyper_params, alpha, ...) -- basic mode (dp-parallel-sampling.jl:121-157), or
     dp_parallel(model_params::String; verbose, gt) -- advanced mode driven by a parameter file (:178-196).
     Returns (dp_model, iter_count, nmi_score_history, likelihood_history, cluster_count_history).
     `save_model=True` writes a checkpoint every `model_save_interval` iterations (global_params.jl:36-41 defaults).
     `project`: a host/project.py Projection, or an int d (= fit_projection(all_data, d, seed=seed or 0); one rank only): `all_data` then
-    has D_in rows, the prior dimension d, and the GPU projects the points while it reads them (Gaussian prior, dense data)."""
+    has D_in rows, the prior dimension d, and the GPU projects the points while it reads them (Gaussian prior, dense data).
+    `keep_samples=T > 0` (basic mode): the labels of T sweeps, `thin` apart, ending with the last sweep that samples its labels, stay on
+    the GPU, and `dp_model.summary` is a host/summary.py PosteriorSummary -- the sampled clustering with the smallest posterior expected
+    `loss` ("vi" or "binder") and a per-point confidence.  The chain itself, and every other result, is unchanged."""
     if isinstance(all_data, (str, bytes)) or hasattr(all_data, "__fspath__"):
         if project is not None:
             raise TypeError("project= is for the basic mode (arrays and tensors), not for a parameter file")
+        if keep_samples != 0 or thin != 1 or loss != "vi":
+            raise TypeError("keep_samples / thin / loss are for the basic mode (arrays and tensors), not for a parameter file")
         return _dp_parallel_from_params(str(all_data), verbose=verbose, gt=gt, comm=comm, device=device, nthreads=nthreads,
                                         worker_factory=worker_factory)
     if not isinstance(local_hyper_params, _priors.distribution_hyper_params):
         raise TypeError("local_hyper_params must be a distribution_hyper_params (niw_hyperparams / multinomial_hyper)")
     _check_next_rows(outlier_weight, outlier_params, smart_splits, local_hyper_params)
+    _summary.check_arguments(keep_samples, thin, loss)
+    if keep_samples:
+        _summary.schedule(iters, 1, _sampler_mod.ARGMAX_SAMPLE_STOP, keep_samples, thin)      # (refuse before anything is uploaded)
     if project is not None and local_hyper_params.kind != _priors.PRIOR_NIW:
         raise TypeError("project= is for the Gaussian (niw_hyperparams) prior only")
     comm, device = _comm_device(comm, _data_device(all_data, device))
@@ -203,11 +230,7 @@ def dp_parallel(all_data, local_hyper_params=None, alpha_param=None, iters=100, 
         s.outlier_weight, s.outlier_prior = float(outlier_weight), outlier_params
     s.init_first_clusters(int(init_clusters))
     hook = _ckpt.SaveHook(save_path, save_file_prefix, model_save_interval, "none", 0.0, verbose) if save_model else None
-    iter_count, nmi, lik, kh = s.run_model(int(iters), 1, verbose=verbose, gt=gt, on_iteration=hook)
-    labels, sub = _final_labels(s, comm)
-    model = dp_parallel_sampling(s, labels, sub)
-    model.checkpoints = hook.files if hook else []
-    return model, iter_count, nmi, lik, kh
+    return _run_and_wrap(s, comm, int(iters), 1, verbose, gt, hook, int(keep_samples), int(thin), loss)
 
 
 def _sampler_from_params(P, comm, device, nthreads, worker_factory):
@@ -264,10 +287,12 @@ def run_model_from_checkpoint(filename, verbose=True, gt=None, comm=None, device
 
 def resume_from_checkpoint(filename, all_data, iters, verbose=True, gt=None, burnout=None, max_clusters=np.inf, comm=None,
                            device=None, nthreads=None, worker_factory=None, save_model=False, save_path="./",
-                           save_file_prefix="checkpoint_", model_save_interval=1000, project=None):
+                           save_file_prefix="checkpoint_", model_save_interval=1000, project=None, keep_samples=0, thin=1, loss="vi"):
     """Basic-mode counterpart of run_model_from_checkpoint: the caller supplies the data array again (D x N) and the
     total number of iterations; the chain continues at iter+1 exactly where the checkpoint left it.  A model fitted with `project`
-    is given the same projection again (the checkpoint file does not hold it)."""
+    is given the same projection again (the checkpoint file does not hold it).  `keep_samples`, `thin`, `loss`: as dp_parallel; the
+    recorded sweeps must lie in the part of the chain this call runs."""
+    _summary.check_arguments(keep_samples, thin, loss)
     ck = _ckpt.load_checkpoint(filename)
     comm, device = _comm_device(comm, _data_device(all_data, device))
     gt = _tensors.host_int64(gt)
@@ -277,16 +302,13 @@ def resume_from_checkpoint(filename, all_data, iters, verbose=True, gt=None, bur
                       max_clusters, comm, device, nthreads, worker_factory, projection=project)
     _ckpt.restore_sampler(s, ck)
     hook = _ckpt.SaveHook(save_path, save_file_prefix, model_save_interval, "none", float(ck["total_time"]), verbose) if save_model else None
-    iter_count, nmi, lik, kh = s.run_model(int(iters), int(ck["iter"]) + 1, verbose=verbose, gt=gt, on_iteration=hook)
-    labels, sub = _final_labels(s, comm)
-    model = dp_parallel_sampling(s, labels, sub)
-    model.checkpoints = hook.files if hook else []
-    return model, iter_count, nmi, lik, kh
+    return _run_and_wrap(s, comm, int(iters), int(ck["iter"]) + 1, verbose, gt, hook, int(keep_samples), int(thin), loss)
 
 
 def fit(all_data, *args, iters=100, init_clusters=1, seed=None, verbose=True, save_model=False, burnout=20, gt=None,
         max_clusters=np.inf, outlier_weight=0, outlier_params=None, smart_splits=False, **kw):
-    """fit(all_data, alpha; ...) or fit(all_data, hyper_params, alpha; ...).
+    """fit(all_data, alpha; ...) or fit(all_data, hyper_params, alpha; ...).  Further keywords go to dp_parallel: `project`, and
+    `keep_samples`, `thin`, `loss` for a posterior summary (`dp_model.summary`, host/summary.py).
 
     Returns the reference's 9-tuple: (labels, clusters, weights, iter_count, nmi_score_history,
     likelihood_history, cluster_count_history, sub_labels, dp_model)."""
