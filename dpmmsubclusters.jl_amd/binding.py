@@ -526,10 +526,14 @@ class Worker:
 
     # ---- prediction (posterior predictive table)
     def predict_table_niw(self, m, R, logdet, df, weights, points=False):
-        K = len(weights)
-        m, R, logdet, df, weights = map(_f32, (m, R, logdet, df, weights))
-        assert m.shape == (K, self.D) and R.size == K * self.D * self.D
-        self._chk(self._lib.dpmm_set_predictive_niw(self._h, K, _p(m, _c_f32p), _p(R, _c_f32p), _p(logdet, _c_f32p), _p(df, _c_f32p), _p(weights, _c_f32p)))
+        self.set_predictive_niw(m, R, logdet, df, weights)
+        return self._predict_table(len(weights), points)
+
+    def predict_table_mult(self, logp, weights, points=False):
+        self.set_predictive_mult(logp, weights)
+        return self._predict_table(len(weights), points)
+
+    def _predict_table(self, K, points):
         self.K = K
         if points:
             return self._predict_points(K)
@@ -750,18 +754,6 @@ class Worker:
             return out
         out = np.empty(self.n, np.int64)
         self._chk(self._lib.dpmm_trace_read(self._h, int(slot), _p(out, _c_i64p), None))
-        return out
-
-    def predict_table_mult(self, logp, weights, points=False):
-        K = len(weights)
-        logp, weights = _f32(logp), _f32(weights)
-        assert logp.shape == (K, self.D)
-        self._chk(self._lib.dpmm_set_predictive_mult(self._h, K, _p(logp, _c_f32p), _p(weights, _c_f32p)))
-        self.K = K
-        if points:
-            return self._predict_points(K)
-        out = np.empty((K, self.n), np.float32)
-        self._chk(self._lib.dpmm_predict(self._h, _p(out, _c_f32p)))
         return out
 
     # ---- on-device evaluation

@@ -28,7 +28,7 @@ import numpy as np
 from .. import binding
 from . import priors as _priors
 from . import checkpoint as _ckpt
-from . import sparse as _sparse
+from . import points as _points
 from . import tensors as _tensors
 from . import project as _project
 from . import summary as _summary
@@ -60,30 +60,18 @@ def _shard(N, comm):
     return lo, hi
 
 
-def _make_sampler(all_data, hyper, alpha, seed, burnout, max_clusters, comm, device, nthreads=None, worker_factory=None,
-                  rows=None, projection=None, **sampler_kw):
-    """`all_data`: Dimensions x Samples (basic mode), or `rows`: Samples x Dimensions as stored in a .npy file (advanced
-    mode; cleaned and converted on the GPU by dpmm_upload_points_npy)."""
-    csc = None if rows is not None else _sparse.as_csc(all_data)
+def _make_sampler(pts, hyper, alpha, seed, burnout, max_clusters, comm, device, nthreads=None, worker_factory=None, projection=None,
+                  **sampler_kw):
+    """`pts`: the host/points.py description of the data -- Dimensions x Samples (basic mode), or the Samples x Dimensions rows of a .npy
+    file (advanced mode; cleaned and converted on the GPU by dpmm_upload_points_npy)."""
     if projection is not None:
         if hyper.kind != _priors.PRIOR_NIW:
             raise TypeError("project= is for the Gaussian (niw_hyperparams) prior only")
-        if csc is not None or rows is not None:
+        if pts.is_sparse:
             raise TypeError("project= takes dense data (an array or a tensor), Dimensions x Samples")
-    desc = None if rows is not None or csc is not None else _tensors.as_device_points(all_data)
-    if rows is not None:
-        N, D = rows.shape
-    elif desc is not None:
-        D, N = desc.shape
-    elif csc is not None:
-        if hyper.kind != _priors.PRIOR_MULT:
-            raise TypeError("sparse data is for the Multinomial prior (multinomial_hyper); the Gaussian prior takes a dense array")
-        D, N = csc.shape
-    else:
-        X = np.asarray(_tensors.as_host_array(all_data))
-        if X.ndim != 2:
-            raise ValueError("all_data must be Dimensions x Samples")
-        D, N = X.shape
+    if pts.is_sparse and hyper.kind != _priors.PRIOR_MULT:
+        raise TypeError("sparse data is for the Multinomial prior (multinomial_hyper); the Gaussian prior takes a dense array")
+    D, N = pts.D, pts.N
     if projection is not None:
         if D != projection.D_in:
             raise ValueError(f"data dimension {D} != the projection's input dimension {projection.D_in}")
@@ -98,33 +86,11 @@ def _make_sampler(all_data, hyper, alpha, seed, burnout, max_clusters, comm, dev
     wk = (worker_factory or binding.Worker)(hyper.kind, D, hi - lo, first_index=lo, device=device, seed=int(seed), **kw)
     if projection is not None:
         projection.apply(wk)
-        if desc is not None and hasattr(wk, "upload_points_projected_tensor"):
-            desc.synchronize()
-            wk.upload_points_projected_tensor(desc, lo, hi)
-        elif desc is not None:
-            wk.upload_points_projected(np.ascontiguousarray(desc.tensor[:, lo:hi].T.float().cpu().numpy()))
-        else:
-            wk.upload_points_projected(np.ascontiguousarray(X[:, lo:hi].T, dtype=np.float32))
-    elif rows is not None:
-        if hasattr(wk, "upload_points_npy"):
-            wk.upload_points_npy(rows[lo:hi])
-        else:
-            wk.upload_points(np.nan_to_num(np.asarray(rows[lo:hi], dtype=np.float32), nan=0.0, posinf=np.inf, neginf=-np.inf))
-    elif desc is not None:
-        if hasattr(wk, "upload_points_tensor"):
-            desc.synchronize()                        # the tensor is complete before the library reads it on its own stream
-            wk.upload_points_tensor(desc, lo, hi)     # points [lo, hi) where they are: an address, no copy and no slicing on the host
-        else:                                         # (test stand-ins, third-party worker factories -- as the sparse path falls back)
-            wk.upload_points(np.ascontiguousarray(desc.tensor[:, lo:hi].T.float().cpu().numpy()))
-    elif csc is not None:
-        _sparse.upload_columns(wk, csc, lo, hi)       # columns [lo, hi): no rank touches another rank's entries
-    else:
-        wk.upload_points(np.ascontiguousarray(X[:, lo:hi].T, dtype=np.float32))  # (n_local, D): row = point
+    pts.synchronize()                                  # a tensor is complete before the library reads it on its own stream
+    pts.upload(wk, lo, hi, projected=projection is not None, results=True)
     s = DPMMSampler(wk, hyper, alpha, N, int(seed), burnout=burnout, max_clusters=max_clusters, comm=comm, nthreads=nthreads,
                     **sampler_kw)
-    if desc is None and isinstance(csc, _sparse.DeviceCSC):
-        desc = csc                                     # (a sparse tensor in device memory: the same three attributes are read of it)
-    s.data_tensor = desc                               # results follow the input (_final_labels)
+    s.data_device = pts.torch_device                   # results follow the input (_final_labels, host/summary.py)
     s.projection = projection
     return s
 
@@ -132,27 +98,13 @@ def _make_sampler(all_data, hyper, alpha, seed, burnout, max_clusters, comm, dev
 def _final_labels(s, comm):
     """(labels, sub_labels) of the whole data set.  numpy, as ever -- unless the points came from a device tensor: then int64 tensors on
     that device, written there by the library when one rank holds all points, else gathered as ever and moved."""
-    desc = getattr(s, "data_tensor", None)
-    if desc is None:
+    dev = getattr(s, "data_device", None)
+    if dev is None:
         return comm.gather_labels(s.wk)
     if getattr(comm, "world", 1) == 1 and hasattr(s.wk, "get_labels_tensor"):
-        return s.wk.get_labels_tensor(desc.torch_device)
+        return s.wk.get_labels_tensor(dev)
     import torch
-    labels, sub = comm.gather_labels(s.wk)
-    return (torch.from_numpy(np.ascontiguousarray(labels, np.int64)).to(desc.torch_device),
-            torch.from_numpy(np.ascontiguousarray(sub, np.int64)).to(desc.torch_device))
-
-
-def _data_device(all_data, device):
-    """The `device` argument, or -- for a tensor in device memory -- that tensor's device (an explicit `device` must agree)."""
-    csc = _sparse.as_csc(all_data)
-    if isinstance(csc, _sparse.DeviceCSC):
-        return _tensors.resolve_device(csc, device)
-    if csc is None:
-        desc = _tensors.as_device_points(all_data)
-        if desc is not None:
-            return _tensors.resolve_device(desc, device)
-    return device
+    return tuple(torch.from_numpy(np.ascontiguousarray(a, np.int64)).to(dev) for a in comm.gather_labels(s.wk))
 
 
 def _check_next_rows(outlier_weight, outlier_params, smart_splits, hyper=None):
@@ -220,10 +172,11 @@ def dp_parallel(all_data, local_hyper_params=None, alpha_param=None, iters=100, 
         _summary.schedule(iters, 1, _sampler_mod.ARGMAX_SAMPLE_STOP, keep_samples, thin)      # (refuse before anything is uploaded)
     if project is not None and local_hyper_params.kind != _priors.PRIOR_NIW:
         raise TypeError("project= is for the Gaussian (niw_hyperparams) prior only")
-    comm, device = _comm_device(comm, _data_device(all_data, device))
+    pts = _points.describe(all_data)
+    comm, device = _comm_device(comm, pts.device_index(device))     # a tensor in device memory: its device (an explicit `device` must agree)
     gt = _tensors.host_int64(gt)
     project = _project.resolve(project, all_data, seed, comm)
-    s = _make_sampler(all_data, local_hyper_params, np.float32(alpha_param), seed, int(burnout), max_clusters, comm, device,
+    s = _make_sampler(pts, local_hyper_params, np.float32(alpha_param), seed, int(burnout), max_clusters, comm, device,
                       nthreads, worker_factory, projection=project)
     s.smart_splits = bool(smart_splits)
     if outlier_weight and outlier_weight > 0:
@@ -237,8 +190,8 @@ def _sampler_from_params(P, comm, device, nthreads, worker_factory):
     use_outlier = P["outlier_hyper_params"] is not None and P["outlier_mod"] and P["outlier_mod"] > 0
     _check_next_rows(P["outlier_mod"] if use_outlier else 0, P["outlier_hyper_params"], P["smart_splits"], P["hyper_params"])
     rows = _ckpt.load_data(P["data_path"], P["data_prefix"], swapDimension=False, mmap=True)     # Samples x Dimensions
-    s = _make_sampler(None, P["hyper_params"], np.float32(P["alpha"]), P["random_seed"], int(P["burnout_period"]),
-                      P["max_clusters"], comm, device, nthreads, worker_factory, rows=rows,
+    s = _make_sampler(_points.describe(None, rows), P["hyper_params"], np.float32(P["alpha"]), P["random_seed"], int(P["burnout_period"]),
+                      P["max_clusters"], comm, device, nthreads, worker_factory,
                       argmax_sample_stop=int(P["argmax_sample_stop"]), split_stop=int(P["split_stop"]))
     s.hard_clustering = bool(P["hard_clustering"])
     s.smart_splits = bool(P["smart_splits"])
@@ -294,11 +247,12 @@ def resume_from_checkpoint(filename, all_data, iters, verbose=True, gt=None, bur
     recorded sweeps must lie in the part of the chain this call runs."""
     _summary.check_arguments(keep_samples, thin, loss)
     ck = _ckpt.load_checkpoint(filename)
-    comm, device = _comm_device(comm, _data_device(all_data, device))
+    pts = _points.describe(all_data)
+    comm, device = _comm_device(comm, pts.device_index(device))
     gt = _tensors.host_int64(gt)
     hyper = _ckpt._prior_from_dict(ck)
     project = _project.resolve(project, all_data, int(ck["seed"]), comm)
-    s = _make_sampler(all_data, hyper, np.float32(ck["alpha"]), int(ck["seed"]), int(ck["burnout"] if burnout is None else burnout),
+    s = _make_sampler(pts, hyper, np.float32(ck["alpha"]), int(ck["seed"]), int(ck["burnout"] if burnout is None else burnout),
                       max_clusters, comm, device, nthreads, worker_factory, projection=project)
     _ckpt.restore_sampler(s, ck)
     hook = _ckpt.SaveHook(save_path, save_file_prefix, model_save_interval, "none", float(ck["total_time"]), verbose) if save_model else None
@@ -313,9 +267,10 @@ def fit(all_data, *args, iters=100, init_clusters=1, seed=None, verbose=True, sa
     Returns the reference's 9-tuple: (labels, clusters, weights, iter_count, nmi_score_history,
     likelihood_history, cluster_count_history, sub_labels, dp_model)."""
     if len(args) == 1:
-        if _sparse.as_csc(all_data) is not None:
+        pts = _points.describe(all_data)
+        if pts.is_sparse:
             raise TypeError("sparse data is for the Multinomial prior: fit(all_data, multinomial_hyper(...), alpha)")
-        D = all_data.shape[0] if _tensors.is_tensor(all_data) else np.asarray(all_data).shape[0]
+        D = pts.D
         project = kw.get("project")
         if project is not None:                   # the default prior is built for the projected space
             if isinstance(project, _project.Projection):
@@ -346,24 +301,14 @@ def predict(dp_model, data, device=None, worker_factory=None):
     writes them there, the table never crosses the host link."""
     s = dp_model.sampler
     post = s.post
-    csc = _sparse.as_csc(data)
-    desc = None if csc is not None else _tensors.as_device_points(data)
-    if desc is not None and not hasattr(worker_factory or binding.Worker, "upload_points_tensor"):
-        data, desc = desc.tensor.float().cpu().numpy(), None          # (a stand-in worker without the device entry points)
+    factory = worker_factory or binding.Worker
+    pts = _points.describe(data).served(factory, results=True)       # (a stand-in worker without the device entry points: host data)
+    if pts.is_sparse and s.prior.kind != _priors.PRIOR_MULT:
+        raise TypeError("sparse data is for the Multinomial prior")
+    device = pts.device_index(device)
+    D, n = pts.D, pts.N
     proj = getattr(dp_model, "projection", None)
-    if csc is not None:
-        if s.prior.kind != _priors.PRIOR_MULT:
-            raise TypeError("sparse data is for the Multinomial prior")
-        D, n = csc.shape
-        if isinstance(csc, _sparse.DeviceCSC):
-            device = _tensors.resolve_device(csc, device)
-    elif desc is not None:
-        D, n = desc.shape
-        device = _tensors.resolve_device(desc, device)
-    else:
-        X = np.ascontiguousarray(np.asarray(_tensors.as_host_array(data), dtype=np.float32).T)
-        n, D = X.shape
-    proj = proj if proj is not None and csc is None and D == proj.D_in else None      # d-row data is taken as already projected
+    proj = proj if proj is not None and not pts.is_sparse and D == proj.D_in else None      # d-row data is taken as already projected
     if proj is not None:
         D = proj.d
     if D != s.prior.dim:
@@ -371,24 +316,12 @@ def predict(dp_model, data, device=None, worker_factory=None):
     w = s.points_count.astype(np.float64) + s.alpha
     w = (w / w.sum()).astype(np.float32)
     dev = getattr(s.wk, "device", 0) if device is None else device
-    wk = (worker_factory or binding.Worker)(s.prior.kind, D, n, first_index=0, device=dev, seed=0)
+    wk = factory(s.prior.kind, D, n, first_index=0, device=dev, seed=0)
     try:
         if proj is not None:
             proj.apply(wk)
-            if desc is not None and hasattr(wk, "upload_points_projected_tensor"):
-                desc.synchronize()
-                wk.upload_points_projected_tensor(desc, 0, n)
-            elif desc is not None:
-                wk.upload_points_projected(np.ascontiguousarray(desc.tensor.T.float().cpu().numpy()))
-            else:
-                wk.upload_points_projected(X)
-        elif csc is not None:
-            _sparse.upload_columns(wk, csc, 0, n)
-        elif desc is not None:
-            desc.synchronize()
-            wk.upload_points_tensor(desc, 0, n)
-        else:
-            wk.upload_points(X)
+        pts.synchronize()
+        pts.upload(wk, 0, n, projected=proj is not None, results=True)
         if getattr(wk, "supports_predict_points", False):     # argmax + normalisation on the device as well
             return s.prior.predictive_table(wk, post, [3 * k for k in range(s.K)], w, points=True)
         parr = s.prior.predictive_table(wk, post, [3 * k for k in range(s.K)], w).T.astype(np.float32)   # (n, K)

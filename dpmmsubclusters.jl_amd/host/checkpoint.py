@@ -39,7 +39,7 @@ DEFAULTS = dict(                      # src/global_params.jl
 def load_data(path, prefix="", swapDimension=True, mmap=False):
     """utils.jl:5-14.  Returns Dimensions x Samples (a transposed view) with NaN replaced by 0; with
     `swapDimension=False` the array as stored.  `mmap=True` returns the read-only memory map untouched (no NaN
-    pass on the host): the caller hands row blocks to `Worker.upload_points_npy`, which cleans them on the GPU."""
+    pass on the host): the caller hands row blocks to the worker (host/points.py), which cleans them on the GPU."""
     fn = os.path.join(path, prefix + ".npy") if not str(path).endswith(".npy") else path
     if not os.path.exists(fn):
         fn = str(path) + prefix + ".npy"            # the reference concatenates path * prefix * ".npy"

@@ -12,6 +12,7 @@ import warnings
 import numpy as np
 
 from .. import binding
+from . import points as _points
 from . import priors as _priors
 from . import tensors as _tensors
 
@@ -100,29 +101,25 @@ class Projection:
         """(d, n) Float32 coordinates of `data` (D_in, n), computed on the GPU in slabs of `capacity` points: projected upload, then the
         points read back.  For a tensor in device memory the result is a tensor on that device whose memory is point-major (the `.T` of
         an (n, d) tensor: what `fit` reads in place); otherwise a numpy array."""
-        desc = _tensors.as_device_points(data)
+        pts = _points.describe(data)
         cap = int(capacity)
         if cap < 1:
             raise ValueError("capacity must be at least 1")
+        if pts.is_sparse:
+            raise TypeError("a projection takes dense data (an array or a tensor), Dimensions x Samples")
         factory = worker_factory or binding.Worker
-        if desc is not None and not hasattr(factory, "upload_points_projected_strided_device"):
-            data, desc = desc.tensor.float().cpu().numpy(), None
-        if desc is not None:
-            import torch
-            D_in, n = desc.shape
-            dev = _tensors.resolve_device(desc, device)
-        else:
-            X = np.asarray(_tensors.as_host_array(data))
-            if X.ndim != 2:
-                raise ValueError("data must be 2-D, Dimensions x Samples")
-            D_in, n = X.shape
-            dev = 0 if device is None else device
+        pts = pts.served(factory, projected=True)      # (a stand-in worker without the device entry points: host data)
+        D_in, n = pts.D, pts.N
         if D_in != self.D_in:
             raise ValueError(f"data has {D_in} rows, the projection reads {self.D_in}")
+        dev = pts.device_index(device)
+        dev = 0 if dev is None else dev
         d = self.d
-        out = torch.empty((n, d), dtype=torch.float32, device=desc.torch_device) if desc is not None else np.empty((n, d), np.float32)
-        if desc is not None:
-            desc.synchronize()
+        on_device = pts.torch_device is not None
+        if on_device:
+            import torch
+        out = torch.empty((n, d), dtype=torch.float32, device=pts.torch_device) if on_device else np.empty((n, d), np.float32)
+        pts.synchronize()
         workers = {}
         try:
             for lo in range(0, n, cap):
@@ -131,19 +128,17 @@ class Projection:
                 if wk is None:
                     wk = workers[m] = factory(_priors.PRIOR_NIW, d, m, first_index=0, device=dev, seed=0)
                     self.apply(wk)
-                if desc is not None:
-                    wk.upload_points_projected_strided_device(desc.shard_ptr(lo), desc.dtype, desc.stride_point, desc.stride_feature)
+                pts.upload(wk, lo, lo + m, projected=True)
+                if on_device:
                     wk.get_points_device(out.data_ptr() + 4 * lo * d, d)
+                elif hasattr(wk, "get_points"):
+                    out[lo:lo + m] = wk.get_points()
                 else:
-                    wk.upload_points_projected(np.ascontiguousarray(X[:, lo:lo + m].T, dtype=np.float32))
-                    if hasattr(wk, "get_points"):
-                        out[lo:lo + m] = wk.get_points()
-                    else:
-                        import torch
-                        t = torch.empty((m, d), dtype=torch.float32, device=torch.device("cuda", int(dev or 0)))
-                        torch.cuda.current_stream(t.device).synchronize()
-                        wk.get_points_device(t.data_ptr(), d)
-                        out[lo:lo + m] = t.cpu().numpy()
+                    import torch
+                    t = torch.empty((m, d), dtype=torch.float32, device=torch.device("cuda", int(dev or 0)))
+                    torch.cuda.current_stream(t.device).synchronize()
+                    wk.get_points_device(t.data_ptr(), d)
+                    out[lo:lo + m] = t.cpu().numpy()
         finally:
             for wk in workers.values():
                 wk.close()

@@ -23,9 +23,9 @@ import collections
 import numpy as np
 
 from .. import binding
+from . import points as _points
 from . import priors as _priors
-from . import sparse as _sparse
-from . import tensors as _tensors
+from . import tensors as _tensors      # noqa: F401  (the recognisers of host/points.py, reachable from here: tests patch them under this name)
 from . import project as _project
 
 
@@ -84,6 +84,21 @@ def _device_index(device):
 
 
 MISSING_MODES = ("propagate", "marginalize")
+
+
+class _Stages:
+    """The staging of a Predictor's short slab as host/points.py asks for it -- "host", "dev", "csc" -- kept on the Predictor as
+    `_host_stage`, `_dev_stage`, `_csc_stage`; suffix "_in": the D_in-wide ones of dense data that is projected on the way in."""
+
+    def __init__(self, owner, suffix):
+        self.owner, self.suffix = owner, suffix
+
+    def get(self, kind, make, fits=lambda st: True):
+        """The kept storage if there is one and it fits, else what `make()` returns, kept from now on."""
+        name = f"_{kind}_stage{self.suffix}"
+        if getattr(self.owner, name) is None or not fits(getattr(self.owner, name)):
+            setattr(self.owner, name, make())
+        return getattr(self.owner, name)
 
 
 class Predictor:
@@ -228,28 +243,18 @@ class Predictor:
         mask = {"typical": binding.RANK_TYPICAL, "fringe": binding.RANK_FRINGE, "both": binding.RANK_TYPICAL | binding.RANK_FRINGE}.get(which)
         if mask is None:
             raise ValueError('which must be "typical", "fringe" or "both"')
-        wk, cap = self._wk, self.capacity
+        wk = self._wk
         if not hasattr(wk, "rank_begin"):
             raise RuntimeError("this Predictor's worker cannot rank points (no dpmm_rank_begin)")
-        n, dev, _, upload = self._open(data)
+        opened = self._open(data)
         wk.rank_begin(m, mask)
-        counts = np.zeros(2, np.int64)
-        for lo in range(0, n, cap):
-            hi = min(n, lo + cap)
-            upload(lo, hi)
-            wk.rank_accumulate(lo, hi - lo)
-            counts += self._slab_counts()
-        self.missing_counts = (int(counts[0]), int(counts[1]))
-        r = wk.rank_read(device=dev)
+        self._walk(opened, [], lambda views, lo, hi: wk.rank_accumulate(lo, hi - lo))
+        r = wk.rank_read(device=opened[1])
         typ, fr = mask & binding.RANK_TYPICAL, mask & binding.RANK_FRINGE
         return Exemplars(r["typ_idx"] if typ else None, r["typ_score"] if typ else None, r["fringe_idx"] if fr else None,
                          r["fringe_score"] if fr else None, r["count"], int(r["skipped"][0]))
 
     # ---- missing features (include/dpmm_hip_missing.h)
-    def _slab_counts(self):
-        """(marginalised, over the cap) of the slab the worker has just evaluated; zeros under "propagate" (the worker is not asked)."""
-        return np.asarray(self._wk.score_missing_counts() if self.missing == "marginalize" else (0, 0), np.int64)
-
     def impute(self, data):
         """(D, n) float32: `data` converted to Float32 with the NaN features of every point that has 1 .. min(16, D - 1) of them replaced
         by sum_k p_k E[x_M | x_O, k] -- the conditional means of the clusters' Student-t predictives, mixed with the probabilities
@@ -261,27 +266,12 @@ class Predictor:
             raise RuntimeError("this Predictor is closed")
         if self.kind != _priors.PRIOR_NIW:
             raise ValueError("impute is for the NIW prior: the Multinomial prior has no missing features")
-        wk, cap, D = self._wk, self.capacity, self.D
+        wk = self._wk
         if not hasattr(wk, "impute_points_into"):
             raise RuntimeError("this Predictor's worker cannot impute points (no dpmm_impute_points)")
-        n, dev, new, upload = self._open(data, refuse_projected="impute")
-        out = new(n, (D,), "float32")
-        counts = np.zeros(2, np.int64)
-        for lo in range(0, n, cap):
-            hi = min(n, lo + cap)
-            upload(lo, hi)
-            if hi - lo == cap:
-                wk.impute_points_into(out[lo:hi])
-            else:
-                key = ("dev" if dev is not None else "host", "impute")
-                b = self._out_stage.get(key)
-                if b is None or (dev is not None and b.device != dev):
-                    b = self._out_stage[key] = new(cap, (D,), "float32")
-                wk.impute_points_into(b)
-                out[lo:hi] = b[:hi - lo]
-            counts += np.asarray(wk.score_missing_counts(), np.int64)
-        self.missing_counts = (int(counts[0]), int(counts[1]))
-        return out.T
+        out = self._walk(self._open(data, refuse_projected="impute"), [("impute", (self.D,), "float32")],
+                         lambda views, lo, hi: wk.impute_points_into(views["impute"]), counts=True)
+        return out["impute"].T
 
     # ---- drawing points (include/dpmm_hip_sample.h)
     def sampler_tables(self):
@@ -396,128 +386,49 @@ class Predictor:
         if self._wk is None:
             raise RuntimeError("this Predictor is closed")
         wk, cap = self._wk, self.capacity
-        csc = _sparse.as_csc(data)
-        dcsc = csc if isinstance(csc, _sparse.DeviceCSC) else None
-        if dcsc is not None:
-            if _tensors.resolve_device(dcsc, self._device_arg) != self.device:
-                raise ValueError(f"the data tensor lives on {dcsc.torch_device}, this Predictor on device {self.device}: open one Predictor per GPU")
-            if not hasattr(wk, "upload_points_csc_device"):
-                csc, dcsc = dcsc.to_host(), None                          # (a stand-in worker without the device entry points)
-        desc = None if csc is not None else _tensors.as_device_points(data)
-        if desc is not None:
-            if _tensors.resolve_device(desc, self._device_arg) != self.device:
-                raise ValueError(f"the data tensor lives on {desc.torch_device}, this Predictor on device {self.device}: open one Predictor per GPU")
-            if not hasattr(wk, "upload_points_strided_device"):
-                data, desc = desc.tensor.float().cpu().numpy(), None      # (a stand-in worker without the device entry points)
-        if csc is not None:
-            if self.kind != _priors.PRIOR_MULT:
-                raise TypeError("sparse data is for the Multinomial prior")
-            D, n = csc.shape
-        elif desc is not None:
-            D, n = desc.shape
-        else:
-            X = np.asarray(_tensors.as_host_array(data))
-            if X.ndim != 2:
-                raise ValueError("data must be 2-D, Dimensions x Samples")
-            D, n = X.shape
-        proj = self.projection if self.projection is not None and csc is None and D == self.projection.D_in else None
+        pts = _points.describe(data)
+        if pts.torch_device is not None and pts.device_index(self._device_arg) != self.device:
+            raise ValueError(f"the data tensor lives on {pts.torch_device}, this Predictor on device {self.device}: open one Predictor per GPU")
+        if pts.is_sparse and self.kind != _priors.PRIOR_MULT:
+            raise TypeError("sparse data is for the Multinomial prior")
+        D, n = pts.D, pts.N
+        proj = self.projection if self.projection is not None and not pts.is_sparse and D == self.projection.D_in else None
         if proj is None and D != self.D:               # (d-row data is taken as already projected)
             raise ValueError("data dimension does not match the model")
         if proj is not None and (refuse_projected or self.missing == "marginalize"):
             # one NaN source feature poisons all d projected coordinates: nothing is left to marginalise over
             what = refuse_projected or 'missing="marginalize"'
             raise ValueError(f"{what} takes data in the model's {self.D} projected coordinates, not the {D} source features of the projection")
-        if proj is not None and desc is not None and not hasattr(wk, "upload_points_projected_strided_device"):
-            data, desc = desc.tensor.float().cpu().numpy(), None
-            X = np.asarray(data)
-        if desc is not None or dcsc is not None:
+        projected = proj is not None
+        pts = pts.served(wk, projected)                # (a stand-in worker without the device entry points: host data)
+        dev = pts.torch_device
+        if dev is not None:
             import torch
-            dev = (desc or dcsc).torch_device
             new = lambda rows, tail, dt: torch.empty((rows,) + tail, dtype=getattr(torch, dt), device=dev)      # noqa: E731
-            (desc or dcsc).synchronize()
+            pts.synchronize()
         else:
-            dev = None
             new = lambda rows, tail, dt: np.empty((rows,) + tail, dt)      # noqa: E731
+        stages = _Stages(self, "_in" if projected else "")
 
-        def upload_projected(lo, hi):                  # as the branches below, D_in wide, through the projected calls
-            full = hi - lo == cap
-            if desc is not None:
-                if full:
-                    wk.upload_points_projected_strided_device(desc.shard_ptr(lo), desc.dtype, desc.stride_point, desc.stride_feature)
-                else:
-                    st = self._dev_stage_in
-                    if st is None or st.device != dev:
-                        st = self._dev_stage_in = torch.zeros((cap, D), dtype=torch.float32, device=dev)
-                    st[:hi - lo].copy_(desc.tensor[:, lo:hi].T)
-                    st[hi - lo:].zero_()
-                    torch.cuda.current_stream(dev).synchronize()
-                    wk.upload_points_projected_strided_device(st.data_ptr(), _tensors.DT_F32, D, 1)
-            elif full:
-                wk.upload_points_projected(np.ascontiguousarray(X[:, lo:hi].T, dtype=np.float32))
+        def upload(lo, hi):                            # a full slab where it is; the short one through the staging the Predictor keeps
+            if hi - lo == cap:
+                pts.upload(wk, lo, hi, projected)
             else:
-                if self._host_stage_in is None:
-                    self._host_stage_in = np.zeros((cap, D), np.float32)
-                self._host_stage_in[:hi - lo] = X[:, lo:hi].T
-                self._host_stage_in[hi - lo:] = 0
-                wk.upload_points_projected(self._host_stage_in)
+                pts.padded(lo, hi, cap, stages).upload(wk, 0, cap, projected)
+        return n, dev, new, upload
 
-        def upload(lo, hi):
-            full = hi - lo == cap
-            if dcsc is not None:
-                if full:                                                  # the slab's offsets where they are, the same entry arrays
-                    cp_ptr = dcsc.colptr_ptr(lo)
-                else:                                                     # the slice, then empty columns behind the last point
-                    st = self._csc_stage
-                    if st is None or st.device != dev or st.dtype != dcsc.colptr.dtype:
-                        st = self._csc_stage = torch.empty(cap + 1, dtype=dcsc.colptr.dtype, device=dev)
-                    st[:hi - lo + 1].copy_(dcsc.colptr[lo:hi + 1])
-                    st[hi - lo + 1:].copy_(dcsc.colptr[hi:hi + 1].expand(cap - (hi - lo)))
-                    torch.cuda.current_stream(dev).synchronize()
-                    cp_ptr = st.data_ptr()
-                wk.upload_points_csc_device(cp_ptr, dcsc.index_dtype, dcsc.rowval_ptr, dcsc.nzval_ptr, dcsc.value_dtype, dcsc.nnz_extent, 0)
-            elif csc is not None:
-                cp, rv, nz = csc.columns(lo, hi, check=not hasattr(wk, "upload_points_csc"))
-                if not full:                                              # empty columns behind the last point
-                    cp = np.concatenate([cp, np.full(cap - (hi - lo), cp[-1], np.int64)])
-                if hasattr(wk, "upload_points_csc"):
-                    wk.upload_points_csc(cp, rv, nz, index_base=0)
-                else:
-                    Xs = np.zeros((cap, D), np.float32)
-                    Xs[np.repeat(np.arange(cap), np.diff(cp)), rv] = nz
-                    wk.upload_points(Xs)
-            elif desc is not None:
-                if full:
-                    wk.upload_points_strided_device(desc.shard_ptr(lo), desc.dtype, desc.stride_point, desc.stride_feature, False)
-                else:
-                    st = self._dev_stage
-                    if st is None or st.device != dev:
-                        st = self._dev_stage = torch.zeros((cap, D), dtype=torch.float32, device=dev)
-                    st[:hi - lo].copy_(desc.tensor[:, lo:hi].T)           # (rounds to Float32 to nearest even, as the library's own read does)
-                    st[hi - lo:].zero_()
-                    torch.cuda.current_stream(dev).synchronize()
-                    wk.upload_points_strided_device(st.data_ptr(), _tensors.DT_F32, D, 1, False)
-            else:
-                if full:
-                    wk.upload_points(np.ascontiguousarray(X[:, lo:hi].T, dtype=np.float32))
-                else:
-                    if self._host_stage is None:
-                        self._host_stage = np.zeros((cap, D), np.float32)
-                    self._host_stage[:hi - lo] = X[:, lo:hi].T
-                    self._host_stage[hi - lo:] = 0
-                    wk.upload_points(self._host_stage)
-        return n, dev, new, (upload_projected if proj is not None else upload)
-
-    def _run(self, data, labels=False, logdens=False, m=0, probs=False):
-        n, dev, new, upload = self._open(data)
+    def _walk(self, opened, spec, evaluate, counts=False):
+        """The one walk over opened data in slabs of `capacity` points: every slab is uploaded and `evaluate(views, lo, hi)` called with its
+        outputs as `spec` lists them -- slices of the result for a full slab, the staging outputs the Predictor keeps for the short one, whose
+        first hi - lo rows are then copied.  Sets `missing_counts` (the worker is asked under "marginalize", or if `counts`); returns the results."""
+        n, dev, new, upload = opened
         wk, cap = self._wk, self.capacity
-        spec = self._spec(labels, logdens, m, probs)
         out = {name: new(n, tail, dt) for name, tail, dt in spec}
-        counts = np.zeros(2, np.int64)
+        total = np.zeros(2, np.int64)
         for lo in range(0, n, cap):
             hi = min(n, lo + cap)
             full = hi - lo == cap
             upload(lo, hi)
-            # -- its outputs: straight into the result for a full slab, through the staging outputs for the short one
             if full:
                 views = {name: out[name][lo:hi] for name, _, _ in spec}
             else:
@@ -528,13 +439,18 @@ class Predictor:
                     if b is None or tuple(b.shape[1:]) != tail or (dev is not None and b.device != dev):
                         b = self._out_stage[(key, name)] = new(cap, tail, dt)
                     views[name] = b
-            wk.score_points_into(views, m=m)
-            counts += self._slab_counts()
+            evaluate(views, lo, hi)
+            if counts or self.missing == "marginalize":
+                total += np.asarray(wk.score_missing_counts(), np.int64)
             if not full:
                 for name, _, _ in spec:
                     out[name][lo:hi] = views[name][:hi - lo]
-        self.missing_counts = (int(counts[0]), int(counts[1]))
+        self.missing_counts = (int(total[0]), int(total[1]))
         return out
+
+    def _run(self, data, labels=False, logdens=False, m=0, probs=False):
+        wk = self._wk
+        return self._walk(self._open(data), self._spec(labels, logdens, m, probs), lambda views, lo, hi: wk.score_points_into(views, m=m))
 
 
 def score_samples(dp_model, data, **kw):

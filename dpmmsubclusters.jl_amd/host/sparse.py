@@ -152,19 +152,3 @@ def as_csc(data):
                     data.sort_indices()
         return CSC(data.indptr, data.indices, data.data, data.shape)
     return None
-
-
-def upload_columns(wk, csc, lo, hi):
-    """The shard [lo, hi) into a worker: sparse where the worker can take it, else made dense on the host (test stand-ins, third-party
-    worker factories) -- as the .npy path falls back.  A DeviceCSC is read where it is by a worker that can, else brought to the host."""
-    if isinstance(csc, DeviceCSC):
-        if hasattr(wk, "upload_points_csc_tensor"):
-            csc.synchronize()                                  # the tensor is complete before the library reads it on its own stream
-            wk.upload_points_csc_tensor(csc, lo, hi)           # the offsets from `lo` on: an address, no copy and no slicing on the host
-            return
-        csc = csc.to_host()
-    if hasattr(wk, "upload_points_csc"):
-        cp, rv, nz = csc.columns(lo, hi, check=False)          # (the device checks what it is given and names the point)
-        wk.upload_points_csc(cp, rv, nz, index_base=0)
-    else:
-        wk.upload_points(csc.dense_rows(lo, hi))

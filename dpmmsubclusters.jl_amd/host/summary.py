@@ -178,14 +178,14 @@ class TraceRecorder:
 
     def _result(self, device_call, host_call):
         """A vector over the whole data set, in the type `_final_labels` gives the labels."""
-        desc = getattr(self.sampler, "data_tensor", None)
-        if desc is not None and self.native and getattr(self.comm, "world", 1) == 1:
-            return device_call(desc.torch_device)
+        dev = getattr(self.sampler, "data_device", None)
+        if dev is not None and self.native and getattr(self.comm, "world", 1) == 1:
+            return device_call(dev)
         whole = self.comm.gather_labels(_Local(host_call()))[0]
-        if desc is None:
+        if dev is None:
             return whole
         import torch
-        return torch.from_numpy(np.ascontiguousarray(whole)).to(desc.torch_device)
+        return torch.from_numpy(np.ascontiguousarray(whole)).to(dev)
 
     def read(self, slot):
         if self.K[slot] == 0:

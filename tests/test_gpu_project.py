@@ -302,6 +302,9 @@ def test_fit_and_predict_with_a_projection_equal_the_pre_projected_run(host, pro
     with host.Predictor(ma, capacity=1100) as p:                                # a short last slab: the Float32 staging, projected
         for r, s in zip(p.predict(emb.T), (la, pa)):
             assert torch.equal(r, s)
+        lh, ph = p.predict(emb.T.float().cpu().numpy())                         # ... and the same points from the host: the host staging, D_in wide
+        assert np.array_equal(lh, la.cpu().numpy()) and np.array_equal(ph.view(np.int32), pa.cpu().numpy().view(np.int32))
+        assert p._host_stage_in.shape == (1100, D_in) and p._dev_stage_in.shape == (1100, D_in)
     with host.Predictor.load(path, capacity=1000) as q:
         assert q.projection is not None and q.projection.basis.tobytes() == P.basis.tobytes()
         for r, s in zip(q.predict(emb.T), (la, pa)):
