@@ -148,6 +148,20 @@ ABI_RANK = [
 ]
 RANK_MAX_M = 64                        # DPMM_RANK_MAX_M
 RANK_TYPICAL, RANK_FRINGE = 1, 2       # DPMM_RANK_TYPICAL, DPMM_RANK_FRINGE
+
+
+class OverlapOut(ctypes.Structure):
+    """dpmm_overlap_out (include/dpmm_hip_overlap.h): host addresses, 0 / None = not asked for."""
+    _fields_ = [("overlap", ctypes.c_void_p), ("mass", ctypes.c_void_p), ("count", ctypes.c_void_p), ("skipped", ctypes.c_void_p)]
+
+
+# include/dpmm_hip_overlap.h: the posterior overlap of the clusters, sum_i p_ik p_ij (additive; bound next to ABI)
+ABI_OVERLAP = [
+    ("dpmm_overlap_begin", ctypes.c_int, [ctypes.c_void_p]),
+    ("dpmm_overlap_accumulate", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64]),
+    ("dpmm_overlap_read", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(OverlapOut)]),
+]
+OVERLAP_PARTIAL_BLOCKS = 512           # DPMM_OVERLAP_PARTIAL_BLOCKS
 # include/dpmm_hip_trace.h: label samples kept on the GPU, their pairwise contingency tables and the per-point confidence (additive)
 ABI_TRACE = [
     ("dpmm_trace_open", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
@@ -254,7 +268,7 @@ def load_library():
         except Exception:  # pragma: no cover  (torch is optional for single-GPU use)
             pass
         lib = ctypes.CDLL(p)
-        for name, res, args in ABI + ABI_TENSOR + ABI_SCORE + ABI_RANK + ABI_TRACE + ABI_MISSING + ABI_CSC + ABI_SAMPLE + ABI_PROJECT:
+        for name, res, args in ABI + ABI_TENSOR + ABI_SCORE + ABI_RANK + ABI_OVERLAP + ABI_TRACE + ABI_MISSING + ABI_CSC + ABI_SAMPLE + ABI_PROJECT:
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -692,6 +706,32 @@ class Worker:
         else:
             res = {name: np.empty(sh, dt) for name, sh, dt in spec}
             self.rank_read_raw(False, **{k: v.ctypes.data for k, v in res.items()})
+        return res
+
+    # ---- cluster overlap (include/dpmm_hip_overlap.h)
+    def overlap_begin(self):
+        """dpmm_overlap_begin: a new accumulation of the overlap matrix, the masses, count and skipped."""
+        self._chk(self._lib.dpmm_overlap_begin(self._h))
+        self._overlap_K = self.K
+
+    def overlap_accumulate(self, n_valid):
+        """dpmm_overlap_accumulate: adds the points 0..n_valid-1 of the current upload."""
+        self._chk(self._lib.dpmm_overlap_accumulate(self._h, int(n_valid)))
+
+    def overlap_read_raw(self, overlap=0, mass=0, count=0, skipped=0):
+        """dpmm_overlap_read on plain host addresses (integers; 0 = not asked for)."""
+        out = OverlapOut(overlap or None, mass or None, count or None, skipped or None)
+        self._chk(self._lib.dpmm_overlap_read(self._h, ctypes.byref(out)))
+
+    def overlap_read(self):
+        """The sums as they stand: a dict of numpy arrays, `overlap` (K, K) float64 (symmetric bit for bit), `mass` (K,) float64,
+        `count` (K,) int64 and `skipped` (1,) int64."""
+        K = getattr(self, "_overlap_K", None)
+        if K is None:
+            self.overlap_read_raw()            # (DPMM_ESTATE: no dpmm_overlap_begin yet)
+            raise RuntimeError("overlap_read needs overlap_begin first")
+        res = dict(overlap=np.empty((K, K), np.float64), mass=np.empty(K, np.float64), count=np.empty(K, np.int64), skipped=np.empty(1, np.int64))
+        self.overlap_read_raw(**{k: v.ctypes.data for k, v in res.items()})
         return res
 
     # ---- label trace (include/dpmm_hip_trace.h)

@@ -10,6 +10,7 @@
 #include "../../include/dpmm_hip_csc.h"
 #include "../../include/dpmm_hip_score.h"
 #include "../../include/dpmm_hip_rank.h"
+#include "../../include/dpmm_hip_overlap.h"
 #include "../../include/dpmm_hip_trace.h"
 #include "../../include/dpmm_hip_missing.h"
 #include "../../include/dpmm_hip_sample.h"
@@ -148,6 +149,13 @@ struct dpmm_ctx {
     bool rank_active = false;
     int rank_m = 0, rank_which = 0, rank_K = 0, rank_parity = 0;
     int64_t rank_cap = 0;
+    // cluster overlap (include/dpmm_hip_overlap.h): overlap | mass | counters; (M, S) of the points of one range; the chunk partials
+    double *d_ov_acc = nullptr; size_t ov_acc_bytes = 0;
+    float2 *d_ov_ms = nullptr; size_t ov_ms_bytes = 0;
+    double *d_ov_part = nullptr; size_t ov_part_bytes = 0;
+    bool ov_active = false;
+    int ov_K = 0;
+    unsigned long long ov_gen = 0;      // pred_gen at dpmm_overlap_begin
     // label trace (include/dpmm_hip_trace.h): slots rows of trace_nvec 16-byte vectors of ids; K per slot (0: never recorded); the device
     // images of a call's tables, descriptors, ratio tables and confidence
     uint16_t *d_trace = nullptr;
@@ -751,6 +759,7 @@ int dpmm_destroy(dpmm_ctx *c) {
     hipFree(c->d_m0); hipFree(c->d_psi_lo); hipFree(c->d_pairs);
     hipFree(c->d_score_table); hipFree(c->d_score_out);
     hipFree(c->d_rank_state); hipFree(c->d_rank_cand); hipFree(c->d_rank_out);
+    hipFree(c->d_ov_acc); hipFree(c->d_ov_ms); hipFree(c->d_ov_part);
     hipFree(c->d_trace); hipFree(c->d_trace_counts); hipFree(c->d_trace_desc); hipFree(c->d_trace_ratio); hipFree(c->d_trace_conf);
     hipFree(c->d_miss_rt); hipFree(c->d_miss_cst); hipFree(c->d_miss_list); hipFree(c->d_miss_cnt);
     hipFree(c->d_sm_m); hipFree(c->d_sm_At); hipFree(c->d_sm_df); hipFree(c->d_sm_thr); hipFree(c->d_sm_alias);
@@ -1583,6 +1592,7 @@ int dpmm_set_predictive_mult(dpmm_ctx *c, int K, const float *logp, const float 
     for (int k = 0; k < K; ++k) memcpy(&lp3[(size_t)3 * k * D], logp + (size_t)k * D, sizeof(float) * D);
     if (int rc = dpmm_set_params_mult(c, K, lp3.data(), lr.data(), w)) return rc;
     c->predictive = true;
+    c->pred_gen += 1;
     return DPMM_OK;
 }
 
@@ -3984,6 +3994,96 @@ static int rank_read(dpmm_ctx *c, const dpmm_rank_out *o, bool device, const cha
 
 int dpmm_rank_read(dpmm_ctx *c, const dpmm_rank_out *out) { return rank_read(c, out, false, "dpmm_rank_read"); }
 int dpmm_rank_read_device(dpmm_ctx *c, const dpmm_rank_out *out) { return rank_read(c, out, true, "dpmm_rank_read_device"); }
+
+// ---- include/dpmm_hip_overlap.h: the posterior overlap of the clusters, sum_i p_ik p_ij (overlap.hip) --------------------------------------
+static size_t overlap_acc_doubles(int K) { return (size_t)K * (size_t)K + (size_t)K; }
+static int overlap_max_chunks(int K) { const int nb = (K + 63) / 64, np = nb * (nb + 1) / 2; return std::max(1, OVERLAP_PARTIAL_BLOCKS / np); }
+
+int dpmm_overlap_begin(dpmm_ctx *c) {
+    static const char *fn = "dpmm_overlap_begin";
+    if (!c) return tensor_no_ctx(fn);
+    const std::string who = std::string(fn) + ": ";
+    if (!c->predictive) return fail(c, DPMM_ESTATE, who + "needs dpmm_set_predictive_* first");
+    HIPCHK(c, hipSetDevice(c->device));
+    c->ov_active = false;
+    const int K = c->K, nb = (K + 63) / 64, npairs = nb * (nb + 1) / 2;
+    const size_t state = sizeof(double) * overlap_acc_doubles(K) + sizeof(unsigned long long) * rank_count_words(K);
+    const size_t part = sizeof(double) * (size_t)overlap_max_chunks(K) * ((size_t)npairs * 4096 + (size_t)nb * 64);
+    if (int rc = ensure_score_buffer(c, reinterpret_cast<void **>(&c->d_ov_acc), &c->ov_acc_bytes, state, "accumulators of dpmm_overlap_begin")) return rc;
+    if (int rc = ensure_score_buffer(c, reinterpret_cast<void **>(&c->d_ov_part), &c->ov_part_bytes, part, "chunk partials of dpmm_overlap_begin")) return rc;
+    if (c->n > 0) {      // (M, S) of one range: sized as dpmm_overlap_accumulate will find it unless the table budget changes in between
+        int rstep = 0;
+        int64_t P = 0;
+        if (int rc = score_table_slab(c, &rstep, &P)) return rc;
+        if (int rc = ensure_score_buffer(c, reinterpret_cast<void **>(&c->d_ov_ms), &c->ov_ms_bytes, sizeof(float2) * (size_t)P, "maxima and sums of dpmm_overlap_begin")) return rc;
+    }
+    HIPCHK(c, hipMemsetAsync(c->d_ov_acc, 0, state, c->stream));
+    c->ov_K = K; c->ov_gen = c->pred_gen;
+    c->ov_active = true;
+    return DPMM_OK;
+}
+
+int dpmm_overlap_accumulate(dpmm_ctx *c, int64_t n_valid) {
+    static const char *fn = "dpmm_overlap_accumulate";
+    if (!c) return tensor_no_ctx(fn);
+    c->miss_counted = false;      // (as score_points)
+    const std::string who = std::string(fn) + ": ";
+    if (!c->ov_active) return fail(c, DPMM_ESTATE, who + "needs dpmm_overlap_begin first");
+    if (!c->predictive || c->K != c->ov_K || c->pred_gen != c->ov_gen) return fail(c, DPMM_ESTATE, who + "the predictive parameters changed since dpmm_overlap_begin");
+    if (n_valid < 0 || n_valid > c->n) return fail(c, DPMM_EINVAL, who + "n_valid must be in 0..n_local");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (n_valid == 0) return DPMM_OK;
+    if (!c->have_points || !c->have_params) return fail(c, DPMM_ESTATE, who + "needs points and parameters");
+    int rstep = 0;
+    int64_t P = 0;
+    if (int rc = score_table_slab(c, &rstep, &P)) return rc;
+    if (int rc = ensure_score_buffer(c, reinterpret_cast<void **>(&c->d_ov_ms), &c->ov_ms_bytes, sizeof(float2) * (size_t)P, "maxima and sums of dpmm_overlap_accumulate")) return rc;
+    const bool miss = c->opt_score_missing != 0;
+    if (int rc = miss_begin(c, miss, P, fn)) return rc;
+    const int K = c->K, nb = (K + 63) / 64, npairs = nb * (nb + 1) / 2;
+    const int most = overlap_max_chunks(K);
+    for (int64_t p0 = 0; p0 < n_valid; p0 += P) {
+        const int64_t np = std::min<int64_t>(P, c->n - p0);              // the range dpmm_score_points evaluates
+        if (int rc = run_sweep(c, 0, 0, c->d_score_table, P, p0, np)) return rc;
+        if (miss) if (int rc = miss_range(c, P, p0, np, nullptr, 0, fn)) return rc;
+        OverlapArgs a{};
+        a.table = c->d_score_table; a.stride = P; a.rstep = rstep; a.n = std::min<int64_t>(np, n_valid - p0); a.K = K; a.nb = nb;
+        overlap_chunks(a.n, K, &a.nchunk, &a.chunk);
+        if (a.nchunk > most) return fail(c, DPMM_EHIP, who + "internal: more chunks than the partial buffer holds");
+        a.ms = c->d_ov_ms;
+        a.acc = c->d_ov_acc;
+        a.count = reinterpret_cast<unsigned long long *>(c->d_ov_acc + overlap_acc_doubles(K));
+        a.part = c->d_ov_part;
+        a.mpart = c->d_ov_part + (size_t)most * (size_t)npairs * 4096;
+        hipError_t e = launch_overlap_range(a, c->stream);
+        if (e != hipSuccess) { c->err = who + hipGetErrorString(e); return DPMM_EHIP; }
+    }
+    return DPMM_OK;
+}
+
+int dpmm_overlap_read(dpmm_ctx *c, const dpmm_overlap_out *o) {
+    static const char *fn = "dpmm_overlap_read";
+    if (!c) return tensor_no_ctx(fn);
+    const std::string who = std::string(fn) + ": ";
+    if (!o) return fail(c, DPMM_EINVAL, who + "out is null");
+    if (!c->ov_active) return fail(c, DPMM_ESTATE, who + "needs dpmm_overlap_begin first");
+    HIPCHK(c, hipSetDevice(c->device));
+    const int K = c->ov_K;
+    const size_t kk = (size_t)K * (size_t)K;
+    std::vector<unsigned long long> cnt(rank_count_words(K));
+    hipError_t e = sync_stream(c, c->stream);
+    if (e == hipSuccess && o->overlap) e = hipMemcpy(o->overlap, c->d_ov_acc, sizeof(double) * kk, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && o->mass) e = hipMemcpy(o->mass, c->d_ov_acc + kk, sizeof(double) * (size_t)K, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && (o->count || o->skipped)) e = hipMemcpy(cnt.data(), c->d_ov_acc + overlap_acc_doubles(K), sizeof(unsigned long long) * cnt.size(), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) { c->err = who + hipGetErrorString(e); return DPMM_EHIP; }
+    for (int k = 0; k <= K; ++k) {
+        unsigned long long v = 0;
+        for (int r = 0; r < RANK_REPL; ++r) v += cnt[(size_t)r * (size_t)(K + 1) + (size_t)k];
+        if (k < K) { if (o->count) o->count[k] = (int64_t)v; }
+        else if (o->skipped) o->skipped[0] = (int64_t)v;
+    }
+    return DPMM_OK;
+}
 
 // ---- include/dpmm_hip_trace.h: label samples kept on the device, their contingency tables and the per-point confidence (trace.hip) ----------
 static int trace_buffer(dpmm_ctx *c, void **buf, size_t *have, size_t need, const char *fn, const char *what) {

@@ -211,6 +211,26 @@ struct RankArgs {
 struct RankOut { int64_t *typ_idx; float *typ_score; int64_t *fringe_idx; float *fringe_score; int64_t *count; int64_t *skipped; };      // = dpmm_rank_out
 hipError_t launch_rank_chunk(const RankArgs &a, hipStream_t s);
 hipError_t launch_rank_read(const unsigned long long *keys, const unsigned long long *count, int K, int m, int which, const RankOut &o, hipStream_t s);
+// ---- cluster overlap (overlap.hip; include/dpmm_hip_overlap.h): one range of the score table, n points from table column 0, added to the
+// ctx's accumulators
+constexpr int OVERLAP_PARTIAL_BLOCKS = 512;      // DPMM_OVERLAP_PARTIAL_BLOCKS: 64 x 64 blocks of chunk partials at most
+struct OverlapArgs {
+    const float *table;
+    int64_t stride;      // floats between two rows of the table
+    int rstep;           // cluster k is row k * rstep
+    int64_t n;           // points of the range that are accumulated
+    int K;
+    int nb;              // row blocks of 64 clusters, (K + 63) / 64
+    int nchunk;          // chunks of the range (overlap_chunks)
+    int64_t chunk;       // points per chunk, a multiple of 64
+    float2 *ms;                     // [n] (M, S) of the point; S = 0: it takes no part
+    unsigned long long *count;      // [RANK_REPL][K + 1] count | skipped
+    double *part;                   // [nchunk][nb (nb + 1) / 2][64][64] partial blocks of the lower block triangle
+    double *mpart;                  // [nchunk][nb * 64] partial masses
+    double *acc;                    // [K][K] overlap | [K] mass
+};
+void overlap_chunks(int64_t n, int K, int *nchunk, int64_t *chunk);
+hipError_t launch_overlap_range(const OverlapArgs &a, hipStream_t s);
 // ---- missing features (missing.hip; include/dpmm_hip_missing.h): one range of the score table, n points from table column 0 and from X
 constexpr int MISS_MAX = 16;              // DPMM_SCORE_MAX_MISSING
 constexpr int MISS_CST = MISS_MAX + 2;    // doubles per cluster in MissArgs::cst

@@ -24,6 +24,7 @@
 // to stay in the last-level cache between the passes.
 #include "dpmm_device.h"
 #include "dpmm_kernels.h"
+#include "score_device.h"
 
 namespace dpmm {
 
@@ -67,9 +68,7 @@ __global__ __launch_bounds__(64 * SC_WAVES) void score_finish_kernel(ScoreArgs A
         // ---- pass 2: e_k and their sum (K <= 64 with probs: the e_k go to the tile on the way)
         float s = 0.f;
         for (int k = 0; k < K; ++k) {
-            float a = col[(int64_t)k * rs];
-            if (a != a) a = -INFINITY;
-            const float e = expf(a - m);
+            const float e = score_e(col[(int64_t)k * rs], m);
             if (PROBS && K <= 64) tw[lane * (K | 1) + k] = e;
             s += e;
         }
@@ -84,9 +83,7 @@ __global__ __launch_bounds__(64 * SC_WAVES) void score_finish_kernel(ScoreArgs A
             for (int j = 0; j < MT; ++j) tk[j] = (unsigned long long)(~(unsigned)j);
 #pragma unroll 1
             for (int k = 0; k < K; ++k) {
-                float a = col[(int64_t)k * rs];
-                if (a != a) a = -INFINITY;
-                const float p = expf(a - m) / s;
+                const float p = score_p(score_e(col[(int64_t)k * rs], m), s);
                 // (a NaN -- the whole row is then NaN -- is never inserted: key 0 ranks below every slot)
                 unsigned long long key = (p == p) ? (((unsigned long long)(__float_as_uint(p) + 1u) << 32) | (unsigned long long)(~(unsigned)k)) : 0ull;
 #pragma unroll
@@ -101,9 +98,7 @@ __global__ __launch_bounds__(64 * SC_WAVES) void score_finish_kernel(ScoreArgs A
             if (s != s) {      // no finite entry: every probability is NaN and none was inserted -- indices 0 .. m - 1 with the NaNs probs holds
 #pragma unroll 1
                 for (int k = 0; k < K && k < MT; ++k) {      // (a rolled loop: sixteen unrolled row offsets cost the kernel its scalar registers)
-                    float a = col[(int64_t)k * rs];
-                    if (a != a) a = -INFINITY;
-                    const float p = expf(a - m) / s;
+                    const float p = score_p(score_e(col[(int64_t)k * rs], m), s);
 #pragma unroll
                     for (int j = 0; j < MT; ++j) tv[j] = (j == k) ? p : tv[j];
                 }
@@ -119,9 +114,7 @@ __global__ __launch_bounds__(64 * SC_WAVES) void score_finish_kernel(ScoreArgs A
                 if (K > 64) {
                     __syncthreads();                       // the previous 64 clusters have left the tile
                     for (int kk = 0; kk < kc; ++kk) {
-                        float a = col[(int64_t)(k0 + kk) * rs];
-                        if (a != a) a = -INFINITY;
-                        tw[lane * sr + kk] = expf(a - m);
+                        tw[lane * sr + kk] = score_e(col[(int64_t)(k0 + kk) * rs], m);
                     }
                 }
                 __syncthreads();
@@ -130,7 +123,7 @@ __global__ __launch_bounds__(64 * SC_WAVES) void score_finish_kernel(ScoreArgs A
                 const int dr = 64 / kc, dk = 64 - dr * kc;
                 const int total = npt * kc;
                 for (int f = lane; f < total; f += 64) {
-                    A.probs[(i0 + r) * (int64_t)K + k0 + kk] = tw[r * sr + kk] / sS[r];
+                    A.probs[(i0 + r) * (int64_t)K + k0 + kk] = score_p(tw[r * sr + kk], sS[r]);
                     r += dr; kk += dk;
                     if (kk >= kc) { kk -= kc; ++r; }
                 }

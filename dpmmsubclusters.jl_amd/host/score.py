@@ -33,6 +33,10 @@ Exemplars = collections.namedtuple("Exemplars", "typical_idx typical_score fring
 Exemplars.__doc__ = """What `Predictor.exemplars` returns: typical_idx, typical_score, fringe_idx, fringe_score (K, m) -- a list that was not asked
 for is None -- count (K,) and skipped, an int."""
 
+Overlap = collections.namedtuple("Overlap", "matrix mass count skipped")
+Overlap.__doc__ = """What `Predictor.overlap` returns: matrix (K, K) float64, O[k][j] = sum_i p_ik p_ij; mass (K,) float64, sum_i p_ik; count (K,)
+int64, the points labelled k + 1; skipped, an int -- numpy arrays always."""
+
 
 class _Capture:
     """Receives what prior.predictive_table would hand a worker."""
@@ -254,6 +258,30 @@ class Predictor:
         return Exemplars(r["typ_idx"] if typ else None, r["typ_score"] if typ else None, r["fringe_idx"] if fr else None,
                          r["fringe_score"] if fr else None, r["count"], int(r["skipped"][0]))
 
+    # ---- cluster overlap (include/dpmm_hip_overlap.h)
+    def overlap(self, data):
+        """How the clusters of the model relate on `data`: an `Overlap` tuple, accumulated on the GPU in Float64.
+
+          matrix[k][j]   sum_i p_ik p_ij, p_i. the probabilities `predict` returns for point i: the expected number of points the model
+                         puts in cluster k + 1 on one draw and in j + 1 on another; symmetric bit for bit;
+          mass[k]        sum_i p_ik, the expected size of the cluster;
+          count[k]       the points `predict_labels` labels k + 1;
+          skipped        points whose row of the table holds a NaN or no finite entry: they are counted here and add nothing else.
+        Every entry of matrix and mass lies within a relative n * 2^-52 of `P.double().T @ P.double()` (of its column sums) for
+        the (n, K) matrix P of `predict`, whatever `capacity` is; count and skipped are exact.  `data` is what `predict` takes.  The
+        arrays are numpy arrays (K * K numbers); nothing of size n is allocated or copied to the host.  `host.merge_tree` turns the
+        result into the agglomerative hierarchy of the clusters."""
+        if self._wk is None:
+            raise RuntimeError("this Predictor is closed")
+        wk = self._wk
+        if not hasattr(wk, "overlap_begin"):
+            raise RuntimeError("this Predictor's worker cannot accumulate the cluster overlap (no dpmm_overlap_begin)")
+        opened = self._open(data)
+        wk.overlap_begin()
+        self._walk(opened, [], lambda views, lo, hi: wk.overlap_accumulate(hi - lo))
+        r = wk.overlap_read()
+        return Overlap(r["overlap"], r["mass"], r["count"], int(r["skipped"][0]))
+
     # ---- missing features (include/dpmm_hip_missing.h)
     def impute(self, data):
         """(D, n) float32: `data` converted to Float32 with the NaN features of every point that has 1 .. min(16, D - 1) of them replaced
@@ -471,6 +499,13 @@ def exemplars(dp_model, data, m, **kw):
     which = kw.pop("which", "both")
     with Predictor(dp_model, **kw) as p:
         return p.exemplars(data, m, which=which)
+
+
+def overlap(dp_model, data, **kw):
+    """The overlap matrix of the clusters on `data` (opens a Predictor, runs, closes): see `Predictor.overlap`;
+    kw: capacity, device, worker_factory, missing."""
+    with Predictor(dp_model, **kw) as p:
+        return p.overlap(data)
 
 
 def impute(dp_model, data, **kw):
