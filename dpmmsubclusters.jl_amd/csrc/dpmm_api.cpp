@@ -36,26 +36,13 @@
 
 #include "dpmm_kernels.h"
 #include "project_image.h"
+#include "dev_mem.h"      // DevBuf / PinBuf: every buffer below is a member or a local of these and is never freed by hand
 
 namespace dpmm {      // test hook in front of every kernel launch (dpmm_kernels.h DPMM_LAUNCH, dpmm_debug_set_prelaunch_hook)
 void (*g_prelaunch)(void *) = nullptr;
 void *g_prelaunch_arg = nullptr;
 }
 using namespace dpmm;
-
-#ifdef DPMM_POISON
-// Diagnostic build (scripts/build_variant.sh poison -DDPMM_POISON=0xFF): every device allocation of this file is filled with the poison byte
-// before anybody uses it -- a kernel that reads memory nobody wrote then reads NaNs / -1 on EVERY box, not only on one whose memory holds
-// another process's leftovers.  (Built while a one-in-twenty chain divergence on fresh boxes was tracked down: it ruled device MEMORY out;
-// the cause was a never-written LDS word, found with tests/tools/poison.py -- DESIGN section 5.)
-template <typename T>
-static hipError_t hipMallocPoisoned(T **p, size_t n) {
-    hipError_t e = hipMalloc(p, n);
-    if (e == hipSuccess && n > 0) { e = hipMemset(*p, DPMM_POISON, n); if (e == hipSuccess) e = hipDeviceSynchronize(); }
-    return e;
-}
-#define hipMalloc hipMallocPoisoned
-#endif
 
 static_assert(DPMM_MAX_CLUSTERS == DPMM_MAX_CLUSTERS_K, "header / kernel limits out of sync");
 
@@ -83,27 +70,27 @@ struct dpmm_ctx {
     int have_parts = 0;                           // 0: no three-kernel sweep timed yet; 1: labels + sub-labels (no lean kernel); 2: lean + labels + sub-labels
     bool have_sweep_ev = false, have_stats_ev = false;
 
-    float *dX = nullptr;
-    int32_t *dbins = nullptr;
+    DevBuf<float> dX;
+    DevBuf<int32_t> dbins;
     bool have_points = false, have_labels = false;
-    int32_t *d_gt = nullptr;  // ground truth of the shard (on-device evaluation)
+    DevBuf<int32_t> d_gt;  // ground truth of the shard (on-device evaluation)
     int n_gt = 0;
-    unsigned long long *d_cont = nullptr;
+    DevBuf<unsigned long long> d_cont;
     bool have_perm = false;   // sb.perm holds a permutation of [0,n) sorted by a recent labelling
 
     // parameters
     int K = 0, Kcap = 0;
-    float *d_raw = nullptr;   // NIW: R [3K][D][D] ; MULT: unused
-    float *d_mu = nullptr;    // NIW raw mu [3K][D]
-    float *d_Rp = nullptr;    // NIW packed fragments / MULT packed logp
-    float *d_mup = nullptr;   // NIW padded mu
-    float *d_cst = nullptr;   // [3K]
-    uint32_t *d_Lp16 = nullptr;  // MULT: 3-plane bf16 split of the log-probabilities (count data fast path)
+    DevBuf<float> d_raw;   // NIW: R [3K][D][D] ; MULT: unused
+    DevBuf<float> d_mu;    // NIW raw mu [3K][D]
+    DevBuf<float> d_Rp;    // NIW packed fragments / MULT packed logp
+    DevBuf<float> d_mup;   // NIW padded mu
+    DevBuf<float> d_cst;   // [3K]
+    DevBuf<uint32_t> d_Lp16;  // MULT: 3-plane bf16 split of the log-probabilities (count data fast path)
     // MULT, device master: the NEXT parameter draws, made right behind the per-step statistics (while the host decides splits and merges) into
     // a second set of buffers; dpmm_mult_master_draw swaps the sets when its epoch / K / outlier flag are the ones guessed and the rows have
     // not changed since (else it draws as before)
-    float *d_raw2 = nullptr, *d_Rp2 = nullptr;
-    uint32_t *d_Lp16_2 = nullptr;
+    DevBuf<float> d_raw2, d_Rp2;
+    DevBuf<uint32_t> d_Lp16_2;
     bool mspec_valid = false;
     bool rp_current = true, rp2_current = true;   // the Float32 fragment image (d_Rp / d_Rp2) matches d_raw / d_raw2: the device master skips it for byte / bf16 data; the Float32 sweep packs it on demand
     uint32_t mspec_epoch = 0, mdraw_epoch = 0;
@@ -118,123 +105,122 @@ struct dpmm_ctx {
     bool cst_inflight = false;
     bool marg_behind_ev = false;       // the log-marginals in the pinned block were complete at ev_rows (no need to wait for the stream)
     int x_bf16_exact = 0;     // MULT: every x is exactly representable in bf16 (checked at upload)
-    uint8_t *dX8 = nullptr;   // MULT: byte copy of the points when every x is an integer in [0, 255] ([n][ld8])
+    DevBuf<uint8_t> dX8;   // MULT: byte copy of the points when every x is an integer in [0, 255] ([n][ld8])
     int64_t ld8 = 0;
     int x_u8 = 0;
     int opt_no_u8 = 0;
     // MULT: the points as compressed sparse columns (dpmm_upload_points_csc; mult_sparse.hip) -- then dX / dX8 are not allocated, and d_Rp / d_Rp2
     // hold the TRANSPOSED parameter image [D][3K] the sparse sweep reads (rp_current stays false: the Float32 fragment image is not kept)
     int x_sparse = 0;
-    int64_t *d_cp = nullptr;
-    uint16_t *d_ri = nullptr;
-    float *d_val = nullptr;
+    DevBuf<int64_t> d_cp;
+    DevBuf<uint16_t> d_ri;
+    DevBuf<float> d_val;
     int64_t nnz = 0;
     int chunk_dense = 512;            // points per statistics item while the points are dense (`chunk` is the one in use: set_points_chunk)
     bool repack_pending = false;      // a dense upload replaced sparse points: the dense kernels' parameter images are made from the raw rows
-    float *d_scratch = nullptr;
+    DevBuf<float> d_scratch;
     int64_t scratch_stride = 0;
     bool have_params = false;
-    float *d_lam = nullptr, *d_mdist = nullptr, *d_tail = nullptr;   // NIW screening constants (per sweep)
+    DevBuf<float> d_lam, d_mdist, d_tail;   // NIW screening constants (per sweep)
     bool have_screen_prep = false, have_tail = false;
-    float *d_tdf = nullptr;   // Student-t constants of the predictive mode ([3K][2]) or null
+    DevBuf<float> d_tdf;   // Student-t constants of the predictive mode ([3K][2]) or null
     bool predictive = false;
     // scoring (include/dpmm_hip_score.h): one slab of the table and, for the host variant, the slab's outputs; allocated on first use, grown on demand
-    float *d_score_table = nullptr; size_t score_table_bytes = 0;
-    char *d_score_out = nullptr; size_t score_out_bytes = 0;
+    DevBuf<float> d_score_table;
+    DevBuf<char> d_score_out;
     double opt_score_mb = 128.0;       // DPMM_OPT_SCORE_TABLE_MB
     // exemplars (include/dpmm_hip_rank.h): running lists | counters | candidate counters; the candidate buffers; the staging of dpmm_rank_read
-    unsigned long long *d_rank_state = nullptr; size_t rank_state_bytes = 0;
-    char *d_rank_cand = nullptr; size_t rank_cand_bytes = 0;
-    char *d_rank_out = nullptr; size_t rank_out_bytes = 0;
+    DevBuf<unsigned long long> d_rank_state;
+    DevBuf<char> d_rank_cand, d_rank_out;
     bool rank_active = false;
     int rank_m = 0, rank_which = 0, rank_K = 0, rank_parity = 0;
     int64_t rank_cap = 0;
     // cluster overlap (include/dpmm_hip_overlap.h): overlap | mass | counters; (M, S) of the points of one range; the chunk partials
-    double *d_ov_acc = nullptr; size_t ov_acc_bytes = 0;
-    float2 *d_ov_ms = nullptr; size_t ov_ms_bytes = 0;
-    double *d_ov_part = nullptr; size_t ov_part_bytes = 0;
+    DevBuf<double> d_ov_acc;
+    DevBuf<float2> d_ov_ms;
+    DevBuf<double> d_ov_part;
     bool ov_active = false;
     int ov_K = 0;
     unsigned long long ov_gen = 0;      // pred_gen at dpmm_overlap_begin
     // label trace (include/dpmm_hip_trace.h): slots rows of trace_nvec 16-byte vectors of ids; K per slot (0: never recorded); the device
     // images of a call's tables, descriptors, ratio tables and confidence
-    uint16_t *d_trace = nullptr;
+    DevBuf<uint16_t> d_trace;
     int trace_slots = 0;
     int64_t trace_nvec = 0;
     std::vector<int> trace_K;
-    unsigned long long *d_trace_counts = nullptr; size_t trace_counts_bytes = 0;
-    char *d_trace_desc = nullptr; size_t trace_desc_bytes = 0;
-    float *d_trace_ratio = nullptr; size_t trace_ratio_bytes = 0;
-    float *d_trace_conf = nullptr; size_t trace_conf_bytes = 0;
+    DevBuf<unsigned long long> d_trace_counts;
+    DevBuf<char> d_trace_desc;
+    DevBuf<float> d_trace_ratio, d_trace_conf;
     // missing features (include/dpmm_hip_missing.h): the constants of the marginals on the host (formed by dpmm_set_predictive_niw); on the
     // device, allocated by the first call that marginalises: their copy, the transposed factors, a range's list and the three counters
     int opt_score_missing = 0;         // DPMM_OPT_SCORE_MISSING
     std::vector<double> h_miss_cst;    // [K][MISS_CST]
     int miss_slots = 0;                // slots of the parameter staging when the predictive parameters were committed (their layout in d_par)
     unsigned long long pred_gen = 0, miss_gen = 0;      // parameter set in force / the one the device copies were made from (0: none)
-    float *d_miss_rt = nullptr; size_t miss_rt_bytes = 0;
-    double *d_miss_cst = nullptr; size_t miss_cst_bytes = 0;
-    uint32_t *d_miss_list = nullptr; size_t miss_list_bytes = 0;
-    unsigned long long *d_miss_cnt = nullptr; size_t miss_cnt_bytes = 0;
+    DevBuf<float> d_miss_rt;
+    DevBuf<double> d_miss_cst;
+    DevBuf<uint32_t> d_miss_list;
+    DevBuf<unsigned long long> d_miss_cnt;
     bool miss_counted = false;         // the last table call marginalised: the counters hold its counts
     // drawing points (include/dpmm_hip_sample.h): the sampler's tables (dpmm_set_sampler_*) and what a call needs beside its outputs
     // (cluster and tile starts; sparse: 4 bytes per point of counts and the scan's tile totals), allocated on first use
-    float *d_sm_m = nullptr, *d_sm_At = nullptr, *d_sm_df = nullptr;
-    uint32_t *d_sm_thr = nullptr;
-    int32_t *d_sm_alias = nullptr;
+    DevBuf<float> d_sm_m, d_sm_At, d_sm_df;
+    DevBuf<uint32_t> d_sm_thr;
+    DevBuf<int32_t> d_sm_alias;
     int sm_K = 0;
-    int64_t *d_sm_cstart = nullptr; int32_t *d_sm_tstart = nullptr; int sm_start_cap = 0;
-    int32_t *d_sm_cnt = nullptr; int64_t *d_sm_bt = nullptr;
+    DevBuf<int64_t> d_sm_cstart; DevBuf<int32_t> d_sm_tstart; int sm_start_cap = 0;
+    DevBuf<int32_t> d_sm_cnt; DevBuf<int64_t> d_sm_bt;
     // projection (include/dpmm_hip_project.h): D_in (0: none), the plane image of W and -b as project.hip reads them, the host call's staging rows
     int proj_Din = 0;
-    void *d_proj_W = nullptr;
-    float *d_proj_bias = nullptr;
-    float *d_proj_stage = nullptr; size_t proj_stage_bytes = 0;
+    DevBuf<void> d_proj_W;
+    DevBuf<float> d_proj_bias, d_proj_stage;
 
     // sort + stats
-    SortBufs sb{};
+    SortBufs sb{};          // a view for the kernels; its arrays are owned by the members of sort_mem (filled by dpmm_create and DPMM_OPT_SORT_TILE)
+    struct {
+        DevBuf<int32_t> tile_hist, tile_cnt, spec_bins, tile_spec, fast_total, bin_total, bin_start, perm, item_start, perm_total;
+        DevBuf<unsigned> ticket;
+        DevBuf<uint16_t> prev_lab;
+        DevBuf<uint8_t> cdirty, cmode, bin_sel;
+    } sort_mem;
     int nt_sort = 0;          // tiles the sort tables are allocated for
     int sort_tile_min = SORT_TILE;   // smallest sort tile the tables can hold
     int chunk = 512;
     int max_items = 0;
-    double *d_slabs = nullptr;
+    DevBuf<double> d_slabs;
     int64_t slab_stride = 0;
-    int32_t *d_row_off = nullptr;      // NIW: packed-row element -> slab position
-    int32_t *d_inv_off = nullptr;      // NIW: slab position -> packed-row element (reduce kernel)
-    double *d_out = nullptr;
+    DevBuf<int32_t> d_row_off;      // NIW: packed-row element -> slab position
+    DevBuf<int32_t> d_inv_off;      // NIW: slab position -> packed-row element (reduce kernel)
+    DevBuf<double> d_out;
     int64_t packed_stride = 0;
-    double *d_proj = nullptr, *d_vals = nullptr, *d_smart = nullptr;   // smart splits: projections [n], compacted copy [n], partials + v + mu
-    int32_t *d_small = nullptr;  // index lists for relabel kernels (Int32, <= 4*DPMM_MAX_CLUSTERS)
+    DevBuf<double> d_proj, d_vals, d_smart;   // smart splits: projections [n], compacted copy [n], partials + v + mu
+    DevBuf<int32_t> d_small;  // index lists for relabel kernels (Int32, <= 4*DPMM_MAX_CLUSTERS)
     std::vector<uint8_t> h_sel;
     // pinned host staging for every per-step transfer (pageable copies stall for tens of ms now and then)
-    char *h_pin = nullptr;
-    size_t h_pin_bytes = 0;
+    PinBuf<char> h_pin;
     // parameter staging (dpmm_params_staging): slot-indexed rows the host writes in place; the pack kernels read it directly
-    char *h_par = nullptr;
-    size_t h_par_bytes = 0;
+    PinBuf<char> h_par;
     int par_slots = 0;
     // statistics output (dpmm_step_stats / dpmm_suffstats_host): packed rows + flags, read by the host in place
-    char *h_out = nullptr;
-    size_t h_out_bytes = 0;
-    char *d_par = nullptr;             // device copy of the staging's mu | R regions (NIW): the pack kernel gathers from HBM, not over the host link
-    size_t d_par_bytes = 0;
+    PinBuf<char> h_out;
+    DevBuf<char> d_par;             // device copy of the staging's mu | R regions (NIW): the pack kernel gathers from HBM, not over the host link
     bool work_zeroed = false;          // the pack kernel cleared d_work and no sweep has run since
     int sel_all_ones = 0, sel_capacity = 0;   // sb.bin_sel[0..sel_all_ones) are known to be 1 (full passes skip the memset)
-    long long *d_counts64 = nullptr;   // [2 * DPMM_MAX_CLUSTERS] global sub-cluster occupancies (multi-GPU)
+    DevBuf<long long> d_counts64;   // [2 * DPMM_MAX_CLUSTERS] global sub-cluster occupancies (multi-GPU)
     // Multinomial master on the device (mult_master.hip): priors, and how many clusters' complete rows the last statistics pass left in d_out
-    float *d_malpha = nullptr;         // [2][ldx]: cluster prior | outlier prior
+    DevBuf<float> d_malpha;         // [2][ldx]: cluster prior | outlier prior
     bool mult_master = false, mult_has_alpha1 = false;
     int rows_full_K = -1;
     // ... and its log-marginals (mult_marginal_kernel): prior constants {sum a, sum lgamma(a)} x 2, the pair list asked for ahead of the
     // next per-step pass, the pinned result block [3K][2] (N, L) | [pairs] and what it currently answers
     double mult_prior_c[4] = {0, 0, 0, 0};
-    int32_t *d_mpairs = nullptr;
+    DevBuf<int32_t> d_mpairs;
     std::vector<int32_t> mpairs_req, mpairs_shadow;
     bool marg_req = false, marg_valid = false;
     int marg_req_outlier = 0, marg_K = 0, marg_np = 0;
-    double *h_marg = nullptr;
+    PinBuf<double> h_marg;
     // derived sub-cluster statistics of the per-step pass (derive_rows_kernel): cached cluster-level rows + label tracking
-    double *d_ccache = nullptr;        // [Kcap][packed_stride] left + right of every cluster as of the last pass that computed both
+    DevBuf<double> d_ccache;        // [Kcap][packed_stride] left + right of every cluster as of the last pass that computed both
     bool cache_force = true;           // the next per-step pass computes every cluster in full (points uploaded, cache re-allocated, K changed)
     int cache_K = -1;
     int opt_derive = 1;
@@ -242,13 +228,14 @@ struct dpmm_ctx {
     int opt_noise_ahead = -1;          // normals of the next draws on the second stream beside the sweep (DPMM_OPT_NOISE_AHEAD): -1 = for D >= 128 or shards below 4e6 points
     // device master (niw_master.hip)
     bool master = false;
-    NiwMasterArgs ma{};
-    double *d_m0 = nullptr, *d_psi_lo = nullptr, *d_pairs = nullptr;
-    double *d_Y[2] = {nullptr, nullptr};           // draw outputs, two sets: [draw_cur] belongs to the parameters in use, the other takes the next draws
-    float *d_mu_draw[2] = {nullptr, nullptr};
+    NiwMasterArgs ma{};                            // a view for the kernels: fac .. rows_store point into master_mem (master_capacity), m0 / psi_lo at d_m0 / d_psi_lo
+    struct { DevBuf<double> fac, mean, kap, nu, rows_store; } master_mem;
+    DevBuf<double> d_m0, d_psi_lo, d_pairs;
+    DevBuf<double> d_Y[2];                         // draw outputs, two sets: [draw_cur] belongs to the parameters in use, the other takes the next draws
+    DevBuf<float> d_mu_draw[2];
     int draw_cur = 0;
     size_t pair_cap = 0;                           // matrices in d_pairs (pooled pair scratch)
-    float *d_ld_sigma[2] = {nullptr, nullptr};
+    DevBuf<float> d_ld_sigma[2];
     int master_slots = 0, master_K = 0;            // capacities: slots (fac / mean / rows_store), clusters (Y / mu_draw)
     // draws launched ahead (dpmm_step_master_device): a second stream, so that the pair kernels of the merge proposals do not queue behind them
     hipStream_t stream2 = nullptr;
@@ -256,16 +243,16 @@ struct dpmm_ctx {
     hipEvent_t ev_noise = nullptr;                          // normals of the next draws generated (stream2)
     // pooled pair log-determinants launched ahead (dpmm_step_master_device): list in device memory, records in a pinned block of their own
     hipEvent_t ev_pairs = nullptr;
-    int32_t *d_apairs = nullptr;                            // [2 cap] slot pairs of the launch-ahead job
+    DevBuf<int32_t> d_apairs;                               // [2 cap] slot pairs of the launch-ahead job
     size_t apairs_cap = 0;
     std::vector<int32_t> apairs_shadow;
-    int32_t *h_apairs_list[2] = {nullptr, nullptr}; size_t h_apairs_list_cap[2] = {0, 0}; int apairs_pin_flip = 0; const int32_t *apairs_pinned_cur = nullptr;      // the fused pair jobs' list in pinned memory (DPMM_OPT_CHAIN_FUSION bit 4)
-    double *h_apairs = nullptr;                             // pinned [cap][DPMM_MASTER_NSCALARS]
+    PinBuf<int32_t> h_apairs_list[2]; int apairs_pin_flip = 0; const int32_t *apairs_pinned_cur = nullptr;      // the fused pair jobs' list in pinned memory (DPMM_OPT_CHAIN_FUSION bit 4)
+    PinBuf<double> h_apairs;                                // pinned [cap][DPMM_MASTER_NSCALARS]
     bool apairs_inflight = false, apairs_valid = false;     // main stream has not waited for ev_pairs yet / the records answer dpmm_niw_master_pairs
     std::unordered_map<uint32_t, int> apairs_index;         // (slot_i << 16 | slot_j) -> record
     std::vector<uint8_t> apairs_dirty;                      // [slot] statistics of the slot changed since the job was launched
     std::vector<int32_t> apairs_req;                        // request of dpmm_niw_master_pairs_ahead, consumed by the next dpmm_step_master_device
-    char *h_draw = nullptr;                                 // pinned: lr [K][2] | w [K] of dpmm_niw_master_draw
+    PinBuf<char> h_draw;                                    // pinned: lr [K][2] | w [K] of dpmm_niw_master_draw
     bool handover_inflight = false;                         // a hand-over kernel (reads lr / w from h_pin) was launched and the host has not waited behind it
     bool noise_pending = false;                             // dpmm_niw_master_draw asked for the next normals; launched behind the sweep (noise_flush)
     uint32_t noise_pend_epoch = 0;
@@ -278,15 +265,13 @@ struct dpmm_ctx {
     std::vector<int32_t> spec_slots;
     // index lists of the master kernels (jobs, slot maps) live in device memory and are re-sent only when they change: read from pinned
     // host memory they cost every workgroup a PCIe round trip (~2 us) before its first useful instruction
-    int32_t *d_jobs = nullptr, *d_dslots = nullptr;          // [2 MAX] jobs of the posterior kernels (main stream) / [MAX] slot map of the draws
-    int32_t *h_list[4] = {nullptr, nullptr, nullptr, nullptr};   // pinned staging ring of device_list
-    size_t h_list_cap[4] = {0, 0, 0, 0};
+    DevBuf<int32_t> d_jobs, d_dslots;                        // [2 MAX] jobs of the posterior kernels (main stream) / [MAX] slot map of the draws
+    PinBuf<int32_t> h_list[4];                                   // pinned staging ring of device_list
     int h_list_next = 0;
     std::vector<int32_t> jobs_shadow, dslots_shadow;
-    uint8_t *h_master = nullptr;                   // pinned: jobs | slot map | lr | w | small
-    size_t h_master_bytes = 0;
+    PinBuf<uint8_t> h_master;                      // pinned: jobs | slot map | lr | w | small
     bool draws_on_device = false;
-    unsigned long long *d_work = nullptr;   // [DPMM_WORK_SLOTS + 4 DPMM_WORK_PER_WAVE sweep_grid_max]: tile queue heads [4], [8 + 16 q]; [DPMM_WORK_SLOTS + DPMM_WORK_PER_WAVE w ..] executed-work counters of wave w of the last sweep
+    DevBuf<unsigned long long> d_work;   // [DPMM_WORK_SLOTS + 4 DPMM_WORK_PER_WAVE sweep_grid_max]: tile queue heads [4], [8 + 16 q]; [DPMM_WORK_SLOTS + DPMM_WORK_PER_WAVE w ..] executed-work counters of wave w of the last sweep
     int work_waves = 0;                      // most waves of a counted sweep launch since the counters were read
     long long work_launches = 0;             // counted sweep launches since the counters were read
     // options (dpmm_set_option)
@@ -296,13 +281,13 @@ struct dpmm_ctx {
     int opt_ball = 1;
     // direction screen of the D in 33..64 sweep (direction_far, niw_sweep.hip; DPMM_OPT_DIRECTION_SCREEN): tables per parameter set, built only while
     // the sweeps report tiles with many candidates (h_need: one word per wave of the last sweep, written by the kernel into pinned memory)
-    uint32_t *d_sp_frag = nullptr;
-    uint32_t *d_refb_big = nullptr;    // D = 128, 256: bf16 images of the cluster-level factors (reference bracket of the LDS-staged kernels), per parameter set
+    DevBuf<uint32_t> d_sp_frag;
+    DevBuf<uint32_t> d_refb_big;    // D = 128, 256: bf16 images of the cluster-level factors (reference bracket of the LDS-staged kernels), per parameter set
     bool have_refb_big = false;
-    uint32_t *d_brk_flag = nullptr;    // [tiles of 128 points] 1 + k0 where the tile is label-homogeneous, else 0 (niw_bracket_big_kernel)
-    float *d_brk_aref = nullptr;       // [positions of the visiting order] the bracket's lower end of a_k0
-    float *d_sp_cons = nullptr;
-    uint32_t *h_need = nullptr;
+    DevBuf<uint32_t> d_brk_flag;    // [tiles of 128 points] 1 + k0 where the tile is label-homogeneous, else 0 (niw_bracket_big_kernel)
+    DevBuf<float> d_brk_aref;       // [positions of the visiting order] the bracket's lower end of a_k0
+    DevBuf<float> d_sp_cons;
+    PinBuf<uint32_t> h_need;
     int opt_direction = -1;             // -1: by the previous sweep's candidate counts, 0: never, 1: always
     bool sp_ready = false, sp_regime = false;
     unsigned sp_count = 0;             // parameter sets since the screen came on: every 32nd sweep measures (tail pairs first), the others run it first
@@ -317,11 +302,11 @@ struct dpmm_ctx {
     int opt_lean_dir = 1;              // DPMM_OPT_LEAN_DIRECTION: the lean kernel runs the direction screen while its tables exist (0: no lean launch in that regime, as in rounds 4-5)
     int opt_master_poll = 1;           // DPMM_OPT_MASTER_POLL: dpmm_step_master_device waits on the posteriors' own records in pinned memory (no event between posteriors and draws)
     int opt_lean = 1;                  // DPMM_OPT_LEAN_TILES: tiles the cheap screens settle completely in niw_lean_kernel (-1 automatic is 1 with a regime switch; 0 never)
-    uint32_t *d_hard = nullptr;        // two lists of [2 + ceil(n / 64)] words, taking turns (hard_flip): count | wave tiles the lean kernel left to the general path;
+    DevBuf<uint32_t> d_hard;        // two lists of [2 + ceil(n / 64)] words, taking turns (hard_flip): count | wave tiles the lean kernel left to the general path;
                                        // a lean launch clears the OTHER list's count for its successor (no fill launch), niw_sub_kernel reports the count to h_hard (no copy launch)
     int hard_flip = 0;
     int perm_nbins = 0;                // bins of the sort that wrote sb.perm / sb.bin_start (0: none yet): the lean kernel aligns its tiles to them
-    uint32_t *h_hard = nullptr;        // pinned: the count of the LAST sweep's list (read by the next sweep's regime decision, never waited for)
+    PinBuf<uint32_t> h_hard;        // pinned: the count of the LAST sweep's list (read by the next sweep's regime decision, never waited for)
     int lean_off = 0;                  // sweeps left without the lean kernel (a sweep that left more than 30 % of its tiles switches it off for lean_backoff)
     bool lean_ran = false;             // the last sweep ran the lean kernel: h_hard holds its list's length
     int lean_backoff = 15;             // 15, doubled by every retry that fails again (up to 1023), back to 15 by one that succeeds: a retry on overlapping
@@ -337,8 +322,7 @@ struct dpmm_ctx {
     int rank = 0, world = 1;
     dpmm_host_allreduce_fn host_fn = nullptr;
     void *host_user = nullptr;
-    char *h_red = nullptr;             // pinned staging of the host transport
-    size_t h_red_bytes = 0;
+    PinBuf<char> h_red;             // pinned staging of the host transport
     hipEvent_t ev_comm[4] = {nullptr, nullptr, nullptr, nullptr};   // [0,1] around the occupancy all-reduce, [2,3] around the packed rows
     bool have_comm_ev[2] = {false, false};
     int64_t comm_bytes[2] = {0, 0};    // payload of the last all-reduce of each kind
@@ -366,8 +350,8 @@ struct dpmm_ctx {
     std::atomic<bool> comm_aborted{false};
     // ONE collective per per-step pass (DPMM_OPT_ONE_COLLECTIVE; NIW, communicator attached): see run_stats
     int opt_one_collective = -1;       // -1: automatic (rows short enough that half a message more is cheaper than a second collective), 0 / 1
-    uint8_t *d_cside = nullptr;        // [DPMM_MAX_CLUSTERS] clusters whose sub-labels this shard reset speculatively: the side its points were on (1 / 2), 0: none
-    double *d_red = nullptr;           // [3 Kcap][packed_stride]: what travels -- 2K rows of the labels as swept | K re-drawn left rows -- input of the finalize kernel
+    DevBuf<uint8_t> d_cside;        // [DPMM_MAX_CLUSTERS] clusters whose sub-labels this shard reset speculatively: the side its points were on (1 / 2), 0: none
+    DevBuf<double> d_red;           // [3 Kcap][packed_stride]: what travels -- 2K rows of the labels as swept | K re-drawn left rows -- input of the finalize kernel
     bool last_pass_one_collective = false;
     bool undo_pending = false;         // niw_undo_reset_kernel of the last one-collective pass not launched yet (flush_undo)
 
@@ -427,22 +411,37 @@ static inline hipError_t sync_event(dpmm_ctx *c, hipEvent_t ev) {
     return e;
 }
 
-static int ensure_pinned(dpmm_ctx *c, size_t bytes) {
-    if (bytes <= c->h_pin_bytes) return DPMM_OK;
-    HIPCHK(c, sync_stream(c, c->stream));
-    if (c->h_pin) hipHostFree(c->h_pin);
-    c->h_pin = nullptr; c->h_pin_bytes = 0;
-    size_t cap = 1 << 20;
-    while (cap < bytes) cap *= 2;
-    HIPCHK(c, hipHostMalloc((void **)&c->h_pin, cap, hipHostMallocDefault));
-    c->h_pin_bytes = cap;
-    return DPMM_OK;
-}
-
 static int fail(dpmm_ctx *c, int code, const std::string &msg) {
     if (c) c->err = msg; else g_create_error = msg;
     return code;
 }
+
+// The one grow-on-demand routine of this file.  grow: a buffer that holds `need` bytes is left alone (a compare and a return: it sits on
+// the per-step path); otherwise the ctx stream is waited for -- something queued may still read the old block -- and the buffer replaced
+// (contents are not kept).  floor == 0: exactly `need` bytes; else the smallest floor * 2^k that holds them.  regrow is the second half
+// alone, for the callers that wait for more than the ctx stream, or on purpose for nothing, before they let go of the old block.
+template <class Buf>
+static int regrow(dpmm_ctx *c, Buf &buf, size_t need, const char *who, const char *what, size_t floor = 0) {
+    const size_t cap = grow_capacity(need, floor);
+    if (buf.alloc(cap) != hipSuccess)
+        return fail(c, DPMM_EHIP, std::string(who) + ": out of device memory for the " + what + " (" + std::to_string((unsigned long long)cap) + " bytes)");
+    return DPMM_OK;
+}
+template <class Buf>
+static inline int grow(dpmm_ctx *c, Buf &buf, size_t need, const char *who, const char *what, size_t floor = 0) {
+    if (need <= buf.bytes) return DPMM_OK;
+    HIPCHK(c, sync_stream(c, c->stream));
+    return regrow(c, buf, need, who, what, floor);
+}
+// a table of the sampler (include/dpmm_hip_sample.h): exactly `bytes`, filled from the host
+template <typename T>
+static int sampler_table(dpmm_ctx *c, DevBuf<T> &dst, const T *src, size_t bytes) {
+    HIPCHK(c, dst.alloc(bytes));
+    HIPCHK(c, hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
+    return DPMM_OK;
+}
+// pinned host staging of every per-step transfer
+static inline int ensure_pinned(dpmm_ctx *c, size_t bytes) { return grow(c, c->h_pin, bytes, "dpmm", "pinned staging block", (size_t)1 << 20); }
 
 // ---- RCCL, bound at run time ---------------------------------------------------------------------------------------------
 // The library must load (and `pytest -m "not gpu"` must be able to check its exports) on machines without RCCL, and a
@@ -501,15 +500,7 @@ static int comm_allreduce(dpmm_ctx *c, void *dbuf, size_t count, int kind) {
         c->coll_pending = true;
     } else {
         const size_t bytes = count * 8;
-        if (bytes > c->h_red_bytes) {
-            HIPCHK(c, sync_stream(c, c->stream));
-            if (c->h_red) hipHostFree(c->h_red);
-            c->h_red = nullptr; c->h_red_bytes = 0;
-            size_t cap = 1 << 16;
-            while (cap < bytes) cap *= 2;
-            HIPCHK(c, hipHostMalloc((void **)&c->h_red, cap, hipHostMallocDefault));
-            c->h_red_bytes = cap;
-        }
+        if (int rc = grow(c, c->h_red, bytes, "host all-reduce", "pinned staging block", (size_t)1 << 16)) return rc;
         HIPCHK(c, launch_copy_bytes(c->h_red, dbuf, bytes, c->stream));
         HIPCHK(c, sync_stream(c, c->stream));
         const int rc = c->host_fn(c->host_user, c->h_red, (int64_t)count, f64 ? 1 : 0);
@@ -565,15 +556,11 @@ int dpmm_abi_version(void) { return DPMM_ABI_VERSION; }
 
 const char *dpmm_last_error(const dpmm_ctx *ctx) { return ctx ? ctx->err.c_str() : g_create_error.c_str(); }
 
+// The buffers whose size depends on the number of clusters are about to be re-allocated (ensure_capacity, member by member): what is
+// known about their contents goes with them
 static void free_params(dpmm_ctx *c) {
-    hipFree(c->d_raw); hipFree(c->d_mu); hipFree(c->d_Rp); hipFree(c->d_mup); hipFree(c->d_cst);
-    hipFree(c->d_ccache); c->d_ccache = nullptr;
-    hipFree(c->d_red); c->d_red = nullptr;
-    hipFree(c->d_scratch); hipFree(c->d_slabs); hipFree(c->d_out); hipFree(c->d_Lp16); hipFree(c->d_tdf); hipFree(c->d_lam); hipFree(c->d_mdist); hipFree(c->d_tail); hipFree(c->d_refb_big);
-    hipFree(c->d_raw2); hipFree(c->d_Rp2); hipFree(c->d_Lp16_2); c->d_raw2 = c->d_Rp2 = nullptr; c->d_Lp16_2 = nullptr; c->mspec_valid = false;
-    c->d_Lp16 = nullptr; c->d_tdf = nullptr; c->d_lam = nullptr; c->d_mdist = nullptr; c->d_tail = nullptr; c->d_refb_big = nullptr; c->have_refb_big = false;
-    c->d_raw = c->d_mu = c->d_Rp = c->d_mup = c->d_cst = c->d_scratch = nullptr;
-    c->d_slabs = c->d_out = nullptr;
+    c->mspec_valid = false;
+    c->have_refb_big = false;
 }
 
 // (re)allocate everything whose size depends on the number of clusters
@@ -587,37 +574,38 @@ static int ensure_capacity(dpmm_ctx *c, int K) {
     const size_t D = (size_t)c->D;
     if (c->prior == DPMM_PRIOR_NIW) {
         const size_t NP = (size_t)c->NB * (c->NB + 1) / 2;
-        HIPCHK(c, hipMalloc(&c->d_raw, sizeof(float) * 3 * cap * D * D));
-        HIPCHK(c, hipMalloc(&c->d_mu, sizeof(float) * 3 * cap * D));
-        HIPCHK(c, hipMalloc(&c->d_Rp, sizeof(float) * 3 * cap * NP * 256));
-        HIPCHK(c, hipMalloc(&c->d_mup, sizeof(float) * 3 * cap * 16 * c->NB));
-        HIPCHK(c, hipMalloc(&c->d_lam, sizeof(float) * cap));
-        if (c->NB == 8 || c->NB == 16) HIPCHK(c, hipMalloc(&c->d_refb_big, sizeof(uint32_t) * cap * niw_refb_big_words(c->NB)));
-        HIPCHK(c, hipMalloc(&c->d_tail, sizeof(float) * (c->NB == 4 ? niw_tail_floats(cap) : 16 * (cap + 2) + 16 * cap + (size_t)REFB_WORDS * cap)));      // pair records | per-cluster ball records | bf16 images of the reference bracket | (NB = 4) three-plane images + offsets of niw_lean.hip
-        HIPCHK(c, hipMalloc(&c->d_mdist, sizeof(float) * (size_t)cap * cap));
+        HIPCHK(c, c->d_raw.alloc(sizeof(float) * 3 * cap * D * D));
+        HIPCHK(c, c->d_mu.alloc(sizeof(float) * 3 * cap * D));
+        HIPCHK(c, c->d_Rp.alloc(sizeof(float) * 3 * cap * NP * 256));
+        HIPCHK(c, c->d_mup.alloc(sizeof(float) * 3 * cap * 16 * c->NB));
+        HIPCHK(c, c->d_lam.alloc(sizeof(float) * cap));
+        if (c->NB == 8 || c->NB == 16) HIPCHK(c, c->d_refb_big.alloc(sizeof(uint32_t) * cap * niw_refb_big_words(c->NB)));
+        HIPCHK(c, c->d_tail.alloc(sizeof(float) * (c->NB == 4 ? niw_tail_floats(cap) : 16 * (cap + 2) + 16 * cap + (size_t)REFB_WORDS * cap)));      // pair records | per-cluster ball records | bf16 images of the reference bracket | (NB = 4) three-plane images + offsets of niw_lean.hip
+        HIPCHK(c, c->d_mdist.alloc(sizeof(float) * (size_t)cap * cap));
     } else {
         const size_t NT = (size_t)(c->ldx + 15) / 16, NRB = (size_t)(3 * cap + 15) / 16;
-        HIPCHK(c, hipMalloc(&c->d_raw, sizeof(float) * 3 * cap * (size_t)c->ldx));
-        HIPCHK(c, hipMalloc(&c->d_Rp, sizeof(float) * NRB * NT * 256));
-        HIPCHK(c, hipMalloc(&c->d_Lp16, sizeof(uint32_t) * std::max(mult_pack_bf16_words(3 * cap, c->ldx), mult_pack_u8_words(3 * cap, (c->D + 127) / 128 * 128))));
-        HIPCHK(c, hipMalloc(&c->d_raw2, sizeof(float) * 3 * cap * (size_t)c->ldx));
-        HIPCHK(c, hipMalloc(&c->d_Rp2, sizeof(float) * NRB * NT * 256));
-        HIPCHK(c, hipMalloc(&c->d_Lp16_2, sizeof(uint32_t) * std::max(mult_pack_bf16_words(3 * cap, c->ldx), mult_pack_u8_words(3 * cap, (c->D + 127) / 128 * 128))));
+        const size_t lp16 = sizeof(uint32_t) * std::max(mult_pack_bf16_words(3 * cap, c->ldx), mult_pack_u8_words(3 * cap, (c->D + 127) / 128 * 128));
+        HIPCHK(c, c->d_raw.alloc(sizeof(float) * 3 * cap * (size_t)c->ldx));
+        HIPCHK(c, c->d_Rp.alloc(sizeof(float) * NRB * NT * 256));
+        HIPCHK(c, c->d_Lp16.alloc(lp16));
+        HIPCHK(c, c->d_raw2.alloc(sizeof(float) * 3 * cap * (size_t)c->ldx));
+        HIPCHK(c, c->d_Rp2.alloc(sizeof(float) * NRB * NT * 256));
+        HIPCHK(c, c->d_Lp16_2.alloc(lp16));
     }
-    HIPCHK(c, hipMalloc(&c->d_cst, sizeof(float) * 3 * cap));
-    HIPCHK(c, hipMalloc(&c->d_tdf, sizeof(float) * 6 * cap));
+    HIPCHK(c, c->d_cst.alloc(sizeof(float) * 3 * cap));
+    HIPCHK(c, c->d_tdf.alloc(sizeof(float) * 6 * cap));
     // sweep scratch: one a_k row set per resident workgroup; the Multinomial kernel keeps all 3K rows
     const int rows = (c->prior == DPMM_PRIOR_NIW) ? cap : 3 * cap;
     c->scratch_stride = (int64_t)c->sweep_grid * c->tile;
-    HIPCHK(c, hipMalloc(&c->d_scratch, sizeof(float) * (size_t)rows * (size_t)c->scratch_stride));
+    HIPCHK(c, c->d_scratch.alloc(sizeof(float) * (size_t)rows * (size_t)c->scratch_stride));
     // statistics
     c->max_items = (int)((c->n + c->chunk - 1) / c->chunk) + 2 * cap;
     // NIW: one slab per SLOT (a workgroup of the statistics kernel, or a bin whose first item lies inside a workgroup's range); Multinomial: per item
     const size_t nslabs = c->prior == DPMM_PRIOR_NIW ? (size_t)NIW_STATS_MAX_GROUPS + 2 * (size_t)cap : (size_t)c->max_items;
-    HIPCHK(c, hipMalloc(&c->d_slabs, sizeof(double) * nslabs * (size_t)c->slab_stride));
-    HIPCHK(c, hipMalloc(&c->d_out, sizeof(double) * 2 * cap * (size_t)c->packed_stride + DPMM_MAX_CLUSTERS + 64));   // rows | bad-cluster flags
-    HIPCHK(c, hipMalloc(&c->d_red, sizeof(double) * 3 * (size_t)cap * (size_t)c->packed_stride));
-    HIPCHK(c, hipMalloc(&c->d_ccache, sizeof(double) * cap * (size_t)c->packed_stride));
+    HIPCHK(c, c->d_slabs.alloc(sizeof(double) * nslabs * (size_t)c->slab_stride));
+    HIPCHK(c, c->d_out.alloc(sizeof(double) * 2 * cap * (size_t)c->packed_stride + DPMM_MAX_CLUSTERS + 64));   // rows | bad-cluster flags
+    HIPCHK(c, c->d_red.alloc(sizeof(double) * 3 * (size_t)cap * (size_t)c->packed_stride));
+    HIPCHK(c, c->d_ccache.alloc(sizeof(double) * cap * (size_t)c->packed_stride));
     HIPCHK(c, hipMemsetAsync(c->d_ccache, 0, sizeof(double) * cap * (size_t)c->packed_stride, c->stream));      // (on the stream its readers run on)
     c->cache_force = true;
     c->Kcap = cap;
@@ -626,6 +614,15 @@ static int ensure_capacity(dpmm_ctx *c, int K) {
 
 // words of ONE tile list of the lean sweep: count + (position, count) per tile; at most ceil(n / 64) + NIW_LEAN_MAX_BINS tiles (bin-aligned)
 static size_t hard_list_words(int64_t n) { return 4 + 2 * ((size_t)((n + 63) / 64) + NIW_LEAN_MAX_BINS + 2); }
+
+// the kernels' view of the sort buffers (dpmm_kernels.h SortBufs): the owners are c->sort_mem
+static void sort_view(dpmm_ctx *c) {
+    auto &m = c->sort_mem;
+    SortBufs &b = c->sb;
+    b.tile_hist = m.tile_hist; b.tile_cnt = m.tile_cnt; b.spec_bins = m.spec_bins; b.tile_spec = m.tile_spec; b.fast_total = m.fast_total;
+    b.ticket = m.ticket; b.prev_lab = m.prev_lab; b.cdirty = m.cdirty; b.cmode = m.cmode; b.bin_total = m.bin_total; b.bin_start = m.bin_start;
+    b.perm = m.perm; b.item_start = m.item_start; b.bin_sel = m.bin_sel; b.perm_total = m.perm_total;
+}
 
 int dpmm_create(dpmm_ctx **out, int prior_kind, int D, int64_t n_local, int64_t first_index, int device, uint64_t seed) {
     if (!out) return fail(nullptr, DPMM_EINVAL, "ctx out pointer is null");
@@ -664,8 +661,8 @@ int dpmm_create(dpmm_ctx **out, int prior_kind, int D, int64_t n_local, int64_t 
         c->slab_stride = niw_slab_stride(D);
         c->packed_stride = 1 + (int64_t)D + (int64_t)D * (D + 1) / 2;
         c->sweep_grid = c->cus * niw_occupancy(c->NB);
-        CHK_CREATE(hipMalloc(&c->d_row_off, sizeof(int32_t) * (size_t)c->packed_stride));
-        CHK_CREATE(hipMalloc(&c->d_inv_off, sizeof(int32_t) * (size_t)c->slab_stride));
+        CHK_CREATE(c->d_row_off.alloc(sizeof(int32_t) * (size_t)c->packed_stride));
+        CHK_CREATE(c->d_inv_off.alloc(sizeof(int32_t) * (size_t)c->slab_stride));
         CHK_CREATE(launch_niw_row_offsets(c->d_row_off, c->d_inv_off, D, c->packed_stride, c->stream));
     } else {
         c->tile = mult_tile_points();
@@ -690,8 +687,8 @@ int dpmm_create(dpmm_ctx **out, int prior_kind, int D, int64_t n_local, int64_t 
     c->chunk_dense = c->chunk;
     const size_t nalloc = (size_t)std::max<int64_t>(n_local, 1);
     // (Multinomial: the dense matrix is allocated by the first dense upload -- ensure_points_buffer -- a context that is given sparse points never holds one)
-    if (prior_kind == DPMM_PRIOR_NIW) CHK_CREATE(hipMalloc(&c->dX, sizeof(float) * nalloc * (size_t)c->ldx));
-    CHK_CREATE(hipMalloc(&c->dbins, sizeof(int32_t) * nalloc));
+    if (prior_kind == DPMM_PRIOR_NIW) CHK_CREATE(c->dX.alloc(sizeof(float) * nalloc * (size_t)c->ldx));
+    CHK_CREATE(c->dbins.alloc(sizeof(int32_t) * nalloc));
     // sort tiles: 512 points per sorting wave below 4e6 points (the tile kernels are one-wave latency chains: at the 8-GPU shard size four
     // times as many waves of a quarter of the trips each), 2048 above; the tables are sized for whichever is in use (DPMM_OPT_SORT_TILE
     // may switch while the shard is small enough for the small tile's tables)
@@ -700,48 +697,49 @@ int dpmm_create(dpmm_ctx **out, int prior_kind, int D, int64_t n_local, int64_t 
     c->sort_tile_min = alloc_tile;
     c->nt_sort = (int)((n_local + alloc_tile - 1) / alloc_tile);
     const size_t nbmax = 2 * DPMM_MAX_CLUSTERS;
-    CHK_CREATE(hipMalloc(&c->sb.tile_hist, sizeof(int32_t) * nbmax * (size_t)std::max(1, c->nt_sort)));
-    CHK_CREATE(hipMalloc(&c->sb.tile_cnt, sizeof(int32_t) * nbmax * (size_t)std::max(1, c->nt_sort)));
-    CHK_CREATE(hipMalloc(&c->sb.tile_spec, sizeof(int32_t) * (size_t)STEP_SPEC_MAX_BINS * (size_t)std::max(1, c->nt_sort)));
-    CHK_CREATE(hipMalloc(&c->sb.spec_bins, sizeof(int32_t) * nalloc));
-    CHK_CREATE(hipMalloc(&c->sb.fast_total, sizeof(int32_t) * nbmax * FAST_TOTAL_STRIDE));
-    CHK_CREATE(hipMemsetAsync(c->sb.fast_total, 0, sizeof(int32_t) * nbmax * FAST_TOTAL_STRIDE, c->stream));
-    CHK_CREATE(hipMalloc(&c->sb.ticket, sizeof(unsigned)));
-    CHK_CREATE(hipMemsetAsync(c->sb.ticket, 0, sizeof(unsigned), c->stream));
-    CHK_CREATE(hipMalloc(&c->sb.prev_lab, sizeof(uint16_t) * (((size_t)nalloc + SORT_TILE - 1) / SORT_TILE * SORT_TILE)));
-    CHK_CREATE(hipMemsetAsync(c->sb.prev_lab, 0xFF, sizeof(uint16_t) * (((size_t)nalloc + SORT_TILE - 1) / SORT_TILE * SORT_TILE), c->stream));
-    CHK_CREATE(hipMalloc(&c->sb.cdirty, DPMM_MAX_CLUSTERS + 8));
-    CHK_CREATE(hipMemsetAsync(c->sb.cdirty, 1, DPMM_MAX_CLUSTERS + 8, c->stream));
-    CHK_CREATE(hipMalloc(&c->sb.cmode, DPMM_MAX_CLUSTERS));
-    CHK_CREATE(hipMemsetAsync(c->sb.cmode, 0, DPMM_MAX_CLUSTERS, c->stream));
-    CHK_CREATE(hipMalloc(&c->sb.bin_total, sizeof(int32_t) * nbmax));
-    CHK_CREATE(hipMalloc(&c->sb.bin_start, sizeof(int32_t) * (nbmax + 1)));
-    CHK_CREATE(hipMalloc(&c->sb.item_start, sizeof(int32_t) * (nbmax + 1)));
-    CHK_CREATE(hipMalloc(&c->sb.perm, sizeof(int32_t) * nalloc));
-    CHK_CREATE(hipMalloc(&c->sb.bin_sel, nbmax));
+    CHK_CREATE(c->sort_mem.tile_hist.alloc(sizeof(int32_t) * nbmax * (size_t)std::max(1, c->nt_sort)));
+    CHK_CREATE(c->sort_mem.tile_cnt.alloc(sizeof(int32_t) * nbmax * (size_t)std::max(1, c->nt_sort)));
+    CHK_CREATE(c->sort_mem.tile_spec.alloc(sizeof(int32_t) * (size_t)STEP_SPEC_MAX_BINS * (size_t)std::max(1, c->nt_sort)));
+    CHK_CREATE(c->sort_mem.spec_bins.alloc(sizeof(int32_t) * nalloc));
+    CHK_CREATE(c->sort_mem.fast_total.alloc(sizeof(int32_t) * nbmax * FAST_TOTAL_STRIDE));
+    CHK_CREATE(hipMemsetAsync(c->sort_mem.fast_total, 0, sizeof(int32_t) * nbmax * FAST_TOTAL_STRIDE, c->stream));
+    CHK_CREATE(c->sort_mem.ticket.alloc(sizeof(unsigned)));
+    CHK_CREATE(hipMemsetAsync(c->sort_mem.ticket, 0, sizeof(unsigned), c->stream));
+    CHK_CREATE(c->sort_mem.prev_lab.alloc(sizeof(uint16_t) * (((size_t)nalloc + SORT_TILE - 1) / SORT_TILE * SORT_TILE)));
+    CHK_CREATE(hipMemsetAsync(c->sort_mem.prev_lab, 0xFF, sizeof(uint16_t) * (((size_t)nalloc + SORT_TILE - 1) / SORT_TILE * SORT_TILE), c->stream));
+    CHK_CREATE(c->sort_mem.cdirty.alloc(DPMM_MAX_CLUSTERS + 8));
+    CHK_CREATE(hipMemsetAsync(c->sort_mem.cdirty, 1, DPMM_MAX_CLUSTERS + 8, c->stream));
+    CHK_CREATE(c->sort_mem.cmode.alloc(DPMM_MAX_CLUSTERS));
+    CHK_CREATE(hipMemsetAsync(c->sort_mem.cmode, 0, DPMM_MAX_CLUSTERS, c->stream));
+    CHK_CREATE(c->sort_mem.bin_total.alloc(sizeof(int32_t) * nbmax));
+    CHK_CREATE(c->sort_mem.bin_start.alloc(sizeof(int32_t) * (nbmax + 1)));
+    CHK_CREATE(c->sort_mem.item_start.alloc(sizeof(int32_t) * (nbmax + 1)));
+    CHK_CREATE(c->sort_mem.perm.alloc(sizeof(int32_t) * nalloc));
+    CHK_CREATE(c->sort_mem.bin_sel.alloc(nbmax));
     c->sel_capacity = (int)nbmax;
-    CHK_CREATE(hipMalloc(&c->sb.perm_total, sizeof(int32_t)));
-    CHK_CREATE(hipMalloc(&c->d_small, sizeof(int32_t) * 4 * DPMM_MAX_CLUSTERS));
-    CHK_CREATE(hipMalloc(&c->d_counts64, sizeof(long long) * 2 * DPMM_MAX_CLUSTERS));
-    CHK_CREATE(hipMalloc(&c->d_cside, DPMM_MAX_CLUSTERS));
+    CHK_CREATE(c->sort_mem.perm_total.alloc(sizeof(int32_t)));
+    sort_view(c);
+    CHK_CREATE(c->d_small.alloc(sizeof(int32_t) * 4 * DPMM_MAX_CLUSTERS));
+    CHK_CREATE(c->d_counts64.alloc(sizeof(long long) * 2 * DPMM_MAX_CLUSTERS));
+    CHK_CREATE(c->d_cside.alloc(DPMM_MAX_CLUSTERS));
     CHK_CREATE(hipMemsetAsync(c->d_cside, 0, DPMM_MAX_CLUSTERS, c->stream));
     if (c->prior == DPMM_PRIOR_NIW && c->NB == 4) {
-        CHK_CREATE(hipMalloc(&c->d_sp_frag, sizeof(uint32_t) * (size_t)SP_MAXK * SP_FRAG_WORDS));
-        CHK_CREATE(hipMalloc(&c->d_sp_cons, sizeof(float) * (size_t)SP_MAXK * SP_CONS_FLOATS));
+        CHK_CREATE(c->d_sp_frag.alloc(sizeof(uint32_t) * (size_t)SP_MAXK * SP_FRAG_WORDS));
+        CHK_CREATE(c->d_sp_cons.alloc(sizeof(float) * (size_t)SP_MAXK * SP_CONS_FLOATS));
         // ([8 grid]: two words per wave of the sweep kernel | [4 grid]: tiles the lean kernel settled, per wave)
         // [0, 8 g): two words per wave of the general kernel | [8 g, 12 g): one word per wave of the lean kernel (tiles settled without the direction
         // screen) | [12 g, 20 g): two words per wave of the lean kernel WITH the direction screen (round 6)      (g = sweep_grid_max workgroups of 4 waves)
-        CHK_CREATE(hipHostMalloc((void **)&c->h_need, sizeof(uint32_t) * 20 * (size_t)std::max(1, c->sweep_grid_max), hipHostMallocDefault));
+        CHK_CREATE(c->h_need.alloc(sizeof(uint32_t) * 20 * (size_t)std::max(1, c->sweep_grid_max)));
         memset(c->h_need, 0, sizeof(uint32_t) * 20 * (size_t)std::max(1, c->sweep_grid_max));
         if (c->NB == 4) {
             const size_t hw = hard_list_words(n_local);
-            CHK_CREATE(hipMalloc(&c->d_hard, sizeof(uint32_t) * 2 * hw));
+            CHK_CREATE(c->d_hard.alloc(sizeof(uint32_t) * 2 * hw));
             CHK_CREATE(hipMemsetAsync(c->d_hard, 0, sizeof(uint32_t) * 2 * hw, c->stream));
-            CHK_CREATE(hipHostMalloc((void **)&c->h_hard, 64, hipHostMallocDefault));
+            CHK_CREATE(c->h_hard.alloc(64));
             memset(c->h_hard, 0, 64);
         }
     }
-    CHK_CREATE(hipMalloc(&c->d_work, sizeof(unsigned long long) * (DPMM_WORK_SLOTS + 4 * DPMM_WORK_PER_WAVE * (size_t)std::max(1, c->sweep_grid_max))));
+    CHK_CREATE(c->d_work.alloc(sizeof(unsigned long long) * (DPMM_WORK_SLOTS + 4 * DPMM_WORK_PER_WAVE * (size_t)std::max(1, c->sweep_grid_max))));
     CHK_CREATE(hipMemsetAsync(c->d_work, 0, sizeof(unsigned long long) * (DPMM_WORK_SLOTS + 4 * DPMM_WORK_PER_WAVE * (size_t)std::max(1, c->sweep_grid_max)), c->stream));
 #undef CHK_CREATE
     *out = c;
@@ -752,51 +750,15 @@ int dpmm_destroy(dpmm_ctx *c) {
     if (!c) return DPMM_OK;
     hipSetDevice(c->device);
     if (c->stream && !c->comm_aborted.load()) hipStreamSynchronize(c->stream);
-    free_params(c);
-    hipFree(c->dX); hipFree(c->dX8); hipFree(c->d_cp); hipFree(c->d_ri); hipFree(c->d_val); hipFree(c->dbins); hipFree(c->d_gt); hipFree(c->d_cont);
-    hipFree(c->sb.tile_hist); hipFree(c->sb.tile_cnt); hipFree(c->sb.tile_spec); hipFree(c->sb.spec_bins); hipFree(c->sb.fast_total); hipFree(c->sb.ticket); hipFree(c->sb.prev_lab); hipFree(c->sb.cdirty); hipFree(c->sb.cmode); hipFree(c->sb.bin_total); hipFree(c->sb.bin_start); hipFree(c->sb.item_start);
-    hipFree(c->sb.perm); hipFree(c->sb.bin_sel); hipFree(c->sb.perm_total); hipFree(c->d_small); hipFree(c->d_proj); hipFree(c->d_vals); hipFree(c->d_smart);
-    hipFree(c->d_m0); hipFree(c->d_psi_lo); hipFree(c->d_pairs);
-    hipFree(c->d_score_table); hipFree(c->d_score_out);
-    hipFree(c->d_rank_state); hipFree(c->d_rank_cand); hipFree(c->d_rank_out);
-    hipFree(c->d_ov_acc); hipFree(c->d_ov_ms); hipFree(c->d_ov_part);
-    hipFree(c->d_trace); hipFree(c->d_trace_counts); hipFree(c->d_trace_desc); hipFree(c->d_trace_ratio); hipFree(c->d_trace_conf);
-    hipFree(c->d_miss_rt); hipFree(c->d_miss_cst); hipFree(c->d_miss_list); hipFree(c->d_miss_cnt);
-    hipFree(c->d_sm_m); hipFree(c->d_sm_At); hipFree(c->d_sm_df); hipFree(c->d_sm_thr); hipFree(c->d_sm_alias);
-    hipFree(c->d_sm_cstart); hipFree(c->d_sm_tstart); hipFree(c->d_sm_cnt); hipFree(c->d_sm_bt);
-    hipFree(c->d_proj_W); hipFree(c->d_proj_bias); hipFree(c->d_proj_stage);
-    for (int i = 0; i < 2; ++i) { hipFree(c->d_Y[i]); hipFree(c->d_ld_sigma[i]); hipFree(c->d_mu_draw[i]); }
-    hipFree(c->ma.fac); hipFree(c->ma.mean); hipFree(c->ma.kap); hipFree(c->ma.nu); hipFree(c->ma.rows_store);
-    if (c->stream2) { hipStreamSynchronize(c->stream2); hipStreamDestroy(c->stream2); }
-    for (auto &e : c->ev_part) if (e) hipEventDestroy(e);
-    if (c->ev_master) hipEventDestroy(c->ev_master);
-    if (c->ev_spec) hipEventDestroy(c->ev_spec);
-    if (c->ev_noise) hipEventDestroy(c->ev_noise);
-    if (c->ev_pairs) hipEventDestroy(c->ev_pairs);
-    if (c->ev_rows) hipEventDestroy(c->ev_rows);
-    hipFree(c->d_apairs);
-    if (c->h_apairs) hipHostFree(c->h_apairs);
-    for (auto &b : c->h_apairs_list) if (b) hipHostFree(b);
-    hipFree(c->d_jobs); hipFree(c->d_dslots);
-    for (int i = 0; i < 4; ++i) if (c->h_list[i]) hipHostFree(c->h_list[i]);
-    if (c->h_master) hipHostFree(c->h_master);
-    if (c->h_draw) hipHostFree(c->h_draw);
-    hipFree(c->d_malpha); hipFree(c->d_mpairs);
-    if (c->h_marg) hipHostFree(c->h_marg);
-    hipFree(c->d_sp_frag); hipFree(c->d_sp_cons); hipFree(c->d_brk_flag); hipFree(c->d_brk_aref);
-    if (c->h_need) hipHostFree(c->h_need);
-    if (c->h_hard) hipHostFree(c->h_hard);
-    hipFree(c->d_hard);
-    hipFree(c->d_counts64); hipFree(c->d_cside); hipFree(c->d_row_off); hipFree(c->d_inv_off); hipFree(c->d_work); hipFree(c->d_par);
+    if (c->stream2) hipStreamSynchronize(c->stream2);
     comm_release(c);
-    if (c->h_red) hipHostFree(c->h_red);
+    for (auto &e : c->ev_part) if (e) hipEventDestroy(e);
+    for (hipEvent_t e : {c->ev_master, c->ev_spec, c->ev_noise, c->ev_pairs, c->ev_rows}) if (e) hipEventDestroy(e);
     for (auto &e : c->ev_comm) if (e) hipEventDestroy(e);
-    if (c->h_pin) hipHostFree(c->h_pin);
-    if (c->h_par) hipHostFree(c->h_par);
-    if (c->h_out) hipHostFree(c->h_out);
     for (auto &e : c->ev) if (e) hipEventDestroy(e);
+    if (c->stream2) hipStreamDestroy(c->stream2);
     if (c->stream) hipStreamDestroy(c->stream);
-    delete c;
+    delete c;       // every buffer is a member: freed here, behind both streams
     return DPMM_OK;
 }
 
@@ -805,7 +767,7 @@ static int finish_upload(dpmm_ctx *c) {
     if (c->prior == DPMM_PRIOR_MULT) {
         const bool force_f32 = c->opt_force_f32 != 0;
         const int was_u8 = c->x_u8, was_bf16 = c->x_bf16_exact;
-        int *flag = reinterpret_cast<int *>(c->d_small);
+        int *flag = reinterpret_cast<int *>(c->d_small.get());
         HIPCHK(c, hipMemsetAsync(flag, 0, sizeof(int), c->stream));
         HIPCHK(c, launch_bf16_exact_check(c->dX, c->n * c->ldx, flag, c->stream));
         int h = 1;
@@ -816,16 +778,16 @@ static int finish_upload(dpmm_ctx *c) {
         if (c->x_bf16_exact && !c->opt_no_u8 && c->n > 0) {
             // small non-negative integers (bag-of-words counts): keep a lossless byte copy and stream 1 byte per element
             c->ld8 = (c->D + 127) / 128 * 128;
-            if (!c->dX8) HIPCHK(c, hipMalloc(&c->dX8, (size_t)c->n * (size_t)c->ld8));
+            if (!c->dX8) HIPCHK(c, c->dX8.alloc((size_t)c->n * (size_t)c->ld8));
             HIPCHK(c, hipMemsetAsync(flag, 0, sizeof(int), c->stream));
             HIPCHK(c, launch_u8_convert(c->dX, c->ldx, c->D, c->n, c->dX8, c->ld8, flag, c->stream));
             HIPCHK(c, hipMemcpyAsync(&h, flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, sync_stream(c, c->stream));
             c->x_u8 = (h == 0) ? 1 : 0;
-            if (!c->x_u8) { hipFree(c->dX8); c->dX8 = nullptr; }
+            if (!c->x_u8) c->dX8.reset();
             // every Multinomial kernel of a byte-path context reads the byte copy (a lossless re-encoding): the Float32 matrix (4 bytes per
             // element, 4 GB at D = 1000, N = 1e6) is dead weight from here on; a new upload allocates it again
-            else { HIPCHK(c, hipFree(c->dX)); c->dX = nullptr; }
+            else c->dX.reset();
         }
         // parameters that stay in place across the upload were packed for the OLD points' sweep kernel (byte planes / bf16 planes / Float32
         // fragments): when the new points take another kernel, the images it reads are made from the raw rows now
@@ -858,15 +820,13 @@ static int set_points_chunk(dpmm_ctx *c, bool sparse) {
     HIPCHK(c, sync_stream(c, c->stream));
     c->chunk = want;
     if (c->Kcap > 0) {      // the slabs are allocated per item (ensure_capacity)
-        hipFree(c->d_slabs); c->d_slabs = nullptr;
         c->max_items = (int)((c->n + c->chunk - 1) / c->chunk) + 2 * c->Kcap;
-        HIPCHK(c, hipMalloc(&c->d_slabs, sizeof(double) * (size_t)c->max_items * (size_t)c->slab_stride));
+        HIPCHK(c, c->d_slabs.alloc(sizeof(double) * (size_t)c->max_items * (size_t)c->slab_stride));
     }
     return DPMM_OK;
 }
 static void free_sparse_points(dpmm_ctx *c) {
-    hipFree(c->d_cp); hipFree(c->d_ri); hipFree(c->d_val);
-    c->d_cp = nullptr; c->d_ri = nullptr; c->d_val = nullptr; c->nnz = 0;
+    c->d_cp.reset(); c->d_ri.reset(); c->d_val.reset(); c->nnz = 0;
 }
 static int ensure_points_buffer(dpmm_ctx *c) {       // (a byte-path Multinomial context gave its Float32 matrix back; one with sparse points never had it)
     if (c->x_sparse) {
@@ -876,7 +836,7 @@ static int ensure_points_buffer(dpmm_ctx *c) {       // (a byte-path Multinomial
         c->repack_pending = true;
         if (int rc = set_points_chunk(c, false)) return rc;
     }
-    if (!c->dX) HIPCHK(c, hipMalloc(&c->dX, sizeof(float) * (size_t)std::max<int64_t>(c->n, 1) * (size_t)c->ldx));
+    if (!c->dX) HIPCHK(c, c->dX.alloc(sizeof(float) * (size_t)std::max<int64_t>(c->n, 1) * (size_t)c->ldx));
     return DPMM_OK;
 }
 static int upload_common(dpmm_ctx *c, const float *X, int64_t ldx, hipMemcpyKind kind) {
@@ -909,8 +869,8 @@ int dpmm_upload_points_npy(dpmm_ctx *c, const void *rows, int is_f64, int64_t ld
         if (c->ldx != c->D) HIPCHK(c, hipMemsetAsync(c->dX, 0, sizeof(float) * (size_t)c->n * c->ldx, c->stream));
         const size_t esz = is_f64 ? sizeof(double) : sizeof(float);
         const int64_t chunk_rows = std::max<int64_t>(1, std::min<int64_t>(c->n, ((int64_t)128 << 20) / (int64_t)(esz * (size_t)ld)));
-        void *tmp = nullptr;
-        HIPCHK(c, hipMalloc(&tmp, esz * (size_t)chunk_rows * (size_t)ld));
+        DevBuf<void> tmp;
+        HIPCHK(c, tmp.alloc(esz * (size_t)chunk_rows * (size_t)ld));
         int rc = DPMM_OK;
         for (int64_t r0 = 0; r0 < c->n && rc == DPMM_OK; r0 += chunk_rows) {
             const int64_t nr = std::min(chunk_rows, c->n - r0);
@@ -919,7 +879,6 @@ int dpmm_upload_points_npy(dpmm_ctx *c, const void *rows, int is_f64, int64_t ld
             if (e == hipSuccess) e = sync_stream(c, c->stream);       // tmp is reused by the next chunk
             if (e != hipSuccess) { c->err = std::string("dpmm_upload_points_npy: ") + hipGetErrorString(e); rc = DPMM_EHIP; }
         }
-        hipFree(tmp);
         if (rc != DPMM_OK) return rc;
         if (int rc2 = finish_upload(c)) return rc2;
     }
@@ -953,24 +912,24 @@ int dpmm_upload_points_csc(dpmm_ctx *c, const int64_t *colptr, const int64_t *ro
     if (total > 0 && (!rowval || !nzval)) return fail(c, DPMM_EINVAL, "dpmm_upload_points_csc: rowval / nzval is null");
     HIPCHK(c, hipSetDevice(c->device));
     // everything is built beside the points in force; they are replaced only when the new ones have passed the checks
-    int64_t *t_cp = nullptr, *t_rv = nullptr, *n_cp = nullptr;
-    float *t_nz = nullptr, *n_val = nullptr;
-    uint16_t *n_ri = nullptr;
-    int32_t *t_cnt = nullptr;
-    unsigned long long *t_bad = nullptr;
+    DevBuf<int64_t> t_cp, t_rv, n_cp;
+    DevBuf<float> t_nz, n_val;
+    DevBuf<uint16_t> n_ri;
+    DevBuf<int32_t> t_cnt;
+    DevBuf<unsigned long long> t_bad;
     std::vector<int32_t> cnt((size_t)n);
     std::vector<int64_t> ncp((size_t)n + 1, 0);
     unsigned long long bad = ~0ull;
     std::string msg;
     int rc = DPMM_OK;
-    hipError_t e = hipMalloc(&n_cp, sizeof(int64_t) * ((size_t)n + 1));
+    hipError_t e = n_cp.alloc(sizeof(int64_t) * ((size_t)n + 1));
     if (e == hipSuccess && n > 0) {
         const size_t tt = (size_t)std::max<int64_t>(total, 1);
-        e = hipMalloc(&t_cp, sizeof(int64_t) * ((size_t)n + 1));
-        if (e == hipSuccess) e = hipMalloc(&t_rv, sizeof(int64_t) * tt);
-        if (e == hipSuccess) e = hipMalloc(&t_nz, sizeof(float) * tt);
-        if (e == hipSuccess) e = hipMalloc(&t_cnt, sizeof(int32_t) * (size_t)n);
-        if (e == hipSuccess) e = hipMalloc(&t_bad, sizeof(unsigned long long));
+        e = t_cp.alloc(sizeof(int64_t) * ((size_t)n + 1));
+        if (e == hipSuccess) e = t_rv.alloc(sizeof(int64_t) * tt);
+        if (e == hipSuccess) e = t_nz.alloc(sizeof(float) * tt);
+        if (e == hipSuccess) e = t_cnt.alloc(sizeof(int32_t) * (size_t)n);
+        if (e == hipSuccess) e = t_bad.alloc(sizeof(unsigned long long));
         if (e == hipSuccess) e = hipMemcpyAsync(t_cp, colptr, sizeof(int64_t) * ((size_t)n + 1), hipMemcpyHostToDevice, c->stream);
         if (e == hipSuccess && total > 0) e = hipMemcpyAsync(t_rv, rowval, sizeof(int64_t) * (size_t)total, hipMemcpyHostToDevice, c->stream);
         if (e == hipSuccess && total > 0) e = hipMemcpyAsync(t_nz, nzval, sizeof(float) * (size_t)total, hipMemcpyHostToDevice, c->stream);
@@ -987,8 +946,8 @@ int dpmm_upload_points_csc(dpmm_ctx *c, const int64_t *colptr, const int64_t *ro
         if (e == hipSuccess && rc == DPMM_OK) {
             for (int64_t i = 0; i < n; ++i) ncp[i + 1] = ncp[i] + cnt[i];      // explicit zeros are dropped
             const size_t nn = (size_t)std::max<int64_t>(ncp[n], 1);
-            e = hipMalloc(&n_ri, sizeof(uint16_t) * nn);
-            if (e == hipSuccess) e = hipMalloc(&n_val, sizeof(float) * nn);
+            e = n_ri.alloc(sizeof(uint16_t) * nn);
+            if (e == hipSuccess) e = n_val.alloc(sizeof(float) * nn);
             if (e == hipSuccess) e = hipMemcpyAsync(n_cp, ncp.data(), sizeof(int64_t) * ((size_t)n + 1), hipMemcpyHostToDevice, c->stream);
             if (e == hipSuccess) e = launch_csc_compact(t_cp, t_rv, t_nz, n, index_base, n_cp, n_ri, n_val, c->stream);
             if (e == hipSuccess) e = sync_stream(c, c->stream);
@@ -997,15 +956,13 @@ int dpmm_upload_points_csc(dpmm_ctx *c, const int64_t *colptr, const int64_t *ro
         e = hipMemsetAsync(n_cp, 0, sizeof(int64_t), c->stream);
         if (e == hipSuccess) e = sync_stream(c, c->stream);
     }
-    hipFree(t_cp); hipFree(t_rv); hipFree(t_nz); hipFree(t_cnt); hipFree(t_bad);
     if (e != hipSuccess || rc != DPMM_OK) {
-        hipFree(n_cp); hipFree(n_ri); hipFree(n_val);
         if (e != hipSuccess) return fail(c, DPMM_EHIP, std::string("dpmm_upload_points_csc: ") + hipGetErrorString(e));
         return fail(c, rc, msg);
     }
-    free_sparse_points(c);
-    hipFree(c->dX); hipFree(c->dX8); c->dX = nullptr; c->dX8 = nullptr;
-    c->d_cp = n_cp; c->d_ri = n_ri; c->d_val = n_val; c->nnz = ncp[n];
+    t_cp.reset(); t_rv.reset(); t_nz.reset(); t_cnt.reset(); t_bad.reset();      // (before set_points_chunk sizes the slabs)
+    c->dX.reset(); c->dX8.reset();
+    c->d_cp = std::move(n_cp); c->d_ri = std::move(n_ri); c->d_val = std::move(n_val); c->nnz = ncp[n];
     c->x_sparse = 1; c->x_u8 = 0; c->x_bf16_exact = 0; c->repack_pending = false;
     if (int rc2 = set_points_chunk(c, true)) return rc2;
     if (c->have_params && c->d_raw) {       // parameters stay in force across an upload: the image the sparse sweep reads, from the raw rows
@@ -1045,15 +1002,14 @@ int dpmm_set_labels(dpmm_ctx *c, const int64_t *labels, const int64_t *sub) {
     if (!c->have_labels && (!labels || !sub)) return fail(c, DPMM_ESTATE, "first dpmm_set_labels must provide both vectors");
     HIPCHK(c, hipSetDevice(c->device));
     if (c->n == 0) { c->have_labels = true; return DPMM_OK; }
-    int64_t *tmp = nullptr;
-    HIPCHK(c, hipMalloc(&tmp, sizeof(int64_t) * 2 * (size_t)c->n));
+    DevBuf<int64_t> tmp;
+    HIPCHK(c, tmp.alloc(sizeof(int64_t) * 2 * (size_t)c->n));
     int rc = DPMM_OK;
     hipError_t e = hipSuccess;
     if (labels) e = hipMemcpyAsync(tmp, labels, sizeof(int64_t) * c->n, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess && sub) e = hipMemcpyAsync(tmp + c->n, sub, sizeof(int64_t) * c->n, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = launch_bins_from_i64(c->dbins, labels ? tmp : nullptr, sub ? tmp + c->n : nullptr, c->n, c->stream);
+    if (e == hipSuccess) e = launch_bins_from_i64(c->dbins, labels ? tmp.get() : nullptr, sub ? tmp + c->n : nullptr, c->n, c->stream);
     if (e == hipSuccess) e = sync_stream(c, c->stream);
-    hipFree(tmp);
     if (e != hipSuccess) { c->err = std::string("dpmm_set_labels: ") + hipGetErrorString(e); rc = DPMM_EHIP; }
     else c->have_labels = true;
     c->rows_full_K = -1;
@@ -1065,13 +1021,12 @@ int dpmm_get_labels(dpmm_ctx *c, int64_t *labels, int64_t *sub) {
     if (!c->have_labels) return fail(c, DPMM_ESTATE, "labels not initialised");
     HIPCHK(c, hipSetDevice(c->device));
     if (c->n == 0) return DPMM_OK;
-    int64_t *tmp = nullptr;
-    HIPCHK(c, hipMalloc(&tmp, sizeof(int64_t) * 2 * (size_t)c->n));
+    DevBuf<int64_t> tmp;
+    HIPCHK(c, tmp.alloc(sizeof(int64_t) * 2 * (size_t)c->n));
     hipError_t e = launch_bins_to_i64(c->dbins, tmp, tmp + c->n, c->n, c->stream);
     if (e == hipSuccess && labels) e = hipMemcpyAsync(labels, tmp, sizeof(int64_t) * c->n, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess && sub) e = hipMemcpyAsync(sub, tmp + c->n, sizeof(int64_t) * c->n, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = sync_stream(c, c->stream);
-    hipFree(tmp);
     if (e != hipSuccess) { c->err = std::string("dpmm_get_labels: ") + hipGetErrorString(e); return DPMM_EHIP; }
     return DPMM_OK;
 }
@@ -1119,9 +1074,9 @@ int dpmm_params_staging(dpmm_ctx *c, int slots, float **mu, float **mat, float *
         while (ns < slots) ns *= 2;
         ns = std::min(ns, DPMM_MAX_CLUSTERS);
         const ParLayout N = par_layout(c, ns);
-        char *nb = nullptr;
+        PinBuf<char> nb;
         HIPCHK(c, sync_stream(c, c->stream));      // a pack kernel may still read the old buffer
-        HIPCHK(c, hipHostMalloc((void **)&nb, N.bytes, hipHostMallocDefault));
+        if (int rc = regrow(c, nb, N.bytes, "dpmm_params_staging", "parameter staging")) return rc;
         memset(nb, 0, N.bytes);
         if (c->h_par) {                                  // contents are preserved (rows are slot-indexed: same offsets inside a region)
             const ParLayout O = par_layout(c, c->par_slots);
@@ -1136,9 +1091,8 @@ int dpmm_params_staging(dpmm_ctx *c, int slots, float **mu, float **mat, float *
             memcpy(nb + N.lr, c->h_par + O.lr, sizeof(float) * 2 * S);
             memcpy(nb + N.w, c->h_par + O.w, sizeof(float) * S);
             memcpy(nb + N.slot, c->h_par + O.slot, sizeof(int32_t) * S);
-            hipHostFree(c->h_par);
         }
-        c->h_par = nb; c->h_par_bytes = N.bytes; c->par_slots = ns;
+        c->h_par = std::move(nb); c->par_slots = ns;
     }
     const ParLayout L = par_layout(c, c->par_slots);
     if (mu) *mu = c->prior == DPMM_PRIOR_NIW ? reinterpret_cast<float *>(c->h_par + L.mu) : nullptr;
@@ -1183,15 +1137,9 @@ int dpmm_commit_params(dpmm_ctx *c, int K) {
         for (int k = 0; k < K; ++k) top = std::max(top, hslot[k] + 1);
         const size_t D = (size_t)c->D, T = D * (D + 1) / 2;
         const size_t img_bytes = (L.mat - L.cst) + sizeof(float) * 3 * (size_t)top * T;
-        const size_t cap = (L.logdet - L.cst) + 1024;
-        if (cap > c->d_par_bytes) {
-            HIPCHK(c, sync_stream(c, c->stream));
-            hipFree(c->d_par); c->d_par = nullptr;
-            HIPCHK(c, hipMalloc(&c->d_par, cap));
-            c->d_par_bytes = cap;
-        }
+        if (int rc = grow(c, c->d_par, (L.logdet - L.cst) + 1024, "dpmm_commit_params", "device copy of the parameter staging")) return rc;
         HIPCHK(c, launch_copy_bytes16(c->d_par, hcst, img_bytes, c->stream));
-        const float *dcst = reinterpret_cast<const float *>(c->d_par);
+        const float *dcst = reinterpret_cast<const float *>(c->d_par.get());
         hmu = reinterpret_cast<const float *>(c->d_par + (L.mu - L.cst));
         hmat = reinterpret_cast<const float *>(c->d_par + (L.mat - L.cst));
         c->have_tail = c->opt_tail && c->D >= 4 && c->D % 4 == 0 && K > 1;
@@ -1434,8 +1382,8 @@ static int run_sweep(dpmm_ctx *c, uint32_t epoch, int final_argmax, float *table
                 // its points were in one cluster, per point the lower end of a certified bracket of that cluster's value
                 if (!c->d_brk_flag) {
                     const size_t nt = (size_t)((c->n + 127) / 128);
-                    HIPCHK(c, hipMalloc(&c->d_brk_flag, sizeof(uint32_t) * std::max<size_t>(nt, 1)));
-                    HIPCHK(c, hipMalloc(&c->d_brk_aref, sizeof(float) * std::max<size_t>(nt * 128, 1)));
+                    HIPCHK(c, c->d_brk_flag.alloc(sizeof(uint32_t) * std::max<size_t>(nt, 1)));
+                    HIPCHK(c, c->d_brk_aref.alloc(sizeof(float) * std::max<size_t>(nt * 128, 1)));
                 }
                 HIPCHK(c, launch_niw_bracket_big(c->NB, a, c->d_refb_big, c->d_brk_flag, c->d_brk_aref, c->stream));
                 a.sp_frag = c->d_brk_flag; a.sp_cons = c->d_brk_aref;
@@ -1489,7 +1437,7 @@ static int run_sweep(dpmm_ctx *c, uint32_t epoch, int final_argmax, float *table
             a.bf16scr |= 4;
             a.tdf = reinterpret_cast<const float *>(list);                         // (the LSTORE instantiations' tile list: null = all tiles)
             const float *mdist_kept = a.mdist;
-            if (list) a.mdist = reinterpret_cast<const float *>(c->h_hard);        // (LIST instantiations: where the list's length goes; they also finish the spans' sub-labels)
+            if (list) a.mdist = reinterpret_cast<const float *>(c->h_hard.get());        // (LIST instantiations: where the list's length goes; they also finish the spans' sub-labels)
             HIPCHK(c, launch_niw_sweep(c->NB, a, c->sweep_grid, c->stream));
             a.mdist = mdist_kept;
             if (parts) HIPCHK(c, hipEventRecord(c->ev_part[1], c->stream));
@@ -1610,21 +1558,20 @@ int dpmm_predict_points(dpmm_ctx *c, int64_t *labels, float *probs) {
     if (c->n == 0) return DPMM_OK;
     const int64_t stride = c->ntiles * c->tile;
     const int rstep = (c->prior == DPMM_PRIOR_NIW) ? 1 : 3;       // Multinomial: rows 3k are the cluster-level rows
-    float *table = nullptr, *d_probs = nullptr;
-    int64_t *d_lab = nullptr;
-    HIPCHK(c, hipMalloc(&table, sizeof(float) * (size_t)(rstep * c->K) * (size_t)stride));
+    DevBuf<float> table, d_probs;
+    DevBuf<int64_t> d_lab;
+    HIPCHK(c, table.alloc(sizeof(float) * (size_t)(rstep * c->K) * (size_t)stride));
     int rc = run_sweep(c, 0, 0, table, stride);
     hipError_t e = hipSuccess;
     if (rc == DPMM_OK) {
-        e = hipMalloc(&d_lab, sizeof(int64_t) * (size_t)c->n);
-        if (e == hipSuccess && probs) e = hipMalloc(&d_probs, sizeof(float) * (size_t)c->n * (size_t)c->K);
+        e = d_lab.alloc(sizeof(int64_t) * (size_t)c->n);
+        if (e == hipSuccess && probs) e = d_probs.alloc(sizeof(float) * (size_t)c->n * (size_t)c->K);
         if (e == hipSuccess) e = launch_predict_finish(table, stride, rstep, c->n, c->K, d_lab, d_probs, c->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(labels, d_lab, sizeof(int64_t) * (size_t)c->n, hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess && probs) e = hipMemcpyAsync(probs, d_probs, sizeof(float) * (size_t)c->n * (size_t)c->K, hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = sync_stream(c, c->stream);
         if (e != hipSuccess) { c->err = std::string("dpmm_predict_points: ") + hipGetErrorString(e); rc = DPMM_EHIP; }
     }
-    hipFree(table); hipFree(d_lab); hipFree(d_probs);
     return rc;
 }
 
@@ -1635,8 +1582,8 @@ int dpmm_debug_loglik(dpmm_ctx *c, float *out) {
     if (c->n == 0) return DPMM_OK;
     const int64_t stride = c->ntiles * c->tile;
     const int rows = (c->prior == DPMM_PRIOR_NIW) ? c->K : 3 * c->K;
-    float *table = nullptr;
-    HIPCHK(c, hipMalloc(&table, sizeof(float) * (size_t)rows * (size_t)stride));
+    DevBuf<float> table;
+    HIPCHK(c, table.alloc(sizeof(float) * (size_t)rows * (size_t)stride));
     int rc = run_sweep(c, 0, 0, table, stride);
     if (rc == DPMM_OK) {
         // Multinomial: rows 3k of the 3K-row table are the cluster-level rows
@@ -1651,23 +1598,17 @@ int dpmm_debug_loglik(dpmm_ctx *c, float *out) {
             for (size_t i = 0; i < (size_t)c->K * (size_t)c->n; ++i) out[i] += k2pi;
         }
     }
-    hipFree(table);
     return rc;
 }
 
 int64_t dpmm_packed_stride(const dpmm_ctx *c) { return c ? c->packed_stride : 0; }
 
-static int ensure_out(dpmm_ctx *c, size_t bytes) {
-    if (bytes <= c->h_out_bytes) return DPMM_OK;
+// statistics output (rows | flags) in pinned memory.  Growing it waits for the stream: rows announced as late have arrived by then
+static inline int ensure_out(dpmm_ctx *c, size_t bytes) {
+    if (bytes <= c->h_out.bytes) return DPMM_OK;
     HIPCHK(c, sync_stream(c, c->stream));
     c->rows_late = false;
-    if (c->h_out) hipHostFree(c->h_out);
-    c->h_out = nullptr; c->h_out_bytes = 0;
-    size_t cap = 1 << 20;
-    while (cap < bytes) cap *= 2;
-    HIPCHK(c, hipHostMalloc((void **)&c->h_out, cap, hipHostMallocDefault));
-    c->h_out_bytes = cap;
-    return DPMM_OK;
+    return regrow(c, c->h_out, bytes, "dpmm", "pinned statistics rows", (size_t)1 << 20);
 }
 
 // One-collective pass: the sub-labels of this shard's candidates that turned out not to be bad go back to the side they were on.  Labels
@@ -1676,7 +1617,7 @@ static int ensure_out(dpmm_ctx *c, size_t bytes) {
 static int flush_undo(dpmm_ctx *c) {
     if (!c->undo_pending) return DPMM_OK;
     c->undo_pending = false;
-    const uint8_t *flags = reinterpret_cast<const uint8_t *>(c->d_out) + sizeof(double) * 2 * (size_t)c->K * (size_t)c->packed_stride;
+    const uint8_t *flags = reinterpret_cast<const uint8_t *>(c->d_out.get()) + sizeof(double) * 2 * (size_t)c->K * (size_t)c->packed_stride;
     HIPCHK(c, launch_niw_undo_reset(c->dbins, c->n, c->K, flags, c->d_cside, c->stream));
     return DPMM_OK;
 }
@@ -1748,7 +1689,7 @@ static int run_stats(dpmm_ctx *c, const int64_t *idx, int n_idx, bool with_reset
             if (int rc = comm_allreduce(c, c->d_counts64, nbins, /*kind=*/0)) return rc;
             gc = c->d_counts64;
         }
-        uint8_t *flags = reinterpret_cast<uint8_t *>(c->d_out) + sizeof(double) * (size_t)nbins * (size_t)c->packed_stride;
+        uint8_t *flags = reinterpret_cast<uint8_t *>(c->d_out.get()) + sizeof(double) * (size_t)nbins * (size_t)c->packed_stride;
         // (one collective: this shard's own occupancies decide which clusters are reset speculatively; the verdict follows the all-reduce)
         if (!fold_reset) HIPCHK(c, launch_step_reset(c->dbins, c->n, c->first, nbins, c->sb, gc, flags, c->K, c->seed, reset_epoch, one_coll ? c->d_cside : nullptr, c->stream));
         // Statistics of the SMALLER sub-cluster only wherever no point entered or left the cluster since its cluster-level row was
@@ -1773,7 +1714,7 @@ static int run_stats(dpmm_ctx *c, const int64_t *idx, int n_idx, bool with_reset
                 if (int rc = comm_allreduce(c, c->d_counts64, nbins, /*kind=*/0)) return rc;
                 gc = c->d_counts64;
             }
-            uint8_t *flags = reinterpret_cast<uint8_t *>(c->d_out) + sizeof(double) * (size_t)nbins * (size_t)c->packed_stride;
+            uint8_t *flags = reinterpret_cast<uint8_t *>(c->d_out.get()) + sizeof(double) * (size_t)nbins * (size_t)c->packed_stride;
             HIPCHK(c, launch_bad_flags(c->sb.bin_total, gc, c->K, flags, c->stream));
         }
         HIPCHK(c, launch_sort_finish(c->dbins, a, c->stream));
@@ -1782,7 +1723,7 @@ static int run_stats(dpmm_ctx *c, const int64_t *idx, int n_idx, bool with_reset
     c->perm_nbins = nbins;
     if (flags_sent) *flags_sent = false;
     if (one_coll) {
-        uint8_t *flags = reinterpret_cast<uint8_t *>(c->d_out) + sizeof(double) * (size_t)nbins * (size_t)c->packed_stride;
+        uint8_t *flags = reinterpret_cast<uint8_t *>(c->d_out.get()) + sizeof(double) * (size_t)nbins * (size_t)c->packed_stride;
         const size_t nred = 3 * (size_t)c->K * (size_t)c->packed_stride;
         if (c->n > 0 && c->prior == DPMM_PRIOR_NIW) {
             if (derive) { a.mode = c->sb.cmode; a.cache = c->d_ccache; a.dirty = c->sb.cdirty; a.K = c->K; }
@@ -1816,7 +1757,7 @@ static int run_stats(dpmm_ctx *c, const int64_t *idx, int n_idx, bool with_reset
     }
     // (flags_to: the caller's pinned block for the bad-cluster flags -- they ride in the derivation's launch when no collective follows it)
     const bool ride = derive && flags_to != nullptr && !comm_attached(c);
-    const uint8_t *fsrc = reinterpret_cast<const uint8_t *>(c->d_out) + sizeof(double) * (size_t)nbins * (size_t)c->packed_stride;
+    const uint8_t *fsrc = reinterpret_cast<const uint8_t *>(c->d_out.get()) + sizeof(double) * (size_t)nbins * (size_t)c->packed_stride;
     if (c->prior == DPMM_PRIOR_NIW) {
         if (derive) {       // the reduce kernel derives the rows that were not computed (one launch and one round trip of the rows less)
             a.mode = c->sb.cmode; a.cache = c->d_ccache; a.dirty = c->sb.cdirty; a.K = c->K;
@@ -1851,7 +1792,7 @@ int dpmm_bin_counts(dpmm_ctx *c, int64_t *counts) {
     HIPCHK(c, launch_sort_by_bin(c->dbins, c->n, nbins, c->sb, c->stream));      // hist + scan -> bin_total
     HIPCHK(c, launch_copy_bytes(c->h_pin, c->sb.bin_total, sizeof(int32_t) * nbins, c->stream));
     HIPCHK(c, sync_stream(c, c->stream));
-    const int32_t *h = reinterpret_cast<const int32_t *>(c->h_pin);
+    const int32_t *h = reinterpret_cast<const int32_t *>(c->h_pin.get());
     for (int b = 0; b < nbins; ++b) counts[b] = h[b];
     return DPMM_OK;
 }
@@ -1872,7 +1813,7 @@ int dpmm_suffstats_host(dpmm_ctx *c, const int64_t *idx, int n_idx, const double
     if (int rc = run_stats(c, idx, n_idx)) return rc;
     HIPCHK(c, launch_copy_bytes(c->h_out, c->d_out, out_bytes, c->stream));
     HIPCHK(c, sync_stream(c, c->stream));
-    *packed = reinterpret_cast<const double *>(c->h_out);
+    *packed = reinterpret_cast<const double *>(c->h_out.get());
     return DPMM_OK;
 }
 
@@ -1891,7 +1832,7 @@ int dpmm_step_stats(dpmm_ctx *c, uint32_t reset_epoch, const double **packed, co
                        (!c->marg_req_outlier || c->mult_has_alpha1);
     const bool late = ahead && c->rows_on_demand;       // the caller reads the rows through dpmm_mult_master_rows_wait only: flags now, rows behind the draws
     c->rows_late = false;
-    if (late) { if (!flags_sent) HIPCHK(c, launch_copy_bytes(c->h_out + out_bytes, reinterpret_cast<const uint8_t *>(c->d_out) + out_bytes, (size_t)c->K + 1, c->stream)); }
+    if (late) { if (!flags_sent) HIPCHK(c, launch_copy_bytes(c->h_out + out_bytes, reinterpret_cast<const uint8_t *>(c->d_out.get()) + out_bytes, (size_t)c->K + 1, c->stream)); }
     else HIPCHK(c, launch_copy_bytes(c->h_out, c->d_out, out_bytes + (size_t)c->K + 1, c->stream));      // rows | flags
     if (int rc = flush_undo(c)) return rc;
     // Multinomial device master: the next Dirichlet draws + their hand-over images go out NOW, behind an event the host waits for instead of
@@ -1922,23 +1863,13 @@ int dpmm_step_stats(dpmm_ctx *c, uint32_t reset_epoch, const double **packed, co
     } else {
         HIPCHK(c, sync_stream(c, c->stream));
     }
-    *packed = reinterpret_cast<const double *>(c->h_out);
+    *packed = reinterpret_cast<const double *>(c->h_out.get());
     *bad = reinterpret_cast<const uint8_t *>(c->h_out + out_bytes);
     return DPMM_OK;
 }
 
 // ---- the master's dense maths on the device --------------------------------------------------------------------------------
-static int master_pinned(dpmm_ctx *c, size_t bytes) {
-    if (bytes <= c->h_master_bytes) return DPMM_OK;
-    HIPCHK(c, sync_stream(c, c->stream));
-    if (c->h_master) hipHostFree(c->h_master);
-    c->h_master = nullptr; c->h_master_bytes = 0;
-    size_t cap = 1 << 16;
-    while (cap < bytes) cap *= 2;
-    HIPCHK(c, hipHostMalloc((void **)&c->h_master, cap, hipHostMallocDefault));
-    c->h_master_bytes = cap;
-    return DPMM_OK;
-}
+static inline int master_pinned(dpmm_ctx *c, size_t bytes) { return grow(c, c->h_master, bytes, "dpmm_niw_master", "pinned block of the device master", (size_t)1 << 16); }
 // the main stream waits for draws launched ahead on stream2 (before anything that writes what they read or reads what they write)
 static int spec_join(dpmm_ctx *c) {
     if (c->spec_inflight) {
@@ -1983,17 +1914,9 @@ static int device_list(dpmm_ctx *c, int32_t *dst, std::vector<int32_t> &shadow, 
     shadow.assign(data, data + n);
     if (n == 0) return DPMM_OK;
     const size_t bytes = sizeof(int32_t) * n;
-    int32_t *&slot = c->h_list[c->h_list_next];
-    size_t &cap = c->h_list_cap[c->h_list_next];
+    PinBuf<int32_t> &slot = c->h_list[c->h_list_next];
     c->h_list_next = (c->h_list_next + 1) % 4;
-    if (bytes > cap) {
-        if (slot) HIPCHK(c, hipHostFree(slot));
-        slot = nullptr; cap = 0;
-        size_t nc = 4096;
-        while (nc < bytes) nc *= 2;
-        HIPCHK(c, hipHostMalloc((void **)&slot, nc, hipHostMallocDefault));
-        cap = nc;
-    }
+    if (bytes > slot.bytes) if (int rc = regrow(c, slot, bytes, "device master", "pinned staging of an index list", 4096)) return rc;      // (no wait: see above)
     memcpy(slot, data, bytes);
     HIPCHK(c, launch_copy_bytes(dst, slot, bytes, st ? st : c->stream));
     return DPMM_OK;
@@ -2008,12 +1931,12 @@ static int master_capacity(dpmm_ctx *c, int slots, int K) {
         HIPCHK(c, sync_stream(c, c->stream));
         if (c->stream2) HIPCHK(c, hipStreamSynchronize(c->stream2));
         c->spec_valid = false; c->noise_valid = false; c->apairs_valid = false;
-        double *fac = nullptr, *mean = nullptr, *kap = nullptr, *nu = nullptr, *rows = nullptr;
-        HIPCHK(c, hipMalloc(&fac, sizeof(double) * 3 * ns * DP * DP));
-        HIPCHK(c, hipMalloc(&mean, sizeof(double) * 3 * ns * DP));
-        HIPCHK(c, hipMalloc(&kap, sizeof(double) * 3 * ns));
-        HIPCHK(c, hipMalloc(&nu, sizeof(double) * 3 * ns));
-        HIPCHK(c, hipMalloc(&rows, sizeof(double) * 2 * ns * stride));
+        DevBuf<double> fac, mean, kap, nu, rows;      // beside the old ones, whose contents they take over
+        HIPCHK(c, fac.alloc(sizeof(double) * 3 * ns * DP * DP));
+        HIPCHK(c, mean.alloc(sizeof(double) * 3 * ns * DP));
+        HIPCHK(c, kap.alloc(sizeof(double) * 3 * ns));
+        HIPCHK(c, nu.alloc(sizeof(double) * 3 * ns));
+        HIPCHK(c, rows.alloc(sizeof(double) * 2 * ns * stride));
         if (c->master_slots > 0) {
             const size_t os = (size_t)c->master_slots;
             HIPCHK(c, hipMemcpy(fac, c->ma.fac, sizeof(double) * 3 * os * DP * DP, hipMemcpyDeviceToDevice));
@@ -2022,8 +1945,9 @@ static int master_capacity(dpmm_ctx *c, int slots, int K) {
             HIPCHK(c, hipMemcpy(nu, c->ma.nu, sizeof(double) * 3 * os, hipMemcpyDeviceToDevice));
             HIPCHK(c, hipMemcpy(rows, c->ma.rows_store, sizeof(double) * 2 * os * stride, hipMemcpyDeviceToDevice));
         }
-        hipFree(c->ma.fac); hipFree(c->ma.mean); hipFree(c->ma.kap); hipFree(c->ma.nu); hipFree(c->ma.rows_store);
-        c->ma.fac = fac; c->ma.mean = mean; c->ma.kap = kap; c->ma.nu = nu; c->ma.rows_store = rows;
+        auto &m = c->master_mem;
+        m.fac = std::move(fac); m.mean = std::move(mean); m.kap = std::move(kap); m.nu = std::move(nu); m.rows_store = std::move(rows);
+        c->ma.fac = m.fac; c->ma.mean = m.mean; c->ma.kap = m.kap; c->ma.nu = m.nu; c->ma.rows_store = m.rows_store;
         c->master_slots = ns;
     }
     if (K > c->master_K) {
@@ -2034,11 +1958,9 @@ static int master_capacity(dpmm_ctx *c, int slots, int K) {
         if (c->stream2) HIPCHK(c, hipStreamSynchronize(c->stream2));
         c->spec_valid = false; c->noise_valid = false; c->apairs_valid = false;
         for (int i = 0; i < 2; ++i) {
-            hipFree(c->d_Y[i]); hipFree(c->d_ld_sigma[i]); hipFree(c->d_mu_draw[i]);
-            c->d_Y[i] = nullptr; c->d_ld_sigma[i] = nullptr; c->d_mu_draw[i] = nullptr;
-            HIPCHK(c, hipMalloc(&c->d_Y[i], sizeof(double) * 3 * nk * DP * DP));
-            HIPCHK(c, hipMalloc(&c->d_ld_sigma[i], sizeof(float) * 3 * nk));
-            HIPCHK(c, hipMalloc(&c->d_mu_draw[i], sizeof(float) * 3 * nk * DP));
+            HIPCHK(c, c->d_Y[i].alloc(sizeof(double) * 3 * nk * DP * DP));
+            HIPCHK(c, c->d_ld_sigma[i].alloc(sizeof(float) * 3 * nk));
+            HIPCHK(c, c->d_mu_draw[i].alloc(sizeof(float) * 3 * nk * DP));
         }
         c->draws_on_device = false;
         c->master_K = nk;
@@ -2057,21 +1979,21 @@ int dpmm_niw_master_setup(dpmm_ctx *c, double kappa, double nu, const double *m,
     for (int a = 0; a < D; ++a)
         for (int b = 0; b <= a; ++b) lo[(size_t)a * (a + 1) / 2 + b] = 0.5 * (psi[(size_t)a * D + b] + psi[(size_t)b * D + a]);
     HIPCHK(c, sync_stream(c, c->stream));
-    if (!c->d_m0) HIPCHK(c, hipMalloc(&c->d_m0, sizeof(double) * D));
-    if (!c->d_psi_lo) HIPCHK(c, hipMalloc(&c->d_psi_lo, sizeof(double) * T));
+    if (!c->d_m0) HIPCHK(c, c->d_m0.alloc(sizeof(double) * D));
+    if (!c->d_psi_lo) HIPCHK(c, c->d_psi_lo.alloc(sizeof(double) * T));
     HIPCHK(c, hipMemcpy(c->d_m0, m, sizeof(double) * D, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(c->d_psi_lo, lo.data(), sizeof(double) * T, hipMemcpyHostToDevice));
     c->ma.D = D; c->ma.DP = 16 * ((D + 15) / 16); c->ma.packed_stride = c->packed_stride;
     c->ma.kappa0 = kappa; c->ma.nu0 = nu; c->ma.m0 = c->d_m0; c->ma.psi_lo = c->d_psi_lo; c->ma.seed = c->seed;
-    if (!c->h_draw) HIPCHK(c, hipHostMalloc((void **)&c->h_draw, sizeof(float) * 3 * DPMM_MAX_CLUSTERS, hipHostMallocDefault));
+    if (!c->h_draw) HIPCHK(c, c->h_draw.alloc(sizeof(float) * 3 * DPMM_MAX_CLUSTERS));
     if (!c->stream2) {
         HIPCHK(c, hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));
         HIPCHK(c, hipEventCreateWithFlags(&c->ev_master, hipEventDisableTiming));
         HIPCHK(c, hipEventCreateWithFlags(&c->ev_spec, hipEventDisableTiming));
         HIPCHK(c, hipEventCreateWithFlags(&c->ev_noise, hipEventDisableTiming));
         HIPCHK(c, hipEventCreateWithFlags(&c->ev_pairs, hipEventDisableTiming));
-        HIPCHK(c, hipMalloc(&c->d_jobs, sizeof(int32_t) * 2 * DPMM_MAX_CLUSTERS));
-        HIPCHK(c, hipMalloc(&c->d_dslots, sizeof(int32_t) * DPMM_MAX_CLUSTERS));
+        HIPCHK(c, c->d_jobs.alloc(sizeof(int32_t) * 2 * DPMM_MAX_CLUSTERS));
+        HIPCHK(c, c->d_dslots.alloc(sizeof(int32_t) * DPMM_MAX_CLUSTERS));
     }
     HIPCHK(c, hipStreamSynchronize(c->stream2));
     c->spec_inflight = false; c->spec_valid = false; c->noise_inflight = false; c->noise_valid = false; c->noise_pending = false;
@@ -2086,10 +2008,10 @@ int dpmm_step_stats_device(dpmm_ctx *c, uint32_t reset_epoch, const uint8_t **ba
     const size_t out_bytes = sizeof(double) * 2 * (size_t)std::max(c->K, 1) * (size_t)c->packed_stride;
     if (int rc = ensure_out(c, DPMM_MAX_CLUSTERS + 64)) return rc;
     if (int rc = run_stats(c, nullptr, 0, true, reset_epoch)) return rc;
-    HIPCHK(c, launch_copy_bytes(c->h_out, reinterpret_cast<const uint8_t *>(c->d_out) + out_bytes, (size_t)c->K + 1, c->stream));
+    HIPCHK(c, launch_copy_bytes(c->h_out, reinterpret_cast<const uint8_t *>(c->d_out.get()) + out_bytes, (size_t)c->K + 1, c->stream));
     if (int rc = flush_undo(c)) return rc;
     HIPCHK(c, sync_stream(c, c->stream));
-    *bad = reinterpret_cast<const uint8_t *>(c->h_out);
+    *bad = reinterpret_cast<const uint8_t *>(c->h_out.get());
     return DPMM_OK;
 }
 
@@ -2188,22 +2110,18 @@ int dpmm_step_master_device(dpmm_ctx *c, uint32_t reset_epoch, const int32_t *sl
         if ((size_t)napairs > c->apairs_cap) {
             HIPCHK(c, sync_stream(c, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream2));
-            size_t cap = 64;
-            while (cap < (size_t)napairs) cap *= 2;
-            hipFree(c->d_apairs); c->d_apairs = nullptr;
-            if (c->h_apairs) hipHostFree(c->h_apairs);
-            c->h_apairs = nullptr; c->apairs_cap = 0; c->apairs_shadow.clear();
-            HIPCHK(c, hipMalloc(&c->d_apairs, sizeof(int32_t) * 2 * cap));
-            HIPCHK(c, hipHostMalloc((void **)&c->h_apairs, sizeof(double) * DPMM_MASTER_NSCALARS * cap, hipHostMallocDefault));
+            const size_t cap = grow_capacity((size_t)napairs, 64);
+            c->apairs_cap = 0; c->apairs_shadow.clear();
+            HIPCHK(c, c->d_apairs.alloc(sizeof(int32_t) * 2 * cap));
+            HIPCHK(c, c->h_apairs.alloc(sizeof(double) * DPMM_MASTER_NSCALARS * cap));
             c->apairs_cap = cap;
         }
         if (c->ma.DP > 128 && (size_t)napairs > c->pair_cap) {      // scratch matrices of the large-D pair kernels
             HIPCHK(c, sync_stream(c, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream2));
-            hipFree(c->d_pairs); c->d_pairs = nullptr; c->pair_cap = 0;
-            size_t cap = 64;
-            while (cap < (size_t)napairs) cap *= 2;
-            HIPCHK(c, hipMalloc(&c->d_pairs, sizeof(double) * cap * (size_t)c->ma.DP * (size_t)c->ma.DP));
+            const size_t cap = grow_capacity((size_t)napairs, 64);
+            c->pair_cap = 0;
+            HIPCHK(c, c->d_pairs.alloc(sizeof(double) * cap * (size_t)c->ma.DP * (size_t)c->ma.DP));
             c->pair_cap = cap;
         }
         // (on the second stream, where the pair job runs: the list changes with the merge gates, and a copy on the main stream would sit
@@ -2225,17 +2143,10 @@ int dpmm_step_master_device(dpmm_ctx *c, uint32_t reset_epoch, const int32_t *sl
                     if (!(c->apairs_shadow.size() == kp.size() && memcmp(c->apairs_shadow.data(), kp.data(), sizeof(int32_t) * kp.size()) == 0) || !c->apairs_pinned_cur) {
                         c->apairs_shadow.assign(kp.begin(), kp.end());
                         c->apairs_pin_flip ^= 1;
-                        int32_t *&buf = c->h_apairs_list[c->apairs_pin_flip];
-                        size_t &cap = c->h_apairs_list_cap[c->apairs_pin_flip];
-                        if (kp.size() > cap) {
-                            if (buf) HIPCHK(c, hipHostFree(buf));
-                            buf = nullptr; cap = 0;
-                            size_t nc = 2048;
-                            while (nc < kp.size()) nc *= 2;
-                            HIPCHK(c, hipHostMalloc((void **)&buf, sizeof(int32_t) * nc, hipHostMallocDefault));
-                            cap = nc;
-                        }
-                        memcpy(buf, kp.data(), sizeof(int32_t) * kp.size());
+                        PinBuf<int32_t> &buf = c->h_apairs_list[c->apairs_pin_flip];
+                        const size_t need = sizeof(int32_t) * kp.size();
+                        if (need > buf.bytes) if (int rc = regrow(c, buf, need, "dpmm_step_master_device", "pinned list of the fused pair jobs", sizeof(int32_t) * 2048)) return rc;      // (no wait: see above)
+                        memcpy(buf, kp.data(), need);
                         c->apairs_pinned_cur = buf;
                     }
                 } else {
@@ -2256,8 +2167,8 @@ int dpmm_step_master_device(dpmm_ctx *c, uint32_t reset_epoch, const int32_t *sl
     master_mark_records(sm, 3 * (int64_t)K);
     const bool poll = c->opt_master_poll != 0;
     bool flags_sent = false;
-    if (int rc = run_stats(c, nullptr, 0, true, reset_epoch, reinterpret_cast<uint8_t *>(c->h_out), &flags_sent)) return rc;
-    if (!flags_sent) HIPCHK(c, launch_copy_bytes(c->h_out, reinterpret_cast<const uint8_t *>(c->d_out) + out_bytes, (size_t)K + 1, c->stream));
+    if (int rc = run_stats(c, nullptr, 0, true, reset_epoch, reinterpret_cast<uint8_t *>(c->h_out.get()), &flags_sent)) return rc;
+    if (!flags_sent) HIPCHK(c, launch_copy_bytes(c->h_out, reinterpret_cast<const uint8_t *>(c->d_out.get()) + out_bytes, (size_t)K + 1, c->stream));
     // DPMM_OPT_CHAIN_FUSION bit 16 (D <= 128, draws launched ahead): the normals of those draws are generated by extra workgroups of the
     // posteriors' launch (niw_post_both_kernel) -- no kernel beside the sweep on the second stream, no cross-stream wait in front of the draws
     const bool noise_in_post = draw_epoch != 0 && (c->opt_chain & 16) != 0 && niw_master_can_fuse_pairs(c->ma);
@@ -2328,7 +2239,7 @@ int dpmm_step_master_device(dpmm_ctx *c, uint32_t reset_epoch, const int32_t *sl
         }
     }
     c->handover_inflight = false;          // (recorded behind the last hand-over kernel on the same stream)
-    *bad = reinterpret_cast<const uint8_t *>(c->h_out);
+    *bad = reinterpret_cast<const uint8_t *>(c->h_out.get());
     *small = sm;
     return DPMM_OK;
 }
@@ -2385,7 +2296,7 @@ int dpmm_niw_master_draw(dpmm_ctx *c, uint32_t epoch, int K, const int32_t *slot
     // synchronise here would wait out: 27 us on the host's critical path at D = 64)
     if (c->handover_inflight) HIPCHK(c, sync_stream(c, c->stream));
     c->handover_inflight = true;
-    float *hlr = reinterpret_cast<float *>(c->h_draw), *hw = hlr + 2 * K;
+    float *hlr = reinterpret_cast<float *>(c->h_draw.get()), *hw = hlr + 2 * K;
     memcpy(hlr, lr, sizeof(float) * 2 * K);
     memcpy(hw, w, sizeof(float) * K);
     c->have_tail = c->opt_tail && c->D >= 4 && c->D % 4 == 0 && K > 1;
@@ -2453,7 +2364,7 @@ int dpmm_niw_master_pairs(dpmm_ctx *c, const int32_t *slots_i, const int32_t *sl
         if (all) {
             if (int rc = master_pinned(c, sizeof(double) * DPMM_MASTER_NSCALARS * (size_t)n)) return rc;
             HIPCHK(c, hipEventSynchronize(c->ev_pairs));
-            double *sm = reinterpret_cast<double *>(c->h_master);      // (free: every user waits for its kernels before it returns)
+            double *sm = reinterpret_cast<double *>(c->h_master.get());      // (free: every user waits for its kernels before it returns)
             for (int i = 0; i < n; ++i) memcpy(sm + (size_t)i * DPMM_MASTER_NSCALARS, c->h_apairs + (size_t)rec[i] * DPMM_MASTER_NSCALARS, sizeof(double) * DPMM_MASTER_NSCALARS);
             *small = sm;
             return DPMM_OK;
@@ -2463,16 +2374,15 @@ int dpmm_niw_master_pairs(dpmm_ctx *c, const int32_t *slots_i, const int32_t *sl
     if ((size_t)n > c->pair_cap) {
         HIPCHK(c, sync_stream(c, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream2));
-        hipFree(c->d_pairs); c->d_pairs = nullptr; c->pair_cap = 0;
-        size_t cap = 64;
-        while (cap < (size_t)n) cap *= 2;
-        HIPCHK(c, hipMalloc(&c->d_pairs, sizeof(double) * cap * DP * DP));
+        const size_t cap = grow_capacity((size_t)n, 64);
+        c->pair_cap = 0;
+        HIPCHK(c, c->d_pairs.alloc(sizeof(double) * cap * DP * DP));
         c->pair_cap = cap;
     }
     const size_t idx_bytes = (sizeof(int32_t) * 2 * (size_t)n + 63) & ~(size_t)63;
     if (int rc = master_pinned(c, idx_bytes + sizeof(double) * DPMM_MASTER_NSCALARS * (size_t)n)) return rc;
     HIPCHK(c, sync_stream(c, c->stream));
-    int32_t *pr = reinterpret_cast<int32_t *>(c->h_master);
+    int32_t *pr = reinterpret_cast<int32_t *>(c->h_master.get());
     for (int i = 0; i < n; ++i) { pr[2 * i] = slots_i[i]; pr[2 * i + 1] = slots_j[i]; }
     double *sm = reinterpret_cast<double *>(c->h_master + idx_bytes);
     HIPCHK(c, launch_niw_master_pairs(c->ma, pr, n, c->d_pairs, sm, c->stream));
@@ -2508,8 +2418,8 @@ int dpmm_niw_master_rows(dpmm_ctx *c, const int32_t *slots, int n, double *out) 
     if (int rc = ensure_pinned(c, sizeof(int32_t) * (size_t)n + 64)) return rc;
     HIPCHK(c, sync_stream(c, c->stream));
     memcpy(c->h_pin, slots, sizeof(int32_t) * (size_t)n);
-    HIPCHK(c, launch_niw_rows_gather(c->ma.rows_store, reinterpret_cast<const int32_t *>(c->h_pin), n, (int64_t)stride,
-                                     reinterpret_cast<double *>(c->h_out), c->stream));
+    HIPCHK(c, launch_niw_rows_gather(c->ma.rows_store, reinterpret_cast<const int32_t *>(c->h_pin.get()), n, (int64_t)stride,
+                                     reinterpret_cast<double *>(c->h_out.get()), c->stream));
     HIPCHK(c, sync_stream(c, c->stream));
     memcpy(out, c->h_out, bytes);
     return DPMM_OK;
@@ -2541,7 +2451,7 @@ int dpmm_mult_master_setup(dpmm_ctx *c, const float *alpha, const float *alpha_o
     if (c->D > DPMM_MULT_MASTER_MAXD) return fail(c, DPMM_ELIMIT, "D exceeds the device Dirichlet draw's limit");
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, sync_stream(c, c->stream));
-    if (!c->d_malpha) HIPCHK(c, hipMalloc(&c->d_malpha, sizeof(float) * 2 * (size_t)c->ldx));
+    if (!c->d_malpha) HIPCHK(c, c->d_malpha.alloc(sizeof(float) * 2 * (size_t)c->ldx));
     HIPCHK(c, hipMemsetAsync(c->d_malpha, 0, sizeof(float) * 2 * (size_t)c->ldx, c->stream));
     HIPCHK(c, sync_stream(c, c->stream));
     HIPCHK(c, hipMemcpy(c->d_malpha, alpha, sizeof(float) * (size_t)c->D, hipMemcpyHostToDevice));
@@ -2553,10 +2463,10 @@ int dpmm_mult_master_setup(dpmm_ctx *c, const float *alpha, const float *alpha_o
         if (al) for (int d = 0; d < c->D; ++d) { sa += (double)al[d]; sl += lgamma((double)al[d]); }
         c->mult_prior_c[2 * p] = sa; c->mult_prior_c[2 * p + 1] = sl;
     }
-    if (!c->d_mpairs) HIPCHK(c, hipMalloc(&c->d_mpairs, sizeof(int32_t) * 2 * DPMM_MULT_MASTER_MAXPAIRS));
-    if (!c->h_marg) HIPCHK(c, hipHostMalloc((void **)&c->h_marg, sizeof(double) * (6 * DPMM_MAX_CLUSTERS + DPMM_MULT_MASTER_MAXPAIRS), hipHostMallocDefault));
+    if (!c->d_mpairs) HIPCHK(c, c->d_mpairs.alloc(sizeof(int32_t) * 2 * DPMM_MULT_MASTER_MAXPAIRS));
+    if (!c->h_marg) HIPCHK(c, c->h_marg.alloc(sizeof(double) * (6 * DPMM_MAX_CLUSTERS + DPMM_MULT_MASTER_MAXPAIRS)));
     c->marg_valid = false; c->marg_req = false; c->mpairs_shadow.clear();
-    if (!c->h_draw) HIPCHK(c, hipHostMalloc((void **)&c->h_draw, sizeof(float) * 3 * DPMM_MAX_CLUSTERS, hipHostMallocDefault));
+    if (!c->h_draw) HIPCHK(c, c->h_draw.alloc(sizeof(float) * 3 * DPMM_MAX_CLUSTERS));
     c->mult_master = true;
     return DPMM_OK;
 }
@@ -2589,7 +2499,7 @@ int dpmm_mult_master_draw(dpmm_ctx *c, uint32_t epoch, int K, int outlier_first,
     // it -- known from the host's waits since, not by waiting for the stream here: the stream may be carrying the draws launched ahead and the late
     // rows, and waiting for those would put them back on the host's path
     if (c->cst_inflight && c->cst_gen == c->sync_gen) HIPCHK(c, sync_stream(c, c->stream));     // (never in the engine's loop: dpmm_step_stats waited in between)
-    float *hcst = reinterpret_cast<float *>(c->h_draw);
+    float *hcst = reinterpret_cast<float *>(c->h_draw.get());
     for (int k = 0; k < K; ++k) { hcst[3 * k] = logf(w[k]); hcst[3 * k + 1] = logf(lr[2 * k]); hcst[3 * k + 2] = logf(lr[2 * k + 1]); }
     HIPCHK(c, launch_copy_bytes(c->d_cst, hcst, sizeof(float) * 3 * K, c->stream));
     c->cst_inflight = true; c->cst_gen = c->sync_gen;
@@ -2699,19 +2609,18 @@ int dpmm_debug_niw_draw_inputs(dpmm_ctx *c, uint32_t epoch, int K, const int32_t
     for (int k = 0; k < K; ++k)
         if (slot_of_cluster[k] < 0 || slot_of_cluster[k] >= c->master_slots) return fail(c, DPMM_EINVAL, "slot without a posterior on the device");
     const size_t D = (size_t)c->D, nA = 3 * (size_t)K * D * D, nx = 3 * (size_t)K * D;
-    double *dA = nullptr, *dxi = nullptr;
-    int32_t *dsl = nullptr;
+    DevBuf<double> dA, dxi;
+    DevBuf<int32_t> dsl;
     HIPCHK(c, sync_stream(c, c->stream));
-    hipError_t e = hipMalloc(&dA, sizeof(double) * nA);
-    if (e == hipSuccess) e = hipMalloc(&dxi, sizeof(double) * nx);
-    if (e == hipSuccess) e = hipMalloc(&dsl, sizeof(int32_t) * K);
+    hipError_t e = dA.alloc(sizeof(double) * nA);
+    if (e == hipSuccess) e = dxi.alloc(sizeof(double) * nx);
+    if (e == hipSuccess) e = dsl.alloc(sizeof(int32_t) * K);
     if (e == hipSuccess) e = hipMemsetAsync(dA, 0, sizeof(double) * nA, c->stream);
     if (e == hipSuccess) e = hipMemcpy(dsl, slot_of_cluster, sizeof(int32_t) * K, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = launch_niw_draw_inputs(c->ma, dsl, K, epoch, dA, dxi, c->stream);
     if (e == hipSuccess) e = sync_stream(c, c->stream);
     if (e == hipSuccess) e = hipMemcpy(A, dA, sizeof(double) * nA, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(xi, dxi, sizeof(double) * nx, hipMemcpyDeviceToHost);
-    hipFree(dA); hipFree(dxi); hipFree(dsl);
     if (e != hipSuccess) { c->err = std::string("dpmm_debug_niw_draw_inputs: ") + hipGetErrorString(e); return DPMM_EHIP; }
     return DPMM_OK;
 }
@@ -2833,9 +2742,9 @@ int dpmm_reset_sublabels(dpmm_ctx *c, const int64_t *idx, int n, uint32_t epoch)
 static int smart_buffers(dpmm_ctx *c) {
     if (c->d_proj) return DPMM_OK;
     const size_t n = (size_t)std::max<int64_t>(c->n, 1);
-    HIPCHK(c, hipMalloc(&c->d_proj, sizeof(double) * n));
-    HIPCHK(c, hipMalloc(&c->d_vals, sizeof(double) * n));
-    HIPCHK(c, hipMalloc(&c->d_smart, sizeof(double) * (4 * (size_t)smart_groups() + 8 + 2 * (size_t)c->D)));
+    HIPCHK(c, c->d_proj.alloc(sizeof(double) * n));
+    HIPCHK(c, c->d_vals.alloc(sizeof(double) * n));
+    HIPCHK(c, c->d_smart.alloc(sizeof(double) * (4 * (size_t)smart_groups() + 8 + 2 * (size_t)c->D)));
     return DPMM_OK;
 }
 static int smart_check(dpmm_ctx *c, int64_t cluster) {
@@ -2892,16 +2801,14 @@ int dpmm_set_ground_truth(dpmm_ctx *c, const int64_t *gt, int n_gt) {
     if (!c) return DPMM_EINVAL;
     if ((!gt && c->n > 0) || n_gt < 1 || n_gt > 65536) return fail(c, DPMM_EINVAL, "bad ground truth");
     HIPCHK(c, hipSetDevice(c->device));
-    if (!c->d_gt) HIPCHK(c, hipMalloc(&c->d_gt, sizeof(int32_t) * (size_t)std::max<int64_t>(c->n, 1)));
-    if (c->d_cont) { hipFree(c->d_cont); c->d_cont = nullptr; }
-    HIPCHK(c, hipMalloc(&c->d_cont, sizeof(unsigned long long) * (size_t)DPMM_MAX_CLUSTERS * n_gt));
+    if (!c->d_gt) HIPCHK(c, c->d_gt.alloc(sizeof(int32_t) * (size_t)std::max<int64_t>(c->n, 1)));
+    HIPCHK(c, c->d_cont.alloc(sizeof(unsigned long long) * (size_t)DPMM_MAX_CLUSTERS * n_gt));
     if (c->n > 0) {
-        int64_t *tmp = nullptr;
-        HIPCHK(c, hipMalloc(&tmp, sizeof(int64_t) * (size_t)c->n));
+        DevBuf<int64_t> tmp;
+        HIPCHK(c, tmp.alloc(sizeof(int64_t) * (size_t)c->n));
         hipError_t e = hipMemcpyAsync(tmp, gt, sizeof(int64_t) * c->n, hipMemcpyHostToDevice, c->stream);
         if (e == hipSuccess) e = launch_i64_to_i32(c->d_gt, tmp, c->n, c->stream);
         if (e == hipSuccess) e = sync_stream(c, c->stream);
-        hipFree(tmp);
         if (e != hipSuccess) { c->err = std::string("dpmm_set_ground_truth: ") + hipGetErrorString(e); return DPMM_EHIP; }
     }
     c->n_gt = n_gt;
@@ -2988,12 +2895,12 @@ int dpmm_set_option(dpmm_ctx *c, int option, double value) {
                 HIPCHK(c, sync_stream(c, c->stream));
                 const int nt = (int)((c->n + t - 1) / t);
                 const size_t nbmax = 2 * DPMM_MAX_CLUSTERS;
-                int32_t *th = nullptr, *tc = nullptr, *tsp = nullptr;
-                HIPCHK(c, hipMalloc(&th, sizeof(int32_t) * nbmax * (size_t)std::max(1, nt)));
-                if (hipMalloc(&tc, sizeof(int32_t) * nbmax * (size_t)std::max(1, nt)) != hipSuccess) { hipFree(th); return fail(c, DPMM_EHIP, "DPMM_OPT_SORT_TILE: out of device memory for the 512-point tile tables"); }
-                if (hipMalloc(&tsp, sizeof(int32_t) * (size_t)STEP_SPEC_MAX_BINS * (size_t)std::max(1, nt)) != hipSuccess) { hipFree(th); hipFree(tc); return fail(c, DPMM_EHIP, "DPMM_OPT_SORT_TILE: out of device memory for the 512-point tile tables"); }
-                hipFree(c->sb.tile_hist); hipFree(c->sb.tile_cnt); hipFree(c->sb.tile_spec);
-                c->sb.tile_hist = th; c->sb.tile_cnt = tc; c->sb.tile_spec = tsp;
+                DevBuf<int32_t> th, tc, tsp;      // all three, then the old ones go
+                if (th.alloc(sizeof(int32_t) * nbmax * (size_t)std::max(1, nt)) != hipSuccess || tc.alloc(sizeof(int32_t) * nbmax * (size_t)std::max(1, nt)) != hipSuccess ||
+                    tsp.alloc(sizeof(int32_t) * (size_t)STEP_SPEC_MAX_BINS * (size_t)std::max(1, nt)) != hipSuccess)
+                    return fail(c, DPMM_EHIP, "DPMM_OPT_SORT_TILE: out of device memory for the 512-point tile tables");
+                c->sort_mem.tile_hist = std::move(th); c->sort_mem.tile_cnt = std::move(tc); c->sort_mem.tile_spec = std::move(tsp);
+                sort_view(c);
                 c->nt_sort = nt; c->sort_tile_min = t;
             }
             c->sb.tile = t; return DPMM_OK;          // (the tile tables are rebuilt by every pass; perm stays a valid order)
@@ -3139,8 +3046,8 @@ int dpmm_comm_allgather_host(dpmm_ctx *c, const void *mine, int64_t bytes, void 
         return DPMM_OK;
     }
     if (int rc = ensure_pinned(c, nb + tot)) return rc;
-    char *dbuf = nullptr;
-    HIPCHK(c, hipMalloc(&dbuf, tot));
+    DevBuf<char> dbuf;
+    HIPCHK(c, dbuf.alloc(tot));
     HIPCHK(c, sync_stream(c, c->stream));
     memcpy(c->h_pin, mine, (size_t)bytes);
     hipError_t e = launch_copy_bytes(dbuf + nb * (size_t)c->rank, c->h_pin, nb, c->stream);
@@ -3152,7 +3059,6 @@ int dpmm_comm_allgather_host(dpmm_ctx *c, const void *mine, int64_t bytes, void 
     }
     if (rc == DPMM_OK && e == hipSuccess) e = launch_copy_bytes(c->h_pin + nb, dbuf, tot, c->stream);
     if (e == hipSuccess) e = sync_stream(c, c->stream);
-    hipFree(dbuf);
     if (e != hipSuccess) { c->err = std::string("dpmm_comm_allgather_host: ") + hipGetErrorString(e); return DPMM_EHIP; }
     if (rc != DPMM_OK) return rc;
     for (int rk = 0; rk < c->world; ++rk) memcpy((char *)all + (size_t)rk * (size_t)bytes, c->h_pin + nb + nb * (size_t)rk, (size_t)bytes);
@@ -3173,26 +3079,24 @@ int dpmm_debug_subloglik(dpmm_ctx *c, float *out) {
         // the sweeps' sub-label phase runs the three-plane bf16 evaluation (niw_lean.hip): the same device functions, for every point and cluster
         NiwSweepArgs a{};
         a.X = c->dX; a.ldx = c->ldx; a.n = c->n; a.K = K; a.mup = c->d_mup; a.cst = c->d_cst; a.tail = c->d_tail;
-        float *tab = nullptr;
-        hipError_t e = hipMalloc(&tab, sizeof(float) * (size_t)K2 * (size_t)c->n);
+        DevBuf<float> tab;
+        hipError_t e = tab.alloc(sizeof(float) * (size_t)K2 * (size_t)c->n);
         if (e == hipSuccess) e = launch_niw_b3_debug(a, tab, c->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(out, tab, sizeof(float) * (size_t)K2 * (size_t)c->n, hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = sync_stream(c, c->stream);
-        hipFree(tab);
         if (e != hipSuccess) { c->err = std::string("dpmm_debug_subloglik: ") + hipGetErrorString(e); return DPMM_EHIP; }
         return DPMM_OK;
     }
     if (c->prior == DPMM_PRIOR_MULT && c->x_sparse) {
         // the sparse sweep's table mode evaluates all 3K rows with the arithmetic of its sub-label phase: rows 3k + 1 + s are the answer
         const int64_t stride = c->ntiles * c->tile;
-        float *table = nullptr;
-        HIPCHK(c, hipMalloc(&table, sizeof(float) * (size_t)(3 * K) * (size_t)stride));
+        DevBuf<float> table;
+        HIPCHK(c, table.alloc(sizeof(float) * (size_t)(3 * K) * (size_t)stride));
         int rc = run_sweep(c, 0, 0, table, stride);
         hipError_t e = hipSuccess;
         for (int j = 0; j < K2 && rc == DPMM_OK && e == hipSuccess; ++j)
             e = hipMemcpyAsync(out + (size_t)j * c->n, table + (size_t)(3 * (j / 2) + 1 + (j % 2)) * stride, sizeof(float) * (size_t)c->n, hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = sync_stream(c, c->stream);
-        hipFree(table);
         if (e != hipSuccess) { c->err = std::string("dpmm_debug_subloglik: ") + hipGetErrorString(e); return DPMM_EHIP; }
         return rc;
     }
@@ -3201,33 +3105,33 @@ int dpmm_debug_subloglik(dpmm_ctx *c, float *out) {
     const bool niw = c->prior == DPMM_PRIOR_NIW;
     // temporary parameter images: row 3j of the temporary set <- row 3k+1+s of the live one (j = 2k+s)
     const size_t NP = niw ? (size_t)c->NB * (c->NB + 1) / 2 : 0, matsz = NP * 256, dp = niw ? (size_t)16 * c->NB : 0;
-    float *tRp = nullptr, *tmu = nullptr, *tcst = nullptr, *table = nullptr, *traw = nullptr;
-    uint32_t *tL16 = nullptr;
-    hipError_t e = hipMalloc(&tcst, sizeof(float) * 3 * K2);
-    if (e == hipSuccess) e = hipMalloc(&table, sizeof(float) * (size_t)(niw ? K2 : 3 * K2) * (size_t)stride);
+    // the temporary images change places with the live ones for the sweep below and change back behind it
+    DevBuf<float> tRp, tmu, tcst, table, traw;
+    DevBuf<uint32_t> tL16;
+    hipError_t e = tcst.alloc(sizeof(float) * 3 * K2);
+    if (e == hipSuccess) e = table.alloc(sizeof(float) * (size_t)(niw ? K2 : 3 * K2) * (size_t)stride);
     int rc = DPMM_OK;
-    float *sRp = c->d_Rp, *smu = c->d_mup, *scst = c->d_cst, *sraw = c->d_raw;
     const bool s_rp_current = c->rp_current;
-    uint32_t *sL16 = c->d_Lp16;
+    bool swapped = false;
     const int sK = c->K;
     const bool s_tail = c->have_tail, s_prep = c->have_screen_prep;
     if (e == hipSuccess && niw) {
-        e = hipMalloc(&tRp, sizeof(float) * 3 * K2 * matsz);
-        if (e == hipSuccess) e = hipMalloc(&tmu, sizeof(float) * 3 * K2 * dp);
+        e = tRp.alloc(sizeof(float) * 3 * K2 * matsz);
+        if (e == hipSuccess) e = tmu.alloc(sizeof(float) * 3 * K2 * dp);
         for (int j = 0; j < K2 && e == hipSuccess; ++j) {
             const int src = 3 * (j / 2) + 1 + (j % 2);
             e = hipMemcpyAsync(tRp + (size_t)(3 * j) * matsz, c->d_Rp + (size_t)src * matsz, sizeof(float) * matsz, hipMemcpyDeviceToDevice, c->stream);
             if (e == hipSuccess) e = hipMemcpyAsync(tmu + (size_t)(3 * j) * dp, c->d_mup + (size_t)src * dp, sizeof(float) * dp, hipMemcpyDeviceToDevice, c->stream);
             if (e == hipSuccess) e = hipMemcpyAsync(tcst + 3 * j, c->d_cst + src, sizeof(float), hipMemcpyDeviceToDevice, c->stream);
         }
-        if (e == hipSuccess) { c->d_Rp = tRp; c->d_mup = tmu; c->d_cst = tcst; }
+        if (e == hipSuccess) { c->d_Rp.swap(tRp); c->d_mup.swap(tmu); c->d_cst.swap(tcst); swapped = true; }
     } else if (e == hipSuccess) {
         // Multinomial: re-pack a raw row image with the sub-cluster rows in the cluster-level positions
-        e = hipMalloc(&traw, sizeof(float) * 3 * K2 * (size_t)c->ldx);
+        e = traw.alloc(sizeof(float) * 3 * K2 * (size_t)c->ldx);
         if (e == hipSuccess) e = hipMemsetAsync(traw, 0, sizeof(float) * 3 * K2 * (size_t)c->ldx, c->stream);
         const size_t NT = (size_t)(c->ldx + 15) / 16, NRB = (size_t)(3 * K2 + 15) / 16;
-        if (e == hipSuccess) e = hipMalloc(&tRp, sizeof(float) * NRB * NT * 256);
-        if (e == hipSuccess) e = hipMalloc(&tL16, sizeof(uint32_t) * std::max(mult_pack_bf16_words(3 * K2, c->ldx), mult_pack_u8_words(3 * K2, (c->D + 127) / 128 * 128)));
+        if (e == hipSuccess) e = tRp.alloc(sizeof(float) * NRB * NT * 256);
+        if (e == hipSuccess) e = tL16.alloc(sizeof(uint32_t) * std::max(mult_pack_bf16_words(3 * K2, c->ldx), mult_pack_u8_words(3 * K2, (c->D + 127) / 128 * 128)));
         if (e == hipSuccess) e = hipMemsetAsync(tcst, 0, sizeof(float) * 3 * K2, c->stream);
         for (int j = 0; j < K2 && e == hipSuccess; ++j) {
             const int src = 3 * (j / 2) + 1 + (j % 2);
@@ -3237,7 +3141,7 @@ int dpmm_debug_subloglik(dpmm_ctx *c, float *out) {
         if (e == hipSuccess) e = launch_mult_pack(traw, tRp, 3 * K2, c->ldx, c->stream);
         if (e == hipSuccess && c->x_u8) e = launch_mult_pack_u8(traw, tL16, 3 * K2, c->ldx, c->ld8, c->stream);
         else if (e == hipSuccess && c->x_bf16_exact) e = launch_mult_pack_bf16(traw, tL16, 3 * K2, c->ldx, c->stream);
-        if (e == hipSuccess) { c->d_Rp = tRp; c->d_cst = tcst; c->d_Lp16 = tL16; c->d_raw = traw; c->rp_current = true; }
+        if (e == hipSuccess) { c->d_Rp.swap(tRp); c->d_cst.swap(tcst); c->d_Lp16.swap(tL16); c->d_raw.swap(traw); c->rp_current = true; swapped = true; }
     }
     if (e == hipSuccess) {
         c->K = K2; c->have_tail = false; c->have_screen_prep = false;
@@ -3249,8 +3153,11 @@ int dpmm_debug_subloglik(dpmm_ctx *c, float *out) {
         }
     }
     hipStreamSynchronize(c->stream);
-    c->d_Rp = sRp; c->d_mup = smu; c->d_cst = scst; c->d_Lp16 = sL16; c->d_raw = sraw; c->rp_current = s_rp_current; c->K = sK; c->have_tail = s_tail; c->have_screen_prep = s_prep;
-    hipFree(tRp); hipFree(tmu); hipFree(tcst); hipFree(table); hipFree(traw); hipFree(tL16);
+    if (swapped) {
+        c->d_Rp.swap(tRp); c->d_cst.swap(tcst);
+        if (niw) c->d_mup.swap(tmu); else { c->d_Lp16.swap(tL16); c->d_raw.swap(traw); }
+    }
+    c->rp_current = s_rp_current; c->K = sK; c->have_tail = s_tail; c->have_screen_prep = s_prep;
     if (e != hipSuccess) { c->err = std::string("dpmm_debug_subloglik: ") + hipGetErrorString(e); return DPMM_EHIP; }
     return rc;
 }
@@ -3265,15 +3172,14 @@ int dpmm_debug_ref_bracket(dpmm_ctx *c, int64_t cluster, float c_override, float
     if (cluster < 1 || cluster > c->K) return fail(c, DPMM_EINVAL, "cluster index out of range");
     HIPCHK(c, hipSetDevice(c->device));
     if (c->n == 0) return DPMM_OK;
-    float *d = nullptr;
-    HIPCHK(c, hipMalloc(&d, sizeof(float) * 2 * (size_t)c->n));
+    DevBuf<float> d;
+    HIPCHK(c, d.alloc(sizeof(float) * 2 * (size_t)c->n));
     NiwSweepArgs a{};
     a.X = c->dX; a.ldx = c->ldx; a.n = c->n; a.K = c->K; a.Rp = c->d_Rp; a.mup = c->d_mup; a.tail = c->d_tail;
     hipError_t e = launch_niw_refb_debug(a, (int)cluster - 1, c_override, d, d + c->n, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(q_hi, d, sizeof(float) * (size_t)c->n, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(q, d + c->n, sizeof(float) * (size_t)c->n, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = sync_stream(c, c->stream);
-    hipFree(d);
     if (e != hipSuccess) { c->err = std::string("dpmm_debug_ref_bracket: ") + hipGetErrorString(e); return DPMM_EHIP; }
     return DPMM_OK;
 }
@@ -3299,9 +3205,9 @@ int dpmm_debug_bracket_big(dpmm_ctx *c, float *aref, uint32_t *tile_flags) {
     HIPCHK(c, hipSetDevice(c->device));
     if (c->n == 0) return DPMM_OK;
     const size_t nt = (size_t)((c->n + 127) / 128);
-    float *d = nullptr; uint32_t *f = nullptr;
-    HIPCHK(c, hipMalloc(&d, sizeof(float) * nt * 128));
-    if (hipMalloc(&f, sizeof(uint32_t) * nt) != hipSuccess) { hipFree(d); return fail(c, DPMM_EHIP, "hipMalloc"); }
+    DevBuf<float> d; DevBuf<uint32_t> f;
+    HIPCHK(c, d.alloc(sizeof(float) * nt * 128));
+    HIPCHK(c, f.alloc(sizeof(uint32_t) * nt));
     NiwSweepArgs a{};
     a.X = c->dX; a.ldx = c->ldx; a.n = c->n; a.K = c->K; a.mup = c->d_mup; a.cst = c->d_cst; a.bins = c->dbins;
     a.order = (c->have_perm && c->opt_ordered) ? c->sb.perm : nullptr; a.order_total = c->sb.perm_total;
@@ -3310,7 +3216,6 @@ int dpmm_debug_bracket_big(dpmm_ctx *c, float *aref, uint32_t *tile_flags) {
     if (e == hipSuccess) e = hipMemcpyAsync(aref, d, sizeof(float) * (size_t)c->n, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(tile_flags, f, sizeof(uint32_t) * nt, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = sync_stream(c, c->stream);
-    hipFree(d); hipFree(f);
     if (e != hipSuccess) { c->err = std::string("dpmm_debug_bracket_big: ") + hipGetErrorString(e); return DPMM_EHIP; }
     return DPMM_OK;
 }
@@ -3419,8 +3324,7 @@ int dpmm_set_projection(dpmm_ctx *c, int D_in, const double *W, const double *mu
     HIPCHK(c, hipSetDevice(c->device));
     if (D_in == 0) {
         HIPCHK(c, sync_stream(c, c->stream));
-        hipFree(c->d_proj_W); hipFree(c->d_proj_bias);
-        c->d_proj_W = nullptr; c->d_proj_bias = nullptr; c->proj_Din = 0;
+        c->d_proj_W.reset(); c->d_proj_bias.reset(); c->proj_Din = 0;
         return DPMM_OK;
     }
     if (!W) return fail(c, DPMM_EINVAL, std::string(fn) + ": W is null");
@@ -3432,16 +3336,15 @@ int dpmm_set_projection(dpmm_ctx *c, int D_in, const double *W, const double *mu
         if (bad == 2) return fail(c, DPMM_EINVAL, std::string(fn) + ": mu has a non-finite entry at [" + std::to_string(where) + "]");
         return fail(c, DPMM_EINVAL, std::string(fn) + ": mu' W overflows Float32 in column " + std::to_string(where));
     }
-    void *dW = nullptr;
-    float *db = nullptr;
-    hipError_t e = hipMalloc(&dW, img.size() * sizeof(uint16_t));
-    if (e == hipSuccess) e = hipMalloc(&db, bias.size() * sizeof(float));
+    DevBuf<void> dW;      // beside the projection in force, which stays when this fails
+    DevBuf<float> db;
+    hipError_t e = dW.alloc(img.size() * sizeof(uint16_t));
+    if (e == hipSuccess) e = db.alloc(bias.size() * sizeof(float));
     if (e == hipSuccess) e = hipMemcpyAsync(dW, img.data(), img.size() * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(db, bias.data(), bias.size() * sizeof(float), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = sync_stream(c, c->stream);
-    if (e != hipSuccess) { hipFree(dW); hipFree(db); return fail(c, DPMM_EHIP, std::string(fn) + ": " + hipGetErrorString(e)); }
-    hipFree(c->d_proj_W); hipFree(c->d_proj_bias);
-    c->d_proj_W = dW; c->d_proj_bias = db; c->proj_Din = D_in;
+    if (e != hipSuccess) return fail(c, DPMM_EHIP, std::string(fn) + ": " + hipGetErrorString(e));
+    c->d_proj_W = std::move(dW); c->d_proj_bias = std::move(db); c->proj_Din = D_in;
     return DPMM_OK;
 }
 
@@ -3490,12 +3393,7 @@ int dpmm_upload_points_projected(dpmm_ctx *c, const float *h_src, int64_t ld_src
         const size_t row_bytes = sizeof(float) * (size_t)c->proj_Din;
         const int64_t chunk_rows = std::max<int64_t>(1, std::min<int64_t>(c->n, (int64_t)(((size_t)64 << 20) / row_bytes)));
         const size_t need = row_bytes * (size_t)chunk_rows;
-        if (c->proj_stage_bytes < need) {
-            HIPCHK(c, sync_stream(c, c->stream));
-            hipFree(c->d_proj_stage); c->d_proj_stage = nullptr; c->proj_stage_bytes = 0;
-            HIPCHK(c, hipMalloc(&c->d_proj_stage, need));
-            c->proj_stage_bytes = need;
-        }
+        if (int rc = grow(c, c->d_proj_stage, need, fn, "staging rows")) return rc;
         for (int64_t r0 = 0; r0 < c->n; r0 += chunk_rows) {
             const int64_t nr = std::min(chunk_rows, c->n - r0);
             HIPCHK(c, hipMemcpy2DAsync(c->d_proj_stage, row_bytes, h_src + (size_t)r0 * (size_t)ld_src, sizeof(float) * (size_t)ld_src, row_bytes, (size_t)nr,
@@ -3535,18 +3433,18 @@ int dpmm_upload_points_csc_device(dpmm_ctx *c, const void *d_colptr, int index_d
         if (int rc = check_device_extent(c, fn, "d_nzval", d_nzval, (uint64_t)nnz_extent * vs, vs)) return rc;
     }
     // everything is built beside the points in force; they are replaced only when the new ones have passed the checks
-    int64_t *n_cp = nullptr, *t_bt = nullptr;
-    float *n_val = nullptr;
-    uint16_t *n_ri = nullptr;
-    int32_t *t_cnt = nullptr;
+    DevBuf<int64_t> n_cp, t_bt;
+    DevBuf<float> n_val;
+    DevBuf<uint16_t> n_ri;
+    DevBuf<int32_t> t_cnt;
     const int64_t ntiles = csc_scan_tiles(n);
     unsigned long long bad = ~0ull;
     int64_t kept = 0;
-    hipError_t e = hipMalloc(&n_cp, sizeof(int64_t) * ((size_t)n + 1));
+    hipError_t e = n_cp.alloc(sizeof(int64_t) * ((size_t)n + 1));
     if (e == hipSuccess && n > 0) {
         unsigned long long *t_bad = nullptr;
-        e = hipMalloc(&t_cnt, sizeof(int32_t) * (size_t)n);
-        if (e == hipSuccess) e = hipMalloc(&t_bt, sizeof(int64_t) * ((size_t)ntiles + 2));       // tile totals, the sum of all, the first offender
+        e = t_cnt.alloc(sizeof(int32_t) * (size_t)n);
+        if (e == hipSuccess) e = t_bt.alloc(sizeof(int64_t) * ((size_t)ntiles + 2));       // tile totals, the sum of all, the first offender
         if (e == hipSuccess) {
             t_bad = reinterpret_cast<unsigned long long *>(t_bt + ntiles + 1);
             e = hipMemsetAsync(t_bad, 0xFF, sizeof(unsigned long long), c->stream);
@@ -3560,8 +3458,8 @@ int dpmm_upload_points_csc_device(dpmm_ctx *c, const void *d_colptr, int index_d
             if (e == hipSuccess) e = hipMemcpyAsync(&kept, t_bt + ntiles, sizeof(kept), hipMemcpyDeviceToHost, c->stream);
             if (e == hipSuccess) e = sync_stream(c, c->stream);
             const size_t nn = (size_t)std::max<int64_t>(kept, 1);
-            if (e == hipSuccess) e = hipMalloc(&n_ri, sizeof(uint16_t) * nn);
-            if (e == hipSuccess) e = hipMalloc(&n_val, sizeof(float) * nn);
+            if (e == hipSuccess) e = n_ri.alloc(sizeof(uint16_t) * nn);
+            if (e == hipSuccess) e = n_val.alloc(sizeof(float) * nn);
             if (e == hipSuccess) e = launch_csc_dev_compact(d_colptr, d_rowval, d_nzval, index_dtype == DPMM_DT_I64, value_dtype, n, index_base, n_cp, n_ri,
                                                             n_val, c->stream);
             if (e == hipSuccess) e = sync_stream(c, c->stream);
@@ -3570,9 +3468,7 @@ int dpmm_upload_points_csc_device(dpmm_ctx *c, const void *d_colptr, int index_d
         e = hipMemsetAsync(n_cp, 0, sizeof(int64_t), c->stream);
         if (e == hipSuccess) e = sync_stream(c, c->stream);
     }
-    hipFree(t_cnt); hipFree(t_bt);
     if (e != hipSuccess || bad != ~0ull) {
-        hipFree(n_cp); hipFree(n_ri); hipFree(n_val);
         if (e != hipSuccess) return fail(c, DPMM_EHIP, who + hipGetErrorString(e));
         const std::string pt = std::to_string((long long)(bad >> 20));
         switch ((int)(bad & 7)) {
@@ -3583,9 +3479,9 @@ int dpmm_upload_points_csc_device(dpmm_ctx *c, const void *d_colptr, int index_d
         }
     }
     // from here on as dpmm_upload_points_csc
-    free_sparse_points(c);
-    hipFree(c->dX); hipFree(c->dX8); c->dX = nullptr; c->dX8 = nullptr;
-    c->d_cp = n_cp; c->d_ri = n_ri; c->d_val = n_val; c->nnz = kept;
+    t_cnt.reset(); t_bt.reset();      // (before set_points_chunk sizes the slabs)
+    c->dX.reset(); c->dX8.reset();
+    c->d_cp = std::move(n_cp); c->d_ri = std::move(n_ri); c->d_val = std::move(n_val); c->nnz = kept;
     c->x_sparse = 1; c->x_u8 = 0; c->x_bf16_exact = 0; c->repack_pending = false;
     if (int rc2 = set_points_chunk(c, true)) return rc2;
     if (c->have_params && c->d_raw) {
@@ -3665,32 +3561,18 @@ int dpmm_predict_points_device(dpmm_ctx *c, int64_t *d_labels, float *d_probs) {
     if (d_probs) if (int rc = check_device_extent(c, fn, "d_probs", d_probs, sizeof(float) * (uint64_t)c->n * (uint64_t)c->K, sizeof(float))) return rc;
     const int64_t stride = c->ntiles * c->tile;
     const int rstep = (c->prior == DPMM_PRIOR_NIW) ? 1 : 3;       // Multinomial: rows 3k are the cluster-level rows
-    float *table = nullptr;
-    HIPCHK(c, hipMalloc(&table, sizeof(float) * (size_t)(rstep * c->K) * (size_t)stride));
+    DevBuf<float> table;
+    HIPCHK(c, table.alloc(sizeof(float) * (size_t)(rstep * c->K) * (size_t)stride));
     int rc = run_sweep(c, 0, 0, table, stride);
     if (rc == DPMM_OK) {
         hipError_t e = launch_predict_finish(table, stride, rstep, c->n, c->K, d_labels, d_probs, c->stream);
         if (e == hipSuccess) e = sync_stream(c, c->stream);
         if (e != hipSuccess) { c->err = std::string(fn) + ": " + hipGetErrorString(e); rc = DPMM_EHIP; }
     }
-    hipFree(table);
     return rc;
 }
 
 // ---- include/dpmm_hip_score.h: log-density, top-m, labels and probabilities, slab by slab ----------------------------------------------
-static int ensure_score_buffer(dpmm_ctx *c, void **buf, size_t *have, size_t need, const char *what) {
-    if (need <= *have) return DPMM_OK;
-    HIPCHK(c, sync_stream(c, c->stream));
-    hipFree(*buf); *buf = nullptr; *have = 0;
-    if (hipMalloc(buf, need) != hipSuccess) {
-        (void)hipGetLastError();
-        *buf = nullptr;
-        return fail(c, DPMM_EHIP, std::string("dpmm_score_points: out of device memory for the ") + what + " (" + std::to_string((unsigned long long)need) + " bytes)");
-    }
-    *have = need;
-    return DPMM_OK;
-}
-
 // slabs of whole tiles: as many as the budget holds, one at least; the ctx's table is grown to one slab.  rstep: cluster k is row k * rstep;
 // P: points of a slab = floats between two rows of the table
 static int score_table_slab(dpmm_ctx *c, int *rstep_out, int64_t *P_out) {
@@ -3701,7 +3583,7 @@ static int score_table_slab(dpmm_ctx *c, int *rstep_out, int64_t *P_out) {
     if (slab_tiles < 1) slab_tiles = 1;
     const int64_t P = slab_tiles * c->tile;
     *rstep_out = rstep; *P_out = P;
-    return ensure_score_buffer(c, reinterpret_cast<void **>(&c->d_score_table), &c->score_table_bytes, sizeof(float) * rows * (size_t)P, "table");
+    return grow(c, c->d_score_table, sizeof(float) * rows * (size_t)P, "dpmm_score_points", "table");
 }
 
 
@@ -3715,11 +3597,11 @@ static int miss_begin(dpmm_ctx *c, bool on, int64_t P, const char *fn) {
     if (c->prior != DPMM_PRIOR_NIW || c->h_miss_cst.size() != (size_t)c->K * MISS_CST || !c->d_par)
         return fail(c, DPMM_ESTATE, who + "missing features need dpmm_set_predictive_niw");
     const size_t K = (size_t)c->K, D = (size_t)c->D;
-    if (int rc = ensure_score_buffer(c, reinterpret_cast<void **>(&c->d_miss_cnt), &c->miss_cnt_bytes, 3 * sizeof(unsigned long long), "counters of the missing-feature pass")) return rc;
-    if (int rc = ensure_score_buffer(c, reinterpret_cast<void **>(&c->d_miss_list), &c->miss_list_bytes, sizeof(uint32_t) * (size_t)P, "list of the missing-feature pass")) return rc;
+    if (int rc = grow(c, c->d_miss_cnt, 3 * sizeof(unsigned long long), "dpmm_score_points", "counters of the missing-feature pass")) return rc;
+    if (int rc = grow(c, c->d_miss_list, sizeof(uint32_t) * (size_t)P, "dpmm_score_points", "list of the missing-feature pass")) return rc;
     if (c->miss_gen != c->pred_gen) {
-        if (int rc = ensure_score_buffer(c, reinterpret_cast<void **>(&c->d_miss_rt), &c->miss_rt_bytes, sizeof(float) * K * D * (size_t)miss_pitch(c->D), "transposed factors of the missing-feature pass")) return rc;
-        if (int rc = ensure_score_buffer(c, reinterpret_cast<void **>(&c->d_miss_cst), &c->miss_cst_bytes, sizeof(double) * K * MISS_CST, "constants of the missing-feature pass")) return rc;
+        if (int rc = grow(c, c->d_miss_rt, sizeof(float) * K * D * (size_t)miss_pitch(c->D), "dpmm_score_points", "transposed factors of the missing-feature pass")) return rc;
+        if (int rc = grow(c, c->d_miss_cst, sizeof(double) * K * MISS_CST, "dpmm_score_points", "constants of the missing-feature pass")) return rc;
         HIPCHK(c, sync_stream(c, c->stream));
         HIPCHK(c, hipMemcpy(c->d_miss_cst, c->h_miss_cst.data(), sizeof(double) * K * MISS_CST, hipMemcpyHostToDevice));
         const ParLayout L = par_layout(c, c->miss_slots);
@@ -3785,7 +3667,7 @@ static int score_points(dpmm_ctx *c, const dpmm_score_out *o, bool device, const
         off_ti = take(o->top_idx != nullptr, sizeof(int64_t) * m);
         off_tp = take(o->top_prob != nullptr, sizeof(float) * m);
         off_pr = take(o->probs != nullptr, sizeof(float) * K);
-        if (int rc = ensure_score_buffer(c, reinterpret_cast<void **>(&c->d_score_out), &c->score_out_bytes, total, "staging of the outputs")) return rc;
+        if (int rc = grow(c, c->d_score_out, total, "dpmm_score_points", "staging of the outputs")) return rc;
     }
     for (int64_t p0 = 0; p0 < c->n; p0 += P) {
         const int64_t np = std::min<int64_t>(P, c->n - p0);
@@ -3860,11 +3742,11 @@ static int impute_points(dpmm_ctx *c, float *out, int64_t ld, bool device, const
     if (int rc = score_table_slab(c, &rstep, &P)) return rc;
     if (int rc = miss_begin(c, true, P, fn)) return rc;
     const int64_t D = c->D;
-    if (!device) if (int rc = ensure_score_buffer(c, reinterpret_cast<void **>(&c->d_score_out), &c->score_out_bytes, sizeof(float) * (size_t)P * (size_t)D, "staging of the outputs")) return rc;
+    if (!device) if (int rc = grow(c, c->d_score_out, sizeof(float) * (size_t)P * (size_t)D, "dpmm_score_points", "staging of the outputs")) return rc;
     for (int64_t p0 = 0; p0 < c->n; p0 += P) {
         const int64_t np = std::min<int64_t>(P, c->n - p0);
         if (int rc = run_sweep(c, 0, 0, c->d_score_table, P, p0, np)) return rc;
-        float *rows = device ? out + p0 * ld : reinterpret_cast<float *>(c->d_score_out);
+        float *rows = device ? out + p0 * ld : reinterpret_cast<float *>(c->d_score_out.get());
         const int64_t ldr = device ? ld : D;
         HIPCHK(c, launch_points_readback(rows, ldr, c->dX + p0 * c->ldx, c->ldx, nullptr, 0, np, c->D, c->stream));
         if (int rc = miss_range(c, P, p0, np, rows, ldr, fn)) return rc;
@@ -3900,9 +3782,9 @@ int dpmm_rank_begin(dpmm_ctx *c, int m, int which) {
     const size_t cand = (size_t)2 * (size_t)cap * (sizeof(unsigned long long) + sizeof(uint16_t));
     const size_t km = (size_t)K * (size_t)m;
     const size_t out = 2 * km * sizeof(int64_t) + 2 * ((km * sizeof(float) + 7) & ~(size_t)7) + (size_t)(K + 1) * sizeof(int64_t);
-    if (int rc = ensure_score_buffer(c, reinterpret_cast<void **>(&c->d_rank_state), &c->rank_state_bytes, state, "running lists of dpmm_rank_begin")) return rc;
-    if (int rc = ensure_score_buffer(c, reinterpret_cast<void **>(&c->d_rank_cand), &c->rank_cand_bytes, cand, "candidate buffers of dpmm_rank_begin")) return rc;
-    if (int rc = ensure_score_buffer(c, reinterpret_cast<void **>(&c->d_rank_out), &c->rank_out_bytes, out, "staging of dpmm_rank_read")) return rc;
+    if (int rc = grow(c, c->d_rank_state, state, "dpmm_score_points", "running lists of dpmm_rank_begin")) return rc;
+    if (int rc = grow(c, c->d_rank_cand, cand, "dpmm_score_points", "candidate buffers of dpmm_rank_begin")) return rc;
+    if (int rc = grow(c, c->d_rank_out, out, "dpmm_score_points", "staging of dpmm_rank_read")) return rc;
     HIPCHK(c, hipMemsetAsync(c->d_rank_state, 0, state, c->stream));
     c->rank_m = m; c->rank_which = which; c->rank_K = K; c->rank_cap = cap; c->rank_parity = 0;
     c->rank_active = true;
@@ -3930,7 +3812,7 @@ int dpmm_rank_accumulate(dpmm_ctx *c, int64_t index_base, int64_t n_valid) {
     const int K = c->K;
     unsigned long long *keys = c->d_rank_state, *count = keys + rank_keys_words(K);
     unsigned *cand_n = reinterpret_cast<unsigned *>(count + rank_count_words(K));
-    unsigned long long *cand_key = reinterpret_cast<unsigned long long *>(c->d_rank_cand);
+    unsigned long long *cand_key = reinterpret_cast<unsigned long long *>(c->d_rank_cand.get());
     uint16_t *cand_k = reinterpret_cast<uint16_t *>(cand_key + 2 * c->rank_cap);
     for (int64_t p0 = 0; p0 < n_valid; p0 += P) {
         const int64_t np = std::min<int64_t>(P, c->n - p0);              // the range dpmm_score_points evaluates
@@ -4009,13 +3891,13 @@ int dpmm_overlap_begin(dpmm_ctx *c) {
     const int K = c->K, nb = (K + 63) / 64, npairs = nb * (nb + 1) / 2;
     const size_t state = sizeof(double) * overlap_acc_doubles(K) + sizeof(unsigned long long) * rank_count_words(K);
     const size_t part = sizeof(double) * (size_t)overlap_max_chunks(K) * ((size_t)npairs * 4096 + (size_t)nb * 64);
-    if (int rc = ensure_score_buffer(c, reinterpret_cast<void **>(&c->d_ov_acc), &c->ov_acc_bytes, state, "accumulators of dpmm_overlap_begin")) return rc;
-    if (int rc = ensure_score_buffer(c, reinterpret_cast<void **>(&c->d_ov_part), &c->ov_part_bytes, part, "chunk partials of dpmm_overlap_begin")) return rc;
+    if (int rc = grow(c, c->d_ov_acc, state, "dpmm_score_points", "accumulators of dpmm_overlap_begin")) return rc;
+    if (int rc = grow(c, c->d_ov_part, part, "dpmm_score_points", "chunk partials of dpmm_overlap_begin")) return rc;
     if (c->n > 0) {      // (M, S) of one range: sized as dpmm_overlap_accumulate will find it unless the table budget changes in between
         int rstep = 0;
         int64_t P = 0;
         if (int rc = score_table_slab(c, &rstep, &P)) return rc;
-        if (int rc = ensure_score_buffer(c, reinterpret_cast<void **>(&c->d_ov_ms), &c->ov_ms_bytes, sizeof(float2) * (size_t)P, "maxima and sums of dpmm_overlap_begin")) return rc;
+        if (int rc = grow(c, c->d_ov_ms, sizeof(float2) * (size_t)P, "dpmm_score_points", "maxima and sums of dpmm_overlap_begin")) return rc;
     }
     HIPCHK(c, hipMemsetAsync(c->d_ov_acc, 0, state, c->stream));
     c->ov_K = K; c->ov_gen = c->pred_gen;
@@ -4037,7 +3919,7 @@ int dpmm_overlap_accumulate(dpmm_ctx *c, int64_t n_valid) {
     int rstep = 0;
     int64_t P = 0;
     if (int rc = score_table_slab(c, &rstep, &P)) return rc;
-    if (int rc = ensure_score_buffer(c, reinterpret_cast<void **>(&c->d_ov_ms), &c->ov_ms_bytes, sizeof(float2) * (size_t)P, "maxima and sums of dpmm_overlap_accumulate")) return rc;
+    if (int rc = grow(c, c->d_ov_ms, sizeof(float2) * (size_t)P, "dpmm_score_points", "maxima and sums of dpmm_overlap_accumulate")) return rc;
     const bool miss = c->opt_score_missing != 0;
     if (int rc = miss_begin(c, miss, P, fn)) return rc;
     const int K = c->K, nb = (K + 63) / 64, npairs = nb * (nb + 1) / 2;
@@ -4086,18 +3968,6 @@ int dpmm_overlap_read(dpmm_ctx *c, const dpmm_overlap_out *o) {
 }
 
 // ---- include/dpmm_hip_trace.h: label samples kept on the device, their contingency tables and the per-point confidence (trace.hip) ----------
-static int trace_buffer(dpmm_ctx *c, void **buf, size_t *have, size_t need, const char *fn, const char *what) {
-    if (need <= *have) return DPMM_OK;
-    HIPCHK(c, sync_stream(c, c->stream));
-    hipFree(*buf); *buf = nullptr; *have = 0;
-    if (hipMalloc(buf, need) != hipSuccess) {
-        (void)hipGetLastError();
-        *buf = nullptr;
-        return fail(c, DPMM_EHIP, std::string(fn) + ": out of device memory for the " + what + " (" + std::to_string((unsigned long long)need) + " bytes)");
-    }
-    *have = need;
-    return DPMM_OK;
-}
 static uint16_t *trace_row(dpmm_ctx *c, int slot) { return c->d_trace + (size_t)slot * (size_t)c->trace_nvec * 8; }
 // a slot a call names: inside the trace (DPMM_EINVAL) and recorded (DPMM_ESTATE)
 static int trace_slot_ok(dpmm_ctx *c, const std::string &who, int slot) {
@@ -4112,7 +3982,7 @@ int dpmm_trace_close(dpmm_ctx *c) {
     if (!c->d_trace) return DPMM_OK;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, sync_stream(c, c->stream));
-    hipFree(c->d_trace); c->d_trace = nullptr;
+    c->d_trace.reset();
     c->trace_slots = 0; c->trace_nvec = 0; c->trace_K.clear();
     return DPMM_OK;
 }
@@ -4126,11 +3996,7 @@ int dpmm_trace_open(dpmm_ctx *c, int slots) {
     HIPCHK(c, hipSetDevice(c->device));
     const int64_t nvec = (c->n + 7) / 8;                           // a row: n ids of 2 bytes, padded to 16 bytes
     const size_t bytes = std::max<size_t>(16, (size_t)slots * (size_t)nvec * 16);
-    if (hipMalloc(&c->d_trace, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        c->d_trace = nullptr;
-        return fail(c, DPMM_EHIP, who + "out of device memory for the trace (" + std::to_string((unsigned long long)bytes) + " bytes)");
-    }
+    if (int rc = regrow(c, c->d_trace, bytes, fn, "trace")) return rc;      // (dpmm_trace_close above waited for the stream)
     c->trace_slots = slots; c->trace_nvec = nvec; c->trace_K.assign((size_t)slots, 0);
     return DPMM_OK;
 }
@@ -4165,7 +4031,7 @@ int dpmm_trace_tables(dpmm_ctx *c, const int32_t *pairs, int npairs, int64_t *co
     if (total == 0) return DPMM_OK;
     HIPCHK(c, hipSetDevice(c->device));
     if (c->n == 0) { memset(counts, 0, sizeof(int64_t) * total); return DPMM_OK; }
-    if (int rc = trace_buffer(c, reinterpret_cast<void **>(&c->d_trace_counts), &c->trace_counts_bytes, sizeof(unsigned long long) * total, fn, "tables")) return rc;
+    if (int rc = grow(c, c->d_trace_counts, sizeof(unsigned long long) * total, fn, "tables")) return rc;
     HIPCHK(c, hipMemsetAsync(c->d_trace_counts, 0, sizeof(unsigned long long) * total, c->stream));
     // pairs by row slot (stable: a row's pairs keep their order), then consecutive pairs of a row into groups within the LDS budget
     std::vector<int> order((size_t)npairs);
@@ -4193,10 +4059,10 @@ int dpmm_trace_tables(dpmm_ctx *c, const int32_t *pairs, int npairs, int64_t *co
     }
     if (!groups.empty()) {
         const size_t gb = (sizeof(TraceGroup) * groups.size() + 15) & ~(size_t)15, pb = sizeof(TracePair) * tp.size();
-        if (int rc = trace_buffer(c, reinterpret_cast<void **>(&c->d_trace_desc), &c->trace_desc_bytes, gb + pb, fn, "pair lists")) return rc;
+        if (int rc = grow(c, c->d_trace_desc, gb + pb, fn, "pair lists")) return rc;
         HIPCHK(c, hipMemcpy(c->d_trace_desc, groups.data(), sizeof(TraceGroup) * groups.size(), hipMemcpyHostToDevice));
         HIPCHK(c, hipMemcpy(c->d_trace_desc + gb, tp.data(), pb, hipMemcpyHostToDevice));
-        HIPCHK(c, launch_trace_tables(reinterpret_cast<const TraceGroup *>(c->d_trace_desc), (int)groups.size(),
+        HIPCHK(c, launch_trace_tables(reinterpret_cast<const TraceGroup *>(c->d_trace_desc.get()), (int)groups.size(),
                                       reinterpret_cast<const TracePair *>(c->d_trace_desc + gb), max_cells, c->trace_nvec, c->stream));
     }
     for (int p : big) {
@@ -4229,16 +4095,16 @@ int dpmm_trace_confidence(dpmm_ctx *c, int anchor, const int32_t *slots, int nsl
     HIPCHK(c, hipSetDevice(c->device));
     if (c->n == 0) return DPMM_OK;
     if (out_device) if (int rc = check_device_extent(c, fn, "out_device", out_device, sizeof(float) * (uint64_t)c->n, sizeof(float))) return rc;
-    if (int rc = trace_buffer(c, reinterpret_cast<void **>(&c->d_trace_ratio), &c->trace_ratio_bytes, sizeof(float) * (size_t)total, fn, "ratio tables")) return rc;
-    if (int rc = trace_buffer(c, reinterpret_cast<void **>(&c->d_trace_desc), &c->trace_desc_bytes, sizeof(TraceConfSlot) * cs.size(), fn, "slot list")) return rc;
+    if (int rc = grow(c, c->d_trace_ratio, sizeof(float) * (size_t)total, fn, "ratio tables")) return rc;
+    if (int rc = grow(c, c->d_trace_desc, sizeof(TraceConfSlot) * cs.size(), fn, "slot list")) return rc;
     float *target = static_cast<float *>(out_device);
     if (!target) {
-        if (int rc = trace_buffer(c, reinterpret_cast<void **>(&c->d_trace_conf), &c->trace_conf_bytes, sizeof(float) * (size_t)c->n, fn, "result")) return rc;
+        if (int rc = grow(c, c->d_trace_conf, sizeof(float) * (size_t)c->n, fn, "result")) return rc;
         target = c->d_trace_conf;
     }
     HIPCHK(c, hipMemcpy(c->d_trace_ratio, ratio, sizeof(float) * (size_t)total, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(c->d_trace_desc, cs.data(), sizeof(TraceConfSlot) * cs.size(), hipMemcpyHostToDevice));
-    HIPCHK(c, launch_trace_confidence(trace_row(c, anchor), Ka, reinterpret_cast<const TraceConfSlot *>(c->d_trace_desc), nslots, c->d_trace_ratio, c->n,
+    HIPCHK(c, launch_trace_confidence(trace_row(c, anchor), Ka, reinterpret_cast<const TraceConfSlot *>(c->d_trace_desc.get()), nslots, c->d_trace_ratio, c->n,
                                       c->trace_nvec, target, c->stream));
     if (out_host) HIPCHK(c, hipMemcpyAsync(out_host, target, sizeof(float) * (size_t)c->n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, sync_stream(c, c->stream));
@@ -4255,27 +4121,20 @@ int dpmm_trace_read(dpmm_ctx *c, int slot, int64_t *labels_host, void *labels_de
     HIPCHK(c, hipSetDevice(c->device));
     if (c->n == 0) return DPMM_OK;
     if (labels_device) if (int rc = check_device_extent(c, fn, "labels_device", labels_device, sizeof(int64_t) * (uint64_t)c->n, sizeof(int64_t))) return rc;
-    int64_t *tmp = nullptr, *target = static_cast<int64_t *>(labels_device);
+    DevBuf<int64_t> tmp;
+    int64_t *target = static_cast<int64_t *>(labels_device);
     if (!target) {
-        HIPCHK(c, hipMalloc(&tmp, sizeof(int64_t) * (size_t)c->n));
+        HIPCHK(c, tmp.alloc(sizeof(int64_t) * (size_t)c->n));
         target = tmp;
     }
     hipError_t e = launch_trace_read(trace_row(c, slot), c->n, target, c->stream);
     if (e == hipSuccess && labels_host) e = hipMemcpyAsync(labels_host, target, sizeof(int64_t) * (size_t)c->n, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = sync_stream(c, c->stream);
-    hipFree(tmp);
     if (e != hipSuccess) { c->err = who + hipGetErrorString(e); return DPMM_EHIP; }
     return DPMM_OK;
 }
 
 // ---- include/dpmm_hip_sample.h: drawing points from a fitted model (sample.hip) -------------------------------------------------------
-static int sampler_table(dpmm_ctx *c, void **dst, const void *src, size_t bytes) {
-    hipFree(*dst); *dst = nullptr;
-    HIPCHK(c, hipMalloc(dst, bytes));
-    HIPCHK(c, hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
-    return DPMM_OK;
-}
-
 int dpmm_set_sampler_niw(dpmm_ctx *c, int K, const float *m, const float *A, const float *df) {
     static const std::string who = "dpmm_set_sampler_niw: ";
     if (!c) return tensor_no_ctx("dpmm_set_sampler_niw");
@@ -4292,9 +4151,9 @@ int dpmm_set_sampler_niw(dpmm_ctx *c, int K, const float *m, const float *A, con
             for (int b = a; b < D; ++b) At[((size_t)k * D + b) * D + a] = A[((size_t)k * D + a) * D + b];
     HIPCHK(c, hipSetDevice(c->device));
     c->sm_K = 0;
-    if (int rc = sampler_table(c, reinterpret_cast<void **>(&c->d_sm_m), m, sizeof(float) * (size_t)K * D)) return rc;
-    if (int rc = sampler_table(c, reinterpret_cast<void **>(&c->d_sm_At), At.data(), sizeof(float) * At.size())) return rc;
-    if (int rc = sampler_table(c, reinterpret_cast<void **>(&c->d_sm_df), df, sizeof(float) * (size_t)K)) return rc;
+    if (int rc = sampler_table(c, c->d_sm_m, m, sizeof(float) * (size_t)K * D)) return rc;
+    if (int rc = sampler_table(c, c->d_sm_At, At.data(), sizeof(float) * At.size())) return rc;
+    if (int rc = sampler_table(c, c->d_sm_df, df, sizeof(float) * (size_t)K)) return rc;
     c->sm_K = K;
     return DPMM_OK;
 }
@@ -4310,8 +4169,8 @@ int dpmm_set_sampler_mult(dpmm_ctx *c, int K, const uint32_t *thr, const int32_t
         if (alias[e] < 0 || alias[e] >= c->D) return fail(c, DPMM_EINVAL, who + "alias[" + std::to_string(e) + "] is outside [0, D)");
     HIPCHK(c, hipSetDevice(c->device));
     c->sm_K = 0;
-    if (int rc = sampler_table(c, reinterpret_cast<void **>(&c->d_sm_thr), thr, sizeof(uint32_t) * cnt)) return rc;
-    if (int rc = sampler_table(c, reinterpret_cast<void **>(&c->d_sm_alias), alias, sizeof(int32_t) * cnt)) return rc;
+    if (int rc = sampler_table(c, c->d_sm_thr, thr, sizeof(uint32_t) * cnt)) return rc;
+    if (int rc = sampler_table(c, c->d_sm_alias, alias, sizeof(int32_t) * cnt)) return rc;
     c->sm_K = K;
     return DPMM_OK;
 }
@@ -4382,9 +4241,9 @@ int dpmm_sample_points_device(dpmm_ctx *c, const dpmm_sample_request *q) {
     }
     cs[0] = 0;
     if (c->sm_start_cap < K + 1) {
-        hipFree(c->d_sm_cstart); hipFree(c->d_sm_tstart); c->d_sm_cstart = nullptr; c->d_sm_tstart = nullptr; c->sm_start_cap = 0;
-        HIPCHK(c, hipMalloc(&c->d_sm_cstart, sizeof(int64_t) * (DPMM_MAX_CLUSTERS + 1)));
-        HIPCHK(c, hipMalloc(&c->d_sm_tstart, sizeof(int32_t) * (DPMM_MAX_CLUSTERS + 1)));
+        c->sm_start_cap = 0;
+        HIPCHK(c, c->d_sm_cstart.alloc(sizeof(int64_t) * (DPMM_MAX_CLUSTERS + 1)));
+        HIPCHK(c, c->d_sm_tstart.alloc(sizeof(int32_t) * (DPMM_MAX_CLUSTERS + 1)));
         c->sm_start_cap = DPMM_MAX_CLUSTERS + 1;
     }
     HIPCHK(c, hipMemcpyAsync(c->d_sm_cstart, cs.data(), sizeof(int64_t) * cs.size(), hipMemcpyHostToDevice, c->stream));
@@ -4399,8 +4258,8 @@ int dpmm_sample_points_device(dpmm_ctx *c, const dpmm_sample_request *q) {
         HIPCHK(c, launch_sample_mult_dense(a, c->stream));
     } else if (!fill) {
         if (!c->d_sm_cnt) {
-            HIPCHK(c, hipMalloc(&c->d_sm_cnt, sizeof(int32_t) * (size_t)c->n));
-            HIPCHK(c, hipMalloc(&c->d_sm_bt, sizeof(int64_t) * ((size_t)csc_scan_tiles(c->n) + 1)));
+            HIPCHK(c, c->d_sm_cnt.alloc(sizeof(int32_t) * (size_t)c->n));
+            HIPCHK(c, c->d_sm_bt.alloc(sizeof(int64_t) * ((size_t)csc_scan_tiles(c->n) + 1)));
         }
         a.cnt = c->d_sm_cnt;
         a.labels = nullptr;
