@@ -204,6 +204,13 @@ ABI_MISSING = [
 ]
 OPT_SCORE_MISSING = 33       # DPMM_OPT_SCORE_MISSING
 SCORE_MAX_MISSING = 16       # DPMM_SCORE_MAX_MISSING
+# include/dpmm_hip_impute.h: draws of the missing features from the fitted mixture (additive; bound next to ABI)
+_IMPUTE_DRAW_TAIL = [ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]
+ABI_IMPUTE = [
+    ("dpmm_impute_draw_points", ctypes.c_int, [ctypes.c_void_p, _c_f32p] + _IMPUTE_DRAW_TAIL),
+    ("dpmm_impute_draw_points_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p] + _IMPUTE_DRAW_TAIL),
+]
+IMPUTE_MAX_DRAWS = 1 << 26   # DPMM_IMPUTE_MAX_DRAWS
 
 HOST_ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int)   # dpmm_host_allreduce_fn
 
@@ -268,7 +275,7 @@ def load_library():
         except Exception:  # pragma: no cover  (torch is optional for single-GPU use)
             pass
         lib = ctypes.CDLL(p)
-        for name, res, args in ABI + ABI_TENSOR + ABI_SCORE + ABI_RANK + ABI_OVERLAP + ABI_TRACE + ABI_MISSING + ABI_CSC + ABI_SAMPLE + ABI_PROJECT:
+        for name, res, args in ABI + ABI_TENSOR + ABI_SCORE + ABI_RANK + ABI_OVERLAP + ABI_TRACE + ABI_MISSING + ABI_IMPUTE + ABI_CSC + ABI_SAMPLE + ABI_PROJECT:
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -670,6 +677,29 @@ class Worker:
         else:
             assert out.dtype == np.float32
             self._chk(self._lib.dpmm_impute_points(self._h, _p(out, _c_f32p), int(out.shape[1])))
+
+    # ---- draws of the missing features (include/dpmm_hip_impute.h)
+    def impute_draws_into(self, out, seed, i0, draw0=0, comp=None):
+        """dpmm_impute_draw_points[_device] into storage the caller made: out (n, ndraws, w >= D) float32, C-contiguous -- the draws of a
+        point side by side: ld = ndraws * w, draw_stride = w -- a numpy array (host variant) or a torch tensor on this worker's GPU (device
+        variant); the draws are draw0 .. draw0 + ndraws - 1 of the points with global indices i0 .. i0 + n - 1.  comp: None or an
+        (ndraws, n) int32 array / tensor of the same kind for the drawn clusters (0-based, -1 off the marginalised points)."""
+        dev = hasattr(out, "data_ptr")
+        nd, w = int(out.shape[1]), int(out.shape[2])
+        assert int(out.shape[0]) == self.n and nd >= 1 and w >= self.D and (out.is_contiguous() if dev else out.flags.c_contiguous)
+        if comp is not None:
+            assert hasattr(comp, "data_ptr") == dev and tuple(comp.shape) == (nd, self.n) and (comp.is_contiguous() if dev else comp.flags.c_contiguous)
+        if self.n == 0:
+            return
+        if dev:
+            import torch
+            assert out.dtype == torch.float32 and (comp is None or comp.dtype == torch.int32)
+            torch.cuda.current_stream(out.device).synchronize()
+            fn, op, cp = self._lib.dpmm_impute_draw_points_device, ctypes.c_void_p(out.data_ptr()), comp.data_ptr() if comp is not None else None
+        else:
+            assert out.dtype == np.float32 and (comp is None or comp.dtype == np.int32)
+            fn, op, cp = self._lib.dpmm_impute_draw_points, _p(out, _c_f32p), comp.ctypes.data if comp is not None else None
+        self._chk(fn(self._h, op, nd * w, w, ctypes.c_void_p(cp), ctypes.c_uint64(int(seed)), int(i0), int(draw0), nd))
 
     # ---- exemplars (include/dpmm_hip_rank.h)
     def rank_begin(self, m, which=RANK_TYPICAL | RANK_FRINGE):

@@ -13,6 +13,7 @@
 #include "../../include/dpmm_hip_overlap.h"
 #include "../../include/dpmm_hip_trace.h"
 #include "../../include/dpmm_hip_missing.h"
+#include "../../include/dpmm_hip_impute.h"
 #include "../../include/dpmm_hip_sample.h"
 #include "../../include/dpmm_hip_project.h"
 
@@ -3762,6 +3763,91 @@ static int impute_points(dpmm_ctx *c, float *out, int64_t ld, bool device, const
 
 int dpmm_impute_points(dpmm_ctx *c, float *out, int64_t ld) { return impute_points(c, out, ld, false, "dpmm_impute_points"); }
 int dpmm_impute_points_device(dpmm_ctx *c, float *d_out, int64_t ld) { return impute_points(c, d_out, ld, true, "dpmm_impute_points_device"); }
+
+// ---- include/dpmm_hip_impute.h: draws of the missing features.  Per range: the table once, list and patch, then the draws -- into the
+// caller's device memory, or in batches of draws through the staging block ([batch][np][D] floats, then [batch][np] components).
+static int impute_draw_points(dpmm_ctx *c, float *out, int64_t ld, int64_t draw_stride, int32_t *comp, uint64_t seed, int64_t i0, int64_t draw0,
+                              int64_t ndraws, bool device, const char *fn) {
+    if (!c) return tensor_no_ctx(fn);
+    c->miss_counted = false;      // (as score_points)
+    const std::string who = std::string(fn) + ": ";
+    if (c->prior != DPMM_PRIOR_NIW) return fail(c, DPMM_EINVAL, who + "the Multinomial prior has no missing features");
+    if (!c->predictive) return fail(c, DPMM_ESTATE, who + "needs dpmm_set_predictive_niw first");
+    const int64_t D = c->D, n = c->n;
+    if (ndraws < 1 || draw0 < 0 || draw0 > DPMM_IMPUTE_MAX_DRAWS || ndraws > DPMM_IMPUTE_MAX_DRAWS - draw0)
+        return fail(c, DPMM_EINVAL, who + "draw0 >= 0, ndraws >= 1 and draw0 + ndraws <= DPMM_IMPUTE_MAX_DRAWS are needed");
+    if (i0 < 0 || (i0 >> 62)) return fail(c, DPMM_EINVAL, who + "i0 out of range");
+    if (ld < D) return fail(c, DPMM_EINVAL, who + "ld < D");
+    if ((ld >> 40) || draw_stride < 0 || (draw_stride >> 37)) return fail(c, DPMM_EINVAL, who + "ld / draw_stride out of range");
+    const bool interleaved = draw_stride >= D && draw_stride <= ld / ndraws;
+    if (!interleaved && (unsigned __int128)draw_stride < (unsigned __int128)n * (unsigned __int128)ld)
+        return fail(c, DPMM_EINVAL, who + "the draws overlap: draw_stride >= n_local * ld (stacked) or D <= draw_stride <= ld / ndraws (interleaved) is needed");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (n == 0) return DPMM_OK;
+    if (!c->have_points || !c->have_params || !c->dX) return fail(c, DPMM_ESTATE, who + "needs points and parameters");
+    if (!out) return fail(c, DPMM_EINVAL, who + "out is null");
+    const int64_t width = std::min(ld, draw_stride);
+    if (device) {
+        const uint64_t words = (uint64_t)(ndraws - 1) * (uint64_t)draw_stride + (uint64_t)(n - 1) * (uint64_t)ld + (uint64_t)width;
+        if (int rc = check_device_extent(c, fn, "d_out", out, words * sizeof(float), sizeof(float))) return rc;
+        if (comp) if (int rc = check_device_extent(c, fn, "d_comp", comp, (uint64_t)ndraws * (uint64_t)n * sizeof(int32_t), sizeof(int32_t))) return rc;
+    }
+    int rstep = 0;
+    int64_t P = 0;
+    if (int rc = score_table_slab(c, &rstep, &P)) return rc;
+    if (int rc = miss_begin(c, true, P, fn)) return rc;
+    int64_t batch = ndraws;
+    if (!device) {
+        batch = std::max<int64_t>(1, std::min<int64_t>(ndraws, ((int64_t)64 << 20) / ((int64_t)sizeof(float) * P * D)));
+        if (int rc = grow(c, c->d_score_out, (size_t)batch * (size_t)P * (sizeof(float) * (size_t)D + sizeof(int32_t)), "dpmm_score_points", "staging of the outputs")) return rc;
+    }
+    const ParLayout L = par_layout(c, c->miss_slots);
+    for (int64_t p0 = 0; p0 < n; p0 += P) {
+        const int64_t np = std::min<int64_t>(P, n - p0);
+        if (int rc = run_sweep(c, 0, 0, c->d_score_table, P, p0, np)) return rc;
+        if (int rc = miss_range(c, P, p0, np, nullptr, 0, fn)) return rc;
+        MissArgs a{};      // (as miss_range)
+        a.table = c->d_score_table; a.stride = P; a.n = np; a.K = c->K; a.D = c->D;
+        a.X = c->dX + p0 * c->ldx; a.ldx = c->ldx;
+        a.Rt = c->d_miss_rt; a.mu = reinterpret_cast<const float *>(c->d_par + (L.mu - L.cst)); a.mu_step = 3 * D;
+        a.cst = c->d_miss_cst; a.list = c->d_miss_list; a.cnt = c->d_miss_cnt;
+        for (int64_t j0 = 0; j0 < ndraws; j0 += batch) {
+            const int64_t nb = std::min(batch, ndraws - j0);
+            MissDraw w{};
+            w.seed = seed; w.i0 = i0 + p0; w.draw0 = draw0 + j0; w.ndraws = (int)nb;
+            if (device) {
+                w.out = out + j0 * draw_stride + p0 * ld; w.ld = ld; w.draw_stride = draw_stride;
+                w.comp = comp ? comp + j0 * n + p0 : nullptr; w.comp_stride = n;
+            } else {
+                w.out = reinterpret_cast<float *>(c->d_score_out.get()); w.ld = D; w.draw_stride = np * D;
+                w.comp = comp ? reinterpret_cast<int32_t *>(w.out + batch * P * D) : nullptr; w.comp_stride = np;
+            }
+            hipError_t e = launch_miss_draw(a, w, 8 * c->cus, c->stream);
+            if (e != hipSuccess) { c->err = who + hipGetErrorString(e); return DPMM_EHIP; }
+            if (!device) {
+                for (int64_t jd = 0; jd < nb; ++jd)
+                    HIPCHK(c, hipMemcpy2DAsync(out + (j0 + jd) * draw_stride + p0 * ld, sizeof(float) * (size_t)ld, w.out + jd * np * D, sizeof(float) * (size_t)D,
+                                               sizeof(float) * (size_t)D, (size_t)np, hipMemcpyDeviceToHost, c->stream));
+                if (comp) HIPCHK(c, hipMemcpy2DAsync(comp + j0 * n + p0, sizeof(int32_t) * (size_t)n, w.comp, sizeof(int32_t) * (size_t)np, sizeof(int32_t) * (size_t)np,
+                                                     (size_t)nb, hipMemcpyDeviceToHost, c->stream));
+                HIPCHK(c, sync_stream(c, c->stream));      // the staging block is rewritten by the next batch
+                if (width > D)
+                    for (int64_t jd = j0; jd < j0 + nb; ++jd)
+                        for (int64_t i = p0; i < p0 + np; ++i) memset(out + jd * draw_stride + i * ld + D, 0, sizeof(float) * (size_t)(width - D));
+            }
+        }
+    }
+    HIPCHK(c, sync_stream(c, c->stream));
+    return DPMM_OK;
+}
+
+int dpmm_impute_draw_points(dpmm_ctx *c, float *out, int64_t ld, int64_t draw_stride, int32_t *comp, uint64_t seed, int64_t i0, int64_t draw0, int64_t ndraws) {
+    return impute_draw_points(c, out, ld, draw_stride, comp, seed, i0, draw0, ndraws, false, "dpmm_impute_draw_points");
+}
+int dpmm_impute_draw_points_device(dpmm_ctx *c, float *d_out, int64_t ld, int64_t draw_stride, int32_t *d_comp, uint64_t seed, int64_t i0, int64_t draw0,
+                                   int64_t ndraws) {
+    return impute_draw_points(c, d_out, ld, draw_stride, d_comp, seed, i0, draw0, ndraws, true, "dpmm_impute_draw_points_device");
+}
 
 // ---- include/dpmm_hip_rank.h: exemplars, the m most and least typical points of every cluster (rank.hip) -----------------------------------
 static size_t rank_keys_words(int K) { return (size_t)2 * (size_t)K * RANK_SLOTS; }

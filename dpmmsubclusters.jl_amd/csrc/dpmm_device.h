@@ -17,6 +17,8 @@ enum : uint32_t { STREAM_SWEEP = 0, STREAM_INIT = 1, STREAM_SPLIT = 2, STREAM_RE
 // Drawing points from a fitted model (sample.hip; include/dpmm_hip_sample.h states the keying).  The masters' streams are 32..34
 // (niw_master.hip) and 35 (mult_master.hip): these stay clear of them.
 enum : uint32_t { STREAM_SAMPLE_NORMAL = 40, STREAM_SAMPLE_CHI = 41, STREAM_SAMPLE_MULT = 42 };
+// Drawing the missing features of a point (missing.hip; include/dpmm_hip_impute.h states the keying): component, normals, chi^2.
+enum : uint32_t { STREAM_IMPUTE_COMP = 43, STREAM_IMPUTE_NORMAL = 44, STREAM_IMPUTE_CHI = 45 };
 
 struct Philox4 {
     uint32_t v[4];

@@ -254,6 +254,19 @@ struct MissArgs {
 hipError_t launch_miss_transpose(const float *Rpk, int64_t step, float *Rt, int K, int D, hipStream_t s);      // Rpk: packed upper triangles, cluster k at Rpk + k * step
 hipError_t launch_miss_list(const MissArgs &a, hipStream_t s);
 hipError_t launch_miss_patch(const MissArgs &a, bool impute, int max_grid, hipStream_t s);
+// draws of the missing features (include/dpmm_hip_impute.h) behind launch_miss_list and launch_miss_patch(a, false, ..) of the same range
+constexpr int64_t MISS_DRAW_MAX = (int64_t)1 << 26;      // draw indices: 64 Philox blocks each in a 32-bit block number
+struct MissDraw {
+    float *out;                  // element (jd, i, f) of the range at out[jd * draw_stride + i * ld + f]: f < min(ld, draw_stride) is written
+    int64_t ld, draw_stride;
+    int32_t *comp;               // null, or comp[jd * comp_stride + i]: the 0-based drawn cluster of a listed point, -1 elsewhere
+    int64_t comp_stride;
+    uint64_t seed;
+    int64_t i0;                  // global index of the range's first point
+    int64_t draw0;               // draw index of jd = 0
+    int ndraws;
+};
+hipError_t launch_miss_draw(const MissArgs &a, const MissDraw &w, int max_grid, hipStream_t s);
 // ---- label trace (trace.hip; include/dpmm_hip_trace.h).  A row holds nvec 16-byte vectors of 8 ids, padded with 0xFFFF.
 constexpr int TRACE_LDS_CELLS = 16384;    // 32-bit counters of a group of tables in LDS (64 KiB)
 struct TracePair {                        // one table of a group

@@ -16,10 +16,16 @@
 //                       The IMPUTE instantiation runs behind it on the patched table: M, S and p_k = e_k / S as score_finish_kernel forms
 //                       them (same operations, same bits), t_k by the same steps, and lane a < r accumulates sum_k p_k (m[M_a] - t_a) in
 //                       Float64 for the one output word it owns.
+//   miss_draw_kernel    (include/dpmm_hip_impute.h, which states the law and the keying) one wave per (listed point, draw) on the patched
+//                       table: the cumulative p_k in Float64 against one 53-bit uniform pick k; for that cluster alone y, g, A = L L', t and
+//                       q_o by the patch kernel's steps, w = L'^-1 n by its back-substitution from r Float32 Box-Muller normals, g ~ chi^2 by
+//                       the sampler's Marsaglia-Tsang; lane a < r writes (m[M_a] - t_a) + sqrt((df + q_o) / g) w_a, Float64 rounded once.
+//                       miss_draw_copy_kernel writes the rest of every draw's image in front of it.
 //   miss_transpose_kernel   Rt[k][j][i] = R_k[i][j] from the packed upper triangles of the parameter staging, once per parameter set.
 // The missing set is not stored: the wave that reads x gets it from a ballot per 64 features.
 #include "dpmm_device.h"
 #include "dpmm_kernels.h"
+#include "sample_device.h"
 
 namespace dpmm {
 
@@ -77,6 +83,143 @@ __global__ __launch_bounds__(256) void miss_list_kernel(MissArgs A) {
     }
 }
 
+// The range's point behind x: its values (0 in the pad), the NaN ballots per 64 features, M_a in lane a < r; returns r.
+template <int NT>
+__device__ __forceinline__ int miss_read_point(const float *x, int D, int lane, float (&xv)[NT], unsigned long long (&nm)[NT], int &myM) {
+    int r = 0;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        const int j = 64 * t + lane;
+        xv[t] = j < D ? x[j] : 0.f;
+        nm[t] = __ballot(xv[t] != xv[t]);
+        r += __popcll(nm[t]);
+    }
+    // lane a < r learns M_a, the a-th missing feature
+    myM = 0;
+    int a = 0;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        unsigned long long mk = nm[t];
+        while (mk) {
+            const int b = __ffsll((long long)mk) - 1;
+            mk &= mk - 1;
+            if (lane == a) myM = 64 * t + b;
+            ++a;
+        }
+    }
+    return r;
+}
+
+// One cluster's small system of a listed point: y = R z, g = C'y, A = C'C = L L' and t = A^-1 g.  Leaves y, t_a in `gl` of lane a < r and L
+// in the wave's LDS (the caller fences before A is overwritten); returns sum_j log L_jj = logdet A / 2.
+template <int NT>
+__device__ __forceinline__ double miss_system(const float *Rk, const float *mk, const float (&xv)[NT], const unsigned long long (&nm)[NT], int myM, int r,
+                                              int D, int lane, double *Am, float (&y)[NT], double &gl) {
+    constexpr int Dp = 64 * NT;
+    float z[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        const int j = 64 * t + lane;
+        const bool miss = (nm[t] >> lane) & 1ull;
+        z[t] = (j < D && !miss) ? xv[t] - mk[j] : 0.f;
+        y[t] = 0.f;
+    }
+    // ---- y = R z: column j of R scaled by z_j; rows above 64 (tj + 1) hold zeros of the triangle and are skipped
+#pragma unroll
+    for (int tj = 0; tj < NT; ++tj) {
+        const int jn = D - 64 * tj < 64 ? D - 64 * tj : 64;
+#pragma unroll 4
+        for (int jj = 0; jj < jn; ++jj) {
+            const float zj = miss_rl_f(z[tj], jj);
+            const float *c = Rk + (int64_t)(64 * tj + jj) * Dp + lane;
+#pragma unroll
+            for (int tr = 0; tr <= tj; ++tr) y[tr] = fmaf(c[64 * tr], zj, y[tr]);
+        }
+    }
+    // ---- g = C'y into lane b, A = C'C (lower triangle) into the wave's LDS
+    gl = 0.0;
+    for (int b = 0; b < r; ++b) {
+        const float *cb = Rk + (int64_t)__builtin_amdgcn_readlane(myM, b) * Dp + lane;
+        float colb[NT];
+        double p = 0.0;
+#pragma unroll
+        for (int t = 0; t < NT; ++t) { colb[t] = cb[64 * t]; p += (double)colb[t] * (double)y[t]; }
+        p = miss_wave_sum(p);
+        if (lane == b) gl = p;
+        for (int a = 0; a <= b; ++a) {
+            const float *ca = Rk + (int64_t)__builtin_amdgcn_readlane(myM, a) * Dp + lane;
+            double s = 0.0;
+#pragma unroll
+            for (int t = 0; t < NT; ++t) s += (double)ca[64 * t] * (double)colb[t];
+            s = miss_wave_sum(s);
+            if (lane == 0) Am[b * MISS_LDA + a] = s;
+        }
+    }
+    miss_lds_fence();
+    // ---- A = L L': lane a owns row a; column j is finished by the lanes j .. r - 1 at once
+    double half_logdet = 0.0;
+    for (int j = 0; j < r; ++j) {
+        const bool act = lane >= j && lane < r;
+        const int row = act ? lane : j;
+        double s = Am[row * MISS_LDA + j];
+        for (int t2 = 0; t2 < j; ++t2) s -= Am[row * MISS_LDA + t2] * Am[j * MISS_LDA + t2];
+        const double dj = sqrt(miss_rl_d(s, j));
+        half_logdet += log(dj);
+        if (act) Am[lane * MISS_LDA + j] = (lane == j) ? dj : s / dj;
+        miss_lds_fence();
+    }
+    // ---- t = A^-1 g: L u = g, then L't = u; lane a ends with t_a
+    for (int j = 0; j < r; ++j) {
+        if (lane == j) gl = gl / Am[j * MISS_LDA + j];
+        const double uj = miss_rl_d(gl, j);
+        if (lane > j && lane < r) gl -= Am[lane * MISS_LDA + j] * uj;
+    }
+    for (int j = r - 1; j >= 0; --j) {
+        if (lane == j) gl = gl / Am[j * MISS_LDA + j];
+        const double tj = miss_rl_d(gl, j);
+        if (lane < j) gl -= Am[j * MISS_LDA + lane] * tj;
+    }
+    return half_logdet;
+}
+
+// q_o = |y - C t|^2, the residual itself (t_a in `gl` of lane a < r); every lane ends with the same bits
+template <int NT>
+__device__ __forceinline__ double miss_residual(const float *Rk, const float (&y)[NT], double gl, int myM, int r, int lane) {
+    constexpr int Dp = 64 * NT;
+    double res[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) res[t] = (double)y[t];
+    for (int a = 0; a < r; ++a) {
+        const float *ca = Rk + (int64_t)__builtin_amdgcn_readlane(myM, a) * Dp + lane;
+        const double ta = miss_rl_d(gl, a);
+#pragma unroll
+        for (int t = 0; t < NT; ++t) res[t] -= (double)ca[64 * t] * ta;
+    }
+    double q = 0.0;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) q += res[t] * res[t];
+    return miss_wave_sum(q);
+}
+
+// M and S of score_finish_kernel from a point's (patched) column: p_k = expf(a_k - M) / S, a NaN entry counting as -Inf
+__device__ __forceinline__ void miss_column_ms(const float *col_i, int64_t stride, int K, float &mx, float &ssum) {
+    mx = -INFINITY; ssum = 0.f;
+    for (int k = 0; k < K; ++k) {
+        const float a = col_i[(int64_t)k * stride];
+        if (a == a && a > mx) mx = a;
+    }
+    for (int k = 0; k < K; ++k) {
+        float a = col_i[(int64_t)k * stride];
+        if (a != a) a = -INFINITY;
+        ssum += expf(a - mx);
+    }
+}
+__device__ __forceinline__ float miss_column_p(const float *col_i, int64_t stride, int k, float mx, float ssum) {
+    float a = col_i[(int64_t)k * stride];
+    if (a != a) a = -INFINITY;
+    return expf(a - mx) / ssum;
+}
+
 template <int NT, bool IMPUTE>
 __global__ __launch_bounds__(64 * MISS_WAVES) void miss_patch_kernel(MissArgs A) {
     __shared__ double sA[MISS_WAVES][MISS_MAX * MISS_LDA];
@@ -88,133 +231,26 @@ __global__ __launch_bounds__(64 * MISS_WAVES) void miss_patch_kernel(MissArgs A)
     const unsigned long long nw = (unsigned long long)gridDim.x * MISS_WAVES;
     for (unsigned long long e = (unsigned long long)blockIdx.x * MISS_WAVES + wave; e < total; e += nw) {
         const int64_t i = A.list[e];
-        const float *x = A.X + i * A.ldx;
         float xv[NT];
         unsigned long long nm[NT];
-        int r = 0;
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-            const int j = 64 * t + lane;
-            xv[t] = j < D ? x[j] : 0.f;
-            nm[t] = __ballot(xv[t] != xv[t]);
-            r += __popcll(nm[t]);
-        }
-        // lane a < r learns M_a, the a-th missing feature
-        int myM = 0;
-        {
-            int a = 0;
-#pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                unsigned long long mk = nm[t];
-                while (mk) {
-                    const int b = __ffsll((long long)mk) - 1;
-                    mk &= mk - 1;
-                    if (lane == a) myM = 64 * t + b;
-                    ++a;
-                }
-            }
-        }
+        int myM;
+        const int r = miss_read_point<NT>(A.X + i * A.ldx, D, lane, xv, nm, myM);
         float *const col_i = A.table + i;
         float mx = -INFINITY, ssum = 0.f;
         double acc = 0.0;
-        if constexpr (IMPUTE) {      // M and S of score_finish_kernel, from the patched column
-            for (int k = 0; k < K; ++k) {
-                const float a = col_i[(int64_t)k * A.stride];
-                if (a == a && a > mx) mx = a;
-            }
-            for (int k = 0; k < K; ++k) {
-                float a = col_i[(int64_t)k * A.stride];
-                if (a != a) a = -INFINITY;
-                ssum += expf(a - mx);
-            }
-        }
+        if constexpr (IMPUTE) miss_column_ms(col_i, A.stride, K, mx, ssum);
         for (int k = 0; k < K; ++k) {
             const float *const Rk = A.Rt + (int64_t)k * D * Dp;
             const float *const mk = A.mu + (int64_t)k * A.mu_step;
-            float z[NT], y[NT];
-#pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                const int j = 64 * t + lane;
-                const bool miss = (nm[t] >> lane) & 1ull;
-                z[t] = (j < D && !miss) ? xv[t] - mk[j] : 0.f;
-                y[t] = 0.f;
-            }
-            // ---- y = R z: column j of R scaled by z_j; rows above 64 (tj + 1) hold zeros of the triangle and are skipped
-#pragma unroll
-            for (int tj = 0; tj < NT; ++tj) {
-                const int jn = D - 64 * tj < 64 ? D - 64 * tj : 64;
-#pragma unroll 4
-                for (int jj = 0; jj < jn; ++jj) {
-                    const float zj = miss_rl_f(z[tj], jj);
-                    const float *c = Rk + (int64_t)(64 * tj + jj) * Dp + lane;
-#pragma unroll
-                    for (int tr = 0; tr <= tj; ++tr) y[tr] = fmaf(c[64 * tr], zj, y[tr]);
-                }
-            }
-            // ---- g = C'y into lane b, A = C'C (lower triangle) into the wave's LDS
-            double gl = 0.0;
-            for (int b = 0; b < r; ++b) {
-                const float *cb = Rk + (int64_t)__builtin_amdgcn_readlane(myM, b) * Dp + lane;
-                float colb[NT];
-                double p = 0.0;
-#pragma unroll
-                for (int t = 0; t < NT; ++t) { colb[t] = cb[64 * t]; p += (double)colb[t] * (double)y[t]; }
-                p = miss_wave_sum(p);
-                if (lane == b) gl = p;
-                for (int a = 0; a <= b; ++a) {
-                    const float *ca = Rk + (int64_t)__builtin_amdgcn_readlane(myM, a) * Dp + lane;
-                    double s = 0.0;
-#pragma unroll
-                    for (int t = 0; t < NT; ++t) s += (double)ca[64 * t] * (double)colb[t];
-                    s = miss_wave_sum(s);
-                    if (lane == 0) Am[b * MISS_LDA + a] = s;
-                }
-            }
-            miss_lds_fence();
-            // ---- A = L L': lane a owns row a; column j is finished by the lanes j .. r - 1 at once
-            double half_logdet = 0.0;      // sum_j log L_jj = logdet A / 2
-            for (int j = 0; j < r; ++j) {
-                const bool act = lane >= j && lane < r;
-                const int row = act ? lane : j;
-                double s = Am[row * MISS_LDA + j];
-                for (int t2 = 0; t2 < j; ++t2) s -= Am[row * MISS_LDA + t2] * Am[j * MISS_LDA + t2];
-                const double dj = sqrt(miss_rl_d(s, j));
-                half_logdet += log(dj);
-                if (act) Am[lane * MISS_LDA + j] = (lane == j) ? dj : s / dj;
-                miss_lds_fence();
-            }
-            // ---- t = A^-1 g: L u = g, then L't = u; lane a ends with t_a
-            for (int j = 0; j < r; ++j) {
-                if (lane == j) gl = gl / Am[j * MISS_LDA + j];
-                const double uj = miss_rl_d(gl, j);
-                if (lane > j && lane < r) gl -= Am[lane * MISS_LDA + j] * uj;
-            }
-            for (int j = r - 1; j >= 0; --j) {
-                if (lane == j) gl = gl / Am[j * MISS_LDA + j];
-                const double tj = miss_rl_d(gl, j);
-                if (lane < j) gl -= Am[j * MISS_LDA + lane] * tj;
-            }
+            float y[NT];
+            double gl;
+            const double half_logdet = miss_system<NT>(Rk, mk, xv, nm, myM, r, D, lane, Am, y, gl);
             miss_lds_fence();      // (the next cluster overwrites A)
             if constexpr (IMPUTE) {
-                float a = col_i[(int64_t)k * A.stride];
-                if (a != a) a = -INFINITY;
-                const float pk = expf(a - mx) / ssum;
+                const float pk = miss_column_p(col_i, A.stride, k, mx, ssum);
                 if (lane < r) acc += (double)pk * ((double)mk[myM] - gl);
             } else {
-                // ---- q_o = |y - C t|^2, the residual itself
-                double res[NT];
-#pragma unroll
-                for (int t = 0; t < NT; ++t) res[t] = (double)y[t];
-                for (int a = 0; a < r; ++a) {
-                    const float *ca = Rk + (int64_t)__builtin_amdgcn_readlane(myM, a) * Dp + lane;
-                    const double ta = miss_rl_d(gl, a);
-#pragma unroll
-                    for (int t = 0; t < NT; ++t) res[t] -= (double)ca[64 * t] * ta;
-                }
-                double q = 0.0;
-#pragma unroll
-                for (int t = 0; t < NT; ++t) q += res[t] * res[t];
-                q = miss_wave_sum(q);
+                const double q = miss_residual<NT>(Rk, y, gl, myM, r, lane);
                 const double *ck = A.cst + (int64_t)k * MISS_CST;
                 const double df = ck[0];
                 const double val = ck[r] - half_logdet - 0.5 * (df + (double)(D - r)) * log1p(q / df);
@@ -224,6 +260,85 @@ __global__ __launch_bounds__(64 * MISS_WAVES) void miss_patch_kernel(MissArgs A)
         if constexpr (IMPUTE) {
             if (lane < r) A.out[i * A.ld_out + myM] = (float)acc;
         }
+    }
+}
+
+// ---- include/dpmm_hip_impute.h: draws of the missing features.  The copy writes every draw's image of the range (the points as they are,
+// zeros in the pad, comp = -1); the draw kernel then rewrites the NaN words of the listed points, one wave per (listed point, draw).
+__global__ __launch_bounds__(256) void miss_draw_copy_kernel(MissArgs A, MissDraw W, int64_t width) {
+    const int64_t step = (int64_t)gridDim.x * 256, q0 = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t words = (int64_t)W.ndraws * A.n * width;
+    for (int64_t e = q0; e < words; e += step) {
+        const int64_t d = e % width, i = (e / width) % A.n, jd = e / (width * A.n);
+        W.out[jd * W.draw_stride + i * W.ld + d] = d < A.D ? A.X[i * A.ldx + d] : 0.f;
+    }
+    if (W.comp)
+        for (int64_t e = q0; e < (int64_t)W.ndraws * A.n; e += step) W.comp[(e / A.n) * W.comp_stride + e % A.n] = -1;
+}
+
+template <int NT>
+__global__ __launch_bounds__(64 * MISS_WAVES) void miss_draw_kernel(MissArgs A, MissDraw W) {
+    __shared__ double sA[MISS_WAVES][MISS_MAX * MISS_LDA];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    double *const Am = sA[wave];
+    const int D = A.D, K = A.K;
+    constexpr int Dp = 64 * NT;
+    const unsigned long long nd = (unsigned long long)W.ndraws;
+    const unsigned long long total = A.cnt[0] * nd;
+    const unsigned long long nw = (unsigned long long)gridDim.x * MISS_WAVES;
+    for (unsigned long long item = (unsigned long long)blockIdx.x * MISS_WAVES + wave; item < total; item += nw) {
+        const unsigned long long e = item / nd;      // (the draws of a point are neighbours: its row and its column stay in the cache)
+        const int64_t jd = (int64_t)(item - e * nd);
+        const int64_t i = A.list[e];
+        float xv[NT];
+        unsigned long long nm[NT];
+        int myM;
+        const int r = miss_read_point<NT>(A.X + i * A.ldx, D, lane, xv, nm, myM);
+        const uint64_t gi = (uint64_t)(W.i0 + i);
+        const uint32_t b0 = 64u * (uint32_t)(W.draw0 + jd);
+        // ---- the component: the cumulative sums of p_k in cluster order, inverted with one uniform
+        const float *const col_i = A.table + i;
+        float mx, ssum;
+        miss_column_ms(col_i, A.stride, K, mx, ssum);
+        const Philox4 rc = philox4x32_10(W.seed, gi, b0, STREAM_IMPUTE_COMP);
+        const double u = sample_u53(rc.v[0], rc.v[1]);
+        double cum = 0.0;
+        int k = -1, klast = 0;      // (no cluster of positive probability -- an infinite observed feature --: cluster 0)
+        for (int kk = 0; kk < K && k < 0; ++kk) {
+            const float pk = miss_column_p(col_i, A.stride, kk, mx, ssum);
+            if (!(pk > 0.f)) continue;
+            cum += (double)pk;
+            klast = kk;
+            if (u < cum) k = kk;
+        }
+        k = __builtin_amdgcn_readfirstlane(k < 0 ? klast : k);
+        // ---- that cluster's system, w = L'^-1 n and q_o
+        const float *const Rk = A.Rt + (int64_t)k * D * Dp;
+        const float *const mk = A.mu + (int64_t)k * A.mu_step;
+        float y[NT];
+        double gl;
+        miss_system<NT>(Rk, mk, xv, nm, myM, r, D, lane, Am, y, gl);
+        float nv = 0.f;
+        if (lane < r) {       // coordinate a of n: word a & 3 of block a >> 2, Box-Muller as sample_niw_kernel
+            const Philox4 rn = philox4x32_10(W.seed, gi, b0 + (uint32_t)(lane >> 2), STREAM_IMPUTE_NORMAL);
+            const bool hi = (lane & 2) != 0;
+            const float rad = sqrtf(fmaxf(-2.0f * __logf(sample_u32(hi ? rn.v[2] : rn.v[0])), 0.0f));
+            const float th = 6.2831853071795865f * sample_u32(hi ? rn.v[3] : rn.v[1]);
+            nv = rad * ((lane & 1) ? __sinf(th) : __cosf(th));
+        }
+        double wv = (double)nv;
+        for (int j = r - 1; j >= 0; --j) {
+            if (lane == j) wv = wv / Am[j * MISS_LDA + j];
+            const double wj = miss_rl_d(wv, j);
+            if (lane < j) wv -= Am[j * MISS_LDA + lane] * wj;
+        }
+        miss_lds_fence();      // (the next item overwrites A)
+        const double q = miss_residual<NT>(Rk, y, gl, myM, r, lane);
+        const double dfo = A.cst[(int64_t)k * MISS_CST] + (double)(D - r);
+        const double g = sample_chi2(dfo, W.seed, gi, STREAM_IMPUTE_CHI, b0);
+        const double sc = sqrt((A.cst[(int64_t)k * MISS_CST] + q) / g);
+        if (lane < r) W.out[jd * W.draw_stride + i * W.ld + myM] = (float)(((double)mk[myM] - gl) + sc * wv);
+        if (W.comp && lane == 0) W.comp[jd * W.comp_stride + i] = k;
     }
 }
 
@@ -259,6 +374,21 @@ hipError_t launch_miss_patch(const MissArgs &a, bool impute, int max_grid, hipSt
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((a.n + MISS_WAVES - 1) / MISS_WAVES, max_grid));
     if (impute) launch_patch_nt<true>(a, grid, s);
     else launch_patch_nt<false>(a, grid, s);
+    return hipGetLastError();
+}
+
+hipError_t launch_miss_draw(const MissArgs &a, const MissDraw &w, int max_grid, hipStream_t s) {
+    if (a.n <= 0 || w.ndraws <= 0) return hipSuccess;
+    const int64_t width = std::min<int64_t>(w.ld, w.draw_stride);
+    if (!miss_args_ok(a) || !w.out || width < a.D || w.i0 < 0 || w.draw0 < 0 || w.draw0 + w.ndraws > MISS_DRAW_MAX) return hipErrorInvalidValue;
+    const int64_t words = (int64_t)w.ndraws * a.n * width, items = (int64_t)w.ndraws * a.n;
+    DPMM_LAUNCH(miss_draw_copy_kernel, dim3((unsigned)std::min<int64_t>((words + 255) / 256, 4096)), dim3(256), 0, s, a, w, width);
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((items + MISS_WAVES - 1) / MISS_WAVES, max_grid));
+    const int nt = (a.D + 63) / 64;
+    if (nt == 1) DPMM_LAUNCH((miss_draw_kernel<1>), dim3(grid), dim3(64 * MISS_WAVES), 0, s, a, w);
+    else if (nt == 2) DPMM_LAUNCH((miss_draw_kernel<2>), dim3(grid), dim3(64 * MISS_WAVES), 0, s, a, w);
+    else if (nt == 3) DPMM_LAUNCH((miss_draw_kernel<3>), dim3(grid), dim3(64 * MISS_WAVES), 0, s, a, w);
+    else DPMM_LAUNCH((miss_draw_kernel<4>), dim3(grid), dim3(64 * MISS_WAVES), 0, s, a, w);
     return hipGetLastError();
 }
 

@@ -283,23 +283,57 @@ class Predictor:
         return Overlap(r["overlap"], r["mass"], r["count"], int(r["skipped"][0]))
 
     # ---- missing features (include/dpmm_hip_missing.h)
-    def impute(self, data):
+    def impute(self, data, draws=None, seed=0, return_components=False):
         """(D, n) float32: `data` converted to Float32 with the NaN features of every point that has 1 .. min(16, D - 1) of them replaced
         by sum_k p_k E[x_M | x_O, k] -- the conditional means of the clusters' Student-t predictives, mixed with the probabilities
         `predict` gives the point under missing="marginalize".  Everything else -- observed features, complete points, points with more NaN
         features than that -- is copied bit for bit.  NIW only; works under either `missing` setting and sets `missing_counts`.
         A numpy array for host data; for a device tensor a tensor on its device (point-major memory: the `.T` view of an (n, D) tensor),
-        written there by the library, nothing of size n crossing the host link.  Integer data has no NaN and comes back converted."""
+        written there by the library, nothing of size n crossing the host link.  Integer data has no NaN and comes back converted.
+
+        draws=m (an int >= 1): MULTIPLE IMPUTATION, (m, D, n) float32 -- m completed copies of the data, copy j with the gaps of every
+        such point DRAWN from p(x_M | x_O) under the fitted mixture (include/dpmm_hip_impute.h: a cluster k ~ p_k, then the conditional
+        Student-t of that cluster) in place of their mean; each [j] has the layout described above.  The mean is the right point estimate
+        and the wrong data set (too little variance, inflated correlations, intervals too narrow downstream): analyse the m copies
+        separately and pool.  Draw j of point i depends on (seed, i = its position in `data`, j, the point, the model) alone -- not on
+        `capacity`, not on m: the first draws of a longer run are those of a shorter one.  return_components=True: also the (m, n) int32
+        drawn clusters, 0-based, -1 for every point that was not drawn for.  The table is evaluated once per slab for all m draws."""
         if self._wk is None:
             raise RuntimeError("this Predictor is closed")
         if self.kind != _priors.PRIOR_NIW:
             raise ValueError("impute is for the NIW prior: the Multinomial prior has no missing features")
         wk = self._wk
+        if draws is not None:
+            return self._impute_draws(data, draws, seed, return_components)
+        if return_components:
+            raise ValueError("return_components is for draws=m: the mean imputation mixes all clusters")
         if not hasattr(wk, "impute_points_into"):
             raise RuntimeError("this Predictor's worker cannot impute points (no dpmm_impute_points)")
         out = self._walk(self._open(data, refuse_projected="impute"), [("impute", (self.D,), "float32")],
                          lambda views, lo, hi: wk.impute_points_into(views["impute"]), counts=True)
         return out["impute"].T
+
+    def _impute_draws(self, data, draws, seed, return_components):
+        m, seed = int(draws), int(seed)
+        if m < 1 or m != draws or m > binding.IMPUTE_MAX_DRAWS:
+            raise ValueError(f"draws must be None or an integer in 1..{binding.IMPUTE_MAX_DRAWS}")
+        if seed < 0 or seed >> 64:
+            raise ValueError("seed must be in 0..2^64 - 1")
+        wk, cap = self._wk, self.capacity
+        if not hasattr(wk, "impute_draws_into"):
+            raise RuntimeError("this Predictor's worker cannot draw missing features (no dpmm_impute_draw_points)")
+        opened = self._open(data, refuse_projected="impute")
+        n, new = opened[0], opened[2]
+        comp = new(m, (n,), "int32") if return_components else None
+        stage = new(m, (cap,), "int32") if return_components and n else None      # the ABI's comp is [m][capacity]: one slab's, then sliced in
+
+        def evaluate(views, lo, hi):
+            wk.impute_draws_into(views["draws"], seed, lo, comp=stage)             # the global index of a point is its position in `data`
+            if stage is not None:
+                comp[:, lo:hi] = stage[:, :hi - lo]
+        out = self._walk(opened, [("draws", (m, self.D), "float32")], evaluate, counts=True)["draws"]      # (n, m, D): ld = m D, draw_stride = D
+        res = out.permute(1, 2, 0) if hasattr(out, "permute") else out.transpose(1, 2, 0)
+        return (res, comp) if return_components else res
 
     # ---- drawing points (include/dpmm_hip_sample.h)
     def sampler_tables(self):
@@ -508,11 +542,11 @@ def overlap(dp_model, data, **kw):
         return p.overlap(data)
 
 
-def impute(dp_model, data, **kw):
-    """`data` with its missing (NaN) features filled in (opens a Predictor, runs, closes): see `Predictor.impute`;
-    kw: capacity, device, worker_factory, missing."""
+def impute(dp_model, data, draws=None, seed=0, return_components=False, **kw):
+    """`data` with its missing (NaN) features filled in -- or, with draws=m, m copies with the gaps drawn -- (opens a Predictor, runs,
+    closes): see `Predictor.impute`; kw: capacity, device, worker_factory, missing."""
     with Predictor(dp_model, **kw) as p:
-        return p.impute(data)
+        return p.impute(data, draws=draws, seed=seed, return_components=return_components)
 
 
 def sample(dp_model, n, seed=0, trials=None, sparse=False, **kw):
