@@ -78,6 +78,7 @@ ABI = [
     ("dpmm_last_sweep_parts_ms", ctypes.c_int, [ctypes.c_void_p, _c_f32p]),
     ("dpmm_last_kernel_ms", ctypes.c_int, [ctypes.c_void_p, _c_f32p, _c_f32p]),
     ("dpmm_debug_counters", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64), ctypes.c_int]),
+    ("dpmm_debug_sort_tables", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     ("dpmm_debug_set_prelaunch_hook", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     ("dpmm_init_labels_from", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_uint32]),
     ("dpmm_set_option", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_double]),
@@ -1110,6 +1111,14 @@ class Worker:
         a = ctypes.c_float(); b = ctypes.c_float()
         self._chk(self._lib.dpmm_last_kernel_ms(self._h, ctypes.byref(a), ctypes.byref(b)))
         return a.value, b.value
+
+    def debug_sort_tables(self):
+        """The counting sort of the last statistics pass (dpmm_debug_sort_tables): (perm[:perm_total] int32 point indices grouped by
+        bin = 2 (label - 1) + (sub - 1), bin_total (2K,), bin_start (2K + 1,))."""
+        perm = np.empty(max(self.n, 1), np.int32); tot = np.empty(2 * self.K, np.int32); start = np.empty(2 * self.K + 1, np.int32)
+        ptot = np.zeros(1, np.int32)
+        self._chk(self._lib.dpmm_debug_sort_tables(self._h, perm.ctypes.data, tot.ctypes.data, start.ctypes.data, ptot.ctypes.data))
+        return perm[:int(ptot[0])].copy(), tot, start
 
     def debug_counters(self):
         """Health counters of the worker (include/dpmm_hip.h dpmm_debug_counters): [0] = event waits that returned early."""

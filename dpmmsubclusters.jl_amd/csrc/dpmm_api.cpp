@@ -2079,6 +2079,18 @@ int dpmm_debug_counters(dpmm_ctx *c, int64_t *out, int n) {
     return DPMM_OK;
 }
 
+int dpmm_debug_sort_tables(dpmm_ctx *c, int32_t *perm, int32_t *bin_total, int32_t *bin_start, int32_t *perm_total) {
+    if (!c || !perm || !bin_total || !bin_start || !perm_total) return DPMM_EINVAL;
+    if (!c->have_perm || c->K < 1) return fail(c, DPMM_ESTATE, "no statistics pass has sorted the points yet");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(perm, c->sb.perm, sizeof(int32_t) * (size_t)c->n, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(bin_total, c->sb.bin_total, sizeof(int32_t) * 2 * (size_t)c->K, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(bin_start, c->sb.bin_start, sizeof(int32_t) * (2 * (size_t)c->K + 1), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(perm_total, c->sb.perm_total, sizeof(int32_t), hipMemcpyDeviceToHost));
+    return DPMM_OK;
+}
+
 int dpmm_step_master_device(dpmm_ctx *c, uint32_t reset_epoch, const int32_t *slots, uint32_t draw_epoch, const uint8_t **bad, const double **small) {
     if (!c || !slots || !bad || !small) return DPMM_EINVAL;
     if (!c->master) return fail(c, DPMM_ESTATE, "dpmm_niw_master_setup first");

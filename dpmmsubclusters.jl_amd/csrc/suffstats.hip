@@ -47,6 +47,37 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // re-draw of those points, counts the result into `tile_spec` (written for such (tile, cluster) pairs only) and notes each point's new bin (`spec_bins`).  The scan
 // then reads tile_spec for flagged clusters and tile_cnt for the rest, and the scatter stores spec_bins for the points of flagged clusters and places them by it
 // (scatter_kernel<.., STEP>, RESET): same labels, same permutation as histogram -> reset_recount -> scan.
+// The four values every lane holds of one 256-point chunk of a sort tile, counted into the LDS counters `cnt` (values outside [0, nbins) are
+// not counted).  The first two distinct values of the wave -- in point order a chunk is ONE cluster with its two sub-labels mixed -- cost four
+// compares + scalar popcounts each and one LDS addition by one lane; the second value comes through v_readlane (no LDS round trip: the
+// leader-by-leader loop this replaces went twice through ds_bpermute per value, and with five waves per SIMD resident the launch was bound by
+// that arithmetic, not by memory).  Whatever else the chunk holds (labels in no particular storage order) goes through the atomics.
+// Call with the whole wave; the order of the values does not matter.
+__device__ __forceinline__ void count_chunk(int x, int y, int z, int w, int *cnt, int nbins, int lane) {
+    const int b0 = __builtin_amdgcn_readfirstlane(x);
+    const bool ex = x == b0, ey = y == b0, ez = z == b0, ew = w == b0;
+    const int c0 = __popcll(__ballot(ex)) + __popcll(__ballot(ey)) + __popcll(__ballot(ez)) + __popcll(__ballot(ew));
+    if (c0 == 256) {                                     // (wave-uniform)
+        if (lane == 0 && (unsigned)b0 < (unsigned)nbins) atomicAdd(&cnt[b0], 256);
+        return;
+    }
+    const int o = !ex ? x : !ey ? y : !ez ? z : w;       // the lane's first value that is not b0
+    const unsigned long long has = __ballot(!(ex && ey && ez && ew));
+    const int b1 = __builtin_amdgcn_readlane(o, __ffsll((long long)has) - 1);
+    const bool fx = x == b1, fy = y == b1, fz = z == b1, fw = w == b1;
+    const int c1 = __popcll(__ballot(fx)) + __popcll(__ballot(fy)) + __popcll(__ballot(fz)) + __popcll(__ballot(fw));
+    if (lane == 0) {
+        if ((unsigned)b0 < (unsigned)nbins) atomicAdd(&cnt[b0], c0);
+        if ((unsigned)b1 < (unsigned)nbins) atomicAdd(&cnt[b1], c1);
+    }
+    if (c0 + c1 != 256) {
+        if (!ex && !fx && (unsigned)x < (unsigned)nbins) atomicAdd(&cnt[x], 1);
+        if (!ey && !fy && (unsigned)y < (unsigned)nbins) atomicAdd(&cnt[y], 1);
+        if (!ez && !fz && (unsigned)z < (unsigned)nbins) atomicAdd(&cnt[z], 1);
+        if (!ew && !fw && (unsigned)w < (unsigned)nbins) atomicAdd(&cnt[w], 1);
+    }
+}
+
 template <int TILE, int W, bool SPEC>
 __global__ __launch_bounds__(64 * W) void hist_kernel(const int32_t *__restrict__ bins, int64_t n, int nbins, int nt,
                                                       int32_t *__restrict__ tile_hist, int32_t *__restrict__ fast_total,
@@ -59,7 +90,17 @@ __global__ __launch_bounds__(64 * W) void hist_kernel(const int32_t *__restrict_
     for (int b = lane; b < nbins; b += 64) cnt[b] = 0;
     __syncthreads();
     const int64_t base = (int64_t)tile * TILE;
-    int4 v[TILE / 256];                      // (a full tile's labels stay in registers for the SPEC phase)
+    // A lane holds four consecutive labels of every 256-point chunk of its tile, element e of v[it] being point base + 4 (64 it + lane) + e (they
+    // stay in registers for the SPEC phase): 16-byte loads of the labels and 8-byte loads of prev_lab, every one of them issued before the first
+    // is used.  The ragged last tile runs the same code: a vector that is not wholly below n is loaded from the tile's last whole vector instead
+    // and masked afterwards, and the up to three points behind the last whole vector go to lanes 0..2 of one more slot (`tv`).  (That tile used to
+    // walk its points with a load under `if (i < n)` per trip, each waiting for the one before it: one wave's 32 dependent round trips.)
+    const int nv = (int)min((int64_t)(TILE / 4), (n - base) >> 2);              // whole vectors of this tile (<= 0: tile >= nt)
+    const int64_t rbase = base + 4 * (int64_t)nv;                                 // first point behind them
+    const bool rem = nv < TILE / 4 && rbase + lane < n;                           // (lanes 0..2 at most)
+    auto pidx = [&](int it, int e) -> int64_t { return base + (int64_t)(it * 64 + lane) * 4 + e; };
+    int4 v[TILE / 256];
+    int tv = -1;
 #pragma unroll
     for (int it = 0; it < TILE / 256; ++it) v[it] = make_int4(-1, -1, -1, -1);
     if (tile < nt) {
@@ -74,78 +115,48 @@ __global__ __launch_bounds__(64 * W) void hist_kernel(const int32_t *__restrict_
             prev_lab[i] = (uint16_t)z;
         }
     };
-    if (base + TILE <= n) {
-        // full tile: 16-byte loads, all of them in flight before the first is used; 256 points with one common bin (the usual case
-        // after an ordered sweep: neighbours share a label) cost one LDS add instead of 256 same-address atomics
+    const int64_t ri = min(rbase + lane, n - 1);     // (clamped: lanes without a remainder point load the shard's last label and drop it)
+    if (nv > 0) {
         const int4 *src = reinterpret_cast<const int4 *>(bins + base);
 #pragma unroll
-        for (int it = 0; it < TILE / 256; ++it) v[it] = src[it * 64 + lane];
-        if (prev_lab) {
-            // four 16-bit labels per lane and trip, all loads in flight with the bins'; ONE wave-level test for the whole tile (nothing
-            // moved: the usual case) in front of the per-point bookkeeping
+        for (int it = 0; it < TILE / 256; ++it) v[it] = src[min(it * 64 + lane, nv - 1)];
+    }
+    if (nv < TILE / 4) tv = bins[ri];               // (wave-uniform: the ragged tile only)
+    unsigned diff = 0u;                      // some label of this lane may differ from prev_lab (the exact test is track's)
+    if (prev_lab) {
+        // ONE wave-level test for the whole tile (nothing moved: the usual case) in front of the per-point bookkeeping
+        uint2 pv[TILE / 256];
+        if (nv > 0) {
             const uint2 *psrc = reinterpret_cast<const uint2 *>(prev_lab + base);
-            uint2 pv[TILE / 256];
 #pragma unroll
-            for (int it = 0; it < TILE / 256; ++it) pv[it] = psrc[it * 64 + lane];
-            unsigned diff = 0u;
+            for (int it = 0; it < TILE / 256; ++it) pv[it] = psrc[min(it * 64 + lane, nv - 1)];
+        }
+        unsigned tp = 0u;
+        if (nv < TILE / 4) tp = prev_lab[ri];
+        if (nv > 0) {
 #pragma unroll
             for (int it = 0; it < TILE / 256; ++it) {
                 const unsigned a0 = (unsigned)v[it].x >> 1, a1 = (unsigned)v[it].y >> 1, a2 = (unsigned)v[it].z >> 1, a3 = (unsigned)v[it].w >> 1;
-                diff |= (pv[it].x ^ (a0 | (a1 << 16))) | (pv[it].y ^ (a2 | (a3 << 16)));
-            }
-            if (__any(diff != 0u)) {
-#pragma unroll
-                for (int it = 0; it < TILE / 256; ++it) {
-                    const int64_t i0 = base + (int64_t)(it * 64 + lane) * 4;
-                    track(i0, v[it].x); track(i0 + 1, v[it].y); track(i0 + 2, v[it].z); track(i0 + 3, v[it].w);
-                }
+                if (it * 64 + lane < nv) diff |= (pv[it].x ^ (a0 | (a1 << 16))) | (pv[it].y ^ (a2 | (a3 << 16)));
             }
         }
-#pragma unroll
-        for (int it = 0; it < TILE / 256; ++it) {
-            const int b0 = __builtin_amdgcn_readfirstlane(v[it].x);
-            const bool same = v[it].x == b0 && v[it].y == b0 && v[it].z == b0 && v[it].w == b0;
-            if (__all(same)) {
-                if (lane == 0 && (unsigned)b0 < (unsigned)nbins) cnt[b0] += 256;
-            } else {
-                // the usual case in point order is ONE cluster with its two sub-labels mixed: 256 atomics on two LDS addresses
-                // serialise (the kernel spent 3/4 of its time there).  Count the first few distinct values of the wave with ballots
-                // (a value costs four ballots and one LDS add), whatever is left goes through the atomics.
-                const int vals[4] = {v[it].x, v[it].y, v[it].z, v[it].w};
-                unsigned todo = 0xFu;                                   // per lane: components not yet counted
-                for (int round = 0; round < 4; ++round) {
-                    const unsigned long long any = __ballot(todo != 0u);
-                    if (!any) break;
-                    const int leader = __ffsll((long long)any) - 1;
-                    const unsigned tl = (unsigned)__shfl((int)todo, leader);
-                    const int comp = __ffs((int)tl) - 1;
-                    const int lv = comp == 0 ? vals[0] : comp == 1 ? vals[1] : comp == 2 ? vals[2] : vals[3];
-                    const int bv = __shfl(lv, leader);
-                    int c = 0;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const bool hit = ((todo >> e) & 1u) && vals[e] == bv;
-                        c += __popcll(__ballot(hit));
-                        if (hit) todo &= ~(1u << e);
-                    }
-                    if (lane == 0 && (unsigned)bv < (unsigned)nbins) cnt[bv] += c;
-                    if (c < 32) break;                                  // many different values (unsorted labels): the atomics are cheaper
-                }
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    if (((todo >> e) & 1u) && (unsigned)vals[e] < (unsigned)nbins) atomicAdd(&cnt[vals[e]], 1);
-            }
-        }
-    } else {
-        for (int it = 0; it < TILE / 64; ++it) {
-            const int64_t i = base + it * 64 + lane;
-            if (i < n) {
-                const int b = bins[i];
-                if ((unsigned)b < (unsigned)nbins) atomicAdd(&cnt[b], 1);
-                if (prev_lab) track(i, b);
-            }
-        }
+        if (rem) diff |= ((unsigned)tv >> 1) ^ tp;
     }
+#pragma unroll
+    for (int it = 0; it < TILE / 256; ++it)
+        if (it * 64 + lane >= nv) v[it] = make_int4(-1, -1, -1, -1);
+    if (!rem) tv = -1;
+    if (prev_lab && __any(diff != 0u)) {
+#pragma unroll
+        for (int it = 0; it < TILE / 256; ++it)
+            if (it * 64 + lane < nv) { track(pidx(it, 0), v[it].x); track(pidx(it, 1), v[it].y); track(pidx(it, 2), v[it].z); track(pidx(it, 3), v[it].w); }
+        if (rem) track(rbase + lane, tv);
+    }
+    // 256 points with one common bin (the usual case after an ordered sweep: neighbours share a label) cost one LDS addition, one cluster with
+    // its two sub-labels mixed costs two
+#pragma unroll
+    for (int it = 0; it < TILE / 256; ++it) count_chunk(v[it].x, v[it].y, v[it].z, v[it].w, cnt, nbins, lane);
+    if (nv < TILE / 4) count_chunk(tv, -1, -1, -1, cnt, nbins, lane);          // (wave-uniform)
     }
     __syncthreads();
     if (tile < nt)
@@ -153,7 +164,6 @@ __global__ __launch_bounds__(64 * W) void hist_kernel(const int32_t *__restrict_
     if constexpr (SPEC) {
         if (tile_spec && tile < nt) {                  // (wave-uniform; everything below is wave-local: this wave's counters, no workgroup barrier)
             int *const spc = cnt_all + (W + wave) * nbins;
-            const bool full = base + TILE <= n;
             auto onesided = [&](int bv) -> bool {
                 if ((unsigned)bv >= (unsigned)nbins) return false;
                 const int z2 = bv & ~1;
@@ -173,15 +183,11 @@ __global__ __launch_bounds__(64 * W) void hist_kernel(const int32_t *__restrict_
                     spec_bins[i] = nb;                      // (what the scatter stores and places by if the cluster is flagged: no second draw there)
                     atomicAdd(&spc[nb], 1);
                 };
-                if (full) {
 #pragma unroll
-                    for (int it = 0; it < TILE / 256; ++it) {
-                        const int64_t i0 = base + (int64_t)(it * 64 + lane) * 4;
-                        redraw(i0, v[it].x); redraw(i0 + 1, v[it].y); redraw(i0 + 2, v[it].z); redraw(i0 + 3, v[it].w);
-                    }
-                } else {
-                    for (int it = 0; it < TILE / 64; ++it) { const int64_t i = base + it * 64 + lane; if (i < n) redraw(i, bins[i]); }
+                for (int it = 0; it < TILE / 256; ++it) {          // (a masked element of the ragged tile is -1: in no cluster)
+                    redraw(pidx(it, 0), v[it].x); redraw(pidx(it, 1), v[it].y); redraw(pidx(it, 2), v[it].z); redraw(pidx(it, 3), v[it].w);
                 }
+                redraw(rbase + lane, tv);
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier();
             }
             if (some)          // (only the one-sided clusters' entries are ever read: scan_tiles_step_kernel)
@@ -258,8 +264,11 @@ __global__ __launch_bounds__(TILE / 8) void reset_recount_kernel(int32_t *__rest
 #pragma unroll
         for (int it = 0; it < PER; ++it) {
             const int64_t i = base + it * NT + tid;
-            v[it] = i < n ? bins[i] : -1;
+            v[it] = bins[i < n ? i : n - 1];       // (clamped, masked below: no load waits for a branch)
         }
+#pragma unroll
+        for (int it = 0; it < PER; ++it)
+            if (base + it * NT + tid >= n) v[it] = -1;
     }
 #pragma unroll
     for (int it = 0; it < PER; ++it) {
@@ -278,9 +287,12 @@ __global__ __launch_bounds__(TILE / 8) void reset_recount_kernel(int32_t *__rest
             const Philox4 r = philox4x32_10(seed, (uint64_t)(first + i), epoch, STREAM_RESET);
             bv = 2 * z + (int)(r.v[0] & 1u);
             bins[i] = bv;
+            v[it] = bv;
         }
-        if ((unsigned)bv < (unsigned)nbins) atomicAdd(&cnt[bv], 1);
     }
+    // the re-count: per wave and value one LDS addition (a tile of ONE flagged cluster ended in 2048 additions to two addresses)
+    count_chunk(v[0], v[1], v[2], v[3], cnt, nbins, tid & 63);
+    count_chunk(v[4], v[5], v[6], v[7], cnt, nbins, tid & 63);
     __syncthreads();
     for (int b = tid; b < nbins; b += NT) tile_cnt[(int64_t)b * nt + blockIdx.x] = cnt[b];
 }

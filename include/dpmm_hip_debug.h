@@ -74,6 +74,10 @@ int dpmm_last_comm_ms(dpmm_ctx *ctx, float *counts_ms, float *rows_ms);
  *   out[0] = dpmm_step_master_device calls whose event wait returned before the posteriors' records had reached host memory (the call
  *            then waits them out; a non-zero count is a runtime / driver anomaly worth reporting, the results are unaffected). */
 int dpmm_debug_counters(dpmm_ctx *ctx, int64_t *out, int n);
+/* The counting sort of the last statistics pass, copied to the host (synchronises the stream; tests/test_gpu_sort_shapes.py):
+ * perm[n_local] (the points grouped by bin = 2 (label - 1) + (sub - 1), ascending point index inside a bin; the first *perm_total entries
+ * are valid), bin_total[2K], bin_start[2K + 1].  DPMM_ESTATE before the first pass. */
+int dpmm_debug_sort_tables(dpmm_ctx *ctx, int32_t *perm, int32_t *bin_total, int32_t *bin_start, int32_t *perm_total);
 /* Test hook, process-wide: fn(arg) is called on the host in front of every kernel launch of the library (fn == NULL: off, the default).
  * tests/tools/poison.py uses it to refill LDS and the register files with a NaN pattern between the library's own kernels
  * (tests/test_gpu_uninit.py); fn may synchronise the device and launch kernels of its own on other streams. */
