@@ -11,6 +11,7 @@
 #include "../../include/dpmm_hip_score.h"
 #include "../../include/dpmm_hip_rank.h"
 #include "../../include/dpmm_hip_overlap.h"
+#include "../../include/dpmm_hip_batchstats.h"
 #include "../../include/dpmm_hip_trace.h"
 #include "../../include/dpmm_hip_missing.h"
 #include "../../include/dpmm_hip_impute.h"
@@ -143,6 +144,14 @@ struct dpmm_ctx {
     bool ov_active = false;
     int ov_K = 0;
     unsigned long long ov_gen = 0;      // pred_gen at dpmm_overlap_begin
+    // batch statistics (include/dpmm_hip_batchstats.h): N | sums | S | counters; two floats per point of one range; the chunk partials
+    DevBuf<double> d_bs_acc;
+    DevBuf<float2> d_bs_ms;
+    DevBuf<double> d_bs_part;
+    bool bs_active = false;
+    int bs_K = 0, bs_mode = 0, bs_floor = 0;
+    float bs_min_logdens = 0.f;
+    unsigned long long bs_gen = 0;      // pred_gen at dpmm_batchstats_begin
     // label trace (include/dpmm_hip_trace.h): slots rows of trace_nvec 16-byte vectors of ids; K per slot (0: never recorded); the device
     // images of a call's tables, descriptors, ratio tables and confidence
     DevBuf<uint16_t> d_trace;
@@ -4061,6 +4070,121 @@ int dpmm_overlap_read(dpmm_ctx *c, const dpmm_overlap_out *o) {
         for (int r = 0; r < RANK_REPL; ++r) v += cnt[(size_t)r * (size_t)(K + 1) + (size_t)k];
         if (k < K) { if (o->count) o->count[k] = (int64_t)v; }
         else if (o->skipped) o->skipped[0] = (int64_t)v;
+    }
+    return DPMM_OK;
+}
+
+// ---- include/dpmm_hip_batchstats.h: per-cluster sufficient statistics of a batch, sum_i w_ik (1, x_i, x_i x_i') (batchstats.hip) -----------
+static size_t batchstats_acc_doubles(int K, int D) { return (size_t)K * ((size_t)D * (size_t)D + (size_t)D + 1); }
+static size_t batchstats_count_words(int K) { return (size_t)RANK_REPL * (size_t)(K + BATCHSTATS_COUNTERS); }
+// doubles of the chunk partials of a range of at most `len` points: blocks | rows of sums | weights (the offsets of the three parts)
+static size_t batchstats_part_doubles(int64_t len, int K, int D, size_t *off_s, size_t *off_n) {
+    const int nb = (D + 63) / 64, npairs = nb * (nb + 1) / 2;
+    int kg = 0, nchunk = 0;
+    int64_t chunk = 0;
+    batchstats_chunks(len, K, D, &kg, &nchunk, &chunk);
+    const size_t most = (size_t)std::max(1, BATCHSTATS_PARTIAL_BLOCKS / (kg * npairs));
+    const size_t ck = std::min<size_t>(most, (size_t)std::max<int64_t>(1, (len + 2047) / 2048)) * (size_t)kg;      // (chunks, cluster) at most
+    if (off_s) *off_s = ck * (size_t)npairs * 4096;
+    if (off_n) *off_n = ck * (size_t)npairs * 4096 + ck * (size_t)nb * 64;
+    return ck * ((size_t)npairs * 4096 + (size_t)nb * 64 + 1);
+}
+
+int dpmm_batchstats_begin(dpmm_ctx *c, int mode, int use_floor, float min_logdens) {
+    static const char *fn = "dpmm_batchstats_begin";
+    if (!c) return tensor_no_ctx(fn);
+    const std::string who = std::string(fn) + ": ";
+    if (c->prior != DPMM_PRIOR_NIW) return fail(c, DPMM_EINVAL, who + "the statistics are those of the NIW prior; the sparse and byte point stores of the Multinomial prior are a separate piece of work");
+    if (mode != DPMM_BATCHSTATS_HARD && mode != DPMM_BATCHSTATS_SOFT) return fail(c, DPMM_EINVAL, who + "mode must be DPMM_BATCHSTATS_HARD or DPMM_BATCHSTATS_SOFT");
+    if (!c->predictive) return fail(c, DPMM_ESTATE, who + "needs dpmm_set_predictive_niw first");
+    HIPCHK(c, hipSetDevice(c->device));
+    c->bs_active = false;
+    const int K = c->K, D = c->D;
+    const size_t state = sizeof(double) * batchstats_acc_doubles(K, D) + sizeof(unsigned long long) * batchstats_count_words(K);
+    if (int rc = grow(c, c->d_bs_acc, state, "dpmm_score_points", "accumulators of dpmm_batchstats_begin")) return rc;
+    if (c->n > 0) {      // one range's floats and partials: sized as dpmm_batchstats_accumulate will find them unless the table budget changes in between
+        int rstep = 0;
+        int64_t P = 0;
+        if (int rc = score_table_slab(c, &rstep, &P)) return rc;
+        if (int rc = grow(c, c->d_bs_ms, sizeof(float2) * (size_t)P, "dpmm_score_points", "maxima and sums of dpmm_batchstats_begin")) return rc;
+        const size_t part = sizeof(double) * batchstats_part_doubles(std::min<int64_t>(P, c->n), K, D, nullptr, nullptr);
+        if (int rc = grow(c, c->d_bs_part, part, "dpmm_score_points", "chunk partials of dpmm_batchstats_begin")) return rc;
+    }
+    HIPCHK(c, hipMemsetAsync(c->d_bs_acc, 0, state, c->stream));
+    c->bs_K = K; c->bs_gen = c->pred_gen; c->bs_mode = mode; c->bs_floor = use_floor ? 1 : 0; c->bs_min_logdens = min_logdens;
+    c->bs_active = true;
+    return DPMM_OK;
+}
+
+int dpmm_batchstats_accumulate(dpmm_ctx *c, int64_t n_valid) {
+    static const char *fn = "dpmm_batchstats_accumulate";
+    if (!c) return tensor_no_ctx(fn);
+    c->miss_counted = false;      // (as score_points)
+    const std::string who = std::string(fn) + ": ";
+    if (!c->bs_active) return fail(c, DPMM_ESTATE, who + "needs dpmm_batchstats_begin first");
+    if (!c->predictive || c->K != c->bs_K || c->pred_gen != c->bs_gen) return fail(c, DPMM_ESTATE, who + "the predictive parameters changed since dpmm_batchstats_begin");
+    if (n_valid < 0 || n_valid > c->n) return fail(c, DPMM_EINVAL, who + "n_valid must be in 0..n_local");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (n_valid == 0) return DPMM_OK;
+    if (!c->have_points || !c->have_params || !c->dX) return fail(c, DPMM_ESTATE, who + "needs points and parameters");
+    int rstep = 0;
+    int64_t P = 0;
+    if (int rc = score_table_slab(c, &rstep, &P)) return rc;
+    if (P >> 31) return fail(c, DPMM_EINVAL, who + "a range of the table must hold fewer than 2^31 points: lower DPMM_OPT_SCORE_TABLE_MB");
+    const int K = c->K, D = c->D;
+    size_t off_s = 0, off_n = 0;
+    const size_t part = sizeof(double) * batchstats_part_doubles(std::min<int64_t>(P, c->n), K, D, &off_s, &off_n);
+    if (int rc = grow(c, c->d_bs_ms, sizeof(float2) * (size_t)P, "dpmm_score_points", "maxima and sums of dpmm_batchstats_accumulate")) return rc;
+    if (int rc = grow(c, c->d_bs_part, part, "dpmm_score_points", "chunk partials of dpmm_batchstats_accumulate")) return rc;
+    const bool miss = c->opt_score_missing != 0;
+    if (int rc = miss_begin(c, miss, P, fn)) return rc;
+    for (int64_t p0 = 0; p0 < n_valid; p0 += P) {
+        const int64_t np = std::min<int64_t>(P, c->n - p0);              // the range dpmm_score_points evaluates
+        if (int rc = run_sweep(c, 0, 0, c->d_score_table, P, p0, np)) return rc;
+        if (miss) if (int rc = miss_range(c, P, p0, np, nullptr, 0, fn)) return rc;
+        BatchStatsArgs a{};
+        a.table = c->d_score_table; a.stride = P; a.rstep = rstep; a.n = std::min<int64_t>(np, n_valid - p0); a.K = K; a.D = D; a.nb = (D + 63) / 64;
+        a.X = c->dX + p0 * c->ldx; a.ldx = c->ldx;
+        a.soft = c->bs_mode == DPMM_BATCHSTATS_SOFT; a.use_floor = c->bs_floor; a.min_logdens = c->bs_min_logdens;
+        batchstats_chunks(a.n, K, D, &a.kgroup, &a.nchunk, &a.chunk);
+        if ((size_t)a.nchunk * (size_t)std::min(a.kgroup, K) * (size_t)(a.nb * (a.nb + 1) / 2) * 4096 > off_s)
+            return fail(c, DPMM_EHIP, who + "internal: more chunks than the partial buffer holds");
+        a.ms = c->d_bs_ms;
+        a.acc = c->d_bs_acc;
+        a.count = reinterpret_cast<unsigned long long *>(c->d_bs_acc + batchstats_acc_doubles(K, D));
+        a.part = c->d_bs_part;
+        a.spart = c->d_bs_part + off_s;
+        a.npart = c->d_bs_part + off_n;
+        hipError_t e = launch_batchstats_range(a, c->stream);
+        if (e != hipSuccess) { c->err = who + hipGetErrorString(e); return DPMM_EHIP; }
+    }
+    return DPMM_OK;
+}
+
+int dpmm_batchstats_read(dpmm_ctx *c, const dpmm_batchstats_out *o) {
+    static const char *fn = "dpmm_batchstats_read";
+    if (!c) return tensor_no_ctx(fn);
+    const std::string who = std::string(fn) + ": ";
+    if (!o) return fail(c, DPMM_EINVAL, who + "out is null");
+    if (!c->bs_active) return fail(c, DPMM_ESTATE, who + "needs dpmm_batchstats_begin first");
+    HIPCHK(c, hipSetDevice(c->device));
+    const int K = c->bs_K;
+    const size_t D = (size_t)c->D, Kz = (size_t)K;
+    std::vector<unsigned long long> cnt(batchstats_count_words(K));
+    hipError_t e = sync_stream(c, c->stream);
+    if (e == hipSuccess && o->N) e = hipMemcpy(o->N, c->d_bs_acc, sizeof(double) * Kz, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && o->sums) e = hipMemcpy(o->sums, c->d_bs_acc + Kz, sizeof(double) * Kz * D, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && o->S) e = hipMemcpy(o->S, c->d_bs_acc + Kz + Kz * D, sizeof(double) * Kz * D * D, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && (o->count || o->skipped || o->incomplete || o->held_out))
+        e = hipMemcpy(cnt.data(), c->d_bs_acc + batchstats_acc_doubles(K, (int)D), sizeof(unsigned long long) * cnt.size(), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) { c->err = who + hipGetErrorString(e); return DPMM_EHIP; }
+    for (int k = 0; k < K + BATCHSTATS_COUNTERS; ++k) {
+        unsigned long long v = 0;
+        for (int r = 0; r < RANK_REPL; ++r) v += cnt[(size_t)r * (size_t)(K + BATCHSTATS_COUNTERS) + (size_t)k];
+        if (k < K) { if (o->count) o->count[k] = (int64_t)v; }
+        else if (k == K) { if (o->skipped) o->skipped[0] = (int64_t)v; }
+        else if (k == K + 1) { if (o->held_out) o->held_out[0] = (int64_t)v; }
+        else if (o->incomplete) o->incomplete[0] = (int64_t)v;
     }
     return DPMM_OK;
 }

@@ -231,6 +231,35 @@ struct OverlapArgs {
 };
 void overlap_chunks(int64_t n, int K, int *nchunk, int64_t *chunk);
 hipError_t launch_overlap_range(const OverlapArgs &a, hipStream_t s);
+// ---- per-cluster batch statistics (batchstats.hip; include/dpmm_hip_batchstats.h): one range of the score table, n points from table
+// column 0 and from X, added to the ctx's accumulators
+constexpr int BATCHSTATS_PARTIAL_BLOCKS = 2048;  // DPMM_BATCHSTATS_PARTIAL_BLOCKS: 64 x 64 blocks of chunk partials at most
+constexpr int BATCHSTATS_COUNTERS = 3;           // behind count[K]: skipped | held out | incomplete
+struct BatchStatsArgs {
+    const float *table;
+    int64_t stride;      // floats between two rows of the table
+    int rstep;           // cluster k is row k * rstep
+    int64_t n;           // points of the range that are accumulated, below 2^31
+    int K, D;
+    const float *X;      // [n][ldx], the range's first point
+    int64_t ldx;
+    int soft;            // 0: w_ik = [label_i == k + 1], 1: w_ik = p_ik
+    int use_floor;       // points with logdens < min_logdens are held out
+    float min_logdens;
+    int nb;              // blocks of 64 features, (D + 63) / 64
+    int kgroup;          // clusters per contraction launch (batchstats_chunks)
+    int nchunk;          // chunks of the range (batchstats_chunks)
+    int64_t chunk;       // points per chunk, a multiple of 64
+    int k0, kcount;      // the clusters of one contraction / reduce launch (set by launch_batchstats_range)
+    float2 *ms;                     // [n] soft: (M, S) of the point; hard: (label, 1); y = 0: it takes no part
+    unsigned long long *count;      // [RANK_REPL][K + BATCHSTATS_COUNTERS]
+    double *part;                   // [nchunk][kcount][nb (nb + 1) / 2][64][64] partial blocks of the lower block triangle
+    double *spart;                  // [nchunk][kcount][nb * 64] partial sums
+    double *npart;                  // [nchunk][kcount] partial weights
+    double *acc;                    // [K] N | [K][D] sums | [K][D][D] S
+};
+void batchstats_chunks(int64_t n, int K, int D, int *kgroup, int *nchunk, int64_t *chunk);
+hipError_t launch_batchstats_range(const BatchStatsArgs &a, hipStream_t s);
 // ---- missing features (missing.hip; include/dpmm_hip_missing.h): one range of the score table, n points from table column 0 and from X
 constexpr int MISS_MAX = 16;              // DPMM_SCORE_MAX_MISSING
 constexpr int MISS_CST = MISS_MAX + 2;    // doubles per cluster in MissArgs::cst

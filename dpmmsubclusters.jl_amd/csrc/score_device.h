@@ -26,4 +26,7 @@ __device__ __forceinline__ float score_e(float a, float m) {
 // the probability probs holds
 __device__ __forceinline__ float score_p(float e, float s) { return e / s; }
 
+// the value logdens holds: the statement of score_finish_kernel's pass 2, for kernels that compare it with a floor (batchstats.hip)
+__device__ __forceinline__ float score_logdens(float m, float s) { return (m == -INFINITY) ? -INFINITY : m + logf(s); }
+
 }  // namespace dpmm

@@ -1,0 +1,54 @@
+"""Folding a batch into a served NIW model: the conjugate update from per-cluster sufficient statistics, on the host in Float64.
+
+The NIW prior is conjugate, so the posterior a `Predictor` carries -- kappa, nu, m and U with nu psi = U U' per cluster -- is the exact
+prior of the next batch.  Given the batch's N_k = sum_i w_ik, sums_k = sum_i w_ik x_i and S_k = sum_i w_ik x_i x_i'
+(`Predictor.statistics`, include/dpmm_hip_batchstats.h), for every cluster with N_k > 0:
+
+    kappa' = kappa + N        nu' = nu + N        m' = (kappa m + sums) / kappa'
+    U' U'^T = nu' psi' = U U^T + S + kappa m m^T - kappa' m' m'^T
+
+-- priors/niw.jl:20-31 with the cluster's own posterior in the prior's place -- factorised as `niw_hyperparams.posterior` does (the
+reverse Cholesky of host/csrc/hostmath.h, U upper triangular), logdet_psi recomputed.  The arithmetic is the library's own
+(`native.niw_posterior`), called with Float64 kappa and nu: `niw_hyperparams.__init__` rounds both to Float32, as the reference does for
+a prior the user types in, which would lose the fractional N of soft weights -- so that constructor is not on this route.
+"""
+import numpy as np
+
+from . import native
+
+POST_KEYS = ("kappa", "nu", "m", "U", "logdet_psi")
+
+
+def niw_absorb(post, points_count, stats):
+    """(post', points_count'): the posterior arrays of K clusters (`Predictor.post`: kappa, nu, logdet_psi (K,), m (K, D), U (K, D, D))
+    and their point counts after the conjugate update with `stats` -- anything with N (K,), sums (K, D), S (K, D, D), e.g. a
+    `BatchStatistics`.  Everything in Float64; the inputs are not modified.  A cluster with N_k == 0 keeps its bits.  ValueError for
+    shapes that do not fit, a negative or non-finite N, non-finite sums or S, and for an update that is not positive definite."""
+    missing = [k for k in POST_KEYS[:4] if k not in post]
+    if missing:
+        raise ValueError(f"niw_absorb is for NIW posteriors: post lacks {missing}")
+    new = {k: np.array(post[k], np.float64 if k in POST_KEYS else None) for k in post}
+    if "logdet_psi" not in new and new["U"].ndim == 3 and new["U"].shape[1:] == new["m"].shape[1:] * 2:      # (a model file written without it)
+        new["logdet_psi"] = 2 * np.log(np.einsum("kii->ki", new["U"])).sum(1) - new["m"].shape[1] * np.log(new["nu"])
+    K, D = new["m"].shape if new["m"].ndim == 2 else (0, 0)
+    if new["m"].ndim != 2 or K < 1 or new["U"].shape != (K, D, D) or any(new[k].shape != (K,) for k in ("kappa", "nu", "logdet_psi")):
+        raise ValueError("post must hold kappa, nu, logdet_psi (K,), m (K, D) and U (K, D, D)")
+    count = np.array(points_count, np.float64)
+    if count.shape != (K,):
+        raise ValueError("points_count must have one entry per cluster")
+    N, sums, S = (np.asarray(getattr(stats, f) if hasattr(stats, f) else stats[f], np.float64) for f in ("N", "sums", "S"))
+    if N.shape != (K,) or sums.shape != (K, D) or S.shape != (K, D, D):
+        raise ValueError(f"the statistics must be N ({K},), sums ({K}, {D}) and S ({K}, {D}, {D})")
+    if not np.isfinite(N).all() or (N < 0).any():
+        raise ValueError("N must be finite and non-negative")
+    if not (np.isfinite(sums).all() and np.isfinite(S).all()):
+        raise ValueError("sums and S must be finite")
+    for k in np.flatnonzero(N > 0):
+        U, nu = new["U"][k], float(new["nu"][k])
+        kap1, nu1, m1, _, U1, ld1 = native.niw_posterior(float(new["kappa"][k]), nu, new["m"][k], (U @ U.T) / nu, N[k:k + 1], sums[k:k + 1], S[k:k + 1],
+                                                         nthreads=1)
+        if not np.isfinite(ld1[0]):
+            raise ValueError(f"the update of cluster {k + 1} is not positive definite")
+        new["kappa"][k], new["nu"][k], new["m"][k], new["U"][k], new["logdet_psi"][k] = kap1[0], nu1[0], m1[0], U1[0], ld1[0]
+        count[k] += N[k]
+    return new, count

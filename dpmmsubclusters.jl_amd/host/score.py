@@ -27,6 +27,8 @@ from . import points as _points
 from . import priors as _priors
 from . import tensors as _tensors      # noqa: F401  (the recognisers of host/points.py, reachable from here: tests patch them under this name)
 from . import project as _project
+from . import absorb as _absorb
+from .absorb import niw_absorb      # noqa: F401
 
 
 Exemplars = collections.namedtuple("Exemplars", "typical_idx typical_score fringe_idx fringe_score count skipped")
@@ -36,6 +38,13 @@ for is None -- count (K,) and skipped, an int."""
 Overlap = collections.namedtuple("Overlap", "matrix mass count skipped")
 Overlap.__doc__ = """What `Predictor.overlap` returns: matrix (K, K) float64, O[k][j] = sum_i p_ik p_ij; mass (K,) float64, sum_i p_ik; count (K,)
 int64, the points labelled k + 1; skipped, an int -- numpy arrays always."""
+
+BatchStatistics = collections.namedtuple("BatchStatistics", "N sums S count skipped incomplete held_out")
+BatchStatistics.__doc__ = """What `Predictor.statistics` returns and `Predictor.absorb` folds in: N (K,), sums (K, D), S (K, D, D) float64 -- sum_i w_ik,
+sum_i w_ik x_i, sum_i w_ik x_i x_i' over the points that take part; count (K,) int64, those of them labelled k + 1; skipped, incomplete,
+held_out, ints, the points that took no part -- numpy arrays always."""
+
+ASSIGN_MODES = {"hard": binding.BATCHSTATS_HARD, "soft": binding.BATCHSTATS_SOFT}
 
 
 class _Capture:
@@ -143,14 +152,10 @@ class Predictor:
         self.device = 0 if idx is None else int(idx)
         w = self.points_count + self.alpha                                   # weights as predict forms them
         self.weights = (w / w.sum()).astype(np.float32)
-        prior = (_priors.niw_hyperparams(1.0, np.zeros(self.D), self.D + 3.0, np.eye(self.D)) if self.kind == _priors.PRIOR_NIW
-                 else _priors.multinomial_hyper(np.ones(self.D)))
-        cap = _Capture()
-        prior.predictive_table(cap, self.post, list(range(self.K)), self.weights)
+        which, args = self._predictive_args()
         factory = worker_factory or binding.Worker
         self._wk = factory(self.kind, self.D, self.capacity, first_index=0, device=self.device, seed=0)
         try:
-            which, args = cap.args
             (self._wk.set_predictive_niw if which == "niw" else self._wk.set_predictive_mult)(*args)      # ONCE
             if projection is not None:
                 projection.apply(self._wk)                                                                # ... as well
@@ -166,6 +171,14 @@ class Predictor:
         self._csc_stage = None           # capacity + 1 offsets on the device, for the short slab of a sparse_csc tensor
         self._out_stage = {}             # outputs of a short slab: name -> array / tensor of `capacity` rows
         self._sampler_set = False        # the sampler's tables are formed and uploaded by the first sample()
+
+    def _predictive_args(self):
+        """("niw" | "mult", the arguments of the worker's set_predictive_*) for `self.post` and `self.weights`."""
+        prior = (_priors.niw_hyperparams(1.0, np.zeros(self.D), self.D + 3.0, np.eye(self.D)) if self.kind == _priors.PRIOR_NIW
+                 else _priors.multinomial_hyper(np.ones(self.D)))
+        cap = _Capture()
+        prior.predictive_table(cap, self.post, list(range(self.K)), self.weights)
+        return cap.args
 
     # ---- life
     def close(self):
@@ -281,6 +294,60 @@ class Predictor:
         self._walk(opened, [], lambda views, lo, hi: wk.overlap_accumulate(hi - lo))
         r = wk.overlap_read()
         return Overlap(r["overlap"], r["mass"], r["count"], int(r["skipped"][0]))
+
+    # ---- batch statistics and the conjugate update (include/dpmm_hip_batchstats.h, host/absorb.py)
+    def statistics(self, data, assign="hard", min_logdens=None):
+        """The per-cluster sufficient statistics of `data` under the model: a `BatchStatistics` tuple, accumulated on the GPU in Float64.
+
+          N[k]      sum_i w_ik          sums[k]   sum_i w_ik x_i          S[k]   sum_i w_ik x_i x_i', symmetric bit for bit
+        with w_ik = 1 for the cluster `predict_labels` gives the point (assign="hard": N == count) or the probability `predict` gives
+        (assign="soft"), over the points that TAKE PART.  Every point is counted in exactly one of
+          skipped      its row of the table holds a NaN or no finite entry (as `overlap` skips it);
+          held_out     min_logdens is given and `score_samples` of the point lies below it: an outlier is not folded into a cluster;
+          incomplete   a feature is not finite -- under missing="marginalize" a point with gaps is labelled, yet its moments are unknown;
+          count[k]     it takes part and `predict_labels` labels it k + 1.
+        x_i is the point as the model sees it: Float32, and with a projection its projected coordinates.  Every entry lies within
+        2 gamma(n + 2) sum_i w_ik |x_id| |x_ie| of any other Float64 evaluation, whatever `capacity` is (include/dpmm_hip_batchstats.h);
+        the counters are exact.  NIW only.  `data` is what `predict` takes; the arrays are numpy arrays (K D^2 numbers), nothing of
+        size n is allocated or copied to the host."""
+        if self._wk is None:
+            raise RuntimeError("this Predictor is closed")
+        if self.kind != _priors.PRIOR_NIW:
+            raise ValueError("statistics are for the NIW prior: the sparse and byte point stores of the Multinomial prior are a separate piece of work")
+        if assign not in ASSIGN_MODES:
+            raise ValueError('assign must be "hard" or "soft"')
+        if min_logdens is not None:
+            min_logdens = float(min_logdens)
+            if min_logdens != min_logdens:
+                raise ValueError("min_logdens must not be NaN")
+        wk = self._wk
+        if not hasattr(wk, "batchstats_begin"):
+            raise RuntimeError("this Predictor's worker cannot accumulate batch statistics (no dpmm_batchstats_begin)")
+        opened = self._open(data)
+        wk.batchstats_begin(ASSIGN_MODES[assign], min_logdens)
+        self._walk(opened, [], lambda views, lo, hi: wk.batchstats_accumulate(hi - lo))
+        r = wk.batchstats_read()
+        return BatchStatistics(r["N"], r["sums"], r["S"], r["count"], int(r["skipped"][0]), int(r["incomplete"][0]), int(r["held_out"][0]))
+
+    def absorb(self, data, assign="hard", min_logdens=None):
+        """Folds `data` into the model and returns the `BatchStatistics` it absorbed (see `statistics` for the arguments).
+
+        The NIW prior is conjugate: the posterior this Predictor carries is the exact prior of the batch, and `niw_absorb` updates every
+        cluster that received weight -- kappa, nu, m, U, logdet_psi -- and `points_count`, hence the mixture weights.  The predictive
+        parameters are then reloaded into the same worker, once, so every later call and `save` see the updated model; an accumulation
+        begun before (`overlap`, `exemplars` pieces at the binding level) is refused afterwards.  Statistics with N.sum() == 0 change
+        nothing.  No new cluster is created: points far from every cluster are either absorbed by the nearest one or, with
+        `min_logdens`, held out and counted."""
+        stats = self.statistics(data, assign=assign, min_logdens=min_logdens)
+        if not stats.N.sum() > 0:
+            return stats
+        self.post, self.points_count = _absorb.niw_absorb(self.post, self.points_count, stats)
+        w = self.points_count + self.alpha
+        self.weights = (w / w.sum()).astype(np.float32)
+        which, args = self._predictive_args()
+        self._wk.set_predictive_niw(*args)
+        self._sampler_set = False            # the sampler's tables are those of the old posterior
+        return stats
 
     # ---- missing features (include/dpmm_hip_missing.h)
     def impute(self, data, draws=None, seed=0, return_components=False):
@@ -540,6 +607,14 @@ def overlap(dp_model, data, **kw):
     kw: capacity, device, worker_factory, missing."""
     with Predictor(dp_model, **kw) as p:
         return p.overlap(data)
+
+
+def statistics(dp_model, data, **kw):
+    """The per-cluster sufficient statistics of `data` under the model (opens a Predictor, runs, closes): see `Predictor.statistics`;
+    kw: assign, min_logdens, capacity, device, worker_factory, missing."""
+    assign, min_logdens = kw.pop("assign", "hard"), kw.pop("min_logdens", None)
+    with Predictor(dp_model, **kw) as p:
+        return p.statistics(data, assign=assign, min_logdens=min_logdens)
 
 
 def impute(dp_model, data, draws=None, seed=0, return_components=False, **kw):
