@@ -179,6 +179,21 @@ ABI_BATCHSTATS = [
 ]
 BATCHSTATS_HARD, BATCHSTATS_SOFT = 0, 1    # DPMM_BATCHSTATS_HARD, DPMM_BATCHSTATS_SOFT
 BATCHSTATS_PARTIAL_BLOCKS = 2048           # DPMM_BATCHSTATS_PARTIAL_BLOCKS
+
+
+class CountStatsOut(ctypes.Structure):
+    """dpmm_countstats_out (include/dpmm_hip_countstats.h): host addresses, 0 / None = not asked for."""
+    _fields_ = [("N", ctypes.c_void_p), ("sums", ctypes.c_void_p), ("count", ctypes.c_void_p), ("skipped", ctypes.c_void_p),
+                ("incomplete", ctypes.c_void_p), ("held_out", ctypes.c_void_p)]
+
+
+# include/dpmm_hip_countstats.h: per-cluster count statistics of a batch under the served Multinomial model (additive; bound next to ABI)
+ABI_COUNTSTATS = [
+    ("dpmm_countstats_begin", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_float]),
+    ("dpmm_countstats_accumulate", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64]),
+    ("dpmm_countstats_read", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(CountStatsOut)]),
+]
+COUNTSTATS_PARTIAL_BYTES = 64 << 20        # DPMM_COUNTSTATS_PARTIAL_BYTES
 # include/dpmm_hip_trace.h: label samples kept on the GPU, their pairwise contingency tables and the per-point confidence (additive)
 ABI_TRACE = [
     ("dpmm_trace_open", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
@@ -292,7 +307,7 @@ def load_library():
         except Exception:  # pragma: no cover  (torch is optional for single-GPU use)
             pass
         lib = ctypes.CDLL(p)
-        for name, res, args in ABI + ABI_TENSOR + ABI_SCORE + ABI_RANK + ABI_OVERLAP + ABI_BATCHSTATS + ABI_TRACE + ABI_MISSING + ABI_IMPUTE + ABI_CSC + ABI_SAMPLE + ABI_PROJECT:
+        for name, res, args in ABI + ABI_TENSOR + ABI_SCORE + ABI_RANK + ABI_OVERLAP + ABI_BATCHSTATS + ABI_COUNTSTATS + ABI_TRACE + ABI_MISSING + ABI_IMPUTE + ABI_CSC + ABI_SAMPLE + ABI_PROJECT:
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -809,6 +824,36 @@ class Worker:
         res = dict(N=np.empty(K, np.float64), sums=np.empty((K, D), np.float64), S=np.empty((K, D, D), np.float64), count=np.empty(K, np.int64),
                    skipped=np.empty(1, np.int64), incomplete=np.empty(1, np.int64), held_out=np.empty(1, np.int64))
         self.batchstats_read_raw(**{k: v.ctypes.data for k, v in res.items()})
+        return res
+
+    # ---- count statistics of the Multinomial prior (include/dpmm_hip_countstats.h)
+    def countstats_begin(self, mode=BATCHSTATS_HARD, min_logdens=None):
+        """dpmm_countstats_begin: a new accumulation of N, sums and the counters with the weights of `mode`; min_logdens: None, or the
+        floor below which a point is held out."""
+        floor = min_logdens is not None
+        self._chk(self._lib.dpmm_countstats_begin(self._h, int(mode), int(floor), float(min_logdens) if floor else 0.0))
+        self._countstats_K = self.K
+
+    def countstats_accumulate(self, n_valid):
+        """dpmm_countstats_accumulate: adds the points 0..n_valid-1 of the current upload, whichever store they are in."""
+        self._chk(self._lib.dpmm_countstats_accumulate(self._h, int(n_valid)))
+
+    def countstats_read_raw(self, N=0, sums=0, count=0, skipped=0, incomplete=0, held_out=0):
+        """dpmm_countstats_read on plain host addresses (integers; 0 = not asked for)."""
+        out = CountStatsOut(N or None, sums or None, count or None, skipped or None, incomplete or None, held_out or None)
+        self._chk(self._lib.dpmm_countstats_read(self._h, ctypes.byref(out)))
+
+    def countstats_read(self):
+        """The sums as they stand: a dict of numpy arrays, `N` (K,), `sums` (K, D) float64, `count` (K,) int64 and `skipped`,
+        `incomplete`, `held_out` (1,) int64."""
+        K = getattr(self, "_countstats_K", None)
+        if K is None:
+            self.countstats_read_raw()         # (DPMM_ESTATE: no dpmm_countstats_begin yet)
+            raise RuntimeError("countstats_read needs countstats_begin first")
+        D = self.D
+        res = dict(N=np.empty(K, np.float64), sums=np.empty((K, D), np.float64), count=np.empty(K, np.int64),
+                   skipped=np.empty(1, np.int64), incomplete=np.empty(1, np.int64), held_out=np.empty(1, np.int64))
+        self.countstats_read_raw(**{k: v.ctypes.data for k, v in res.items()})
         return res
 
     # ---- label trace (include/dpmm_hip_trace.h)

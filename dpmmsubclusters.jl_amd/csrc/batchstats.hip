@@ -31,6 +31,7 @@
 #include "dpmm_device.h"
 #include "dpmm_kernels.h"
 #include "score_device.h"
+#include "batchstats_device.h"
 
 namespace dpmm {
 
@@ -40,8 +41,6 @@ constexpr int BS_THREADS = 256;
 constexpr int BS_PITCH = 80;             // words per staged point: 64 features, = 16 (mod 64)
 constexpr int BS_RING = 512;             // slots of the ring: at most 63 points left over + 256 new ones
 constexpr int BS_CHUNK_MIN = 2048;       // points per chunk at least (unless the range is shorter)
-
-__device__ __forceinline__ bool bs_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
 
 __global__ __launch_bounds__(BS_THREADS) void batchstats_prep_kernel(BatchStatsArgs A) {
     __shared__ unsigned cnt[DPMM_MAX_CLUSTERS_K + BATCHSTATS_COUNTERS];
@@ -66,12 +65,10 @@ __global__ __launch_bounds__(BS_THREADS) void batchstats_prep_kernel(BatchStatsA
         const int64_t i = base + tid;
         const bool valid = i < A.n;
         const float *col = A.table + (valid ? i : 0);      // (lanes past the end read point 0 and contribute nothing)
-        float m = -INFINITY;
-        int best = 0;
-        bool nan_seen = false;
-        for (int k = 0; k < K; ++k) score_max_step(col[(int64_t)k * rs], k, m, best, nan_seen);
-        float s = 0.f;
-        for (int k = 0; k < K; ++k) s += score_e(col[(int64_t)k * rs], m);
+        float m, s;
+        int best;
+        bool nan_seen;
+        bs_table_passes(col, rs, K, m, best, nan_seen, s);
         __syncthreads();
         // ---- the class: skipped, else held out, else incomplete, else it takes part
         const bool scored = valid && !nan_seen && m > -INFINITY && m < INFINITY;
@@ -80,27 +77,10 @@ __global__ __launch_bounds__(BS_THREADS) void batchstats_prep_kernel(BatchStatsA
         const bool part = scored && !held && !incomplete;
         if (valid) A.ms[i] = !part ? make_float2(0.f, 0.f) : A.soft ? make_float2(m, s) : make_float2((float)best, 1.f);
         // ---- the counters (as overlap_prep_kernel)
-        const unsigned long long pm = __ballot(part);
-        if (pm) {
-            const int first = __ffsll((long long)pm) - 1;
-            const int k0 = __shfl(best, first);
-            if (__ballot(part && best != k0) == 0) {
-                if (lane == first) atomicAdd(&cnt[k0], (unsigned)__popcll(pm));
-            } else if (part) {
-                atomicAdd(&cnt[best], 1u);
-            }
-        }
-        const unsigned long long sm = __ballot(valid && !scored), hm = __ballot(held), im = __ballot(incomplete);
-        if (lane == 0) {
-            if (sm) atomicAdd(&cnt[K], (unsigned)__popcll(sm));
-            if (hm) atomicAdd(&cnt[K + 1], (unsigned)__popcll(hm));
-            if (im) atomicAdd(&cnt[K + 2], (unsigned)__popcll(im));
-        }
+        bs_count(cnt, K, lane, valid, scored, held, incomplete, part, best);
     }
     __syncthreads();
-    unsigned long long *count = A.count + (int64_t)(blockIdx.x % RANK_REPL) * (K + BATCHSTATS_COUNTERS);
-    for (int k = tid; k < K + BATCHSTATS_COUNTERS; k += BS_THREADS)
-        if (cnt[k]) atomicAdd(&count[k], (unsigned long long)cnt[k]);
+    bs_flush(cnt, A.count, K, tid, BS_THREADS);
 }
 
 // pair p of the lower block triangle, p = ba (ba + 1) / 2 + bb, ba >= bb

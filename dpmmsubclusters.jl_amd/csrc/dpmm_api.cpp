@@ -12,6 +12,7 @@
 #include "../../include/dpmm_hip_rank.h"
 #include "../../include/dpmm_hip_overlap.h"
 #include "../../include/dpmm_hip_batchstats.h"
+#include "../../include/dpmm_hip_countstats.h"
 #include "../../include/dpmm_hip_trace.h"
 #include "../../include/dpmm_hip_missing.h"
 #include "../../include/dpmm_hip_impute.h"
@@ -152,6 +153,14 @@ struct dpmm_ctx {
     int bs_K = 0, bs_mode = 0, bs_floor = 0;
     float bs_min_logdens = 0.f;
     unsigned long long bs_gen = 0;      // pred_gen at dpmm_batchstats_begin
+    // count statistics (include/dpmm_hip_countstats.h): N | sums | counters; two floats per point of one range; the chunk partials
+    DevBuf<double> d_cs_acc;
+    DevBuf<float2> d_cs_ms;
+    DevBuf<double> d_cs_part;
+    bool cs_active = false;
+    int cs_K = 0, cs_mode = 0, cs_floor = 0;
+    float cs_min_logdens = 0.f;
+    unsigned long long cs_gen = 0;      // pred_gen at dpmm_countstats_begin
     // label trace (include/dpmm_hip_trace.h): slots rows of trace_nvec 16-byte vectors of ids; K per slot (0: never recorded); the device
     // images of a call's tables, descriptors, ratio tables and confidence
     DevBuf<uint16_t> d_trace;
@@ -4094,7 +4103,7 @@ int dpmm_batchstats_begin(dpmm_ctx *c, int mode, int use_floor, float min_logden
     static const char *fn = "dpmm_batchstats_begin";
     if (!c) return tensor_no_ctx(fn);
     const std::string who = std::string(fn) + ": ";
-    if (c->prior != DPMM_PRIOR_NIW) return fail(c, DPMM_EINVAL, who + "the statistics are those of the NIW prior; the sparse and byte point stores of the Multinomial prior are a separate piece of work");
+    if (c->prior != DPMM_PRIOR_NIW) return fail(c, DPMM_EINVAL, who + "the statistics are those of the NIW prior; a Multinomial ctx has dpmm_countstats_begin / _accumulate / _read (include/dpmm_hip_countstats.h)");
     if (mode != DPMM_BATCHSTATS_HARD && mode != DPMM_BATCHSTATS_SOFT) return fail(c, DPMM_EINVAL, who + "mode must be DPMM_BATCHSTATS_HARD or DPMM_BATCHSTATS_SOFT");
     if (!c->predictive) return fail(c, DPMM_ESTATE, who + "needs dpmm_set_predictive_niw first");
     HIPCHK(c, hipSetDevice(c->device));
@@ -4177,6 +4186,115 @@ int dpmm_batchstats_read(dpmm_ctx *c, const dpmm_batchstats_out *o) {
     if (e == hipSuccess && o->S) e = hipMemcpy(o->S, c->d_bs_acc + Kz + Kz * D, sizeof(double) * Kz * D * D, hipMemcpyDeviceToHost);
     if (e == hipSuccess && (o->count || o->skipped || o->incomplete || o->held_out))
         e = hipMemcpy(cnt.data(), c->d_bs_acc + batchstats_acc_doubles(K, (int)D), sizeof(unsigned long long) * cnt.size(), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) { c->err = who + hipGetErrorString(e); return DPMM_EHIP; }
+    for (int k = 0; k < K + BATCHSTATS_COUNTERS; ++k) {
+        unsigned long long v = 0;
+        for (int r = 0; r < RANK_REPL; ++r) v += cnt[(size_t)r * (size_t)(K + BATCHSTATS_COUNTERS) + (size_t)k];
+        if (k < K) { if (o->count) o->count[k] = (int64_t)v; }
+        else if (k == K) { if (o->skipped) o->skipped[0] = (int64_t)v; }
+        else if (k == K + 1) { if (o->held_out) o->held_out[0] = (int64_t)v; }
+        else if (o->incomplete) o->incomplete[0] = (int64_t)v;
+    }
+    return DPMM_OK;
+}
+
+// ---- include/dpmm_hip_countstats.h: per-cluster count statistics of a batch under the Multinomial model, sum_i w_ik (1, x_i) (countstats.hip)
+static size_t countstats_acc_doubles(int K, int D) { return (size_t)K * ((size_t)D + 1); }
+// doubles of the chunk partials of a range of at most `len` points: rows of dp doubles | one weight per row
+static size_t countstats_part_doubles(const dpmm_ctx *c, int64_t len) {
+    int kg = 0, nchunk = 0;
+    int64_t chunk = 0, dp = 0;
+    countstats_chunks(len, c->K, c->D, c->x_sparse ? 1 : 0, &kg, &nchunk, &chunk, &dp);
+    return (size_t)nchunk * (size_t)kg * ((size_t)dp + 1);
+}
+
+int dpmm_countstats_begin(dpmm_ctx *c, int mode, int use_floor, float min_logdens) {
+    static const char *fn = "dpmm_countstats_begin";
+    if (!c) return tensor_no_ctx(fn);
+    const std::string who = std::string(fn) + ": ";
+    if (c->prior != DPMM_PRIOR_MULT) return fail(c, DPMM_EINVAL, who + "the count statistics are those of the Multinomial prior; an NIW ctx has dpmm_batchstats_begin (include/dpmm_hip_batchstats.h)");
+    if (mode != DPMM_BATCHSTATS_HARD && mode != DPMM_BATCHSTATS_SOFT) return fail(c, DPMM_EINVAL, who + "mode must be DPMM_BATCHSTATS_HARD or DPMM_BATCHSTATS_SOFT");
+    if (!c->predictive) return fail(c, DPMM_ESTATE, who + "needs dpmm_set_predictive_mult first");
+    HIPCHK(c, hipSetDevice(c->device));
+    c->cs_active = false;
+    const int K = c->K, D = c->D;
+    const size_t state = sizeof(double) * countstats_acc_doubles(K, D) + sizeof(unsigned long long) * batchstats_count_words(K);
+    if (int rc = grow(c, c->d_cs_acc, state, "dpmm_score_points", "accumulators of dpmm_countstats_begin")) return rc;
+    if (c->n > 0) {      // one range's floats and partials: sized as dpmm_countstats_accumulate will find them unless the table budget or the store changes in between
+        int rstep = 0;
+        int64_t P = 0;
+        if (int rc = score_table_slab(c, &rstep, &P)) return rc;
+        if (int rc = grow(c, c->d_cs_ms, sizeof(float2) * (size_t)P, "dpmm_score_points", "maxima and sums of dpmm_countstats_begin")) return rc;
+        const size_t part = sizeof(double) * countstats_part_doubles(c, std::min<int64_t>(P, c->n));
+        if (int rc = grow(c, c->d_cs_part, part, "dpmm_score_points", "chunk partials of dpmm_countstats_begin")) return rc;
+    }
+    HIPCHK(c, hipMemsetAsync(c->d_cs_acc, 0, state, c->stream));
+    c->cs_K = K; c->cs_gen = c->pred_gen; c->cs_mode = mode; c->cs_floor = use_floor ? 1 : 0; c->cs_min_logdens = min_logdens;
+    c->cs_active = true;
+    return DPMM_OK;
+}
+
+int dpmm_countstats_accumulate(dpmm_ctx *c, int64_t n_valid) {
+    static const char *fn = "dpmm_countstats_accumulate";
+    if (!c) return tensor_no_ctx(fn);
+    c->miss_counted = false;      // (as score_points)
+    const std::string who = std::string(fn) + ": ";
+    if (!c->cs_active) return fail(c, DPMM_ESTATE, who + "needs dpmm_countstats_begin first");
+    if (!c->predictive || c->K != c->cs_K || c->pred_gen != c->cs_gen) return fail(c, DPMM_ESTATE, who + "the predictive parameters changed since dpmm_countstats_begin");
+    if (n_valid < 0 || n_valid > c->n) return fail(c, DPMM_EINVAL, who + "n_valid must be in 0..n_local");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (n_valid == 0) return DPMM_OK;
+    const int store = c->x_sparse ? COUNTSTATS_SPARSE : c->x_u8 ? COUNTSTATS_U8 : COUNTSTATS_F32;
+    const bool have = store == COUNTSTATS_SPARSE ? (bool)c->d_cp : store == COUNTSTATS_U8 ? (bool)c->dX8 : (bool)c->dX;
+    if (!c->have_points || !c->have_params || !have) return fail(c, DPMM_ESTATE, who + "needs points and parameters");
+    if (store == COUNTSTATS_SPARSE && c->nnz > 0 && (!c->d_ri || !c->d_val)) return fail(c, DPMM_ESTATE, who + "needs points and parameters");
+    int rstep = 0;
+    int64_t P = 0;
+    if (int rc = score_table_slab(c, &rstep, &P)) return rc;
+    if (P >> 31) return fail(c, DPMM_EINVAL, who + "a range of the table must hold fewer than 2^31 points: lower DPMM_OPT_SCORE_TABLE_MB");
+    const int K = c->K, D = c->D;
+    const size_t part = sizeof(double) * countstats_part_doubles(c, std::min<int64_t>(P, c->n));
+    if (int rc = grow(c, c->d_cs_ms, sizeof(float2) * (size_t)P, "dpmm_score_points", "maxima and sums of dpmm_countstats_accumulate")) return rc;
+    if (int rc = grow(c, c->d_cs_part, part, "dpmm_score_points", "chunk partials of dpmm_countstats_accumulate")) return rc;
+    for (int64_t p0 = 0; p0 < n_valid; p0 += P) {
+        const int64_t np = std::min<int64_t>(P, c->n - p0);              // the range dpmm_score_points evaluates
+        if (int rc = run_sweep(c, 0, 0, c->d_score_table, P, p0, np)) return rc;
+        CountStatsArgs a{};
+        a.table = c->d_score_table; a.stride = P; a.rstep = rstep; a.n = std::min<int64_t>(np, n_valid - p0); a.K = K; a.D = D;
+        a.store = store;
+        if (store == COUNTSTATS_SPARSE) { a.cp = c->d_cp + p0; a.ri = c->d_ri; a.val = c->d_val; }
+        else if (store == COUNTSTATS_U8) { a.X8 = c->dX8 + p0 * c->ld8; a.ld8 = c->ld8; }
+        else { a.X = c->dX + p0 * c->ldx; a.ldx = c->ldx; }
+        a.soft = c->cs_mode == DPMM_BATCHSTATS_SOFT; a.use_floor = c->cs_floor; a.min_logdens = c->cs_min_logdens;
+        countstats_chunks(a.n, K, D, store == COUNTSTATS_SPARSE, &a.kgroup, &a.nchunk, &a.chunk, &a.dp);
+        if (sizeof(double) * (size_t)a.nchunk * (size_t)a.kgroup * ((size_t)a.dp + 1) > part)
+            return fail(c, DPMM_EHIP, who + "internal: more chunks than the partial buffer holds");
+        a.ms = c->d_cs_ms;
+        a.acc = c->d_cs_acc;
+        a.count = reinterpret_cast<unsigned long long *>(c->d_cs_acc + countstats_acc_doubles(K, D));
+        a.part = c->d_cs_part;
+        a.npart = c->d_cs_part + (size_t)a.nchunk * (size_t)a.kgroup * (size_t)a.dp;
+        hipError_t e = launch_countstats_range(a, c->stream);
+        if (e != hipSuccess) { c->err = who + hipGetErrorString(e); return DPMM_EHIP; }
+    }
+    return DPMM_OK;
+}
+
+int dpmm_countstats_read(dpmm_ctx *c, const dpmm_countstats_out *o) {
+    static const char *fn = "dpmm_countstats_read";
+    if (!c) return tensor_no_ctx(fn);
+    const std::string who = std::string(fn) + ": ";
+    if (!o) return fail(c, DPMM_EINVAL, who + "out is null");
+    if (!c->cs_active) return fail(c, DPMM_ESTATE, who + "needs dpmm_countstats_begin first");
+    HIPCHK(c, hipSetDevice(c->device));
+    const int K = c->cs_K;
+    const size_t D = (size_t)c->D, Kz = (size_t)K;
+    std::vector<unsigned long long> cnt(batchstats_count_words(K));
+    hipError_t e = sync_stream(c, c->stream);
+    if (e == hipSuccess && o->N) e = hipMemcpy(o->N, c->d_cs_acc, sizeof(double) * Kz, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && o->sums) e = hipMemcpy(o->sums, c->d_cs_acc + Kz, sizeof(double) * Kz * D, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && (o->count || o->skipped || o->incomplete || o->held_out))
+        e = hipMemcpy(cnt.data(), c->d_cs_acc + countstats_acc_doubles(K, (int)D), sizeof(unsigned long long) * cnt.size(), hipMemcpyDeviceToHost);
     if (e != hipSuccess) { c->err = who + hipGetErrorString(e); return DPMM_EHIP; }
     for (int k = 0; k < K + BATCHSTATS_COUNTERS; ++k) {
         unsigned long long v = 0;

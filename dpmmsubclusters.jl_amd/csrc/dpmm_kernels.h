@@ -260,6 +260,40 @@ struct BatchStatsArgs {
 };
 void batchstats_chunks(int64_t n, int K, int D, int *kgroup, int *nchunk, int64_t *chunk);
 hipError_t launch_batchstats_range(const BatchStatsArgs &a, hipStream_t s);
+// ---- per-cluster count statistics of the Multinomial prior (countstats.hip; include/dpmm_hip_countstats.h): one range of the score table,
+// n points from table column 0 and from whichever point store is live, added to the ctx's accumulators
+constexpr int64_t COUNTSTATS_PARTIAL_BYTES = (int64_t)64 << 20;      // DPMM_COUNTSTATS_PARTIAL_BYTES: the chunk partials at most
+constexpr int COUNTSTATS_F32 = 0, COUNTSTATS_U8 = 1, COUNTSTATS_SPARSE = 2;
+struct CountStatsArgs {
+    const float *table;
+    int64_t stride;      // floats between two rows of the table
+    int rstep;           // cluster k is row k * rstep
+    int64_t n;           // points of the range that are accumulated, below 2^31
+    int K, D;
+    int store;           // COUNTSTATS_F32: X [n][ldx]; _U8: X8 [n][ld8]; _SPARSE: cp / ri / val (cp at the range's first point)
+    const float *X;
+    int64_t ldx;
+    const uint8_t *X8;
+    int64_t ld8;
+    const int64_t *cp;
+    const uint16_t *ri;
+    const float *val;
+    int soft;            // 0: w_ik = [label_i == k + 1], 1: w_ik = p_ik
+    int use_floor;       // points with logdens < min_logdens are held out
+    float min_logdens;
+    int kgroup;          // clusters per contraction launch (countstats_chunks): a multiple of 16 for the dense stores
+    int nchunk;          // chunks of the range (countstats_chunks)
+    int64_t chunk;       // points per chunk, a multiple of 64
+    int64_t dp;          // doubles per cluster row of the partials, >= D (countstats_chunks)
+    int k0, kcount, krows;   // the clusters of one contraction / reduce launch and the rows their partials have (set by launch_countstats_range)
+    float2 *ms;                     // [n] soft: (M, S) of the point; hard: (label, 1); y = 0: it takes no part
+    unsigned long long *count;      // [RANK_REPL][K + BATCHSTATS_COUNTERS]
+    double *part;                   // [nchunk][krows][dp] partial sums
+    double *npart;                  // [nchunk][krows] partial weights
+    double *acc;                    // [K] N | [K][D] sums
+};
+void countstats_chunks(int64_t n, int K, int D, int sparse, int *kgroup, int *nchunk, int64_t *chunk, int64_t *dp);
+hipError_t launch_countstats_range(const CountStatsArgs &a, hipStream_t s);
 // ---- missing features (missing.hip; include/dpmm_hip_missing.h): one range of the score table, n points from table column 0 and from X
 constexpr int MISS_MAX = 16;              // DPMM_SCORE_MAX_MISSING
 constexpr int MISS_CST = MISS_MAX + 2;    // doubles per cluster in MissArgs::cst

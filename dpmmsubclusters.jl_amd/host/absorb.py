@@ -11,6 +11,13 @@ prior of the next batch.  Given the batch's N_k = sum_i w_ik, sums_k = sum_i w_i
 reverse Cholesky of host/csrc/hostmath.h, U upper triangular), logdet_psi recomputed.  The arithmetic is the library's own
 (`native.niw_posterior`), called with Float64 kappa and nu: `niw_hyperparams.__init__` rounds both to Float32, as the reference does for
 a prior the user types in, which would lose the fractional N of soft weights -- so that constructor is not on this route.
+
+The Dirichlet prior of the Multinomial is conjugate too, and its update is a sum: alpha' = alpha + sums (priors/multinomial_prior.jl:16-21
+with the cluster's own posterior in the prior's place), from `Predictor.count_statistics` (include/dpmm_hip_countstats.h).
+`dirichlet_absorb` keeps alpha' in Float64.  The reference stores Float32, and `multinomial_hyper.posterior` rounds to it, as is right for
+one fit; a served cluster whose alpha has grown to 1e6 would lose a soft weight of 0.01 at every batch (the spacing of Float32 there is
+0.0625) -- the reasoning of the note on kappa and nu above.  `predictive_table` widens alpha to Float64 anyway, and `save` / `load` keep
+the type the array has.
 """
 import numpy as np
 
@@ -51,4 +58,35 @@ def niw_absorb(post, points_count, stats):
             raise ValueError(f"the update of cluster {k + 1} is not positive definite")
         new["kappa"][k], new["nu"][k], new["m"][k], new["U"][k], new["logdet_psi"][k] = kap1[0], nu1[0], m1[0], U1[0], ld1[0]
         count[k] += N[k]
+    return new, count
+
+
+def dirichlet_absorb(post, points_count, stats):
+    """(post', points_count'): the posterior of K Multinomial clusters (`Predictor.post`: alpha (K, D)) and their point counts after the
+    conjugate update alpha' = alpha + sums with `stats` -- anything with N (K,) and sums (K, D), e.g. a `CountStatistics`.  Everything in
+    Float64, so the alpha returned is Float64 whatever it was; the inputs are not modified.  A cluster with N_k == 0 keeps its values.
+    ValueError for a posterior that is not a Multinomial one, shapes that do not fit, a negative or non-finite N, and non-finite or
+    negative sums."""
+    if "alpha" not in post:
+        raise ValueError(f"dirichlet_absorb is for posteriors of the Multinomial prior: post lacks 'alpha' (it holds {sorted(post)})")
+    new = {k: np.array(post[k], np.float64 if k == "alpha" else None) for k in post}
+    alpha = new["alpha"]
+    if alpha.ndim != 2 or alpha.shape[0] < 1:
+        raise ValueError("post must hold alpha (K, D)")
+    K, D = alpha.shape
+    count = np.array(points_count, np.float64)
+    if count.shape != (K,):
+        raise ValueError("points_count must have one entry per cluster")
+    N, sums = (np.asarray(getattr(stats, f) if hasattr(stats, f) else stats[f], np.float64) for f in ("N", "sums"))
+    if N.shape != (K,) or sums.shape != (K, D):
+        raise ValueError(f"the statistics must be N ({K},) and sums ({K}, {D})")
+    if not np.isfinite(N).all() or (N < 0).any():
+        raise ValueError("N must be finite and non-negative")
+    if not np.isfinite(sums).all():
+        raise ValueError("sums must be finite")
+    if (sums < 0).any():
+        raise ValueError("sums must be non-negative: counts are")
+    hit = N > 0
+    alpha[hit] += sums[hit]
+    count[hit] += N[hit]
     return new, count

@@ -28,7 +28,7 @@ from . import priors as _priors
 from . import tensors as _tensors      # noqa: F401  (the recognisers of host/points.py, reachable from here: tests patch them under this name)
 from . import project as _project
 from . import absorb as _absorb
-from .absorb import niw_absorb      # noqa: F401
+from .absorb import niw_absorb, dirichlet_absorb      # noqa: F401
 
 
 Exemplars = collections.namedtuple("Exemplars", "typical_idx typical_score fringe_idx fringe_score count skipped")
@@ -43,6 +43,11 @@ BatchStatistics = collections.namedtuple("BatchStatistics", "N sums S count skip
 BatchStatistics.__doc__ = """What `Predictor.statistics` returns and `Predictor.absorb` folds in: N (K,), sums (K, D), S (K, D, D) float64 -- sum_i w_ik,
 sum_i w_ik x_i, sum_i w_ik x_i x_i' over the points that take part; count (K,) int64, those of them labelled k + 1; skipped, incomplete,
 held_out, ints, the points that took no part -- numpy arrays always."""
+
+CountStatistics = collections.namedtuple("CountStatistics", "N sums count skipped incomplete held_out")
+CountStatistics.__doc__ = """What `Predictor.count_statistics` returns and `Predictor.absorb_counts` folds in: N (K,), sums (K, D) float64 -- sum_i w_ik,
+sum_i w_ik x_i over the points that take part; count (K,) int64, those of them labelled k + 1; skipped, incomplete, held_out, ints, the
+points that took no part -- numpy arrays always."""
 
 ASSIGN_MODES = {"hard": binding.BATCHSTATS_HARD, "soft": binding.BATCHSTATS_SOFT}
 
@@ -313,7 +318,7 @@ class Predictor:
         if self._wk is None:
             raise RuntimeError("this Predictor is closed")
         if self.kind != _priors.PRIOR_NIW:
-            raise ValueError("statistics are for the NIW prior: the sparse and byte point stores of the Multinomial prior are a separate piece of work")
+            raise ValueError("statistics are for the NIW prior: a Multinomial model has count_statistics / absorb_counts")
         if assign not in ASSIGN_MODES:
             raise ValueError('assign must be "hard" or "soft"')
         if min_logdens is not None:
@@ -347,6 +352,61 @@ class Predictor:
         which, args = self._predictive_args()
         self._wk.set_predictive_niw(*args)
         self._sampler_set = False            # the sampler's tables are those of the old posterior
+        return stats
+
+    # ---- count statistics and the Dirichlet update (include/dpmm_hip_countstats.h, host/absorb.py)
+    def count_statistics(self, data, assign="hard", min_logdens=None):
+        """The per-cluster sufficient statistics of count `data` under a Multinomial model: a `CountStatistics` tuple, accumulated on the
+        GPU in Float64.
+
+          N[k]      sum_i w_ik          sums[k]   sum_i w_ik x_i
+        with w_ik = 1 for the cluster `predict_labels` gives the point (assign="hard": N == count) or the probability `predict` gives
+        (assign="soft"), over the points that TAKE PART.  Every point is counted in exactly one of
+          skipped      its row of the table holds a NaN or no finite entry (as `overlap` skips it);
+          held_out     min_logdens is given and `score_samples` of the point lies below it: an outlier is not folded into a cluster;
+          incomplete   a value of it is not finite (of its D features, or of its stored entries when the data is sparse);
+          count[k]     it takes part and `predict_labels` labels it k + 1.
+        `data` is whatever `predict` takes for a Multinomial model -- a dense array or tensor, scipy CSC, the (colptr, rowval, nzval,
+        shape) tuple, a torch.sparse_csc tensor on the host or the device -- and is read from the store the worker keeps it in: Float32,
+        the lossless byte copy of small integer counts, or sparse columns; nothing is densified.  With assign="hard" and integer data the
+        sums are exact and the same to the bit whatever the capacity or the store; otherwise every entry lies within
+        2 gamma(n + 2) sum_i w_ik |x_id| of any other Float64 evaluation (include/dpmm_hip_countstats.h); the counters are exact.
+        Multinomial only.  The arrays are numpy arrays (K D numbers), nothing of size n is allocated or copied to the host."""
+        if self._wk is None:
+            raise RuntimeError("this Predictor is closed")
+        if self.kind != _priors.PRIOR_MULT:
+            raise ValueError("count_statistics are for the Multinomial prior: an NIW model has statistics / absorb")
+        if assign not in ASSIGN_MODES:
+            raise ValueError('assign must be "hard" or "soft"')
+        if min_logdens is not None:
+            min_logdens = float(min_logdens)
+            if min_logdens != min_logdens:
+                raise ValueError("min_logdens must not be NaN")
+        wk = self._wk
+        if not hasattr(wk, "countstats_begin"):
+            raise RuntimeError("this Predictor's worker cannot accumulate count statistics (no dpmm_countstats_begin)")
+        opened = self._open(data)
+        wk.countstats_begin(ASSIGN_MODES[assign], min_logdens)
+        self._walk(opened, [], lambda views, lo, hi: wk.countstats_accumulate(hi - lo))
+        r = wk.countstats_read()
+        return CountStatistics(r["N"], r["sums"], r["count"], int(r["skipped"][0]), int(r["incomplete"][0]), int(r["held_out"][0]))
+
+    def absorb_counts(self, data, assign="hard", min_logdens=None):
+        """Folds count `data` into a Multinomial model and returns the `CountStatistics` it absorbed (see `count_statistics`).
+
+        The Dirichlet prior is conjugate: `dirichlet_absorb` adds the sums to alpha -- kept in Float64 from then on -- of every cluster
+        that received weight, and N to `points_count`, hence the mixture weights.  The predictive parameters are then reloaded into the
+        same worker, once, so every later call, `sample` and `save` see the updated model; an accumulation begun before is refused
+        afterwards.  Statistics with N.sum() == 0 change nothing.  No new cluster is created: see `absorb`."""
+        stats = self.count_statistics(data, assign=assign, min_logdens=min_logdens)
+        if not stats.N.sum() > 0:
+            return stats
+        self.post, self.points_count = _absorb.dirichlet_absorb(self.post, self.points_count, stats)
+        w = self.points_count + self.alpha
+        self.weights = (w / w.sum()).astype(np.float32)
+        which, args = self._predictive_args()
+        self._wk.set_predictive_mult(*args)
+        self._sampler_set = False            # the alias tables of `sample` are those of the old posterior
         return stats
 
     # ---- missing features (include/dpmm_hip_missing.h)
@@ -615,6 +675,14 @@ def statistics(dp_model, data, **kw):
     assign, min_logdens = kw.pop("assign", "hard"), kw.pop("min_logdens", None)
     with Predictor(dp_model, **kw) as p:
         return p.statistics(data, assign=assign, min_logdens=min_logdens)
+
+
+def count_statistics(dp_model, data, **kw):
+    """The per-cluster count statistics of `data` under a Multinomial model (opens a Predictor, runs, closes): see
+    `Predictor.count_statistics`; kw: assign, min_logdens, capacity, device, worker_factory."""
+    assign, min_logdens = kw.pop("assign", "hard"), kw.pop("min_logdens", None)
+    with Predictor(dp_model, **kw) as p:
+        return p.count_statistics(data, assign=assign, min_logdens=min_logdens)
 
 
 def impute(dp_model, data, draws=None, seed=0, return_components=False, **kw):

@@ -34,8 +34,8 @@
  * chunk the points with w_ik != 0 are taken in increasing i; every (chunk, cluster, pair of 64-row blocks) has one writer, and the
  * chunks are added in increasing order.  Across other cuts or budgets the results agree within the bound; the counters are equal.
  *
- * Limits: the NIW prior, every D it takes, K up to DPMM_MAX_CLUSTERS.  A Multinomial ctx is refused (DPMM_EINVAL): its sparse and byte
- * point stores are a separate piece of work.
+ * Limits: the NIW prior, every D it takes, K up to DPMM_MAX_CLUSTERS.  A Multinomial ctx is refused (DPMM_EINVAL): its statistics, over
+ * the Float32, byte and sparse point stores, are those of dpmm_hip_countstats.h.
  *
  * Memory: the accumulators (K * (D * D + D + 1) doubles, 8 * (K + 3) counters), two floats per point of one range of the score table
  * and the chunk partials -- at most DPMM_BATCHSTATS_PARTIAL_BLOCKS blocks of 64 * 64 doubles, 64 MB, plus at most as many rows of
