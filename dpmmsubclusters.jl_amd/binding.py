@@ -194,6 +194,20 @@ ABI_COUNTSTATS = [
     ("dpmm_countstats_read", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(CountStatsOut)]),
 ]
 COUNTSTATS_PARTIAL_BYTES = 64 << 20        # DPMM_COUNTSTATS_PARTIAL_BYTES
+
+
+class TypicalityOut(ctypes.Structure):
+    """dpmm_typicality_out (include/dpmm_hip_typicality.h): host or device addresses (the two counters always host), 0 / None = not asked for."""
+    _fields_ = [("labels", ctypes.c_void_p), ("mahalanobis", ctypes.c_void_p), ("tail", ctypes.c_void_p), ("skipped", ctypes.c_void_p),
+                ("incomplete", ctypes.c_void_p)]
+
+
+# include/dpmm_hip_typicality.h: calibrated outlier scores, the tail of a point's Mahalanobis distance under its own cluster (additive; bound next to ABI)
+ABI_TYPICALITY = [
+    ("dpmm_typicality_points", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(TypicalityOut)]),
+    ("dpmm_typicality_points_device", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(TypicalityOut)]),
+    ("dpmm_batchstats_set_min_tail", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_float]),
+]
 # include/dpmm_hip_trace.h: label samples kept on the GPU, their pairwise contingency tables and the per-point confidence (additive)
 ABI_TRACE = [
     ("dpmm_trace_open", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
@@ -307,7 +321,7 @@ def load_library():
         except Exception:  # pragma: no cover  (torch is optional for single-GPU use)
             pass
         lib = ctypes.CDLL(p)
-        for name, res, args in ABI + ABI_TENSOR + ABI_SCORE + ABI_RANK + ABI_OVERLAP + ABI_BATCHSTATS + ABI_COUNTSTATS + ABI_TRACE + ABI_MISSING + ABI_IMPUTE + ABI_CSC + ABI_SAMPLE + ABI_PROJECT:
+        for name, res, args in ABI + ABI_TENSOR + ABI_SCORE + ABI_RANK + ABI_OVERLAP + ABI_BATCHSTATS + ABI_COUNTSTATS + ABI_TYPICALITY + ABI_TRACE + ABI_MISSING + ABI_IMPUTE + ABI_CSC + ABI_SAMPLE + ABI_PROJECT:
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -687,6 +701,31 @@ class Worker:
             self.score_points_into(res, m=m)
         return res
 
+    # ---- calibrated outlier scores (include/dpmm_hip_typicality.h)
+    def typicality_points_raw(self, device, labels=0, mahalanobis=0, tail=0, skipped=0, incomplete=0):
+        """dpmm_typicality_points[_device] on plain addresses (integers; 0 = not asked for); skipped, incomplete: host addresses."""
+        out = TypicalityOut(labels or None, mahalanobis or None, tail or None, skipped or None, incomplete or None)
+        fn = self._lib.dpmm_typicality_points_device if device else self._lib.dpmm_typicality_points
+        self._chk(fn(self._h, ctypes.byref(out)))
+
+    def typicality_points_into(self, outs):
+        """dpmm_typicality_points[_device] into storage the caller made: `outs` maps `labels` / `mahalanobis` / `tail` to contiguous numpy
+        arrays (host variant) or torch tensors on this worker's GPU (device variant) with n entries each; returns (skipped, incomplete)."""
+        ptr, on_device = {}, None
+        for name, a in outs.items():
+            dev = hasattr(a, "data_ptr")
+            if on_device is None:
+                on_device = dev
+            assert dev == on_device, "typicality_points_into: numpy arrays or tensors, not both"
+            assert a.is_contiguous() if dev else a.flags.c_contiguous, name
+            ptr[name] = (a.data_ptr() if a.numel() else 0) if dev else (a.ctypes.data if a.size else 0)
+        if on_device:
+            import torch
+            torch.cuda.current_stream(next(iter(outs.values())).device).synchronize()
+        cnt = np.zeros(2, np.int64)
+        self.typicality_points_raw(bool(on_device), skipped=cnt[0:].ctypes.data, incomplete=cnt[1:].ctypes.data, **ptr)
+        return int(cnt[0]), int(cnt[1])
+
     # ---- missing features (include/dpmm_hip_missing.h)
     def score_missing_counts(self):
         """dpmm_score_missing_counts: (marginalised, over the cap) among the points the last score / rank / impute call evaluated."""
@@ -803,6 +842,12 @@ class Worker:
         floor = min_logdens is not None
         self._chk(self._lib.dpmm_batchstats_begin(self._h, int(mode), int(floor), float(min_logdens) if floor else 0.0))
         self._batchstats_K = self.K
+
+    def batchstats_set_min_tail(self, min_tail=None):
+        """dpmm_batchstats_set_min_tail (include/dpmm_hip_typicality.h), between batchstats_begin and the first batchstats_accumulate:
+        min_tail in (0, 1], the tail below which a complete point is held out, or None for no such floor."""
+        use = min_tail is not None
+        self._chk(self._lib.dpmm_batchstats_set_min_tail(self._h, int(use), float(min_tail) if use else 0.0))
 
     def batchstats_accumulate(self, n_valid):
         """dpmm_batchstats_accumulate: adds the points 0..n_valid-1 of the current upload."""

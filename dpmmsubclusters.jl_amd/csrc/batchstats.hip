@@ -7,7 +7,9 @@
 // Launches per range, nothing in them waits for another workgroup:
 //   prep      a workgroup per 256 points.  Lanes along i over the table: passes 1 and 2 of score_finish_kernel -- M, the label, NaN seen,
 //             S, logdens.  The workgroup's 256 rows of X are one contiguous piece of memory: it is read flat, lanes along the words, and a
-//             word that is not finite (features d < D only) marks its row in LDS.  The class of the point follows, and one float2 per
+//             word that is not finite (features d < D only) marks its row in LDS.  With dpmm_batchstats_set_min_tail a complete point is
+//             also held out when its tail -- one float per point of the range, written by typicality.hip in front of this kernel --
+//             lies below the floor; without it that buffer does not exist and is not read.  The class of the point follows, and one float2 per
 //             point: (M, S) in SOFT mode, (label, 1) in HARD mode, (0, 0) for a point that takes no part.  The counters are integer
 //             adds in LDS, flushed to one of RANK_REPL replicas of the global counters: sums of integers, order-free.
 //   contract  the range is cut into nchunk chunks, the features into blocks of 64; a workgroup of four waves owns (chunk, cluster k,
@@ -72,7 +74,8 @@ __global__ __launch_bounds__(BS_THREADS) void batchstats_prep_kernel(BatchStatsA
         __syncthreads();
         // ---- the class: skipped, else held out, else incomplete, else it takes part
         const bool scored = valid && !nan_seen && m > -INFINITY && m < INFINITY;
-        const bool held = scored && A.use_floor && score_logdens(m, s) < A.min_logdens;
+        // (the tail of a point with a feature that is not finite is NaN and compares false: such a point stays incomplete)
+        const bool held = scored && ((A.use_floor && score_logdens(m, s) < A.min_logdens) || (A.use_tail && gap[tid] == 0 && A.tail[i] < A.min_tail));
         const bool incomplete = scored && !held && gap[tid] != 0;
         const bool part = scored && !held && !incomplete;
         if (valid) A.ms[i] = !part ? make_float2(0.f, 0.f) : A.soft ? make_float2(m, s) : make_float2((float)best, 1.f);

@@ -13,6 +13,7 @@
 #include "../../include/dpmm_hip_overlap.h"
 #include "../../include/dpmm_hip_batchstats.h"
 #include "../../include/dpmm_hip_countstats.h"
+#include "../../include/dpmm_hip_typicality.h"
 #include "../../include/dpmm_hip_trace.h"
 #include "../../include/dpmm_hip_missing.h"
 #include "../../include/dpmm_hip_impute.h"
@@ -153,6 +154,15 @@ struct dpmm_ctx {
     int bs_K = 0, bs_mode = 0, bs_floor = 0;
     float bs_min_logdens = 0.f;
     unsigned long long bs_gen = 0;      // pred_gen at dpmm_batchstats_begin
+    // calibrated outlier scores (include/dpmm_hip_typicality.h): class word and q per point of one range, the two counters; the tails of one
+    // range for the hold-out of dpmm_batchstats_set_min_tail (allocated only when it is in use)
+    DevBuf<int32_t> d_typ_cls;
+    DevBuf<float> d_typ_q;
+    DevBuf<unsigned long long> d_typ_cnt;
+    DevBuf<float> d_bs_tail;
+    int bs_use_tail = 0;
+    float bs_min_tail = 0.f;
+    bool bs_accumulated = false;        // a dpmm_batchstats_accumulate has run since dpmm_batchstats_begin
     // count statistics (include/dpmm_hip_countstats.h): N | sums | counters; two floats per point of one range; the chunk partials
     DevBuf<double> d_cs_acc;
     DevBuf<float2> d_cs_ms;
@@ -3619,17 +3629,13 @@ static int score_table_slab(dpmm_ctx *c, int *rstep_out, int64_t *P_out) {
 
 
 // ---- include/dpmm_hip_missing.h: the marginal entries of points with NaN features, range by range (missing.hip) ---------------------------
-// Called once per table call, behind score_table_slab.  on: the call marginalises -- the device buffers exist afterwards (the list sized for
-// one range of P points), the copies of the parameters are those of the predictive set in force, the per-call counters are cleared.
-static int miss_begin(dpmm_ctx *c, bool on, int64_t P, const char *fn) {
-    c->miss_counted = false;
-    if (!on) return DPMM_OK;
+// The device copies that missing.hip and typicality.hip read -- the transposed factors Rt and the constants [K][MISS_CST] -- are those of the
+// predictive set in force afterwards.
+static int miss_params(dpmm_ctx *c, const char *fn) {
     const std::string who = std::string(fn) + ": ";
     if (c->prior != DPMM_PRIOR_NIW || c->h_miss_cst.size() != (size_t)c->K * MISS_CST || !c->d_par)
         return fail(c, DPMM_ESTATE, who + "missing features need dpmm_set_predictive_niw");
     const size_t K = (size_t)c->K, D = (size_t)c->D;
-    if (int rc = grow(c, c->d_miss_cnt, 3 * sizeof(unsigned long long), "dpmm_score_points", "counters of the missing-feature pass")) return rc;
-    if (int rc = grow(c, c->d_miss_list, sizeof(uint32_t) * (size_t)P, "dpmm_score_points", "list of the missing-feature pass")) return rc;
     if (c->miss_gen != c->pred_gen) {
         if (int rc = grow(c, c->d_miss_rt, sizeof(float) * K * D * (size_t)miss_pitch(c->D), "dpmm_score_points", "transposed factors of the missing-feature pass")) return rc;
         if (int rc = grow(c, c->d_miss_cst, sizeof(double) * K * MISS_CST, "dpmm_score_points", "constants of the missing-feature pass")) return rc;
@@ -3640,6 +3646,17 @@ static int miss_begin(dpmm_ctx *c, bool on, int64_t P, const char *fn) {
         HIPCHK(c, launch_miss_transpose(Rpk, 3 * (int64_t)(D * (D + 1) / 2), c->d_miss_rt, c->K, c->D, c->stream));
         c->miss_gen = c->pred_gen;
     }
+    return DPMM_OK;
+}
+
+// Called once per table call, behind score_table_slab.  on: the call marginalises -- the device buffers exist afterwards (the list sized for
+// one range of P points), the copies of the parameters are those of the predictive set in force, the per-call counters are cleared.
+static int miss_begin(dpmm_ctx *c, bool on, int64_t P, const char *fn) {
+    c->miss_counted = false;
+    if (!on) return DPMM_OK;
+    if (int rc = grow(c, c->d_miss_cnt, 3 * sizeof(unsigned long long), "dpmm_score_points", "counters of the missing-feature pass")) return rc;
+    if (int rc = grow(c, c->d_miss_list, sizeof(uint32_t) * (size_t)P, "dpmm_score_points", "list of the missing-feature pass")) return rc;
+    if (int rc = miss_params(c, fn)) return rc;
     HIPCHK(c, hipMemsetAsync(c->d_miss_cnt, 0, 3 * sizeof(unsigned long long), c->stream));
     c->miss_counted = true;
     return DPMM_OK;
@@ -3754,6 +3771,93 @@ int dpmm_score_missing_counts(dpmm_ctx *c, int64_t out[2]) {
     out[0] = (int64_t)h[1]; out[1] = (int64_t)h[2];
     return DPMM_OK;
 }
+
+// ---- include/dpmm_hip_typicality.h: label, q = |R_k (x - m_k)|^2 of the point's own cluster and its tail, range by range (typicality.hip) ----
+// The scratch of one range of P points (class words, q) and the two counters; the parameter copies of missing.hip are those in force.
+static int typ_begin(dpmm_ctx *c, int64_t P, const char *fn) {
+    if (int rc = grow(c, c->d_typ_cls, sizeof(int32_t) * (size_t)P, "dpmm_score_points", "class words of the typicality pass")) return rc;
+    if (int rc = grow(c, c->d_typ_q, sizeof(float) * (size_t)P, "dpmm_score_points", "squared distances of the typicality pass")) return rc;
+    if (int rc = grow(c, c->d_typ_cnt, 2 * sizeof(unsigned long long), "dpmm_score_points", "counters of the typicality pass")) return rc;
+    return miss_params(c, fn);
+}
+
+// One range of the table (np points from point p0, rows P floats apart), just evaluated (and patched) on the ctx stream.  labels, q, tail:
+// device memory of np entries or null; q == null: the ctx's scratch.  The counters are added to.
+static int typ_range(dpmm_ctx *c, int64_t P, int64_t p0, int64_t np, int64_t *labels, float *q, float *tail, const char *fn) {
+    const ParLayout L = par_layout(c, c->miss_slots);
+    TypicalityArgs a{};
+    a.table = c->d_score_table; a.stride = P; a.n = np; a.K = c->K; a.D = c->D;
+    a.X = c->dX + p0 * c->ldx; a.ldx = c->ldx;
+    a.Rt = c->d_miss_rt; a.mu = reinterpret_cast<const float *>(c->d_par + (L.mu - L.cst)); a.mu_step = 3 * (int64_t)c->D;
+    a.cst = c->d_miss_cst; a.cls = c->d_typ_cls; a.labels = labels; a.q = q ? q : c->d_typ_q.get(); a.tail = tail; a.cnt = c->d_typ_cnt;
+    const hipError_t e = launch_typicality_range(a, 32 * c->cus, c->stream);
+    if (e != hipSuccess) { c->err = std::string(fn) + ": " + hipGetErrorString(e); return DPMM_EHIP; }
+    return DPMM_OK;
+}
+
+static int typicality_points(dpmm_ctx *c, const dpmm_typicality_out *o, bool device, const char *fn) {
+    if (!c) return tensor_no_ctx(fn);
+    c->miss_counted = false;      // (as score_points)
+    const std::string who = std::string(fn) + ": ";
+    if (!o) return fail(c, DPMM_EINVAL, who + "out is null");
+    if (c->prior != DPMM_PRIOR_NIW) return fail(c, DPMM_EINVAL, who + "the tail is that of the NIW prior's Student-t predictive; the Multinomial predictive has no closed-form tail");
+    if (!o->labels && !o->mahalanobis && !o->tail && !o->skipped && !o->incomplete) return fail(c, DPMM_EINVAL, who + "every output pointer is null");
+    if (!c->predictive) return fail(c, DPMM_ESTATE, who + "needs dpmm_set_predictive_niw first");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (o->skipped) o->skipped[0] = 0;
+    if (o->incomplete) o->incomplete[0] = 0;
+    if (c->n == 0) return DPMM_OK;
+    if (!c->have_points || !c->have_params || !c->dX) return fail(c, DPMM_ESTATE, who + "needs points and parameters");
+    const uint64_t n = (uint64_t)c->n;
+    if (device) {
+        if (o->labels) if (int rc = check_device_extent(c, fn, "labels", o->labels, sizeof(int64_t) * n, sizeof(int64_t))) return rc;
+        if (o->mahalanobis) if (int rc = check_device_extent(c, fn, "mahalanobis", o->mahalanobis, sizeof(float) * n, sizeof(float))) return rc;
+        if (o->tail) if (int rc = check_device_extent(c, fn, "tail", o->tail, sizeof(float) * n, sizeof(float))) return rc;
+    }
+    int rstep = 0;
+    int64_t P = 0;
+    if (int rc = score_table_slab(c, &rstep, &P)) return rc;
+    const bool miss = c->opt_score_missing != 0;
+    if (int rc = miss_begin(c, miss, P, fn)) return rc;
+    if (int rc = typ_begin(c, P, fn)) return rc;
+    HIPCHK(c, hipMemsetAsync(c->d_typ_cnt, 0, 2 * sizeof(unsigned long long), c->stream));
+    // host variant: the range's outputs on the device, one block per output (each 8-byte aligned)
+    size_t off_lab = 0, off_q = 0, off_t = 0, total = 0;
+    if (!device) {
+        auto take = [&](bool want, size_t bytes_per_point) { const size_t at = total; if (want) total += ((size_t)P * bytes_per_point + 7) & ~(size_t)7; return at; };
+        off_lab = take(o->labels != nullptr, sizeof(int64_t));
+        off_q = take(o->mahalanobis != nullptr, sizeof(float));
+        off_t = take(o->tail != nullptr, sizeof(float));
+        if (int rc = grow(c, c->d_score_out, total, "dpmm_score_points", "staging of the outputs")) return rc;
+    }
+    for (int64_t p0 = 0; p0 < c->n; p0 += P) {
+        const int64_t np = std::min<int64_t>(P, c->n - p0);
+        if (int rc = run_sweep(c, 0, 0, c->d_score_table, P, p0, np)) return rc;
+        if (miss) if (int rc = miss_range(c, P, p0, np, nullptr, 0, fn)) return rc;
+        int64_t *lab = !o->labels ? nullptr : device ? o->labels + p0 : reinterpret_cast<int64_t *>(c->d_score_out + off_lab);
+        float *q = !o->mahalanobis ? nullptr : device ? o->mahalanobis + p0 : reinterpret_cast<float *>(c->d_score_out + off_q);
+        float *tl = !o->tail ? nullptr : device ? o->tail + p0 : reinterpret_cast<float *>(c->d_score_out + off_t);
+        if (int rc = typ_range(c, P, p0, np, lab, q, tl, fn)) return rc;
+        if (!device) {
+            const size_t z = (size_t)np;
+            hipError_t e = hipSuccess;
+            if (o->labels) e = hipMemcpyAsync(o->labels + p0, lab, sizeof(int64_t) * z, hipMemcpyDeviceToHost, c->stream);
+            if (e == hipSuccess && o->mahalanobis) e = hipMemcpyAsync(o->mahalanobis + p0, q, sizeof(float) * z, hipMemcpyDeviceToHost, c->stream);
+            if (e == hipSuccess && o->tail) e = hipMemcpyAsync(o->tail + p0, tl, sizeof(float) * z, hipMemcpyDeviceToHost, c->stream);
+            if (e == hipSuccess) e = sync_stream(c, c->stream);      // the staging block is rewritten by the next range
+            if (e != hipSuccess) { c->err = who + hipGetErrorString(e); return DPMM_EHIP; }
+        }
+    }
+    HIPCHK(c, sync_stream(c, c->stream));
+    unsigned long long h[2] = {0, 0};
+    HIPCHK(c, hipMemcpy(h, c->d_typ_cnt, sizeof(h), hipMemcpyDeviceToHost));
+    if (o->skipped) o->skipped[0] = (int64_t)h[0];
+    if (o->incomplete) o->incomplete[0] = (int64_t)h[1];
+    return DPMM_OK;
+}
+
+int dpmm_typicality_points(dpmm_ctx *c, const dpmm_typicality_out *out) { return typicality_points(c, out, false, "dpmm_typicality_points"); }
+int dpmm_typicality_points_device(dpmm_ctx *c, const dpmm_typicality_out *out) { return typicality_points(c, out, true, "dpmm_typicality_points_device"); }
 
 static int impute_points(dpmm_ctx *c, float *out, int64_t ld, bool device, const char *fn) {
     if (!c) return tensor_no_ctx(fn);
@@ -4121,7 +4225,21 @@ int dpmm_batchstats_begin(dpmm_ctx *c, int mode, int use_floor, float min_logden
     }
     HIPCHK(c, hipMemsetAsync(c->d_bs_acc, 0, state, c->stream));
     c->bs_K = K; c->bs_gen = c->pred_gen; c->bs_mode = mode; c->bs_floor = use_floor ? 1 : 0; c->bs_min_logdens = min_logdens;
+    c->bs_use_tail = 0; c->bs_min_tail = 0.f; c->bs_accumulated = false;
     c->bs_active = true;
+    return DPMM_OK;
+}
+
+// include/dpmm_hip_typicality.h: the calibrated floor of the accumulation just begun
+int dpmm_batchstats_set_min_tail(dpmm_ctx *c, int use, float min_tail) {
+    static const char *fn = "dpmm_batchstats_set_min_tail";
+    if (!c) return tensor_no_ctx(fn);
+    const std::string who = std::string(fn) + ": ";
+    if (!c->bs_active) return fail(c, DPMM_ESTATE, who + "needs dpmm_batchstats_begin first");
+    if (c->bs_accumulated) return fail(c, DPMM_ESTATE, who + "belongs between dpmm_batchstats_begin and the first dpmm_batchstats_accumulate");
+    if (use && !(min_tail > 0.f && min_tail <= 1.f)) return fail(c, DPMM_EINVAL, who + "min_tail must lie in (0, 1]");
+    c->bs_use_tail = use ? 1 : 0;
+    c->bs_min_tail = use ? min_tail : 0.f;
     return DPMM_OK;
 }
 
@@ -4147,14 +4265,21 @@ int dpmm_batchstats_accumulate(dpmm_ctx *c, int64_t n_valid) {
     if (int rc = grow(c, c->d_bs_part, part, "dpmm_score_points", "chunk partials of dpmm_batchstats_accumulate")) return rc;
     const bool miss = c->opt_score_missing != 0;
     if (int rc = miss_begin(c, miss, P, fn)) return rc;
+    if (c->bs_use_tail) {
+        if (int rc = grow(c, c->d_bs_tail, sizeof(float) * (size_t)P, "dpmm_score_points", "tails of dpmm_batchstats_accumulate")) return rc;
+        if (int rc = typ_begin(c, P, fn)) return rc;
+    }
+    c->bs_accumulated = true;
     for (int64_t p0 = 0; p0 < n_valid; p0 += P) {
         const int64_t np = std::min<int64_t>(P, c->n - p0);              // the range dpmm_score_points evaluates
         if (int rc = run_sweep(c, 0, 0, c->d_score_table, P, p0, np)) return rc;
         if (miss) if (int rc = miss_range(c, P, p0, np, nullptr, 0, fn)) return rc;
+        if (c->bs_use_tail) if (int rc = typ_range(c, P, p0, std::min<int64_t>(np, n_valid - p0), nullptr, nullptr, c->d_bs_tail, fn)) return rc;
         BatchStatsArgs a{};
         a.table = c->d_score_table; a.stride = P; a.rstep = rstep; a.n = std::min<int64_t>(np, n_valid - p0); a.K = K; a.D = D; a.nb = (D + 63) / 64;
         a.X = c->dX + p0 * c->ldx; a.ldx = c->ldx;
         a.soft = c->bs_mode == DPMM_BATCHSTATS_SOFT; a.use_floor = c->bs_floor; a.min_logdens = c->bs_min_logdens;
+        a.use_tail = c->bs_use_tail; a.min_tail = c->bs_min_tail; a.tail = c->bs_use_tail ? c->d_bs_tail.get() : nullptr;
         batchstats_chunks(a.n, K, D, &a.kgroup, &a.nchunk, &a.chunk);
         if ((size_t)a.nchunk * (size_t)std::min(a.kgroup, K) * (size_t)(a.nb * (a.nb + 1) / 2) * 4096 > off_s)
             return fail(c, DPMM_EHIP, who + "internal: more chunks than the partial buffer holds");

@@ -246,6 +246,9 @@ struct BatchStatsArgs {
     int soft;            // 0: w_ik = [label_i == k + 1], 1: w_ik = p_ik
     int use_floor;       // points with logdens < min_logdens are held out
     float min_logdens;
+    int use_tail;        // complete points with tail[i] < min_tail are held out (include/dpmm_hip_typicality.h)
+    float min_tail;
+    const float *tail;   // [n] the range's tails as launch_typicality_range wrote them (NaN: skipped or incomplete); read only if use_tail
     int nb;              // blocks of 64 features, (D + 63) / 64
     int kgroup;          // clusters per contraction launch (batchstats_chunks)
     int nchunk;          // chunks of the range (batchstats_chunks)
@@ -317,6 +320,26 @@ struct MissArgs {
 hipError_t launch_miss_transpose(const float *Rpk, int64_t step, float *Rt, int K, int D, hipStream_t s);      // Rpk: packed upper triangles, cluster k at Rpk + k * step
 hipError_t launch_miss_list(const MissArgs &a, hipStream_t s);
 hipError_t launch_miss_patch(const MissArgs &a, bool impute, int max_grid, hipStream_t s);
+// ---- calibrated outlier scores (typicality.hip; include/dpmm_hip_typicality.h): one range of the score table, n points from table column 0:
+// the label and the class of every point, q = |R_k (x - m_k)|^2 for its own cluster k in Float32, the tail of q in Float64
+struct TypicalityArgs {
+    const float *table;          // entry (k, i) at table[k * stride + i] (NIW: one row per cluster)
+    int64_t stride;
+    int64_t n;
+    int K, D;
+    const float *X;              // [n][ldx], the range's first point
+    int64_t ldx;
+    const float *Rt;             // as MissArgs::Rt
+    const float *mu;             // cluster k's mean: mu + k * mu_step
+    int64_t mu_step;
+    const double *cst;           // as MissArgs::cst: [k * MISS_CST] = df_k, the Float32 value widened
+    int32_t *cls;                // [n] scratch: the 0-based cluster of the point, -1 for a skipped one
+    int64_t *labels;             // [n] or null
+    float *q;                    // [n] never null (the caller's array or scratch)
+    float *tail;                 // [n] or null: no tail pass
+    unsigned long long *cnt;     // [0] skipped, [1] incomplete: added to
+};
+hipError_t launch_typicality_range(const TypicalityArgs &a, int max_grid, hipStream_t s);
 // draws of the missing features (include/dpmm_hip_impute.h) behind launch_miss_list and launch_miss_patch(a, false, ..) of the same range
 constexpr int64_t MISS_DRAW_MAX = (int64_t)1 << 26;      // draw indices: 64 Philox blocks each in a 32-bit block number
 struct MissDraw {

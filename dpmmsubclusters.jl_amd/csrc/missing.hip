@@ -26,21 +26,13 @@
 #include "dpmm_device.h"
 #include "dpmm_kernels.h"
 #include "sample_device.h"
+#include "missing_device.h"
 
 namespace dpmm {
 
 constexpr int MISS_WAVES = 4;                  // waves per workgroup of the patch kernel (they share nothing)
 constexpr int MISS_LDA = MISS_MAX + 1;         // doubles per row of a wave's A (odd: the lanes of a column fall into different banks)
 
-__device__ __forceinline__ float miss_rl_f(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
-__device__ __forceinline__ double miss_rl_d(double v, int l) {
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
-}
-__device__ __forceinline__ double miss_wave_sum(double v) {      // (a butterfly: every lane ends with the same bits)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 __device__ __forceinline__ void miss_lds_fence() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); }
 
 __global__ __launch_bounds__(256) void miss_transpose_kernel(const float *__restrict__ Rpk, int64_t step, float *__restrict__ Rt, int K, int D, int Dp) {
@@ -122,20 +114,8 @@ __device__ __forceinline__ double miss_system(const float *Rk, const float *mk, 
         const int j = 64 * t + lane;
         const bool miss = (nm[t] >> lane) & 1ull;
         z[t] = (j < D && !miss) ? xv[t] - mk[j] : 0.f;
-        y[t] = 0.f;
     }
-    // ---- y = R z: column j of R scaled by z_j; rows above 64 (tj + 1) hold zeros of the triangle and are skipped
-#pragma unroll
-    for (int tj = 0; tj < NT; ++tj) {
-        const int jn = D - 64 * tj < 64 ? D - 64 * tj : 64;
-#pragma unroll 4
-        for (int jj = 0; jj < jn; ++jj) {
-            const float zj = miss_rl_f(z[tj], jj);
-            const float *c = Rk + (int64_t)(64 * tj + jj) * Dp + lane;
-#pragma unroll
-            for (int tr = 0; tr <= tj; ++tr) y[tr] = fmaf(c[64 * tr], zj, y[tr]);
-        }
-    }
+    miss_rz<NT>(Rk, z, D, lane, y);      // ---- y = R z (missing_device.h)
     // ---- g = C'y into lane b, A = C'C (lower triangle) into the wave's LDS
     gl = 0.0;
     for (int b = 0; b < r; ++b) {

@@ -49,6 +49,10 @@ CountStatistics.__doc__ = """What `Predictor.count_statistics` returns and `Pred
 sum_i w_ik x_i over the points that take part; count (K,) int64, those of them labelled k + 1; skipped, incomplete, held_out, ints, the
 points that took no part -- numpy arrays always."""
 
+Typicality = collections.namedtuple("Typicality", "labels mahalanobis tail skipped incomplete")
+Typicality.__doc__ = """What `Predictor.typicality` returns: labels (n,) int64 1-based, mahalanobis (n,) float32, tail (n,) float32 -- tensors on
+the data's device for a device tensor, else numpy arrays -- and skipped, incomplete, ints: the points whose mahalanobis and tail are NaN."""
+
 ASSIGN_MODES = {"hard": binding.BATCHSTATS_HARD, "soft": binding.BATCHSTATS_SOFT}
 
 
@@ -241,6 +245,47 @@ class Predictor:
         """(n,) float32: log of the mixture's posterior predictive density at every point."""
         return self._run(data, logdens=True)["logdens"]
 
+    # ---- calibrated outlier scores (include/dpmm_hip_typicality.h)
+    def typicality(self, data):
+        """How typical every point is of the cluster it is given: a `Typicality` tuple, computed on the GPU.
+
+          labels        (n,) int64, 1-based: bit-identical to `predict_labels(data)`;
+          mahalanobis   (n,) float32: q_i = |R_k (x_i - m_k)|^2 for k = labels[i] - 1, the squared Mahalanobis distance of the point under
+                        its own cluster's posterior predictive t_df(m_k, Sigma_k), Sigma_k^-1 = R_k' R_k, evaluated in Float32 from the
+                        Float32 x, m, R the worker holds (with a projection: in the projected space);
+          tail          (n,) float32: P(Q >= q_i) for a draw from that predictive -- Q / D ~ F(D, df_k), so the tail is the regularised
+                        incomplete beta function I_{df / (df + q)}(df / 2, D / 2) -- evaluated in Float64 and rounded once.  It is
+                        uniform on (0, 1) for points that belong to the cluster, whatever D, the cluster's scale or weight, before and
+                        after an `absorb`: tail < 1e-6 means the same everywhere, which no threshold on `score_samples` does.
+                        q == 0 gives exactly 1; tails below the smallest normal Float32 may come back as 0;
+          skipped       points whose row of the table holds a NaN or no finite entry (the rule of `overlap` and `statistics`);
+          incomplete    points that are not skipped but have a feature that is not finite: under missing="marginalize" a point with
+                        gaps is labelled, but q is not marginalised here (out of scope).
+        Skipped and incomplete points have mahalanobis = tail = NaN.  NIW only: the Multinomial predictive has no closed-form tail.
+        `data` is what `predict` takes; for a device tensor the three arrays are tensors on its device, written there by the library,
+        nothing of size n crossing the host link.  No result depends on `capacity` or the table budget, to the bit."""
+        if self._wk is None:
+            raise RuntimeError("this Predictor is closed")
+        if self.kind != _priors.PRIOR_NIW:
+            raise ValueError("typicality is for the NIW prior: the Multinomial predictive has no closed-form tail")
+        wk = self._wk
+        if not hasattr(wk, "typicality_points_into"):
+            raise RuntimeError("this Predictor's worker cannot score typicality (no dpmm_typicality_points)")
+        total = [0, 0]
+
+        def evaluate(views, lo, hi):
+            sk, inc = wk.typicality_points_into(views)
+            if hi - lo < self.capacity:
+                # the short slab: the worker scored its padding too -- equal points with finite features, so never incomplete and all of
+                # one class, which the first of them shows
+                q0 = float(views["mahalanobis"][hi - lo])
+                if q0 != q0:
+                    sk -= self.capacity - (hi - lo)
+            total[0] += sk
+            total[1] += inc
+        out = self._walk(self._open(data), [("labels", (), "int64"), ("mahalanobis", (), "float32"), ("tail", (), "float32")], evaluate)
+        return Typicality(out["labels"], out["mahalanobis"], out["tail"], total[0], total[1])
+
     # ---- exemplars (include/dpmm_hip_rank.h)
     def exemplars(self, data, m, which="both"):
         """The m most and the m least typical points of every cluster, selected on the GPU: an `Exemplars` tuple.
@@ -301,14 +346,17 @@ class Predictor:
         return Overlap(r["overlap"], r["mass"], r["count"], int(r["skipped"][0]))
 
     # ---- batch statistics and the conjugate update (include/dpmm_hip_batchstats.h, host/absorb.py)
-    def statistics(self, data, assign="hard", min_logdens=None):
+    def statistics(self, data, assign="hard", min_logdens=None, min_tail=None):
         """The per-cluster sufficient statistics of `data` under the model: a `BatchStatistics` tuple, accumulated on the GPU in Float64.
 
           N[k]      sum_i w_ik          sums[k]   sum_i w_ik x_i          S[k]   sum_i w_ik x_i x_i', symmetric bit for bit
         with w_ik = 1 for the cluster `predict_labels` gives the point (assign="hard": N == count) or the probability `predict` gives
         (assign="soft"), over the points that TAKE PART.  Every point is counted in exactly one of
           skipped      its row of the table holds a NaN or no finite entry (as `overlap` skips it);
-          held_out     min_logdens is given and `score_samples` of the point lies below it: an outlier is not folded into a cluster;
+          held_out     min_logdens is given and `score_samples` of the point lies below it, or min_tail is given (a number in (0, 1]), the
+                       point's features are all finite and its `typicality` tail lies below it: an outlier is not folded into a cluster.
+                       The tail is the calibrated floor -- min_tail=1e-6 means the same at every D, for every cluster and after every
+                       `absorb`, which no value of min_logdens does; either floor holds a point out;
           incomplete   a feature is not finite -- under missing="marginalize" a point with gaps is labelled, yet its moments are unknown;
           count[k]     it takes part and `predict_labels` labels it k + 1.
         x_i is the point as the model sees it: Float32, and with a projection its projected coordinates.  Every entry lies within
@@ -325,16 +373,24 @@ class Predictor:
             min_logdens = float(min_logdens)
             if min_logdens != min_logdens:
                 raise ValueError("min_logdens must not be NaN")
+        if min_tail is not None:
+            min_tail = float(min_tail)
+            if not 0.0 < min_tail <= 1.0:
+                raise ValueError("min_tail must lie in (0, 1]")
         wk = self._wk
         if not hasattr(wk, "batchstats_begin"):
             raise RuntimeError("this Predictor's worker cannot accumulate batch statistics (no dpmm_batchstats_begin)")
+        if min_tail is not None and not hasattr(wk, "batchstats_set_min_tail"):
+            raise RuntimeError("this Predictor's worker cannot hold points out by their tail (no dpmm_batchstats_set_min_tail)")
         opened = self._open(data)
         wk.batchstats_begin(ASSIGN_MODES[assign], min_logdens)
+        if min_tail is not None:
+            wk.batchstats_set_min_tail(min_tail)
         self._walk(opened, [], lambda views, lo, hi: wk.batchstats_accumulate(hi - lo))
         r = wk.batchstats_read()
         return BatchStatistics(r["N"], r["sums"], r["S"], r["count"], int(r["skipped"][0]), int(r["incomplete"][0]), int(r["held_out"][0]))
 
-    def absorb(self, data, assign="hard", min_logdens=None):
+    def absorb(self, data, assign="hard", min_logdens=None, min_tail=None):
         """Folds `data` into the model and returns the `BatchStatistics` it absorbed (see `statistics` for the arguments).
 
         The NIW prior is conjugate: the posterior this Predictor carries is the exact prior of the batch, and `niw_absorb` updates every
@@ -342,8 +398,8 @@ class Predictor:
         parameters are then reloaded into the same worker, once, so every later call and `save` see the updated model; an accumulation
         begun before (`overlap`, `exemplars` pieces at the binding level) is refused afterwards.  Statistics with N.sum() == 0 change
         nothing.  No new cluster is created: points far from every cluster are either absorbed by the nearest one or, with
-        `min_logdens`, held out and counted."""
-        stats = self.statistics(data, assign=assign, min_logdens=min_logdens)
+        `min_logdens` or `min_tail`, held out and counted."""
+        stats = self.statistics(data, assign=assign, min_logdens=min_logdens, min_tail=min_tail)
         if not stats.N.sum() > 0:
             return stats
         self.post, self.points_count = _absorb.niw_absorb(self.post, self.points_count, stats)
@@ -662,6 +718,13 @@ def exemplars(dp_model, data, m, **kw):
         return p.exemplars(data, m, which=which)
 
 
+def typicality(dp_model, data, **kw):
+    """Labels, squared Mahalanobis distances and their calibrated tails (opens a Predictor, runs, closes): see `Predictor.typicality`;
+    kw: capacity, device, worker_factory, missing."""
+    with Predictor(dp_model, **kw) as p:
+        return p.typicality(data)
+
+
 def overlap(dp_model, data, **kw):
     """The overlap matrix of the clusters on `data` (opens a Predictor, runs, closes): see `Predictor.overlap`;
     kw: capacity, device, worker_factory, missing."""
@@ -671,10 +734,10 @@ def overlap(dp_model, data, **kw):
 
 def statistics(dp_model, data, **kw):
     """The per-cluster sufficient statistics of `data` under the model (opens a Predictor, runs, closes): see `Predictor.statistics`;
-    kw: assign, min_logdens, capacity, device, worker_factory, missing."""
-    assign, min_logdens = kw.pop("assign", "hard"), kw.pop("min_logdens", None)
+    kw: assign, min_logdens, min_tail, capacity, device, worker_factory, missing."""
+    assign, min_logdens, min_tail = kw.pop("assign", "hard"), kw.pop("min_logdens", None), kw.pop("min_tail", None)
     with Predictor(dp_model, **kw) as p:
-        return p.statistics(data, assign=assign, min_logdens=min_logdens)
+        return p.statistics(data, assign=assign, min_logdens=min_logdens, min_tail=min_tail)
 
 
 def count_statistics(dp_model, data, **kw):
