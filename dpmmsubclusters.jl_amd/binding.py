@@ -89,6 +89,8 @@ ABI = [
     ("dpmm_debug_subloglik", ctypes.c_int, [ctypes.c_void_p, _c_f32p]),
     ("dpmm_debug_ref_bracket", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_float, _c_f32p, _c_f32p]),
     ("dpmm_debug_pair_ball", ctypes.c_int, [ctypes.c_void_p, _c_f32p, _c_f32p]),
+    ("dpmm_debug_pair_ball_sn2", ctypes.c_int, [ctypes.c_void_p, _c_f32p]),
+    ("dpmm_debug_norm_cert_points", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_uint8)]),
     ("dpmm_debug_bracket_big", ctypes.c_int, [ctypes.c_void_p, _c_f32p, ctypes.POINTER(ctypes.c_uint32)]),
     ("dpmm_debug_mult_draws_ahead", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_longlong)]),
     ("dpmm_last_sweep_work", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
@@ -263,6 +265,8 @@ HOST_ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_voi
 # dpmm_set_option keys (include/dpmm_hip.h)
 MASTER_NSCALARS = 8          # DPMM_MASTER_NSCALARS
 OPT_SCREEN_MARGIN, OPT_TAIL_SCREEN, OPT_PRESCREEN, OPT_ORDERED_SWEEP, OPT_MULT_FORCE_F32, OPT_STATS_ITEMS, OPT_STATS_GROUPS, OPT_TRACE_SLOW, OPT_LOGLIK_REF_CONST, OPT_WAVE_PRIO, OPT_MULT_NO_U8, OPT_SWEEP_GRID, OPT_SWEEP_QUEUE_ROUNDS, OPT_BALL_SCREEN, OPT_KERNEL_TIMING, OPT_STATS_DERIVE, OPT_NOISE_AHEAD, OPT_REF_BRACKET, OPT_SORT_TILE, OPT_ONE_COLLECTIVE, OPT_BF16_SCREENS, OPT_COMM_TIMEOUT_MS, OPT_DIRECTION_SCREEN, _OPT_RESERVED_24, OPT_MULT_DRAWS_AHEAD, OPT_B3_SUBLABELS, OPT_LEAN_TILES, OPT_MASTER_POLL, OPT_CHAIN_FUSION, OPT_LEAN_DIRECTION, OPT_PAIR_BALL = range(1, 32)
+OPT_LEAN_NORM_CERT = 34      # DPMM_OPT_LEAN_NORM_CERT
+PB_MAXK = 256                # PB_MAXK (csrc/dpmm_kernels.h): the most clusters the pair-ball table, and with it the norm certificate, takes
 
 
 class DpmmError(RuntimeError):
@@ -1179,11 +1183,12 @@ class Worker:
         sp = 8 * ((self.K + 15) // 16)      # bf16 matrix instructions of one direction screen: two per 16 clusters and point group
         # executed_flops: Float32 matrix work only (= SQ_INSTS_VALU_MFMA_MOPS_F32 x 512); the bf16 work (brackets, screens) beside it
         dirs, b3 = v[15] & 0xFFFFFFFF, v[15] >> 32      # direction screens | bf16 three-plane sub-cluster evaluations (144 bf16 matrix instructions + 4 Float32 row sums each)
-        bf16 = v[8] * v[9] + v[11] * v[12] + v[13] * v[14] + dirs * sp + b3 * 144
+        tops, cheap = v[13] & 0xFFFFFFFF, v[13] >> 32  # bf16 top screens | tiles the lean kernel settled by the norm certificate (no bracket)
+        bf16 = v[8] * v[9] + v[11] * v[12] + tops * v[14] + dirs * sp + b3 * 144
         return dict(wave_tiles=v[0] / n, full_evals=v[1] / n, screens16=v[2] / n, tail_pairs=v[3] / n, mfma_per_full=v[4], mfma_per_screen=v[5],
                     flops_per_mfma=v[6], executed_flops=(v[1] * v[4] + v[2] * v[5] + 4 * b3) * v[6] / n, launches=v[7],
-                    brackets=v[8] / n, bf16_mfma_per_bracket=v[9], bf16_bottom_screens=v[11] / n, bf16_top_screens=v[13] / n,
-                    direction_screens=dirs / n, b3_evals=b3 / n,
+                    brackets=v[8] / n, bf16_mfma_per_bracket=v[9], bf16_bottom_screens=v[11] / n, bf16_top_screens=tops / n,
+                    direction_screens=dirs / n, b3_evals=b3 / n, norm_cert_tiles=cheap / n,
                     bf16_mfma=bf16 / n, bf16_flops=bf16 * v[10] / n)
 
     # ---- diagnostics
@@ -1204,6 +1209,19 @@ class Worker:
         pd = np.empty((self.K, self.K), np.float32); sn = np.empty(self.K, np.float32)
         self._chk(self._lib.dpmm_debug_pair_ball(self._h, _p(pd, _c_f32p), _p(sn, _c_f32p)))
         return pd, sn
+
+    def debug_pair_ball_sn2(self):
+        """sn2 (K,): the pair-ball table's tighter norm bounds (DPMM_OPT_LEAN_NORM_CERT); include/dpmm_hip_debug.h."""
+        sn2 = np.empty(self.K, np.float32)
+        self._chk(self._lib.dpmm_debug_pair_ball_sn2(self._h, _p(sn2, _c_f32p)))
+        return sn2
+
+    def debug_norm_cert_points(self, enable=True, read=True):
+        """bool (n,): the points whose tile the lean kernel's norm certificate settled in the sweeps since the record was last cleared (read=False, or
+        the record was off: None); then the record is cleared and stays on (enable) or is freed; include/dpmm_hip_debug.h."""
+        out = np.zeros(self.n, np.uint8) if read else None
+        self._chk(self._lib.dpmm_debug_norm_cert_points(self._h, int(bool(enable)), _p(out, ctypes.POINTER(ctypes.c_uint8)) if read else None))
+        return None if out is None else out.astype(bool)
 
     def debug_bracket_big(self):
         """(aref (n,), tile_flags (ceil(n / 128),)): what the D > 64 sweep reads from the bracket launch in front of it; include/dpmm_hip_debug.h."""

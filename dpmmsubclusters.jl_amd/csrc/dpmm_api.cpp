@@ -326,6 +326,8 @@ struct dpmm_ctx {
     int opt_b3 = 1;                    // DPMM_OPT_B3_SUBLABELS: D in 33..64: sub-cluster evaluations through three-plane bf16 images, in kernels of their own (niw_lean.hip)
     bool have_b3 = false;              // the images behind the bracket's in d_tail belong to the parameter set on the device
     int opt_chain = 0x7fffffff & ~(8 | 32);  // (bits 8 / 32: built, value-neutral, measured -- no gain at either size: off by default) DPMM_OPT_CHAIN_FUSION (bit mask): 1 = the sort's starts inside the scatter launch; 2 = the three-plane images in the hand-over launch; 4 = the fused pair jobs' list read from pinned memory; 8 = the bad-cluster reset counted ahead by the histogram and applied by the scatter (no reset launch); 16 = the draws' normals generated inside the posteriors' launch
+    DevBuf<uint8_t> d_cert_rec;        // dpmm_debug_norm_cert_points: a byte per point, set by niw_lean_kernel for the tiles its norm certificate settled (empty: no record)
+    int opt_lean_norm_cert = 1;        // DPMM_OPT_LEAN_NORM_CERT: niw_lean_kernel settles a tile by the norm bound of a_k0 + the pair-ball test where that suffices (no bracket)
     int opt_pair_ball = 1;             // DPMM_OPT_PAIR_BALL: the lean kernel's full-dimension ball test on the K x K table of pair distances (niw_pair_ball_kernel, K <= 256)
     bool have_pb = false;              // ... and that table belongs to the parameter set on the device
     int opt_lean_dir = 1;              // DPMM_OPT_LEAN_DIRECTION: the lean kernel runs the direction screen while its tables exist (0: no lean launch in that regime, as in rounds 4-5)
@@ -336,6 +338,9 @@ struct dpmm_ctx {
     int hard_flip = 0;
     int perm_nbins = 0;                // bins of the sort that wrote sb.perm / sb.bin_start (0: none yet): the lean kernel aligns its tiles to them
     PinBuf<uint32_t> h_hard;        // pinned: the count of the LAST sweep's list (read by the next sweep's regime decision, never waited for)
+    bool sn2_tight = false;            // the pair-ball table on the device has the tight sn2 block (else sn2 = sn)
+    bool cert_fb = false;              // the last lean launch ran the norm certificate and reported its settled tiles (h_need)
+    int cert_cool = 0;                 // parameter sets left without the tight block (the certificate settled too few tiles to pay for it)
     int lean_off = 0;                  // sweeps left without the lean kernel (a sweep that left more than 30 % of its tiles switches it off for lean_backoff)
     bool lean_ran = false;             // the last sweep ran the lean kernel: h_hard holds its list's length
     int lean_backoff = 15;             // 15, doubled by every retry that fails again (up to 1023), back to 15 by one that succeeds: a retry on overlapping
@@ -1211,6 +1216,24 @@ int dpmm_commit_params(dpmm_ctx *c, int K) {
 // after a change of K keep the usual order and count.
 static bool want_pair_ball(const dpmm_ctx *c, int K) { return c->opt_pair_ball && c->opt_ball && K >= 2 && K <= PB_MAXK; }      // (with the images: want_b3_images)
 static bool want_b3_images(const dpmm_ctx *c) { return c->prior == DPMM_PRIOR_NIW && c->NB == 4 && c->opt_b3 && c->have_tail && !c->predictive; }
+// The tight sn2 block of the pair-ball table costs the launch that writes it 19 us (hand-over 17.2 -> 36.1 us, K = 32 as K = 256: one workgroup per
+// cluster); a tile settled by the norm certificate saves the lean launch 0.58 ns of its time (60 us for 103 000 tiles at N = 1e7).  DPMM_OPT_LEAN_NORM_CERT
+// = 1 writes it only where that can come back: lean launch on, not the direction screen's regime (its instantiation runs no pair-ball test), at least
+// 2^22 points (break-even 3.2e6 at the headline's 66 %), and -- once a sweep has reported -- at least 2^15 tiles settled by the certificate in the last
+// sweep that had the block; else off for 63 parameter sets.  Without the block sn2 = sn and the certificate still runs, with the looser bound, for nothing.
+// Called once per parameter set, before the launch that writes the table.  (Whatever it answers, labels and sub-labels are the same.)
+static bool norm_tight(dpmm_ctx *c) {
+    if (c->opt_lean_norm_cert == 2) return true;
+    if (!c->opt_lean_norm_cert) return false;
+    if (c->cert_fb && c->sn2_tight) {
+        unsigned long long cheap = 0;
+        for (int w = 0; w < 4 * c->sweep_grid; ++w) cheap += c->h_need[8 * (size_t)c->sweep_grid_max + w] >> 16;
+        if (cheap < (1ull << 15)) c->cert_cool = 64;
+    }
+    c->cert_fb = false;
+    if (c->cert_cool > 0) { c->cert_cool -= 1; return false; }
+    return c->opt_lean != 0 && c->lean_off == 0 && !c->sp_regime && c->n >= (int64_t)1 << 22;
+}
 static int direction_tables(dpmm_ctx *c, int K, bool b3_done, bool pb_done) {
     c->sp_ready = false;
     c->have_refb_big = false;
@@ -1219,7 +1242,8 @@ static int direction_tables(dpmm_ctx *c, int K, bool b3_done, bool pb_done) {
         // the sub-cluster factors' bf16 planes + offsets (niw_lean.hip) -- b3_done: the hand-over launch wrote them (niw_master_pack_roles_kernel)
         // ... and the lean kernel's pair-ball table (same life as the images; one more row of workgroups of the same launch -- or a role of the hand-over launch)
         const bool pb = want_pair_ball(c, K);
-        const int what = (b3_done ? 0 : 1) | ((pb && !pb_done) ? 2 : 0);
+        if (pb && !pb_done) c->sn2_tight = norm_tight(c);
+        const int what = (b3_done ? 0 : 1) | ((pb && !pb_done) ? 2 : 0) | ((pb && !pb_done && c->sn2_tight) ? 4 : 0);
         if (what) HIPCHK(c, launch_niw_b3_pack(c->d_Rp, c->d_mup, K, c->d_tail, what, c->stream));
         c->have_b3 = true;
         c->have_pb = pb;
@@ -1240,7 +1264,7 @@ static int direction_tables(dpmm_ctx *c, int K, bool b3_done, bool pb_done) {
             const uint32_t v = c->h_need[2 * w];
             if (v & 0x8000u) { many_ub += v >> 16; tiles_ub += v & 0x7FFFu; } else { many += v >> 16; tiles += v & 0x7FFFu; }
             if (c->sp_last) { const uint32_t y = c->h_need[2 * w + 1]; given += y & 0xFFFFu; removed += y >> 16; }
-            tiles += c->h_need[8 * (size_t)c->sweep_grid_max + w];      // tiles niw_lean_kernel settled (no candidate behind the 4-row tests)
+            tiles += c->h_need[8 * (size_t)c->sweep_grid_max + w] & 0xFFFFu;      // tiles niw_lean_kernel settled (no candidate behind the 4-row tests)
             // ... and the tiles it settled WITH the direction screen: their candidates and the screen's yield, in the general kernel's format
             const uint32_t v3 = c->h_need[12 * (size_t)c->sweep_grid_max + 2 * w], y3 = c->h_need[12 * (size_t)c->sweep_grid_max + 2 * w + 1];
             if (v3 & 0x8000u) { many_ub += v3 >> 16; tiles_ub += v3 & 0x7FFFu; } else { many += v3 >> 16; tiles += v3 & 0x7FFFu; }
@@ -1458,7 +1482,11 @@ static int run_sweep(dpmm_ctx *c, uint32_t epoch, int final_argmax, float *table
                 uint32_t *need3 = a.need ? c->h_need + 12 * (size_t)c->sweep_grid_max : nullptr;
                 NiwSweepArgs al_args = a;
                 if (!c->opt_lean_dir) { al_args.sp_frag = nullptr; al_args.sp_cons = nullptr; }
-                if (c->have_pb && c->opt_pair_ball && al_args.ball) al_args.ball |= 2;      // (a bit of `ball`: a field of its own re-lays every kernel's scalars)
+                if (c->have_pb && c->opt_pair_ball && al_args.ball) al_args.ball |= c->opt_lean_norm_cert ? 6 : 2;      // (bits of `ball`: a field of its own re-lays every kernel's scalars)
+                c->cert_fb = need2 != nullptr && (al_args.ball & 4) != 0 && !(al_args.sp_frag && al_args.sp_cons);
+#ifndef DPMM_STAMPS
+                al_args.dbg = reinterpret_cast<unsigned long long *>(c->d_cert_rec.get());
+#endif
                 HIPCHK(c, launch_niw_lean(al_args, mine, need2, other, al ? c->sb.bin_start : nullptr, al ? c->perm_nbins : 0, need3, c->sweep_grid, c->stream));
                 if (parts) HIPCHK(c, hipEventRecord(c->ev_part[0], c->stream));
                 list = mine;
@@ -2356,8 +2384,9 @@ int dpmm_niw_master_draw(dpmm_ctx *c, uint32_t epoch, int K, const int32_t *slot
     c->predictive = false;              // (before the tables, as in set_params)
     // DPMM_OPT_CHAIN_FUSION bit 2: the hand-over partitioned by role, with the three-plane images in the same launch (no niw_b3_pack launch)
     const bool roles = (c->opt_chain & 2) != 0, b3_in_pack = roles && want_b3_images(c), pb_in_pack = b3_in_pack && want_pair_ball(c, K);
+    if (pb_in_pack) c->sn2_tight = norm_tight(c);
     HIPCHK(c, launch_niw_master_draw(ma, hs, K, epoch, c->d_Y[c->draw_cur], c->d_ld_sigma[c->draw_cur], hlr, hw, c->d_Rp, c->d_mup, c->d_cst,
-                                     c->have_tail ? c->d_tail : nullptr, c->NB, c->d_work, (ahead ? 2 : (normals ? 7 : 3)) | (roles ? 8 : 0) | (b3_in_pack ? 16 : 0) | (pb_in_pack ? 32 : 0), c->stream));
+                                     c->have_tail ? c->d_tail : nullptr, c->NB, c->d_work, (ahead ? 2 : (normals ? 7 : 3)) | (roles ? 8 : 0) | (b3_in_pack ? 16 : 0) | (pb_in_pack ? 32 : 0) | ((pb_in_pack && c->sn2_tight) ? 64 : 0), c->stream));
     if (int rc = direction_tables(c, K, b3_in_pack, pb_in_pack)) return rc;
     // The normals of the NEXT draws (epoch + 1, a few clusters more than now for the splits in between) into the other buffer, on the
     // second stream: they depend on nothing the master decides, and run beside the sweep instead of in front of it.  Whoever draws
@@ -2918,6 +2947,7 @@ int dpmm_set_option(dpmm_ctx *c, int option, double value) {
         case DPMM_OPT_BF16_SCREENS: c->opt_bf16scr = value != 0; return DPMM_OK;
         case DPMM_OPT_MASTER_POLL: c->opt_master_poll = value != 0; return DPMM_OK;
         case DPMM_OPT_PAIR_BALL: c->opt_pair_ball = value != 0; if (!c->opt_pair_ball) c->have_pb = false; return DPMM_OK;      // (ON takes effect with the next parameter set)
+        case DPMM_OPT_LEAN_NORM_CERT: c->opt_lean_norm_cert = value == 2 ? 2 : (value != 0); c->cert_cool = 0; c->cert_fb = false; return DPMM_OK;      // (the table's sn2 block follows with the next parameter set)
         case DPMM_OPT_LEAN_DIRECTION: c->opt_lean_dir = value != 0; c->lean_off = 0; c->lean_backoff = 15; c->lean_ran = false; return DPMM_OK;
         case DPMM_OPT_CHAIN_FUSION: c->opt_chain = value < 0 ? (0x7fffffff & ~(8 | 32)) : (int)value; return DPMM_OK;
         case DPMM_OPT_LEAN_TILES: c->opt_lean = value != 0; c->lean_off = 0; c->lean_backoff = 15; c->lean_ran = false; return DPMM_OK;
@@ -2973,17 +3003,18 @@ int dpmm_last_sweep_work(dpmm_ctx *c, uint64_t *out16) {
     std::vector<unsigned long long> h((size_t)DPMM_WORK_PER_WAVE * (size_t)c->work_waves);
     if (!h.empty()) HIPCHK(c, hipMemcpy(h.data(), c->d_work + DPMM_WORK_SLOTS, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost));
     for (int i = 0; i < 16; ++i) out16[i] = 0;
-    unsigned long long w7_lo = 0, w7_hi = 0;
+    unsigned long long w7_lo = 0, w7_hi = 0, w6_lo = 0, w6_hi = 0;
     for (size_t w = 0; w < (size_t)c->work_waves; ++w) {
         for (int i = 0; i < 4; ++i) out16[i] += h[DPMM_WORK_PER_WAVE * w + i];
         out16[8] += h[DPMM_WORK_PER_WAVE * w + 4];
         out16[11] += h[DPMM_WORK_PER_WAVE * w + 5];
-        out16[13] += h[DPMM_WORK_PER_WAVE * w + 6];
+        w6_lo += h[DPMM_WORK_PER_WAVE * w + 6] & 0xFFFFFFFFull; w6_hi += h[DPMM_WORK_PER_WAVE * w + 6] >> 32;      // (bf16 top screens | tiles settled by the norm certificate)
         // slot 7 packs two counters per wave -- low half: direction screens (8 bf16 matrix instructions per 16 clusters + 4 Float32 row sums
         // each); high half: bf16 three-plane sub-cluster evaluations (niw_lean.hip).  The halves are summed SEPARATELY over the waves (a raw
         // 64-bit sum lets the low halves' carry run into the evaluation count after a few thousand launches between two reads: ADVICE r5)
         w7_lo += h[DPMM_WORK_PER_WAVE * w + 7] & 0xFFFFFFFFull; w7_hi += h[DPMM_WORK_PER_WAVE * w + 7] >> 32;
     }
+    out16[13] = std::min<unsigned long long>(w6_lo, 0xFFFFFFFFull) | (std::min<unsigned long long>(w6_hi, 0xFFFFFFFFull) << 32);
     out16[15] = std::min<unsigned long long>(w7_lo, 0xFFFFFFFFull) | (std::min<unsigned long long>(w7_hi, 0xFFFFFFFFull) << 32);      // (each half saturates at 2^32 - 1)
     // totals of the launches since the previous call (out16[7] of them); the slots start again from zero
     const long long launches = c->work_launches;
@@ -3235,6 +3266,34 @@ int dpmm_debug_pair_ball(dpmm_ctx *c, float *pd, float *sn) {
     HIPCHK(c, hipMemcpyAsync(pd, t, sizeof(float) * K * K, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(sn, t + K * K, sizeof(float) * K, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, sync_stream(c, c->stream));
+    return DPMM_OK;
+}
+
+int dpmm_debug_pair_ball_sn2(dpmm_ctx *c, float *sn2) {
+    if (!c || !sn2) return DPMM_EINVAL;
+    if (c->prior != DPMM_PRIOR_NIW || c->NB != 4) return fail(c, DPMM_ESTATE, "the pair-ball table exists for the NIW prior with D in 33..64 only");
+    if (!c->have_params || !c->have_pb) return fail(c, DPMM_ESTATE, "no pair-ball table for the parameters on the device (DPMM_OPT_PAIR_BALL, 2 <= K <= 256, tail records)");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t K = (size_t)c->K;
+    HIPCHK(c, hipMemcpyAsync(sn2, c->d_tail + niw_pair_ball_offset(K) + K * K + K, sizeof(float) * K, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, sync_stream(c, c->stream));
+    return DPMM_OK;
+}
+
+int dpmm_debug_norm_cert_points(dpmm_ctx *c, int enable, uint8_t *flags) {
+    if (!c) return DPMM_EINVAL;
+    if (c->prior != DPMM_PRIOR_NIW || c->NB != 4) return fail(c, DPMM_ESTATE, "the norm certificate exists for the NIW prior with D in 33..64 only");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, sync_stream(c, c->stream));
+    const size_t nb = ((size_t)std::max<int64_t>(c->n, 1) + 7) & ~(size_t)7;
+    if (flags) {
+        if (!c->d_cert_rec) return fail(c, DPMM_ESTATE, "dpmm_debug_norm_cert_points: the record is not switched on");
+        HIPCHK(c, hipMemcpy(flags, c->d_cert_rec, (size_t)c->n, hipMemcpyDeviceToHost));
+    }
+    if (enable) {
+        if (!c->d_cert_rec || c->d_cert_rec.bytes != nb) HIPCHK(c, c->d_cert_rec.alloc(nb));
+        HIPCHK(c, hipMemset(c->d_cert_rec, 0, nb));
+    } else c->d_cert_rec.reset();
     return DPMM_OK;
 }
 

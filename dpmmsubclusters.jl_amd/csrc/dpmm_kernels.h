@@ -59,7 +59,8 @@ struct NiwSweepArgs {
     uint32_t *need;           // [waves][2] (pinned host memory, may be null): [0] = (candidates this wave's tiles kept behind the 4-row tests, saturating) << 16 | tiles
                               // (15 bits), bit 15: counted in FRONT of the tail-pair tests (direction screen first): an upper bound;
                               // [1] (written by the DIR kernel only) = (candidates its direction screens removed) << 16 | candidates they were given
-    unsigned long long *dbg;  // diagnostic builds only (DPMM_STAMPS): per-wave phase cycle sums
+    unsigned long long *dbg;  // diagnostic builds (DPMM_STAMPS): per-wave phase cycle sums; product build, lean launch only: a byte per point of the shard, set for the points of
+                              // the tiles the norm certificate settled (dpmm_debug_norm_cert_points; null unless that call switched the record on)
     int queue_rounds;         // D <= 64 kernel: rounds of tiles handed out through the queue at the end of the launch (-1: automatic)
     int prio;                 // 1: s_setprio -- low while the wave streams MFMAs, high in its scalar / VALU phases (DPMM_OPT_WAVE_PRIO)
     unsigned long long *work; // [4] tile queue head of the LDS-staged kernel, [8 + 16 q], q < 8: the eight queue heads of the D <= 64 kernel (one 128-byte
@@ -86,11 +87,16 @@ hipError_t launch_niw_refb_big(const float *Rp, int NB, int K, uint32_t *out, hi
 hipError_t launch_niw_bracket_big(int NB, const NiwSweepArgs &a, const uint32_t *refb, uint32_t *tile_flag, float *aref, hipStream_t s);
 // ---- niw_lean.hip: the bf16 three-plane evaluation of the sub-cluster quadratic forms (NB = 4)
 // images [3K][B3_WORDS] and offset vectors [3K][B3_DVEC] of the 2K sub-cluster factors from the Float32 fragment image, written behind the bracket's images in `tail`
-hipError_t launch_niw_b3_pack(const float *Rp, const float *mup, int K, float *tail, int what, hipStream_t s);      // what bit 0: images + offsets; bit 1: the pair-ball table (2 <= K <= PB_MAXK) behind them
+hipError_t launch_niw_b3_pack(const float *Rp, const float *mup, int K, float *tail, int what, hipStream_t s);      // what bit 0: images + offsets; bit 1: the pair-ball table (2 <= K <= PB_MAXK) behind them; bit 2: with the tight sn2 block (else sn2 = sn)
 // the pair-ball table behind the offsets (round 6; K <= PB_MAXK): pd [K][K] -- pd[k K + j] = a certified LOWER bound of |R_j (mu_k - mu_j)|, the distance of
 // cluster k's mean from cluster j's in j's own metric -- and sn [K], certified UPPER bounds of the spectral norms |R_j|_2 (niw_pair_ball_kernel, niw_lean.hip)
+// and sn2 [K] behind them: tighter certified upper bounds of the same norms (power bound, PB_NORM_SQUARINGS squarings of R' R in Float64; sn2 <= sn) for the lean kernel's norm certificate
 constexpr int PB_MAXK = 256;
-inline size_t niw_pair_ball_floats(size_t K) { return K <= (size_t)PB_MAXK ? K * K + K : 0; }
+#ifndef DPMM_PB_NORM_SQUARINGS
+#define DPMM_PB_NORM_SQUARINGS 3
+#endif
+constexpr int PB_NORM_SQUARINGS = DPMM_PB_NORM_SQUARINGS;      // (hand-over launch 17.2 us without the block; DESIGN 10 has the cost and the hit rate for 1, 2, 3)
+inline size_t niw_pair_ball_floats(size_t K) { return K <= (size_t)PB_MAXK ? K * K + 2 * K : 0; }
 inline size_t niw_pair_ball_offset(size_t K) { return 32 * ((K + 1) >> 1) + 16 * K + (size_t)REFB_WORDS * K + 3 * K * (size_t)B3_WORDS + 3 * K * (size_t)B3_DVEC; }      // floats from `tail` (= b3_offsets(tail, K) + 3 K B3_DVEC, niw_b3.h)
 inline size_t niw_tail_floats(size_t cap) {      // pair records | ball records | bracket images | b3 images | b3 offsets | pair-ball table
     return 16 * (cap + 2) + 16 * cap + (size_t)REFB_WORDS * cap + 3 * cap * (size_t)B3_WORDS + 3 * cap * (size_t)B3_DVEC + niw_pair_ball_floats(cap < (size_t)PB_MAXK ? cap : (size_t)PB_MAXK);

@@ -11,7 +11,7 @@ namespace dpmm {
 __host__ __device__ __forceinline__ const uint32_t *b3_images(const float *tail, int K) { return refb_records(tail, K) + (size_t)K * REFB_WORDS; }
 __host__ __device__ __forceinline__ const float *b3_offsets(const float *tail, int K) { return reinterpret_cast<const float *>(b3_images(tail, K) + (size_t)3 * K * B3_WORDS); }
 
-__host__ __device__ __forceinline__ const float *pair_ball_table(const float *tail, int K) { return b3_offsets(tail, K) + (size_t)3 * K * B3_DVEC; }      // pd [K][K] | sn [K] (= tail + niw_pair_ball_offset(K), dpmm_kernels.h)
+__host__ __device__ __forceinline__ const float *pair_ball_table(const float *tail, int K) { return b3_offsets(tail, K) + (size_t)3 * K * B3_DVEC; }      // pd [K][K] | sn [K] | sn2 [K] (= tail + niw_pair_ball_offset(K), dpmm_kernels.h)
 
 // One workgroup (256 threads) tabulates column j of the pair-ball table and s_j (niw_lean.hip: the test and its derivation).  elemR(row, col): R_j's
 // Float32 element for col >= row; mean(k, c): the Float32 cluster-level mean the sweep subtracts.
@@ -22,7 +22,7 @@ __host__ __device__ __forceinline__ const float *pair_ball_table(const float *ta
 // errors of a row add up to <= 5e-4 of the largest eigenvalue), 1e-4 s_j |v| comes off D, which is itself rounded DOWN by 1e-4.
 // (COLMAJOR: consecutive threads of the staging loop take consecutive ROWS of a column -- for a source stored column by column)
 template <bool COLMAJOR, class ElemR, class Mean>
-__device__ __forceinline__ void pair_ball_block(ElemR elemR, Mean mean, int K, int j, float *__restrict__ pd) {
+__device__ __forceinline__ void pair_ball_block(ElemR elemR, Mean mean, int K, int j, float *__restrict__ pd, bool tight) {
     float *sn = pd + (size_t)K * K;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     constexpr int LD = 68;                                  // (rows 16-byte aligned)
@@ -64,6 +64,88 @@ __device__ __forceinline__ void pair_ball_block(ElemR elemR, Mean mean, int K, i
         if (lane == 0) { const float sj = __builtin_sqrtf(mx) * 1.001f; s_sh = sj; sn[j] = (mx == mx && mx < INFINITY) ? sj : INFINITY; }
     }
     __syncthreads();
+    // sn2_j: a tighter certified bound of |R_j|_2 for the lean kernel's norm certificate (niw_lean.hip).  P = R' R in Float64 (the products of
+    // Float32 elements are exact there); for a symmetric positive semi-definite P, lambda_max(P)^(2^m) = lambda_max(P^(2^m)) <= |P^(2^m)|_inf, the
+    // largest row sum: PB_NORM_SQUARINGS squarings, thread (tr, tc) keeping its 4 x 4 block in registers and reading rows through LDS as above
+    // (P is symmetric: column a of row i is row a's element i).  In front of every squaring the matrix is scaled by a power of two (exact) so that
+    // its largest row sum lies in [1/2, 1): with Q_1 = P / c_0, Q_(s+1) = Q_s^2 / c_s:  lambda(Q_s)^2 = c_s lambda(Q_(s+1)), all equalities but the last
+    // step's row sum.  Slack: a Float64 dot product of 64 terms errs by <= 64 * 2^-53 of the sum of its terms' magnitudes: <= 7.2e-15 on a row sum
+    // of a scaled square, whose largest eigenvalue is >= (1/2 / sqrt(64))^2 = 1/256 -- 2e-12 relative per squaring, 4e-12 for P itself
+    // (| |R|' |R| |_inf <= 512 lambda_max); the square roots and the rounding to Float32 add < 1e-7.  The factor 1 + 1e-6 on s^2 covers all of it.
+    // `tight` (kernel-uniform) = the host expects the lean launch to earn the block's time back (19 us of the hand-over launch); without it
+    // sn2 = sn, a certified value as well (it is what the clamp falls back to).
+    if (!tight) {
+        if (tid == 0) sn[(size_t)K + j] = sn[j];
+    } else {
+        constexpr int M = PB_NORM_SQUARINGS;
+        __shared__ __attribute__((aligned(16))) double Pd[64 * 64];
+        __shared__ double rowsum_d[64];
+        const int tr = tid >> 4, tc = tid & 15;
+        double p[4][4];
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int b = 0; b < 4; ++b) p[a][b] = 0.0;
+#pragma unroll 4
+        for (int i = 0; i < 64; ++i) {
+            const f32x4 ra = *reinterpret_cast<const f32x4 *>(Rs + i * LD + 4 * tr), rb = *reinterpret_cast<const f32x4 *>(Rs + i * LD + 4 * tc);
+#pragma unroll
+            for (int a = 0; a < 4; ++a)
+#pragma unroll
+                for (int b = 0; b < 4; ++b) p[a][b] = __builtin_fma((double)ra[a], (double)rb[b], p[a][b]);
+        }
+        double cs[M];
+        double tnorm = 0.0;
+#pragma unroll
+        for (int step = 0; step <= M; ++step) {
+            double rs[4];
+#pragma unroll
+            for (int a = 0; a < 4; ++a) {
+                rs[a] = __builtin_fabs(p[a][0]) + __builtin_fabs(p[a][1]) + __builtin_fabs(p[a][2]) + __builtin_fabs(p[a][3]);
+#pragma unroll
+                for (int o = 8; o > 0; o >>= 1) rs[a] += __shfl_xor(rs[a], o);
+            }
+            if (tc == 0) { rowsum_d[4 * tr] = rs[0]; rowsum_d[4 * tr + 1] = rs[1]; rowsum_d[4 * tr + 2] = rs[2]; rowsum_d[4 * tr + 3] = rs[3]; }
+            __syncthreads();
+            double t = rowsum_d[lane];                      // (every wave: the largest row sum)
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) { const double u = __shfl_xor(t, o); t = (u > t || u != u) ? u : t; }
+            tnorm = t;
+            if (step == M) break;
+            int ex = 0;
+            if (t > 0.0 && t < INFINITY) frexp(t, &ex);
+            const double sc = ldexp(1.0, -ex);
+            if (step < M) cs[step] = ldexp(1.0, ex);
+#pragma unroll
+            for (int a = 0; a < 4; ++a) {
+                double2 lo, hi;
+                lo.x = p[a][0] * sc; lo.y = p[a][1] * sc; hi.x = p[a][2] * sc; hi.y = p[a][3] * sc;
+                *reinterpret_cast<double2 *>(Pd + (4 * tr + a) * 64 + 4 * tc) = lo;
+                *reinterpret_cast<double2 *>(Pd + (4 * tr + a) * 64 + 4 * tc + 2) = hi;
+                p[a][0] = 0.0; p[a][1] = 0.0; p[a][2] = 0.0; p[a][3] = 0.0;
+            }
+            __syncthreads();
+#pragma unroll 4
+            for (int i = 0; i < 64; ++i) {
+                const double2 a0 = *reinterpret_cast<const double2 *>(Pd + i * 64 + 4 * tr), a1 = *reinterpret_cast<const double2 *>(Pd + i * 64 + 4 * tr + 2);
+                const double2 b0 = *reinterpret_cast<const double2 *>(Pd + i * 64 + 4 * tc), b1 = *reinterpret_cast<const double2 *>(Pd + i * 64 + 4 * tc + 2);
+                const double qa[4] = {a0.x, a0.y, a1.x, a1.y}, qb[4] = {b0.x, b0.y, b1.x, b1.y};
+#pragma unroll
+                for (int a = 0; a < 4; ++a)
+#pragma unroll
+                    for (int b = 0; b < 4; ++b) p[a][b] = __builtin_fma(qa[a], qb[b], p[a][b]);
+            }
+        }
+        if (tid == 0) {
+            double bound = __builtin_sqrt(tnorm);
+#pragma unroll
+            for (int step = M - 1; step >= 1; --step) bound = __builtin_sqrt(cs[step] * bound);
+            bound *= cs[0];                                  // >= lambda_max(R' R) but for the roundings the slack covers
+            const float s2 = (float)(__builtin_sqrt(bound * (1.0 + 1e-6)) * (1.0 + 1e-7));
+            const float s1 = sn[j];
+            sn[(size_t)K + j] = (s2 == s2 && s2 < s1) ? s2 : s1;      // (clamped: sn2 <= sn; a NaN or an overflow leaves sn's value)
+        }
+    }
     const float sj = s_sh;
     const float mj = mean(j, lane);
     for (int k0 = w; k0 < K; k0 += 16) {                     // four clusters per trip and wave (wave-uniform): one LDS read of R per column serves all four

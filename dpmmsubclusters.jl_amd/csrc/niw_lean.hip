@@ -43,7 +43,7 @@ namespace dpmm {
 // ------------------------------------------------------------------------------------------------------------------ images
 // Three-plane bf16 images and offset vectors of the 2K sub-cluster factors from the Float32 fragment image both pack kernels write
 // (NB = 4: Rp [3K][10][64][4], mup [3K][64]); one workgroup per sub-cluster matrix.
-__global__ __launch_bounds__(256) void niw_b3_pack_kernel(const float *__restrict__ Rp, const float *__restrict__ mup, float *__restrict__ tail, int K, int y0) {
+__global__ __launch_bounds__(256) void niw_b3_pack_kernel(const float *__restrict__ Rp, const float *__restrict__ mup, float *__restrict__ tail, int K, int y0, int tight) {
     constexpr int NP = 10;
     uint32_t *img = const_cast<uint32_t *>(b3_images(tail, K));
     float *dvec = const_cast<float *>(b3_offsets(tail, K));
@@ -64,7 +64,7 @@ __global__ __launch_bounds__(256) void niw_b3_pack_kernel(const float *__restric
             const int bi = row >> 4, t = col >> 4;
             return Rk[(size_t)(pair_base<4>(bi) + (t - bi)) * 256 + ((row & 15) + 16 * ((col & 15) >> 2)) * 4 + (col & 3)];
         };
-        pair_ball_block<false>(elemR, [&](int kk, int c) -> float { return mup[(size_t)(3 * kk) * 64 + c]; }, K, k, const_cast<float *>(pair_ball_table(tail, K)));
+        pair_ball_block<false>(elemR, [&](int kk, int c) -> float { return mup[(size_t)(3 * kk) * 64 + c]; }, K, k, const_cast<float *>(pair_ball_table(tail, K)), tight != 0);
         return;
     }
     if (yy < 3) {                       // one plane of the matrix: 1536 dwords, six per thread
@@ -86,11 +86,11 @@ __global__ __launch_bounds__(256) void niw_b3_pack_kernel(const float *__restric
         if (part == 0) dvec[(size_t)j * B3_DVEC + row] = (float)acc;
     }
 }
-hipError_t launch_niw_b3_pack(const float *Rp, const float *mup, int K, float *tail, int what, hipStream_t s) {      // what bit 0: images + offsets, bit 1: the pair-ball table
+hipError_t launch_niw_b3_pack(const float *Rp, const float *mup, int K, float *tail, int what, hipStream_t s) {      // what bit 0: images + offsets, bit 1: the pair-ball table, bit 2: its sn2 block tight
     const bool pb = (what & 2) && K >= 2 && K <= PB_MAXK;
     if (K < 1 || !((what & 1) || pb)) return hipSuccess;
     const int y0 = (what & 1) ? 0 : 4, ny = (pb ? 5 : 4) - y0;
-    DPMM_LAUNCH(niw_b3_pack_kernel, dim3(2 * K, ny), dim3(256), 0, s, Rp, mup, tail, K, y0);
+    DPMM_LAUNCH(niw_b3_pack_kernel, dim3(2 * K, ny), dim3(256), 0, s, Rp, mup, tail, K, y0, (what & 4) ? 1 : 0);
     return hipGetLastError();
 }
 
@@ -294,7 +294,7 @@ __device__ __forceinline__ void niw_lean_body(NiwSweepArgs A, uint32_t *__restri
     const bool use_order = A.order != nullptr && *A.order_total == (int32_t)A.n;
     const int K = A.K;
     const int wave_id = (int)blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = (int)gridDim.x * 4;
-    unsigned nw_easy = 0, nw_br = 0, nw_tail = 0, nw_bb = 0;
+    unsigned nw_easy = 0, nw_br = 0, nw_tail = 0, nw_bb = 0, nw_cheap = 0;
     // THE DIRECTION SCREEN IN THIS KERNEL (round 6).  While the library keeps the screen's tables (overlapping clusters: tiles keep eight or more
     // candidates behind the 4-row tests; A.sp_frag / A.sp_cons, K <= 64) rounds 4-5 ran no lean launch at all: nothing settles without the screen,
     // and the two launches that took every tile instead cost 1.9 ms at N = 1e7 against 1.0.  The screen's operand is plane h of z0 = x - mu_k0 --
@@ -318,8 +318,17 @@ __device__ __forceinline__ void niw_lean_body(NiwSweepArgs A, uint32_t *__restri
     __shared__ float pb_s[PB_MAXK];
     const bool use_pb = !DIR && (A.ball & 2) != 0 && ball_in_lds && K <= PB_MAXK;
     const float *pb_d = pair_ball_table(A.tail, K);
+    // THE NORM CERTIFICATE (A.ball bit 2, DPMM_OPT_LEAN_NORM_CERT).  The bracket's only product is the threshold a_k0(x) - margin of the tests behind it, and
+    //     a_k0(x) = c0 - 1/2 |R_k0 z|^2 >= c0 - 1/2 (s_k0 r)^2     for |z| <= r, s_k0 >= |R_k0|_2
+    // needs nothing but the tile's radius r (pb_r below, certified from plane h) and the table's tighter norm bound sn2 (pair_ball_block).  Where the
+    // pair-ball test with THIS threshold leaves no candidate, the tile is settled without the bracket, its fragments, the ball and the tail pairs; any
+    // other tile takes the path below unchanged.  eps = 1e-4 (the bracket's own convention, 1.0001f): the Float32 quadratic form the threshold stands in for
+    // errs by <= 64 * 2^-24 | |R| |z| |, | |R| |_2 <= 8 |R|_2: a factor 1 + 3.1e-5 on |R z|, squared and summed in Float32: 1 + 6.6e-5; the four roundings
+    // of the expression itself add 2.4e-7.
+    __shared__ float pb_s2[PB_MAXK];
+    const bool use_cert = !DIR && use_pb && (A.ball & 4) != 0;
     if (use_pb)
-        for (int e = threadIdx.x; e < K; e += 256) pb_s[e] = pb_d[(size_t)K * K + e];
+        for (int e = threadIdx.x; e < K; e += 256) { pb_s[e] = pb_d[(size_t)K * K + e]; pb_s2[e] = pb_d[(size_t)K * K + K + e]; }
     if (ball_in_lds) {
         const float *src = ball_records(A.tail, K);
         for (int e = threadIdx.x; e < 16 * K; e += 256) ball_lds[e] = src[e];
@@ -396,6 +405,7 @@ __device__ __forceinline__ void niw_lean_body(NiwSweepArgs A, uint32_t *__restri
         B3Z Z;
         B3Head H;
         float u_sub = 0.f;
+        bool cheap = false;                                      // (wave-uniform) settled by the norm certificate
         if (!hard) {
             f32x4 xt = (f32x4){0.f, 0.f, 0.f, 0.f};
             f32x4 x3[4];                                           // the last 16 features (the bf16 bottom screens' operand)
@@ -449,13 +459,56 @@ __device__ __forceinline__ void niw_lean_body(NiwSweepArgs A, uint32_t *__restri
 #ifdef DPMM_STAMPS
             { LSTAMP(t2); s2 = t2; }
 #endif
+            const float c0 = A.cst[3 * k0];
+            // the pair-ball radius: r >= max |x - mu_k0| over the tile's points.  |z_h|^2 of 16 points at a time is the diagonal of the Gram matrix of
+            // plane h with itself (the lane's registers ARE both operands: row = column = lane & 15, the same eight features per lane group);
+            // |z| <= |z_h| / (1 - 2^-9) component by component, the products are exact, their Float32 sum of 64 non-negative terms errs by < 4e-6:
+            // the factor 1.005 covers both.  Point p of a group sits in lane group p / 4, register p % 4.  (A NaN of a point is kept: fmaxf would drop it.)
+            float pb_r = INFINITY;
+            if (use_pb) {
+                float m2 = 0.f;
+                bool nan_seen = false;
+#pragma unroll
+                for (int n = 0; n < 4; ++n) {
+                    f32x4 gq = (f32x4){0.f, 0.f, 0.f, 0.f};
+                    gq = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, Z.p[n][0][0]), __builtin_bit_cast(bf16x8_t, Z.p[n][0][0]), gq, 0, 0, 0);
+                    gq = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, Z.p[n][1][0]), __builtin_bit_cast(bf16x8_t, Z.p[n][1][0]), gq, 0, 0, 0);
+                    const float dsel = (ci & 2) ? ((ci & 1) ? gq[3] : gq[2]) : ((ci & 1) ? gq[1] : gq[0]);
+                    const bool mine = g == (ci >> 2) && 16 * n + ci < c_cn;
+                    m2 = fmaxf(m2, mine ? dsel : 0.f);
+                    nan_seen |= mine && !(dsel == dsel);
+                }
+                const float mx = wave_max_f32(m2);
+                pb_r = (mx == mx && __ballot(nan_seen) == 0ull) ? __builtin_amdgcn_sqrtf(mx) * 1.005f : INFINITY;
+            }
+            if constexpr (!DIR) {
+                if (use_cert && pb_r < INFINITY) {
+                    const float sr = pb_s2[k0] * pb_r;
+                    const float thr_cheap = __builtin_fmaf(-0.5f * sr, sr * 1.0001f, c0) - A.screen_margin;
+                    if (thr_cheap == thr_cheap && fabsf(thr_cheap) < INFINITY) {
+                        bool left = false;
+                        for (int base = 0; base < K && !left; base += 64) {
+                            unsigned long long cand = (K - base >= 64) ? ~0ull : ((1ull << (K - base)) - 1ull);
+                            if (k0 >= base && k0 < base + 64) cand &= ~(1ull << (k0 - base));
+                            const int j = base + lane, jj = j < K ? j : 0;
+                            const float dv = base == 0 ? pbv0 : pb_d[(size_t)k0 * K + jj];
+                            const float lb = fmaxf(__builtin_fmaf(-pb_s[jj], pb_r, dv), 0.f);
+                            const float ub = __builtin_fmaf(-0.5f * lb, lb, ball_lds[16 * jj + 15]);
+                            cand &= ~__ballot(j < K && ub < thr_cheap);
+                            left = cand != 0ull;
+                        }
+                        cheap = !left;
+                    }
+                }
+            }
+            if (cheap) ++nw_cheap;
+            else {
             float qhi[4];
             ref_bracket_planes(abr, Z, qhi);
             ++nw_br;
 #ifdef DPMM_STAMPS
             { LSTAMP(t3); s3 = t3; }
 #endif
-            const float c0 = A.cst[3 * k0];
             float my_best = -INFINITY;
             float thrb[4];                                         // per point group: threshold of the column's point (+inf for a column without a point)
 #pragma unroll
@@ -472,25 +525,7 @@ __device__ __forceinline__ void niw_lean_body(NiwSweepArgs A, uint32_t *__restri
             const bool thr_ok = use_pb && __ballot(valid && !(my_thr == my_thr)) == 0ull;       // (the pair-ball test's threshold: the wave's lowest)
             if (use_pb) thr_min = wave_min_f32(my_thr);
             else if (A.ball) { ball = ball_of_wave(A.tail, K, k0, xt, my_thr, valid); ball_made = true; }
-            // the pair-ball radius: r >= max |x - mu_k0| over the tile's points.  |z_h|^2 of 16 points at a time is the diagonal of the Gram matrix of
-            // plane h with itself (the lane's registers ARE both operands: row = column = lane & 15, the same eight features per lane group);
-            // |z| <= |z_h| / (1 - 2^-9) component by component, the products are exact, their Float32 sum of 64 non-negative terms errs by < 4e-6:
-            // the factor 1.005 covers both.  Point p of a group sits in lane group p / 4, register p % 4.
-            float pb_r = INFINITY;
-            if (thr_ok) {
-                float m2 = 0.f;
-#pragma unroll
-                for (int n = 0; n < 4; ++n) {
-                    f32x4 gq = (f32x4){0.f, 0.f, 0.f, 0.f};
-                    gq = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, Z.p[n][0][0]), __builtin_bit_cast(bf16x8_t, Z.p[n][0][0]), gq, 0, 0, 0);
-                    gq = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, Z.p[n][1][0]), __builtin_bit_cast(bf16x8_t, Z.p[n][1][0]), gq, 0, 0, 0);
-                    const float dsel = (ci & 2) ? ((ci & 1) ? gq[3] : gq[2]) : ((ci & 1) ? gq[1] : gq[0]);
-                    const bool mine = g == (ci >> 2) && 16 * n + ci < c_cn;
-                    m2 = fmaxf(m2, mine ? dsel : 0.f);
-                }
-                const float mx = wave_max_f32(m2);
-                pb_r = (mx == mx) ? __builtin_amdgcn_sqrtf(mx) * 1.005f : INFINITY;
-            }
+            if (!thr_ok) pb_r = INFINITY;                         // (the radius was formed in front of the norm certificate)
             for (int base = 0; base < K && !hard; base += 64) {
                 unsigned long long cand = (K - base >= 64) ? ~0ull : ((1ull << (K - base)) - 1ull);
                 if (k0 >= base && k0 < base + 64) cand &= ~(1ull << (k0 - base));
@@ -542,6 +577,7 @@ __device__ __forceinline__ void niw_lean_body(NiwSweepArgs A, uint32_t *__restri
                 hard = cand != 0ull;
                 if constexpr (DIR) { if (use_dir && !hard) { nw_cand += tile_cand; nw_sp += tile_sp; nw_dcand += tile_dc; nw_dexcl += tile_dx; ++nw_ctiles; } }
             }
+            }
         }
 #ifdef DPMM_STAMPS
         { LSTAMP(t4); s4 = t4; }
@@ -559,6 +595,9 @@ __device__ __forceinline__ void niw_lean_body(NiwSweepArgs A, uint32_t *__restri
             float bl, br;
             b3_eval(A.tail, K, k0, Z, H, lane, g, bl, br);
             if (valid) A.bins[myp32] = 2 * k0 + draw2(bl, br, u_sub);
+#ifndef DPMM_STAMPS
+            if (cheap && A.dbg && valid) reinterpret_cast<uint8_t *>(A.dbg)[myp32] = 1;      // (dpmm_debug_norm_cert_points: the points of the tiles settled by the certificate)
+#endif
             ++nw_easy;
         }
         nx_p = pf_p; nx_prev = label_of(pf_bin);
@@ -578,10 +617,12 @@ __device__ __forceinline__ void niw_lean_body(NiwSweepArgs A, uint32_t *__restri
     if (A.work && lane == 0) {
         unsigned long long *slot = A.work + DPMM_WORK_SLOTS + (size_t)wave_id * DPMM_WORK_PER_WAVE;      // (accumulates; cleared by the reader)
         slot[0] += nw_easy; slot[3] += nw_tail; slot[4] += nw_br; slot[5] += nw_bb; slot[7] += ((unsigned long long)(2 * nw_easy) << 32) + nw_sp;
+        slot[6] += (unsigned long long)nw_cheap << 32;        // (high half: tiles the norm certificate settled; the low half is the general kernel's top screens, added to the raw word there: 2^32 of them between two reads would carry into this count -- slot 7 has the same exposure)
     }
     // tiles settled here: without the screen they had no candidate behind the 4-row tests (need2: a plain count); with it, the candidates they had
     // and the screen's yield in the general kernel's two-word format (need3; bit 15: counted in front of the 4-row tests, an upper bound)
-    if (need2 && lane == 0) need2[wave_id] = use_dir ? 0u : (nw_easy < 65535u ? nw_easy : 65535u);
+    // (high half: the tiles the norm certificate settled -- the host's feedback on whether the tight sn2 block earns its time)
+    if (need2 && lane == 0) need2[wave_id] = use_dir ? 0u : ((nw_easy < 65535u ? nw_easy : 65535u) | ((nw_cheap < 65535u ? nw_cheap : 65535u) << 16));
     if (need3 && lane == 0) {
         uint32_t word = 0u, yield = 0u;
         if (use_dir) {

@@ -804,10 +804,10 @@ __global__ __launch_bounds__(256) void niw_master_pack_roles_kernel(const double
         const int j = (int)blockIdx.x - R.first[5];
         pair_ball_block<true>([&](int row, int col) -> float { return Rel(3 * (int64_t)j, row, col); },
                               [&](int kk, int c) -> float { return c < D ? mu_draw[(int64_t)(3 * kk) * DPm + c] : 0.f; }, K, j,
-                              const_cast<float *>(pair_ball_table(tail, K)));
+                              const_cast<float *>(pair_ball_table(tail, K)), (with_b3 & 2) != 0);
         return;
     }
-    if (!with_b3) return;
+    if (!(with_b3 & 1)) return;
     uint32_t *img = refb + (size_t)K * REFB_WORDS;                                         // = b3_images(tail, K)
     float *dvec = reinterpret_cast<float *>(img + (size_t)3 * K * B3_WORDS);              // = b3_offsets(tail, K)
     if (role == 3) {                       // the three planes of the 2K sub-cluster factors: one element pair -> three dwords
@@ -1288,7 +1288,7 @@ hipError_t launch_niw_master_draw(const NiwMasterArgs &a, const int32_t *slot_of
         const bool pb = b3 && (what & 32) && K >= 2 && K <= PB_MAXK;
         R.first[6] = R.first[5] + (pb ? K : 0);
         DPMM_LAUNCH(niw_master_pack_roles_kernel, dim3(R.first[6]), dim3(256), 0, s, Y, a.mu_draw, logdet_sigma, lr, wts, Rp, mup, cst, tail, a.D, a.DP, NB,
-                    nmat, work, R, b3 ? 1 : 0);
+                    nmat, work, R, (b3 ? 1 : 0) | ((what & 64) ? 2 : 0));      // (bit 1: the pair-ball table's sn2 block tight)
     } else if (what & 2) DPMM_LAUNCH(niw_master_pack_kernel, dim3(512), dim3(256), 0, s, Y, a.mu_draw, logdet_sigma, lr, wts, Rp, mup, cst, tail, a.D, a.DP, NB,
                                      3 * K, work);
     return hipGetLastError();

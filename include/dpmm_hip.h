@@ -35,7 +35,9 @@
 extern "C" {
 #endif
 
-#define DPMM_ABI_VERSION 3   /* 3 (round 5): dpmm_last_sweep_work fills 16 words (was 8 in version 2), DPMM_OPT_NOISE_AHEAD's -1 = automatic, options 18..27 */
+#define DPMM_ABI_VERSION 3   /* 3 (round 5): dpmm_last_sweep_work fills 16 words (was 8 in version 2), DPMM_OPT_NOISE_AHEAD's -1 = automatic, options 18..27.
+                                Since, without a new version: dpmm_last_sweep_work's out16[13] carries the bf16 top screens in its LOW 32 bits only (saturating) and the tiles
+                                settled by the norm certificate (DPMM_OPT_LEAN_NORM_CERT) in its high 32 bits, as out16[15] packs two counters: a raw reader masks it */
 
 typedef struct dpmm_ctx dpmm_ctx;
 
@@ -119,6 +121,14 @@ enum {
                                          metric -- and per cluster an upper bound of |R_j|_2; niw_lean_kernel then excludes cluster j for a whole tile of points
                                          within r of mu_k0 when cst_j - (D_k0,j - |R_j|_2 r)^2 / 2 is below the tile's lowest threshold: the ball test in all D
                                          features, one comparison per cluster and tile, in front of the 4-feature one.  0: without it.  Same labels and sub-labels. */
+    DPMM_OPT_LEAN_NORM_CERT = 34,     /* 1 (default): niw_lean_kernel, with the pair-ball table (DPMM_OPT_PAIR_BALL): a tile of points within r of mu_k0 has
+                                         a_k0(x) >= c0 - (s_k0 r)^2 / 2 for a certified s_k0 >= |R_k0|_2 (the table's third block sn2: a power bound, tighter than sn);
+                                         where the pair-ball test with that threshold already excludes every other cluster, the tile is settled without the
+                                         reference bracket, the ball test and the tail screens.  The tight sn2 costs the launch that writes the table 19 us per
+                                         parameter set: with 1 the library writes it only where the sweep can earn that back (lean launch on, outside the direction
+                                         screen's regime, >= 2^22 points, and >= 2^15 tiles settled by the certificate in the last sweep that had it; else sn2 = sn and
+                                         the certificate runs with the looser bound).  2: always the tight sn2.  0: every tile runs the bracket, sn2 = sn.
+                                         Same labels and sub-labels whatever the value. */
     DPMM_OPT_MULT_DRAWS_AHEAD = 25,   /* 1 (default): Multinomial device master: dpmm_step_stats launches the NEXT Dirichlet draws and their hand-over images
                                        * behind the statistics (the epoch after the last dpmm_mult_master_draw, the same K and outlier flag), into a second set of
                                        * buffers, and returns when the rows are on the host -- the draws run while the caller decides splits and merges.

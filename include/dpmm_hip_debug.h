@@ -37,6 +37,12 @@ int dpmm_debug_ref_bracket(dpmm_ctx *ctx, int64_t cluster, float c_override, flo
 /* The pair-ball table of the parameters on the device (DPMM_OPT_PAIR_BALL; NIW, D in 33..64, 2 <= K <= 256): pd [K][K], pd[k K + j] = the
  * tabulated lower bound of |R_j (mu_k - mu_j)|; sn [K] = the tabulated upper bounds of |R_j|_2.  Tests check both against Float64 values. */
 int dpmm_debug_pair_ball(dpmm_ctx *ctx, float *pd, float *sn);
+/* The table's third block (DPMM_OPT_LEAN_NORM_CERT): sn2 [K], certified upper bounds of |R_j|_2, sn2_j <= sn_j: the tight power bound where the library wrote it (see the option), else sn itself.  Same conditions. */
+int dpmm_debug_pair_ball_sn2(dpmm_ctx *ctx, float *sn2);
+/* Which points the norm certificate settled (DPMM_OPT_LEAN_NORM_CERT).  flags != NULL: copies the record out, flags[i] = 1 for local point i if a
+ * dpmm_sweep since the record was last cleared settled i's tile by the certificate (no bracket ran for it), else 0 (DPMM_ESTATE while the record is
+ * off).  Then enable != 0: the record is switched on (n bytes of device memory) and cleared; enable == 0: switched off and freed.  Synchronises. */
+int dpmm_debug_norm_cert_points(dpmm_ctx *ctx, int enable, uint8_t *flags);
 /* D = 65 .. 256 (the LDS-staged sweep kernels): the reference bracket runs as a launch of its own in front of the sweep (niw_bracket_big_kernel).
    This runs it on the current labels and parameters and returns what the sweep would read: tile_flags[ceil(n / 128)] = 1 + k0 (0-based k0)
    for a 128-point tile of the visiting order whose points all carry label k0 + 1, else 0; aref[n] = per POSITION of the visiting order
@@ -58,7 +64,8 @@ int dpmm_last_sweep_parts_ms(dpmm_ctx *ctx, float *out3);
 /* Work the dpmm_sweep calls (NIW) since the previous call really executed, counted on the device (a slot per wave, no atomics):
  *   TOTALS over out16[7] launches of: out16[0] wave tiles, [1] full quadratic-form evaluations (per wave), [2] Float32 16-row MFMA screens
  *   (per wave; an evaluation left after its first row block counts as four), [3] tail-screened cluster pairs (per wave), [8] reference
- *   brackets, [11] bf16 bottom screens, [13] bf16 top screens (per wave: bf16 matrix work, NOT part of the Float32 figure);
+ *   brackets, [11] bf16 bottom screens, [13] low 32 bits: bf16 top screens, high 32 bits: tiles niw_lean_kernel settled by the norm certificate
+ *   (DPMM_OPT_LEAN_NORM_CERT: no bracket ran for them) (per wave: bf16 matrix work, NOT part of the Float32 figure);
  *   [4] Float32 matrix instructions per full evaluation, [5] per 16-row screen, [6] flops per Float32 matrix instruction
  *   (v_mfma_f32_16x16x4_f32: 2048), [9] / [12] / [14] bf16 matrix instructions per bracket / bottom screen / top screen, [10] flops per
  *   bf16 matrix instruction (v_mfma_f32_16x16x32_bf16: 16384), [15] low 32 bits: direction screens, high 32 bits: bf16 three-plane
