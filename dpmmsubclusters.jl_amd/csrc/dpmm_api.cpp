@@ -59,6 +59,14 @@ thread_local std::string g_create_error;
 int nb_for_dim(int D) { return D <= 16 ? 1 : D <= 32 ? 2 : D <= 64 ? 4 : D <= 128 ? 8 : 16; }
 }  // namespace
 
+// What the *_begin of an accumulation over the score table (overlap, batchstats, countstats) leaves for its _accumulate and _read calls
+struct AccSession {
+    bool active = false;
+    int K = 0, mode = 0, floor = 0;      // K at the begin; the begin's arguments (overlap has none)
+    float min_logdens = 0.f;
+    unsigned long long gen = 0;          // pred_gen at the begin
+};
+
 struct dpmm_ctx {
     int prior = 0, D = 0, device = 0;
     int64_t n = 0, first = 0, ldx = 0;
@@ -143,17 +151,12 @@ struct dpmm_ctx {
     DevBuf<double> d_ov_acc;
     DevBuf<float2> d_ov_ms;
     DevBuf<double> d_ov_part;
-    bool ov_active = false;
-    int ov_K = 0;
-    unsigned long long ov_gen = 0;      // pred_gen at dpmm_overlap_begin
+    AccSession ov;
     // batch statistics (include/dpmm_hip_batchstats.h): N | sums | S | counters; two floats per point of one range; the chunk partials
     DevBuf<double> d_bs_acc;
     DevBuf<float2> d_bs_ms;
     DevBuf<double> d_bs_part;
-    bool bs_active = false;
-    int bs_K = 0, bs_mode = 0, bs_floor = 0;
-    float bs_min_logdens = 0.f;
-    unsigned long long bs_gen = 0;      // pred_gen at dpmm_batchstats_begin
+    AccSession bs;
     // calibrated outlier scores (include/dpmm_hip_typicality.h): class word and q per point of one range, the two counters; the tails of one
     // range for the hold-out of dpmm_batchstats_set_min_tail (allocated only when it is in use)
     DevBuf<int32_t> d_typ_cls;
@@ -167,10 +170,7 @@ struct dpmm_ctx {
     DevBuf<double> d_cs_acc;
     DevBuf<float2> d_cs_ms;
     DevBuf<double> d_cs_part;
-    bool cs_active = false;
-    int cs_K = 0, cs_mode = 0, cs_floor = 0;
-    float cs_min_logdens = 0.f;
-    unsigned long long cs_gen = 0;      // pred_gen at dpmm_countstats_begin
+    AccSession cs;
     // label trace (include/dpmm_hip_trace.h): slots rows of trace_nvec 16-byte vectors of ids; K per slot (0: never recorded); the device
     // images of a call's tables, descriptors, ratio tables and confidence
     DevBuf<uint16_t> d_trace;
@@ -3708,6 +3708,26 @@ static int miss_params(dpmm_ctx *c, const char *fn) {
     return DPMM_OK;
 }
 
+// The result of a table call's launches and copies as its return code (an int is one already)
+static int table_result(dpmm_ctx *c, const char *fn, hipError_t e) {
+    if (e != hipSuccess) { c->err = std::string(fn) + ": " + hipGetErrorString(e); return DPMM_EHIP; }
+    return DPMM_OK;
+}
+static int table_result(dpmm_ctx *, const char *, int rc) { return rc; }
+
+extern "C++" {      // down to the staging of the outputs: the templates among these helpers cannot have the C linkage of the block around them
+// What MissArgs and TypicalityArgs share: one range of the table (np points from point p0, rows P floats apart), its points, miss_params' copies
+template <class Args>
+static Args niw_range_args(dpmm_ctx *c, int64_t P, int64_t p0, int64_t np) {
+    const ParLayout L = par_layout(c, c->miss_slots);
+    Args a{};
+    a.table = c->d_score_table; a.stride = P; a.n = np; a.K = c->K; a.D = c->D;
+    a.X = c->dX + p0 * c->ldx; a.ldx = c->ldx;
+    a.Rt = c->d_miss_rt; a.mu = reinterpret_cast<const float *>(c->d_par + (L.mu - L.cst)); a.mu_step = 3 * (int64_t)c->D;
+    a.cst = c->d_miss_cst;
+    return a;
+}
+
 // Called once per table call, behind score_table_slab.  on: the call marginalises -- the device buffers exist afterwards (the list sized for
 // one range of P points), the copies of the parameters are those of the predictive set in force, the per-call counters are cleared.
 static int miss_begin(dpmm_ctx *c, bool on, int64_t P, const char *fn) {
@@ -3724,19 +3744,89 @@ static int miss_begin(dpmm_ctx *c, bool on, int64_t P, const char *fn) {
 // One range of the table (np points from point p0, rows P floats apart), just evaluated on the ctx stream: list, then patch.  out != null
 // (rows of the range's points, ld floats apart): the imputation behind them.
 static int miss_range(dpmm_ctx *c, int64_t P, int64_t p0, int64_t np, float *out, int64_t ld, const char *fn) {
-    const ParLayout L = par_layout(c, c->miss_slots);
-    MissArgs a{};
-    a.table = c->d_score_table; a.stride = P; a.n = np; a.K = c->K; a.D = c->D;
-    a.X = c->dX + p0 * c->ldx; a.ldx = c->ldx;
-    a.Rt = c->d_miss_rt; a.mu = reinterpret_cast<const float *>(c->d_par + (L.mu - L.cst)); a.mu_step = 3 * (int64_t)c->D;
-    a.cst = c->d_miss_cst; a.list = c->d_miss_list; a.cnt = c->d_miss_cnt; a.out = out; a.ld_out = ld;
+    MissArgs a = niw_range_args<MissArgs>(c, P, p0, np);
+    a.list = c->d_miss_list; a.cnt = c->d_miss_cnt; a.out = out; a.ld_out = ld;
     hipError_t e = hipMemsetAsync(c->d_miss_cnt, 0, sizeof(unsigned long long), c->stream);
     if (e == hipSuccess) e = launch_miss_list(a, c->stream);
     if (e == hipSuccess) e = launch_miss_patch(a, false, 8 * c->cus, c->stream);
     if (e == hipSuccess && out) e = launch_miss_patch(a, true, 8 * c->cus, c->stream);
-    if (e != hipSuccess) { c->err = std::string(fn) + ": " + hipGetErrorString(e); return DPMM_EHIP; }
+    return table_result(c, fn, e);
+}
+
+// ---- the walk every call over the score table makes: the table range by range, each range evaluated, patched where the call marginalises,
+// and handed to the call's consumer.  A new scoring call plugs in here.
+enum WalkMissing { WALK_MISS_NEVER, WALK_MISS_OPTION, WALK_MISS_ALWAYS };      // never (count data) | per DPMM_OPT_SCORE_MISSING | always (imputation)
+struct TableWalk {
+    int rstep = 0;       // cluster k is row k * rstep
+    int64_t P = 0;       // points of a range = floats between two rows of the table
+    bool miss = false;   // walk_ranges runs the missing-feature pass on every range
+};
+
+// The ctx's table grown to one range, then `size(P)` -- the refusals and per-range buffers of the call that go in front of the missing-feature
+// pass -- then that pass made ready (miss_begin).
+template <class Size>
+static int walk_open(dpmm_ctx *c, const char *fn, WalkMissing missing, TableWalk *w, Size size) {
+    if (int rc = score_table_slab(c, &w->rstep, &w->P)) return rc;
+    if (int rc = size(w->P)) return rc;
+    w->miss = missing == WALK_MISS_ALWAYS || (missing == WALK_MISS_OPTION && c->opt_score_missing != 0);
+    return miss_begin(c, w->miss, w->P, fn);
+}
+static int walk_open(dpmm_ctx *c, const char *fn, WalkMissing missing, TableWalk *w) {
+    return walk_open(c, fn, missing, w, [](int64_t) { return DPMM_OK; });
+}
+
+// The ranges that hold points 0 .. limit - 1 (limit = n_local for the per-point calls, n_valid for the accumulators), in order on the ctx
+// stream.  consume(p0, np, nv) -> int or hipError_t: the call's own launches for the range at point p0; np points were evaluated, the first nv
+// of them lie below the limit.
+template <class Consume>
+static int walk_ranges(dpmm_ctx *c, const TableWalk &w, int64_t limit, const char *fn, Consume consume) {
+    for (int64_t p0 = 0; p0 < limit; p0 += w.P) {
+        const int64_t np = std::min<int64_t>(w.P, c->n - p0);              // the range dpmm_score_points evaluates
+        if (int rc = run_sweep(c, 0, 0, c->d_score_table, w.P, p0, np)) return rc;
+        if (w.miss) if (int rc = miss_range(c, w.P, p0, np, nullptr, 0, fn)) return rc;
+        if (int rc = table_result(c, fn, consume(p0, np, std::min<int64_t>(np, limit - p0)))) return rc;      // (nv: what of the range the call consumes)
+    }
     return DPMM_OK;
 }
+
+// ---- outputs of a table call: written into the caller's device memory, or staged on the device and copied back to the caller's host memory.
+// A column is the caller's pointer (null: not asked for) and its bytes per element; in the staging buffer the columns follow each other in
+// list order, each block 8-byte aligned.
+struct OutCol {
+    void *dst;
+    size_t bytes;
+    size_t off = 0;
+};
+template <int N>
+struct OutStage {
+    OutCol col[N];
+    bool device;         // dst is device memory: nothing is staged
+    bool every = false;  // the kernel writes every column, also those not asked for (dpmm_rank_read)
+    char *buf = nullptr; // the staging buffer of layout(count) bytes
+    // bytes of the staging buffer for `count` elements per column
+    size_t layout(size_t count) {
+        size_t total = 0;
+        for (OutCol &q : col) { q.off = total; if (q.dst || every) total += (count * q.bytes + 7) & ~(size_t)7; }
+        return total;
+    }
+    // where the kernel writes column i for the elements from e0 on (null: not at all)
+    template <class T>
+    T *at(int i, int64_t e0) const {
+        const OutCol &q = col[i];
+        if (device) return q.dst ? reinterpret_cast<T *>(static_cast<char *>(q.dst) + (size_t)e0 * q.bytes) : nullptr;
+        return q.dst || every ? reinterpret_cast<T *>(buf + q.off) : nullptr;
+    }
+    // host variant, behind the launch: `count` elements of every column asked for to the caller's element e0, in list order; then the wait,
+    // since the blocks are rewritten by the next range
+    hipError_t flush(dpmm_ctx *c, int64_t e0, size_t count) const {
+        hipError_t e = hipSuccess;
+        for (const OutCol &q : col)
+            if (e == hipSuccess && q.dst) e = hipMemcpyAsync(static_cast<char *>(q.dst) + (size_t)e0 * q.bytes, buf + q.off, count * q.bytes, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = sync_stream(c, c->stream);
+        return e;
+    }
+};
+}  // extern "C++"
 
 static int score_points(dpmm_ctx *c, const dpmm_score_out *o, bool device, const char *fn) {
     if (!c) return tensor_no_ctx(fn);
@@ -3760,58 +3850,24 @@ static int score_points(dpmm_ctx *c, const dpmm_score_out *o, bool device, const
         if (o->top_prob) if (int rc = check_device_extent(c, fn, "top_prob", o->top_prob, sizeof(float) * n * m, sizeof(float))) return rc;
         if (o->probs) if (int rc = check_device_extent(c, fn, "probs", o->probs, sizeof(float) * n * K, sizeof(float))) return rc;
     }
-    int rstep = 0;
-    int64_t P = 0;
-    if (int rc = score_table_slab(c, &rstep, &P)) return rc;
-    const bool miss = c->opt_score_missing != 0;
-    if (int rc = miss_begin(c, miss, P, fn)) return rc;
-    // host variant: the slab's outputs on the device, one block per output (each 8-byte aligned)
-    size_t off_lab = 0, off_ld = 0, off_ti = 0, off_tp = 0, off_pr = 0, total = 0;
+    TableWalk w;
+    if (int rc = walk_open(c, fn, WALK_MISS_OPTION, &w)) return rc;
+    OutStage<5> out{{{o->labels, sizeof(int64_t)}, {o->logdens, sizeof(float)}, {o->top_idx, sizeof(int64_t) * m}, {o->top_prob, sizeof(float) * m},
+                     {o->probs, sizeof(float) * K}}, device};
     if (!device) {
-        auto take = [&](bool want, size_t bytes_per_point) { const size_t at = total; if (want) total += ((size_t)P * bytes_per_point + 7) & ~(size_t)7; return at; };
-        off_lab = take(o->labels != nullptr, sizeof(int64_t));
-        off_ld = take(o->logdens != nullptr, sizeof(float));
-        off_ti = take(o->top_idx != nullptr, sizeof(int64_t) * m);
-        off_tp = take(o->top_prob != nullptr, sizeof(float) * m);
-        off_pr = take(o->probs != nullptr, sizeof(float) * K);
-        if (int rc = grow(c, c->d_score_out, total, "dpmm_score_points", "staging of the outputs")) return rc;
+        if (int rc = grow(c, c->d_score_out, out.layout((size_t)w.P), "dpmm_score_points", "staging of the outputs")) return rc;
+        out.buf = c->d_score_out;
     }
-    for (int64_t p0 = 0; p0 < c->n; p0 += P) {
-        const int64_t np = std::min<int64_t>(P, c->n - p0);
-        if (int rc = run_sweep(c, 0, 0, c->d_score_table, P, p0, np)) return rc;
-        if (miss) if (int rc = miss_range(c, P, p0, np, nullptr, 0, fn)) return rc;
-        ScoreArgs a{};
-        a.table = c->d_score_table; a.stride = P; a.rstep = rstep; a.n = np; a.K = c->K; a.m = o->m;
-        if (device) {
-            a.labels = o->labels ? o->labels + p0 : nullptr;
-            a.logdens = o->logdens ? o->logdens + p0 : nullptr;
-            a.top_idx = o->top_idx ? o->top_idx + p0 * o->m : nullptr;
-            a.top_prob = o->top_prob ? o->top_prob + p0 * o->m : nullptr;
-            a.probs = o->probs ? o->probs + p0 * (int64_t)c->K : nullptr;
-        } else {
-            a.labels = o->labels ? reinterpret_cast<int64_t *>(c->d_score_out + off_lab) : nullptr;
-            a.logdens = o->logdens ? reinterpret_cast<float *>(c->d_score_out + off_ld) : nullptr;
-            a.top_idx = o->top_idx ? reinterpret_cast<int64_t *>(c->d_score_out + off_ti) : nullptr;
-            a.top_prob = o->top_prob ? reinterpret_cast<float *>(c->d_score_out + off_tp) : nullptr;
-            a.probs = o->probs ? reinterpret_cast<float *>(c->d_score_out + off_pr) : nullptr;
-        }
-        hipError_t e = launch_score_finish(a, c->stream);
-        if (e == hipSuccess && !device) {
-            const size_t q = (size_t)np;
-            if (o->labels) e = hipMemcpyAsync(o->labels + p0, a.labels, sizeof(int64_t) * q, hipMemcpyDeviceToHost, c->stream);
-            if (e == hipSuccess && o->logdens) e = hipMemcpyAsync(o->logdens + p0, a.logdens, sizeof(float) * q, hipMemcpyDeviceToHost, c->stream);
-            if (e == hipSuccess && o->top_idx) e = hipMemcpyAsync(o->top_idx + p0 * o->m, a.top_idx, sizeof(int64_t) * q * m, hipMemcpyDeviceToHost, c->stream);
-            if (e == hipSuccess && o->top_prob) e = hipMemcpyAsync(o->top_prob + p0 * o->m, a.top_prob, sizeof(float) * q * m, hipMemcpyDeviceToHost, c->stream);
-            if (e == hipSuccess && o->probs) e = hipMemcpyAsync(o->probs + p0 * (int64_t)c->K, a.probs, sizeof(float) * q * K, hipMemcpyDeviceToHost, c->stream);
-            if (e == hipSuccess) e = sync_stream(c, c->stream);      // the staging block is rewritten by the next slab
-        }
-        if (e != hipSuccess) { c->err = who + hipGetErrorString(e); return DPMM_EHIP; }
-    }
-    if (device) {
-        hipError_t e = sync_stream(c, c->stream);
-        if (e != hipSuccess) { c->err = who + hipGetErrorString(e); return DPMM_EHIP; }
-    }
-    return DPMM_OK;
+    if (int rc = walk_ranges(c, w, c->n, fn, [&](int64_t p0, int64_t np, int64_t) {
+            ScoreArgs a{};
+            a.table = c->d_score_table; a.stride = w.P; a.rstep = w.rstep; a.n = np; a.K = c->K; a.m = o->m;
+            a.labels = out.at<int64_t>(0, p0); a.logdens = out.at<float>(1, p0);
+            a.top_idx = out.at<int64_t>(2, p0); a.top_prob = out.at<float>(3, p0); a.probs = out.at<float>(4, p0);
+            hipError_t e = launch_score_finish(a, c->stream);
+            if (e == hipSuccess && !device) e = out.flush(c, p0, (size_t)np);
+            return e;
+        })) return rc;
+    return device ? table_result(c, fn, sync_stream(c, c->stream)) : DPMM_OK;
 }
 
 int dpmm_score_points(dpmm_ctx *c, const dpmm_score_out *out) { return score_points(c, out, false, "dpmm_score_points"); }
@@ -3843,15 +3899,9 @@ static int typ_begin(dpmm_ctx *c, int64_t P, const char *fn) {
 // One range of the table (np points from point p0, rows P floats apart), just evaluated (and patched) on the ctx stream.  labels, q, tail:
 // device memory of np entries or null; q == null: the ctx's scratch.  The counters are added to.
 static int typ_range(dpmm_ctx *c, int64_t P, int64_t p0, int64_t np, int64_t *labels, float *q, float *tail, const char *fn) {
-    const ParLayout L = par_layout(c, c->miss_slots);
-    TypicalityArgs a{};
-    a.table = c->d_score_table; a.stride = P; a.n = np; a.K = c->K; a.D = c->D;
-    a.X = c->dX + p0 * c->ldx; a.ldx = c->ldx;
-    a.Rt = c->d_miss_rt; a.mu = reinterpret_cast<const float *>(c->d_par + (L.mu - L.cst)); a.mu_step = 3 * (int64_t)c->D;
-    a.cst = c->d_miss_cst; a.cls = c->d_typ_cls; a.labels = labels; a.q = q ? q : c->d_typ_q.get(); a.tail = tail; a.cnt = c->d_typ_cnt;
-    const hipError_t e = launch_typicality_range(a, 32 * c->cus, c->stream);
-    if (e != hipSuccess) { c->err = std::string(fn) + ": " + hipGetErrorString(e); return DPMM_EHIP; }
-    return DPMM_OK;
+    TypicalityArgs a = niw_range_args<TypicalityArgs>(c, P, p0, np);
+    a.cls = c->d_typ_cls; a.labels = labels; a.q = q ? q : c->d_typ_q.get(); a.tail = tail; a.cnt = c->d_typ_cnt;
+    return table_result(c, fn, launch_typicality_range(a, 32 * c->cus, c->stream));
 }
 
 static int typicality_points(dpmm_ctx *c, const dpmm_typicality_out *o, bool device, const char *fn) {
@@ -3873,40 +3923,19 @@ static int typicality_points(dpmm_ctx *c, const dpmm_typicality_out *o, bool dev
         if (o->mahalanobis) if (int rc = check_device_extent(c, fn, "mahalanobis", o->mahalanobis, sizeof(float) * n, sizeof(float))) return rc;
         if (o->tail) if (int rc = check_device_extent(c, fn, "tail", o->tail, sizeof(float) * n, sizeof(float))) return rc;
     }
-    int rstep = 0;
-    int64_t P = 0;
-    if (int rc = score_table_slab(c, &rstep, &P)) return rc;
-    const bool miss = c->opt_score_missing != 0;
-    if (int rc = miss_begin(c, miss, P, fn)) return rc;
-    if (int rc = typ_begin(c, P, fn)) return rc;
+    TableWalk w;
+    if (int rc = walk_open(c, fn, WALK_MISS_OPTION, &w)) return rc;
+    if (int rc = typ_begin(c, w.P, fn)) return rc;
     HIPCHK(c, hipMemsetAsync(c->d_typ_cnt, 0, 2 * sizeof(unsigned long long), c->stream));
-    // host variant: the range's outputs on the device, one block per output (each 8-byte aligned)
-    size_t off_lab = 0, off_q = 0, off_t = 0, total = 0;
+    OutStage<3> out{{{o->labels, sizeof(int64_t)}, {o->mahalanobis, sizeof(float)}, {o->tail, sizeof(float)}}, device};
     if (!device) {
-        auto take = [&](bool want, size_t bytes_per_point) { const size_t at = total; if (want) total += ((size_t)P * bytes_per_point + 7) & ~(size_t)7; return at; };
-        off_lab = take(o->labels != nullptr, sizeof(int64_t));
-        off_q = take(o->mahalanobis != nullptr, sizeof(float));
-        off_t = take(o->tail != nullptr, sizeof(float));
-        if (int rc = grow(c, c->d_score_out, total, "dpmm_score_points", "staging of the outputs")) return rc;
+        if (int rc = grow(c, c->d_score_out, out.layout((size_t)w.P), "dpmm_score_points", "staging of the outputs")) return rc;
+        out.buf = c->d_score_out;
     }
-    for (int64_t p0 = 0; p0 < c->n; p0 += P) {
-        const int64_t np = std::min<int64_t>(P, c->n - p0);
-        if (int rc = run_sweep(c, 0, 0, c->d_score_table, P, p0, np)) return rc;
-        if (miss) if (int rc = miss_range(c, P, p0, np, nullptr, 0, fn)) return rc;
-        int64_t *lab = !o->labels ? nullptr : device ? o->labels + p0 : reinterpret_cast<int64_t *>(c->d_score_out + off_lab);
-        float *q = !o->mahalanobis ? nullptr : device ? o->mahalanobis + p0 : reinterpret_cast<float *>(c->d_score_out + off_q);
-        float *tl = !o->tail ? nullptr : device ? o->tail + p0 : reinterpret_cast<float *>(c->d_score_out + off_t);
-        if (int rc = typ_range(c, P, p0, np, lab, q, tl, fn)) return rc;
-        if (!device) {
-            const size_t z = (size_t)np;
-            hipError_t e = hipSuccess;
-            if (o->labels) e = hipMemcpyAsync(o->labels + p0, lab, sizeof(int64_t) * z, hipMemcpyDeviceToHost, c->stream);
-            if (e == hipSuccess && o->mahalanobis) e = hipMemcpyAsync(o->mahalanobis + p0, q, sizeof(float) * z, hipMemcpyDeviceToHost, c->stream);
-            if (e == hipSuccess && o->tail) e = hipMemcpyAsync(o->tail + p0, tl, sizeof(float) * z, hipMemcpyDeviceToHost, c->stream);
-            if (e == hipSuccess) e = sync_stream(c, c->stream);      // the staging block is rewritten by the next range
-            if (e != hipSuccess) { c->err = who + hipGetErrorString(e); return DPMM_EHIP; }
-        }
-    }
+    if (int rc = walk_ranges(c, w, c->n, fn, [&](int64_t p0, int64_t np, int64_t) -> int {
+            if (int rc = typ_range(c, w.P, p0, np, out.at<int64_t>(0, p0), out.at<float>(1, p0), out.at<float>(2, p0), fn)) return rc;
+            return device ? DPMM_OK : table_result(c, fn, out.flush(c, p0, (size_t)np));
+        })) return rc;
     HIPCHK(c, sync_stream(c, c->stream));
     unsigned long long h[2] = {0, 0};
     HIPCHK(c, hipMemcpy(h, c->d_typ_cnt, sizeof(h), hipMemcpyDeviceToHost));
@@ -3931,25 +3960,23 @@ static int impute_points(dpmm_ctx *c, float *out, int64_t ld, bool device, const
     if (!c->have_points || !c->have_params || !c->dX) return fail(c, DPMM_ESTATE, who + "needs points and parameters");
     if (!out) return fail(c, DPMM_EINVAL, who + "out is null");
     if (device) if (int rc = check_device_extent(c, fn, "d_out", out, (uint64_t)c->n * (uint64_t)ld * sizeof(float), sizeof(float))) return rc;
-    int rstep = 0;
-    int64_t P = 0;
-    if (int rc = score_table_slab(c, &rstep, &P)) return rc;
-    if (int rc = miss_begin(c, true, P, fn)) return rc;
-    const int64_t D = c->D;
+    TableWalk w;
+    if (int rc = walk_open(c, fn, WALK_MISS_ALWAYS, &w)) return rc;
+    w.miss = false;      // the consumer patches: the rows the imputation is written behind are copied first
+    const int64_t P = w.P, D = c->D;
     if (!device) if (int rc = grow(c, c->d_score_out, sizeof(float) * (size_t)P * (size_t)D, "dpmm_score_points", "staging of the outputs")) return rc;
-    for (int64_t p0 = 0; p0 < c->n; p0 += P) {
-        const int64_t np = std::min<int64_t>(P, c->n - p0);
-        if (int rc = run_sweep(c, 0, 0, c->d_score_table, P, p0, np)) return rc;
-        float *rows = device ? out + p0 * ld : reinterpret_cast<float *>(c->d_score_out.get());
-        const int64_t ldr = device ? ld : D;
-        HIPCHK(c, launch_points_readback(rows, ldr, c->dX + p0 * c->ldx, c->ldx, nullptr, 0, np, c->D, c->stream));
-        if (int rc = miss_range(c, P, p0, np, rows, ldr, fn)) return rc;
-        if (!device) {
-            HIPCHK(c, hipMemcpy2DAsync(out + p0 * ld, sizeof(float) * (size_t)ld, rows, sizeof(float) * (size_t)D, sizeof(float) * (size_t)D, (size_t)np, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, sync_stream(c, c->stream));      // the staging block is rewritten by the next range
-            if (ld > D) for (int64_t i = p0; i < p0 + np; ++i) memset(out + i * ld + D, 0, sizeof(float) * (size_t)(ld - D));
-        }
-    }
+    if (int rc = walk_ranges(c, w, c->n, fn, [&](int64_t p0, int64_t np, int64_t) -> int {
+            float *rows = device ? out + p0 * ld : reinterpret_cast<float *>(c->d_score_out.get());
+            const int64_t ldr = device ? ld : D;
+            HIPCHK(c, launch_points_readback(rows, ldr, c->dX + p0 * c->ldx, c->ldx, nullptr, 0, np, c->D, c->stream));
+            if (int rc = miss_range(c, P, p0, np, rows, ldr, fn)) return rc;
+            if (!device) {
+                HIPCHK(c, hipMemcpy2DAsync(out + p0 * ld, sizeof(float) * (size_t)ld, rows, sizeof(float) * (size_t)D, sizeof(float) * (size_t)D, (size_t)np, hipMemcpyDeviceToHost, c->stream));
+                HIPCHK(c, sync_stream(c, c->stream));      // the staging block is rewritten by the next range
+                if (ld > D) for (int64_t i = p0; i < p0 + np; ++i) memset(out + i * ld + D, 0, sizeof(float) * (size_t)(ld - D));
+            }
+            return DPMM_OK;
+        })) return rc;
     HIPCHK(c, sync_stream(c, c->stream));
     return DPMM_OK;
 }
@@ -3985,51 +4012,43 @@ static int impute_draw_points(dpmm_ctx *c, float *out, int64_t ld, int64_t draw_
         if (int rc = check_device_extent(c, fn, "d_out", out, words * sizeof(float), sizeof(float))) return rc;
         if (comp) if (int rc = check_device_extent(c, fn, "d_comp", comp, (uint64_t)ndraws * (uint64_t)n * sizeof(int32_t), sizeof(int32_t))) return rc;
     }
-    int rstep = 0;
-    int64_t P = 0;
-    if (int rc = score_table_slab(c, &rstep, &P)) return rc;
-    if (int rc = miss_begin(c, true, P, fn)) return rc;
+    TableWalk tw;
+    if (int rc = walk_open(c, fn, WALK_MISS_ALWAYS, &tw)) return rc;
+    const int64_t P = tw.P;
     int64_t batch = ndraws;
     if (!device) {
         batch = std::max<int64_t>(1, std::min<int64_t>(ndraws, ((int64_t)64 << 20) / ((int64_t)sizeof(float) * P * D)));
         if (int rc = grow(c, c->d_score_out, (size_t)batch * (size_t)P * (sizeof(float) * (size_t)D + sizeof(int32_t)), "dpmm_score_points", "staging of the outputs")) return rc;
     }
-    const ParLayout L = par_layout(c, c->miss_slots);
-    for (int64_t p0 = 0; p0 < n; p0 += P) {
-        const int64_t np = std::min<int64_t>(P, n - p0);
-        if (int rc = run_sweep(c, 0, 0, c->d_score_table, P, p0, np)) return rc;
-        if (int rc = miss_range(c, P, p0, np, nullptr, 0, fn)) return rc;
-        MissArgs a{};      // (as miss_range)
-        a.table = c->d_score_table; a.stride = P; a.n = np; a.K = c->K; a.D = c->D;
-        a.X = c->dX + p0 * c->ldx; a.ldx = c->ldx;
-        a.Rt = c->d_miss_rt; a.mu = reinterpret_cast<const float *>(c->d_par + (L.mu - L.cst)); a.mu_step = 3 * D;
-        a.cst = c->d_miss_cst; a.list = c->d_miss_list; a.cnt = c->d_miss_cnt;
-        for (int64_t j0 = 0; j0 < ndraws; j0 += batch) {
-            const int64_t nb = std::min(batch, ndraws - j0);
-            MissDraw w{};
-            w.seed = seed; w.i0 = i0 + p0; w.draw0 = draw0 + j0; w.ndraws = (int)nb;
-            if (device) {
-                w.out = out + j0 * draw_stride + p0 * ld; w.ld = ld; w.draw_stride = draw_stride;
-                w.comp = comp ? comp + j0 * n + p0 : nullptr; w.comp_stride = n;
-            } else {
-                w.out = reinterpret_cast<float *>(c->d_score_out.get()); w.ld = D; w.draw_stride = np * D;
-                w.comp = comp ? reinterpret_cast<int32_t *>(w.out + batch * P * D) : nullptr; w.comp_stride = np;
+    if (int rc = walk_ranges(c, tw, n, fn, [&](int64_t p0, int64_t np, int64_t) -> int {
+            MissArgs a = niw_range_args<MissArgs>(c, P, p0, np);
+            a.list = c->d_miss_list; a.cnt = c->d_miss_cnt;      // the list the walk's pass has just made of this range
+            for (int64_t j0 = 0; j0 < ndraws; j0 += batch) {
+                const int64_t nb = std::min(batch, ndraws - j0);
+                MissDraw w{};
+                w.seed = seed; w.i0 = i0 + p0; w.draw0 = draw0 + j0; w.ndraws = (int)nb;
+                if (device) {
+                    w.out = out + j0 * draw_stride + p0 * ld; w.ld = ld; w.draw_stride = draw_stride;
+                    w.comp = comp ? comp + j0 * n + p0 : nullptr; w.comp_stride = n;
+                } else {
+                    w.out = reinterpret_cast<float *>(c->d_score_out.get()); w.ld = D; w.draw_stride = np * D;
+                    w.comp = comp ? reinterpret_cast<int32_t *>(w.out + batch * P * D) : nullptr; w.comp_stride = np;
+                }
+                if (int rc = table_result(c, fn, launch_miss_draw(a, w, 8 * c->cus, c->stream))) return rc;
+                if (!device) {
+                    for (int64_t jd = 0; jd < nb; ++jd)
+                        HIPCHK(c, hipMemcpy2DAsync(out + (j0 + jd) * draw_stride + p0 * ld, sizeof(float) * (size_t)ld, w.out + jd * np * D, sizeof(float) * (size_t)D,
+                                                   sizeof(float) * (size_t)D, (size_t)np, hipMemcpyDeviceToHost, c->stream));
+                    if (comp) HIPCHK(c, hipMemcpy2DAsync(comp + j0 * n + p0, sizeof(int32_t) * (size_t)n, w.comp, sizeof(int32_t) * (size_t)np, sizeof(int32_t) * (size_t)np,
+                                                         (size_t)nb, hipMemcpyDeviceToHost, c->stream));
+                    HIPCHK(c, sync_stream(c, c->stream));      // the staging block is rewritten by the next batch
+                    if (width > D)
+                        for (int64_t jd = j0; jd < j0 + nb; ++jd)
+                            for (int64_t i = p0; i < p0 + np; ++i) memset(out + jd * draw_stride + i * ld + D, 0, sizeof(float) * (size_t)(width - D));
+                }
             }
-            hipError_t e = launch_miss_draw(a, w, 8 * c->cus, c->stream);
-            if (e != hipSuccess) { c->err = who + hipGetErrorString(e); return DPMM_EHIP; }
-            if (!device) {
-                for (int64_t jd = 0; jd < nb; ++jd)
-                    HIPCHK(c, hipMemcpy2DAsync(out + (j0 + jd) * draw_stride + p0 * ld, sizeof(float) * (size_t)ld, w.out + jd * np * D, sizeof(float) * (size_t)D,
-                                               sizeof(float) * (size_t)D, (size_t)np, hipMemcpyDeviceToHost, c->stream));
-                if (comp) HIPCHK(c, hipMemcpy2DAsync(comp + j0 * n + p0, sizeof(int32_t) * (size_t)n, w.comp, sizeof(int32_t) * (size_t)np, sizeof(int32_t) * (size_t)np,
-                                                     (size_t)nb, hipMemcpyDeviceToHost, c->stream));
-                HIPCHK(c, sync_stream(c, c->stream));      // the staging block is rewritten by the next batch
-                if (width > D)
-                    for (int64_t jd = j0; jd < j0 + nb; ++jd)
-                        for (int64_t i = p0; i < p0 + np; ++i) memset(out + jd * draw_stride + i * ld + D, 0, sizeof(float) * (size_t)(width - D));
-            }
-        }
-    }
+            return DPMM_OK;
+        })) return rc;
     HIPCHK(c, sync_stream(c, c->stream));
     return DPMM_OK;
 }
@@ -4045,6 +4064,12 @@ int dpmm_impute_draw_points_device(dpmm_ctx *c, float *d_out, int64_t ld, int64_
 // ---- include/dpmm_hip_rank.h: exemplars, the m most and least typical points of every cluster (rank.hip) -----------------------------------
 static size_t rank_keys_words(int K) { return (size_t)2 * (size_t)K * RANK_SLOTS; }
 static size_t rank_count_words(int K) { return (size_t)RANK_REPL * (size_t)(K + 1); }
+// the outputs of dpmm_rank_read in the order of its staging block: idx | idx | score | score | count | skipped (launch_rank_read writes all six)
+static OutStage<6> rank_out_stage(const dpmm_rank_out &o, int K, int m, bool device) {
+    const size_t km = (size_t)K * (size_t)m;
+    return {{{o.typ_idx, sizeof(int64_t) * km}, {o.fringe_idx, sizeof(int64_t) * km}, {o.typ_score, sizeof(float) * km}, {o.fringe_score, sizeof(float) * km},
+             {o.count, sizeof(int64_t) * (size_t)K}, {o.skipped, sizeof(int64_t)}}, device, true};
+}
 
 int dpmm_rank_begin(dpmm_ctx *c, int m, int which) {
     static const char *fn = "dpmm_rank_begin";
@@ -4059,8 +4084,7 @@ int dpmm_rank_begin(dpmm_ctx *c, int m, int which) {
     const int64_t cap = std::max<int64_t>(1, std::min<int64_t>(RANK_CHUNK, c->n));
     const size_t state = sizeof(unsigned long long) * (rank_keys_words(K) + rank_count_words(K) + 2);      // (2 words: the four candidate counters)
     const size_t cand = (size_t)2 * (size_t)cap * (sizeof(unsigned long long) + sizeof(uint16_t));
-    const size_t km = (size_t)K * (size_t)m;
-    const size_t out = 2 * km * sizeof(int64_t) + 2 * ((km * sizeof(float) + 7) & ~(size_t)7) + (size_t)(K + 1) * sizeof(int64_t);
+    const size_t out = rank_out_stage(dpmm_rank_out{}, K, m, false).layout(1);
     if (int rc = grow(c, c->d_rank_state, state, "dpmm_score_points", "running lists of dpmm_rank_begin")) return rc;
     if (int rc = grow(c, c->d_rank_cand, cand, "dpmm_score_points", "candidate buffers of dpmm_rank_begin")) return rc;
     if (int rc = grow(c, c->d_rank_out, out, "dpmm_score_points", "staging of dpmm_rank_read")) return rc;
@@ -4083,32 +4107,25 @@ int dpmm_rank_accumulate(dpmm_ctx *c, int64_t index_base, int64_t n_valid) {
     if (n_valid == 0) return DPMM_OK;
     if (!c->have_points || !c->have_params) return fail(c, DPMM_ESTATE, who + "needs points and parameters");
     if (c->rank_cap < std::min<int64_t>(RANK_CHUNK, c->n)) return fail(c, DPMM_ESTATE, who + "the context's points changed since dpmm_rank_begin");
-    int rstep = 0;
-    int64_t P = 0;
-    if (int rc = score_table_slab(c, &rstep, &P)) return rc;
-    const bool miss = c->opt_score_missing != 0;
-    if (int rc = miss_begin(c, miss, P, fn)) return rc;
+    TableWalk w;
+    if (int rc = walk_open(c, fn, WALK_MISS_OPTION, &w)) return rc;
     const int K = c->K;
     unsigned long long *keys = c->d_rank_state, *count = keys + rank_keys_words(K);
     unsigned *cand_n = reinterpret_cast<unsigned *>(count + rank_count_words(K));
     unsigned long long *cand_key = reinterpret_cast<unsigned long long *>(c->d_rank_cand.get());
     uint16_t *cand_k = reinterpret_cast<uint16_t *>(cand_key + 2 * c->rank_cap);
-    for (int64_t p0 = 0; p0 < n_valid; p0 += P) {
-        const int64_t np = std::min<int64_t>(P, c->n - p0);              // the range dpmm_score_points evaluates
-        if (int rc = run_sweep(c, 0, 0, c->d_score_table, P, p0, np)) return rc;
-        if (miss) if (int rc = miss_range(c, P, p0, np, nullptr, 0, fn)) return rc;
-        const int64_t nv = std::min<int64_t>(np, n_valid - p0);          // what of it is ranked
-        for (int64_t q0 = 0; q0 < nv; q0 += c->rank_cap) {
+    return walk_ranges(c, w, n_valid, fn, [&](int64_t p0, int64_t, int64_t nv) {
+        hipError_t e = hipSuccess;
+        for (int64_t q0 = 0; q0 < nv && e == hipSuccess; q0 += c->rank_cap) {
             RankArgs a{};
-            a.table = c->d_score_table + q0; a.stride = P; a.rstep = rstep; a.n = std::min<int64_t>(c->rank_cap, nv - q0); a.K = K;
+            a.table = c->d_score_table + q0; a.stride = w.P; a.rstep = w.rstep; a.n = std::min<int64_t>(c->rank_cap, nv - q0); a.K = K;
             a.index0 = index_base + p0 + q0; a.m = c->rank_m; a.which = c->rank_which;
             a.keys = keys; a.count = count; a.cand_key = cand_key; a.cand_k = cand_k; a.cand_n = cand_n; a.cap = c->rank_cap; a.parity = c->rank_parity;
-            hipError_t e = launch_rank_chunk(a, c->stream);
-            if (e != hipSuccess) { c->err = who + hipGetErrorString(e); return DPMM_EHIP; }
-            c->rank_parity ^= 1;
+            e = launch_rank_chunk(a, c->stream);
+            if (e == hipSuccess) c->rank_parity ^= 1;
         }
-    }
-    return DPMM_OK;
+        return e;
+    });
 }
 
 static int rank_read(dpmm_ctx *c, const dpmm_rank_out *o, bool device, const char *fn) {
@@ -4119,7 +4136,6 @@ static int rank_read(dpmm_ctx *c, const dpmm_rank_out *o, bool device, const cha
     HIPCHK(c, hipSetDevice(c->device));
     const int K = c->rank_K, m = c->rank_m;
     const uint64_t km = (uint64_t)K * (uint64_t)m;
-    RankOut r{};
     if (device) {
         if (o->typ_idx) if (int rc = check_device_extent(c, fn, "typ_idx", o->typ_idx, sizeof(int64_t) * km, sizeof(int64_t))) return rc;
         if (o->typ_score) if (int rc = check_device_extent(c, fn, "typ_score", o->typ_score, sizeof(float) * km, sizeof(float))) return rc;
@@ -4127,34 +4143,33 @@ static int rank_read(dpmm_ctx *c, const dpmm_rank_out *o, bool device, const cha
         if (o->fringe_score) if (int rc = check_device_extent(c, fn, "fringe_score", o->fringe_score, sizeof(float) * km, sizeof(float))) return rc;
         if (o->count) if (int rc = check_device_extent(c, fn, "count", o->count, sizeof(int64_t) * (uint64_t)K, sizeof(int64_t))) return rc;
         if (o->skipped) if (int rc = check_device_extent(c, fn, "skipped", o->skipped, sizeof(int64_t), sizeof(int64_t))) return rc;
-        r = RankOut{o->typ_idx, o->typ_score, o->fringe_idx, o->fringe_score, o->count, o->skipped};
-    } else {      // the staging block dpmm_rank_begin sized: idx | idx | score | score | count | skipped, each 8-byte aligned
-        const size_t sb = ((size_t)km * sizeof(float) + 7) & ~(size_t)7;
-        char *p = c->d_rank_out;
-        r.typ_idx = reinterpret_cast<int64_t *>(p); p += km * sizeof(int64_t);
-        r.fringe_idx = reinterpret_cast<int64_t *>(p); p += km * sizeof(int64_t);
-        r.typ_score = reinterpret_cast<float *>(p); p += sb;
-        r.fringe_score = reinterpret_cast<float *>(p); p += sb;
-        r.count = reinterpret_cast<int64_t *>(p); p += (size_t)K * sizeof(int64_t);
-        r.skipped = reinterpret_cast<int64_t *>(p);
     }
+    OutStage<6> out = rank_out_stage(*o, K, m, device);      // one element per column: the whole array
+    out.layout(1);
+    out.buf = c->d_rank_out;      // (dpmm_rank_begin sized it)
+    const RankOut r{out.at<int64_t>(0, 0), out.at<float>(2, 0), out.at<int64_t>(1, 0), out.at<float>(3, 0), out.at<int64_t>(4, 0), out.at<int64_t>(5, 0)};
     const unsigned long long *keys = c->d_rank_state, *count = keys + rank_keys_words(K);
     hipError_t e = launch_rank_read(keys, count, K, m, c->rank_which, r, c->stream);
-    if (e == hipSuccess && !device) {
-        if (o->typ_idx) e = hipMemcpyAsync(o->typ_idx, r.typ_idx, sizeof(int64_t) * km, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && o->fringe_idx) e = hipMemcpyAsync(o->fringe_idx, r.fringe_idx, sizeof(int64_t) * km, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && o->typ_score) e = hipMemcpyAsync(o->typ_score, r.typ_score, sizeof(float) * km, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && o->fringe_score) e = hipMemcpyAsync(o->fringe_score, r.fringe_score, sizeof(float) * km, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && o->count) e = hipMemcpyAsync(o->count, r.count, sizeof(int64_t) * (size_t)K, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && o->skipped) e = hipMemcpyAsync(o->skipped, r.skipped, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream);
-    }
-    if (e == hipSuccess) e = sync_stream(c, c->stream);
-    if (e != hipSuccess) { c->err = who + hipGetErrorString(e); return DPMM_EHIP; }
-    return DPMM_OK;
+    if (e == hipSuccess) e = device ? sync_stream(c, c->stream) : out.flush(c, 0, 1);
+    return table_result(c, fn, e);
 }
 
 int dpmm_rank_read(dpmm_ctx *c, const dpmm_rank_out *out) { return rank_read(c, out, false, "dpmm_rank_read"); }
 int dpmm_rank_read_device(dpmm_ctx *c, const dpmm_rank_out *out) { return rank_read(c, out, true, "dpmm_rank_read_device"); }
+
+// ---- what the accumulations over the table share (overlap, batchstats, countstats): the session record and the replicated counters ---------
+// an _accumulate call: its *_begin has run, and under the parameters in force now
+static int session_check(dpmm_ctx *c, const AccSession &s, const char *begin_name, const char *fn) {
+    if (!s.active) return fail(c, DPMM_ESTATE, std::string(fn) + ": needs " + begin_name + " first");
+    if (!c->predictive || c->K != s.K || c->pred_gen != s.gen) return fail(c, DPMM_ESTATE, std::string(fn) + ": the predictive parameters changed since " + begin_name);
+    return DPMM_OK;
+}
+// counter k of RANK_REPL replicas, `stride` words apart (a workgroup adds to one replica)
+static int64_t fold_replicated(const std::vector<unsigned long long> &cnt, size_t stride, size_t k) {
+    unsigned long long v = 0;
+    for (int r = 0; r < RANK_REPL; ++r) v += cnt[(size_t)r * stride + k];
+    return (int64_t)v;
+}
 
 // ---- include/dpmm_hip_overlap.h: the posterior overlap of the clusters, sum_i p_ik p_ij (overlap.hip) --------------------------------------
 static size_t overlap_acc_doubles(int K) { return (size_t)K * (size_t)K + (size_t)K; }
@@ -4166,7 +4181,7 @@ int dpmm_overlap_begin(dpmm_ctx *c) {
     const std::string who = std::string(fn) + ": ";
     if (!c->predictive) return fail(c, DPMM_ESTATE, who + "needs dpmm_set_predictive_* first");
     HIPCHK(c, hipSetDevice(c->device));
-    c->ov_active = false;
+    c->ov.active = false;
     const int K = c->K, nb = (K + 63) / 64, npairs = nb * (nb + 1) / 2;
     const size_t state = sizeof(double) * overlap_acc_doubles(K) + sizeof(unsigned long long) * rank_count_words(K);
     const size_t part = sizeof(double) * (size_t)overlap_max_chunks(K) * ((size_t)npairs * 4096 + (size_t)nb * 64);
@@ -4179,8 +4194,7 @@ int dpmm_overlap_begin(dpmm_ctx *c) {
         if (int rc = grow(c, c->d_ov_ms, sizeof(float2) * (size_t)P, "dpmm_score_points", "maxima and sums of dpmm_overlap_begin")) return rc;
     }
     HIPCHK(c, hipMemsetAsync(c->d_ov_acc, 0, state, c->stream));
-    c->ov_K = K; c->ov_gen = c->pred_gen;
-    c->ov_active = true;
+    c->ov = AccSession{true, K, 0, 0, 0.f, c->pred_gen};
     return DPMM_OK;
 }
 
@@ -4189,26 +4203,20 @@ int dpmm_overlap_accumulate(dpmm_ctx *c, int64_t n_valid) {
     if (!c) return tensor_no_ctx(fn);
     c->miss_counted = false;      // (as score_points)
     const std::string who = std::string(fn) + ": ";
-    if (!c->ov_active) return fail(c, DPMM_ESTATE, who + "needs dpmm_overlap_begin first");
-    if (!c->predictive || c->K != c->ov_K || c->pred_gen != c->ov_gen) return fail(c, DPMM_ESTATE, who + "the predictive parameters changed since dpmm_overlap_begin");
+    if (int rc = session_check(c, c->ov, "dpmm_overlap_begin", fn)) return rc;
     if (n_valid < 0 || n_valid > c->n) return fail(c, DPMM_EINVAL, who + "n_valid must be in 0..n_local");
     HIPCHK(c, hipSetDevice(c->device));
     if (n_valid == 0) return DPMM_OK;
     if (!c->have_points || !c->have_params) return fail(c, DPMM_ESTATE, who + "needs points and parameters");
-    int rstep = 0;
-    int64_t P = 0;
-    if (int rc = score_table_slab(c, &rstep, &P)) return rc;
-    if (int rc = grow(c, c->d_ov_ms, sizeof(float2) * (size_t)P, "dpmm_score_points", "maxima and sums of dpmm_overlap_accumulate")) return rc;
-    const bool miss = c->opt_score_missing != 0;
-    if (int rc = miss_begin(c, miss, P, fn)) return rc;
+    TableWalk w;
+    if (int rc = walk_open(c, fn, WALK_MISS_OPTION, &w, [&](int64_t P) {
+            return grow(c, c->d_ov_ms, sizeof(float2) * (size_t)P, "dpmm_score_points", "maxima and sums of dpmm_overlap_accumulate");
+        })) return rc;
     const int K = c->K, nb = (K + 63) / 64, npairs = nb * (nb + 1) / 2;
     const int most = overlap_max_chunks(K);
-    for (int64_t p0 = 0; p0 < n_valid; p0 += P) {
-        const int64_t np = std::min<int64_t>(P, c->n - p0);              // the range dpmm_score_points evaluates
-        if (int rc = run_sweep(c, 0, 0, c->d_score_table, P, p0, np)) return rc;
-        if (miss) if (int rc = miss_range(c, P, p0, np, nullptr, 0, fn)) return rc;
+    return walk_ranges(c, w, n_valid, fn, [&](int64_t, int64_t, int64_t nv) -> int {
         OverlapArgs a{};
-        a.table = c->d_score_table; a.stride = P; a.rstep = rstep; a.n = std::min<int64_t>(np, n_valid - p0); a.K = K; a.nb = nb;
+        a.table = c->d_score_table; a.stride = w.P; a.rstep = w.rstep; a.n = nv; a.K = K; a.nb = nb;
         overlap_chunks(a.n, K, &a.nchunk, &a.chunk);
         if (a.nchunk > most) return fail(c, DPMM_EHIP, who + "internal: more chunks than the partial buffer holds");
         a.ms = c->d_ov_ms;
@@ -4216,10 +4224,8 @@ int dpmm_overlap_accumulate(dpmm_ctx *c, int64_t n_valid) {
         a.count = reinterpret_cast<unsigned long long *>(c->d_ov_acc + overlap_acc_doubles(K));
         a.part = c->d_ov_part;
         a.mpart = c->d_ov_part + (size_t)most * (size_t)npairs * 4096;
-        hipError_t e = launch_overlap_range(a, c->stream);
-        if (e != hipSuccess) { c->err = who + hipGetErrorString(e); return DPMM_EHIP; }
-    }
-    return DPMM_OK;
+        return table_result(c, fn, launch_overlap_range(a, c->stream));
+    });
 }
 
 int dpmm_overlap_read(dpmm_ctx *c, const dpmm_overlap_out *o) {
@@ -4227,9 +4233,9 @@ int dpmm_overlap_read(dpmm_ctx *c, const dpmm_overlap_out *o) {
     if (!c) return tensor_no_ctx(fn);
     const std::string who = std::string(fn) + ": ";
     if (!o) return fail(c, DPMM_EINVAL, who + "out is null");
-    if (!c->ov_active) return fail(c, DPMM_ESTATE, who + "needs dpmm_overlap_begin first");
+    if (!c->ov.active) return fail(c, DPMM_ESTATE, who + "needs dpmm_overlap_begin first");
     HIPCHK(c, hipSetDevice(c->device));
-    const int K = c->ov_K;
+    const int K = c->ov.K;
     const size_t kk = (size_t)K * (size_t)K;
     std::vector<unsigned long long> cnt(rank_count_words(K));
     hipError_t e = sync_stream(c, c->stream);
@@ -4237,18 +4243,28 @@ int dpmm_overlap_read(dpmm_ctx *c, const dpmm_overlap_out *o) {
     if (e == hipSuccess && o->mass) e = hipMemcpy(o->mass, c->d_ov_acc + kk, sizeof(double) * (size_t)K, hipMemcpyDeviceToHost);
     if (e == hipSuccess && (o->count || o->skipped)) e = hipMemcpy(cnt.data(), c->d_ov_acc + overlap_acc_doubles(K), sizeof(unsigned long long) * cnt.size(), hipMemcpyDeviceToHost);
     if (e != hipSuccess) { c->err = who + hipGetErrorString(e); return DPMM_EHIP; }
-    for (int k = 0; k <= K; ++k) {
-        unsigned long long v = 0;
-        for (int r = 0; r < RANK_REPL; ++r) v += cnt[(size_t)r * (size_t)(K + 1) + (size_t)k];
-        if (k < K) { if (o->count) o->count[k] = (int64_t)v; }
-        else if (o->skipped) o->skipped[0] = (int64_t)v;
-    }
+    if (o->count) for (int k = 0; k < K; ++k) o->count[k] = fold_replicated(cnt, (size_t)K + 1, (size_t)k);
+    if (o->skipped) o->skipped[0] = fold_replicated(cnt, (size_t)K + 1, (size_t)K);
     return DPMM_OK;
 }
 
 // ---- include/dpmm_hip_batchstats.h: per-cluster sufficient statistics of a batch, sum_i w_ik (1, x_i, x_i x_i') (batchstats.hip) -----------
 static size_t batchstats_acc_doubles(int K, int D) { return (size_t)K * ((size_t)D * (size_t)D + (size_t)D + 1); }
 static size_t batchstats_count_words(int K) { return (size_t)RANK_REPL * (size_t)(K + BATCHSTATS_COUNTERS); }
+// The tail of dpmm_batchstats_read and dpmm_countstats_read: e, the result of the copies so far; d_cnt, the session's counters
+// count[K] | skipped | held out | incomplete behind its accumulators.  Read only if one of them is asked for.
+static int stats_counters_read(dpmm_ctx *c, const char *fn, hipError_t e, const double *d_cnt, int K, int64_t *count, int64_t *skipped, int64_t *held_out,
+                               int64_t *incomplete) {
+    std::vector<unsigned long long> cnt(batchstats_count_words(K));
+    if (e == hipSuccess && (count || skipped || incomplete || held_out)) e = hipMemcpy(cnt.data(), d_cnt, sizeof(unsigned long long) * cnt.size(), hipMemcpyDeviceToHost);
+    if (int rc = table_result(c, fn, e)) return rc;
+    const size_t stride = (size_t)K + BATCHSTATS_COUNTERS;
+    if (count) for (int k = 0; k < K; ++k) count[k] = fold_replicated(cnt, stride, (size_t)k);
+    if (skipped) skipped[0] = fold_replicated(cnt, stride, (size_t)K);
+    if (held_out) held_out[0] = fold_replicated(cnt, stride, (size_t)K + 1);
+    if (incomplete) incomplete[0] = fold_replicated(cnt, stride, (size_t)K + 2);
+    return DPMM_OK;
+}
 // doubles of the chunk partials of a range of at most `len` points: blocks | rows of sums | weights (the offsets of the three parts)
 static size_t batchstats_part_doubles(int64_t len, int K, int D, size_t *off_s, size_t *off_n) {
     const int nb = (D + 63) / 64, npairs = nb * (nb + 1) / 2;
@@ -4270,7 +4286,7 @@ int dpmm_batchstats_begin(dpmm_ctx *c, int mode, int use_floor, float min_logden
     if (mode != DPMM_BATCHSTATS_HARD && mode != DPMM_BATCHSTATS_SOFT) return fail(c, DPMM_EINVAL, who + "mode must be DPMM_BATCHSTATS_HARD or DPMM_BATCHSTATS_SOFT");
     if (!c->predictive) return fail(c, DPMM_ESTATE, who + "needs dpmm_set_predictive_niw first");
     HIPCHK(c, hipSetDevice(c->device));
-    c->bs_active = false;
+    c->bs.active = false;
     const int K = c->K, D = c->D;
     const size_t state = sizeof(double) * batchstats_acc_doubles(K, D) + sizeof(unsigned long long) * batchstats_count_words(K);
     if (int rc = grow(c, c->d_bs_acc, state, "dpmm_score_points", "accumulators of dpmm_batchstats_begin")) return rc;
@@ -4283,9 +4299,8 @@ int dpmm_batchstats_begin(dpmm_ctx *c, int mode, int use_floor, float min_logden
         if (int rc = grow(c, c->d_bs_part, part, "dpmm_score_points", "chunk partials of dpmm_batchstats_begin")) return rc;
     }
     HIPCHK(c, hipMemsetAsync(c->d_bs_acc, 0, state, c->stream));
-    c->bs_K = K; c->bs_gen = c->pred_gen; c->bs_mode = mode; c->bs_floor = use_floor ? 1 : 0; c->bs_min_logdens = min_logdens;
+    c->bs = AccSession{true, K, mode, use_floor ? 1 : 0, min_logdens, c->pred_gen};
     c->bs_use_tail = 0; c->bs_min_tail = 0.f; c->bs_accumulated = false;
-    c->bs_active = true;
     return DPMM_OK;
 }
 
@@ -4294,7 +4309,7 @@ int dpmm_batchstats_set_min_tail(dpmm_ctx *c, int use, float min_tail) {
     static const char *fn = "dpmm_batchstats_set_min_tail";
     if (!c) return tensor_no_ctx(fn);
     const std::string who = std::string(fn) + ": ";
-    if (!c->bs_active) return fail(c, DPMM_ESTATE, who + "needs dpmm_batchstats_begin first");
+    if (!c->bs.active) return fail(c, DPMM_ESTATE, who + "needs dpmm_batchstats_begin first");
     if (c->bs_accumulated) return fail(c, DPMM_ESTATE, who + "belongs between dpmm_batchstats_begin and the first dpmm_batchstats_accumulate");
     if (use && !(min_tail > 0.f && min_tail <= 1.f)) return fail(c, DPMM_EINVAL, who + "min_tail must lie in (0, 1]");
     c->bs_use_tail = use ? 1 : 0;
@@ -4307,37 +4322,31 @@ int dpmm_batchstats_accumulate(dpmm_ctx *c, int64_t n_valid) {
     if (!c) return tensor_no_ctx(fn);
     c->miss_counted = false;      // (as score_points)
     const std::string who = std::string(fn) + ": ";
-    if (!c->bs_active) return fail(c, DPMM_ESTATE, who + "needs dpmm_batchstats_begin first");
-    if (!c->predictive || c->K != c->bs_K || c->pred_gen != c->bs_gen) return fail(c, DPMM_ESTATE, who + "the predictive parameters changed since dpmm_batchstats_begin");
+    if (int rc = session_check(c, c->bs, "dpmm_batchstats_begin", fn)) return rc;
     if (n_valid < 0 || n_valid > c->n) return fail(c, DPMM_EINVAL, who + "n_valid must be in 0..n_local");
     HIPCHK(c, hipSetDevice(c->device));
     if (n_valid == 0) return DPMM_OK;
     if (!c->have_points || !c->have_params || !c->dX) return fail(c, DPMM_ESTATE, who + "needs points and parameters");
-    int rstep = 0;
-    int64_t P = 0;
-    if (int rc = score_table_slab(c, &rstep, &P)) return rc;
-    if (P >> 31) return fail(c, DPMM_EINVAL, who + "a range of the table must hold fewer than 2^31 points: lower DPMM_OPT_SCORE_TABLE_MB");
     const int K = c->K, D = c->D;
     size_t off_s = 0, off_n = 0;
-    const size_t part = sizeof(double) * batchstats_part_doubles(std::min<int64_t>(P, c->n), K, D, &off_s, &off_n);
-    if (int rc = grow(c, c->d_bs_ms, sizeof(float2) * (size_t)P, "dpmm_score_points", "maxima and sums of dpmm_batchstats_accumulate")) return rc;
-    if (int rc = grow(c, c->d_bs_part, part, "dpmm_score_points", "chunk partials of dpmm_batchstats_accumulate")) return rc;
-    const bool miss = c->opt_score_missing != 0;
-    if (int rc = miss_begin(c, miss, P, fn)) return rc;
+    TableWalk w;
+    if (int rc = walk_open(c, fn, WALK_MISS_OPTION, &w, [&](int64_t P) -> int {
+            if (P >> 31) return fail(c, DPMM_EINVAL, who + "a range of the table must hold fewer than 2^31 points: lower DPMM_OPT_SCORE_TABLE_MB");
+            const size_t part = sizeof(double) * batchstats_part_doubles(std::min<int64_t>(P, c->n), K, D, &off_s, &off_n);
+            if (int rc = grow(c, c->d_bs_ms, sizeof(float2) * (size_t)P, "dpmm_score_points", "maxima and sums of dpmm_batchstats_accumulate")) return rc;
+            return grow(c, c->d_bs_part, part, "dpmm_score_points", "chunk partials of dpmm_batchstats_accumulate");
+        })) return rc;
     if (c->bs_use_tail) {
-        if (int rc = grow(c, c->d_bs_tail, sizeof(float) * (size_t)P, "dpmm_score_points", "tails of dpmm_batchstats_accumulate")) return rc;
-        if (int rc = typ_begin(c, P, fn)) return rc;
+        if (int rc = grow(c, c->d_bs_tail, sizeof(float) * (size_t)w.P, "dpmm_score_points", "tails of dpmm_batchstats_accumulate")) return rc;
+        if (int rc = typ_begin(c, w.P, fn)) return rc;
     }
     c->bs_accumulated = true;
-    for (int64_t p0 = 0; p0 < n_valid; p0 += P) {
-        const int64_t np = std::min<int64_t>(P, c->n - p0);              // the range dpmm_score_points evaluates
-        if (int rc = run_sweep(c, 0, 0, c->d_score_table, P, p0, np)) return rc;
-        if (miss) if (int rc = miss_range(c, P, p0, np, nullptr, 0, fn)) return rc;
-        if (c->bs_use_tail) if (int rc = typ_range(c, P, p0, std::min<int64_t>(np, n_valid - p0), nullptr, nullptr, c->d_bs_tail, fn)) return rc;
+    return walk_ranges(c, w, n_valid, fn, [&](int64_t p0, int64_t, int64_t nv) -> int {
+        if (c->bs_use_tail) if (int rc = typ_range(c, w.P, p0, nv, nullptr, nullptr, c->d_bs_tail, fn)) return rc;
         BatchStatsArgs a{};
-        a.table = c->d_score_table; a.stride = P; a.rstep = rstep; a.n = std::min<int64_t>(np, n_valid - p0); a.K = K; a.D = D; a.nb = (D + 63) / 64;
+        a.table = c->d_score_table; a.stride = w.P; a.rstep = w.rstep; a.n = nv; a.K = K; a.D = D; a.nb = (D + 63) / 64;
         a.X = c->dX + p0 * c->ldx; a.ldx = c->ldx;
-        a.soft = c->bs_mode == DPMM_BATCHSTATS_SOFT; a.use_floor = c->bs_floor; a.min_logdens = c->bs_min_logdens;
+        a.soft = c->bs.mode == DPMM_BATCHSTATS_SOFT; a.use_floor = c->bs.floor; a.min_logdens = c->bs.min_logdens;
         a.use_tail = c->bs_use_tail; a.min_tail = c->bs_min_tail; a.tail = c->bs_use_tail ? c->d_bs_tail.get() : nullptr;
         batchstats_chunks(a.n, K, D, &a.kgroup, &a.nchunk, &a.chunk);
         if ((size_t)a.nchunk * (size_t)std::min(a.kgroup, K) * (size_t)(a.nb * (a.nb + 1) / 2) * 4096 > off_s)
@@ -4348,10 +4357,8 @@ int dpmm_batchstats_accumulate(dpmm_ctx *c, int64_t n_valid) {
         a.part = c->d_bs_part;
         a.spart = c->d_bs_part + off_s;
         a.npart = c->d_bs_part + off_n;
-        hipError_t e = launch_batchstats_range(a, c->stream);
-        if (e != hipSuccess) { c->err = who + hipGetErrorString(e); return DPMM_EHIP; }
-    }
-    return DPMM_OK;
+        return table_result(c, fn, launch_batchstats_range(a, c->stream));
+    });
 }
 
 int dpmm_batchstats_read(dpmm_ctx *c, const dpmm_batchstats_out *o) {
@@ -4359,27 +4366,15 @@ int dpmm_batchstats_read(dpmm_ctx *c, const dpmm_batchstats_out *o) {
     if (!c) return tensor_no_ctx(fn);
     const std::string who = std::string(fn) + ": ";
     if (!o) return fail(c, DPMM_EINVAL, who + "out is null");
-    if (!c->bs_active) return fail(c, DPMM_ESTATE, who + "needs dpmm_batchstats_begin first");
+    if (!c->bs.active) return fail(c, DPMM_ESTATE, who + "needs dpmm_batchstats_begin first");
     HIPCHK(c, hipSetDevice(c->device));
-    const int K = c->bs_K;
+    const int K = c->bs.K;
     const size_t D = (size_t)c->D, Kz = (size_t)K;
-    std::vector<unsigned long long> cnt(batchstats_count_words(K));
     hipError_t e = sync_stream(c, c->stream);
     if (e == hipSuccess && o->N) e = hipMemcpy(o->N, c->d_bs_acc, sizeof(double) * Kz, hipMemcpyDeviceToHost);
     if (e == hipSuccess && o->sums) e = hipMemcpy(o->sums, c->d_bs_acc + Kz, sizeof(double) * Kz * D, hipMemcpyDeviceToHost);
     if (e == hipSuccess && o->S) e = hipMemcpy(o->S, c->d_bs_acc + Kz + Kz * D, sizeof(double) * Kz * D * D, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && (o->count || o->skipped || o->incomplete || o->held_out))
-        e = hipMemcpy(cnt.data(), c->d_bs_acc + batchstats_acc_doubles(K, (int)D), sizeof(unsigned long long) * cnt.size(), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) { c->err = who + hipGetErrorString(e); return DPMM_EHIP; }
-    for (int k = 0; k < K + BATCHSTATS_COUNTERS; ++k) {
-        unsigned long long v = 0;
-        for (int r = 0; r < RANK_REPL; ++r) v += cnt[(size_t)r * (size_t)(K + BATCHSTATS_COUNTERS) + (size_t)k];
-        if (k < K) { if (o->count) o->count[k] = (int64_t)v; }
-        else if (k == K) { if (o->skipped) o->skipped[0] = (int64_t)v; }
-        else if (k == K + 1) { if (o->held_out) o->held_out[0] = (int64_t)v; }
-        else if (o->incomplete) o->incomplete[0] = (int64_t)v;
-    }
-    return DPMM_OK;
+    return stats_counters_read(c, fn, e, c->d_bs_acc + batchstats_acc_doubles(K, (int)D), K, o->count, o->skipped, o->held_out, o->incomplete);
 }
 
 // ---- include/dpmm_hip_countstats.h: per-cluster count statistics of a batch under the Multinomial model, sum_i w_ik (1, x_i) (countstats.hip)
@@ -4400,7 +4395,7 @@ int dpmm_countstats_begin(dpmm_ctx *c, int mode, int use_floor, float min_logden
     if (mode != DPMM_BATCHSTATS_HARD && mode != DPMM_BATCHSTATS_SOFT) return fail(c, DPMM_EINVAL, who + "mode must be DPMM_BATCHSTATS_HARD or DPMM_BATCHSTATS_SOFT");
     if (!c->predictive) return fail(c, DPMM_ESTATE, who + "needs dpmm_set_predictive_mult first");
     HIPCHK(c, hipSetDevice(c->device));
-    c->cs_active = false;
+    c->cs.active = false;
     const int K = c->K, D = c->D;
     const size_t state = sizeof(double) * countstats_acc_doubles(K, D) + sizeof(unsigned long long) * batchstats_count_words(K);
     if (int rc = grow(c, c->d_cs_acc, state, "dpmm_score_points", "accumulators of dpmm_countstats_begin")) return rc;
@@ -4413,8 +4408,7 @@ int dpmm_countstats_begin(dpmm_ctx *c, int mode, int use_floor, float min_logden
         if (int rc = grow(c, c->d_cs_part, part, "dpmm_score_points", "chunk partials of dpmm_countstats_begin")) return rc;
     }
     HIPCHK(c, hipMemsetAsync(c->d_cs_acc, 0, state, c->stream));
-    c->cs_K = K; c->cs_gen = c->pred_gen; c->cs_mode = mode; c->cs_floor = use_floor ? 1 : 0; c->cs_min_logdens = min_logdens;
-    c->cs_active = true;
+    c->cs = AccSession{true, K, mode, use_floor ? 1 : 0, min_logdens, c->pred_gen};
     return DPMM_OK;
 }
 
@@ -4423,8 +4417,7 @@ int dpmm_countstats_accumulate(dpmm_ctx *c, int64_t n_valid) {
     if (!c) return tensor_no_ctx(fn);
     c->miss_counted = false;      // (as score_points)
     const std::string who = std::string(fn) + ": ";
-    if (!c->cs_active) return fail(c, DPMM_ESTATE, who + "needs dpmm_countstats_begin first");
-    if (!c->predictive || c->K != c->cs_K || c->pred_gen != c->cs_gen) return fail(c, DPMM_ESTATE, who + "the predictive parameters changed since dpmm_countstats_begin");
+    if (int rc = session_check(c, c->cs, "dpmm_countstats_begin", fn)) return rc;
     if (n_valid < 0 || n_valid > c->n) return fail(c, DPMM_EINVAL, who + "n_valid must be in 0..n_local");
     HIPCHK(c, hipSetDevice(c->device));
     if (n_valid == 0) return DPMM_OK;
@@ -4432,24 +4425,23 @@ int dpmm_countstats_accumulate(dpmm_ctx *c, int64_t n_valid) {
     const bool have = store == COUNTSTATS_SPARSE ? (bool)c->d_cp : store == COUNTSTATS_U8 ? (bool)c->dX8 : (bool)c->dX;
     if (!c->have_points || !c->have_params || !have) return fail(c, DPMM_ESTATE, who + "needs points and parameters");
     if (store == COUNTSTATS_SPARSE && c->nnz > 0 && (!c->d_ri || !c->d_val)) return fail(c, DPMM_ESTATE, who + "needs points and parameters");
-    int rstep = 0;
-    int64_t P = 0;
-    if (int rc = score_table_slab(c, &rstep, &P)) return rc;
-    if (P >> 31) return fail(c, DPMM_EINVAL, who + "a range of the table must hold fewer than 2^31 points: lower DPMM_OPT_SCORE_TABLE_MB");
     const int K = c->K, D = c->D;
-    const size_t part = sizeof(double) * countstats_part_doubles(c, std::min<int64_t>(P, c->n));
-    if (int rc = grow(c, c->d_cs_ms, sizeof(float2) * (size_t)P, "dpmm_score_points", "maxima and sums of dpmm_countstats_accumulate")) return rc;
-    if (int rc = grow(c, c->d_cs_part, part, "dpmm_score_points", "chunk partials of dpmm_countstats_accumulate")) return rc;
-    for (int64_t p0 = 0; p0 < n_valid; p0 += P) {
-        const int64_t np = std::min<int64_t>(P, c->n - p0);              // the range dpmm_score_points evaluates
-        if (int rc = run_sweep(c, 0, 0, c->d_score_table, P, p0, np)) return rc;
+    size_t part = 0;
+    TableWalk w;
+    if (int rc = walk_open(c, fn, WALK_MISS_NEVER, &w, [&](int64_t P) -> int {
+            if (P >> 31) return fail(c, DPMM_EINVAL, who + "a range of the table must hold fewer than 2^31 points: lower DPMM_OPT_SCORE_TABLE_MB");
+            part = sizeof(double) * countstats_part_doubles(c, std::min<int64_t>(P, c->n));
+            if (int rc = grow(c, c->d_cs_ms, sizeof(float2) * (size_t)P, "dpmm_score_points", "maxima and sums of dpmm_countstats_accumulate")) return rc;
+            return grow(c, c->d_cs_part, part, "dpmm_score_points", "chunk partials of dpmm_countstats_accumulate");
+        })) return rc;
+    return walk_ranges(c, w, n_valid, fn, [&](int64_t p0, int64_t, int64_t nv) -> int {
         CountStatsArgs a{};
-        a.table = c->d_score_table; a.stride = P; a.rstep = rstep; a.n = std::min<int64_t>(np, n_valid - p0); a.K = K; a.D = D;
+        a.table = c->d_score_table; a.stride = w.P; a.rstep = w.rstep; a.n = nv; a.K = K; a.D = D;
         a.store = store;
         if (store == COUNTSTATS_SPARSE) { a.cp = c->d_cp + p0; a.ri = c->d_ri; a.val = c->d_val; }
         else if (store == COUNTSTATS_U8) { a.X8 = c->dX8 + p0 * c->ld8; a.ld8 = c->ld8; }
         else { a.X = c->dX + p0 * c->ldx; a.ldx = c->ldx; }
-        a.soft = c->cs_mode == DPMM_BATCHSTATS_SOFT; a.use_floor = c->cs_floor; a.min_logdens = c->cs_min_logdens;
+        a.soft = c->cs.mode == DPMM_BATCHSTATS_SOFT; a.use_floor = c->cs.floor; a.min_logdens = c->cs.min_logdens;
         countstats_chunks(a.n, K, D, store == COUNTSTATS_SPARSE, &a.kgroup, &a.nchunk, &a.chunk, &a.dp);
         if (sizeof(double) * (size_t)a.nchunk * (size_t)a.kgroup * ((size_t)a.dp + 1) > part)
             return fail(c, DPMM_EHIP, who + "internal: more chunks than the partial buffer holds");
@@ -4458,10 +4450,8 @@ int dpmm_countstats_accumulate(dpmm_ctx *c, int64_t n_valid) {
         a.count = reinterpret_cast<unsigned long long *>(c->d_cs_acc + countstats_acc_doubles(K, D));
         a.part = c->d_cs_part;
         a.npart = c->d_cs_part + (size_t)a.nchunk * (size_t)a.kgroup * (size_t)a.dp;
-        hipError_t e = launch_countstats_range(a, c->stream);
-        if (e != hipSuccess) { c->err = who + hipGetErrorString(e); return DPMM_EHIP; }
-    }
-    return DPMM_OK;
+        return table_result(c, fn, launch_countstats_range(a, c->stream));
+    });
 }
 
 int dpmm_countstats_read(dpmm_ctx *c, const dpmm_countstats_out *o) {
@@ -4469,26 +4459,14 @@ int dpmm_countstats_read(dpmm_ctx *c, const dpmm_countstats_out *o) {
     if (!c) return tensor_no_ctx(fn);
     const std::string who = std::string(fn) + ": ";
     if (!o) return fail(c, DPMM_EINVAL, who + "out is null");
-    if (!c->cs_active) return fail(c, DPMM_ESTATE, who + "needs dpmm_countstats_begin first");
+    if (!c->cs.active) return fail(c, DPMM_ESTATE, who + "needs dpmm_countstats_begin first");
     HIPCHK(c, hipSetDevice(c->device));
-    const int K = c->cs_K;
+    const int K = c->cs.K;
     const size_t D = (size_t)c->D, Kz = (size_t)K;
-    std::vector<unsigned long long> cnt(batchstats_count_words(K));
     hipError_t e = sync_stream(c, c->stream);
     if (e == hipSuccess && o->N) e = hipMemcpy(o->N, c->d_cs_acc, sizeof(double) * Kz, hipMemcpyDeviceToHost);
     if (e == hipSuccess && o->sums) e = hipMemcpy(o->sums, c->d_cs_acc + Kz, sizeof(double) * Kz * D, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && (o->count || o->skipped || o->incomplete || o->held_out))
-        e = hipMemcpy(cnt.data(), c->d_cs_acc + countstats_acc_doubles(K, (int)D), sizeof(unsigned long long) * cnt.size(), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) { c->err = who + hipGetErrorString(e); return DPMM_EHIP; }
-    for (int k = 0; k < K + BATCHSTATS_COUNTERS; ++k) {
-        unsigned long long v = 0;
-        for (int r = 0; r < RANK_REPL; ++r) v += cnt[(size_t)r * (size_t)(K + BATCHSTATS_COUNTERS) + (size_t)k];
-        if (k < K) { if (o->count) o->count[k] = (int64_t)v; }
-        else if (k == K) { if (o->skipped) o->skipped[0] = (int64_t)v; }
-        else if (k == K + 1) { if (o->held_out) o->held_out[0] = (int64_t)v; }
-        else if (o->incomplete) o->incomplete[0] = (int64_t)v;
-    }
-    return DPMM_OK;
+    return stats_counters_read(c, fn, e, c->d_cs_acc + countstats_acc_doubles(K, (int)D), K, o->count, o->skipped, o->held_out, o->incomplete);
 }
 
 // ---- include/dpmm_hip_trace.h: label samples kept on the device, their contingency tables and the per-point confidence (trace.hip) ----------
