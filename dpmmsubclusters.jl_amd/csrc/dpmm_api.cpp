@@ -1219,11 +1219,14 @@ static bool want_b3_images(const dpmm_ctx *c) { return c->prior == DPMM_PRIOR_NI
 // The tight sn2 block of the pair-ball table costs the launch that writes it 19 us (hand-over 17.2 -> 36.1 us, K = 32 as K = 256: one workgroup per
 // cluster); a tile settled by the norm certificate saves the lean launch 0.58 ns of its time (60 us for 103 000 tiles at N = 1e7).  DPMM_OPT_LEAN_NORM_CERT
 // = 1 writes it only where that can come back: lean launch on, not the direction screen's regime (its instantiation runs no pair-ball test), at least
-// 2^22 points (break-even 3.2e6 at the headline's 66 %), and -- once a sweep has reported -- at least 2^15 tiles settled by the certificate in the last
-// sweep that had the block; else off for 63 parameter sets.  Without the block sn2 = sn and the certificate still runs, with the looser bound, for nothing.
+// 2^22 points, and -- once a sweep has reported -- at least 2^15 tiles settled by the certificate in the last sweep that had the block; else off for 63
+// parameter sets.  Re-derived with sn2 for the neighbours: the block's cost is unchanged (the scalar squarings: 19 us), so the break-even stays
+// 19 us / 0.58 ns = 32 800 = 2^15 settled tiles; the headline now settles 81 % (measured 0.56 ns per settled tile: lean launches 0.9316 -> 0.8606 ms for
+// 126 600 tiles), which puts the break-even at 64 * 32 800 / 0.81 = 2.6e6 points (3.2e6 at 66 %): 2^21 is below it, 2^22 the first power of two above.  At
+// the shard size (n = 1.25e6: 66 % of 19 500 tiles with the block, 23 % without) the step is 0.3089 ms with it against 0.2984 without: it stays without.  Without the block sn2 = sn and the certificate still runs, with the looser bound, for nothing.
 // Called once per parameter set, before the launch that writes the table.  (Whatever it answers, labels and sub-labels are the same.)
 static bool norm_tight(dpmm_ctx *c) {
-    if (c->opt_lean_norm_cert == 2) return true;
+    if (c->opt_lean_norm_cert >= 2) return true;
     if (!c->opt_lean_norm_cert) return false;
     if (c->cert_fb && c->sn2_tight) {
         unsigned long long cheap = 0;
@@ -1482,7 +1485,7 @@ static int run_sweep(dpmm_ctx *c, uint32_t epoch, int final_argmax, float *table
                 uint32_t *need3 = a.need ? c->h_need + 12 * (size_t)c->sweep_grid_max : nullptr;
                 NiwSweepArgs al_args = a;
                 if (!c->opt_lean_dir) { al_args.sp_frag = nullptr; al_args.sp_cons = nullptr; }
-                if (c->have_pb && c->opt_pair_ball && al_args.ball) al_args.ball |= c->opt_lean_norm_cert ? 6 : 2;      // (bits of `ball`: a field of its own re-lays every kernel's scalars)
+                if (c->have_pb && c->opt_pair_ball && al_args.ball) al_args.ball |= c->opt_lean_norm_cert == 3 ? 14 : (c->opt_lean_norm_cert ? 6 : 2);      // (bits of `ball`: a field of its own re-lays every kernel's scalars; bit 3: the neighbours keep sn)
                 c->cert_fb = need2 != nullptr && (al_args.ball & 4) != 0 && !(al_args.sp_frag && al_args.sp_cons);
 #ifndef DPMM_STAMPS
                 al_args.dbg = reinterpret_cast<unsigned long long *>(c->d_cert_rec.get());
@@ -2947,7 +2950,7 @@ int dpmm_set_option(dpmm_ctx *c, int option, double value) {
         case DPMM_OPT_BF16_SCREENS: c->opt_bf16scr = value != 0; return DPMM_OK;
         case DPMM_OPT_MASTER_POLL: c->opt_master_poll = value != 0; return DPMM_OK;
         case DPMM_OPT_PAIR_BALL: c->opt_pair_ball = value != 0; if (!c->opt_pair_ball) c->have_pb = false; return DPMM_OK;      // (ON takes effect with the next parameter set)
-        case DPMM_OPT_LEAN_NORM_CERT: c->opt_lean_norm_cert = value == 2 ? 2 : (value != 0); c->cert_cool = 0; c->cert_fb = false; return DPMM_OK;      // (the table's sn2 block follows with the next parameter set)
+        case DPMM_OPT_LEAN_NORM_CERT: c->opt_lean_norm_cert = (value == 2 || value == 3) ? value : (value != 0); c->cert_cool = 0; c->cert_fb = false; return DPMM_OK;      // (the table's sn2 block follows with the next parameter set)
         case DPMM_OPT_LEAN_DIRECTION: c->opt_lean_dir = value != 0; c->lean_off = 0; c->lean_backoff = 15; c->lean_ran = false; return DPMM_OK;
         case DPMM_OPT_CHAIN_FUSION: c->opt_chain = value < 0 ? (0x7fffffff & ~(8 | 32)) : (int)value; return DPMM_OK;
         case DPMM_OPT_LEAN_TILES: c->opt_lean = value != 0; c->lean_off = 0; c->lean_backoff = 15; c->lean_ran = false; return DPMM_OK;

@@ -325,10 +325,22 @@ __device__ __forceinline__ void niw_lean_body(NiwSweepArgs A, uint32_t *__restri
     // other tile takes the path below unchanged.  eps = 1e-4 (the bracket's own convention, 1.0001f): the Float32 quadratic form the threshold stands in for
     // errs by <= 64 * 2^-24 | |R| |z| |, | |R| |_2 <= 8 |R|_2: a factor 1 + 3.1e-5 on |R z|, squared and summed in Float32: 1 + 6.6e-5; the four roundings
     // of the expression itself add 2.4e-7.
-    __shared__ float pb_s2[PB_MAXK];
+    // THE NEIGHBOURS take the same bound in the certificate's comparison: pb_sc holds sn2 for EVERY cluster -- s_j of the certificate's pair-ball loop
+    // (selected here, once per workgroup; A.ball bit 3, DPMM_OPT_LEAN_NORM_CERT = 3: sn, the behaviour before, for comparisons in one process).  Slack
+    // on the neighbours' side: s_j enters lb = D_k0,j - s_j r once; sn2_j >= |R_j|_2 with its own roundings covered by its factor 1 + 1e-6
+    // (pair_ball_block), r carries its 0.5 %, D_k0,j its 1e-4 and the matrix-vector product's 1e-4 sn_j |v| (formed with the LOOSE sn: more than it
+    // needs); the fma rounds lb once (2^-24 of operands the 0.5 % of r dwarfs), and ub < thr compares against a threshold that carries eps = 1e-4 and
+    // the margin as before.  Without the tight block sn2 = sn bit for bit and nothing changes.
+    // The ORDINARY pair-ball test behind the bracket keeps sn (pb_s): with sn2 there the kernel settles tiles it hands on when the option is 0, the
+    // host's "lean launch off above 30 % handed on" then decides differently for different values of the option, and the launches -- not the labels --
+    // of a chain differ (tests/test_gpu_lean_norm_cert.py counts them: D = 36, K = 65, 6 sd).  The certificate's tiles are the ones that save the bracket.
+    // (Three arrays, not one with a per-tile choice: a scalar load of sn2[k0] under the flag cost this kernel 7 spilled vector registers.)
+    __shared__ float pb_s0[PB_MAXK], pb_sc[PB_MAXK];
     const bool use_cert = !DIR && use_pb && (A.ball & 4) != 0;
-    if (use_pb)
-        for (int e = threadIdx.x; e < K; e += 256) { pb_s[e] = pb_d[(size_t)K * K + e]; pb_s2[e] = pb_d[(size_t)K * K + K + e]; }
+    if (use_pb) {
+        const float *s_own = pb_d + (size_t)K * K + K, *s_nb = (A.ball & 12) == 4 ? s_own : s_own - K;
+        for (int e = threadIdx.x; e < K; e += 256) { pb_s[e] = s_own[e - K]; pb_sc[e] = s_nb[e]; pb_s0[e] = s_own[e]; }
+    }
     if (ball_in_lds) {
         const float *src = ball_records(A.tail, K);
         for (int e = threadIdx.x; e < 16 * K; e += 256) ball_lds[e] = src[e];
@@ -483,7 +495,7 @@ __device__ __forceinline__ void niw_lean_body(NiwSweepArgs A, uint32_t *__restri
             }
             if constexpr (!DIR) {
                 if (use_cert && pb_r < INFINITY) {
-                    const float sr = pb_s2[k0] * pb_r;
+                    const float sr = pb_s0[k0] * pb_r;
                     const float thr_cheap = __builtin_fmaf(-0.5f * sr, sr * 1.0001f, c0) - A.screen_margin;
                     if (thr_cheap == thr_cheap && fabsf(thr_cheap) < INFINITY) {
                         bool left = false;
@@ -492,7 +504,7 @@ __device__ __forceinline__ void niw_lean_body(NiwSweepArgs A, uint32_t *__restri
                             if (k0 >= base && k0 < base + 64) cand &= ~(1ull << (k0 - base));
                             const int j = base + lane, jj = j < K ? j : 0;
                             const float dv = base == 0 ? pbv0 : pb_d[(size_t)k0 * K + jj];
-                            const float lb = fmaxf(__builtin_fmaf(-pb_s[jj], pb_r, dv), 0.f);
+                            const float lb = fmaxf(__builtin_fmaf(-pb_sc[jj], pb_r, dv), 0.f);
                             const float ub = __builtin_fmaf(-0.5f * lb, lb, ball_lds[16 * jj + 15]);
                             cand &= ~__ballot(j < K && ub < thr_cheap);
                             left = cand != 0ull;

@@ -127,8 +127,10 @@ enum {
                                          reference bracket, the ball test and the tail screens.  The tight sn2 costs the launch that writes the table 19 us per
                                          parameter set: with 1 the library writes it only where the sweep can earn that back (lean launch on, outside the direction
                                          screen's regime, >= 2^22 points, and >= 2^15 tiles settled by the certificate in the last sweep that had it; else sn2 = sn and
-                                         the certificate runs with the looser bound).  2: always the tight sn2.  0: every tile runs the bracket, sn2 = sn.
-                                         Same labels and sub-labels whatever the value. */
+                                         the certificate runs with the looser bound).  Where the block is tight, sn2_j also bounds |R_j|_2 of every OTHER cluster j
+                                         in the certificate's pair-ball comparison (the ordinary pair-ball test behind the bracket keeps sn).  2: always the tight
+                                         sn2.  3: as 2, but the other clusters keep the loose sn in the certificate too (the behaviour before sn2 served them: for
+                                         comparisons in one process).  0: every tile runs the bracket, sn2 = sn.  Same labels and sub-labels whatever the value. */
     DPMM_OPT_MULT_DRAWS_AHEAD = 25,   /* 1 (default): Multinomial device master: dpmm_step_stats launches the NEXT Dirichlet draws and their hand-over images
                                        * behind the statistics (the epoch after the last dpmm_mult_master_draw, the same K and outlier flag), into a second set of
                                        * buffers, and returns when the rows are on the host -- the draws run while the caller decides splits and merges.
