@@ -210,6 +210,21 @@ ABI_TYPICALITY = [
     ("dpmm_typicality_points_device", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(TypicalityOut)]),
     ("dpmm_batchstats_set_min_tail", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_float]),
 ]
+
+
+class HoldoutOut(ctypes.Structure):
+    """dpmm_holdout_out (include/dpmm_hip_holdout.h): host addresses, 0 / None = not asked for."""
+    _fields_ = [("total", ctypes.c_void_p), ("stored", ctypes.c_void_p), ("skipped", ctypes.c_void_p), ("incomplete", ctypes.c_void_p),
+                ("scored", ctypes.c_void_p)]
+
+
+# include/dpmm_hip_holdout.h: the held-out points of a batch, compacted on the GPU into the caller's device memory (additive; bound next to ABI)
+ABI_HOLDOUT = [
+    ("dpmm_holdout_begin", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.c_int64]),
+    ("dpmm_holdout_accumulate", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64]),
+    ("dpmm_holdout_read", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(HoldoutOut)]),
+]
 # include/dpmm_hip_trace.h: label samples kept on the GPU, their pairwise contingency tables and the per-point confidence (additive)
 ABI_TRACE = [
     ("dpmm_trace_open", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
@@ -325,7 +340,7 @@ def load_library():
         except Exception:  # pragma: no cover  (torch is optional for single-GPU use)
             pass
         lib = ctypes.CDLL(p)
-        for name, res, args in ABI + ABI_TENSOR + ABI_SCORE + ABI_RANK + ABI_OVERLAP + ABI_BATCHSTATS + ABI_COUNTSTATS + ABI_TYPICALITY + ABI_TRACE + ABI_MISSING + ABI_IMPUTE + ABI_CSC + ABI_SAMPLE + ABI_PROJECT:
+        for name, res, args in ABI + ABI_TENSOR + ABI_SCORE + ABI_RANK + ABI_OVERLAP + ABI_BATCHSTATS + ABI_COUNTSTATS + ABI_TYPICALITY + ABI_HOLDOUT + ABI_TRACE + ABI_MISSING + ABI_IMPUTE + ABI_CSC + ABI_SAMPLE + ABI_PROJECT:
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -874,6 +889,31 @@ class Worker:
                    skipped=np.empty(1, np.int64), incomplete=np.empty(1, np.int64), held_out=np.empty(1, np.int64))
         self.batchstats_read_raw(**{k: v.ctypes.data for k, v in res.items()})
         return res
+
+    # ---- held-out points (include/dpmm_hip_holdout.h)
+    def holdout_begin(self, dst_points, dst_index, cap, min_logdens=None, min_tail=None):
+        """dpmm_holdout_begin: a new collection of the points below the floor min_logdens and / or the tail floor min_tail (None: not in
+        use) into dst_points [cap][D] float32 and dst_index [cap] int64 -- device addresses (integers) or torch tensors on this worker's
+        GPU, which the caller keeps alive until holdout_read."""
+        floor, tail = min_logdens is not None, min_tail is not None
+        if hasattr(dst_points, "data_ptr"):
+            import torch
+            torch.cuda.current_stream(dst_points.device).synchronize()      # nothing queued on torch's stream still uses this memory
+        addr = [ctypes.c_void_p((a.data_ptr() if a.numel() else 0) if hasattr(a, "data_ptr") else int(a or 0)) for a in (dst_points, dst_index)]
+        self._chk(self._lib.dpmm_holdout_begin(self._h, int(floor), float(min_logdens) if floor else 0.0, int(tail), float(min_tail) if tail else 0.0,
+                                               addr[0], addr[1], int(cap)))
+
+    def holdout_accumulate(self, lo, n_valid):
+        """dpmm_holdout_accumulate: classifies the points 0..n_valid-1 of the current upload, global indices lo + i, and appends the
+        held-out ones."""
+        self._chk(self._lib.dpmm_holdout_accumulate(self._h, int(lo), int(n_valid)))
+
+    def holdout_read(self):
+        """The counters as they stand, after the stream has been waited for: a dict of ints `total`, `stored`, `skipped`, `incomplete`, `scored`."""
+        cnt = np.zeros(5, np.int64)
+        out = HoldoutOut(*[cnt[j:].ctypes.data for j in range(5)])
+        self._chk(self._lib.dpmm_holdout_read(self._h, ctypes.byref(out)))
+        return dict(zip(("total", "stored", "skipped", "incomplete", "scored"), (int(v) for v in cnt)))
 
     # ---- count statistics of the Multinomial prior (include/dpmm_hip_countstats.h)
     def countstats_begin(self, mode=BATCHSTATS_HARD, min_logdens=None):

@@ -59,10 +59,7 @@ __global__ __launch_bounds__(BS_THREADS) void batchstats_prep_kernel(BatchStatsA
         // ---- rows base .. base + 255 of X, flat: word f is feature f % ldx of row f / ldx
         const int rows = (int)(A.n - base < BS_THREADS ? A.n - base : BS_THREADS);
         const float *xr = A.X + base * A.ldx;
-        for (int f = tid; f < rows * ldx; f += BS_THREADS) {
-            const int r = f / ldx;
-            if (f - r * ldx < D && !bs_finite(xr[f])) gap[r] = 1;      // (every writer writes 1)
-        }
+        bs_mark_gaps(gap, xr, rows, ldx, D, tid, BS_THREADS);
         // ---- the table: passes 1 and 2 of score_finish_kernel
         const int64_t i = base + tid;
         const bool valid = i < A.n;
@@ -72,12 +69,9 @@ __global__ __launch_bounds__(BS_THREADS) void batchstats_prep_kernel(BatchStatsA
         bool nan_seen;
         bs_table_passes(col, rs, K, m, best, nan_seen, s);
         __syncthreads();
-        // ---- the class: skipped, else held out, else incomplete, else it takes part
-        const bool scored = valid && !nan_seen && m > -INFINITY && m < INFINITY;
-        // (the tail of a point with a feature that is not finite is NaN and compares false: such a point stays incomplete)
-        const bool held = scored && ((A.use_floor && score_logdens(m, s) < A.min_logdens) || (A.use_tail && gap[tid] == 0 && A.tail[i] < A.min_tail));
-        const bool incomplete = scored && !held && gap[tid] != 0;
-        const bool part = scored && !held && !incomplete;
+        // ---- the class: skipped, else held out, else incomplete, else it takes part (bs_class, batchstats_device.h)
+        bool scored, held, incomplete, part;
+        bs_class(valid, nan_seen, m, s, gap[tid], A.use_floor, A.min_logdens, A.use_tail, A.min_tail, A.tail, i, scored, held, incomplete, part);
         if (valid) A.ms[i] = !part ? make_float2(0.f, 0.f) : A.soft ? make_float2(m, s) : make_float2((float)best, 1.f);
         // ---- the counters (as overlap_prep_kernel)
         bs_count(cnt, K, lane, valid, scored, held, incomplete, part, best);

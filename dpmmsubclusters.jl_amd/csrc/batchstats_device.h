@@ -21,6 +21,27 @@ __device__ __forceinline__ void bs_table_passes(const float *col, int64_t rs, in
     for (int k = 0; k < K; ++k) s += score_e(col[(int64_t)k * rs], m);
 }
 
+// rows base .. base + rows - 1 of X, flat: word f is feature f % ldx of row f / ldx; a word that is not finite (features d < D only) marks
+// its row in gap[] (LDS, cleared by the caller; every writer writes 1).  Called by whole workgroups of `nthreads`.
+__device__ __forceinline__ void bs_mark_gaps(unsigned *gap, const float *xr, int rows, int ldx, int D, int tid, int nthreads) {
+    for (int f = tid; f < rows * ldx; f += nthreads) {
+        const int r = f / ldx;
+        if (f - r * ldx < D && !bs_finite(xr[f])) gap[r] = 1;
+    }
+}
+
+// the class of point i of a range from what bs_table_passes left and its mark: skipped, else held out, else incomplete, else it takes part.
+// tail: the range's tails as launch_typicality_range wrote them, read only if use_tail.  batchstats_prep_kernel (batchstats.hip) and
+// holdout_class_kernel (holdout.hip) both call this: one rule, one piece of code.
+__device__ __forceinline__ void bs_class(bool valid, bool nan_seen, float m, float s, unsigned gapped, int use_floor, float min_logdens, int use_tail,
+                                         float min_tail, const float *tail, int64_t i, bool &scored, bool &held, bool &incomplete, bool &part) {
+    scored = valid && !nan_seen && m > -INFINITY && m < INFINITY;
+    // (the tail of a point with a feature that is not finite is NaN and compares false: such a point stays incomplete)
+    held = scored && ((use_floor && score_logdens(m, s) < min_logdens) || (use_tail && gapped == 0 && tail[i] < min_tail));
+    incomplete = scored && !held && gapped != 0;
+    part = scored && !held && !incomplete;
+}
+
 // the counters of one trip (as overlap_prep_kernel): cnt[0..K) the points that take part by label, cnt[K] skipped, cnt[K + 1] held out,
 // cnt[K + 2] incomplete.  Called by whole waves.
 __device__ __forceinline__ void bs_count(unsigned *cnt, int K, int lane, bool valid, bool scored, bool held, bool incomplete, bool part, int best) {

@@ -14,6 +14,7 @@
 #include "../../include/dpmm_hip_batchstats.h"
 #include "../../include/dpmm_hip_countstats.h"
 #include "../../include/dpmm_hip_typicality.h"
+#include "../../include/dpmm_hip_holdout.h"
 #include "../../include/dpmm_hip_trace.h"
 #include "../../include/dpmm_hip_missing.h"
 #include "../../include/dpmm_hip_impute.h"
@@ -166,6 +167,17 @@ struct dpmm_ctx {
     int bs_use_tail = 0;
     float bs_min_tail = 0.f;
     bool bs_accumulated = false;        // a dpmm_batchstats_accumulate has run since dpmm_batchstats_begin
+    // held-out points (include/dpmm_hip_holdout.h): ballots, class counts and first slots of the workgroups of one range; the running totals;
+    // the caller's destination as dpmm_holdout_begin took it.  With a tail floor the tails of a range go through d_bs_tail, as batchstats' do.
+    DevBuf<unsigned long long> d_ho_ballot, d_ho_state;
+    DevBuf<unsigned> d_ho_count;
+    DevBuf<int64_t> d_ho_off;
+    AccSession ho;
+    int ho_use_tail = 0;
+    float ho_min_tail = 0.f;
+    float *ho_points = nullptr;
+    int64_t *ho_index = nullptr;
+    int64_t ho_cap = 0;
     // count statistics (include/dpmm_hip_countstats.h): N | sums | counters; two floats per point of one range; the chunk partials
     DevBuf<double> d_cs_acc;
     DevBuf<float2> d_cs_ms;
@@ -4378,6 +4390,90 @@ int dpmm_batchstats_read(dpmm_ctx *c, const dpmm_batchstats_out *o) {
     if (e == hipSuccess && o->sums) e = hipMemcpy(o->sums, c->d_bs_acc + Kz, sizeof(double) * Kz * D, hipMemcpyDeviceToHost);
     if (e == hipSuccess && o->S) e = hipMemcpy(o->S, c->d_bs_acc + Kz + Kz * D, sizeof(double) * Kz * D * D, hipMemcpyDeviceToHost);
     return stats_counters_read(c, fn, e, c->d_bs_acc + batchstats_acc_doubles(K, (int)D), K, o->count, o->skipped, o->held_out, o->incomplete);
+}
+
+// ---- include/dpmm_hip_holdout.h: the held-out points of the batch, compacted into the caller's device memory (holdout.hip) -----------------
+static int holdout_check_dst(dpmm_ctx *c, const char *fn, float *points, int64_t *index, int64_t cap) {
+    if (cap <= 0) return DPMM_OK;
+    if (int rc = check_device_extent(c, fn, "dst_points", points, (uint64_t)cap * (uint64_t)c->D * sizeof(float), sizeof(float))) return rc;
+    return check_device_extent(c, fn, "dst_index", index, (uint64_t)cap * sizeof(int64_t), sizeof(int64_t));
+}
+
+int dpmm_holdout_begin(dpmm_ctx *c, int use_floor, float min_logdens, int use_tail, float min_tail, float *dst_points, int64_t *dst_index, int64_t cap) {
+    static const char *fn = "dpmm_holdout_begin";
+    if (!c) return tensor_no_ctx(fn);
+    const std::string who = std::string(fn) + ": ";
+    if (c->prior != DPMM_PRIOR_NIW) return fail(c, DPMM_EINVAL, who + "held-out points are collected under the NIW prior and from dense points; a Multinomial ctx is out of scope");
+    if (!use_floor && !use_tail) return fail(c, DPMM_EINVAL, who + "needs a floor: use_floor or use_tail");
+    if (use_tail && !(min_tail > 0.f && min_tail <= 1.f)) return fail(c, DPMM_EINVAL, who + "min_tail must lie in (0, 1]");
+    if (cap < 0 || (cap >> 40)) return fail(c, DPMM_EINVAL, who + "cap must be in 0..2^40 - 1");
+    if (!c->predictive) return fail(c, DPMM_ESTATE, who + "needs dpmm_set_predictive_niw first");
+    HIPCHK(c, hipSetDevice(c->device));
+    c->ho.active = false;
+    if (int rc = holdout_check_dst(c, fn, dst_points, dst_index, cap)) return rc;
+    if (int rc = grow(c, c->d_ho_state, sizeof(unsigned long long) * HOLDOUT_STATE, "dpmm_score_points", "counters of dpmm_holdout_begin")) return rc;
+    HIPCHK(c, hipMemsetAsync(c->d_ho_state, 0, sizeof(unsigned long long) * HOLDOUT_STATE, c->stream));
+    c->ho = AccSession{true, c->K, 0, use_floor ? 1 : 0, min_logdens, c->pred_gen};
+    c->ho_use_tail = use_tail ? 1 : 0; c->ho_min_tail = use_tail ? min_tail : 0.f;
+    c->ho_points = dst_points; c->ho_index = dst_index; c->ho_cap = cap;
+    return DPMM_OK;
+}
+
+int dpmm_holdout_accumulate(dpmm_ctx *c, int64_t lo, int64_t n_valid) {
+    static const char *fn = "dpmm_holdout_accumulate";
+    if (!c) return tensor_no_ctx(fn);
+    c->miss_counted = false;      // (as score_points)
+    const std::string who = std::string(fn) + ": ";
+    if (int rc = session_check(c, c->ho, "dpmm_holdout_begin", fn)) return rc;
+    if (n_valid < 0 || n_valid > c->n) return fail(c, DPMM_EINVAL, who + "n_valid must be in 0..n_local");
+    if (lo < 0 || lo > ((int64_t)1 << 62) - n_valid) return fail(c, DPMM_EINVAL, who + "global indices must lie in 0..2^62");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (n_valid == 0) return DPMM_OK;
+    if (!c->have_points || !c->have_params || !c->dX) return fail(c, DPMM_ESTATE, who + "needs points and parameters");
+    if (int rc = holdout_check_dst(c, fn, c->ho_points, c->ho_index, c->ho_cap)) return rc;      // (the caller may have freed it since the begin)
+    TableWalk w;
+    if (int rc = walk_open(c, fn, WALK_MISS_OPTION, &w, [&](int64_t P) -> int {
+            if (P >> 31) return fail(c, DPMM_EINVAL, who + "a range of the table must hold fewer than 2^31 points: lower DPMM_OPT_SCORE_TABLE_MB");
+            const size_t groups = (size_t)holdout_groups(std::min<int64_t>(P, c->n));
+            if (int rc = grow(c, c->d_ho_ballot, sizeof(unsigned long long) * groups * (HOLDOUT_THREADS / 64), "dpmm_score_points", "ballots of dpmm_holdout_accumulate")) return rc;
+            if (int rc = grow(c, c->d_ho_count, sizeof(unsigned) * groups * HOLDOUT_STATE, "dpmm_score_points", "workgroup counts of dpmm_holdout_accumulate")) return rc;
+            return grow(c, c->d_ho_off, sizeof(int64_t) * groups, "dpmm_score_points", "workgroup slots of dpmm_holdout_accumulate");
+        })) return rc;
+    if (c->ho_use_tail) {
+        if (int rc = grow(c, c->d_bs_tail, sizeof(float) * (size_t)w.P, "dpmm_score_points", "tails of dpmm_holdout_accumulate")) return rc;
+        if (int rc = typ_begin(c, w.P, fn)) return rc;
+    }
+    return walk_ranges(c, w, n_valid, fn, [&](int64_t p0, int64_t, int64_t nv) -> int {
+        if (c->ho_use_tail) if (int rc = typ_range(c, w.P, p0, nv, nullptr, nullptr, c->d_bs_tail, fn)) return rc;
+        HoldoutArgs a{};
+        a.table = c->d_score_table; a.stride = w.P; a.rstep = w.rstep; a.n = nv; a.K = c->K; a.D = c->D;
+        a.X = c->dX + p0 * c->ldx; a.ldx = c->ldx;
+        a.use_floor = c->ho.floor; a.min_logdens = c->ho.min_logdens;
+        a.use_tail = c->ho_use_tail; a.min_tail = c->ho_min_tail; a.tail = c->ho_use_tail ? c->d_bs_tail.get() : nullptr;
+        a.index0 = lo + p0;
+        a.ballot = c->d_ho_ballot; a.wgcount = c->d_ho_count; a.wgoff = c->d_ho_off; a.state = c->d_ho_state;
+        a.dst_points = c->ho_points; a.dst_index = c->ho_index; a.cap = c->ho_cap;
+        return table_result(c, fn, launch_holdout_range(a, c->stream));
+    });
+}
+
+int dpmm_holdout_read(dpmm_ctx *c, const dpmm_holdout_out *o) {
+    static const char *fn = "dpmm_holdout_read";
+    if (!c) return tensor_no_ctx(fn);
+    const std::string who = std::string(fn) + ": ";
+    if (!o) return fail(c, DPMM_EINVAL, who + "out is null");
+    if (!c->ho.active) return fail(c, DPMM_ESTATE, who + "needs dpmm_holdout_begin first");
+    HIPCHK(c, hipSetDevice(c->device));
+    unsigned long long h[HOLDOUT_STATE] = {0, 0, 0, 0};
+    hipError_t e = sync_stream(c, c->stream);
+    if (e == hipSuccess) e = hipMemcpy(h, c->d_ho_state, sizeof(h), hipMemcpyDeviceToHost);
+    if (int rc = table_result(c, fn, e)) return rc;
+    if (o->total) o->total[0] = (int64_t)h[0];
+    if (o->stored) o->stored[0] = std::min<int64_t>((int64_t)h[0], c->ho_cap);
+    if (o->skipped) o->skipped[0] = (int64_t)h[1];
+    if (o->incomplete) o->incomplete[0] = (int64_t)h[2];
+    if (o->scored) o->scored[0] = (int64_t)h[3];
+    return DPMM_OK;
 }
 
 // ---- include/dpmm_hip_countstats.h: per-cluster count statistics of a batch under the Multinomial model, sum_i w_ik (1, x_i) (countstats.hip)

@@ -269,6 +269,34 @@ struct BatchStatsArgs {
 };
 void batchstats_chunks(int64_t n, int K, int D, int *kgroup, int *nchunk, int64_t *chunk);
 hipError_t launch_batchstats_range(const BatchStatsArgs &a, hipStream_t s);
+// ---- held-out points (holdout.hip; include/dpmm_hip_holdout.h): one range of the score table, n points from table column 0 and from X; the
+// points the rule of BatchStatsArgs holds out are appended to the caller's buffers in increasing index
+constexpr int HOLDOUT_THREADS = 256;             // points per workgroup of the class and gather passes
+constexpr int HOLDOUT_STATE = 4;                 // running totals: held out | skipped | incomplete | taking part
+inline int64_t holdout_groups(int64_t n) { return (n + HOLDOUT_THREADS - 1) / HOLDOUT_THREADS; }
+struct HoldoutArgs {
+    const float *table;
+    int64_t stride;      // floats between two rows of the table
+    int rstep;           // cluster k is row k * rstep
+    int64_t n;           // points of the range that are classified, below 2^31
+    int K, D;
+    const float *X;      // [n][ldx], the range's first point
+    int64_t ldx;
+    int use_floor;       // as BatchStatsArgs
+    float min_logdens;
+    int use_tail;
+    float min_tail;
+    const float *tail;   // [n], read only if use_tail
+    int64_t index0;      // global index of the range's first point
+    unsigned long long *ballot;     // [4 * holdout_groups(n)] bit l of word j: point 64 j + l is held out
+    unsigned *wgcount;              // [holdout_groups(n)][HOLDOUT_STATE] the classes of the workgroup's points, counted
+    int64_t *wgoff;                 // [holdout_groups(n)] slot of the workgroup's first held-out point
+    unsigned long long *state;      // [HOLDOUT_STATE] running totals: read, then advanced, by the scan
+    float *dst_points;              // [cap][D]
+    int64_t *dst_index;             // [cap]
+    int64_t cap;
+};
+hipError_t launch_holdout_range(const HoldoutArgs &a, hipStream_t s);
 // ---- per-cluster count statistics of the Multinomial prior (countstats.hip; include/dpmm_hip_countstats.h): one range of the score table,
 // n points from table column 0 and from whichever point store is live, added to the ctx's accumulators
 constexpr int64_t COUNTSTATS_PARTIAL_BYTES = (int64_t)64 << 20;      // DPMM_COUNTSTATS_PARTIAL_BYTES: the chunk partials at most

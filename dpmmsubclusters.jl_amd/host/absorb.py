@@ -18,6 +18,9 @@ with the cluster's own posterior in the prior's place), from `Predictor.count_st
 one fit; a served cluster whose alpha has grown to 1e6 would lose a soft weight of 0.01 at every batch (the spacing of Float32 there is
 0.0625) -- the reasoning of the note on kappa and nu above.  `predictive_table` widens alpha to Float64 anyway, and `save` / `load` keep
 the type the array has.
+
+`niw_graft` appends clusters: the posteriors `Predictor.grow` found for the points no cluster explains go behind the ones the model has,
+which keep their numbers and their bits.
 """
 import numpy as np
 
@@ -59,6 +62,44 @@ def niw_absorb(post, points_count, stats):
         new["kappa"][k], new["nu"][k], new["m"][k], new["U"][k], new["logdet_psi"][k] = kap1[0], nu1[0], m1[0], U1[0], ld1[0]
         count[k] += N[k]
     return new, count
+
+
+def _niw_arrays(post, what):
+    """The five posterior arrays of `post` in Float64 (copies), K and D; ValueError for anything that is not K >= 1 NIW posteriors."""
+    missing = [k for k in POST_KEYS[:4] if k not in post]
+    if missing:
+        raise ValueError(f"niw_graft is for NIW posteriors: {what} lacks {missing}")
+    a = {k: np.array(post[k], np.float64) for k in POST_KEYS if k in post}
+    if "logdet_psi" not in a and a["U"].ndim == 3 and a["U"].shape[1:] == a["m"].shape[1:] * 2:      # (a model file written without it, as niw_absorb)
+        a["logdet_psi"] = 2 * np.log(np.einsum("kii->ki", a["U"])).sum(1) - a["m"].shape[1] * np.log(a["nu"])
+    if "logdet_psi" not in a:
+        raise ValueError(f"{what} must hold kappa, nu, logdet_psi (K,), m (K, D) and U (K, D, D)")
+    K, D = a["m"].shape if a["m"].ndim == 2 else (0, 0)
+    if a["m"].ndim != 2 or K < 1 or D < 1 or a["U"].shape != (K, D, D) or any(a[k].shape != (K,) for k in ("kappa", "nu", "logdet_psi")):
+        raise ValueError(f"{what} must hold kappa, nu, logdet_psi (K,), m (K, D) and U (K, D, D)")
+    if not all(np.isfinite(a[k]).all() for k in POST_KEYS):
+        raise ValueError(f"{what} holds an entry that is not finite")
+    return a, K, D
+
+
+def niw_graft(post, points_count, new_post, new_count):
+    """(post', points_count'): the posterior arrays of K clusters (`Predictor.post`) and their point counts with the K' clusters of
+    `new_post` (the same five arrays, e.g. rows 3 k of a sub-fit's `sampler.post`) and `new_count` appended behind them.  Everything in
+    Float64; the inputs are not modified; rows 0 .. K - 1 keep their bits and their numbers.  ValueError for shapes that do not fit
+    (another D among them), an entry that is not finite, a negative count, and K + K' > binding.MAX_CLUSTERS."""
+    from .. import binding
+    old, K, D = _niw_arrays(post, "post")
+    new, Kn, Dn = _niw_arrays(new_post, "new_post")
+    if Dn != D:
+        raise ValueError(f"new_post has {Dn} features, post {D}")
+    count, ncount = np.array(points_count, np.float64), np.array(new_count, np.float64)
+    if count.shape != (K,) or ncount.shape != (Kn,):
+        raise ValueError("points_count and new_count must have one entry per cluster")
+    if not (np.isfinite(count).all() and np.isfinite(ncount).all()) or (count < 0).any() or (ncount < 0).any():
+        raise ValueError("points_count and new_count must be finite and non-negative")
+    if K + Kn > binding.MAX_CLUSTERS:
+        raise ValueError(f"{K} + {Kn} clusters exceed binding.MAX_CLUSTERS = {binding.MAX_CLUSTERS}")
+    return {k: np.concatenate([old[k], new[k]]) for k in POST_KEYS}, np.concatenate([count, ncount])
 
 
 def dirichlet_absorb(post, points_count, stats):

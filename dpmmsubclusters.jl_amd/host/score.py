@@ -28,7 +28,7 @@ from . import priors as _priors
 from . import tensors as _tensors      # noqa: F401  (the recognisers of host/points.py, reachable from here: tests patch them under this name)
 from . import project as _project
 from . import absorb as _absorb
-from .absorb import niw_absorb, dirichlet_absorb      # noqa: F401
+from .absorb import niw_absorb, niw_graft, dirichlet_absorb      # noqa: F401
 
 
 Exemplars = collections.namedtuple("Exemplars", "typical_idx typical_score fringe_idx fringe_score count skipped")
@@ -52,6 +52,17 @@ points that took no part -- numpy arrays always."""
 Typicality = collections.namedtuple("Typicality", "labels mahalanobis tail skipped incomplete")
 Typicality.__doc__ = """What `Predictor.typicality` returns: labels (n,) int64 1-based, mahalanobis (n,) float32, tail (n,) float32 -- tensors on
 the data's device for a device tensor, else numpy arrays -- and skipped, incomplete, ints: the points whose mahalanobis and tail are NaN."""
+
+HeldOut = collections.namedtuple("HeldOut", "points index total skipped incomplete")
+HeldOut.__doc__ = """What `Predictor.held_out` returns: points (D, stored) float32 -- a view of the (stored, D) buffer the GPU wrote -- and index
+(stored,) int64, 0-based positions in `data`, increasing -- tensors on the data's device for a device tensor, else numpy arrays; total, the
+held-out points there are (stored = min(total, max_points)); skipped, incomplete, ints, as `statistics` counts them."""
+
+Growth = collections.namedtuple("Growth", "added sizes index labels dropped total model")
+Growth.__doc__ = """What `Predictor.grow` returns: added, the number of clusters appended; sizes (added,) int64, their points; index (kept,) int64,
+the 0-based positions in `data` of the points that went into them, increasing, and labels (kept,) int64, their new 1-based cluster ids
+(K_old + 1 ..) -- numpy arrays; dropped, the captured points that went nowhere (a value that is not finite, or a sub-cluster below
+min_points); total, the held-out points there were; model, the sub-fit's dp_model (None when nothing was fitted)."""
 
 ASSIGN_MODES = {"hard": binding.BATCHSTATS_HARD, "soft": binding.BATCHSTATS_SOFT}
 
@@ -108,6 +119,19 @@ def _device_index(device):
 MISSING_MODES = ("propagate", "marginalize")
 
 
+def _floors(min_logdens, min_tail):
+    """The two floors of `statistics`, `held_out` and `grow` as floats or None; ValueError for a NaN min_logdens or a min_tail outside (0, 1]."""
+    if min_logdens is not None:
+        min_logdens = float(min_logdens)
+        if min_logdens != min_logdens:
+            raise ValueError("min_logdens must not be NaN")
+    if min_tail is not None:
+        min_tail = float(min_tail)
+        if not 0.0 < min_tail <= 1.0:
+            raise ValueError("min_tail must lie in (0, 1]")
+    return min_logdens, min_tail
+
+
 class _Stages:
     """The staging of a Predictor's short slab as host/points.py asks for it -- "host", "dev", "csc" -- kept on the Predictor as
     `_host_stage`, `_dev_stage`, `_csc_stage`; suffix "_in": the D_in-wide ones of dense data that is projected on the way in."""
@@ -139,10 +163,15 @@ class Predictor:
         post = {k: np.asarray(v)[rows] for k, v in s.post.items()}
         if device is None:
             device = getattr(getattr(s, "wk", None), "device", 0)
+        hyper = None
+        if s.prior.kind == _priors.PRIOR_NIW and all(hasattr(s.prior, k) for k in ("kappa", "m", "nu", "psi")):      # what `grow` fits new clusters under
+            hyper = {k: getattr(s.prior, k) for k in ("kappa", "m", "nu", "psi")}
         self._setup(s.prior.kind, s.prior.dim, s.alpha, np.asarray(s.points_count), post, capacity, device, worker_factory,
-                    projection=getattr(dp_model, "projection", None), missing=missing)
+                    projection=getattr(dp_model, "projection", None), missing=missing, prior_hyper=hyper)
 
-    def _setup(self, kind, D, alpha, points_count, post, capacity, device, worker_factory, projection=None, missing="propagate"):
+    def _setup(self, kind, D, alpha, points_count, post, capacity, device, worker_factory, projection=None, missing="propagate", prior_hyper=None):
+        # the model's NIW hyper-parameters kappa, m (D,), nu, psi (D, D) in Float64, or None: a model file written without them
+        self.prior_hyper = None if prior_hyper is None else {k: np.array(prior_hyper[k], np.float64) for k in ("kappa", "m", "nu", "psi")}
         if missing not in MISSING_MODES:
             raise ValueError('missing must be "propagate" or "marginalize"')
         if missing == "marginalize" and int(kind) != _priors.PRIOR_NIW:
@@ -211,17 +240,20 @@ class Predictor:
 
     # ---- a model to serve, without the training data or the sampler
     def save(self, path):
-        """One .npz: prior kind, D, alpha, points_count, the posterior arrays of the K clusters and the projection, if the model has one."""
+        """One .npz: prior kind, D, alpha, points_count, the posterior arrays of the K clusters, the projection, if the model has one, and
+        the NIW hyper-parameters `grow` fits new clusters under (prior_kappa, prior_m, prior_nu, prior_psi), if the Predictor has them."""
         np.savez(path, kind=np.int64(self.kind), D=np.int64(self.D), alpha=np.float64(self.alpha), points_count=self.points_count,
-                 **{"post_" + k: v for k, v in self.post.items()}, **(self.projection.arrays("proj_") if self.projection is not None else {}))
+                 **{"post_" + k: v for k, v in self.post.items()}, **(self.projection.arrays("proj_") if self.projection is not None else {}),
+                 **({"prior_" + k: v for k, v in self.prior_hyper.items()} if self.prior_hyper is not None else {}))
 
     @classmethod
     def load(cls, path, device=None, capacity=65536, worker_factory=None, missing="propagate"):
         with np.load(path) as z:
             post = {k[5:]: z[k] for k in z.files if k.startswith("post_")}
+            hyper = {k: z["prior_" + k] for k in ("kappa", "m", "nu", "psi")} if all("prior_" + k in z.files for k in ("kappa", "m", "nu", "psi")) else None
             self = cls.__new__(cls)
             self._setup(int(z["kind"]), int(z["D"]), float(z["alpha"]), z["points_count"], post, capacity, 0 if device is None else device, worker_factory,
-                        projection=_project.Projection.from_arrays(z, "proj_"), missing=missing)
+                        projection=_project.Projection.from_arrays(z, "proj_"), missing=missing, prior_hyper=hyper)
         return self
 
     # ---- the public methods
@@ -369,14 +401,7 @@ class Predictor:
             raise ValueError("statistics are for the NIW prior: a Multinomial model has count_statistics / absorb_counts")
         if assign not in ASSIGN_MODES:
             raise ValueError('assign must be "hard" or "soft"')
-        if min_logdens is not None:
-            min_logdens = float(min_logdens)
-            if min_logdens != min_logdens:
-                raise ValueError("min_logdens must not be NaN")
-        if min_tail is not None:
-            min_tail = float(min_tail)
-            if not 0.0 < min_tail <= 1.0:
-                raise ValueError("min_tail must lie in (0, 1]")
+        min_logdens, min_tail = _floors(min_logdens, min_tail)
         wk = self._wk
         if not hasattr(wk, "batchstats_begin"):
             raise RuntimeError("this Predictor's worker cannot accumulate batch statistics (no dpmm_batchstats_begin)")
@@ -398,7 +423,7 @@ class Predictor:
         parameters are then reloaded into the same worker, once, so every later call and `save` see the updated model; an accumulation
         begun before (`overlap`, `exemplars` pieces at the binding level) is refused afterwards.  Statistics with N.sum() == 0 change
         nothing.  No new cluster is created: points far from every cluster are either absorbed by the nearest one or, with
-        `min_logdens` or `min_tail`, held out and counted."""
+        `min_logdens` or `min_tail`, held out and counted.  `held_out` collects those points and `grow` turns them into new clusters."""
         stats = self.statistics(data, assign=assign, min_logdens=min_logdens, min_tail=min_tail)
         if not stats.N.sum() > 0:
             return stats
@@ -409,6 +434,133 @@ class Predictor:
         self._wk.set_predictive_niw(*args)
         self._sampler_set = False            # the sampler's tables are those of the old posterior
         return stats
+
+    # ---- held-out points and new clusters (include/dpmm_hip_holdout.h, host/absorb.py)
+    def _capture(self, data, min_logdens, min_tail, max_points, what):
+        """The held-out points of `data` as the GPU compacted them: (points (stored, D) float32 tensor, index (stored,) int64 tensor, the
+        worker's counters, the torch device of device data or None)."""
+        if self._wk is None:
+            raise RuntimeError("this Predictor is closed")
+        if self.kind != _priors.PRIOR_NIW:
+            raise ValueError(f"{what} is for the NIW prior and dense points: the Multinomial prior and sparse stores are out of scope")
+        min_logdens, min_tail = _floors(min_logdens, min_tail)
+        if min_logdens is None and min_tail is None:
+            raise ValueError(f"{what} needs a floor: min_logdens or min_tail")
+        if max_points != int(max_points) or int(max_points) < 0:
+            raise ValueError("max_points must be a non-negative integer")
+        wk = self._wk
+        if not hasattr(wk, "holdout_begin"):
+            raise RuntimeError("this Predictor's worker cannot collect held-out points (no dpmm_holdout_begin)")
+        opened = self._open(data)
+        n, dev = opened[0], opened[1]
+        import torch
+        cap = min(int(max_points), n)
+        where = torch.device(getattr(wk, "holdout_device", None) or f"cuda:{self.device}")      # (a stand-in worker names where its buffers live)
+        points = torch.empty((cap, self.D), dtype=torch.float32, device=where)
+        index = torch.empty((cap,), dtype=torch.int64, device=where)
+        wk.holdout_begin(points, index, cap, min_logdens, min_tail)
+        self._walk(opened, [], lambda views, lo, hi: wk.holdout_accumulate(lo, hi - lo))
+        r = wk.holdout_read()                              # (waits for the worker's stream: the buffers are complete)
+        return points[:r["stored"]], index[:r["stored"]], r, dev
+
+    def held_out(self, data, min_logdens=None, min_tail=None, max_points=1 << 20):
+        """The points of `data` that `statistics` / `absorb` would HOLD OUT under the same floors -- those far from every cluster, the ones
+        that say the data has changed -- collected on the GPU while the score table goes by: a `HeldOut` tuple.
+
+          points       (D, stored) float32, the points as the model sees them (with a projection: their projected coordinates), in
+                       increasing position; a view of the (stored, D) buffer the library wrote, the layout `fit` and `predict` read in place;
+          index        (stored,) int64, their 0-based positions along the Samples axis of `data`;
+          total        the held-out points there are; stored = min(total, max_points) -- the FIRST max_points of them are kept;
+          skipped, incomplete   as `statistics` counts them (a point in either class is never held out).
+        At least one floor is required; both are validated as `statistics` validates them, and either one holds a point out.  points and
+        index are tensors on the data's device when `data` is a device tensor -- nothing of size n crosses the host link, and nothing of
+        size n is allocated beyond the destination of min(max_points, n) points -- else numpy arrays.  The result does not depend on
+        `capacity` or the table budget, to the bit.  NIW and dense points only: the Multinomial prior and sparse stores are out of scope,
+        and so are several ranks (each Predictor collects from the data it is given)."""
+        points, index, r, dev = self._capture(data, min_logdens, min_tail, max_points, "held_out")
+        if dev is None:
+            points, index = points.cpu().numpy(), index.cpu().numpy()
+        return HeldOut(points.T, index, r["total"], r["skipped"], r["incomplete"])
+
+    def _prior_object(self, prior):
+        """The niw_hyperparams `grow` fits under: the caller's, else the model's."""
+        if prior is None and self.prior_hyper is not None:
+            h = self.prior_hyper
+            prior = _priors.niw_hyperparams(float(h["kappa"]), h["m"], float(h["nu"]), h["psi"])
+        if prior is None:
+            raise ValueError("grow needs the model's NIW hyper-parameters and this Predictor has none (a model file written without "
+                             "prior_kappa / prior_m / prior_nu / prior_psi): pass prior=niw_hyperparams(...)")
+        if getattr(prior, "kind", None) != _priors.PRIOR_NIW or getattr(prior, "dim", None) != self.D:
+            raise ValueError(f"prior must be niw_hyperparams over the model's {self.D} dimensions")
+        return prior
+
+    def grow(self, data, min_logdens=None, min_tail=None, prior=None, alpha=None, iters=100, min_points=None, max_points=1 << 20, seed=0, **fit_kw):
+        """Adds clusters for the part of `data` the model does not explain, and returns a `Growth` tuple.
+
+        The held-out points of `data` (`held_out`, the same floors) are clustered where the GPU left them by the project's own sampler --
+        `fit(points, prior, alpha, iters=iters, seed=seed, verbose=False, **fit_kw)`; they are already in the model's space, so no
+        projection is applied -- and every cluster of that sub-fit with at least `min_points` points (default D + 1) is appended to the
+        served model: its posterior (rows 3 k of the sub-model's `sampler.post`) behind the K the model has (`niw_graft`), its size to
+        `points_count`; the weights are re-formed from points_count + alpha and the predictive parameters reloaded into the same worker,
+        once.  The old clusters keep their numbers and their bits; every later call and `save` see K + added clusters.
+          prior        niw_hyperparams for the new clusters; default: the model's own (`prior_hyper`, recorded from the fitted model and
+                       kept by `save` / `load`).  A model file written before they were kept has none: ValueError unless prior= is given;
+          alpha        of the sub-fit; default: the Predictor's;
+          dropped      captured points that went into no new cluster: one with a value that is not finite (only the min_logdens floor can
+                       hold such a point out), or a member of a sub-cluster below min_points.
+        Nothing left to cluster, or no sub-cluster large enough: added = 0 and the model is untouched.  Any failure before the reload leaves
+        the Predictor as it was.  `grow` does NOT absorb the points that take part: the idiom is
+            p.grow(batch, min_tail=t); p.absorb(batch, min_tail=t)
+        where the second call sees the GROWN model -- the points of the new clusters now take part and are folded into them (again: their
+        posteriors already hold them once; absorb the batch first and grow afterwards if that matters).  NIW only; the Multinomial prior,
+        sparse stores, several ranks and merging a new cluster with an old one are out of scope."""
+        if self.kind != _priors.PRIOR_NIW:
+            raise ValueError("grow is for the NIW prior and dense points: the Multinomial prior and sparse stores are out of scope")
+        hyper = self._prior_object(prior)
+        alpha = self.alpha if alpha is None else float(alpha)
+        if not alpha > 0:
+            raise ValueError("alpha must be positive")
+        min_points = self.D + 1 if min_points is None else int(min_points)
+        if min_points < 1:
+            raise ValueError("min_points must be at least 1")
+        points, index, r, _ = self._capture(data, min_logdens, min_tail, max_points, "grow")
+        import torch
+        total, K0 = r["total"], self.K
+        finite = torch.isfinite(points).all(1)
+        dropped = int(points.shape[0] - int(finite.sum()))
+        if dropped:
+            points, index = points[finite], index[finite]
+        none = np.zeros(0, np.int64)
+        if points.shape[0] == 0:
+            return Growth(0, none, none, none, dropped, total, None)
+        from . import api as _api
+        res = _api.fit(points.T, hyper, alpha, iters=int(iters), seed=seed, verbose=False, **fit_kw)
+        model, lab = res[8], res[0]
+        lab = (lab.cpu().numpy() if hasattr(lab, "cpu") else np.asarray(lab)).astype(np.int64)
+        s = model.sampler
+        sizes = np.bincount(lab - 1, minlength=s.K)
+        if len(sizes) != s.K or len(lab) != points.shape[0]:
+            raise RuntimeError("grow: the sub-fit's labels do not match its clusters")
+        keep = np.flatnonzero(sizes >= min_points)
+        dropped += int(sizes.sum() - sizes[keep].sum())
+        if len(keep) == 0:
+            return Growth(0, none, none, none, dropped, total, model)
+        new_post = {k: np.asarray(s.post[k])[3 * keep] for k in _absorb.POST_KEYS}
+        post, count = _absorb.niw_graft(self.post, self.points_count, new_post, sizes[keep])
+        w = count + self.alpha
+        old = self.post, self.points_count, self.weights, self.K
+        self.post, self.points_count, self.weights, self.K = post, count, (w / w.sum()).astype(np.float32), len(count)
+        try:
+            which, args = self._predictive_args()
+            self._wk.set_predictive_niw(*args)             # ONCE, with the new K
+        except Exception:
+            self.post, self.points_count, self.weights, self.K = old
+            raise
+        self._sampler_set = False                          # the sampler's tables are those of the old K
+        new_id = np.zeros(s.K, np.int64)
+        new_id[keep] = K0 + 1 + np.arange(len(keep))
+        kept = new_id[lab - 1] > 0
+        return Growth(len(keep), sizes[keep].astype(np.int64), index.cpu().numpy()[kept], new_id[lab - 1][kept], dropped, total, model)
 
     # ---- count statistics and the Dirichlet update (include/dpmm_hip_countstats.h, host/absorb.py)
     def count_statistics(self, data, assign="hard", min_logdens=None):
@@ -723,6 +875,14 @@ def typicality(dp_model, data, **kw):
     kw: capacity, device, worker_factory, missing."""
     with Predictor(dp_model, **kw) as p:
         return p.typicality(data)
+
+
+def held_out(dp_model, data, **kw):
+    """The points of `data` below the model's floors, collected on the GPU (opens a Predictor, runs, closes): see `Predictor.held_out`;
+    kw: min_logdens, min_tail, max_points, capacity, device, worker_factory, missing."""
+    args = {k: kw.pop(k) for k in ("min_logdens", "min_tail", "max_points") if k in kw}
+    with Predictor(dp_model, **kw) as p:
+        return p.held_out(data, **args)
 
 
 def overlap(dp_model, data, **kw):
