@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "stats_ranges.h"
 
 #define DPMM_MAX_CLUSTERS_K 1024
 
@@ -555,7 +556,7 @@ struct StatsArgs {
     // clusters' sub-labels were reset speculatively on this shard (suffstats.hip reset_recount_kernel); zero2 = two flag bytes to clear
     const uint8_t *cside; uint8_t *zero2;
 };
-constexpr int NIW_STATS_MAX_GROUPS = 4096;   // workgroups of the NIW statistics kernel at most; slab slots = this + 2 K (suffstats.hip head_slot)
+// (NIW_STATS_MAX_GROUPS, the workgroups of the NIW statistics kernel at most -- slab slots = this + 2 K -- comes from stats_ranges.h)
 int64_t niw_slab_stride(int D);
 hipError_t launch_niw_row_offsets(int32_t *row_off, int32_t *inv_off, int D, int64_t packed_stride, hipStream_t s);
 int64_t mult_slab_stride(int D);

@@ -5,6 +5,7 @@ the same seeded inputs.  Tolerances (fp32 contraction on the matrix cores vs the
       counts are printed; each label flip explained by a CDF margin below 1e-3 of the row mass)
   draw given the GPU's own table: bit-exact (same exp_det / scan arithmetic)
   N counts and all relabel bookkeeping: bit-exact; sum x, sum xx' vs Float64 oracle: rtol 1e-12
+      (the statistics kernels at their edge shapes, EXACTLY, on integer-valued data: tests/test_gpu_niw_stats_shapes.py)
 """
 import numpy as np
 import pytest
