@@ -772,9 +772,7 @@ int dpmm_create(dpmm_ctx **out, int prior_kind, int D, int64_t n_local, int64_t 
     if (c->prior == DPMM_PRIOR_NIW && c->NB == 4) {
         CHK_CREATE(c->d_sp_frag.alloc(sizeof(uint32_t) * (size_t)SP_MAXK * SP_FRAG_WORDS));
         CHK_CREATE(c->d_sp_cons.alloc(sizeof(float) * (size_t)SP_MAXK * SP_CONS_FLOATS));
-        // ([8 grid]: two words per wave of the sweep kernel | [4 grid]: tiles the lean kernel settled, per wave)
-        // [0, 8 g): two words per wave of the general kernel | [8 g, 12 g): one word per wave of the lean kernel (tiles settled without the direction
-        // screen) | [12 g, 20 g): two words per wave of the lean kernel WITH the direction screen (round 6)      (g = sweep_grid_max workgroups of 4 waves)
+        // (20 g words in three parts: need_lean_settled, need_lean_dir)
         CHK_CREATE(c->h_need.alloc(sizeof(uint32_t) * 20 * (size_t)std::max(1, c->sweep_grid_max)));
         memset(c->h_need, 0, sizeof(uint32_t) * 20 * (size_t)std::max(1, c->sweep_grid_max));
         if (c->NB == 4) {
@@ -1226,6 +1224,10 @@ int dpmm_commit_params(dpmm_ctx *c, int K) {
 // write their counts into pinned memory; that sweep has been waited for by whoever brings new parameters), with hysteresis: on from 8 per
 // tile, off below 4.  While it is on, the sweeps run the screen in front of the 4-row pair tests; the first sweep, every 32nd and the one
 // after a change of K keep the usual order and count.
+// h_need in words (g = sweep_grid_max workgroups of 4 waves): [0, 8 g) two words per wave of the general kernel | [8 g, 12 g) one word per wave of the lean
+// kernel: tiles settled (low half), of them by the norm certificate (high half) | [12 g, 20 g) two words per wave of the lean kernel WITH the direction screen
+static uint32_t *need_lean_settled(const dpmm_ctx *c) { return c->h_need + 8 * (size_t)c->sweep_grid_max; }
+static uint32_t *need_lean_dir(const dpmm_ctx *c) { return c->h_need + 12 * (size_t)c->sweep_grid_max; }
 static bool want_pair_ball(const dpmm_ctx *c, int K) { return c->opt_pair_ball && c->opt_ball && K >= 2 && K <= PB_MAXK; }      // (with the images: want_b3_images)
 static bool want_b3_images(const dpmm_ctx *c) { return c->prior == DPMM_PRIOR_NIW && c->NB == 4 && c->opt_b3 && c->have_tail && !c->predictive; }
 // The tight sn2 block of the pair-ball table costs the launch that writes it 19 us (hand-over 17.2 -> 36.1 us, K = 32 as K = 256: one workgroup per
@@ -1242,7 +1244,7 @@ static bool norm_tight(dpmm_ctx *c) {
     if (!c->opt_lean_norm_cert) return false;
     if (c->cert_fb && c->sn2_tight) {
         unsigned long long cheap = 0;
-        for (int w = 0; w < 4 * c->sweep_grid; ++w) cheap += c->h_need[8 * (size_t)c->sweep_grid_max + w] >> 16;
+        for (int w = 0; w < 4 * c->sweep_grid; ++w) cheap += need_lean_settled(c)[w] >> 16;
         if (cheap < (1ull << 15)) c->cert_cool = 64;
     }
     c->cert_fb = false;
@@ -1279,16 +1281,16 @@ static int direction_tables(dpmm_ctx *c, int K, bool b3_done, bool pb_done) {
             const uint32_t v = c->h_need[2 * w];
             if (v & 0x8000u) { many_ub += v >> 16; tiles_ub += v & 0x7FFFu; } else { many += v >> 16; tiles += v & 0x7FFFu; }
             if (c->sp_last) { const uint32_t y = c->h_need[2 * w + 1]; given += y & 0xFFFFu; removed += y >> 16; }
-            tiles += c->h_need[8 * (size_t)c->sweep_grid_max + w] & 0xFFFFu;      // tiles niw_lean_kernel settled (no candidate behind the 4-row tests)
+            tiles += need_lean_settled(c)[w] & 0xFFFFu;      // tiles niw_lean_kernel settled (no candidate behind the 4-row tests)
             // ... and the tiles it settled WITH the direction screen: their candidates and the screen's yield, in the general kernel's format
-            const uint32_t v3 = c->h_need[12 * (size_t)c->sweep_grid_max + 2 * w], y3 = c->h_need[12 * (size_t)c->sweep_grid_max + 2 * w + 1];
+            const uint32_t v3 = need_lean_dir(c)[2 * w], y3 = need_lean_dir(c)[2 * w + 1];
             if (v3 & 0x8000u) { many_ub += v3 >> 16; tiles_ub += v3 & 0x7FFFu; } else { many += v3 >> 16; tiles += v3 & 0x7FFFu; }
             given += y3 & 0xFFFFu; removed += y3 >> 16;
             if (y3) lean_dir = true;
         }
         memset(c->h_need, 0, sizeof(uint32_t) * 2 * (size_t)nw);
-        memset(c->h_need + 8 * (size_t)c->sweep_grid_max, 0, sizeof(uint32_t) * (size_t)nw);      // (read once: a later launch on a smaller grid, or one that does not count, leaves zeros -- "no tiles")
-        memset(c->h_need + 12 * (size_t)c->sweep_grid_max, 0, sizeof(uint32_t) * 2 * (size_t)nw);
+        memset(need_lean_settled(c), 0, sizeof(uint32_t) * (size_t)nw);      // (read once: a later launch on a smaller grid, or one that does not count, leaves zeros -- "no tiles")
+        memset(need_lean_dir(c), 0, sizeof(uint32_t) * 2 * (size_t)nw);
         // (break-even measured on the growth run: at 4.3 candidates per tile the screen costs 3 % of the step, at 28 it saves a third)
         if (tiles > 0) c->sp_regime = c->sp_regime ? (many >= tiles * 4) : (many >= tiles * 8);
         else if (tiles_ub > 0 && many_ub < tiles_ub * 4) c->sp_regime = false;        // even the upper bound is below the switch-off level
@@ -1399,6 +1401,112 @@ int dpmm_numa_node(dpmm_ctx *c) {
 }
 
 static int noise_flush(dpmm_ctx *c);
+
+// ---- run_sweep's NIW branch in three parts.  (1) The argument block every launch of the sweep shares -- and, at D = 128, 256, the bracket launch in
+// front of the sweep, whose output the block then names.
+static int niw_sweep_args(dpmm_ctx *c, NiwSweepArgs &a, uint32_t epoch, int final_argmax, float *table, int64_t table_stride, bool ranged, int64_t p0, int64_t rn, int64_t rtiles) {
+    a.X = (ranged && c->dX) ? c->dX + p0 * c->ldx : c->dX; a.ldx = c->ldx; a.n = rn; a.first_index = c->first + p0; a.ntiles = rtiles; a.K = c->K;
+    a.Rp = c->d_Rp; a.mup = c->d_mup; a.cst = c->d_cst;
+    a.tdf = c->predictive ? c->d_tdf : nullptr;
+    a.scratch = table ? table : c->d_scratch; a.scratch_stride = table ? table_stride : c->scratch_stride;
+    a.scratch_by_tile = table ? 1 : 0; a.labels_only = table ? 1 : 0;
+    a.bins = c->dbins; a.seed = c->seed; a.epoch = epoch; a.final_argmax = final_argmax;
+    a.screen_margin = table ? 0.f : c->opt_margin;
+    a.use_prev = (c->have_labels && !ranged) ? 1 : 0;      // (a range: bins stays unshifted and must not be read, not even as a prefetch hint)
+    a.lam = (c->have_screen_prep && !c->predictive) ? c->d_lam : nullptr;
+    a.mdist = c->d_mdist;
+    a.tail = (c->have_tail && !c->predictive) ? c->d_tail : nullptr;
+    a.tail_g = ((c->D - 4) % 16) / 4;
+    a.ball = c->opt_ball ? NIW_BALL_ON : 0; a.bracket = c->opt_bracket;
+    a.bf16scr = (c->opt_bf16scr && c->NB == 4 && a.tail != nullptr) ? NIW_SCR_ON : 0;
+    if (c->sp_ready && a.bf16scr && !table && !final_argmax) {
+        a.sp_frag = c->d_sp_frag; a.sp_cons = c->d_sp_cons;
+        // the DIR kernel -- the one that writes the yield words -- runs (store_labels only waives Student-t mode, which never meets the bf16 screens)
+        c->sp_last = niw_steady_launch(a, false) && niw_dir_screen(a);
+        if (c->opt_direction > 0 || c->sp_count % 32u != 1u) a.bf16scr |= NIW_SCR_DIR_FIRST;
+    }
+    a.need = (table || c->opt_direction == 0) ? nullptr : c->h_need;
+    // the visiting order is set BEFORE the bracket launch: its tiles and thresholds are indexed by visiting position and
+    // must be those the sweep walks (a bracket computed in storage order would hand a point another point's threshold)
+    a.order = (!table && c->have_perm && c->opt_ordered) ? c->sb.perm : nullptr; a.order_total = c->sb.perm_total;
+    if (c->have_refb_big && a.tail != nullptr && !table && a.bracket && a.use_prev && a.screen_margin > 0.f && !final_argmax) {
+        // D = 128, 256: the reference bracket as a launch of its own in front of the sweep (niw_bracket_big_kernel): per tile whether all
+        // its points were in one cluster, per point the lower end of a certified bracket of that cluster's value
+        if (!c->d_brk_flag) {
+            const size_t nt = (size_t)((c->n + 127) / 128);
+            HIPCHK(c, c->d_brk_flag.alloc(sizeof(uint32_t) * std::max<size_t>(nt, 1)));
+            HIPCHK(c, c->d_brk_aref.alloc(sizeof(float) * std::max<size_t>(nt * 128, 1)));
+        }
+        HIPCHK(c, launch_niw_bracket_big(c->NB, a, c->d_refb_big, c->d_brk_flag, c->d_brk_aref, c->stream));
+        a.brk_flag = c->d_brk_flag; a.brk_aref = c->d_brk_aref;
+    }
+    a.work = table ? nullptr : c->d_work;
+    if (!table) { c->work_waves = std::max(c->work_waves, 4 * c->sweep_grid); c->work_launches += 1; }
+    a.prio = c->opt_prio; a.queue_rounds = c->opt_queue_rounds;
+#ifdef DPMM_STAMPS
+    if (!g_dbg) { hipMalloc(&g_dbg, sizeof(unsigned long long) * 16 * 4 * 4096); hipMemset(g_dbg, 0, sizeof(unsigned long long) * 16 * 4 * 4096); }
+    a.dbg = g_dbg;
+#endif
+    return DPMM_OK;
+}
+
+// (2) Does this label-storing sweep start with the lean kernel?  niw_lean_kernel settles the tiles the cheap screens settle completely, labels and
+// sub-labels in one go, and leaves the others on a list.  A sweep that left more than 30 % of its tiles (overlapping clusters: the screens' later stages
+// do the work) switches it off for lean_backoff sweeps -- every path gives the same labels and sub-labels, so the decision is free to be local.  The
+// verdict is on the last sweep that ran it: h_hard[0], the length of the list it left.  (The lean kernel runs the direction screen itself while the
+// tables exist, unless DPMM_OPT_LEAN_DIRECTION is off: then it stays out of that regime.)
+static bool lean_this_sweep(dpmm_ctx *c, const NiwSweepArgs &a) {
+    const bool lean_ok = c->opt_lean != 0 && c->opt_bracket && a.use_prev && a.screen_margin > 0.f && !a.final_argmax && a.lam == nullptr && c->K > 1 && c->d_hard &&
+                         !(c->opt_lean_dir == 0 && c->sp_regime && c->opt_direction != 0 && c->sp_ready);
+    if (!lean_ok) return false;
+    if (c->lean_off == 0 && c->lean_ran) {
+        const int64_t nwt = (c->n + 63) / 64;
+        if ((int64_t)c->h_hard[0] * 10 > nwt * 3) { c->lean_off = c->lean_backoff; c->lean_backoff = std::min(2 * c->lean_backoff + 1, 1023); }
+        else c->lean_backoff = 15;
+        c->lean_ran = false;
+    }
+    if (c->lean_off > 0) { c->lean_off -= 1; c->h_hard[0] = 0; return false; }
+    c->lean_ran = true;
+    return true;
+}
+
+// (3) The sweep's launches while the bf16 sub-label evaluation is active (niw_lean.hip), with their part events: lean kernel (if asked for) -> the sweep
+// kernel on the list it left, or on every tile: it draws and STORES the labels (LSTORE instantiations) -> the sub-labels of every tile where no list was
+// walked (a list's spans were finished by the LIST launch) -- every sub-cluster value of a sweep then comes from the same arithmetic.
+static int niw_label_store_chain(dpmm_ctx *c, const NiwSweepArgs &a, bool use_lean) {
+    const bool parts = (c->opt_timing & 8) != 0 && (c->opt_timing & 1) != 0;
+    if (parts && !c->ev_part[0]) for (auto &e : c->ev_part) HIPCHK(c, hipEventCreate(&e));
+    NiwLabelStore ls{true};
+    if (use_lean) {
+        const size_t hw = hard_list_words(c->n);
+        uint32_t *mine = c->d_hard + (size_t)c->hard_flip * hw, *other = c->d_hard + (size_t)(c->hard_flip ^ 1) * hw;
+        c->hard_flip ^= 1;
+        uint32_t *need2 = a.need ? need_lean_settled(c) : nullptr, *need3 = a.need ? need_lean_dir(c) : nullptr;
+        // (tiles aligned to the bins of the sort that wrote the visiting order, when there is one and it fits the kernel's table)
+        const bool al = a.order != nullptr && c->perm_nbins > 0 && c->perm_nbins <= NIW_LEAN_MAX_BINS;
+        NiwSweepArgs al_args = a;
+        if (!c->opt_lean_dir) { al_args.sp_frag = nullptr; al_args.sp_cons = nullptr; }
+        if (c->have_pb && c->opt_pair_ball && al_args.ball) {
+            al_args.ball |= NIW_BALL_PAIR_TABLE;
+            if (c->opt_lean_norm_cert) al_args.ball |= NIW_BALL_NORM_CERT;
+            if (c->opt_lean_norm_cert == 3) al_args.ball |= NIW_BALL_NB_LOOSE;
+        }
+        c->cert_fb = need2 != nullptr && (al_args.ball & NIW_BALL_NORM_CERT) != 0 && !(al_args.sp_frag && al_args.sp_cons);
+#ifndef DPMM_STAMPS
+        al_args.cert_points = c->d_cert_rec;
+#endif
+        HIPCHK(c, launch_niw_lean(al_args, mine, need2, other, al ? c->sb.bin_start : nullptr, al ? c->perm_nbins : 0, need3, c->sweep_grid, c->stream));
+        if (parts) HIPCHK(c, hipEventRecord(c->ev_part[0], c->stream));
+        ls.tile_list = mine;
+        ls.list_len = c->h_hard;
+    }
+    HIPCHK(c, launch_niw_sweep(c->NB, a, c->sweep_grid, c->stream, ls));
+    if (parts) HIPCHK(c, hipEventRecord(c->ev_part[1], c->stream));
+    c->have_parts = parts ? (use_lean ? 2 : 1) : 0;
+    if (!ls.tile_list) HIPCHK(c, launch_niw_sub(a, nullptr, nullptr, c->sweep_grid, c->stream));
+    return DPMM_OK;
+}
+
 // Table mode takes a range of the points, [p0, p0 + np) with p0 a multiple of the tile (np < 0: all of them, the launch every caller but the
 // scoring entry points makes): the kernels see shifted base pointers, n = np and the range's tiles, and write table column 0 for point p0.
 // Table mode draws nothing and visits in storage order; the sparse columns' offsets are absolute, so shifting cp is enough.  What stays
@@ -1420,103 +1528,10 @@ static int run_sweep(dpmm_ctx *c, uint32_t epoch, int final_argmax, float *table
     if (!table && (c->opt_timing & 1)) HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
     if (c->prior == DPMM_PRIOR_NIW) {
         NiwSweepArgs a{};
-        a.X = (ranged && c->dX) ? c->dX + p0 * c->ldx : c->dX; a.ldx = c->ldx; a.n = rn; a.first_index = c->first + p0; a.ntiles = rtiles; a.K = c->K;
-        a.Rp = c->d_Rp; a.mup = c->d_mup; a.cst = c->d_cst;
-        a.tdf = c->predictive ? c->d_tdf : nullptr;
-        a.scratch = table ? table : c->d_scratch;
-        a.scratch_stride = table ? table_stride : c->scratch_stride;
-        a.scratch_by_tile = table ? 1 : 0;
-        a.labels_only = table ? 1 : 0;
-        a.bins = c->dbins; a.seed = c->seed; a.epoch = epoch; a.final_argmax = final_argmax;
-        {
-            const bool no_order = !c->opt_ordered;
-            a.screen_margin = table ? 0.f : c->opt_margin;
-            a.use_prev = (c->have_labels && !ranged) ? 1 : 0;      // (a range: bins stays unshifted and must not be read, not even as a prefetch hint)
-            a.lam = (c->have_screen_prep && !c->predictive) ? c->d_lam : nullptr;
-            a.mdist = c->d_mdist;
-            a.tail = (c->have_tail && !c->predictive) ? c->d_tail : nullptr;
-            a.tail_g = ((c->D - 4) % 16) / 4;
-            a.ball = c->opt_ball;
-            a.bracket = c->opt_bracket;
-            a.bf16scr = (c->opt_bf16scr && c->NB == 4 && a.tail != nullptr) ? 1 : 0;
-            if (c->sp_ready && a.bf16scr && !table && !final_argmax) { c->sp_last = a.lam == nullptr && a.tdf == nullptr && a.screen_margin > 0.f && c->K > 1 && c->K <= SP_MAXK; /* (exactly the conditions of launch_direct's DIR instantiation -- the kernel that writes the yield words; K <= 64 fits the LDS table) */ a.sp_frag = c->d_sp_frag; a.sp_cons = c->d_sp_cons; if (c->opt_direction > 0 || c->sp_count % 32u != 1u) a.bf16scr |= 2; }
-            a.need = (table || c->opt_direction == 0) ? nullptr : c->h_need;
-            // the visiting order is set BEFORE the bracket launch: its tiles and thresholds are indexed by visiting position and
-            // must be those the sweep walks (a bracket computed in storage order would hand a point another point's threshold)
-            a.order = (!table && c->have_perm && !no_order) ? c->sb.perm : nullptr;
-            a.order_total = c->sb.perm_total;
-            if (c->have_refb_big && a.tail != nullptr && !table && a.bracket && a.use_prev && a.screen_margin > 0.f && !final_argmax) {
-                // D = 128, 256: the reference bracket as a launch of its own in front of the sweep (niw_bracket_big_kernel): per tile whether all
-                // its points were in one cluster, per point the lower end of a certified bracket of that cluster's value
-                if (!c->d_brk_flag) {
-                    const size_t nt = (size_t)((c->n + 127) / 128);
-                    HIPCHK(c, c->d_brk_flag.alloc(sizeof(uint32_t) * std::max<size_t>(nt, 1)));
-                    HIPCHK(c, c->d_brk_aref.alloc(sizeof(float) * std::max<size_t>(nt * 128, 1)));
-                }
-                HIPCHK(c, launch_niw_bracket_big(c->NB, a, c->d_refb_big, c->d_brk_flag, c->d_brk_aref, c->stream));
-                a.sp_frag = c->d_brk_flag; a.sp_cons = c->d_brk_aref;
-            }
-            a.work = table ? nullptr : c->d_work;
-            if (!table) { c->work_waves = std::max(c->work_waves, 4 * c->sweep_grid); c->work_launches += 1; }
-            a.prio = c->opt_prio;
-            a.queue_rounds = c->opt_queue_rounds;
-        }
-#ifdef DPMM_STAMPS
-        if (!g_dbg) { hipMalloc(&g_dbg, sizeof(unsigned long long) * 16 * 4 * 4096); hipMemset(g_dbg, 0, sizeof(unsigned long long) * 16 * 4 * 4096); }
-        a.dbg = g_dbg;
-#endif
+        if (int rc = niw_sweep_args(c, a, epoch, final_argmax, table, table_stride, ranged, p0, rn, rtiles)) return rc;
         const bool b3 = c->NB == 4 && c->have_b3 && c->opt_b3 && !table && !c->predictive && a.tail != nullptr;
         if (b3) {
-            // bf16 sub-label evaluation active (niw_lean.hip): the sweep kernel draws and STORES the labels (LSTORE instantiations), the sub-labels of
-            // the same tiles follow in a launch of their own -- every sub-cluster value of a sweep then comes from the same arithmetic
-            // First the tiles the cheap screens settle completely (niw_lean_kernel: labels and sub-labels in one go); what it leaves goes through
-            // the list.  A sweep that left more than 30 % of its tiles (overlapping clusters: the screens' later stages do the work) switches the
-            // lean kernel off for 15 sweeps -- every path gives the same labels and sub-labels, so the decision is free to be local.
-            // (round 6: the lean kernel runs the direction screen itself while the tables exist -- it used to stay off in that regime)
-            const bool lean_ok = c->opt_lean != 0 && c->opt_bracket && a.use_prev && a.screen_margin > 0.f && !final_argmax && a.lam == nullptr && c->K > 1 && c->d_hard &&
-                                 !(c->opt_lean_dir == 0 && c->sp_regime && c->opt_direction != 0 && c->sp_ready);
-            const int64_t nwt = (c->n + 63) / 64;
-            if (lean_ok && c->lean_off == 0 && c->lean_ran) {            // the verdict on the last sweep that ran the lean kernel
-                if ((int64_t)c->h_hard[0] * 10 > nwt * 3) { c->lean_off = c->lean_backoff; c->lean_backoff = std::min(2 * c->lean_backoff + 1, 1023); }
-                else c->lean_backoff = 15;
-                c->lean_ran = false;
-            }
-            const bool use_lean = lean_ok && c->lean_off == 0;
-            if (lean_ok && c->lean_off > 0) { c->lean_off -= 1; c->h_hard[0] = 0; }
-            const uint32_t *list = nullptr;
-            const bool parts = (c->opt_timing & 8) != 0 && (c->opt_timing & 1) != 0;
-            if (parts && !c->ev_part[0]) for (auto &e : c->ev_part) HIPCHK(c, hipEventCreate(&e));
-            if (use_lean) {
-                const size_t hw = hard_list_words(c->n);
-                uint32_t *mine = c->d_hard + (size_t)c->hard_flip * hw, *other = c->d_hard + (size_t)(c->hard_flip ^ 1) * hw;
-                c->hard_flip ^= 1;
-                c->lean_ran = true;
-                uint32_t *need2 = a.need ? c->h_need + 8 * (size_t)c->sweep_grid_max : nullptr;
-                // (tiles aligned to the bins of the sort that wrote the visiting order, when there is one and it fits the kernel's table)
-                const bool al = a.order != nullptr && c->perm_nbins > 0 && c->perm_nbins <= NIW_LEAN_MAX_BINS;
-                uint32_t *need3 = a.need ? c->h_need + 12 * (size_t)c->sweep_grid_max : nullptr;
-                NiwSweepArgs al_args = a;
-                if (!c->opt_lean_dir) { al_args.sp_frag = nullptr; al_args.sp_cons = nullptr; }
-                if (c->have_pb && c->opt_pair_ball && al_args.ball) al_args.ball |= c->opt_lean_norm_cert == 3 ? 14 : (c->opt_lean_norm_cert ? 6 : 2);      // (bits of `ball`: a field of its own re-lays every kernel's scalars; bit 3: the neighbours keep sn)
-                c->cert_fb = need2 != nullptr && (al_args.ball & 4) != 0 && !(al_args.sp_frag && al_args.sp_cons);
-#ifndef DPMM_STAMPS
-                al_args.dbg = reinterpret_cast<unsigned long long *>(c->d_cert_rec.get());
-#endif
-                HIPCHK(c, launch_niw_lean(al_args, mine, need2, other, al ? c->sb.bin_start : nullptr, al ? c->perm_nbins : 0, need3, c->sweep_grid, c->stream));
-                if (parts) HIPCHK(c, hipEventRecord(c->ev_part[0], c->stream));
-                list = mine;
-            }
-            a.bf16scr |= 4;
-            a.tdf = reinterpret_cast<const float *>(list);                         // (the LSTORE instantiations' tile list: null = all tiles)
-            const float *mdist_kept = a.mdist;
-            if (list) a.mdist = reinterpret_cast<const float *>(c->h_hard.get());        // (LIST instantiations: where the list's length goes; they also finish the spans' sub-labels)
-            HIPCHK(c, launch_niw_sweep(c->NB, a, c->sweep_grid, c->stream));
-            a.mdist = mdist_kept;
-            if (parts) HIPCHK(c, hipEventRecord(c->ev_part[1], c->stream));
-            c->have_parts = parts ? (use_lean ? 2 : 1) : 0;
-            a.bf16scr &= 3;
-            a.tdf = nullptr;
-            if (!list) HIPCHK(c, launch_niw_sub(a, nullptr, nullptr, c->sweep_grid, c->stream));      // (every tile; a list's spans were finished by the LIST launch)
+            if (int rc = niw_label_store_chain(c, a, lean_this_sweep(c, a))) return rc;
         } else {
             HIPCHK(c, launch_niw_sweep(c->NB, a, rgrid, c->stream));
             if (!table) c->have_parts = 0;          // (a one-launch sweep records no part events: dpmm_last_sweep_parts_ms must not mix its ev[0] / ev[1] with an older sweep's)

@@ -1,6 +1,7 @@
 // dpmm_kernels.h -- kernel argument blocks and host-side launchers (internal to libdpmmhip.so).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 #include "stats_ranges.h"
 
@@ -19,6 +20,20 @@ constexpr int REFB_FRAGS = 6, REFB_WORDS = REFB_FRAGS * 256;      // dwords of a
 constexpr int B3_WORDS = 3 * REFB_WORDS;                           // dwords of a matrix's three-plane bf16 image (planes h | m | l, each in the bracket's fragment layout): niw_lean.hip
 constexpr int B3_DVEC = 64;                                        // floats of a sub-cluster's offset vector d = R_s (mu_k - mu_s)
 
+// The flag bits of NiwSweepArgs::ball and ::bf16scr.  They share two ints because the block's layout is frozen (see the static_asserts behind it).
+enum NiwBall : int {
+    NIW_BALL_ON = 1,            // cluster-per-lane ball test in front of the per-point tail screen (records [K][16] behind the pair records)
+    NIW_BALL_PAIR_TABLE = 2,    // lean launch: the pair-ball table of niw_pair_ball_kernel belongs to these parameters
+    NIW_BALL_NORM_CERT = 4,     // lean launch: the norm certificate runs (DPMM_OPT_LEAN_NORM_CERT)
+    NIW_BALL_NB_LOOSE = 8,      // ... and the neighbours keep the loose norm sn in its comparison (DPMM_OPT_LEAN_NORM_CERT = 3)
+};
+enum NiwScreens : int {
+    NIW_SCR_ON = 1,             // D in 33..64 with tail records: bf16 screens in front of the Float32 16-row screen and of every survivor's first row block (DPMM_OPT_BF16_SCREENS)
+    NIW_SCR_DIR_FIRST = 2,      // (with sp_frag): the direction screen runs in FRONT of the tail-pair tests (the sweeps between two measuring ones)
+};
+
+// THE RULE of this block: its size and every offset are frozen (static_asserts below).  A slot that means something else in another launch gets a
+// union member and a name of its own -- never a cast, never a new field.
 struct NiwSweepArgs {
     const float *X;      // [n][ldx] points (zero padded to ldx = roundup(D,4))
     int64_t ldx;
@@ -29,7 +44,10 @@ struct NiwSweepArgs {
     const float *Rp;     // packed factor fragments [3K][NP][64][4]
     const float *mup;    // [3K][DP]
     const float *cst;    // [3K]: 3k: -logdet/2 + log w_k ; 3k+1+s: -logdet/2 + log lr_w[k][s]
-    const float *tdf;    // null: Gaussian a = cst - q/2 ; else Student-t (posterior predictive): [3K][2] = {df, (df+D)/2}, a = cst - hdf*log1p(q/df)
+    union {
+        const float *tdf;           // null: Gaussian a = cst - q/2 ; else Student-t (posterior predictive): [3K][2] = {df, (df+D)/2}, a = cst - hdf*log1p(q/df)
+        const uint32_t *tile_list;  // label-storing launches (NiwLabelStore; no Student-t mode there): [0] = count, [1 ..] = the spans to walk; null: all tiles
+    };
     float *scratch;      // a_k rows: scratch[k*scratch_stride + base + point_in_tile]
     int64_t scratch_stride;
     int scratch_by_tile; // 1: base = tile*TILE (full table, debug) ; 0: base = blockIdx*TILE
@@ -43,25 +61,34 @@ struct NiwSweepArgs {
     float screen_margin;      // > 0: skip clusters whose a_k is provably below (reference - margin) for a whole wave (NIW, D in 17..64)
     const float *tail;        // [ceil(K/2)][16][2] tail-screen records of the cluster-level matrices, pairs interleaved, then [K][16] ball records (null: no tail screen)
     int tail_g;               // row group (lane >> 4) whose x registers of the last block hold features D-4..D-1
-    int ball;                 // 1: cluster-per-lane ball test in front of the per-point tail screen (records [K][16] behind the pair records)
-    int bf16scr;              // bit 0: D in 33..64 with tail records: bf16 screens in front of the Float32 16-row screen and of every survivor's first row block (DPMM_OPT_BF16_SCREENS);
-                              // bit 1 (with sp_frag): the direction screen runs in FRONT of the tail-pair tests (the sweeps between two measuring ones).
-                              // (A field of its own for bit 1 cost the common kernel 32 spilled registers: the argument block's size decides how the compiler lays out its scalars.)
+    int ball;                 // NiwBall bits
+    int bf16scr;              // NiwScreens bits
+                              // (A field of its own for NIW_SCR_DIR_FIRST cost the common kernel 32 spilled registers: the argument block's size decides how the compiler lays out its scalars.)
     int bracket;              // 1: D in 33..64, homogeneous waves: certified bf16 bracket of the reference cluster's value first; its Float32 evaluation only if a cluster survives the screens (bf16 images behind the ball records)
     const float *lam;         // [K] lower bounds of lambda_min(Sigma_k^-1) (null: no scalar pre-screen)
-    const float *mdist;       // [K][K] distances between the cluster means
+    union {
+        const float *mdist;   // [K][K] distances between the cluster means (the scalar pre-screen's table: read only with lam)
+        uint32_t *list_len;   // launches that walk a tile_list (lam is null there): pinned host word that receives the list's length (nullable)
+    };
     int screen_lds;           // set by the launcher: screen operands of all K clusters are staged in LDS
     int use_prev;             // bins hold labels from a previous sweep (reference clusters of the screen)
     int lds_rows;             // set by the launcher: rows of the a_k table that live in LDS (0: global scratch)
-    const uint32_t *sp_frag;  // direction screen (D in 33..64, K <= 64; null: none): [K][4][2][64][4] bf16 fragments of the pair directions w, k0 major (launch_niw_direction);
-                              // D = 128, 256: one word per 128-point tile, 1 + k0 where launch_niw_bracket_big bracketed the tile's reference cluster, else 0 (null: none)
-    const float *sp_cons;     // [K][3][64]: per reference cluster k0 the constants {b, e, cst} of every cluster (direction_far, niw_sweep.hip);
-                              // D = 128, 256: per position of the visiting order the bracket's lower end of a_k0 (launch_niw_bracket_big)
+    union {
+        const uint32_t *sp_frag;   // direction screen (D in 33..64, K <= 64; null: none): [K][4][2][64][4] bf16 fragments of the pair directions w, k0 major (launch_niw_direction)
+        const uint32_t *brk_flag;  // D = 128, 256: one word per 128-point tile, 1 + k0 where launch_niw_bracket_big bracketed the tile's reference cluster, else 0 (null: none)
+    };
+    union {
+        const float *sp_cons;      // [K][3][64]: per reference cluster k0 the constants {b, e, cst} of every cluster (direction_far, niw_sweep.hip)
+        const float *brk_aref;     // D = 128, 256: per position of the visiting order the bracket's lower end of a_k0 (launch_niw_bracket_big)
+    };
     uint32_t *need;           // [waves][2] (pinned host memory, may be null): [0] = (candidates this wave's tiles kept behind the 4-row tests, saturating) << 16 | tiles
                               // (15 bits), bit 15: counted in FRONT of the tail-pair tests (direction screen first): an upper bound;
                               // [1] (written by the DIR kernel only) = (candidates its direction screens removed) << 16 | candidates they were given
-    unsigned long long *dbg;  // diagnostic builds (DPMM_STAMPS): per-wave phase cycle sums; product build, lean launch only: a byte per point of the shard, set for the points of
-                              // the tiles the norm certificate settled (dpmm_debug_norm_cert_points; null unless that call switched the record on)
+    union {
+        unsigned long long *dbg;   // diagnostic builds (DPMM_STAMPS): per-wave phase cycle sums
+        uint8_t *cert_points;      // product build, lean launch only: a byte per point of the shard, set for the points of the tiles the norm certificate
+                                   // settled (dpmm_debug_norm_cert_points; null unless that call switched the record on)
+    };
     int queue_rounds;         // D <= 64 kernel: rounds of tiles handed out through the queue at the end of the launch (-1: automatic)
     int prio;                 // 1: s_setprio -- low while the wave streams MFMAs, high in its scalar / VALU phases (DPMM_OPT_WAVE_PRIO)
     unsigned long long *work; // [4] tile queue head of the LDS-staged kernel, [8 + 16 q], q < 8: the eight queue heads of the D <= 64 kernel (one 128-byte
@@ -69,10 +96,28 @@ struct NiwSweepArgs {
                               // wave w of this launch (wave tiles, full evaluations, 16-row screens, tail-screened cluster pairs, reference brackets), plain
                               // stores at kernel end, summed by the reader; may be null
 };
+// The argument block's size decides how the compiler lays out its scalars (a field of its own for one flag bit cost the common kernel 32 spilled
+// registers), so the layout is pinned: a change that moves any of this re-lays every sweep kernel's scalars and has to be measured as a kernel change.
+static_assert(sizeof(NiwSweepArgs) == 256, "NiwSweepArgs: frozen size");
+static_assert(offsetof(NiwSweepArgs, tdf) == 72 && offsetof(NiwSweepArgs, tile_list) == 72, "NiwSweepArgs: frozen layout");
+static_assert(offsetof(NiwSweepArgs, ball) == 164 && offsetof(NiwSweepArgs, bf16scr) == 168, "NiwSweepArgs: frozen layout");
+static_assert(offsetof(NiwSweepArgs, mdist) == 184 && offsetof(NiwSweepArgs, list_len) == 184, "NiwSweepArgs: frozen layout");
+static_assert(offsetof(NiwSweepArgs, sp_frag) == 208 && offsetof(NiwSweepArgs, brk_flag) == 208, "NiwSweepArgs: frozen layout");
+static_assert(offsetof(NiwSweepArgs, sp_cons) == 216 && offsetof(NiwSweepArgs, brk_aref) == 216, "NiwSweepArgs: frozen layout");
+static_assert(offsetof(NiwSweepArgs, dbg) == 232 && offsetof(NiwSweepArgs, cert_points) == 232, "NiwSweepArgs: frozen layout");
+static_assert(offsetof(NiwSweepArgs, work) == 248, "NiwSweepArgs: frozen layout");
+
+// What a caller of launch_niw_sweep asks for beyond the block (host side only, D in 33..64): the label-storing instantiations -- labels drawn and stored,
+// niw_sub_kernel draws the sub-labels -- for every tile or for the spans of tile_list; the launcher writes NiwSweepArgs::tile_list / list_len itself.
+struct NiwLabelStore {
+    bool store_labels = false;
+    const uint32_t *tile_list = nullptr;   // device: [0] = count, [1 ..] = spans (null: all tiles)
+    uint32_t *list_len = nullptr;          // pinned host word (nullable), written only when a list is walked
+};
 
 int niw_tile_points(int NB);
 int niw_occupancy(int NB);  // resident 256-thread workgroups per CU the sweep kernel is built for
-hipError_t launch_niw_sweep(int NB, const NiwSweepArgs &a, int grid, hipStream_t s);
+hipError_t launch_niw_sweep(int NB, const NiwSweepArgs &a, int grid, hipStream_t s, const NiwLabelStore &ls = {});
 hipError_t launch_niw_refb_debug(const NiwSweepArgs &a, int k, float c_override, float *qhi_out, float *q_out, hipStream_t s);   // needs X, ldx, n, K, Rp, mup, tail
 hipError_t launch_niw_screen_prep(const float *R, const float *mu, int D, int K, float *lam, float *dist, const int32_t *slot, hipStream_t s);
 hipError_t launch_niw_pack(const float *R, const float *mu, float *Rp, float *mup, int D, int NB, int nmat, float *tail, const float *cst,
@@ -80,8 +125,15 @@ hipError_t launch_niw_pack(const float *R, const float *mu, float *Rp, float *mu
 // Tables of the direction screen from the sweep's own images (Rp, mup, cst of the K cluster-level distributions; D in 33..64, K <= SP_MAXK):
 // frag [K][SP_FRAG_WORDS], cons [K][SP_CONS_FLOATS]
 constexpr int SP_MAXK = 64, SP_FRAG_WORDS = 4 * 2 * 256, SP_CONS_FLOATS = 3 * 64;
+// The launch-independent part of "this launch is a steady-state one" (the FAST instantiations; launch_direct adds NB >= 2 and the LDS budget, which every
+// K <= SP_MAXK meets at D in 33..64), and THE condition of the direction-screen instantiations (DIR) on top of it: the tables are there, the bf16 screens
+// are on and K fits.  launch_direct, launch_niw_lean (which asks K >= 3 more) and run_sweep's record of "the DIR kernel wrote its yield words" all ask here.
+inline bool niw_steady_launch(const NiwSweepArgs &a, bool store_labels) {
+    return a.screen_margin > 0.f && (store_labels || !a.tdf) && !a.scratch_by_tile && !a.labels_only && a.K > 1 && a.lam == nullptr && a.tail != nullptr && !a.final_argmax;
+}
+inline bool niw_dir_screen(const NiwSweepArgs &a) { return a.sp_frag && a.sp_cons && a.bf16scr && a.K <= SP_MAXK; }
 // bf16 images of the K cluster-level factors for the reference bracket of the LDS-staged kernels (NB = 8, 16), from the Float32 fragment
-// image: out [K][niw_refb_big_words(NB)]  (passed to the sweep as NiwSweepArgs::sp_frag)
+// image: out [K][niw_refb_big_words(NB)]  (launch_niw_bracket_big reads it; the sweep sees that launch's output as brk_flag / brk_aref)
 inline size_t niw_refb_big_words(int NB) { size_t c = 0; for (int bi = 0; bi < NB; ++bi) c += NB / 2 - bi / 2; return c * 256; }
 hipError_t launch_niw_refb_big(const float *Rp, int NB, int K, uint32_t *out, hipStream_t s);
 // the bracket itself, in front of the sweep launch (same NiwSweepArgs: X, order, bins, mup, cst): tile_flag [ceil(n / 128)], aref [128 ceil(n / 128)]

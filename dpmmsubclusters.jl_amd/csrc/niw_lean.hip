@@ -306,19 +306,19 @@ __device__ __forceinline__ void niw_lean_body(NiwSweepArgs A, uint32_t *__restri
     // (an instantiation of its own, as in the general kernel: the screen's code in the ONE kernel cost the tiles that never use it 8 spilled vector
     //  registers and 10 % -- lean launch 1.00 -> 1.11 ms at N = 1e7 on the bench data)
     const bool use_dir = DIR && A.sp_frag != nullptr && A.sp_cons != nullptr && A.bf16scr && K >= 3 && K <= SP_MAXK;
-    const bool dir_first = use_dir && (A.bf16scr & 2) != 0;
+    const bool dir_first = use_dir && (A.bf16scr & NIW_SCR_DIR_FIRST) != 0;
     unsigned nw_sp = 0, nw_cand = 0, nw_dcand = 0, nw_dexcl = 0, nw_ctiles = 0;
     // the ball test's records (16 floats per cluster, the same for every tile) once per workgroup in LDS: the test then waits for an LDS read
     // instead of an L2 round trip per tile
     constexpr int BALL_LDS_K = 256;
     __shared__ __attribute__((aligned(16))) float ball_lds[BALL_LDS_K * 16];
     const bool ball_in_lds = A.ball && K <= BALL_LDS_K;
-    // the pair-ball test (A.ball bit 1: the table of niw_pair_ball_kernel belongs to these parameters; not in the direction-screen instantiation: on
+    // the pair-ball test (NIW_BALL_PAIR_TABLE: the table of niw_pair_ball_kernel belongs to these parameters; not in the direction-screen instantiation: on
     // overlapping clusters it clears nothing): the norm bounds s_j once per workgroup in LDS, the row of distances of a tile's k0 requested per tile
     __shared__ float pb_s[PB_MAXK];
-    const bool use_pb = !DIR && (A.ball & 2) != 0 && ball_in_lds && K <= PB_MAXK;
+    const bool use_pb = !DIR && (A.ball & NIW_BALL_PAIR_TABLE) != 0 && ball_in_lds && K <= PB_MAXK;
     const float *pb_d = pair_ball_table(A.tail, K);
-    // THE NORM CERTIFICATE (A.ball bit 2, DPMM_OPT_LEAN_NORM_CERT).  The bracket's only product is the threshold a_k0(x) - margin of the tests behind it, and
+    // THE NORM CERTIFICATE (NIW_BALL_NORM_CERT, DPMM_OPT_LEAN_NORM_CERT).  The bracket's only product is the threshold a_k0(x) - margin of the tests behind it, and
     //     a_k0(x) = c0 - 1/2 |R_k0 z|^2 >= c0 - 1/2 (s_k0 r)^2     for |z| <= r, s_k0 >= |R_k0|_2
     // needs nothing but the tile's radius r (pb_r below, certified from plane h) and the table's tighter norm bound sn2 (pair_ball_block).  Where the
     // pair-ball test with THIS threshold leaves no candidate, the tile is settled without the bracket, its fragments, the ball and the tail pairs; any
@@ -326,7 +326,7 @@ __device__ __forceinline__ void niw_lean_body(NiwSweepArgs A, uint32_t *__restri
     // errs by <= 64 * 2^-24 | |R| |z| |, | |R| |_2 <= 8 |R|_2: a factor 1 + 3.1e-5 on |R z|, squared and summed in Float32: 1 + 6.6e-5; the four roundings
     // of the expression itself add 2.4e-7.
     // THE NEIGHBOURS take the same bound in the certificate's comparison: pb_sc holds sn2 for EVERY cluster -- s_j of the certificate's pair-ball loop
-    // (selected here, once per workgroup; A.ball bit 3, DPMM_OPT_LEAN_NORM_CERT = 3: sn, the behaviour before, for comparisons in one process).  Slack
+    // (selected here, once per workgroup; NIW_BALL_NB_LOOSE, DPMM_OPT_LEAN_NORM_CERT = 3: sn, the behaviour before, for comparisons in one process).  Slack
     // on the neighbours' side: s_j enters lb = D_k0,j - s_j r once; sn2_j >= |R_j|_2 with its own roundings covered by its factor 1 + 1e-6
     // (pair_ball_block), r carries its 0.5 %, D_k0,j its 1e-4 and the matrix-vector product's 1e-4 sn_j |v| (formed with the LOOSE sn: more than it
     // needs); the fma rounds lb once (2^-24 of operands the 0.5 % of r dwarfs), and ub < thr compares against a threshold that carries eps = 1e-4 and
@@ -336,9 +336,9 @@ __device__ __forceinline__ void niw_lean_body(NiwSweepArgs A, uint32_t *__restri
     // of a chain differ (tests/test_gpu_lean_norm_cert.py counts them: D = 36, K = 65, 6 sd).  The certificate's tiles are the ones that save the bracket.
     // (Three arrays, not one with a per-tile choice: a scalar load of sn2[k0] under the flag cost this kernel 7 spilled vector registers.)
     __shared__ float pb_s0[PB_MAXK], pb_sc[PB_MAXK];
-    const bool use_cert = !DIR && use_pb && (A.ball & 4) != 0;
+    const bool use_cert = !DIR && use_pb && (A.ball & NIW_BALL_NORM_CERT) != 0;
     if (use_pb) {
-        const float *s_own = pb_d + (size_t)K * K + K, *s_nb = (A.ball & 12) == 4 ? s_own : s_own - K;
+        const float *s_own = pb_d + (size_t)K * K + K, *s_nb = (A.ball & (NIW_BALL_NORM_CERT | NIW_BALL_NB_LOOSE)) == NIW_BALL_NORM_CERT ? s_own : s_own - K;
         for (int e = threadIdx.x; e < K; e += 256) { pb_s[e] = s_own[e - K]; pb_sc[e] = s_nb[e]; pb_s0[e] = s_own[e]; }
     }
     if (ball_in_lds) {
@@ -608,7 +608,7 @@ __device__ __forceinline__ void niw_lean_body(NiwSweepArgs A, uint32_t *__restri
             b3_eval(A.tail, K, k0, Z, H, lane, g, bl, br);
             if (valid) A.bins[myp32] = 2 * k0 + draw2(bl, br, u_sub);
 #ifndef DPMM_STAMPS
-            if (cheap && A.dbg && valid) reinterpret_cast<uint8_t *>(A.dbg)[myp32] = 1;      // (dpmm_debug_norm_cert_points: the points of the tiles settled by the certificate)
+            if (cheap && A.cert_points && valid) A.cert_points[myp32] = 1;      // (dpmm_debug_norm_cert_points: the points of the tiles settled by the certificate)
 #endif
             ++nw_easy;
         }
@@ -657,7 +657,7 @@ __global__ __launch_bounds__(256, 2) void niw_lean_kernel_dir(NiwSweepArgs A, ui
 hipError_t launch_niw_lean(const NiwSweepArgs &a, uint32_t *list, uint32_t *need2, uint32_t *other_list, const int32_t *bin_start, int nbins, uint32_t *need3, int grid, hipStream_t s) {
     if (!a.tail || a.n <= 0 || !list) return hipErrorInvalidValue;
     if (nbins > NIW_LEAN_MAX_BINS) { bin_start = nullptr; nbins = 0; }
-    if (a.sp_frag && a.sp_cons && a.bf16scr && a.K >= 3 && a.K <= SP_MAXK) DPMM_LAUNCH(niw_lean_kernel_dir, dim3(grid), dim3(256), 0, s, a, list, need2, other_list, bin_start, nbins, need3);
+    if (niw_dir_screen(a) && a.K >= 3) DPMM_LAUNCH(niw_lean_kernel_dir, dim3(grid), dim3(256), 0, s, a, list, need2, other_list, bin_start, nbins, need3);
     else DPMM_LAUNCH(niw_lean_kernel, dim3(grid), dim3(256), 0, s, a, list, need2, other_list, bin_start, nbins, need3);
     return hipGetLastError();
 }

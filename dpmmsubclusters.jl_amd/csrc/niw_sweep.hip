@@ -646,11 +646,11 @@ __global__ __launch_bounds__(256, (NB <= 8 ? 2 : 1)) void niw_sweep_kernel(NiwSw
             // cluster survives them for some wave (else the draw returns k0 whatever the exact value is: the one-cluster draw below).
             bool bracketed = false, ref_skipped = false;
             if constexpr (NB >= 8) {
-                // (launch_niw_bracket_big ran in front of this launch: A.sp_frag = one word per tile -- 1 + k0 where every point of the tile
-                // was in k0, else 0 --, A.sp_cons = the bracket's lower end of a_k0 per position of the visiting order)
-                if (A.sp_frag != nullptr && nref == 1 && A.sp_frag[tile] == (uint32_t)(k0 + 1)) {
+                // (launch_niw_bracket_big ran in front of this launch: A.brk_flag = one word per tile -- 1 + k0 where every point of the tile
+                // was in k0, else 0 --, A.brk_aref = the bracket's lower end of a_k0 per position of the visiting order)
+                if (A.brk_flag != nullptr && nref == 1 && A.brk_flag[tile] == (uint32_t)(k0 + 1)) {
                     bracketed = true;
-                    aref = valid ? A.sp_cons[mypos] : -INFINITY;
+                    aref = valid ? A.brk_aref[mypos] : -INFINITY;
                     ++nw_br;
                 }
             }
@@ -1049,21 +1049,21 @@ __device__ __forceinline__ void load_rb0(const float *__restrict__ Rm, const flo
 // for all four point groups) would cost the common kernel 40 spilled registers and 15 % of its time for a branch it never takes.
 // LSTORE (D in 33 .. 64 while the bf16 sub-label evaluation of niw_lean.hip is active): the instantiation stops behind the label draw and
 // STORES the labels (bins = 2 z; the sub-label bit is a placeholder) -- niw_sub_kernel draws the sub-labels of the same tiles in a launch of
-// its own.  The tiles come from a list (A.tdf re-used as `const uint32_t *`: [0] = count, [1 ..] = wave-tile indices; Student-t mode does
+// its own.  The tiles come from a list (A.tile_list, the slot of A.tdf: [0] = count, [1 ..] = wave-tile indices; Student-t mode does
 // not exist in these instantiations) or, with a null list, from the usual schedule.
-// LIST (with LSTORE): A.tdf names a list of spans to process instead of every tile -- an instantiation of its own, so that the all-tiles
+// LIST (with LSTORE): A.tile_list names a list of spans to process instead of every tile -- an instantiation of its own, so that the all-tiles
 // LSTORE kernels do not carry the list's state (15 instead of 4 spilled registers, all-tiles sweep 1.53 -> 1.64 ms when they did)
 template <int NB, int NG, int OCC, bool FAST = false, bool DIR = false, bool LSTORE = false, bool LIST = false>
 __global__ __launch_bounds__(256, OCC) void niw_sweep_direct_kernel(NiwSweepArgs A) {
     const float *const a_tdf = LSTORE ? nullptr : A.tdf;
     static_assert(!LIST || LSTORE, "a list belongs to the label-storing instantiations");
-    const uint32_t *const tlist = LIST ? reinterpret_cast<const uint32_t *>(A.tdf) : nullptr;
+    const uint32_t *const tlist = LIST ? A.tile_list : nullptr;
     if constexpr (LIST) {
         // most sweeps hand on nothing (and a workgroup whose four waves are beyond the list has nothing to do either): leave before the staging below;
-        // the list's length still goes to the host (A.mdist: see further down)
+        // the list's length still goes to the host (A.list_len: see further down)
         const uint32_t lc = tlist[0];
         if (lc == 0u || blockIdx.x * 4u >= lc) {
-            if (A.mdist && blockIdx.x == 0 && threadIdx.x == 0) *reinterpret_cast<uint32_t *>(const_cast<float *>(A.mdist)) = lc;
+            if (A.list_len && blockIdx.x == 0 && threadIdx.x == 0) *A.list_len = lc;
             return;
         }
     }
@@ -1160,9 +1160,9 @@ __global__ __launch_bounds__(256, OCC) void niw_sweep_direct_kernel(NiwSweepArgs
     int li = wave_id;
     const int lcount = LIST ? (int)tlist[0] : 0;
     const int tile_sent = LIST ? 0x7fffffff : nwtiles;      // "no further tile"
-    // (the list's length for the host's regime decision: A.mdist -- the pre-screen's table, never read when a list is walked (lam == nullptr) --
-    // carries a pinned word for it; a field of its own would move every instantiation's scalars)
-    if constexpr (LIST) { if (A.mdist && blockIdx.x == 0 && tid == 0) *reinterpret_cast<uint32_t *>(const_cast<float *>(A.mdist)) = tlist[0]; }
+    // (the list's length for the host's regime decision: A.list_len, a pinned word in the slot of mdist -- the pre-screen's table, never read when a
+    // list is walked (lam == nullptr); a field of its own would move every instantiation's scalars)
+    if constexpr (LIST) { if (A.list_len && blockIdx.x == 0 && tid == 0) *A.list_len = tlist[0]; }
     int l_pos = 0, l_end = 0;                  // (wave-uniform, positions < 2^31)
     if (LIST) {
         tile0 = li < lcount ? li : -1;
@@ -1529,10 +1529,10 @@ __global__ __launch_bounds__(256, OCC) void niw_sweep_direct_kernel(NiwSweepArgs
                         ++nw_tail;                                                                                               \
                         cand &= ~((unsigned long long)tail_pair_far(tail_load_pair(A.tail, pr), xt, my_thr) << sh);             \
                     }
-                    // (DIR, (A.bf16scr & 2): the direction screen runs in FRONT of the tail pairs -- in the regime that switched it on they exclude
+                    // (DIR, NIW_SCR_DIR_FIRST: the direction screen runs in FRONT of the tail pairs -- in the regime that switched it on they exclude
                     // nothing and cost 16 pair tests per tile; every 32nd sweep keeps the usual order and counts what the 4-row tests leave)
                     if constexpr (!DIR) { DPMM_TAIL_PAIRS() }
-                    else if (!(A.bf16scr & 2)) { DPMM_TAIL_PAIRS() }
+                    else if (!(A.bf16scr & NIW_SCR_DIR_FIRST)) { DPMM_TAIL_PAIRS() }
                     if constexpr (NB == 4) {
                         if (A.bf16scr) {
                             // bf16 screens of the remaining candidates, software-pipelined: the operands of the NEXT candidate (fragment, tail means,
@@ -1554,7 +1554,7 @@ __global__ __launch_bounds__(256, OCC) void niw_sweep_direct_kernel(NiwSweepArgs
                                     nw_dcand += (unsigned)nc;
                                     nw_dexcl += (unsigned)(nc - __builtin_popcountll(cand));
                                 }
-                                if ((A.bf16scr & 2)) { DPMM_TAIL_PAIRS() }
+                                if ((A.bf16scr & NIW_SCR_DIR_FIRST)) { DPMM_TAIL_PAIRS() }
                             }
                             const u32x4_t *Rb0 = reinterpret_cast<const u32x4_t *>(refb_records(A.tail, K));
                             auto loadk = [&](int k, u32x4_t &a, f32x4 &m4, float &ck) {
@@ -1854,7 +1854,7 @@ __global__ __launch_bounds__(256, OCC) void niw_sweep_direct_kernel(NiwSweepArgs
     if (A.need && lane == 0) {                // (this launch only: plain store into the host's pinned block)
         const unsigned nc = DIR ? nw_cand : nw_bb;
         uint32_t word = ((nc < 65535u ? nc : 65535u) << 16) | (nw_tiles < 32767u ? nw_tiles : 32767u);
-        if constexpr (DIR) { if ((A.bf16scr & 2)) word = (word & 0xFFFF7FFFu) | 0x8000u; }      // (bit 15: counted in front of the tail pairs, an upper bound)
+        if constexpr (DIR) { if ((A.bf16scr & NIW_SCR_DIR_FIRST)) word = (word & 0xFFFF7FFFu) | 0x8000u; }      // (bit 15: counted in front of the tail pairs, an upper bound)
         A.need[2 * wave_id] = word;
         if constexpr (DIR) A.need[2 * wave_id + 1] = ((nw_dexcl < 65535u ? nw_dexcl : 65535u) << 16) | (nw_dcand < 65535u ? nw_dcand : 65535u);
     }
@@ -1869,8 +1869,22 @@ __global__ __launch_bounds__(256, OCC) void niw_sweep_direct_kernel(NiwSweepArgs
 
 #undef DPMM_TAIL_PAIRS
 
+// one instantiation: its dynamic LDS limit on first use, then the launch
+template <int NB, int NG, int OCC, bool FAST, bool DIR, bool LSTORE, bool LIST>
+static hipError_t launch_one(const NiwSweepArgs &b, int grid, size_t lds_bytes, hipStream_t s) {
+    static bool attr_set = false;
+    if (!attr_set) {
+        hipFuncSetAttribute((const void *)niw_sweep_direct_kernel<NB, NG, OCC, FAST, DIR, LSTORE, LIST>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 / OCC);
+        attr_set = true;
+    }
+    DPMM_LAUNCH((niw_sweep_direct_kernel<NB, NG, OCC, FAST, DIR, LSTORE, LIST>), dim3(grid), dim3(256), lds_bytes, s, b);
+    return hipGetLastError();
+}
+
+// (FAST, DIR, LSTORE, LIST) decided once; eleven instantiations exist: generic and FAST for every NB, and for NB = 4 FAST + DIR and {generic, FAST, FAST + DIR} x
+// {LSTORE, LSTORE + LIST}
 template <int NB, int NG, int OCC>
-static hipError_t launch_direct(const NiwSweepArgs &a, int grid, hipStream_t s) {
+static hipError_t launch_direct(const NiwSweepArgs &a, const NiwLabelStore &ls, int grid, hipStream_t s) {
     // a_k table in LDS: the CU's 160 KiB split over OCC resident workgroups of 4 waves
     NiwSweepArgs b = a;
     const int budget_rows = (int)((160 * 1024 / OCC - 512) / (4 * 16 * NG * sizeof(float)));
@@ -1882,62 +1896,31 @@ static hipError_t launch_direct(const NiwSweepArgs &a, int grid, hipStream_t s) 
     b.screen_lds = (NB >= 2 && a.screen_margin > 0.f && lds_bytes + screen_bytes + slot_bytes + 1024 <= (size_t)(160 * 1024 / OCC)) ? 1 : 0;
     if (b.screen_lds) lds_bytes += screen_bytes;
     lds_bytes += slot_bytes;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipFuncSetAttribute((const void *)niw_sweep_direct_kernel<NB, NG, OCC>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 / OCC);
-        attr_set = true;
-    }
-    // bit 2 of bf16scr (NB = 4, set by run_sweep while the bf16 sub-label evaluation is active): the LSTORE instantiations -- labels only, stored;
-    // b.tdf then carries the tile list (or null: all tiles), never Student-t parameters
-    const bool lstore = NB == 4 && (a.bf16scr & 4) != 0;
-    b.bf16scr &= 3;
-    const bool fast = NB >= 2 && b.screen_margin > 0.f && (lstore || !b.tdf) && !b.scratch_by_tile && !b.labels_only && b.K > 1 && b.lam == nullptr &&
-                      b.tail != nullptr && b.lds_rows >= b.K && !b.final_argmax;
+    // store_labels (NB = 4, asked for by run_sweep while the bf16 sub-label evaluation is active): the LSTORE instantiations -- labels only, stored;
+    // the slot of tdf then carries the tile list (or null: all tiles), never Student-t parameters, and with a list the slot of mdist its length's word
+    const bool lstore = NB == 4 && ls.store_labels, list = lstore && ls.tile_list != nullptr;
+    if (lstore) b.tile_list = ls.tile_list;
+    if (list) b.list_len = ls.list_len;
+    const bool fast = NB >= 2 && niw_steady_launch(b, lstore) && b.lds_rows >= b.K;
+    const bool dir = NB == 4 && fast && niw_dir_screen(b);
+    static_assert(NB != 4 || budget_rows >= SP_MAXK, "at NB = 4 a steady launch with K <= SP_MAXK must be FAST: run_sweep's sp_last asks niw_steady_launch && niw_dir_screen");
+    // (a list of spans, behind niw_lean_kernel, takes the direction screen too while its tables exist: the lean kernel runs in that regime, and the
+    //  spans it hands on there keep dozens of candidates behind the 4-row tests)
+    if (!fast && !lstore) return launch_one<NB, NG, OCC, false, false, false, false>(b, grid, lds_bytes, s);
     if constexpr (NB == 4) {
-        if (lstore) {
-            static bool attr_ls = false;
-            if (!attr_ls) {
-                hipFuncSetAttribute((const void *)niw_sweep_direct_kernel<NB, NG, OCC, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 / OCC);
-                hipFuncSetAttribute((const void *)niw_sweep_direct_kernel<NB, NG, OCC, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 / OCC);
-                hipFuncSetAttribute((const void *)niw_sweep_direct_kernel<NB, NG, OCC, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 / OCC);
-                hipFuncSetAttribute((const void *)niw_sweep_direct_kernel<NB, NG, OCC, false, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 / OCC);
-                hipFuncSetAttribute((const void *)niw_sweep_direct_kernel<NB, NG, OCC, true, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 / OCC);
-                hipFuncSetAttribute((const void *)niw_sweep_direct_kernel<NB, NG, OCC, true, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 / OCC);
-                attr_ls = true;
-            }
-            if (b.tdf != nullptr) {             // a list of spans (behind niw_lean_kernel): with the direction screen while its tables exist (round 6: the lean kernel
-                                                //  runs in that regime too, and the spans it hands on there keep dozens of candidates behind the 4-row tests)
-                if (fast && b.sp_frag && b.sp_cons && b.bf16scr && b.K <= SP_MAXK) DPMM_LAUNCH((niw_sweep_direct_kernel<NB, NG, OCC, true, true, true, true>), dim3(grid), dim3(256), lds_bytes, s, b);
-                else if (fast) DPMM_LAUNCH((niw_sweep_direct_kernel<NB, NG, OCC, true, false, true, true>), dim3(grid), dim3(256), lds_bytes, s, b);
-                else DPMM_LAUNCH((niw_sweep_direct_kernel<NB, NG, OCC, false, false, true, true>), dim3(grid), dim3(256), lds_bytes, s, b);
-                return hipGetLastError();
-            }
-            if (fast && b.sp_frag && b.sp_cons && b.bf16scr && b.K <= SP_MAXK) DPMM_LAUNCH((niw_sweep_direct_kernel<NB, NG, OCC, true, true, true>), dim3(grid), dim3(256), lds_bytes, s, b);
-            else if (fast) DPMM_LAUNCH((niw_sweep_direct_kernel<NB, NG, OCC, true, false, true>), dim3(grid), dim3(256), lds_bytes, s, b);
-            else DPMM_LAUNCH((niw_sweep_direct_kernel<NB, NG, OCC, false, false, true>), dim3(grid), dim3(256), lds_bytes, s, b);
-            return hipGetLastError();
+        if (lstore && !list) {
+            if (!fast) return launch_one<NB, NG, OCC, false, false, true, false>(b, grid, lds_bytes, s);
+            if (!dir) return launch_one<NB, NG, OCC, true, false, true, false>(b, grid, lds_bytes, s);
+            return launch_one<NB, NG, OCC, true, true, true, false>(b, grid, lds_bytes, s);
         }
-        if (fast && b.sp_frag && b.sp_cons && b.bf16scr && b.K <= SP_MAXK) {
-            static bool attr_dir = false;
-            if (!attr_dir) {
-                hipFuncSetAttribute((const void *)niw_sweep_direct_kernel<NB, NG, OCC, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 / OCC);
-                attr_dir = true;
-            }
-            DPMM_LAUNCH((niw_sweep_direct_kernel<NB, NG, OCC, true, true>), dim3(grid), dim3(256), lds_bytes, s, b);
-            return hipGetLastError();
+        if (list) {
+            if (!fast) return launch_one<NB, NG, OCC, false, false, true, true>(b, grid, lds_bytes, s);
+            if (!dir) return launch_one<NB, NG, OCC, true, false, true, true>(b, grid, lds_bytes, s);
+            return launch_one<NB, NG, OCC, true, true, true, true>(b, grid, lds_bytes, s);
         }
+        if (dir) return launch_one<NB, NG, OCC, true, true, false, false>(b, grid, lds_bytes, s);
     }
-    if (fast) {
-        static bool attr_fast = false;
-        if (!attr_fast) {
-            hipFuncSetAttribute((const void *)niw_sweep_direct_kernel<NB, NG, OCC, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 / OCC);
-            attr_fast = true;
-        }
-        DPMM_LAUNCH((niw_sweep_direct_kernel<NB, NG, OCC, true>), dim3(grid), dim3(256), lds_bytes, s, b);
-    } else {
-        DPMM_LAUNCH((niw_sweep_direct_kernel<NB, NG, OCC>), dim3(grid), dim3(256), lds_bytes, s, b);
-    }
-    return hipGetLastError();
+    return launch_one<NB, NG, OCC, true, false, false, false>(b, grid, lds_bytes, s);
 }
 
 template <int NB, int NG, int CH>
@@ -1957,11 +1940,11 @@ int niw_tile_points(int NB) {
     }
 }
 
-hipError_t launch_niw_sweep(int NB, const NiwSweepArgs &a, int grid, hipStream_t s) {
+hipError_t launch_niw_sweep(int NB, const NiwSweepArgs &a, int grid, hipStream_t s, const NiwLabelStore &ls) {
     switch (NB) {
-        case 1: return launch_direct<1, 4, 4>(a, grid, s);
-        case 2: return launch_direct<2, 4, 3>(a, grid, s);
-        case 4: return launch_direct<4, 4, 2>(a, grid, s);
+        case 1: return launch_direct<1, 4, 4>(a, ls, grid, s);
+        case 2: return launch_direct<2, 4, 3>(a, ls, grid, s);
+        case 4: return launch_direct<4, 4, 2>(a, ls, grid, s);
         case 8: return launch_cfg<8, 2, 2>(a, grid, s);
         case 16: return launch_cfg<16, 2, 1>(a, grid, s);
         default: return hipErrorInvalidValue;

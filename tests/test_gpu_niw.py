@@ -1090,6 +1090,37 @@ def test_direction_screen_does_not_change_labels(pkg, D, sep, K):
     assert w1["bf16_bottom_screens"] <= w0["bf16_bottom_screens"] and w1["screens16"] <= w0["screens16"] and w1["full_evals"] <= w0["full_evals"]
 
 
+def test_direction_screen_in_the_one_launch_sweep(pkg):
+    """The direction-screen instantiation of the ONE-launch sweep (labels and sub-labels from the same kernel) runs only with DPMM_OPT_B3_SUBLABELS = 0 and the
+    screen's tables: every other direction test takes the label-storing instantiations.  Smallest shape that reaches it: D = 64, K = 3 (the least the
+    tables are written for), 700 points = two full 256-point tiles and a ragged third whose last 64-point wave tile is ragged too.  Labels and sub-labels
+    of a chain of sweeps equal the chain with DPMM_OPT_DIRECTION_SCREEN = 0, bit for bit."""
+    from dpmmsubclusters_jl_amd import binding
+    D, n, K = 64, 700, 3
+    P = make_problem(D, n, K, seed=171, sep=1.0, sorted_points=True)
+    out = {}
+    for on in (1, 0):
+        wk = gpu_worker(pkg, P, seed=31)
+        wk.set_option(binding.OPT_B3_SUBLABELS, 0)
+        wk.set_option(binding.OPT_DIRECTION_SCREEN, on)
+        wk.set_timing(15)
+        wk.set_labels(P["z"] + 1, 1 + (np.arange(n) & 1))
+        wk.suffstats_packed(None)                      # the bin-sorted visiting order
+        wk.set_params_niw(P["mu"], P["invS"], P["logdet"], P["lr"], P["w"])
+        labs = []
+        for ep in (1, 2, 3):
+            wk.sweep(ep)
+            labs.append(wk.get_labels())
+            assert tuple(wk.last_sweep_parts_ms()) == (0.0, 0.0, 0.0)      # one launch: no part events
+            wk.suffstats_packed(None)
+            wk.set_params_niw(P["mu"], P["invS"], P["logdet"], P["lr"], P["w"])
+        out[on] = labs
+        wk.close()
+    for a, b in zip(out[1], out[0]):
+        assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
+    assert len(np.unique(out[1][-1][0])) == K          # (not a degenerate draw)
+
+
 @pytest.mark.parametrize("D,sep,K,n", [(64, 2.0, 12, 60000), (64, 1.0, 20, 60000), (52, 2.0, 7, 30000), (64, 1.5, 60, 90000), (64, 0.3, 5, 20000), (64, 3.0, 3, 20000)])
 def test_lean_kernel_with_the_direction_screen(pkg, D, sep, K, n):
     """Round 6 (DPMM_OPT_LEAN_DIRECTION): while the direction screen's tables exist, niw_lean_kernel runs the screen itself -- its operand is plane h
