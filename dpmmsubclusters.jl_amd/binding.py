@@ -212,6 +212,22 @@ ABI_TYPICALITY = [
 ]
 
 
+class ExplainOut(ctypes.Structure):
+    """dpmm_explain_out (include/dpmm_hip_explain.h): host or device addresses (the two counters always host), 0 / None = not asked for;
+    top (0: all D features in order) and ld, the entries between two points' rows."""
+    _fields_ = [("labels", ctypes.c_void_p), ("mahalanobis", ctypes.c_void_p), ("tail", ctypes.c_void_p), ("skipped", ctypes.c_void_p),
+                ("incomplete", ctypes.c_void_p), ("residual", ctypes.c_void_p), ("zscore", ctypes.c_void_p), ("feature_tail", ctypes.c_void_p),
+                ("features", ctypes.c_void_p), ("top", ctypes.c_int32), ("ld", ctypes.c_int64)]
+
+
+# include/dpmm_hip_explain.h: per-feature conditional residuals, z-scores and tails of a point under its own cluster (additive; bound next to ABI)
+ABI_EXPLAIN = [
+    ("dpmm_explain_points", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ExplainOut)]),
+    ("dpmm_explain_points_device", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ExplainOut)]),
+]
+EXPLAIN_MAX_TOP = 16                   # DPMM_EXPLAIN_MAX_TOP
+
+
 class HoldoutOut(ctypes.Structure):
     """dpmm_holdout_out (include/dpmm_hip_holdout.h): host addresses, 0 / None = not asked for."""
     _fields_ = [("total", ctypes.c_void_p), ("stored", ctypes.c_void_p), ("skipped", ctypes.c_void_p), ("incomplete", ctypes.c_void_p),
@@ -340,7 +356,7 @@ def load_library():
         except Exception:  # pragma: no cover  (torch is optional for single-GPU use)
             pass
         lib = ctypes.CDLL(p)
-        for name, res, args in ABI + ABI_TENSOR + ABI_SCORE + ABI_RANK + ABI_OVERLAP + ABI_BATCHSTATS + ABI_COUNTSTATS + ABI_TYPICALITY + ABI_HOLDOUT + ABI_TRACE + ABI_MISSING + ABI_IMPUTE + ABI_CSC + ABI_SAMPLE + ABI_PROJECT:
+        for name, res, args in ABI + ABI_TENSOR + ABI_SCORE + ABI_RANK + ABI_OVERLAP + ABI_BATCHSTATS + ABI_COUNTSTATS + ABI_TYPICALITY + ABI_EXPLAIN + ABI_HOLDOUT + ABI_TRACE + ABI_MISSING + ABI_IMPUTE + ABI_CSC + ABI_SAMPLE + ABI_PROJECT:
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -743,6 +759,37 @@ class Worker:
             torch.cuda.current_stream(next(iter(outs.values())).device).synchronize()
         cnt = np.zeros(2, np.int64)
         self.typicality_points_raw(bool(on_device), skipped=cnt[0:].ctypes.data, incomplete=cnt[1:].ctypes.data, **ptr)
+        return int(cnt[0]), int(cnt[1])
+
+    # ---- per-feature explanations (include/dpmm_hip_explain.h)
+    def explain_points_raw(self, device, top=0, ld=0, labels=0, mahalanobis=0, tail=0, skipped=0, incomplete=0, residual=0, zscore=0, feature_tail=0,
+                           features=0):
+        """dpmm_explain_points[_device] on plain addresses (integers; 0 = not asked for); skipped, incomplete: host addresses."""
+        out = ExplainOut(labels or None, mahalanobis or None, tail or None, skipped or None, incomplete or None, residual or None, zscore or None,
+                         feature_tail or None, features or None, int(top), int(ld))
+        fn = self._lib.dpmm_explain_points_device if device else self._lib.dpmm_explain_points
+        self._chk(fn(self._h, ctypes.byref(out)))
+
+    def explain_points_into(self, outs, top=0):
+        """dpmm_explain_points[_device] into storage the caller made: `outs` maps `labels` / `mahalanobis` / `tail` (n entries each) and
+        `residual` / `zscore` / `feature_tail` / `features` ((n, ld) each, one ld for all, features int32 and only with top > 0) to contiguous
+        numpy arrays (host variant) or torch tensors on this worker's GPU (device variant); returns (skipped, incomplete)."""
+        ptr, on_device, ld = {}, None, 0
+        for name, a in outs.items():
+            dev = hasattr(a, "data_ptr")
+            if on_device is None:
+                on_device = dev
+            assert dev == on_device, "explain_points_into: numpy arrays or tensors, not both"
+            assert a.is_contiguous() if dev else a.flags.c_contiguous, name
+            if name in ("residual", "zscore", "feature_tail", "features"):
+                assert len(a.shape) == 2 and ld in (0, a.shape[1]), name
+                ld = int(a.shape[1])
+            ptr[name] = (a.data_ptr() if a.numel() else 0) if dev else (a.ctypes.data if a.size else 0)
+        if on_device:
+            import torch
+            torch.cuda.current_stream(next(iter(outs.values())).device).synchronize()
+        cnt = np.zeros(2, np.int64)
+        self.explain_points_raw(bool(on_device), top=top, ld=ld, skipped=cnt[0:].ctypes.data, incomplete=cnt[1:].ctypes.data, **ptr)
         return int(cnt[0]), int(cnt[1])
 
     # ---- missing features (include/dpmm_hip_missing.h)

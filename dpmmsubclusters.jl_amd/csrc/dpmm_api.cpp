@@ -14,6 +14,7 @@
 #include "../../include/dpmm_hip_batchstats.h"
 #include "../../include/dpmm_hip_countstats.h"
 #include "../../include/dpmm_hip_typicality.h"
+#include "../../include/dpmm_hip_explain.h"
 #include "../../include/dpmm_hip_holdout.h"
 #include "../../include/dpmm_hip_trace.h"
 #include "../../include/dpmm_hip_missing.h"
@@ -167,6 +168,10 @@ struct dpmm_ctx {
     int bs_use_tail = 0;
     float bs_min_tail = 0.f;
     bool bs_accumulated = false;        // a dpmm_batchstats_accumulate has run since dpmm_batchstats_begin
+    // per-feature explanations (include/dpmm_hip_explain.h): the row-major factors and the diagonals of R'R, allocated by the first explain
+    // call and made from the parameter set exp_gen (0: none)
+    DevBuf<float> d_exp_rr, d_exp_a;
+    unsigned long long exp_gen = 0;
     // held-out points (include/dpmm_hip_holdout.h): ballots, class counts and first slots of the workgroups of one range; the running totals;
     // the caller's destination as dpmm_holdout_begin took it.  With a tail floor the tails of a range go through d_bs_tail, as batchstats' do.
     DevBuf<unsigned long long> d_ho_ballot, d_ho_state;
@@ -3976,6 +3981,102 @@ static int typicality_points(dpmm_ctx *c, const dpmm_typicality_out *o, bool dev
 
 int dpmm_typicality_points(dpmm_ctx *c, const dpmm_typicality_out *out) { return typicality_points(c, out, false, "dpmm_typicality_points"); }
 int dpmm_typicality_points_device(dpmm_ctx *c, const dpmm_typicality_out *out) { return typicality_points(c, out, true, "dpmm_typicality_points_device"); }
+
+// ---- include/dpmm_hip_explain.h: behind the typicality pass of every range, the per-feature residuals, z-scores and tails (explain.hip) ----
+// The device copies explain.hip reads beside miss_params' -- the row-major factors Rr and the diagonals a of R'R -- are those of the
+// predictive set in force afterwards.  Called behind miss_params (typ_begin), which has checked the prior and the parameters.
+static int explain_params(dpmm_ctx *c) {
+    if (c->exp_gen == c->pred_gen) return DPMM_OK;
+    const size_t K = (size_t)c->K, D = (size_t)c->D, Dp = (size_t)miss_pitch(c->D);
+    if (int rc = grow(c, c->d_exp_rr, sizeof(float) * K * D * Dp, "dpmm_explain_points", "row-major factors of the explain pass")) return rc;
+    if (int rc = grow(c, c->d_exp_a, sizeof(float) * K * Dp, "dpmm_explain_points", "diagonals of the explain pass")) return rc;
+    const ParLayout L = par_layout(c, c->miss_slots);
+    const float *Rpk = reinterpret_cast<const float *>(c->d_par + (L.mat - L.cst));      // (as miss_params)
+    HIPCHK(c, launch_explain_params(Rpk, 3 * (int64_t)(D * (D + 1) / 2), c->d_exp_rr, c->d_exp_a, c->K, c->D, c->stream));
+    c->exp_gen = c->pred_gen;
+    return DPMM_OK;
+}
+
+static int explain_points(dpmm_ctx *c, const dpmm_explain_out *o, bool device, const char *fn) {
+    if (!c) return tensor_no_ctx(fn);
+    c->miss_counted = false;      // (as score_points)
+    const std::string who = std::string(fn) + ": ";
+    if (!o) return fail(c, DPMM_EINVAL, who + "out is null");
+    if (c->prior != DPMM_PRIOR_NIW) return fail(c, DPMM_EINVAL, who + "the explanation is that of the NIW prior's Student-t predictive; the Multinomial predictive has no closed-form tail");
+    const int cap = std::min(c->D, DPMM_EXPLAIN_MAX_TOP);
+    if (o->top < 0 || o->top > cap) return fail(c, DPMM_EINVAL, who + "top must be in 0.." + std::to_string(cap));
+    if (o->top == 0 && o->features) return fail(c, DPMM_EINVAL, who + "features given with top = 0");
+    const bool rows = o->residual || o->zscore || o->feature_tail || o->features;
+    if (!o->labels && !o->mahalanobis && !o->tail && !o->skipped && !o->incomplete && !rows) return fail(c, DPMM_EINVAL, who + "every output pointer is null");
+    const int64_t width = o->top ? o->top : c->D;
+    if (rows && o->ld < width) return fail(c, DPMM_EINVAL, who + "ld < " + (o->top ? "top" : "D"));
+    if (rows && (o->ld >> 31)) return fail(c, DPMM_EINVAL, who + "ld out of range (below 2^31)");
+    if (!c->predictive) return fail(c, DPMM_ESTATE, who + "needs dpmm_set_predictive_niw first");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (o->skipped) o->skipped[0] = 0;
+    if (o->incomplete) o->incomplete[0] = 0;
+    if (c->n == 0) return DPMM_OK;
+    if (!c->have_points || !c->have_params || !c->dX) return fail(c, DPMM_ESTATE, who + "needs points and parameters");
+    const uint64_t n = (uint64_t)c->n, ld = rows ? (uint64_t)o->ld : 0;
+    if (ld && n > (UINT64_MAX / sizeof(int64_t)) / ld) return fail(c, DPMM_EINVAL, who + "n_local * ld out of range");      // (the extents below cannot wrap)
+    if (device) {
+        if (o->labels) if (int rc = check_device_extent(c, fn, "labels", o->labels, sizeof(int64_t) * n, sizeof(int64_t))) return rc;
+        if (o->mahalanobis) if (int rc = check_device_extent(c, fn, "mahalanobis", o->mahalanobis, sizeof(float) * n, sizeof(float))) return rc;
+        if (o->tail) if (int rc = check_device_extent(c, fn, "tail", o->tail, sizeof(float) * n, sizeof(float))) return rc;
+        if (o->residual) if (int rc = check_device_extent(c, fn, "residual", o->residual, sizeof(float) * n * ld, sizeof(float))) return rc;
+        if (o->zscore) if (int rc = check_device_extent(c, fn, "zscore", o->zscore, sizeof(float) * n * ld, sizeof(float))) return rc;
+        if (o->feature_tail) if (int rc = check_device_extent(c, fn, "feature_tail", o->feature_tail, sizeof(float) * n * ld, sizeof(float))) return rc;
+        if (o->features) if (int rc = check_device_extent(c, fn, "features", o->features, sizeof(int32_t) * n * ld, sizeof(int32_t))) return rc;
+    }
+    TableWalk w;
+    if (int rc = walk_open(c, fn, WALK_MISS_OPTION, &w)) return rc;
+    if (int rc = typ_begin(c, w.P, fn)) return rc;
+    if (rows) if (int rc = explain_params(c)) return rc;
+    HIPCHK(c, hipMemsetAsync(c->d_typ_cnt, 0, 2 * sizeof(unsigned long long), c->stream));
+    // the rows: in the caller's device memory ld entries apart; staged (host variant) dense, `width` apart, and copied row by row, so that the
+    // words of the caller's rows behind `width` are not touched
+    const uint64_t sld = device ? ld : (uint64_t)width;
+    OutStage<7> out{{{o->labels, sizeof(int64_t)}, {o->mahalanobis, sizeof(float)}, {o->tail, sizeof(float)}, {o->residual, sizeof(float) * sld},
+                     {o->zscore, sizeof(float) * sld}, {o->feature_tail, sizeof(float) * sld}, {o->features, sizeof(int32_t) * sld}}, device};
+    if (!device) {
+        if (int rc = grow(c, c->d_score_out, out.layout((size_t)w.P), "dpmm_score_points", "staging of the outputs")) return rc;
+        out.buf = c->d_score_out;
+    }
+    if (int rc = walk_ranges(c, w, c->n, fn, [&](int64_t p0, int64_t np, int64_t) -> int {
+            if (int rc = typ_range(c, w.P, p0, np, out.at<int64_t>(0, p0), out.at<float>(1, p0), out.at<float>(2, p0), fn)) return rc;
+            if (rows) {
+                ExplainArgs a{};
+                a.n = np; a.K = c->K; a.D = c->D;
+                a.X = c->dX + p0 * c->ldx; a.ldx = c->ldx;
+                const TypicalityArgs t = niw_range_args<TypicalityArgs>(c, w.P, p0, np);      // (the copies and the means the typicality pass has just read)
+                a.Rt = t.Rt; a.mu = t.mu; a.mu_step = t.mu_step; a.cst = t.cst;
+                a.Rr = c->d_exp_rr; a.a = c->d_exp_a; a.cls = c->d_typ_cls;
+                a.residual = out.at<float>(3, p0); a.zscore = out.at<float>(4, p0); a.feature_tail = out.at<float>(5, p0); a.features = out.at<int32_t>(6, p0);
+                a.top = o->top; a.ld = (int64_t)sld;
+                if (int rc = table_result(c, fn, launch_explain_range(a, 32 * c->cus, c->stream))) return rc;
+            }
+            if (device) return DPMM_OK;
+            for (int i = 3; i < 7; ++i) {      // (4-byte entries all; then the three vectors and the wait, by flush)
+                OutCol &q = out.col[i];
+                if (!q.dst) continue;
+                HIPCHK(c, hipMemcpy2DAsync(static_cast<char *>(q.dst) + (size_t)p0 * ld * 4, (size_t)ld * 4, out.buf + q.off, (size_t)width * 4, (size_t)width * 4, (size_t)np,
+                                           hipMemcpyDeviceToHost, c->stream));
+                q.dst = nullptr;
+            }
+            const int rc = table_result(c, fn, out.flush(c, p0, (size_t)np));
+            out.col[3].dst = o->residual; out.col[4].dst = o->zscore; out.col[5].dst = o->feature_tail; out.col[6].dst = o->features;
+            return rc;
+        })) return rc;
+    HIPCHK(c, sync_stream(c, c->stream));
+    unsigned long long h[2] = {0, 0};
+    HIPCHK(c, hipMemcpy(h, c->d_typ_cnt, sizeof(h), hipMemcpyDeviceToHost));
+    if (o->skipped) o->skipped[0] = (int64_t)h[0];
+    if (o->incomplete) o->incomplete[0] = (int64_t)h[1];
+    return DPMM_OK;
+}
+
+int dpmm_explain_points(dpmm_ctx *c, const dpmm_explain_out *out) { return explain_points(c, out, false, "dpmm_explain_points"); }
+int dpmm_explain_points_device(dpmm_ctx *c, const dpmm_explain_out *out) { return explain_points(c, out, true, "dpmm_explain_points_device"); }
 
 static int impute_points(dpmm_ctx *c, float *out, int64_t ld, bool device, const char *fn) {
     if (!c) return tensor_no_ctx(fn);

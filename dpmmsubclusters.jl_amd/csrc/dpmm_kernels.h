@@ -427,6 +427,30 @@ struct TypicalityArgs {
     unsigned long long *cnt;     // [0] skipped, [1] incomplete: added to
 };
 hipError_t launch_typicality_range(const TypicalityArgs &a, int max_grid, hipStream_t s);
+// ---- per-feature explanation of a point (explain.hip; include/dpmm_hip_explain.h): behind launch_typicality_range of the same range, whose
+// class words it reads: for a scored point g = R_k' R_k (x - m_k), the conditional residual, z-score and two-sided tail of every feature
+constexpr int EXPLAIN_MAX_TOP = 16;       // DPMM_EXPLAIN_MAX_TOP
+struct ExplainArgs {
+    int64_t n;
+    int K, D;
+    const float *X;              // [n][ldx], the range's first point
+    int64_t ldx;
+    const float *Rt;             // as MissArgs::Rt
+    const float *Rr;             // [K][D][miss_pitch(D)]: Rr[k][r][d] = R_k[r][d], zero below the diagonal (d < r) and in the pad (d >= D)
+    const float *a;              // [K][miss_pitch(D)]: a[k][d] = sum_{r <= d} R_k[r][d]^2, summed in Float64 and rounded once; zero in the pad
+    const float *mu;             // cluster k's mean: mu + k * mu_step
+    int64_t mu_step;
+    const double *cst;           // as MissArgs::cst: [k * MISS_CST] = df_k
+    const int32_t *cls;          // [n] the class words launch_typicality_range wrote for this range
+    float *residual;             // [n][ld] or null
+    float *zscore;               // [n][ld] or null
+    float *feature_tail;         // [n][ld] or null
+    int32_t *features;           // [n][ld] or null; written only if top > 0
+    int top;                     // 0: all D features in order; else the top features of largest |zscore|, 1 <= top <= min(D, EXPLAIN_MAX_TOP)
+    int64_t ld;                  // >= (top ? top : D)
+};
+hipError_t launch_explain_params(const float *Rpk, int64_t step, float *Rr, float *a, int K, int D, hipStream_t s);      // Rpk: as launch_miss_transpose
+hipError_t launch_explain_range(const ExplainArgs &a, int max_grid, hipStream_t s);
 // draws of the missing features (include/dpmm_hip_impute.h) behind launch_miss_list and launch_miss_patch(a, false, ..) of the same range
 constexpr int64_t MISS_DRAW_MAX = (int64_t)1 << 26;      // draw indices: 64 Philox blocks each in a 32-bit block number
 struct MissDraw {

@@ -36,4 +36,26 @@ __device__ __forceinline__ void miss_rz(const float *Rk, const float (&z)[NT], i
     }
 }
 
+// g = R' y, the sibling of miss_rz for the lower-triangular R': row r of R (one coalesced row of Rk = Rr + k D Dp of the row-major copy
+// ExplainArgs::Rr, zero below the diagonal and in the pad) scaled by y_r, r increasing; y_r goes round with v_readlane; lane l accumulates
+// g[64 t + l] = fma(Rr[r][64 t + l], y_r, g) for the tiles t >= r / 64 (the tiles below hold zeros of the triangle and are skipped).
+// g is overwritten.
+template <int NT>
+__device__ __forceinline__ void miss_rty(const float *Rk, const float (&y)[NT], int D, int lane, float (&g)[NT]) {
+    constexpr int Dp = 64 * NT;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) g[t] = 0.f;
+#pragma unroll
+    for (int tr = 0; tr < NT; ++tr) {
+        const int rn = D - 64 * tr < 64 ? D - 64 * tr : 64;
+#pragma unroll 4
+        for (int rr = 0; rr < rn; ++rr) {
+            const float yr = miss_rl_f(y[tr], rr);
+            const float *c = Rk + (int64_t)(64 * tr + rr) * Dp + lane;
+#pragma unroll
+            for (int t = tr; t < NT; ++t) g[t] = fmaf(c[64 * t], yr, g[t]);
+        }
+    }
+}
+
 }  // namespace dpmm

@@ -53,6 +53,11 @@ Typicality = collections.namedtuple("Typicality", "labels mahalanobis tail skipp
 Typicality.__doc__ = """What `Predictor.typicality` returns: labels (n,) int64 1-based, mahalanobis (n,) float32, tail (n,) float32 -- tensors on
 the data's device for a device tensor, else numpy arrays -- and skipped, incomplete, ints: the points whose mahalanobis and tail are NaN."""
 
+Explanation = collections.namedtuple("Explanation", "labels mahalanobis tail residual zscore feature_tail features skipped incomplete")
+Explanation.__doc__ = """What `Predictor.explain` returns: labels, mahalanobis, tail, skipped, incomplete as `Typicality`; residual, zscore,
+feature_tail float32 -- (D, n) in feature order with features None, or with top=m (n, m) and features (n, m) int32, 0-based, the m features of
+largest |zscore|, largest first -- tensors on the data's device for a device tensor, else numpy arrays."""
+
 HeldOut = collections.namedtuple("HeldOut", "points index total skipped incomplete")
 HeldOut.__doc__ = """What `Predictor.held_out` returns: points (D, stored) float32 -- a view of the (stored, D) buffer the GPU wrote -- and index
 (stored,) int64, 0-based positions in `data`, increasing -- tensors on the data's device for a device tensor, else numpy arrays; total, the
@@ -317,6 +322,60 @@ class Predictor:
             total[1] += inc
         out = self._walk(self._open(data), [("labels", (), "int64"), ("mahalanobis", (), "float32"), ("tail", (), "float32")], evaluate)
         return Typicality(out["labels"], out["mahalanobis"], out["tail"], total[0], total[1])
+
+    # ---- per-feature explanations (include/dpmm_hip_explain.h)
+    def explain(self, data, top=None):
+        """WHICH features make a point atypical of the cluster it is given: an `Explanation` tuple, computed on the GPU.
+
+        `typicality` says that a point is far out; the first question then is which features are off.  A per-feature marginal z-score
+        answers it badly: in a correlated cluster a point can sit twelve conditional standard deviations out while every marginal looks
+        ordinary.  Under the point's own Student-t predictive the law of one feature given ALL the others is again a Student-t in closed
+        form.  With k = labels[i] - 1, z = x_i - m_k, A = R_k' R_k = Sigma_k^-1, g = A z, q = mahalanobis[i], df = df_k:
+
+          labels, mahalanobis, tail, skipped, incomplete    the values and classes of `typicality(data)`, bit for bit;
+          residual      e_d = x_d - E[x_d | the other features, k] = g_d / A_dd, in the units of the data;
+          zscore        t_d = g_d sqrt((df + D - 1) / (A_dd (df + q - g_d^2 / A_dd))): for a point of the cluster a Student-t variable with
+                        df + D - 1 degrees of freedom, whatever its other features are -- comparable across features, clusters and D;
+          feature_tail  P(|T| >= |t_d|) for that Student-t, evaluated in Float64 and rounded once: uniform on (0, 1) for points of the
+                        cluster; zscore == 0 gives exactly 1.  At D = 1 it is `tail`.
+        top=None: residual, zscore, feature_tail are (D, n) float32 in feature order (point-major memory, the `.T` view of an (n, D) array,
+        as `impute` returns) and features is None.
+        top=m, 1 <= m <= min(D, 16): the three arrays are (n, m), the layout of `predict_topk`, and features (n, m) int32 holds the 0-based
+        m features of largest |zscore|, largest first, ties to the lower index, a NaN zscore last; nothing of size D n is formed.
+        Skipped and incomplete points (see `typicality`: gaps are not marginalised here) have NaN in the three arrays and -1 in features.
+        Float32 arithmetic from the Float32 x, m, R the worker holds; include/dpmm_hip_explain.h states the error bounds.  With a
+        projection, D and the feature indices are those of the PROJECTED space (the coordinates `Projection.transform` gives), not the
+        source features.  NIW only.  `data` is what `predict` takes; for a device tensor every array is a tensor on its device, written
+        there by the library.  No result depends on `capacity`, the cut into uploads or the table budget, to the bit."""
+        if self._wk is None:
+            raise RuntimeError("this Predictor is closed")
+        if self.kind != _priors.PRIOR_NIW:
+            raise ValueError("explain is for the NIW prior: the Multinomial predictive has no closed-form tail")
+        m = 0
+        if top is not None:
+            m = int(top)
+            if m != top or not 1 <= m <= min(self.D, binding.EXPLAIN_MAX_TOP):
+                raise ValueError(f"top must be None or an integer in 1..{min(self.D, binding.EXPLAIN_MAX_TOP)}")
+        wk = self._wk
+        if not hasattr(wk, "explain_points_into"):
+            raise RuntimeError("this Predictor's worker cannot explain points (no dpmm_explain_points)")
+        total = [0, 0]
+
+        def evaluate(views, lo, hi):
+            sk, inc = wk.explain_points_into(views, top=m)
+            if hi - lo < self.capacity:
+                # the short slab: the padding is of one class, which its first point shows (as `typicality`)
+                q0 = float(views["mahalanobis"][hi - lo])
+                if q0 != q0:
+                    sk -= self.capacity - (hi - lo)
+            total[0] += sk
+            total[1] += inc
+        width = (m or self.D,)
+        spec = [("labels", (), "int64"), ("mahalanobis", (), "float32"), ("tail", (), "float32"), ("residual", width, "float32"),
+                ("zscore", width, "float32"), ("feature_tail", width, "float32")] + ([("features", width, "int32")] if m else [])
+        out = self._walk(self._open(data), spec, evaluate)
+        rows = [out[name] if m else out[name].T for name in ("residual", "zscore", "feature_tail")]
+        return Explanation(out["labels"], out["mahalanobis"], out["tail"], rows[0], rows[1], rows[2], out["features"] if m else None, total[0], total[1])
 
     # ---- exemplars (include/dpmm_hip_rank.h)
     def exemplars(self, data, m, which="both"):
@@ -875,6 +934,13 @@ def typicality(dp_model, data, **kw):
     kw: capacity, device, worker_factory, missing."""
     with Predictor(dp_model, **kw) as p:
         return p.typicality(data)
+
+
+def explain(dp_model, data, top=None, **kw):
+    """Per-feature conditional residuals, z-scores and tails of every point under its own cluster (opens a Predictor, runs, closes): see
+    `Predictor.explain`; kw: capacity, device, worker_factory, missing."""
+    with Predictor(dp_model, **kw) as p:
+        return p.explain(data, top=top)
 
 
 def held_out(dp_model, data, **kw):
