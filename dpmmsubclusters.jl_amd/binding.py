@@ -241,6 +241,28 @@ ABI_HOLDOUT = [
     ("dpmm_holdout_accumulate", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64]),
     ("dpmm_holdout_read", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(HoldoutOut)]),
 ]
+
+
+class CountHoldoutDst(ctypes.Structure):
+    """dpmm_countholdout_dst (include/dpmm_hip_countholdout.h): device addresses -- points (dense stores) or colptr / rowval / val (sparse
+    store), index -- and the two caps."""
+    _fields_ = [("points", ctypes.c_void_p), ("colptr", ctypes.c_void_p), ("rowval", ctypes.c_void_p), ("val", ctypes.c_void_p), ("index", ctypes.c_void_p),
+                ("cap", ctypes.c_int64), ("entry_cap", ctypes.c_int64)]
+
+
+class CountHoldoutOut(ctypes.Structure):
+    """dpmm_countholdout_out (include/dpmm_hip_countholdout.h): host addresses, 0 / None = not asked for."""
+    _fields_ = [("total", ctypes.c_void_p), ("total_entries", ctypes.c_void_p), ("stored", ctypes.c_void_p), ("stored_entries", ctypes.c_void_p),
+                ("skipped", ctypes.c_void_p), ("incomplete", ctypes.c_void_p), ("scored", ctypes.c_void_p)]
+
+
+# include/dpmm_hip_countholdout.h: the floor per count and the held-out points of a batch of count data, compacted on the GPU (additive; bound next to ABI)
+ABI_COUNTHOLDOUT = [
+    ("dpmm_countstats_set_per_count", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_float]),
+    ("dpmm_countholdout_begin", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_int, ctypes.c_float, ctypes.POINTER(CountHoldoutDst)]),
+    ("dpmm_countholdout_accumulate", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64]),
+    ("dpmm_countholdout_read", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(CountHoldoutOut)]),
+]
 # include/dpmm_hip_trace.h: label samples kept on the GPU, their pairwise contingency tables and the per-point confidence (additive)
 ABI_TRACE = [
     ("dpmm_trace_open", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
@@ -356,7 +378,7 @@ def load_library():
         except Exception:  # pragma: no cover  (torch is optional for single-GPU use)
             pass
         lib = ctypes.CDLL(p)
-        for name, res, args in ABI + ABI_TENSOR + ABI_SCORE + ABI_RANK + ABI_OVERLAP + ABI_BATCHSTATS + ABI_COUNTSTATS + ABI_TYPICALITY + ABI_EXPLAIN + ABI_HOLDOUT + ABI_TRACE + ABI_MISSING + ABI_IMPUTE + ABI_CSC + ABI_SAMPLE + ABI_PROJECT:
+        for name, res, args in ABI + ABI_TENSOR + ABI_SCORE + ABI_RANK + ABI_OVERLAP + ABI_BATCHSTATS + ABI_COUNTSTATS + ABI_TYPICALITY + ABI_EXPLAIN + ABI_HOLDOUT + ABI_COUNTHOLDOUT + ABI_TRACE + ABI_MISSING + ABI_IMPUTE + ABI_CSC + ABI_SAMPLE + ABI_PROJECT:
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -991,6 +1013,45 @@ class Worker:
                    skipped=np.empty(1, np.int64), incomplete=np.empty(1, np.int64), held_out=np.empty(1, np.int64))
         self.countstats_read_raw(**{k: v.ctypes.data for k, v in res.items()})
         return res
+
+    # ---- the floor per count and the held-out points of count data (include/dpmm_hip_countholdout.h)
+    def countstats_set_per_count(self, min_logdens_per_count):
+        """dpmm_countstats_set_per_count: the accumulation just begun also holds out the complete points whose log-density per count lies
+        below `min_logdens_per_count` (None: switched off); between countstats_begin and the first countstats_accumulate."""
+        use = min_logdens_per_count is not None
+        self._chk(self._lib.dpmm_countstats_set_per_count(self._h, int(use), float(min_logdens_per_count) if use else 0.0))
+
+    def countholdout_begin(self, dst, min_logdens=None, min_logdens_per_count=None):
+        """dpmm_countholdout_begin: a new collection of the points below the floor min_logdens and / or the floor per count (None: not in
+        use).  dst: None (count only) or a dict -- `cap`, `index` and either `points` [cap][D] float32 (dense stores) or `colptr` [cap + 1]
+        int64, `rowval` [entry_cap] int32, `val` [entry_cap] float32 and `entry_cap` (sparse store) -- of device addresses (integers) or
+        torch tensors on this worker's GPU, which the caller keeps alive until countholdout_read."""
+        floor, pc = min_logdens is not None, min_logdens_per_count is not None
+        dst = dict(dst or {})
+        for a in dst.values():
+            if hasattr(a, "data_ptr"):
+                import torch
+                torch.cuda.current_stream(a.device).synchronize()      # nothing queued on torch's stream still uses this memory
+                break
+
+        def addr(a):
+            return (a.data_ptr() if a.numel() else 0) if hasattr(a, "data_ptr") else int(a or 0)
+        d = CountHoldoutDst(*[addr(dst.get(k)) or None for k in ("points", "colptr", "rowval", "val", "index")], int(dst.get("cap", 0)), int(dst.get("entry_cap", 0)))
+        self._chk(self._lib.dpmm_countholdout_begin(self._h, int(floor), float(min_logdens) if floor else 0.0, int(pc),
+                                                    float(min_logdens_per_count) if pc else 0.0, ctypes.byref(d)))
+
+    def countholdout_accumulate(self, lo, n_valid):
+        """dpmm_countholdout_accumulate: classifies the points 0..n_valid-1 of the current upload, global indices lo + i, and appends the
+        held-out ones from whichever store is live."""
+        self._chk(self._lib.dpmm_countholdout_accumulate(self._h, int(lo), int(n_valid)))
+
+    def countholdout_read(self):
+        """The counters as they stand, after the stream has been waited for: a dict of ints `total`, `total_entries`, `stored`,
+        `stored_entries`, `skipped`, `incomplete`, `scored`."""
+        cnt = np.zeros(7, np.int64)
+        out = CountHoldoutOut(*[cnt[j:].ctypes.data for j in range(7)])
+        self._chk(self._lib.dpmm_countholdout_read(self._h, ctypes.byref(out)))
+        return dict(zip(("total", "total_entries", "stored", "stored_entries", "skipped", "incomplete", "scored"), (int(v) for v in cnt)))
 
     # ---- label trace (include/dpmm_hip_trace.h)
     def trace_open(self, slots):

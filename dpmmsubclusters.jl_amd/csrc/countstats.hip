@@ -5,10 +5,12 @@
 // probability score.hip writes, formed with the same functions (score_device.h) and widened to Float64; w x is formed in Float64.
 //
 // Launches per range, nothing in them waits for another workgroup:
-//   prep      batchstats_prep_kernel's classification (batchstats_device.h), a workgroup per 256 points, one float2 per point: (M, S) in SOFT
-//             mode, (label, 1) in HARD mode, (0, 0) for a point that takes no part.  The scan for a value that is not finite goes over the
-//             live store: the workgroup's rows of X read flat; nothing for bytes; for sparse points the workgroup's entries
-//             cp[base] .. cp[base + rows] read flat, and the (rare) offender's column found by bisection in cp.
+//   totals    only with the floor per count (dpmm_countstats_set_per_count), in front of prep by the caller: t_i, the Float64 total of every
+//             point's values, one wave per point, lanes strided over the entries and a fixed butterfly -- a function of the point alone.
+//   prep      the classification of countstats_device.h (cs_mark_gaps, cs_class -- shared with countholdout.hip), a workgroup per 256 points,
+//             one float2 per point: (M, S) in SOFT mode, (label, 1) in HARD mode, (0, 0) for a point that takes no part.  The scan for a
+//             value that is not finite goes over the live store: the workgroup's rows of X read flat; nothing for bytes; for sparse points
+//             the workgroup's entries cp[base] .. cp[base + rows] read flat, and the (rare) offender's column found by bisection in cp.
 //   contract, dense and byte stores: W' X on the Float64 matrix pipe (v_mfma_f64_16x16x4_f64, operands as in overlap.hip / batchstats.hip).
 //             The range is cut into nchunk chunks, the clusters into groups of 16, the features into blocks of 256; a workgroup of four
 //             waves owns (chunk, group, block) and writes its 16 x 256 partial sums -- one writer, no atomics.  It walks its chunk 256
@@ -37,6 +39,7 @@
 #include "dpmm_kernels.h"
 #include "score_device.h"
 #include "batchstats_device.h"
+#include "countstats_device.h"
 
 namespace dpmm {
 
@@ -52,6 +55,42 @@ constexpr int CS_SP_WAVE = 1792;         // features (doubles of LDS) of a wave 
 constexpr int CS_SP_WG = 4 * CS_SP_WAVE; // ... of its workgroup: 56 KB
 constexpr int CS_SP_SCAN = 128;          // columns up to this length are scanned from their start, longer ones bisected
 
+// t_i, the Float64 total of a point's values, for the floor per count: one wave per point.  Lane l adds entries l, l + 64, .. in order, then
+// a fixed butterfly combines the lanes (every lane ends with the same sum): a function of the point alone, exact for integer data.
+template <typename T>
+__device__ __forceinline__ double cs_wave_total(const T *v, int64_t len, int lane) {
+    double t = 0.;
+    for (int64_t e = lane; e < len; e += 64) t += (double)v[e];
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) t += __shfl_xor(t, o);
+    return t;
+}
+
+__global__ __launch_bounds__(CS_THREADS) void countstats_totals_kernel(CountTotalsArgs A) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    constexpr int WAVES = CS_THREADS / 64;
+    // (the trip count is the same for every lane of a wave: the shuffles see whole waves)
+    for (int64_t i = (int64_t)blockIdx.x * WAVES + w; i < A.n; i += (int64_t)gridDim.x * WAVES) {
+        double t;
+        if (A.store == COUNTSTATS_F32) t = cs_wave_total(A.X + i * A.ldx, A.D, lane);
+        else if (A.store == COUNTSTATS_U8) t = cs_wave_total(A.X8 + i * A.ld8, A.D, lane);
+        else { const int64_t lo = A.cp[i]; t = cs_wave_total(A.val + lo, A.cp[i + 1] - lo, lane); }
+        if (lane == 0) A.tot[i] = t;
+    }
+}
+
+hipError_t launch_countstats_totals(const CountTotalsArgs &a, hipStream_t s) {
+    if (a.n <= 0) return hipSuccess;
+    if (a.n >> 31 || a.D < 1 || !a.tot) return hipErrorInvalidValue;
+    if (a.store == COUNTSTATS_F32) { if (!a.X || a.ldx < a.D) return hipErrorInvalidValue; }
+    else if (a.store == COUNTSTATS_U8) { if (!a.X8 || a.ld8 < a.D) return hipErrorInvalidValue; }
+    else if (a.store == COUNTSTATS_SPARSE) { if (!a.cp) return hipErrorInvalidValue; }      // (val is read only where a column has entries)
+    else return hipErrorInvalidValue;
+    const int64_t g = std::min<int64_t>((a.n + CS_THREADS / 64 - 1) / (CS_THREADS / 64), (int64_t)1 << 20);
+    DPMM_LAUNCH(countstats_totals_kernel, dim3((unsigned)g), dim3(CS_THREADS), 0, s, a);
+    return hipGetLastError();
+}
+
 __global__ __launch_bounds__(CS_THREADS) void countstats_prep_kernel(CountStatsArgs A) {
     __shared__ unsigned cnt[DPMM_MAX_CLUSTERS_K + BATCHSTATS_COUNTERS];
     __shared__ unsigned gap[CS_THREADS];
@@ -64,26 +103,9 @@ __global__ __launch_bounds__(CS_THREADS) void countstats_prep_kernel(CountStatsA
         gap[tid] = 0;
         __syncthreads();
         const int rows = (int)(A.n - base < CS_THREADS ? A.n - base : CS_THREADS);
-        if (A.store == COUNTSTATS_F32) {                       // rows base .. base + 255 of X, flat: word f is feature f % ldx of row f / ldx
-            const int ldx = (int)A.ldx;
-            const float *xr = A.X + base * A.ldx;
-            for (int f = tid; f < rows * ldx; f += CS_THREADS) {
-                const int r = f / ldx;
-                if (f - r * ldx < D && !bs_finite(xr[f])) gap[r] = 1;      // (every writer writes 1)
-            }
-        } else if (A.store == COUNTSTATS_SPARSE) {             // the entries of columns base .. base + rows - 1, flat
-            const int64_t *cpb = A.cp + base;
-            const int64_t e1 = cpb[rows];
-            for (int64_t e = cpb[0] + tid; e < e1; e += CS_THREADS)
-                if (!bs_finite(A.val[e])) {
-                    int lo = 0, hi = rows - 1;                 // the last column that starts at or before e
-                    while (lo < hi) {
-                        const int mid = (lo + hi + 1) >> 1;
-                        if (cpb[mid] <= e) lo = mid; else hi = mid - 1;
-                    }
-                    gap[lo] = 1;
-                }
-        }                                                      // (a byte is finite)
+        // a value that is not finite, over the live store (countstats_device.h): the rows of X flat; the entries of the columns flat; a byte is finite
+        cs_mark_gaps(gap, A.store, A.store == COUNTSTATS_F32 ? A.X + base * A.ldx : nullptr, (int)A.ldx, A.store == COUNTSTATS_SPARSE ? A.cp + base : nullptr, A.val, rows, D,
+                     tid, CS_THREADS);
         const int64_t i = base + tid;
         const bool valid = i < A.n;
         const float *col = A.table + (valid ? i : 0);      // (lanes past the end read point 0 and contribute nothing)
@@ -93,10 +115,8 @@ __global__ __launch_bounds__(CS_THREADS) void countstats_prep_kernel(CountStatsA
         bs_table_passes(col, rs, K, m, best, nan_seen, s);
         __syncthreads();
         // ---- the class: skipped, else held out, else incomplete, else it takes part
-        const bool scored = valid && !nan_seen && m > -INFINITY && m < INFINITY;
-        const bool held = scored && A.use_floor && score_logdens(m, s) < A.min_logdens;
-        const bool incomplete = scored && !held && gap[tid] != 0;
-        const bool part = scored && !held && !incomplete;
+        bool scored, held, incomplete, part;
+        cs_class(valid, nan_seen, m, s, gap[tid], A.use_floor, A.min_logdens, A.use_pc, A.min_pc, A.tot, i, scored, held, incomplete, part);
         if (valid) A.ms[i] = !part ? make_float2(0.f, 0.f) : A.soft ? make_float2(m, s) : make_float2((float)best, 1.f);
         bs_count(cnt, K, lane, valid, scored, held, incomplete, part, best);
     }
@@ -364,7 +384,8 @@ hipError_t launch_countstats_range(const CountStatsArgs &a0, hipStream_t s) {
     if (a.n <= 0) return hipSuccess;
     const bool sparse = a.store == COUNTSTATS_SPARSE;
     if (a.K < 1 || a.K > DPMM_MAX_CLUSTERS_K || a.D < 1 || a.D > (1 << 20) || a.n >> 31 || a.kgroup < 1 || a.nchunk < 1 || a.chunk < 64 || (a.chunk & 63) ||
-        (int64_t)a.nchunk * a.chunk < a.n || a.nchunk > 65535 || a.dp < a.D || !a.table || !a.ms || !a.count || !a.part || !a.npart || !a.acc)
+        (int64_t)a.nchunk * a.chunk < a.n || a.nchunk > 65535 || a.dp < a.D || !a.table || !a.ms || !a.count || !a.part || !a.npart || !a.acc ||
+        (a.use_pc && !a.tot))
         return hipErrorInvalidValue;
     if (a.store == COUNTSTATS_F32) { if (!a.X || a.ldx < a.D || a.ldx > (1 << 22)) return hipErrorInvalidValue; }
     else if (a.store == COUNTSTATS_U8) { if (!a.X8 || a.ld8 < a.D) return hipErrorInvalidValue; }

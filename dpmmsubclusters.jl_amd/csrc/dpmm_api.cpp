@@ -16,6 +16,7 @@
 #include "../../include/dpmm_hip_typicality.h"
 #include "../../include/dpmm_hip_explain.h"
 #include "../../include/dpmm_hip_holdout.h"
+#include "../../include/dpmm_hip_countholdout.h"
 #include "../../include/dpmm_hip_trace.h"
 #include "../../include/dpmm_hip_missing.h"
 #include "../../include/dpmm_hip_impute.h"
@@ -188,6 +189,20 @@ struct dpmm_ctx {
     DevBuf<float2> d_cs_ms;
     DevBuf<double> d_cs_part;
     AccSession cs;
+    // the floor per count (dpmm_countstats_set_per_count): the Float64 totals of the points of one range, allocated only when a floor per
+    // count is in use and shared with the collection below
+    DevBuf<double> d_cs_tot;
+    int cs_use_pc = 0;
+    float cs_min_pc = 0.f;
+    bool cs_accumulated = false;        // a dpmm_countstats_accumulate has run since dpmm_countstats_begin
+    // held-out count points (include/dpmm_hip_countholdout.h): ballots, class counts and first slots go through d_ho_ballot / d_ho_count /
+    // d_ho_off (a ctx has one prior); the workgroups' entry counts and first entry offsets; the running totals; the caller's destination
+    DevBuf<unsigned long long> d_ch_ent, d_ch_state;
+    DevBuf<int64_t> d_ch_eoff;
+    AccSession ch;
+    int ch_use_pc = 0;
+    float ch_min_pc = 0.f;
+    dpmm_countholdout_dst ch_dst = {nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0};
     // label trace (include/dpmm_hip_trace.h): slots rows of trace_nvec 16-byte vectors of ids; K per slot (0: never recorded); the device
     // images of a call's tables, descriptors, ratio tables and confidence
     DevBuf<uint16_t> d_trace;
@@ -4624,6 +4639,36 @@ int dpmm_countstats_begin(dpmm_ctx *c, int mode, int use_floor, float min_logden
     }
     HIPCHK(c, hipMemsetAsync(c->d_cs_acc, 0, state, c->stream));
     c->cs = AccSession{true, K, mode, use_floor ? 1 : 0, min_logdens, c->pred_gen};
+    c->cs_use_pc = 0; c->cs_min_pc = 0.f; c->cs_accumulated = false;
+    return DPMM_OK;
+}
+
+// The live point store as the count kernels name it, and whether its buffers are there
+static int count_store(const dpmm_ctx *c) { return c->x_sparse ? COUNTSTATS_SPARSE : c->x_u8 ? COUNTSTATS_U8 : COUNTSTATS_F32; }
+static bool count_store_ready(const dpmm_ctx *c, int store) {
+    const bool have = store == COUNTSTATS_SPARSE ? (bool)c->d_cp : store == COUNTSTATS_U8 ? (bool)c->dX8 : (bool)c->dX;
+    return c->have_points && c->have_params && have && !(store == COUNTSTATS_SPARSE && c->nnz > 0 && (!c->d_ri || !c->d_val));
+}
+// t_i of the points p0 .. p0 + nv - 1 into d_cs_tot (one range), for the floor per count
+static hipError_t count_totals_range(dpmm_ctx *c, int store, int64_t p0, int64_t nv) {
+    CountTotalsArgs t{};
+    t.n = nv; t.D = c->D; t.store = store; t.tot = c->d_cs_tot;
+    if (store == COUNTSTATS_SPARSE) { t.cp = c->d_cp + p0; t.val = c->d_val; }
+    else if (store == COUNTSTATS_U8) { t.X8 = c->dX8 + p0 * c->ld8; t.ld8 = c->ld8; }
+    else { t.X = c->dX + p0 * c->ldx; t.ldx = c->ldx; }
+    return launch_countstats_totals(t, c->stream);
+}
+
+// include/dpmm_hip_countholdout.h: the floor per count of the accumulation just begun
+int dpmm_countstats_set_per_count(dpmm_ctx *c, int use, float min_logdens_per_count) {
+    static const char *fn = "dpmm_countstats_set_per_count";
+    if (!c) return tensor_no_ctx(fn);
+    const std::string who = std::string(fn) + ": ";
+    if (!c->cs.active) return fail(c, DPMM_ESTATE, who + "needs dpmm_countstats_begin first");
+    if (c->cs_accumulated) return fail(c, DPMM_ESTATE, who + "belongs between dpmm_countstats_begin and the first dpmm_countstats_accumulate");
+    if (use && min_logdens_per_count != min_logdens_per_count) return fail(c, DPMM_EINVAL, who + "min_logdens_per_count must not be NaN");
+    c->cs_use_pc = use ? 1 : 0;
+    c->cs_min_pc = use ? min_logdens_per_count : 0.f;
     return DPMM_OK;
 }
 
@@ -4636,10 +4681,8 @@ int dpmm_countstats_accumulate(dpmm_ctx *c, int64_t n_valid) {
     if (n_valid < 0 || n_valid > c->n) return fail(c, DPMM_EINVAL, who + "n_valid must be in 0..n_local");
     HIPCHK(c, hipSetDevice(c->device));
     if (n_valid == 0) return DPMM_OK;
-    const int store = c->x_sparse ? COUNTSTATS_SPARSE : c->x_u8 ? COUNTSTATS_U8 : COUNTSTATS_F32;
-    const bool have = store == COUNTSTATS_SPARSE ? (bool)c->d_cp : store == COUNTSTATS_U8 ? (bool)c->dX8 : (bool)c->dX;
-    if (!c->have_points || !c->have_params || !have) return fail(c, DPMM_ESTATE, who + "needs points and parameters");
-    if (store == COUNTSTATS_SPARSE && c->nnz > 0 && (!c->d_ri || !c->d_val)) return fail(c, DPMM_ESTATE, who + "needs points and parameters");
+    const int store = count_store(c);
+    if (!count_store_ready(c, store)) return fail(c, DPMM_ESTATE, who + "needs points and parameters");
     const int K = c->K, D = c->D;
     size_t part = 0;
     TableWalk w;
@@ -4649,7 +4692,10 @@ int dpmm_countstats_accumulate(dpmm_ctx *c, int64_t n_valid) {
             if (int rc = grow(c, c->d_cs_ms, sizeof(float2) * (size_t)P, "dpmm_score_points", "maxima and sums of dpmm_countstats_accumulate")) return rc;
             return grow(c, c->d_cs_part, part, "dpmm_score_points", "chunk partials of dpmm_countstats_accumulate");
         })) return rc;
+    if (c->cs_use_pc) if (int rc = grow(c, c->d_cs_tot, sizeof(double) * (size_t)w.P, "dpmm_score_points", "totals of dpmm_countstats_accumulate")) return rc;
+    c->cs_accumulated = true;
     return walk_ranges(c, w, n_valid, fn, [&](int64_t p0, int64_t, int64_t nv) -> int {
+        if (c->cs_use_pc) if (int rc = table_result(c, fn, count_totals_range(c, store, p0, nv))) return rc;
         CountStatsArgs a{};
         a.table = c->d_score_table; a.stride = w.P; a.rstep = w.rstep; a.n = nv; a.K = K; a.D = D;
         a.store = store;
@@ -4657,6 +4703,7 @@ int dpmm_countstats_accumulate(dpmm_ctx *c, int64_t n_valid) {
         else if (store == COUNTSTATS_U8) { a.X8 = c->dX8 + p0 * c->ld8; a.ld8 = c->ld8; }
         else { a.X = c->dX + p0 * c->ldx; a.ldx = c->ldx; }
         a.soft = c->cs.mode == DPMM_BATCHSTATS_SOFT; a.use_floor = c->cs.floor; a.min_logdens = c->cs.min_logdens;
+        a.use_pc = c->cs_use_pc; a.min_pc = c->cs_min_pc; a.tot = c->cs_use_pc ? c->d_cs_tot.get() : nullptr;
         countstats_chunks(a.n, K, D, store == COUNTSTATS_SPARSE, &a.kgroup, &a.nchunk, &a.chunk, &a.dp);
         if (sizeof(double) * (size_t)a.nchunk * (size_t)a.kgroup * ((size_t)a.dp + 1) > part)
             return fail(c, DPMM_EHIP, who + "internal: more chunks than the partial buffer holds");
@@ -4682,6 +4729,117 @@ int dpmm_countstats_read(dpmm_ctx *c, const dpmm_countstats_out *o) {
     if (e == hipSuccess && o->N) e = hipMemcpy(o->N, c->d_cs_acc, sizeof(double) * Kz, hipMemcpyDeviceToHost);
     if (e == hipSuccess && o->sums) e = hipMemcpy(o->sums, c->d_cs_acc + Kz, sizeof(double) * Kz * D, hipMemcpyDeviceToHost);
     return stats_counters_read(c, fn, e, c->d_cs_acc + countstats_acc_doubles(K, (int)D), K, o->count, o->skipped, o->held_out, o->incomplete);
+}
+
+// ---- include/dpmm_hip_countholdout.h: the held-out points of a batch of count data, compacted into the caller's device memory (countholdout.hip)
+// kind of a destination: 0 count only, 1 rows of Float32 (dense stores), 2 compressed sparse columns
+static int countholdout_kind(const dpmm_countholdout_dst &d) { return d.cap <= 0 ? 0 : d.colptr ? 2 : 1; }
+static int countholdout_check_dst(dpmm_ctx *c, const char *fn, const dpmm_countholdout_dst &d) {
+    if (d.cap <= 0) return DPMM_OK;
+    if (int rc = check_device_extent(c, fn, "dst_index", d.index, (uint64_t)d.cap * sizeof(int64_t), sizeof(int64_t))) return rc;
+    if (countholdout_kind(d) == 1) return check_device_extent(c, fn, "dst_points", d.points, (uint64_t)d.cap * (uint64_t)c->D * sizeof(float), sizeof(float));
+    if (int rc = check_device_extent(c, fn, "dst_colptr", d.colptr, ((uint64_t)d.cap + 1) * sizeof(int64_t), sizeof(int64_t))) return rc;
+    if (int rc = check_device_extent(c, fn, "dst_rowval", d.rowval, (uint64_t)d.entry_cap * sizeof(int32_t), sizeof(int32_t))) return rc;
+    return check_device_extent(c, fn, "dst_val", d.val, (uint64_t)d.entry_cap * sizeof(float), sizeof(float));
+}
+
+int dpmm_countholdout_begin(dpmm_ctx *c, int use_floor, float min_logdens, int use_per_count, float min_logdens_per_count, const dpmm_countholdout_dst *dst) {
+    static const char *fn = "dpmm_countholdout_begin";
+    if (!c) return tensor_no_ctx(fn);
+    const std::string who = std::string(fn) + ": ";
+    if (c->prior != DPMM_PRIOR_MULT) return fail(c, DPMM_EINVAL, who + "held-out count points are collected under the Multinomial prior; an NIW ctx has dpmm_holdout_begin (include/dpmm_hip_holdout.h)");
+    if (!use_floor && !use_per_count) return fail(c, DPMM_EINVAL, who + "needs a floor: use_floor or use_per_count");
+    if (use_per_count && min_logdens_per_count != min_logdens_per_count) return fail(c, DPMM_EINVAL, who + "min_logdens_per_count must not be NaN");
+    dpmm_countholdout_dst d = {nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0};
+    if (dst) d = *dst;
+    if (d.cap < 0 || (d.cap >> 40) || d.entry_cap < 0 || (d.entry_cap >> 48)) return fail(c, DPMM_EINVAL, who + "cap must be in 0..2^40 - 1 and entry_cap in 0..2^48 - 1");
+    if (d.cap > 0 && d.points && d.colptr) return fail(c, DPMM_EINVAL, who + "the destination is either dst_points (dense stores) or dst_colptr / dst_rowval / dst_val (sparse store), not both");
+    if (d.cap > 0 && !d.points && !d.colptr) return fail(c, DPMM_EINVAL, who + "cap > 0 needs a destination: dst_points or dst_colptr");
+    if (!c->predictive) return fail(c, DPMM_ESTATE, who + "needs dpmm_set_predictive_mult first");
+    HIPCHK(c, hipSetDevice(c->device));
+    c->ch.active = false;
+    if (int rc = countholdout_check_dst(c, fn, d)) return rc;
+    if (int rc = grow(c, c->d_ch_state, sizeof(unsigned long long) * COUNTHOLDOUT_STATE, "dpmm_score_points", "counters of dpmm_countholdout_begin")) return rc;
+    HIPCHK(c, hipMemsetAsync(c->d_ch_state, 0, sizeof(unsigned long long) * COUNTHOLDOUT_STATE, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->d_ch_state + 5, 0xFF, sizeof(unsigned long long) * 2, c->stream));      // stored, stored entries: COUNTHOLDOUT_UNSET
+    if (countholdout_kind(d) == 2) HIPCHK(c, hipMemsetAsync(d.colptr, 0, sizeof(int64_t), c->stream));    // slot 0
+    c->ch = AccSession{true, c->K, 0, use_floor ? 1 : 0, min_logdens, c->pred_gen};
+    c->ch_use_pc = use_per_count ? 1 : 0; c->ch_min_pc = use_per_count ? min_logdens_per_count : 0.f;
+    c->ch_dst = d;
+    return DPMM_OK;
+}
+
+int dpmm_countholdout_accumulate(dpmm_ctx *c, int64_t lo, int64_t n_valid) {
+    static const char *fn = "dpmm_countholdout_accumulate";
+    if (!c) return tensor_no_ctx(fn);
+    c->miss_counted = false;      // (as score_points)
+    const std::string who = std::string(fn) + ": ";
+    if (int rc = session_check(c, c->ch, "dpmm_countholdout_begin", fn)) return rc;
+    if (n_valid < 0 || n_valid > c->n) return fail(c, DPMM_EINVAL, who + "n_valid must be in 0..n_local");
+    if (lo < 0 || lo > ((int64_t)1 << 62) - n_valid) return fail(c, DPMM_EINVAL, who + "global indices must lie in 0..2^62");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (n_valid == 0) return DPMM_OK;
+    const int store = count_store(c);
+    if (!count_store_ready(c, store)) return fail(c, DPMM_ESTATE, who + "needs points and parameters");
+    const int kind = countholdout_kind(c->ch_dst);
+    if (kind != 0 && (kind == 2) != (store == COUNTSTATS_SPARSE))
+        return fail(c, DPMM_ESTATE, who + (store == COUNTSTATS_SPARSE ? "the sparse store is live and dpmm_countholdout_begin was given the dense destination dst_points"
+                                                                      : "a dense store is live and dpmm_countholdout_begin was given the sparse destination dst_colptr"));
+    if (int rc = countholdout_check_dst(c, fn, c->ch_dst)) return rc;      // (the caller may have freed it since the begin)
+    TableWalk w;
+    if (int rc = walk_open(c, fn, WALK_MISS_NEVER, &w, [&](int64_t P) -> int {
+            if (P >> 31) return fail(c, DPMM_EINVAL, who + "a range of the table must hold fewer than 2^31 points: lower DPMM_OPT_SCORE_TABLE_MB");
+            const size_t groups = (size_t)holdout_groups(std::min<int64_t>(P, c->n));
+            if (int rc = grow(c, c->d_ho_ballot, sizeof(unsigned long long) * groups * (HOLDOUT_THREADS / 64), "dpmm_score_points", "ballots of dpmm_countholdout_accumulate")) return rc;
+            if (int rc = grow(c, c->d_ho_count, sizeof(unsigned) * groups * HOLDOUT_STATE, "dpmm_score_points", "workgroup counts of dpmm_countholdout_accumulate")) return rc;
+            if (int rc = grow(c, c->d_ch_ent, sizeof(unsigned long long) * groups, "dpmm_score_points", "workgroup entry counts of dpmm_countholdout_accumulate")) return rc;
+            if (int rc = grow(c, c->d_ch_eoff, sizeof(int64_t) * groups, "dpmm_score_points", "workgroup entry offsets of dpmm_countholdout_accumulate")) return rc;
+            return grow(c, c->d_ho_off, sizeof(int64_t) * groups, "dpmm_score_points", "workgroup slots of dpmm_countholdout_accumulate");
+        })) return rc;
+    if (c->ch_use_pc) if (int rc = grow(c, c->d_cs_tot, sizeof(double) * (size_t)w.P, "dpmm_score_points", "totals of dpmm_countholdout_accumulate")) return rc;
+    return walk_ranges(c, w, n_valid, fn, [&](int64_t p0, int64_t, int64_t nv) -> int {
+        if (c->ch_use_pc) if (int rc = table_result(c, fn, count_totals_range(c, store, p0, nv))) return rc;
+        CountHoldoutArgs a{};
+        a.table = c->d_score_table; a.stride = w.P; a.rstep = w.rstep; a.n = nv; a.K = c->K; a.D = c->D;
+        a.store = store;
+        if (store == COUNTSTATS_SPARSE) { a.cp = c->d_cp + p0; a.ri = c->d_ri; a.val = c->d_val; }
+        else if (store == COUNTSTATS_U8) { a.X8 = c->dX8 + p0 * c->ld8; a.ld8 = c->ld8; }
+        else { a.X = c->dX + p0 * c->ldx; a.ldx = c->ldx; }
+        a.use_floor = c->ch.floor; a.min_logdens = c->ch.min_logdens;
+        a.use_pc = c->ch_use_pc; a.min_pc = c->ch_min_pc; a.tot = c->ch_use_pc ? c->d_cs_tot.get() : nullptr;
+        a.index0 = lo + p0;
+        a.ballot = c->d_ho_ballot; a.wgcount = c->d_ho_count; a.wgent = c->d_ch_ent; a.wgoff = c->d_ho_off; a.wgeoff = c->d_ch_eoff; a.state = c->d_ch_state;
+        a.dst_points = c->ch_dst.points; a.dst_colptr = c->ch_dst.colptr; a.dst_rowval = c->ch_dst.rowval; a.dst_val = c->ch_dst.val; a.dst_index = c->ch_dst.index;
+        a.cap = c->ch_dst.cap; a.entry_cap = kind == 2 ? c->ch_dst.entry_cap : 0;
+        return table_result(c, fn, launch_countholdout_range(a, c->stream));
+    });
+}
+
+int dpmm_countholdout_read(dpmm_ctx *c, const dpmm_countholdout_out *o) {
+    static const char *fn = "dpmm_countholdout_read";
+    if (!c) return tensor_no_ctx(fn);
+    const std::string who = std::string(fn) + ": ";
+    if (!o) return fail(c, DPMM_EINVAL, who + "out is null");
+    if (!c->ch.active) return fail(c, DPMM_ESTATE, who + "needs dpmm_countholdout_begin first");
+    HIPCHK(c, hipSetDevice(c->device));
+    unsigned long long h[COUNTHOLDOUT_STATE] = {0, 0, 0, 0, 0, 0, 0, 0};
+    hipError_t e = sync_stream(c, c->stream);
+    if (e == hipSuccess) e = hipMemcpy(h, c->d_ch_state, sizeof(h), hipMemcpyDeviceToHost);
+    if (int rc = table_result(c, fn, e)) return rc;
+    const int kind = countholdout_kind(c->ch_dst);
+    // dense stores: an entry is a feature; sparse store: the one workgroup that met a cap wrote [5] and [6], else everything fitted
+    const int64_t total = (int64_t)h[0], entries = c->x_sparse ? (int64_t)h[4] : total * c->D;
+    int64_t stored = 0, stored_entries = 0;
+    if (kind == 1) { stored = std::min<int64_t>(total, c->ch_dst.cap); stored_entries = stored * c->D; }
+    else if (kind == 2) { stored = h[5] == COUNTHOLDOUT_UNSET ? total : (int64_t)h[5]; stored_entries = h[5] == COUNTHOLDOUT_UNSET ? (int64_t)h[4] : (int64_t)h[6]; }
+    if (o->total) o->total[0] = total;
+    if (o->total_entries) o->total_entries[0] = entries;
+    if (o->stored) o->stored[0] = stored;
+    if (o->stored_entries) o->stored_entries[0] = stored_entries;
+    if (o->skipped) o->skipped[0] = (int64_t)h[1];
+    if (o->incomplete) o->incomplete[0] = (int64_t)h[2];
+    if (o->scored) o->scored[0] = (int64_t)h[3];
+    return DPMM_OK;
 }
 
 // ---- include/dpmm_hip_trace.h: label samples kept on the device, their contingency tables and the per-point confidence (trace.hip) ----------

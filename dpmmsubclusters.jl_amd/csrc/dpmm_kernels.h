@@ -371,6 +371,9 @@ struct CountStatsArgs {
     int soft;            // 0: w_ik = [label_i == k + 1], 1: w_ik = p_ik
     int use_floor;       // points with logdens < min_logdens are held out
     float min_logdens;
+    int use_pc;          // complete points with t_i > 0 and (double)logdens < (double)min_pc * t_i are held out too
+    float min_pc;
+    const double *tot;   // [n] t_i as launch_countstats_totals wrote them, read only if use_pc
     int kgroup;          // clusters per contraction launch (countstats_chunks): a multiple of 16 for the dense stores
     int nchunk;          // chunks of the range (countstats_chunks)
     int64_t chunk;       // points per chunk, a multiple of 64
@@ -384,6 +387,59 @@ struct CountStatsArgs {
 };
 void countstats_chunks(int64_t n, int K, int D, int sparse, int *kgroup, int *nchunk, int64_t *chunk, int64_t *dp);
 hipError_t launch_countstats_range(const CountStatsArgs &a, hipStream_t s);
+// t_i, the Float64 total of the values of every point of a range, for the floor per count (countstats.hip): one wave per point
+struct CountTotalsArgs {
+    int64_t n;           // points of the range, below 2^31
+    int D;
+    int store;           // as CountStatsArgs, the pointers at the range's first point (cp) / the whole entry arrays (val)
+    const float *X;
+    int64_t ldx;
+    const uint8_t *X8;
+    int64_t ld8;
+    const int64_t *cp;
+    const float *val;
+    double *tot;         // [n]
+};
+hipError_t launch_countstats_totals(const CountTotalsArgs &a, hipStream_t s);
+// ---- held-out points of count data (countholdout.hip; include/dpmm_hip_countholdout.h): one range of the score table, n points from table
+// column 0 and from whichever point store is live; the points the rule of countstats_device.h holds out are appended to the caller's buffers
+// in increasing index -- rows of Float32 for the dense stores, compressed sparse columns for the sparse one
+constexpr int COUNTHOLDOUT_STATE = 8;            // running totals: held out | skipped | incomplete | taking part | held-out entries | stored | stored entries | unused
+constexpr unsigned long long COUNTHOLDOUT_UNSET = ~0ull;      // stored / stored entries while every held-out point so far has fitted
+struct CountHoldoutArgs {
+    const float *table;
+    int64_t stride;      // floats between two rows of the table
+    int rstep;           // cluster k is row k * rstep
+    int64_t n;           // points of the range that are classified, below 2^31
+    int K, D;
+    int store;           // as CountStatsArgs
+    const float *X;
+    int64_t ldx;
+    const uint8_t *X8;
+    int64_t ld8;
+    const int64_t *cp;
+    const uint16_t *ri;
+    const float *val;
+    int use_floor;       // as CountStatsArgs
+    float min_logdens;
+    int use_pc;
+    float min_pc;
+    const double *tot;
+    int64_t index0;      // global index of the range's first point
+    unsigned long long *ballot;     // [4 * holdout_groups(n)] bit l of word j: point 64 j + l is held out
+    unsigned *wgcount;              // [holdout_groups(n)][HOLDOUT_STATE] the classes of the workgroup's points, counted
+    unsigned long long *wgent;      // [holdout_groups(n)] stored entries of the workgroup's held-out points (sparse store; else 0)
+    int64_t *wgoff;                 // [holdout_groups(n)] slot of the workgroup's first held-out point
+    int64_t *wgeoff;                // [holdout_groups(n)] entry offset of the workgroup's first held-out point
+    unsigned long long *state;      // [COUNTHOLDOUT_STATE] running totals: read, then advanced, by the scan; [5], [6] by the one boundary workgroup
+    float *dst_points;              // dense stores: [cap][D]
+    int64_t *dst_colptr;            // sparse store: [cap + 1]
+    int32_t *dst_rowval;            // [entry_cap]
+    float *dst_val;                 // [entry_cap]
+    int64_t *dst_index;             // [cap]
+    int64_t cap, entry_cap;
+};
+hipError_t launch_countholdout_range(const CountHoldoutArgs &a, hipStream_t s);
 // ---- missing features (missing.hip; include/dpmm_hip_missing.h): one range of the score table, n points from table column 0 and from X
 constexpr int MISS_MAX = 16;              // DPMM_SCORE_MAX_MISSING
 constexpr int MISS_CST = MISS_MAX + 2;    // doubles per cluster in MissArgs::cst

@@ -20,7 +20,8 @@ one fit; a served cluster whose alpha has grown to 1e6 would lose a soft weight 
 the type the array has.
 
 `niw_graft` appends clusters: the posteriors `Predictor.grow` found for the points no cluster explains go behind the ones the model has,
-which keep their numbers and their bits.
+which keep their numbers and their bits.  `dirichlet_graft` does the same for the alpha rows of a Multinomial model
+(`Predictor.grow_counts`).
 """
 import numpy as np
 
@@ -131,3 +132,34 @@ def dirichlet_absorb(post, points_count, stats):
     alpha[hit] += sums[hit]
     count[hit] += N[hit]
     return new, count
+
+
+def dirichlet_graft(post, points_count, new_post, new_count):
+    """(post', points_count'): the posterior of K Multinomial clusters (`Predictor.post`: alpha (K, D)) and their point counts with the K'
+    alpha rows of `new_post` (e.g. rows 3 k of a sub-fit's `sampler.post`) and `new_count` appended behind them.  Everything in Float64;
+    the inputs are not modified; rows 0 .. K - 1 keep their values -- their bits when alpha is Float64 already -- and their numbers.
+    ValueError for a posterior that is not a Multinomial one, shapes that do not fit (another D among them), an entry that is not finite or
+    negative, a count that is not finite or negative, and K + K' > binding.MAX_CLUSTERS."""
+    from .. import binding
+    for what, p in (("post", post), ("new_post", new_post)):
+        if "alpha" not in p:
+            raise ValueError(f"dirichlet_graft is for posteriors of the Multinomial prior: {what} lacks 'alpha' (it holds {sorted(p)})")
+    old, new = np.array(post["alpha"], np.float64), np.array(new_post["alpha"], np.float64)
+    if old.ndim != 2 or old.shape[0] < 1 or old.shape[1] < 1 or new.ndim != 2 or new.shape[0] < 1:
+        raise ValueError("post and new_post must hold alpha (K, D)")
+    (K, D), (Kn, Dn) = old.shape, new.shape
+    if Dn != D:
+        raise ValueError(f"new_post has {Dn} features, post {D}")
+    for what, a in (("post", old), ("new_post", new)):
+        if not np.isfinite(a).all() or (a < 0).any():
+            raise ValueError(f"{what} holds an alpha that is not finite or is negative")
+    count, ncount = np.array(points_count, np.float64), np.array(new_count, np.float64)
+    if count.shape != (K,) or ncount.shape != (Kn,):
+        raise ValueError("points_count and new_count must have one entry per cluster")
+    if not (np.isfinite(count).all() and np.isfinite(ncount).all()) or (count < 0).any() or (ncount < 0).any():
+        raise ValueError("points_count and new_count must be finite and non-negative")
+    if K + Kn > binding.MAX_CLUSTERS:
+        raise ValueError(f"{K} + {Kn} clusters exceed binding.MAX_CLUSTERS = {binding.MAX_CLUSTERS}")
+    out = {k: np.array(v) for k, v in post.items() if k != "alpha"}
+    out["alpha"] = np.concatenate([old, new])
+    return out, np.concatenate([count, ncount])

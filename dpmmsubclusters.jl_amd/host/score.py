@@ -28,7 +28,7 @@ from . import priors as _priors
 from . import tensors as _tensors      # noqa: F401  (the recognisers of host/points.py, reachable from here: tests patch them under this name)
 from . import project as _project
 from . import absorb as _absorb
-from .absorb import niw_absorb, niw_graft, dirichlet_absorb      # noqa: F401
+from .absorb import niw_absorb, niw_graft, dirichlet_absorb, dirichlet_graft      # noqa: F401
 
 
 Exemplars = collections.namedtuple("Exemplars", "typical_idx typical_score fringe_idx fringe_score count skipped")
@@ -62,6 +62,12 @@ HeldOut = collections.namedtuple("HeldOut", "points index total skipped incomple
 HeldOut.__doc__ = """What `Predictor.held_out` returns: points (D, stored) float32 -- a view of the (stored, D) buffer the GPU wrote -- and index
 (stored,) int64, 0-based positions in `data`, increasing -- tensors on the data's device for a device tensor, else numpy arrays; total, the
 held-out points there are (stored = min(total, max_points)); skipped, incomplete, ints, as `statistics` counts them."""
+
+HeldOutCounts = collections.namedtuple("HeldOutCounts", "points index total total_entries skipped incomplete")
+HeldOutCounts.__doc__ = """What `Predictor.held_out_counts` returns: points (D, stored), following the input -- a dense float32 tensor on the data's
+device or a numpy array; a torch.sparse_csc tensor (int32 indices, float32 values) for a sparse tensor; a scipy CSC matrix for scipy or tuple
+input -- and index (stored,) int64, 0-based positions in `data`, increasing; total, total_entries, the held-out points there are and their
+entries (dense data: D each); skipped, incomplete, ints, as `count_statistics` counts them."""
 
 Growth = collections.namedtuple("Growth", "added sizes index labels dropped total model")
 Growth.__doc__ = """What `Predictor.grow` returns: added, the number of clusters appended; sizes (added,) int64, their points; index (kept,) int64,
@@ -137,6 +143,18 @@ def _floors(min_logdens, min_tail):
     return min_logdens, min_tail
 
 
+def _count_floors(min_logdens, min_logdens_per_count):
+    """The two floors of `count_statistics`, `held_out_counts` and `grow_counts` as floats or None; ValueError for a NaN."""
+    out = []
+    for name, v in (("min_logdens", min_logdens), ("min_logdens_per_count", min_logdens_per_count)):
+        if v is not None:
+            v = float(v)
+            if v != v:
+                raise ValueError(f"{name} must not be NaN")
+        out.append(v)
+    return out
+
+
 class _Stages:
     """The staging of a Predictor's short slab as host/points.py asks for it -- "host", "dev", "csc" -- kept on the Predictor as
     `_host_stage`, `_dev_stage`, `_csc_stage`; suffix "_in": the D_in-wide ones of dense data that is projected on the way in."""
@@ -171,10 +189,14 @@ class Predictor:
         hyper = None
         if s.prior.kind == _priors.PRIOR_NIW and all(hasattr(s.prior, k) for k in ("kappa", "m", "nu", "psi")):      # what `grow` fits new clusters under
             hyper = {k: getattr(s.prior, k) for k in ("kappa", "m", "nu", "psi")}
+        prior_alpha = getattr(s.prior, "alpha", None) if s.prior.kind == _priors.PRIOR_MULT else None      # what `grow_counts` fits new clusters under
         self._setup(s.prior.kind, s.prior.dim, s.alpha, np.asarray(s.points_count), post, capacity, device, worker_factory,
-                    projection=getattr(dp_model, "projection", None), missing=missing, prior_hyper=hyper)
+                    projection=getattr(dp_model, "projection", None), missing=missing, prior_hyper=hyper, prior_alpha=prior_alpha)
 
-    def _setup(self, kind, D, alpha, points_count, post, capacity, device, worker_factory, projection=None, missing="propagate", prior_hyper=None):
+    def _setup(self, kind, D, alpha, points_count, post, capacity, device, worker_factory, projection=None, missing="propagate", prior_hyper=None,
+               prior_alpha=None):
+        # the Multinomial prior's Dirichlet alpha (D,) in Float64, or None: an NIW model, or a model file written without it
+        self.prior_alpha = None if prior_alpha is None else np.array(prior_alpha, np.float64).ravel()
         # the model's NIW hyper-parameters kappa, m (D,), nu, psi (D, D) in Float64, or None: a model file written without them
         self.prior_hyper = None if prior_hyper is None else {k: np.array(prior_hyper[k], np.float64) for k in ("kappa", "m", "nu", "psi")}
         if missing not in MISSING_MODES:
@@ -246,10 +268,12 @@ class Predictor:
     # ---- a model to serve, without the training data or the sampler
     def save(self, path):
         """One .npz: prior kind, D, alpha, points_count, the posterior arrays of the K clusters, the projection, if the model has one, and
-        the NIW hyper-parameters `grow` fits new clusters under (prior_kappa, prior_m, prior_nu, prior_psi), if the Predictor has them."""
+        the NIW hyper-parameters `grow` fits new clusters under (prior_kappa, prior_m, prior_nu, prior_psi) or the Multinomial prior's
+        alpha `grow_counts` fits them under (prior_alpha), if the Predictor has them."""
         np.savez(path, kind=np.int64(self.kind), D=np.int64(self.D), alpha=np.float64(self.alpha), points_count=self.points_count,
                  **{"post_" + k: v for k, v in self.post.items()}, **(self.projection.arrays("proj_") if self.projection is not None else {}),
-                 **({"prior_" + k: v for k, v in self.prior_hyper.items()} if self.prior_hyper is not None else {}))
+                 **({"prior_" + k: v for k, v in self.prior_hyper.items()} if self.prior_hyper is not None else {}),
+                 **({"prior_alpha": self.prior_alpha} if self.prior_alpha is not None else {}))
 
     @classmethod
     def load(cls, path, device=None, capacity=65536, worker_factory=None, missing="propagate"):
@@ -258,7 +282,8 @@ class Predictor:
             hyper = {k: z["prior_" + k] for k in ("kappa", "m", "nu", "psi")} if all("prior_" + k in z.files for k in ("kappa", "m", "nu", "psi")) else None
             self = cls.__new__(cls)
             self._setup(int(z["kind"]), int(z["D"]), float(z["alpha"]), z["points_count"], post, capacity, 0 if device is None else device, worker_factory,
-                        projection=_project.Projection.from_arrays(z, "proj_"), missing=missing, prior_hyper=hyper)
+                        projection=_project.Projection.from_arrays(z, "proj_"), missing=missing, prior_hyper=hyper,
+                        prior_alpha=z["prior_alpha"] if "prior_alpha" in z.files else None)
         return self
 
     # ---- the public methods
@@ -501,7 +526,8 @@ class Predictor:
         if self._wk is None:
             raise RuntimeError("this Predictor is closed")
         if self.kind != _priors.PRIOR_NIW:
-            raise ValueError(f"{what} is for the NIW prior and dense points: the Multinomial prior and sparse stores are out of scope")
+            raise ValueError(f"{what} is for the NIW prior and dense points: the Multinomial prior and sparse stores are out of scope here "
+                             f"-- a Multinomial model has {what}_counts")
         min_logdens, min_tail = _floors(min_logdens, min_tail)
         if min_logdens is None and min_tail is None:
             raise ValueError(f"{what} needs a floor: min_logdens or min_tail")
@@ -574,7 +600,8 @@ class Predictor:
         posteriors already hold them once; absorb the batch first and grow afterwards if that matters).  NIW only; the Multinomial prior,
         sparse stores, several ranks and merging a new cluster with an old one are out of scope."""
         if self.kind != _priors.PRIOR_NIW:
-            raise ValueError("grow is for the NIW prior and dense points: the Multinomial prior and sparse stores are out of scope")
+            raise ValueError("grow is for the NIW prior and dense points: the Multinomial prior and sparse stores are out of scope here "
+                             "-- a Multinomial model has grow_counts")
         hyper = self._prior_object(prior)
         alpha = self.alpha if alpha is None else float(alpha)
         if not alpha > 0:
@@ -622,7 +649,7 @@ class Predictor:
         return Growth(len(keep), sizes[keep].astype(np.int64), index.cpu().numpy()[kept], new_id[lab - 1][kept], dropped, total, model)
 
     # ---- count statistics and the Dirichlet update (include/dpmm_hip_countstats.h, host/absorb.py)
-    def count_statistics(self, data, assign="hard", min_logdens=None):
+    def count_statistics(self, data, assign="hard", min_logdens=None, min_logdens_per_count=None):
         """The per-cluster sufficient statistics of count `data` under a Multinomial model: a `CountStatistics` tuple, accumulated on the
         GPU in Float64.
 
@@ -630,7 +657,11 @@ class Predictor:
         with w_ik = 1 for the cluster `predict_labels` gives the point (assign="hard": N == count) or the probability `predict` gives
         (assign="soft"), over the points that TAKE PART.  Every point is counted in exactly one of
           skipped      its row of the table holds a NaN or no finite entry (as `overlap` skips it);
-          held_out     min_logdens is given and `score_samples` of the point lies below it: an outlier is not folded into a cluster;
+          held_out     min_logdens is given and `score_samples` of the point lies below it, or min_logdens_per_count is given, every value
+                       of the point is finite, its total t (the Float64 sum of its values) is positive and `score_samples` of the point lies
+                       below min_logdens_per_count * t: an outlier is not folded into a cluster.  The log-density scales with the number of
+                       counts in the point, so min_logdens is mostly a length filter; the log-density PER COUNT -- the log of the inverse
+                       perplexity -- is comparable across lengths and is what this prior has in the place of `min_tail`;
           incomplete   a value of it is not finite (of its D features, or of its stored entries when the data is sparse);
           count[k]     it takes part and `predict_labels` labels it k + 1.
         `data` is whatever `predict` takes for a Multinomial model -- a dense array or tensor, scipy CSC, the (colptr, rowval, nzval,
@@ -645,27 +676,30 @@ class Predictor:
             raise ValueError("count_statistics are for the Multinomial prior: an NIW model has statistics / absorb")
         if assign not in ASSIGN_MODES:
             raise ValueError('assign must be "hard" or "soft"')
-        if min_logdens is not None:
-            min_logdens = float(min_logdens)
-            if min_logdens != min_logdens:
-                raise ValueError("min_logdens must not be NaN")
+        min_logdens, per_count = _count_floors(min_logdens, min_logdens_per_count)
         wk = self._wk
         if not hasattr(wk, "countstats_begin"):
             raise RuntimeError("this Predictor's worker cannot accumulate count statistics (no dpmm_countstats_begin)")
+        if per_count is not None and not hasattr(wk, "countstats_set_per_count"):
+            raise RuntimeError("this Predictor's worker cannot hold points out per count (no dpmm_countstats_set_per_count)")
         opened = self._open(data)
         wk.countstats_begin(ASSIGN_MODES[assign], min_logdens)
+        if per_count is not None:
+            wk.countstats_set_per_count(per_count)
         self._walk(opened, [], lambda views, lo, hi: wk.countstats_accumulate(hi - lo))
         r = wk.countstats_read()
         return CountStatistics(r["N"], r["sums"], r["count"], int(r["skipped"][0]), int(r["incomplete"][0]), int(r["held_out"][0]))
 
-    def absorb_counts(self, data, assign="hard", min_logdens=None):
+    def absorb_counts(self, data, assign="hard", min_logdens=None, min_logdens_per_count=None):
         """Folds count `data` into a Multinomial model and returns the `CountStatistics` it absorbed (see `count_statistics`).
 
         The Dirichlet prior is conjugate: `dirichlet_absorb` adds the sums to alpha -- kept in Float64 from then on -- of every cluster
         that received weight, and N to `points_count`, hence the mixture weights.  The predictive parameters are then reloaded into the
         same worker, once, so every later call, `sample` and `save` see the updated model; an accumulation begun before is refused
-        afterwards.  Statistics with N.sum() == 0 change nothing.  No new cluster is created: see `absorb`."""
-        stats = self.count_statistics(data, assign=assign, min_logdens=min_logdens)
+        afterwards.  Statistics with N.sum() == 0 change nothing.  No new cluster is created: points far from every cluster are absorbed
+        by the nearest one or, with a floor, held out and counted; `held_out_counts` collects those and `grow_counts` turns them into new
+        clusters."""
+        stats = self.count_statistics(data, assign=assign, min_logdens=min_logdens, min_logdens_per_count=min_logdens_per_count)
         if not stats.N.sum() > 0:
             return stats
         self.post, self.points_count = _absorb.dirichlet_absorb(self.post, self.points_count, stats)
@@ -675,6 +709,183 @@ class Predictor:
         self._wk.set_predictive_mult(*args)
         self._sampler_set = False            # the alias tables of `sample` are those of the old posterior
         return stats
+
+    # ---- held-out count points and new clusters (include/dpmm_hip_countholdout.h, host/absorb.py)
+    def _capture_counts(self, data, min_logdens, min_logdens_per_count, max_points, max_entries, what):
+        """The held-out points of count `data` as the GPU compacted them: (sparse?, the destination tensors cut to what was stored, the
+        worker's counters, the Points description of `data`)."""
+        if self._wk is None:
+            raise RuntimeError("this Predictor is closed")
+        if self.kind != _priors.PRIOR_MULT:
+            raise ValueError(f"{what} is for the Multinomial prior: an NIW model has {what[:-7]}")
+        min_logdens, per_count = _count_floors(min_logdens, min_logdens_per_count)
+        if min_logdens is None and per_count is None:
+            raise ValueError(f"{what} needs a floor: min_logdens or min_logdens_per_count")
+        for name, v in (("max_points", max_points), ("max_entries", max_entries)):
+            if v != int(v) or int(v) < 0:
+                raise ValueError(f"{name} must be a non-negative integer")
+        wk = self._wk
+        if not hasattr(wk, "countholdout_begin"):
+            raise RuntimeError("this Predictor's worker cannot collect held-out count points (no dpmm_countholdout_begin)")
+        opened = self._open(data)
+        n = opened[0]
+        pts = _points.describe(data)
+        sparse = pts.is_sparse and hasattr(wk, "upload_points_csc")          # (a worker without the sparse upload is given dense rows)
+        import torch
+        where = torch.device(getattr(wk, "holdout_device", None) or f"cuda:{self.device}")      # (a stand-in worker names where its buffers live)
+        if sparse:
+            nnz = int(pts.desc.nnz_extent) if hasattr(pts, "desc") else int(len(pts.csc.data))
+            cap, ecap = min(int(max_points), n), min(int(max_entries), nnz)
+            dst = dict(colptr=torch.empty((cap + 1,), dtype=torch.int64, device=where), rowval=torch.empty((ecap,), dtype=torch.int32, device=where),
+                       val=torch.empty((ecap,), dtype=torch.float32, device=where), entry_cap=ecap)
+        else:
+            cap = min(int(max_points), n, int(max_entries) // self.D)
+            dst = dict(points=torch.empty((cap, self.D), dtype=torch.float32, device=where))
+        dst.update(index=torch.empty((cap,), dtype=torch.int64, device=where), cap=cap)
+        wk.countholdout_begin(dst, min_logdens, per_count)
+        self._walk(opened, [], lambda views, lo, hi: wk.countholdout_accumulate(lo, hi - lo))
+        r = wk.countholdout_read()                         # (waits for the worker's stream: the buffers are complete)
+        st, se = r["stored"], r["stored_entries"]
+        if sparse:
+            if cap == 0:
+                dst["colptr"] = torch.zeros((1,), dtype=torch.int64, device=where)
+            got = dict(colptr=dst["colptr"][:st + 1], rowval=dst["rowval"][:se], val=dst["val"][:se], index=dst["index"][:st])
+        else:
+            got = dict(points=dst["points"][:st], index=dst["index"][:st])
+        return sparse, got, r, pts
+
+    def held_out_counts(self, data, min_logdens=None, min_logdens_per_count=None, max_points=1 << 20, max_entries=1 << 24):
+        """The points of count `data` that `count_statistics` / `absorb_counts` would HOLD OUT under the same floors -- the documents no
+        topic of the model explains -- collected on the GPU while the score table goes by: a `HeldOutCounts` tuple.
+
+          points       (D, stored), the points as the worker holds them, in increasing position, and following the input: dense data gives a
+                       float32 tensor on the data's device (a view of the (stored, D) buffer the library wrote) or a numpy array for host
+                       data; a torch.sparse_csc tensor gives one on its device, int32 indices (the int64 offsets cast alongside the int32
+                       rows) and float32 values; scipy CSC or the (colptr, rowval, nzval, shape) tuple gives a scipy CSC matrix.  `fit` and
+                       `predict` read these layouts in place;
+          index        (stored,) int64, their 0-based positions along the Samples axis of `data`;
+          total, total_entries   the held-out points there are and their entries (dense data: D per point);
+          skipped, incomplete    as `count_statistics` counts them (a point in either class is never held out).
+        At least one floor is required; either one holds a point out (see `count_statistics`).  The points kept are the longest prefix
+        inside both caps: dense data keeps the first min(max_points, n, max_entries // D) held-out points; sparse data the first
+        max_points whose entries all lie inside min(max_entries, nnz(data)) -- a point whose entries do not all fit is dropped with every
+        point behind it.  Nothing of size n crosses the host link and nothing of size n is allocated beyond the destination.  The result
+        does not depend on `capacity`, the caps or the table budget, to the bit.  Multinomial only; several ranks are out of scope."""
+        sparse, got, r, pts = self._capture_counts(data, min_logdens, min_logdens_per_count, max_points, max_entries, "held_out_counts")
+        index = got["index"]
+        if not sparse:
+            points = got["points"]
+            if pts.torch_device is None:
+                points, index = points.cpu().numpy(), index.cpu().numpy()
+            points = points.T
+        else:
+            import torch
+            stored = int(index.shape[0])
+            if isinstance(data, torch.Tensor):
+                points = torch.sparse_csc_tensor(got["colptr"].to(torch.int32), got["rowval"], got["val"], size=(self.D, stored)).to(data.device)
+                index = index.to(data.device)
+            else:
+                import scipy.sparse
+                points = scipy.sparse.csc_matrix((got["val"].cpu().numpy(), got["rowval"].cpu().numpy(), got["colptr"].cpu().numpy()), shape=(self.D, stored))
+                index = index.cpu().numpy()
+        return HeldOutCounts(points, index, r["total"], r["total_entries"], r["skipped"], r["incomplete"])
+
+    def _prior_alpha_object(self, prior):
+        """The multinomial_hyper `grow_counts` fits under: the caller's, else the model's."""
+        if prior is None and self.prior_alpha is not None:
+            prior = _priors.multinomial_hyper(self.prior_alpha)
+        if prior is None:
+            raise ValueError("grow_counts needs the model's Multinomial prior and this Predictor has none (a model file written without "
+                             "prior_alpha): pass prior=multinomial_hyper(alpha)")
+        if getattr(prior, "kind", None) != _priors.PRIOR_MULT or getattr(prior, "dim", None) != self.D:
+            raise ValueError(f"prior must be multinomial_hyper over the model's {self.D} features")
+        return prior
+
+    def grow_counts(self, data, min_logdens=None, min_logdens_per_count=None, prior=None, alpha=None, iters=100, min_points=10, max_points=1 << 20,
+                    max_entries=1 << 24, seed=0, **fit_kw):
+        """Adds clusters for the part of count `data` the model does not explain, and returns a `Growth` tuple: `grow` for the Multinomial
+        prior.
+
+        The held-out points of `data` (`held_out_counts`, the same floors and caps) are clustered where the GPU left them -- sparse data
+        stays sparse -- by the project's own sampler, `fit(points, prior, alpha, iters=iters, seed=seed, verbose=False, **fit_kw)`, and every
+        cluster of that sub-fit with at least `min_points` points is appended to the served model: its alpha row (row 3 k of the
+        sub-model's `sampler.post`) behind the K the model has (`dirichlet_graft`), its size to `points_count`; the weights are re-formed
+        from points_count + alpha and the predictive parameters reloaded into the same worker, once.  The old clusters keep their numbers
+        and their bits; every later call, `sample` and `save` see K + added clusters.
+          prior        multinomial_hyper for the new clusters; default: the model's own (`prior_alpha`, recorded from the fitted model and
+                       kept by `save` / `load`).  A model file written before it was kept has none: ValueError unless prior= is given;
+          alpha        of the sub-fit; default: the Predictor's;
+          dropped      captured points that went into no new cluster: one with a value that is not finite, or a member of a sub-cluster
+                       below min_points.
+        Nothing left to cluster, or no sub-cluster large enough: added = 0 and the model is untouched.  Any failure before the reload leaves
+        the Predictor as it was.  `grow_counts` does NOT absorb: the idiom is
+            p.grow_counts(batch, min_logdens_per_count=f); p.absorb_counts(batch, min_logdens_per_count=f)
+        where the second call sees the GROWN model.  Multinomial only; several ranks and merging a new cluster with an old one are out of
+        scope."""
+        if self.kind != _priors.PRIOR_MULT:
+            raise ValueError("grow_counts is for the Multinomial prior: an NIW model has grow")
+        hyper = self._prior_alpha_object(prior)
+        alpha = self.alpha if alpha is None else float(alpha)
+        if not alpha > 0:
+            raise ValueError("alpha must be positive")
+        min_points = int(min_points)
+        if min_points < 1:
+            raise ValueError("min_points must be at least 1")
+        sparse, got, r, _ = self._capture_counts(data, min_logdens, min_logdens_per_count, max_points, max_entries, "grow_counts")
+        import torch
+        total, K0 = r["total"], self.K
+        index = got["index"]
+        stored = int(index.shape[0])
+        if sparse:                                         # a value that is not finite drops its column
+            colptr, rowval, val = got["colptr"], got["rowval"], got["val"]
+            lens = colptr[1:] - colptr[:-1]
+            finite = torch.ones((stored,), dtype=torch.bool, device=index.device)
+            okv = torch.isfinite(val)
+            if not bool(okv.all()):
+                col = torch.repeat_interleave(torch.arange(stored, device=index.device), lens)
+                finite[col[~okv]] = False
+                keep_e = finite[col]
+                rowval, val, lens = rowval[keep_e], val[keep_e], lens[finite]
+                colptr = torch.cat([torch.zeros((1,), dtype=torch.int64, device=index.device), torch.cumsum(lens, 0)])
+        else:
+            finite = torch.isfinite(got["points"]).all(1)
+        dropped = int(stored - int(finite.sum()))
+        if dropped:
+            index = index[finite]
+        none = np.zeros(0, np.int64)
+        if index.shape[0] == 0:
+            return Growth(0, none, none, none, dropped, total, None)
+        if sparse:
+            points = torch.sparse_csc_tensor(colptr.to(torch.int32), rowval, val, size=(self.D, int(index.shape[0])))
+        else:
+            points = (got["points"][finite] if dropped else got["points"]).T
+        from . import api as _api
+        res = _api.fit(points, hyper, alpha, iters=int(iters), seed=seed, verbose=False, **fit_kw)
+        model, lab = res[8], res[0]
+        lab = (lab.cpu().numpy() if hasattr(lab, "cpu") else np.asarray(lab)).astype(np.int64)
+        s = model.sampler
+        sizes = np.bincount(lab - 1, minlength=s.K)
+        if len(sizes) != s.K or len(lab) != index.shape[0]:
+            raise RuntimeError("grow_counts: the sub-fit's labels do not match its clusters")
+        keep = np.flatnonzero(sizes >= min_points)
+        dropped += int(sizes.sum() - sizes[keep].sum())
+        if len(keep) == 0:
+            return Growth(0, none, none, none, dropped, total, model)
+        post, count = _absorb.dirichlet_graft(self.post, self.points_count, {"alpha": np.asarray(s.post["alpha"])[3 * keep]}, sizes[keep])
+        w = count + self.alpha
+        old = self.post, self.points_count, self.weights, self.K
+        self.post, self.points_count, self.weights, self.K = post, count, (w / w.sum()).astype(np.float32), len(count)
+        try:
+            which, args = self._predictive_args()
+            self._wk.set_predictive_mult(*args)            # ONCE, with the new K
+        except Exception:
+            self.post, self.points_count, self.weights, self.K = old
+            raise
+        self._sampler_set = False                          # the alias tables of `sample` are those of the old K
+        new_id = np.zeros(s.K, np.int64)
+        new_id[keep] = K0 + 1 + np.arange(len(keep))
+        kept = new_id[lab - 1] > 0
+        return Growth(len(keep), sizes[keep].astype(np.int64), index.cpu().numpy()[kept], new_id[lab - 1][kept], dropped, total, model)
 
     # ---- missing features (include/dpmm_hip_missing.h)
     def impute(self, data, draws=None, seed=0, return_components=False):
@@ -951,6 +1162,14 @@ def held_out(dp_model, data, **kw):
         return p.held_out(data, **args)
 
 
+def held_out_counts(dp_model, data, **kw):
+    """The points of count `data` below a Multinomial model's floors, collected on the GPU (opens a Predictor, runs, closes): see
+    `Predictor.held_out_counts`; kw: min_logdens, min_logdens_per_count, max_points, max_entries, capacity, device, worker_factory."""
+    args = {k: kw.pop(k) for k in ("min_logdens", "min_logdens_per_count", "max_points", "max_entries") if k in kw}
+    with Predictor(dp_model, **kw) as p:
+        return p.held_out_counts(data, **args)
+
+
 def overlap(dp_model, data, **kw):
     """The overlap matrix of the clusters on `data` (opens a Predictor, runs, closes): see `Predictor.overlap`;
     kw: capacity, device, worker_factory, missing."""
@@ -968,10 +1187,10 @@ def statistics(dp_model, data, **kw):
 
 def count_statistics(dp_model, data, **kw):
     """The per-cluster count statistics of `data` under a Multinomial model (opens a Predictor, runs, closes): see
-    `Predictor.count_statistics`; kw: assign, min_logdens, capacity, device, worker_factory."""
-    assign, min_logdens = kw.pop("assign", "hard"), kw.pop("min_logdens", None)
+    `Predictor.count_statistics`; kw: assign, min_logdens, min_logdens_per_count, capacity, device, worker_factory."""
+    assign, min_logdens, per_count = kw.pop("assign", "hard"), kw.pop("min_logdens", None), kw.pop("min_logdens_per_count", None)
     with Predictor(dp_model, **kw) as p:
-        return p.count_statistics(data, assign=assign, min_logdens=min_logdens)
+        return p.count_statistics(data, assign=assign, min_logdens=min_logdens, min_logdens_per_count=per_count)
 
 
 def impute(dp_model, data, draws=None, seed=0, return_components=False, **kw):

@@ -15,7 +15,8 @@
  * (score_device.h) from the table the Multinomial kernels' table mode writes; the sparse store keeps its convention that a feature a
  * point does not store contributes nothing.  Every point 0 .. n_valid - 1 is in exactly one class:
  *   skipped      a NaN in its row of parr, or M not finite (the rule of dpmm_hip_overlap.h / dpmm_hip_batchstats.h); else
- *   held out     use_floor != 0 and logdens_i < min_logdens, logdens_i the Float32 value dpmm_score_points writes; else
+ *   held out     use_floor != 0 and logdens_i < min_logdens, logdens_i the Float32 value dpmm_score_points writes; or the floor
+ *                per count of include/dpmm_hip_countholdout.h, when it has been set, holds the point out; else
  *   incomplete   one of its values is not finite: of the D features of its row (Float32 store), of its stored values (sparse store);
  *                a point of the byte store never is; else
  *   takes part   and is counted in count[k], k + 1 its label.
