@@ -305,6 +305,7 @@ ABI_MISSING = [
 ]
 OPT_SCORE_MISSING = 33       # DPMM_OPT_SCORE_MISSING
 SCORE_MAX_MISSING = 16       # DPMM_SCORE_MAX_MISSING
+OPT_TYPICALITY_GAPS = 35     # DPMM_OPT_TYPICALITY_GAPS (include/dpmm_hip_typicality.h): typicality / explain marginalise a point's gaps
 # include/dpmm_hip_impute.h: draws of the missing features from the fitted mixture (additive; bound next to ABI)
 _IMPUTE_DRAW_TAIL = [ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]
 ABI_IMPUTE = [

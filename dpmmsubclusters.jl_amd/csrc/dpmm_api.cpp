@@ -215,6 +215,7 @@ struct dpmm_ctx {
     // missing features (include/dpmm_hip_missing.h): the constants of the marginals on the host (formed by dpmm_set_predictive_niw); on the
     // device, allocated by the first call that marginalises: their copy, the transposed factors, a range's list and the three counters
     int opt_score_missing = 0;         // DPMM_OPT_SCORE_MISSING
+    int opt_typ_gaps = 0;              // DPMM_OPT_TYPICALITY_GAPS
     std::vector<double> h_miss_cst;    // [K][MISS_CST]
     int miss_slots = 0;                // slots of the parameter staging when the predictive parameters were committed (their layout in d_par)
     unsigned long long pred_gen = 0, miss_gen = 0;      // parameter set in force / the one the device copies were made from (0: none)
@@ -3042,6 +3043,9 @@ int dpmm_set_option(dpmm_ctx *c, int option, double value) {
         case DPMM_OPT_SCORE_MISSING:
             if (value != 0 && c->prior != DPMM_PRIOR_NIW) return fail(c, DPMM_EINVAL, "DPMM_OPT_SCORE_MISSING: the Multinomial prior has no missing features");
             c->opt_score_missing = value != 0; return DPMM_OK;
+        case DPMM_OPT_TYPICALITY_GAPS:
+            if (value != 0 && c->prior != DPMM_PRIOR_NIW) return fail(c, DPMM_EINVAL, "DPMM_OPT_TYPICALITY_GAPS: the Multinomial prior has no missing features");
+            c->opt_typ_gaps = value != 0; return DPMM_OK;
         default: return fail(c, DPMM_EINVAL, "unknown option");
     }
 }
@@ -3938,19 +3942,21 @@ int dpmm_score_missing_counts(dpmm_ctx *c, int64_t out[2]) {
 }
 
 // ---- include/dpmm_hip_typicality.h: label, q = |R_k (x - m_k)|^2 of the point's own cluster and its tail, range by range (typicality.hip) ----
-// The scratch of one range of P points (class words, q) and the two counters; the parameter copies of missing.hip are those in force.
+// The scratch of one range of P points (class words, q) and the three counters; the parameter copies of missing.hip are those in force.
 static int typ_begin(dpmm_ctx *c, int64_t P, const char *fn) {
     if (int rc = grow(c, c->d_typ_cls, sizeof(int32_t) * (size_t)P, "dpmm_score_points", "class words of the typicality pass")) return rc;
     if (int rc = grow(c, c->d_typ_q, sizeof(float) * (size_t)P, "dpmm_score_points", "squared distances of the typicality pass")) return rc;
-    if (int rc = grow(c, c->d_typ_cnt, 2 * sizeof(unsigned long long), "dpmm_score_points", "counters of the typicality pass")) return rc;
+    if (int rc = grow(c, c->d_typ_cnt, 3 * sizeof(unsigned long long), "dpmm_score_points", "counters of the typicality pass")) return rc;
     return miss_params(c, fn);
 }
 
 // One range of the table (np points from point p0, rows P floats apart), just evaluated (and patched) on the ctx stream.  labels, q, tail:
-// device memory of np entries or null; q == null: the ctx's scratch.  The counters are added to.
-static int typ_range(dpmm_ctx *c, int64_t P, int64_t p0, int64_t np, int64_t *labels, float *q, float *tail, const char *fn) {
+// device memory of np entries or null; q == null: the ctx's scratch.  The counters are added to.  gaps: the walk's missing-feature pass has
+// just listed this range's points with gaps, and q and tail of those are marginalised (DPMM_OPT_TYPICALITY_GAPS).
+static int typ_range(dpmm_ctx *c, int64_t P, int64_t p0, int64_t np, int64_t *labels, float *q, float *tail, const char *fn, bool gaps = false) {
     TypicalityArgs a = niw_range_args<TypicalityArgs>(c, P, p0, np);
     a.cls = c->d_typ_cls; a.labels = labels; a.q = q ? q : c->d_typ_q.get(); a.tail = tail; a.cnt = c->d_typ_cnt;
+    if (gaps) { a.list = c->d_miss_list; a.list_cnt = c->d_miss_cnt; }
     return table_result(c, fn, launch_typicality_range(a, 32 * c->cus, c->stream));
 }
 
@@ -3976,21 +3982,22 @@ static int typicality_points(dpmm_ctx *c, const dpmm_typicality_out *o, bool dev
     TableWalk w;
     if (int rc = walk_open(c, fn, WALK_MISS_OPTION, &w)) return rc;
     if (int rc = typ_begin(c, w.P, fn)) return rc;
-    HIPCHK(c, hipMemsetAsync(c->d_typ_cnt, 0, 2 * sizeof(unsigned long long), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->d_typ_cnt, 0, 3 * sizeof(unsigned long long), c->stream));
+    const bool gaps = w.miss && c->opt_typ_gaps != 0;      // (without a list nothing new runs)
     OutStage<3> out{{{o->labels, sizeof(int64_t)}, {o->mahalanobis, sizeof(float)}, {o->tail, sizeof(float)}}, device};
     if (!device) {
         if (int rc = grow(c, c->d_score_out, out.layout((size_t)w.P), "dpmm_score_points", "staging of the outputs")) return rc;
         out.buf = c->d_score_out;
     }
     if (int rc = walk_ranges(c, w, c->n, fn, [&](int64_t p0, int64_t np, int64_t) -> int {
-            if (int rc = typ_range(c, w.P, p0, np, out.at<int64_t>(0, p0), out.at<float>(1, p0), out.at<float>(2, p0), fn)) return rc;
+            if (int rc = typ_range(c, w.P, p0, np, out.at<int64_t>(0, p0), out.at<float>(1, p0), out.at<float>(2, p0), fn, gaps)) return rc;
             return device ? DPMM_OK : table_result(c, fn, out.flush(c, p0, (size_t)np));
         })) return rc;
     HIPCHK(c, sync_stream(c, c->stream));
-    unsigned long long h[2] = {0, 0};
+    unsigned long long h[3] = {0, 0, 0};
     HIPCHK(c, hipMemcpy(h, c->d_typ_cnt, sizeof(h), hipMemcpyDeviceToHost));
     if (o->skipped) o->skipped[0] = (int64_t)h[0];
-    if (o->incomplete) o->incomplete[0] = (int64_t)h[1];
+    if (o->incomplete) o->incomplete[0] = (int64_t)(h[1] - h[2]);      // (h[2]: scored with gaps, 0 without the option)
     return DPMM_OK;
 }
 
@@ -4047,7 +4054,8 @@ static int explain_points(dpmm_ctx *c, const dpmm_explain_out *o, bool device, c
     if (int rc = walk_open(c, fn, WALK_MISS_OPTION, &w)) return rc;
     if (int rc = typ_begin(c, w.P, fn)) return rc;
     if (rows) if (int rc = explain_params(c)) return rc;
-    HIPCHK(c, hipMemsetAsync(c->d_typ_cnt, 0, 2 * sizeof(unsigned long long), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->d_typ_cnt, 0, 3 * sizeof(unsigned long long), c->stream));
+    const bool gaps = w.miss && c->opt_typ_gaps != 0;      // (without a list nothing new runs)
     // the rows: in the caller's device memory ld entries apart; staged (host variant) dense, `width` apart, and copied row by row, so that the
     // words of the caller's rows behind `width` are not touched
     const uint64_t sld = device ? ld : (uint64_t)width;
@@ -4058,7 +4066,7 @@ static int explain_points(dpmm_ctx *c, const dpmm_explain_out *o, bool device, c
         out.buf = c->d_score_out;
     }
     if (int rc = walk_ranges(c, w, c->n, fn, [&](int64_t p0, int64_t np, int64_t) -> int {
-            if (int rc = typ_range(c, w.P, p0, np, out.at<int64_t>(0, p0), out.at<float>(1, p0), out.at<float>(2, p0), fn)) return rc;
+            if (int rc = typ_range(c, w.P, p0, np, out.at<int64_t>(0, p0), out.at<float>(1, p0), out.at<float>(2, p0), fn, gaps)) return rc;
             if (rows) {
                 ExplainArgs a{};
                 a.n = np; a.K = c->K; a.D = c->D;
@@ -4068,7 +4076,9 @@ static int explain_points(dpmm_ctx *c, const dpmm_explain_out *o, bool device, c
                 a.Rr = c->d_exp_rr; a.a = c->d_exp_a; a.cls = c->d_typ_cls;
                 a.residual = out.at<float>(3, p0); a.zscore = out.at<float>(4, p0); a.feature_tail = out.at<float>(5, p0); a.features = out.at<int32_t>(6, p0);
                 a.top = o->top; a.ld = (int64_t)sld;
+                if (gaps) { a.list = c->d_miss_list; a.list_cnt = c->d_miss_cnt; }
                 if (int rc = table_result(c, fn, launch_explain_range(a, 32 * c->cus, c->stream))) return rc;
+                if (gaps) if (int rc = table_result(c, fn, launch_explain_gap_range(a, 32 * c->cus, c->stream))) return rc;
             }
             if (device) return DPMM_OK;
             for (int i = 3; i < 7; ++i) {      // (4-byte entries all; then the three vectors and the wait, by flush)
@@ -4083,10 +4093,10 @@ static int explain_points(dpmm_ctx *c, const dpmm_explain_out *o, bool device, c
             return rc;
         })) return rc;
     HIPCHK(c, sync_stream(c, c->stream));
-    unsigned long long h[2] = {0, 0};
+    unsigned long long h[3] = {0, 0, 0};
     HIPCHK(c, hipMemcpy(h, c->d_typ_cnt, sizeof(h), hipMemcpyDeviceToHost));
     if (o->skipped) o->skipped[0] = (int64_t)h[0];
-    if (o->incomplete) o->incomplete[0] = (int64_t)h[1];
+    if (o->incomplete) o->incomplete[0] = (int64_t)(h[1] - h[2]);      // (h[2]: scored with gaps, 0 without the option)
     return DPMM_OK;
 }
 

@@ -480,7 +480,9 @@ struct TypicalityArgs {
     int64_t *labels;             // [n] or null
     float *q;                    // [n] never null (the caller's array or scratch)
     float *tail;                 // [n] or null: no tail pass
-    unsigned long long *cnt;     // [0] skipped, [1] incomplete: added to
+    unsigned long long *cnt;     // [0] skipped, [1] incomplete, [2] (list != null only) scored with gaps, which [1] counted too: added to
+    const uint32_t *list;        // null, or MissArgs::list of this range as launch_miss_list left it (DPMM_OPT_TYPICALITY_GAPS): behind the passes
+    const unsigned long long *list_cnt;      // above, typ_gap_kernel rewrites q and tail of the listed points; [0] = entries of list
 };
 hipError_t launch_typicality_range(const TypicalityArgs &a, int max_grid, hipStream_t s);
 // ---- per-feature explanation of a point (explain.hip; include/dpmm_hip_explain.h): behind launch_typicality_range of the same range, whose
@@ -497,16 +499,20 @@ struct ExplainArgs {
     const float *mu;             // cluster k's mean: mu + k * mu_step
     int64_t mu_step;
     const double *cst;           // as MissArgs::cst: [k * MISS_CST] = df_k
-    const int32_t *cls;          // [n] the class words launch_typicality_range wrote for this range
+    int32_t *cls;                // [n] the class words launch_typicality_range wrote for this range (read; with a list, explain_gap_kernel
+                                 // adds r << 24 to a listed point's word for its tail pass)
     float *residual;             // [n][ld] or null
     float *zscore;               // [n][ld] or null
     float *feature_tail;         // [n][ld] or null
     int32_t *features;           // [n][ld] or null; written only if top > 0
     int top;                     // 0: all D features in order; else the top features of largest |zscore|, 1 <= top <= min(D, EXPLAIN_MAX_TOP)
     int64_t ld;                  // >= (top ? top : D)
+    const uint32_t *list;        // null, or as TypicalityArgs::list: explain_gap_kernel rewrites the rows of the listed points
+    const unsigned long long *list_cnt;
 };
 hipError_t launch_explain_params(const float *Rpk, int64_t step, float *Rr, float *a, int K, int D, hipStream_t s);      // Rpk: as launch_miss_transpose
 hipError_t launch_explain_range(const ExplainArgs &a, int max_grid, hipStream_t s);
+hipError_t launch_explain_gap_range(const ExplainArgs &a, int max_grid, hipStream_t s);      // explain_gap.hip: behind launch_explain_range, a.list != null
 // draws of the missing features (include/dpmm_hip_impute.h) behind launch_miss_list and launch_miss_patch(a, false, ..) of the same range
 constexpr int64_t MISS_DRAW_MAX = (int64_t)1 << 26;      // draw indices: 64 Philox blocks each in a 32-bit block number
 struct MissDraw {

@@ -7,7 +7,7 @@
 //   miss_patch_kernel   one wave per listed point, looping over the clusters; no workgroup barrier anywhere (the list's length is read
 //                       from device memory, waves leave when they please).  Lane l carries features / rows l, l + 64, .. (NT = ceil(D / 64)
 //                       of them).  Per cluster:
-//                         z = x - m on O, 0 on M; y = R z in Float32: column j of R is one coalesced row of the transposed copy Rt
+//                         (miss_system, missing_device.h) z = x - m on O, 0 on M; y = R z in Float32 by miss_rz<NT>: column j of R is one coalesced row of the transposed copy Rt
 //                         (zero below the diagonal and in the pad), z_j goes round with v_readlane;
 //                         g = C'y, A = C'C (C = R[:, M]): columns of Rt again, products and wave sums in Float64; A goes to r x r words of
 //                         wave-private LDS, where lane a factors row a (Cholesky, column by column) and the two triangular solves leave t_a
@@ -31,9 +31,6 @@
 namespace dpmm {
 
 constexpr int MISS_WAVES = 4;                  // waves per workgroup of the patch kernel (they share nothing)
-constexpr int MISS_LDA = MISS_MAX + 1;         // doubles per row of a wave's A (odd: the lanes of a column fall into different banks)
-
-__device__ __forceinline__ void miss_lds_fence() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); }
 
 __global__ __launch_bounds__(256) void miss_transpose_kernel(const float *__restrict__ Rpk, int64_t step, float *__restrict__ Rt, int K, int D, int Dp) {
     const int64_t total = (int64_t)K * D * Dp;
@@ -73,112 +70,6 @@ __global__ __launch_bounds__(256) void miss_list_kernel(MissArgs A) {
         }
         if (mo && lane == 0) atomicAdd(&A.cnt[2], (unsigned long long)__popcll(mo));
     }
-}
-
-// The range's point behind x: its values (0 in the pad), the NaN ballots per 64 features, M_a in lane a < r; returns r.
-template <int NT>
-__device__ __forceinline__ int miss_read_point(const float *x, int D, int lane, float (&xv)[NT], unsigned long long (&nm)[NT], int &myM) {
-    int r = 0;
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        const int j = 64 * t + lane;
-        xv[t] = j < D ? x[j] : 0.f;
-        nm[t] = __ballot(xv[t] != xv[t]);
-        r += __popcll(nm[t]);
-    }
-    // lane a < r learns M_a, the a-th missing feature
-    myM = 0;
-    int a = 0;
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        unsigned long long mk = nm[t];
-        while (mk) {
-            const int b = __ffsll((long long)mk) - 1;
-            mk &= mk - 1;
-            if (lane == a) myM = 64 * t + b;
-            ++a;
-        }
-    }
-    return r;
-}
-
-// One cluster's small system of a listed point: y = R z, g = C'y, A = C'C = L L' and t = A^-1 g.  Leaves y, t_a in `gl` of lane a < r and L
-// in the wave's LDS (the caller fences before A is overwritten); returns sum_j log L_jj = logdet A / 2.
-template <int NT>
-__device__ __forceinline__ double miss_system(const float *Rk, const float *mk, const float (&xv)[NT], const unsigned long long (&nm)[NT], int myM, int r,
-                                              int D, int lane, double *Am, float (&y)[NT], double &gl) {
-    constexpr int Dp = 64 * NT;
-    float z[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        const int j = 64 * t + lane;
-        const bool miss = (nm[t] >> lane) & 1ull;
-        z[t] = (j < D && !miss) ? xv[t] - mk[j] : 0.f;
-    }
-    miss_rz<NT>(Rk, z, D, lane, y);      // ---- y = R z (missing_device.h)
-    // ---- g = C'y into lane b, A = C'C (lower triangle) into the wave's LDS
-    gl = 0.0;
-    for (int b = 0; b < r; ++b) {
-        const float *cb = Rk + (int64_t)__builtin_amdgcn_readlane(myM, b) * Dp + lane;
-        float colb[NT];
-        double p = 0.0;
-#pragma unroll
-        for (int t = 0; t < NT; ++t) { colb[t] = cb[64 * t]; p += (double)colb[t] * (double)y[t]; }
-        p = miss_wave_sum(p);
-        if (lane == b) gl = p;
-        for (int a = 0; a <= b; ++a) {
-            const float *ca = Rk + (int64_t)__builtin_amdgcn_readlane(myM, a) * Dp + lane;
-            double s = 0.0;
-#pragma unroll
-            for (int t = 0; t < NT; ++t) s += (double)ca[64 * t] * (double)colb[t];
-            s = miss_wave_sum(s);
-            if (lane == 0) Am[b * MISS_LDA + a] = s;
-        }
-    }
-    miss_lds_fence();
-    // ---- A = L L': lane a owns row a; column j is finished by the lanes j .. r - 1 at once
-    double half_logdet = 0.0;
-    for (int j = 0; j < r; ++j) {
-        const bool act = lane >= j && lane < r;
-        const int row = act ? lane : j;
-        double s = Am[row * MISS_LDA + j];
-        for (int t2 = 0; t2 < j; ++t2) s -= Am[row * MISS_LDA + t2] * Am[j * MISS_LDA + t2];
-        const double dj = sqrt(miss_rl_d(s, j));
-        half_logdet += log(dj);
-        if (act) Am[lane * MISS_LDA + j] = (lane == j) ? dj : s / dj;
-        miss_lds_fence();
-    }
-    // ---- t = A^-1 g: L u = g, then L't = u; lane a ends with t_a
-    for (int j = 0; j < r; ++j) {
-        if (lane == j) gl = gl / Am[j * MISS_LDA + j];
-        const double uj = miss_rl_d(gl, j);
-        if (lane > j && lane < r) gl -= Am[lane * MISS_LDA + j] * uj;
-    }
-    for (int j = r - 1; j >= 0; --j) {
-        if (lane == j) gl = gl / Am[j * MISS_LDA + j];
-        const double tj = miss_rl_d(gl, j);
-        if (lane < j) gl -= Am[j * MISS_LDA + lane] * tj;
-    }
-    return half_logdet;
-}
-
-// q_o = |y - C t|^2, the residual itself (t_a in `gl` of lane a < r); every lane ends with the same bits
-template <int NT>
-__device__ __forceinline__ double miss_residual(const float *Rk, const float (&y)[NT], double gl, int myM, int r, int lane) {
-    constexpr int Dp = 64 * NT;
-    double res[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) res[t] = (double)y[t];
-    for (int a = 0; a < r; ++a) {
-        const float *ca = Rk + (int64_t)__builtin_amdgcn_readlane(myM, a) * Dp + lane;
-        const double ta = miss_rl_d(gl, a);
-#pragma unroll
-        for (int t = 0; t < NT; ++t) res[t] -= (double)ca[64 * t] * ta;
-    }
-    double q = 0.0;
-#pragma unroll
-    for (int t = 0; t < NT; ++t) q += res[t] * res[t];
-    return miss_wave_sum(q);
 }
 
 // M and S of score_finish_kernel from a point's (patched) column: p_k = expf(a_k - M) / S, a NaN entry counting as -Inf

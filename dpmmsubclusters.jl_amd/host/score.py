@@ -128,6 +128,7 @@ def _device_index(device):
 
 
 MISSING_MODES = ("propagate", "marginalize")
+GAPS_MODES = ("incomplete", "marginalize")      # `gaps` of Predictor.typicality / explain
 
 
 def _floors(min_logdens, min_tail):
@@ -308,7 +309,29 @@ class Predictor:
         return self._run(data, logdens=True)["logdens"]
 
     # ---- calibrated outlier scores (include/dpmm_hip_typicality.h)
-    def typicality(self, data):
+    def _gaps_option(self, gaps, what):
+        """The value of DPMM_OPT_TYPICALITY_GAPS for a call with `gaps`; raises before the worker is touched."""
+        if gaps not in GAPS_MODES:
+            raise ValueError('gaps must be "incomplete" or "marginalize"')
+        if gaps == "incomplete":
+            return 0
+        if self.kind != _priors.PRIOR_NIW:
+            raise ValueError(f'{what}: gaps="marginalize" is for the NIW prior: the Multinomial prior has no missing features')
+        if self.missing != "marginalize":
+            raise ValueError(f'{what}: gaps="marginalize" needs a Predictor made with missing="marginalize"')
+        return 1
+
+    def _with_gaps(self, on, run):
+        """run() with DPMM_OPT_TYPICALITY_GAPS set for its duration (the option is never touched by a default call)."""
+        if not on:
+            return run()
+        self._wk.set_option(binding.OPT_TYPICALITY_GAPS, 1)
+        try:
+            return run()
+        finally:
+            self._wk.set_option(binding.OPT_TYPICALITY_GAPS, 0)
+
+    def typicality(self, data, gaps="incomplete"):
         """How typical every point is of the cluster it is given: a `Typicality` tuple, computed on the GPU.
 
           labels        (n,) int64, 1-based: bit-identical to `predict_labels(data)`;
@@ -322,14 +345,22 @@ class Predictor:
                         q == 0 gives exactly 1; tails below the smallest normal Float32 may come back as 0;
           skipped       points whose row of the table holds a NaN or no finite entry (the rule of `overlap` and `statistics`);
           incomplete    points that are not skipped but have a feature that is not finite: under missing="marginalize" a point with
-                        gaps is labelled, but q is not marginalised here (out of scope).
+                        gaps is labelled, but with gaps="incomplete" (the default) q is not marginalised.
         Skipped and incomplete points have mahalanobis = tail = NaN.  NIW only: the Multinomial predictive has no closed-form tail.
+        gaps="marginalize" (a Predictor made with missing="marginalize" only, else ValueError): a point with 1 .. min(16, D - 1) NaN
+        features whose observed features are finite is SCORED under the marginal t_df(m_O, Sigma_OO) of its cluster over the r features O
+        it has: mahalanobis is q_o = z_O' (Sigma_OO)^-1 z_O -- the squared residual of the small system that gave the point its table entry,
+        Float64 rounded once -- and tail is I_{df / (df + q_o)}(df / 2, (D - r) / 2), uniform on (0, 1) as for a complete point.  (Imputing
+        first and scoring the filled point gives the same q but judges it with D degrees of freedom: every such point looks more typical
+        than it is.)  `incomplete` then counts only the points still not scored -- an observed feature that is not finite; points with more
+        gaps stay skipped.  Complete points keep their bits; `statistics`, `absorb`, `held_out`, `grow` and `min_tail` never marginalise.
         `data` is what `predict` takes; for a device tensor the three arrays are tensors on its device, written there by the library,
         nothing of size n crossing the host link.  No result depends on `capacity` or the table budget, to the bit."""
         if self._wk is None:
             raise RuntimeError("this Predictor is closed")
         if self.kind != _priors.PRIOR_NIW:
             raise ValueError("typicality is for the NIW prior: the Multinomial predictive has no closed-form tail")
+        on = self._gaps_option(gaps, "typicality")
         wk = self._wk
         if not hasattr(wk, "typicality_points_into"):
             raise RuntimeError("this Predictor's worker cannot score typicality (no dpmm_typicality_points)")
@@ -345,11 +376,12 @@ class Predictor:
                     sk -= self.capacity - (hi - lo)
             total[0] += sk
             total[1] += inc
-        out = self._walk(self._open(data), [("labels", (), "int64"), ("mahalanobis", (), "float32"), ("tail", (), "float32")], evaluate)
+        spec = [("labels", (), "int64"), ("mahalanobis", (), "float32"), ("tail", (), "float32")]
+        out = self._with_gaps(on, lambda: self._walk(self._open(data), spec, evaluate))
         return Typicality(out["labels"], out["mahalanobis"], out["tail"], total[0], total[1])
 
     # ---- per-feature explanations (include/dpmm_hip_explain.h)
-    def explain(self, data, top=None):
+    def explain(self, data, top=None, gaps="incomplete"):
         """WHICH features make a point atypical of the cluster it is given: an `Explanation` tuple, computed on the GPU.
 
         `typicality` says that a point is far out; the first question then is which features are off.  A per-feature marginal z-score
@@ -367,7 +399,12 @@ class Predictor:
         as `impute` returns) and features is None.
         top=m, 1 <= m <= min(D, 16): the three arrays are (n, m), the layout of `predict_topk`, and features (n, m) int32 holds the 0-based
         m features of largest |zscore|, largest first, ties to the lower index, a NaN zscore last; nothing of size D n is formed.
-        Skipped and incomplete points (see `typicality`: gaps are not marginalised here) have NaN in the three arrays and -1 in features.
+        Skipped and incomplete points (see `typicality`) have NaN in the three arrays and -1 in features.
+        gaps="marginalize" (see `typicality`): a point with r gaps is explained under the marginal over its D_o = D - r observed features O.
+        With P = (Sigma_OO)^-1 = A_OO - A_OM A_MM^-1 A_MO, g' = P z_O and q_o = mahalanobis: residual = g'_d / P_dd is x_d minus its
+        expectation given the OTHER OBSERVED features, zscore = g'_d sqrt((df + D_o - 1) / (P_dd (df + q_o - g'_d^2 / P_dd))) a Student-t
+        variable with df + D_o - 1 degrees of freedom and feature_tail its two-sided tail.  A missing feature has NaN in the three arrays
+        (top=None) or, ranked last, NaN and -1 in features (top=m > D_o).
         Float32 arithmetic from the Float32 x, m, R the worker holds; include/dpmm_hip_explain.h states the error bounds.  With a
         projection, D and the feature indices are those of the PROJECTED space (the coordinates `Projection.transform` gives), not the
         source features.  NIW only.  `data` is what `predict` takes; for a device tensor every array is a tensor on its device, written
@@ -381,6 +418,7 @@ class Predictor:
             m = int(top)
             if m != top or not 1 <= m <= min(self.D, binding.EXPLAIN_MAX_TOP):
                 raise ValueError(f"top must be None or an integer in 1..{min(self.D, binding.EXPLAIN_MAX_TOP)}")
+        on = self._gaps_option(gaps, "explain")
         wk = self._wk
         if not hasattr(wk, "explain_points_into"):
             raise RuntimeError("this Predictor's worker cannot explain points (no dpmm_explain_points)")
@@ -398,7 +436,7 @@ class Predictor:
         width = (m or self.D,)
         spec = [("labels", (), "int64"), ("mahalanobis", (), "float32"), ("tail", (), "float32"), ("residual", width, "float32"),
                 ("zscore", width, "float32"), ("feature_tail", width, "float32")] + ([("features", width, "int32")] if m else [])
-        out = self._walk(self._open(data), spec, evaluate)
+        out = self._with_gaps(on, lambda: self._walk(self._open(data), spec, evaluate))
         rows = [out[name] if m else out[name].T for name in ("residual", "zscore", "feature_tail")]
         return Explanation(out["labels"], out["mahalanobis"], out["tail"], rows[0], rows[1], rows[2], out["features"] if m else None, total[0], total[1])
 
@@ -1142,16 +1180,18 @@ def exemplars(dp_model, data, m, **kw):
 
 def typicality(dp_model, data, **kw):
     """Labels, squared Mahalanobis distances and their calibrated tails (opens a Predictor, runs, closes): see `Predictor.typicality`;
-    kw: capacity, device, worker_factory, missing."""
+    kw: gaps, capacity, device, worker_factory, missing."""
+    gaps = kw.pop("gaps", "incomplete")
     with Predictor(dp_model, **kw) as p:
-        return p.typicality(data)
+        return p.typicality(data, gaps=gaps)
 
 
 def explain(dp_model, data, top=None, **kw):
     """Per-feature conditional residuals, z-scores and tails of every point under its own cluster (opens a Predictor, runs, closes): see
-    `Predictor.explain`; kw: capacity, device, worker_factory, missing."""
+    `Predictor.explain`; kw: gaps, capacity, device, worker_factory, missing."""
+    gaps = kw.pop("gaps", "incomplete")
     with Predictor(dp_model, **kw) as p:
-        return p.explain(data, top=top)
+        return p.explain(data, top=top, gaps=gaps)
 
 
 def held_out(dp_model, data, **kw):

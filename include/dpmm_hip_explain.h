@@ -19,7 +19,33 @@
  *   feature_tail P(|T| >= |t_d|) for that Student-t: I_x(nu / 2, 1 / 2) at nu = df + D - 1, x = nu / (nu + t_d^2) -- the tail of
  *                dpmm_hip_typicality.h at D = 1.
  * At D = 1: t^2 = q and feature_tail = tail.  Skipped and incomplete points get NaN in residual, zscore and feature_tail and -1 in
- * features: an incomplete point's gaps are not marginalised here.
+ * features: without DPMM_OPT_TYPICALITY_GAPS an incomplete point's gaps are not marginalised ("Points with gaps" below).
+ *
+ * Points with gaps (DPMM_OPT_TYPICALITY_GAPS of dpmm_hip_typicality.h, whose "Points with gaps" defines M, O, D_o, C, t, res, P, q_o and says
+ * which points are scored).  For such a point the law of one observed feature d given the OTHER OBSERVED features is again a Student-t:
+ *   g'_d         = (P z_O)_d = (R' res)_d for d in O (on M, R' res = C' res = 0 by construction);
+ *   a'_d         = P_dd = A_dd - w_d' A_MM^-1 w_d, w_d[a] = (R' c_a)_d = A_{d, M_a}, c_a column M_a of R: A_dd - |L^-1 w_d|^2 with C'C = L L';
+ *   residual     g'_d / a'_d;   zscore  g'_d sqrt((df + D_o - 1) / (a'_d (df + max(q_o - g'_d^2 / a'_d, 0))));
+ *   feature_tail the two-sided tail of the z-score at df + D_o - 1 degrees of freedom, by the routine above.
+ * A feature of M has NaN in the three arrays; in top mode it ranks last (a NaN z-score) and its entry of `features` is -1.
+ * Arithmetic: res in Float64 as for q_o, ROUNDED TO FLOAT32, then g' as a chain of Float32 FMAs in increasing r; w_a likewise (Float32
+ * chains over the Float32 column); the forward substitution L v = w_d, |v|^2 and the subtraction from A_dd (the Float32 a_d above, widened)
+ * in Float64; the three formulas in Float64 from the Float32 g', q_o, df, each result rounded once to Float32.
+ * Error bounds (u = 2^-24, kappa = cond(A_MM), a_i over O, F = 2 r (D + 8 r + 16) 2^-52 kappa the Float64 term of dpmm_hip_typicality.h):
+ *   g'         |dres| <= |dy| <= (D + 2) u sqrt(a_i), the rounding of res adds u |res|, the chain gamma(D) sum_r |R_rd| |res_r|, and
+ *              sum_r |R_rd| |res_r| <= sqrt(A_dd) |res| <= sqrt(A_dd a_i):  |g'_d - exact| <= ((2 D + 3) u + F) sqrt(A_dd a_i) =: dg.
+ *   a'         every w_d[a] carries at most D u sqrt(A_dd A_{M_a M_a}), so |dw_d| <= D u sqrt(A_dd tr A_MM); |L^-1| = lambda_min(A_MM)^-1/2
+ *              and |v| <= sqrt(A_dd) give |d |v|^2| <= 2 D u A_dd sqrt(r kappa); the Float64 L is the factor of A_MM perturbed by at most
+ *              r (D + 12 r + 10) u64 |A_MM| (dpmm_hip_typicality.h), which moves |v|^2 = w' A_MM^-1 w by at most F A_dd, the substitution's
+ *              own Float64 roundings included; with the rounding of a_d:
+ *              |a'_d - exact| / a'_d <= (A_dd / a'_d) (u (1 + 2 D sqrt(r kappa)) + F) =: ra -- the cancellation in A_dd - |v|^2 is the factor
+ *              A_dd / a'_d.
+ *   residual   |e_d - exact| <= dg / a'_d + |e_d| (ra + u).
+ *   zscore     with dq the bound on q_o and h = df + q_o - g'_d^2 / a'_d, to first order
+ *              |t_d - exact| <= sqrt((df + D_o - 1) / (a'_d h)) dg + |t_d| ra / 2 + |t_d| / (2 h) (dq + 2 |g'_d| dg / a'_d + g'_d^2 / a'_d ra) + 2 u |t_d|;
+ *              twice that covers the second-order terms.
+ *   tail       as above, at df + D_o - 1.
+ * Out of scope: what dpmm_hip_typicality.h lists.
  *
  * Arithmetic.  z, y and q by the statements of dpmm_hip_typicality.h.  g_d as a chain of Float32 FMAs in increasing r.  a_d: the Float64 sum
  * of the squares of the Float32 R_rd, rounded once to Float32.  Then in Float32, every operation rounded once, divisions and square roots
