@@ -313,6 +313,13 @@ ABI_IMPUTE = [
     ("dpmm_impute_draw_points_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p] + _IMPUTE_DRAW_TAIL),
 ]
 IMPUTE_MAX_DRAWS = 1 << 26   # DPMM_IMPUTE_MAX_DRAWS
+# include/dpmm_hip_regress.h: mixture regression, the given features to the targets (additive; bound next to ABI)
+ABI_REGRESS = [
+    ("dpmm_set_regression", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _c_f64p, _c_f64p, _c_f64p, _c_f64p]),
+    ("dpmm_regress_points", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, _c_i64p]),
+    ("dpmm_regress_points_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, _c_i64p]),
+]
+REGRESS_MAX_TARGETS = 256    # DPMM_REGRESS_MAX_TARGETS
 
 HOST_ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int)   # dpmm_host_allreduce_fn
 
@@ -379,7 +386,7 @@ def load_library():
         except Exception:  # pragma: no cover  (torch is optional for single-GPU use)
             pass
         lib = ctypes.CDLL(p)
-        for name, res, args in ABI + ABI_TENSOR + ABI_SCORE + ABI_RANK + ABI_OVERLAP + ABI_BATCHSTATS + ABI_COUNTSTATS + ABI_TYPICALITY + ABI_EXPLAIN + ABI_HOLDOUT + ABI_COUNTHOLDOUT + ABI_TRACE + ABI_MISSING + ABI_IMPUTE + ABI_CSC + ABI_SAMPLE + ABI_PROJECT:
+        for name, res, args in ABI + ABI_TENSOR + ABI_SCORE + ABI_RANK + ABI_OVERLAP + ABI_BATCHSTATS + ABI_COUNTSTATS + ABI_TYPICALITY + ABI_EXPLAIN + ABI_HOLDOUT + ABI_COUNTHOLDOUT + ABI_TRACE + ABI_MISSING + ABI_IMPUTE + ABI_REGRESS + ABI_CSC + ABI_SAMPLE + ABI_PROJECT:
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -860,6 +867,36 @@ class Worker:
             assert out.dtype == np.float32 and (comp is None or comp.dtype == np.int32)
             fn, op, cp = self._lib.dpmm_impute_draw_points, _p(out, _c_f32p), comp.ctypes.data if comp is not None else None
         self._chk(fn(self._h, op, nd * w, w, ctypes.c_void_p(cp), ctypes.c_uint64(int(seed)), int(i0), int(draw0), nd))
+
+    # ---- mixture regression (include/dpmm_hip_regress.h)
+    def set_regression(self, B, c, V, h):
+        """dpmm_set_regression: the tables B (K, D_t, D), c (K, D_t), V (K, D_t), h (K,) in Float64 for the predictive parameters in force."""
+        B, c, V, h = (np.ascontiguousarray(a, np.float64) for a in (B, c, V, h))
+        K, Dt = c.shape
+        assert B.shape == (K, Dt, self.D) and V.shape == (K, Dt) and h.shape == (K,)
+        self._chk(self._lib.dpmm_set_regression(self._h, int(Dt), _p(B, _c_f64p), _p(c, _c_f64p), _p(V, _c_f64p), _p(h, _c_f64p)))
+        self._regress_Dt = int(Dt)
+
+    def regress_points_into(self, mean, std=None, labels=None):
+        """dpmm_regress_points[_device] into storage the caller made: mean and std C-contiguous (n, ld >= D_t) float32, labels (n,) int64
+        -- numpy arrays (host variant) or torch tensors on this worker's GPU (device variant); std and labels may be None.  Returns the
+        number of points that took no part."""
+        dev = hasattr(mean, "data_ptr")
+        outs = [a for a in (mean, std, labels) if a is not None]
+        assert all(hasattr(a, "data_ptr") == dev for a in outs), "regress_points_into: numpy arrays or tensors, not both"
+        assert all(int(a.shape[0]) == self.n and (a.is_contiguous() if dev else a.flags.c_contiguous) for a in outs)
+        assert std is None or tuple(std.shape) == tuple(mean.shape)
+        skipped = np.zeros(1, np.int64)
+        if dev:
+            import torch
+            assert mean.dtype == torch.float32 and (std is None or std.dtype == torch.float32) and (labels is None or labels.dtype == torch.int64)
+            torch.cuda.current_stream(mean.device).synchronize()
+            fn, ptr = self._lib.dpmm_regress_points_device, lambda a: None if a is None or a.numel() == 0 else ctypes.c_void_p(a.data_ptr())
+        else:
+            assert mean.dtype == np.float32 and (std is None or std.dtype == np.float32) and (labels is None or labels.dtype == np.int64)
+            fn, ptr = self._lib.dpmm_regress_points, lambda a: None if a is None or a.size == 0 else ctypes.c_void_p(a.ctypes.data)
+        self._chk(fn(self._h, ptr(mean), ptr(std), int(mean.shape[1]), ptr(labels), _p(skipped, _c_i64p)))
+        return int(skipped[0])
 
     # ---- exemplars (include/dpmm_hip_rank.h)
     def rank_begin(self, m, which=RANK_TYPICAL | RANK_FRINGE):

@@ -20,6 +20,7 @@
 #include "../../include/dpmm_hip_trace.h"
 #include "../../include/dpmm_hip_missing.h"
 #include "../../include/dpmm_hip_impute.h"
+#include "../../include/dpmm_hip_regress.h"
 #include "../../include/dpmm_hip_sample.h"
 #include "../../include/dpmm_hip_project.h"
 
@@ -224,6 +225,14 @@ struct dpmm_ctx {
     DevBuf<uint32_t> d_miss_list;
     DevBuf<unsigned long long> d_miss_cnt;
     bool miss_counted = false;         // the last table call marginalised: the counters hold its counts
+    // mixture regression (include/dpmm_hip_regress.h): the Float32 tables of dpmm_set_regression, made for the parameter set reg_gen (0: none);
+    // the per-tile counts of the points that take no part, of one range, allocated by the first dpmm_regress_points
+    int reg_Dt = 0;
+    bool reg_no_var = false;           // a cluster has df + D <= 2: no variance
+    unsigned long long reg_gen = 0;
+    DevBuf<float> d_reg_bt, d_reg_c, d_reg_v;
+    DevBuf<double> d_reg_hd;
+    DevBuf<unsigned> d_reg_skip;
     // drawing points (include/dpmm_hip_sample.h): the sampler's tables (dpmm_set_sampler_*) and what a call needs beside its outputs
     // (cluster and tile starts; sparse: 4 bytes per point of counts and the scan's tile totals), allocated on first use
     DevBuf<float> d_sm_m, d_sm_At, d_sm_df;
@@ -4215,6 +4224,123 @@ int dpmm_impute_draw_points(dpmm_ctx *c, float *out, int64_t ld, int64_t draw_st
 int dpmm_impute_draw_points_device(dpmm_ctx *c, float *d_out, int64_t ld, int64_t draw_stride, int32_t *d_comp, uint64_t seed, int64_t i0, int64_t draw0,
                                    int64_t ndraws) {
     return impute_draw_points(c, d_out, ld, draw_stride, d_comp, seed, i0, draw0, ndraws, true, "dpmm_impute_draw_points_device");
+}
+
+// ---- include/dpmm_hip_regress.h: the mixture of the clusters' conditional means and its spread, range by range (regress.hip) -------------
+int dpmm_set_regression(dpmm_ctx *c, int Dt, const double *B, const double *cc, const double *V, const double *h) {
+    static const char *fn = "dpmm_set_regression";
+    if (!c) return tensor_no_ctx(fn);
+    const std::string who = std::string(fn) + ": ";
+    if (c->prior != DPMM_PRIOR_NIW) return fail(c, DPMM_EINVAL, who + "the regression is that of the NIW prior's Student-t predictive");
+    if (Dt < 1 || Dt > DPMM_REGRESS_MAX_TARGETS) return fail(c, DPMM_EINVAL, who + "D_t must be in 1.." + std::to_string(DPMM_REGRESS_MAX_TARGETS));
+    if (!B || !cc || !V || !h) return fail(c, DPMM_EINVAL, who + "null table");
+    if (!c->predictive || c->h_miss_cst.size() != (size_t)c->K * MISS_CST) return fail(c, DPMM_ESTATE, who + "needs dpmm_set_predictive_niw first");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t K = (size_t)c->K, D = (size_t)c->D, Tp = (size_t)regress_pitch(Dt);
+    c->reg_gen = 0;      // (a failure below leaves no tables in force)
+    if (int rc = grow(c, c->d_reg_bt, sizeof(float) * K * D * Tp, fn, "regression matrices")) return rc;
+    if (int rc = grow(c, c->d_reg_c, sizeof(float) * K * Tp, fn, "regression offsets")) return rc;
+    if (int rc = grow(c, c->d_reg_v, sizeof(float) * K * Tp, fn, "regression variances")) return rc;
+    if (int rc = grow(c, c->d_reg_hd, sizeof(double) * 2 * K, fn, "regression constants")) return rc;
+    // each value rounded to Float32 once; B transposed to [K][D][Tp], zeros in the pad
+    std::vector<float> bt(K * D * Tp, 0.f), cv(K * Tp, 0.f), vv(K * Tp, 0.f);
+    std::vector<double> hd(2 * K);
+    bool no_var = false;
+    for (size_t k = 0; k < K; ++k) {
+        for (size_t d = 0; d < (size_t)Dt; ++d) {
+            for (size_t e = 0; e < D; ++e) bt[(k * D + e) * Tp + d] = (float)B[(k * (size_t)Dt + d) * D + e];
+            cv[k * Tp + d] = (float)cc[k * (size_t)Dt + d];
+            vv[k * Tp + d] = (float)V[k * (size_t)Dt + d];
+        }
+        hd[2 * k] = h[k];
+        hd[2 * k + 1] = c->h_miss_cst[k * MISS_CST];      // df_k, the Float32 value the table kernel reads, widened
+        if (!(hd[2 * k + 1] + (double)D > 2.0)) no_var = true;
+    }
+    HIPCHK(c, sync_stream(c, c->stream));
+    HIPCHK(c, hipMemcpy(c->d_reg_bt, bt.data(), sizeof(float) * bt.size(), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->d_reg_c, cv.data(), sizeof(float) * cv.size(), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->d_reg_v, vv.data(), sizeof(float) * vv.size(), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->d_reg_hd, hd.data(), sizeof(double) * hd.size(), hipMemcpyHostToDevice));
+    c->reg_Dt = Dt;
+    c->reg_no_var = no_var;
+    c->reg_gen = c->pred_gen;
+    return DPMM_OK;
+}
+
+static int regress_points(dpmm_ctx *c, float *mean, float *sd, int64_t ld, int64_t *labels, int64_t *skipped, bool device, const char *fn) {
+    if (!c) return tensor_no_ctx(fn);
+    c->miss_counted = false;      // (as score_points)
+    const std::string who = std::string(fn) + ": ";
+    if (c->prior != DPMM_PRIOR_NIW) return fail(c, DPMM_EINVAL, who + "the regression is that of the NIW prior's Student-t predictive");
+    if (!c->predictive) return fail(c, DPMM_ESTATE, who + "needs dpmm_set_predictive_niw first");
+    if (c->reg_gen == 0 || c->reg_gen != c->pred_gen) return fail(c, DPMM_ESTATE, who + "needs dpmm_set_regression for the predictive parameters in force");
+    const int64_t Dt = c->reg_Dt;
+    if (ld < Dt) return fail(c, DPMM_EINVAL, who + "ld < D_t");
+    if (ld >> 40) return fail(c, DPMM_EINVAL, who + "ld out of range");
+    if (sd && c->reg_no_var) return fail(c, DPMM_EINVAL, who + "a cluster has df + D <= 2: its conditional law has no variance");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (skipped) skipped[0] = 0;
+    if (c->n == 0) return DPMM_OK;
+    if (!c->have_points || !c->have_params || !c->dX) return fail(c, DPMM_ESTATE, who + "needs points and parameters");
+    if (!mean) return fail(c, DPMM_EINVAL, who + "mean is null");
+    const uint64_t n = (uint64_t)c->n;
+    if (device) {
+        if (int rc = check_device_extent(c, fn, "d_mean", mean, n * (uint64_t)ld * sizeof(float), sizeof(float))) return rc;
+        if (sd) if (int rc = check_device_extent(c, fn, "d_std", sd, n * (uint64_t)ld * sizeof(float), sizeof(float))) return rc;
+        if (labels) if (int rc = check_device_extent(c, fn, "d_labels", labels, n * sizeof(int64_t), sizeof(int64_t))) return rc;
+    }
+    TableWalk w;
+    if (int rc = walk_open(c, fn, WALK_MISS_NEVER, &w)) return rc;
+    const int64_t P = w.P;
+    const size_t tiles = (size_t)((P + 31) / 32);
+    if (int rc = grow(c, c->d_reg_skip, sizeof(unsigned) * tiles, fn, "counts of the regression pass")) return rc;
+    HIPCHK(c, hipMemsetAsync(c->d_reg_skip, 0, sizeof(unsigned) * tiles, c->stream));
+    // the rows: in the caller's device memory ld floats apart; staged (host variant) dense, D_t apart, and copied row by row
+    const int64_t sld = device ? ld : Dt;
+    OutStage<3> out{{{mean, sizeof(float) * (size_t)sld}, {sd, sizeof(float) * (size_t)sld}, {labels, sizeof(int64_t)}}, device};
+    if (!device) {
+        if (int rc = grow(c, c->d_score_out, out.layout((size_t)P), "dpmm_score_points", "staging of the outputs")) return rc;
+        out.buf = c->d_score_out;
+    }
+    if (int rc = walk_ranges(c, w, c->n, fn, [&](int64_t p0, int64_t np, int64_t) -> int {
+            RegressArgs a{};
+            a.table = c->d_score_table; a.stride = P; a.n = np; a.K = c->K; a.D = c->D; a.Dt = (int)Dt; a.Tp = regress_pitch((int)Dt);
+            a.X = c->dX + p0 * c->ldx; a.ldx = c->ldx;
+            a.Bt = c->d_reg_bt; a.c = c->d_reg_c; a.V = c->d_reg_v; a.hd = c->d_reg_hd;
+            a.mean = out.at<float>(0, p0); a.std = out.at<float>(1, p0); a.ld = sld; a.labels = out.at<int64_t>(2, p0); a.skip = c->d_reg_skip;
+            if (int rc = table_result(c, fn, launch_regress_range(a, c->stream))) return rc;
+            if (device) return DPMM_OK;
+            for (int j = 0; j < 2; ++j) {
+                float *dst = j == 0 ? mean : sd;
+                if (!dst) continue;
+                HIPCHK(c, hipMemcpy2DAsync(dst + p0 * ld, sizeof(float) * (size_t)ld, out.buf + out.col[j].off, sizeof(float) * (size_t)Dt, sizeof(float) * (size_t)Dt, (size_t)np,
+                                           hipMemcpyDeviceToHost, c->stream));
+            }
+            if (labels) HIPCHK(c, hipMemcpyAsync(labels + p0, out.buf + out.col[2].off, sizeof(int64_t) * (size_t)np, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, sync_stream(c, c->stream));      // the staging block is rewritten by the next range
+            if (ld > Dt)
+                for (int64_t i = p0; i < p0 + np; ++i) {
+                    memset(mean + i * ld + Dt, 0, sizeof(float) * (size_t)(ld - Dt));
+                    if (sd) memset(sd + i * ld + Dt, 0, sizeof(float) * (size_t)(ld - Dt));
+                }
+            return DPMM_OK;
+        })) return rc;
+    HIPCHK(c, sync_stream(c, c->stream));
+    if (skipped) {
+        std::vector<unsigned> cnt(tiles);
+        HIPCHK(c, hipMemcpy(cnt.data(), c->d_reg_skip, sizeof(unsigned) * tiles, hipMemcpyDeviceToHost));
+        int64_t total = 0;
+        for (unsigned v : cnt) total += v;
+        skipped[0] = total;
+    }
+    return DPMM_OK;
+}
+
+int dpmm_regress_points(dpmm_ctx *c, float *mean, float *std, int64_t ld, int64_t *labels, int64_t *skipped) {
+    return regress_points(c, mean, std, ld, labels, skipped, false, "dpmm_regress_points");
+}
+int dpmm_regress_points_device(dpmm_ctx *c, float *d_mean, float *d_std, int64_t ld, int64_t *d_labels, int64_t *skipped) {
+    return regress_points(c, d_mean, d_std, ld, d_labels, skipped, true, "dpmm_regress_points_device");
 }
 
 // ---- include/dpmm_hip_rank.h: exemplars, the m most and least typical points of every cluster (rank.hip) -----------------------------------

@@ -463,6 +463,26 @@ struct MissArgs {
 hipError_t launch_miss_transpose(const float *Rpk, int64_t step, float *Rt, int K, int D, hipStream_t s);      // Rpk: packed upper triangles, cluster k at Rpk + k * step
 hipError_t launch_miss_list(const MissArgs &a, hipStream_t s);
 hipError_t launch_miss_patch(const MissArgs &a, bool impute, int max_grid, hipStream_t s);
+// ---- mixture regression (regress.hip; include/dpmm_hip_regress.h): one range of the score table, n points from table column 0 and from X
+constexpr int REGRESS_MAX_TARGETS = 256;  // DPMM_REGRESS_MAX_TARGETS
+inline int regress_pitch(int Dt) { return 32 * ((Dt + 31) / 32); }
+struct RegressArgs {
+    const float *table;          // entry (k, i) at table[k * stride + i] (NIW: one row per cluster)
+    int64_t stride;
+    int64_t n;
+    int K, D;                    // D: the given features, the ctx's dimension
+    int Dt, Tp;                  // targets; Tp = regress_pitch(Dt)
+    const float *X;              // [n][ldx], the range's first point
+    int64_t ldx;
+    const float *Bt;             // [K][D][Tp]: Bt[k][e][d] = B_k[d][e], zero in the pad (d >= Dt)
+    const float *c, *V;          // [K][Tp], zero in the pad
+    const double *hd;            // [K][2]: h_k, df_k
+    float *mean, *std;           // [n][ld] rows of the range's points; std null: not asked for
+    int64_t ld;
+    int64_t *labels;             // [n] or null
+    unsigned *skip;              // [ceil(n / 32)] points of tile j that take no part, ADDED to word j
+};
+hipError_t launch_regress_range(const RegressArgs &a, hipStream_t s);
 // ---- calibrated outlier scores (typicality.hip; include/dpmm_hip_typicality.h): one range of the score table, n points from table column 0:
 // the label and the class of every point, q = |R_k (x - m_k)|^2 for its own cluster k in Float32, the tail of q in Float64
 struct TypicalityArgs {

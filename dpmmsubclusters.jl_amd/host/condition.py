@@ -1,0 +1,105 @@
+"""Conditioning a fitted NIW mixture on a fixed set of features, in Float64 on the host (include/dpmm_hip_regress.h serves the result).
+
+Two facts carry everything here.
+
+  * CLOSURE.  The marginal of an NIW posterior over a subset O of the features is an NIW posterior again.  With Psi = U U' (= nu psi, as
+    host/priors.py keeps it), D_o = |O|:
+        kappa' = kappa,   m' = m[O],   nu' = nu - (D - D_o),   Psi' = Psi[O, O] = U' U''  (U' upper triangular),
+        logdet_psi' = log det(Psi[O, O]) - D_o log nu'         (what `posterior()` calls logdet_psi: that of psi = Psi / nu).
+    Its Student-t predictive has nu' - D_o + 1 = nu - D + 1 degrees of freedom: the same as the full model's.  `niw_marginal` is that rule;
+    a Predictor made from its result scores, samples, absorbs and grows like any other.
+
+  * REGRESSION.  Cluster k's predictive is t_df(m, Sigma), Sigma^-1 = A = R'R.  Split into the targets M and the given features O:
+        E[x_M | x_O, k]   = m_M - (A_MM)^-1 A_MO (x_O - m_O)                      = c_k + B_k x_O
+        Cov[x_M | x_O, k] = (df + q) / (df + D_o - 2) (A_MM)^-1,   q = (x_O - m_O)' Sigma_OO^-1 (x_O - m_O)
+    (a conditional of a multivariate t is a multivariate t with df + D_o degrees of freedom).  `regression_tables` forms B, c, the
+    diagonal V of (A_MM)^-1 and the constant h of the marginal model's table entry, per cluster, by Cholesky of A_MM.
+"""
+import numpy as np
+from scipy.special import gammaln
+
+
+def check_features(features, D, what="features"):
+    """`features` as a list of distinct 0-based indices below D, 1 <= len <= D - 1; ValueError otherwise."""
+    try:
+        idx = [int(f) for f in features]
+        same = all(i == f for i, f in zip(idx, features))
+    except (TypeError, ValueError):
+        raise ValueError(f"{what} must be a list of feature indices") from None
+    if not same:
+        raise ValueError(f"{what} must be a list of integer feature indices")
+    if not 1 <= len(idx) <= D - 1:
+        raise ValueError(f"{what} must name between 1 and D - 1 = {D - 1} features")
+    if min(idx) < 0 or max(idx) >= D:
+        raise ValueError(f"{what} must lie in 0..{D - 1}")
+    if len(set(idx)) != len(idx):
+        raise ValueError(f"{what} must not repeat a feature")
+    return idx
+
+
+def upper_factor(A):
+    """Upper-triangular U with U U' = A for a batch of SPD matrices (n, d, d): the Cholesky factor of A with rows and columns reversed,
+    reversed back."""
+    A = np.asarray(A, np.float64)
+    L = np.linalg.cholesky(A[..., ::-1, ::-1])
+    return L[..., ::-1, ::-1]
+
+
+def niw_marginal(post, features):
+    """The NIW posterior arrays (kappa, nu, m, U, logdet_psi; any number of rows) of the features `features`, in that order."""
+    O = np.asarray(features, np.int64)
+    U = np.asarray(post["U"], np.float64)
+    D, Do = U.shape[-1], len(O)
+    Psi = np.einsum("nij,nkj->nik", U, U)[:, O[:, None], O[None, :]]
+    Uo = upper_factor(Psi)
+    nu = np.asarray(post["nu"], np.float64) - (D - Do)
+    logdet = 2.0 * np.log(np.einsum("nii->ni", Uo)).sum(1) - Do * np.log(nu)
+    return dict(kappa=np.array(post["kappa"], np.float64), nu=nu, m=np.asarray(post["m"], np.float64)[:, O].copy(), U=Uo, logdet_psi=logdet)
+
+
+def hyper_marginal(hyper, features):
+    """The hyper-parameters kappa, m, nu, psi (psi mean-like: the scale is nu psi) of the same features, by the same rule."""
+    O = np.asarray(features, np.int64)
+    psi = np.asarray(hyper["psi"], np.float64)
+    D, Do = psi.shape[0], len(O)
+    nu = float(hyper["nu"])
+    nu_o = nu - (D - Do)
+    return dict(kappa=np.float64(hyper["kappa"]), m=np.asarray(hyper["m"], np.float64).ravel()[O].copy(), nu=np.float64(nu_o),
+                psi=psi[O[:, None], O[None, :]] * (nu / nu_o))
+
+
+def table_constant(logdet, df, w, D):
+    """h_k = lgamma((df + D) / 2) - lgamma(df / 2) - D / 2 log(df pi) - logdet / 2 + log w: the x-independent part of the table entry
+    parr_ik = h_k - (df_k + D) / 2 log1p(q_ik / df_k) of a D-dimensional Student-t predictive."""
+    logdet, df, w = (np.asarray(a, np.float64) for a in (logdet, df, w))
+    return gammaln(0.5 * (df + D)) - gammaln(0.5 * df) - 0.5 * D * np.log(df * np.pi) - 0.5 * logdet + np.log(w)
+
+
+def regression_tables(m, R, given, targets):
+    """(B (K, D_t, D_o), c (K, D_t), V (K, D_t)) in Float64 from the predictive parameters m (K, D), R (K, D, D) or (K, D D) upper triangular
+    with Sigma^-1 = R'R, over the features of one model: `given` and `targets` index it, disjoint.  Features in neither are marginalised
+    away first -- the precision of the sub-model over given + targets is the inverse of that block of Sigma -- then, with A that precision,
+        B = -(A_MM)^-1 A_MO,   c = m_M - B m_O,   V = diag((A_MM)^-1)
+    by Cholesky of A_MM."""
+    m = np.asarray(m, np.float64)
+    K, D = m.shape
+    R = np.asarray(R, np.float64).reshape(K, D, D)
+    O, M = np.asarray(given, np.int64), np.asarray(targets, np.int64)
+    S = np.concatenate([O, M])
+    Do, Dt = len(O), len(M)
+    if len(S) == D:
+        A = np.einsum("kji,kjl->kil", R, R)[:, S[:, None], S[None, :]]
+    else:      # Sigma = R^-1 R^-T; its block over S, inverted
+        Ri = np.linalg.inv(R)
+        Sig = np.einsum("kij,klj->kil", Ri, Ri)[:, S[:, None], S[None, :]]
+        A = np.linalg.inv(Sig)
+        A = 0.5 * (A + A.transpose(0, 2, 1))
+    Amm, Amo = A[:, Do:, Do:], A[:, Do:, :Do]
+    L = np.linalg.cholesky(Amm)
+    Li = np.linalg.inv(L)                                   # lower triangular: (A_MM)^-1 = Li' Li
+    Ainv = np.einsum("kji,kjl->kil", Li, Li)
+    B = -np.einsum("kij,kjl->kil", Ainv, Amo)
+    c = m[:, M] - np.einsum("kij,kj->ki", B, m[:, O])
+    V = np.einsum("kii->ki", Ainv).copy()
+    assert B.shape == (K, Dt, Do)
+    return B, c, V

@@ -28,6 +28,7 @@ from . import priors as _priors
 from . import tensors as _tensors      # noqa: F401  (the recognisers of host/points.py, reachable from here: tests patch them under this name)
 from . import project as _project
 from . import absorb as _absorb
+from . import condition as _condition
 from .absorb import niw_absorb, niw_graft, dirichlet_absorb, dirichlet_graft      # noqa: F401
 
 
@@ -74,6 +75,10 @@ Growth.__doc__ = """What `Predictor.grow` returns: added, the number of clusters
 the 0-based positions in `data` of the points that went into them, increasing, and labels (kept,) int64, their new 1-based cluster ids
 (K_old + 1 ..) -- numpy arrays; dropped, the captured points that went nowhere (a value that is not finite, or a sub-cluster below
 min_points); total, the held-out points there were; model, the sub-fit's dp_model (None when nothing was fitted)."""
+
+Regression = collections.namedtuple("Regression", "mean std labels skipped")
+Regression.__doc__ = """What `Regressor.predict` returns: mean (D_t, n) float32, std the same or None, labels (n,) int64 1-based -- tensors on the
+data's device for a device tensor, else numpy arrays -- and skipped, an int: the points whose mean and std columns are NaN."""
 
 ASSIGN_MODES = {"hard": binding.BATCHSTATS_HARD, "soft": binding.BATCHSTATS_SOFT}
 
@@ -925,6 +930,30 @@ class Predictor:
         kept = new_id[lab - 1] > 0
         return Growth(len(keep), sizes[keep].astype(np.int64), index.cpu().numpy()[kept], new_id[lab - 1][kept], dropped, total, model)
 
+    # ---- a fixed split of the features (host/condition.py, include/dpmm_hip_regress.h)
+    def _refuse_conditioning(self, what):
+        if self.kind != _priors.PRIOR_NIW:
+            raise ValueError(f"{what} is for the NIW prior: a Multinomial model has no Gaussian marginals")
+        if self.projection is not None:
+            raise ValueError(f"{what} is refused for a model with a projection: its features are mixtures of the source features")
+
+    def marginal(self, features, capacity=None, worker_factory=None, missing=None):
+        """A new Predictor over exactly the features `features` (distinct 0-based indices, 1 <= len <= D - 1), in the order given: the
+        marginal of an NIW posterior is an NIW posterior (host/condition.py), so everything a Predictor serves works on it -- `absorb`,
+        `grow`, `save` and `load` included: the hyper-parameters are marginalised by the same rule.  capacity, device and `missing` are
+        this Predictor's unless given.  NIW only, no projection; ValueError before any worker is made."""
+        self._refuse_conditioning("marginal")
+        idx = _condition.check_features(features, self.D)
+        hyper = _condition.hyper_marginal(self.prior_hyper, idx) if self.prior_hyper is not None else None
+        new = Predictor.__new__(Predictor)
+        new._setup(self.kind, len(idx), self.alpha, self.points_count, _condition.niw_marginal(self.post, idx), capacity or self.capacity,
+                   self._device_arg, worker_factory, missing=missing or self.missing, prior_hyper=hyper)
+        return new
+
+    def regressor(self, given, targets=None, capacity=None, worker_factory=None):
+        """A `Regressor` from the features `given` to `targets` (default: every other feature): see the class."""
+        return Regressor(self, given, targets, capacity=capacity, worker_factory=worker_factory)
+
     # ---- missing features (include/dpmm_hip_missing.h)
     def impute(self, data, draws=None, seed=0, return_components=False):
         """(D, n) float32: `data` converted to Float32 with the NaN features of every point that has 1 .. min(16, D - 1) of them replaced
@@ -1156,6 +1185,108 @@ class Predictor:
     def _run(self, data, labels=False, logdens=False, m=0, probs=False):
         wk = self._wk
         return self._walk(self._open(data), self._spec(labels, logdens, m, probs), lambda views, lo, hi: wk.score_points_into(views, m=m))
+
+
+class Regressor:
+    """Regressor(predictor, given, targets=None): Gaussian-mixture regression from the features `given` to `targets` of a fitted NIW model
+    (include/dpmm_hip_regress.h).  `given` and `targets` are lists of distinct 0-based feature indices, disjoint; `targets` defaults to
+    every feature not in `given`; features in neither are marginalised away.  Use as a context manager or close().
+
+    `marginal` is `predictor.marginal(given)`, made with missing="propagate" whatever the parent's setting, owned and closed by the
+    Regressor.  The per-cluster tables B, c, V, h (host/condition.py) are formed in Float64 from the predictive parameters the marginal
+    worker is handed -- m, R, logdet, df, w as the Float32 values it receives -- over given + targets, and refreshed whenever the marginal
+    model's parameters change (`marginal.absorb`): the probabilities, h and df then follow the marginal model, while the conditional mean
+    function c + B x and V stay those of the joint model the Regressor was made from -- data of the given features alone says nothing
+    about the law of the targets given them."""
+
+    def __init__(self, predictor, given, targets=None, capacity=None, worker_factory=None):
+        predictor._refuse_conditioning("regressor")
+        D = predictor.D
+        self.given = _condition.check_features(given, D, "given")
+        if targets is None:
+            targets = [f for f in range(D) if f not in set(self.given)]
+        self.targets = _condition.check_features(targets, D, "targets")
+        if set(self.given) & set(self.targets):
+            raise ValueError("given and targets must be disjoint")
+        if len(self.targets) > binding.REGRESS_MAX_TARGETS:
+            raise ValueError(f"at most {binding.REGRESS_MAX_TARGETS} targets")
+        # the joint model over given + targets (the closure rule with D_o + D_t features: a permutation when nothing is left out)
+        self._sub_post = _condition.niw_marginal(predictor.post, self.given + self.targets)
+        self.D_o, self.D_t = len(self.given), len(self.targets)
+        self.marginal = predictor.marginal(self.given, capacity=capacity, worker_factory=worker_factory, missing="propagate")
+        self._tables_for = None
+        try:
+            self._refresh()
+        except Exception:
+            self.marginal.close()
+            raise
+
+    def tables(self):
+        """(B (K, D_t, D_o), c (K, D_t), V (K, D_t), h (K,), df (K,)) in Float64 for the model as it stands."""
+        mg = self.marginal
+        sub = Predictor.__new__(Predictor)      # only the conversion of host/priors.py is used: no worker
+        sub.kind, sub.D, sub.K, sub.post, sub.weights = mg.kind, self.D_o + self.D_t, mg.K, self._sub_post, mg.weights
+        f32 = lambda a: np.asarray(a, np.float32).astype(np.float64)      # noqa: E731  (what the worker receives)
+        m, R, _, _, _ = (f32(a) for a in sub._predictive_args()[1])
+        B, c, V = _condition.regression_tables(m, R, range(self.D_o), range(self.D_o, self.D_o + self.D_t))
+        _, _, logdet, df, w = (f32(a) for a in mg._predictive_args()[1])
+        return B, c, V, _condition.table_constant(logdet, df, w, self.D_o), df
+
+    def _refresh(self):
+        """The worker's tables are those of the marginal model's posterior as it stands (absorb replaces `post` and reloads the worker)."""
+        mg = self.marginal
+        if mg._wk is None:
+            raise RuntimeError("this Regressor is closed")
+        if self._tables_for is mg.post:
+            return
+        if not hasattr(mg._wk, "set_regression"):
+            raise RuntimeError("this Regressor's worker cannot regress (no dpmm_set_regression)")
+        B, c, V, h, df = self.tables()
+        self._no_var = bool(np.any(df + self.D_o <= 2))
+        mg._wk.set_regression(B, c, V, h)
+        self._tables_for = mg.post
+
+    def close(self):
+        self.marginal.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def predict(self, data, return_std=False):
+        """`Regression(mean, std, labels, skipped)` for `data` of D_o rows in the order of `given` (a caller holding the full table passes
+        X[given]); every input kind the marginal Predictor takes.  mean[d, i] = sum_k p_ik (c_k + B_k x_i)_d with the probabilities
+        `marginal.predict` returns; std (return_std=True) the root of the mixture's predictive variance per target; labels the marginal
+        model's.  A point with a NaN or no finite entry in its row of the table, or a feature that is not finite, takes no part: NaN
+        columns, counted in `skipped`."""
+        mg = self.marginal
+        self._refresh()
+        if return_std and self._no_var:
+            raise ValueError("return_std needs df + D_o > 2 for every cluster: a conditional law has no variance")
+        wk = mg._wk
+        spec = [("mean", (self.D_t,), "float32")] + ([("std", (self.D_t,), "float32")] if return_std else []) + [("labels", (), "int64")]
+        total = [0]
+
+        def evaluate(views, lo, hi):
+            sk = wk.regress_points_into(views["mean"], views.get("std"), views["labels"])
+            if hi - lo < mg.capacity:           # the padding of a short slab is zeros: points that take part, but if they did not, not ours
+                pad = views["mean"][hi - lo:]
+                bad = pad[:, 0] != pad[:, 0]
+                sk -= int(bad.sum())
+            total[0] += sk
+        out = mg._walk(mg._open(data), spec, evaluate)
+        return Regression(out["mean"].T, out["std"].T if return_std else None, out["labels"], total[0])
+
+
+def regress(dp_model, data, given, targets=None, return_std=False, **kw):
+    """Mixture regression from the features `given` to `targets` (opens a Predictor and its Regressor, runs, closes): see `Regressor`;
+    `data` has the rows of `given`; kw: capacity, device, worker_factory."""
+    factory = kw.pop("worker_factory", None)
+    with Predictor(dp_model, worker_factory=factory, **kw) as p:
+        with p.regressor(given, targets, worker_factory=factory) as r:
+            return r.predict(data, return_std=return_std)
 
 
 def score_samples(dp_model, data, **kw):
