@@ -365,6 +365,21 @@ def build_library(force=False):
 _LIB = None
 
 
+def _floor(v):
+    """A floor as the C calls take it: (in use?, its value), None for a floor that is not in use."""
+    return (0, 0.0) if v is None else (1, float(v))
+
+
+def _device_addresses(*dst):
+    """The device addresses (integers) of caller-owned destinations: torch tensors on the worker's GPU, addresses, or None (0)."""
+    for a in dst:
+        if hasattr(a, "data_ptr"):
+            import torch
+            torch.cuda.current_stream(a.device).synchronize()      # nothing queued on torch's stream still uses this memory
+            break
+    return [(a.data_ptr() if a.numel() else 0) if hasattr(a, "data_ptr") else int(a or 0) for a in dst]
+
+
 ABI_VERSION = 3      # DPMM_ABI_VERSION of include/dpmm_hip.h this file is written against
 
 
@@ -965,15 +980,13 @@ class Worker:
     def batchstats_begin(self, mode=BATCHSTATS_HARD, min_logdens=None):
         """dpmm_batchstats_begin: a new accumulation of N, sums, S and the counters with the weights of `mode`; min_logdens: None, or the
         floor below which a point is held out."""
-        floor = min_logdens is not None
-        self._chk(self._lib.dpmm_batchstats_begin(self._h, int(mode), int(floor), float(min_logdens) if floor else 0.0))
+        self._chk(self._lib.dpmm_batchstats_begin(self._h, int(mode), *_floor(min_logdens)))
         self._batchstats_K = self.K
 
     def batchstats_set_min_tail(self, min_tail=None):
         """dpmm_batchstats_set_min_tail (include/dpmm_hip_typicality.h), between batchstats_begin and the first batchstats_accumulate:
         min_tail in (0, 1], the tail below which a complete point is held out, or None for no such floor."""
-        use = min_tail is not None
-        self._chk(self._lib.dpmm_batchstats_set_min_tail(self._h, int(use), float(min_tail) if use else 0.0))
+        self._chk(self._lib.dpmm_batchstats_set_min_tail(self._h, *_floor(min_tail)))
 
     def batchstats_accumulate(self, n_valid):
         """dpmm_batchstats_accumulate: adds the points 0..n_valid-1 of the current upload."""
@@ -987,14 +1000,18 @@ class Worker:
     def batchstats_read(self):
         """The sums as they stand: a dict of numpy arrays, `N` (K,), `sums` (K, D), `S` (K, D, D) float64 (S[k] symmetric bit for bit),
         `count` (K,) int64 and `skipped`, `incomplete`, `held_out` (1,) int64."""
-        K = getattr(self, "_batchstats_K", None)
+        return self._stats_read("batchstats", dict(N=(), sums=(self.D,), S=(self.D, self.D)))
+
+    def _stats_read(self, family, sums):
+        """batchstats_read / countstats_read: `sums` names the family's float64 arrays and the shape of one cluster's part of each."""
+        K = getattr(self, f"_{family}_K", None)
+        raw = getattr(self, family + "_read_raw")
         if K is None:
-            self.batchstats_read_raw()         # (DPMM_ESTATE: no dpmm_batchstats_begin yet)
-            raise RuntimeError("batchstats_read needs batchstats_begin first")
-        D = self.D
-        res = dict(N=np.empty(K, np.float64), sums=np.empty((K, D), np.float64), S=np.empty((K, D, D), np.float64), count=np.empty(K, np.int64),
-                   skipped=np.empty(1, np.int64), incomplete=np.empty(1, np.int64), held_out=np.empty(1, np.int64))
-        self.batchstats_read_raw(**{k: v.ctypes.data for k, v in res.items()})
+            raw()                              # (DPMM_ESTATE: no dpmm_*_begin yet)
+            raise RuntimeError(f"{family}_read needs {family}_begin first")
+        res = {k: np.empty((K,) + per, np.float64) for k, per in sums.items()}
+        res.update(count=np.empty(K, np.int64), skipped=np.empty(1, np.int64), incomplete=np.empty(1, np.int64), held_out=np.empty(1, np.int64))
+        raw(**{k: v.ctypes.data for k, v in res.items()})
         return res
 
     # ---- held-out points (include/dpmm_hip_holdout.h)
@@ -1002,13 +1019,8 @@ class Worker:
         """dpmm_holdout_begin: a new collection of the points below the floor min_logdens and / or the tail floor min_tail (None: not in
         use) into dst_points [cap][D] float32 and dst_index [cap] int64 -- device addresses (integers) or torch tensors on this worker's
         GPU, which the caller keeps alive until holdout_read."""
-        floor, tail = min_logdens is not None, min_tail is not None
-        if hasattr(dst_points, "data_ptr"):
-            import torch
-            torch.cuda.current_stream(dst_points.device).synchronize()      # nothing queued on torch's stream still uses this memory
-        addr = [ctypes.c_void_p((a.data_ptr() if a.numel() else 0) if hasattr(a, "data_ptr") else int(a or 0)) for a in (dst_points, dst_index)]
-        self._chk(self._lib.dpmm_holdout_begin(self._h, int(floor), float(min_logdens) if floor else 0.0, int(tail), float(min_tail) if tail else 0.0,
-                                               addr[0], addr[1], int(cap)))
+        addr = [ctypes.c_void_p(a) for a in _device_addresses(dst_points, dst_index)]
+        self._chk(self._lib.dpmm_holdout_begin(self._h, *_floor(min_logdens), *_floor(min_tail), addr[0], addr[1], int(cap)))
 
     def holdout_accumulate(self, lo, n_valid):
         """dpmm_holdout_accumulate: classifies the points 0..n_valid-1 of the current upload, global indices lo + i, and appends the
@@ -1026,8 +1038,7 @@ class Worker:
     def countstats_begin(self, mode=BATCHSTATS_HARD, min_logdens=None):
         """dpmm_countstats_begin: a new accumulation of N, sums and the counters with the weights of `mode`; min_logdens: None, or the
         floor below which a point is held out."""
-        floor = min_logdens is not None
-        self._chk(self._lib.dpmm_countstats_begin(self._h, int(mode), int(floor), float(min_logdens) if floor else 0.0))
+        self._chk(self._lib.dpmm_countstats_begin(self._h, int(mode), *_floor(min_logdens)))
         self._countstats_K = self.K
 
     def countstats_accumulate(self, n_valid):
@@ -1042,41 +1053,23 @@ class Worker:
     def countstats_read(self):
         """The sums as they stand: a dict of numpy arrays, `N` (K,), `sums` (K, D) float64, `count` (K,) int64 and `skipped`,
         `incomplete`, `held_out` (1,) int64."""
-        K = getattr(self, "_countstats_K", None)
-        if K is None:
-            self.countstats_read_raw()         # (DPMM_ESTATE: no dpmm_countstats_begin yet)
-            raise RuntimeError("countstats_read needs countstats_begin first")
-        D = self.D
-        res = dict(N=np.empty(K, np.float64), sums=np.empty((K, D), np.float64), count=np.empty(K, np.int64),
-                   skipped=np.empty(1, np.int64), incomplete=np.empty(1, np.int64), held_out=np.empty(1, np.int64))
-        self.countstats_read_raw(**{k: v.ctypes.data for k, v in res.items()})
-        return res
+        return self._stats_read("countstats", dict(N=(), sums=(self.D,)))
 
     # ---- the floor per count and the held-out points of count data (include/dpmm_hip_countholdout.h)
     def countstats_set_per_count(self, min_logdens_per_count):
         """dpmm_countstats_set_per_count: the accumulation just begun also holds out the complete points whose log-density per count lies
         below `min_logdens_per_count` (None: switched off); between countstats_begin and the first countstats_accumulate."""
-        use = min_logdens_per_count is not None
-        self._chk(self._lib.dpmm_countstats_set_per_count(self._h, int(use), float(min_logdens_per_count) if use else 0.0))
+        self._chk(self._lib.dpmm_countstats_set_per_count(self._h, *_floor(min_logdens_per_count)))
 
     def countholdout_begin(self, dst, min_logdens=None, min_logdens_per_count=None):
         """dpmm_countholdout_begin: a new collection of the points below the floor min_logdens and / or the floor per count (None: not in
         use).  dst: None (count only) or a dict -- `cap`, `index` and either `points` [cap][D] float32 (dense stores) or `colptr` [cap + 1]
         int64, `rowval` [entry_cap] int32, `val` [entry_cap] float32 and `entry_cap` (sparse store) -- of device addresses (integers) or
         torch tensors on this worker's GPU, which the caller keeps alive until countholdout_read."""
-        floor, pc = min_logdens is not None, min_logdens_per_count is not None
         dst = dict(dst or {})
-        for a in dst.values():
-            if hasattr(a, "data_ptr"):
-                import torch
-                torch.cuda.current_stream(a.device).synchronize()      # nothing queued on torch's stream still uses this memory
-                break
-
-        def addr(a):
-            return (a.data_ptr() if a.numel() else 0) if hasattr(a, "data_ptr") else int(a or 0)
-        d = CountHoldoutDst(*[addr(dst.get(k)) or None for k in ("points", "colptr", "rowval", "val", "index")], int(dst.get("cap", 0)), int(dst.get("entry_cap", 0)))
-        self._chk(self._lib.dpmm_countholdout_begin(self._h, int(floor), float(min_logdens) if floor else 0.0, int(pc),
-                                                    float(min_logdens_per_count) if pc else 0.0, ctypes.byref(d)))
+        addr = _device_addresses(*[dst.get(k) for k in ("points", "colptr", "rowval", "val", "index")])
+        d = CountHoldoutDst(*[a or None for a in addr], int(dst.get("cap", 0)), int(dst.get("entry_cap", 0)))
+        self._chk(self._lib.dpmm_countholdout_begin(self._h, *_floor(min_logdens), *_floor(min_logdens_per_count), ctypes.byref(d)))
 
     def countholdout_accumulate(self, lo, n_valid):
         """dpmm_countholdout_accumulate: classifies the points 0..n_valid-1 of the current upload, global indices lo + i, and appends the

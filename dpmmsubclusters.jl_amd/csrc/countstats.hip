@@ -7,7 +7,7 @@
 // Launches per range, nothing in them waits for another workgroup:
 //   totals    only with the floor per count (dpmm_countstats_set_per_count), in front of prep by the caller: t_i, the Float64 total of every
 //             point's values, one wave per point, lanes strided over the entries and a fixed butterfly -- a function of the point alone.
-//   prep      the classification of countstats_device.h (cs_mark_gaps, cs_class -- shared with countholdout.hip), a workgroup per 256 points,
+//   prep      the classification of countstats_device.h (cs_mark_gaps, cs_class -- shared with holdout.hip), a workgroup per 256 points,
 //             one float2 per point: (M, S) in SOFT mode, (label, 1) in HARD mode, (0, 0) for a point that takes no part.  The scan for a
 //             value that is not finite goes over the live store: the workgroup's rows of X read flat; nothing for bytes; for sparse points
 //             the workgroup's entries cp[base] .. cp[base + rows] read flat, and the (rare) offender's column found by bisection in cp.

@@ -1,4 +1,4 @@
-// countstats_device.h -- what countstats_prep_kernel (countstats.hip) and countholdout_class_kernel (countholdout.hip) have in common: the
+// countstats_device.h -- what countstats_prep_kernel (countstats.hip) and countholdout_class_kernel (holdout.hip) have in common: the
 // scan of a workgroup's points for a value that is not finite, over whichever of the three point stores is live, and the class of a point
 // under the Multinomial model -- skipped, else held out, else incomplete, else it takes part -- with both floors, the raw one on logdens and
 // the one per count.  One rule, one piece of code: the counters of the two headers are equal because the same statements form them.

@@ -63,12 +63,15 @@ thread_local std::string g_create_error;
 int nb_for_dim(int D) { return D <= 16 ? 1 : D <= 32 ? 2 : D <= 64 ? 4 : D <= 128 ? 8 : 16; }
 }  // namespace
 
-// What the *_begin of an accumulation over the score table (overlap, batchstats, countstats) leaves for its _accumulate and _read calls
+// What the *_begin of an accumulation over the score table (overlap, batchstats, holdout, countstats, countholdout) leaves for its _accumulate and _read calls
 struct AccSession {
     bool active = false;
     int K = 0, mode = 0, floor = 0;      // K at the begin; the begin's arguments (overlap has none)
     float min_logdens = 0.f;
     unsigned long long gen = 0;          // pred_gen at the begin
+    int use2 = 0;                        // the second floor: the tail (NIW) or the log-density per count (Multinomial); the holdouts take it
+    float min2 = 0.f;                    // at their begin, the statistics by their set call, between the begin and the first _accumulate
+    bool accumulated = false;            // an _accumulate has run since the begin
 };
 
 struct dpmm_ctx {
@@ -167,9 +170,6 @@ struct dpmm_ctx {
     DevBuf<float> d_typ_q;
     DevBuf<unsigned long long> d_typ_cnt;
     DevBuf<float> d_bs_tail;
-    int bs_use_tail = 0;
-    float bs_min_tail = 0.f;
-    bool bs_accumulated = false;        // a dpmm_batchstats_accumulate has run since dpmm_batchstats_begin
     // per-feature explanations (include/dpmm_hip_explain.h): the row-major factors and the diagonals of R'R, allocated by the first explain
     // call and made from the parameter set exp_gen (0: none)
     DevBuf<float> d_exp_rr, d_exp_a;
@@ -180,8 +180,6 @@ struct dpmm_ctx {
     DevBuf<unsigned> d_ho_count;
     DevBuf<int64_t> d_ho_off;
     AccSession ho;
-    int ho_use_tail = 0;
-    float ho_min_tail = 0.f;
     float *ho_points = nullptr;
     int64_t *ho_index = nullptr;
     int64_t ho_cap = 0;
@@ -193,16 +191,11 @@ struct dpmm_ctx {
     // the floor per count (dpmm_countstats_set_per_count): the Float64 totals of the points of one range, allocated only when a floor per
     // count is in use and shared with the collection below
     DevBuf<double> d_cs_tot;
-    int cs_use_pc = 0;
-    float cs_min_pc = 0.f;
-    bool cs_accumulated = false;        // a dpmm_countstats_accumulate has run since dpmm_countstats_begin
     // held-out count points (include/dpmm_hip_countholdout.h): ballots, class counts and first slots go through d_ho_ballot / d_ho_count /
     // d_ho_off (a ctx has one prior); the workgroups' entry counts and first entry offsets; the running totals; the caller's destination
     DevBuf<unsigned long long> d_ch_ent, d_ch_state;
     DevBuf<int64_t> d_ch_eoff;
     AccSession ch;
-    int ch_use_pc = 0;
-    float ch_min_pc = 0.f;
     dpmm_countholdout_dst ch_dst = {nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0};
     // label trace (include/dpmm_hip_trace.h): slots rows of trace_nvec 16-byte vectors of ids; K per slot (0: never recorded); the device
     // images of a call's tables, descriptors, ratio tables and confidence
@@ -4439,11 +4432,69 @@ static int rank_read(dpmm_ctx *c, const dpmm_rank_out *o, bool device, const cha
 int dpmm_rank_read(dpmm_ctx *c, const dpmm_rank_out *out) { return rank_read(c, out, false, "dpmm_rank_read"); }
 int dpmm_rank_read_device(dpmm_ctx *c, const dpmm_rank_out *out) { return rank_read(c, out, true, "dpmm_rank_read_device"); }
 
-// ---- what the accumulations over the table share (overlap, batchstats, countstats): the session record and the replicated counters ---------
+// ---- what the accumulations over the table share (overlap, batchstats, holdout, countstats, countholdout): the session record, the fronts of
+// their _accumulate and _read calls, the second floor, the count data's point store and the replicated counters ---------------------------
 // an _accumulate call: its *_begin has run, and under the parameters in force now
 static int session_check(dpmm_ctx *c, const AccSession &s, const char *begin_name, const char *fn) {
     if (!s.active) return fail(c, DPMM_ESTATE, std::string(fn) + ": needs " + begin_name + " first");
     if (!c->predictive || c->K != s.K || c->pred_gen != s.gen) return fail(c, DPMM_ESTATE, std::string(fn) + ": the predictive parameters changed since " + begin_name);
+    return DPMM_OK;
+}
+// The live point store as the count kernels name it, and whether its buffers are there
+static int count_store(const dpmm_ctx *c) { return c->x_sparse ? COUNTSTATS_SPARSE : c->x_u8 ? COUNTSTATS_U8 : COUNTSTATS_F32; }
+static bool count_store_ready(const dpmm_ctx *c, int store) {
+    const bool have = store == COUNTSTATS_SPARSE ? (bool)c->d_cp : store == COUNTSTATS_U8 ? (bool)c->dX8 : (bool)c->dX;
+    return c->have_points && c->have_params && have && !(store == COUNTSTATS_SPARSE && c->nnz > 0 && (!c->d_ri || !c->d_val));
+}
+// ... and the points from p0 on, in the members every argument struct of the count kernels has (CountTotalsArgs reads no rows: no `ri`)
+extern "C++" {
+template <class Args> static auto count_rows(Args &a, const uint16_t *ri, int) -> decltype((void)(a.ri = ri)) { a.ri = ri; }
+template <class Args> static void count_rows(Args &, const uint16_t *, long) {}
+template <class Args>
+static void count_points(const dpmm_ctx *c, int store, int64_t p0, Args &a) {
+    a.store = store;
+    if (store == COUNTSTATS_SPARSE) { a.cp = c->d_cp + p0; count_rows(a, c->d_ri, 0); a.val = c->d_val; }
+    else if (store == COUNTSTATS_U8) { a.X8 = c->dX8 + p0 * c->ld8; a.ld8 = c->ld8; }
+    else { a.X = c->dX + p0 * c->ldx; a.ldx = c->ldx; }
+}
+}  // extern "C++"
+// The front of an _accumulate call, in the order the headers state: session, n_valid, lo (the calls that take one), device, nothing to do
+// (*empty), points and parameters.  What a call checks beyond these follows at its own place.
+enum AccPoints { ACC_POINTS, ACC_DENSE, ACC_COUNTS };      // the points it reads: through the table only | the Float32 matrix | the live count store
+static int acc_front(dpmm_ctx *c, AccSession dpmm_ctx::*session, const char *begin_name, const char *fn, int64_t n_valid, const int64_t *lo, AccPoints need,
+                     bool *empty) {
+    if (!c) return tensor_no_ctx(fn);
+    c->miss_counted = false;      // (as score_points)
+    const std::string who = std::string(fn) + ": ";
+    if (int rc = session_check(c, c->*session, begin_name, fn)) return rc;
+    if (n_valid < 0 || n_valid > c->n) return fail(c, DPMM_EINVAL, who + "n_valid must be in 0..n_local");
+    if (lo && (*lo < 0 || *lo > ((int64_t)1 << 62) - n_valid)) return fail(c, DPMM_EINVAL, who + "global indices must lie in 0..2^62");
+    HIPCHK(c, hipSetDevice(c->device));
+    *empty = n_valid == 0;
+    if (*empty) return DPMM_OK;
+    const bool ready = need == ACC_COUNTS ? count_store_ready(c, count_store(c)) : c->have_points && c->have_params && (need == ACC_POINTS || c->dX);
+    if (!ready) return fail(c, DPMM_ESTATE, who + "needs points and parameters");
+    return DPMM_OK;
+}
+// The front of a _read call
+static int read_front(dpmm_ctx *c, AccSession dpmm_ctx::*session, const char *begin_name, const char *fn, const void *out) {
+    if (!c) return tensor_no_ctx(fn);
+    const std::string who = std::string(fn) + ": ";
+    if (!out) return fail(c, DPMM_EINVAL, who + "out is null");
+    if (!(c->*session).active) return fail(c, DPMM_ESTATE, who + "needs " + begin_name + " first");
+    HIPCHK(c, hipSetDevice(c->device));
+    return DPMM_OK;
+}
+// The second floor of the statistics just begun (`family`: dpmm_batchstats / dpmm_countstats); `bad`: what is wrong with the value, or null
+static int set_second_floor(dpmm_ctx *c, AccSession dpmm_ctx::*session, const std::string &family, const char *fn, int use, float v, const char *bad) {
+    if (!c) return tensor_no_ctx(fn);
+    const std::string who = std::string(fn) + ": ";
+    AccSession &s = c->*session;
+    if (!s.active) return fail(c, DPMM_ESTATE, who + "needs " + family + "_begin first");
+    if (s.accumulated) return fail(c, DPMM_ESTATE, who + "belongs between " + family + "_begin and the first " + family + "_accumulate");
+    if (use && bad) return fail(c, DPMM_EINVAL, who + bad);
+    s.use2 = use ? 1 : 0;
+    s.min2 = use ? v : 0.f;
     return DPMM_OK;
 }
 // counter k of RANK_REPL replicas, `stride` words apart (a workgroup adds to one replica)
@@ -4452,6 +4503,7 @@ static int64_t fold_replicated(const std::vector<unsigned long long> &cnt, size_
     for (int r = 0; r < RANK_REPL; ++r) v += cnt[(size_t)r * stride + k];
     return (int64_t)v;
 }
+static const char *const RANGE_TOO_LONG = "a range of the table must hold fewer than 2^31 points: lower DPMM_OPT_SCORE_TABLE_MB";
 
 // ---- include/dpmm_hip_overlap.h: the posterior overlap of the clusters, sum_i p_ik p_ij (overlap.hip) --------------------------------------
 static size_t overlap_acc_doubles(int K) { return (size_t)K * (size_t)K + (size_t)K; }
@@ -4482,14 +4534,10 @@ int dpmm_overlap_begin(dpmm_ctx *c) {
 
 int dpmm_overlap_accumulate(dpmm_ctx *c, int64_t n_valid) {
     static const char *fn = "dpmm_overlap_accumulate";
-    if (!c) return tensor_no_ctx(fn);
-    c->miss_counted = false;      // (as score_points)
+    bool empty = false;
+    if (int rc = acc_front(c, &dpmm_ctx::ov, "dpmm_overlap_begin", fn, n_valid, nullptr, ACC_POINTS, &empty)) return rc;
+    if (empty) return DPMM_OK;
     const std::string who = std::string(fn) + ": ";
-    if (int rc = session_check(c, c->ov, "dpmm_overlap_begin", fn)) return rc;
-    if (n_valid < 0 || n_valid > c->n) return fail(c, DPMM_EINVAL, who + "n_valid must be in 0..n_local");
-    HIPCHK(c, hipSetDevice(c->device));
-    if (n_valid == 0) return DPMM_OK;
-    if (!c->have_points || !c->have_params) return fail(c, DPMM_ESTATE, who + "needs points and parameters");
     TableWalk w;
     if (int rc = walk_open(c, fn, WALK_MISS_OPTION, &w, [&](int64_t P) {
             return grow(c, c->d_ov_ms, sizeof(float2) * (size_t)P, "dpmm_score_points", "maxima and sums of dpmm_overlap_accumulate");
@@ -4512,11 +4560,7 @@ int dpmm_overlap_accumulate(dpmm_ctx *c, int64_t n_valid) {
 
 int dpmm_overlap_read(dpmm_ctx *c, const dpmm_overlap_out *o) {
     static const char *fn = "dpmm_overlap_read";
-    if (!c) return tensor_no_ctx(fn);
-    const std::string who = std::string(fn) + ": ";
-    if (!o) return fail(c, DPMM_EINVAL, who + "out is null");
-    if (!c->ov.active) return fail(c, DPMM_ESTATE, who + "needs dpmm_overlap_begin first");
-    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = read_front(c, &dpmm_ctx::ov, "dpmm_overlap_begin", fn, o)) return rc;
     const int K = c->ov.K;
     const size_t kk = (size_t)K * (size_t)K;
     std::vector<unsigned long long> cnt(rank_count_words(K));
@@ -4524,7 +4568,7 @@ int dpmm_overlap_read(dpmm_ctx *c, const dpmm_overlap_out *o) {
     if (e == hipSuccess && o->overlap) e = hipMemcpy(o->overlap, c->d_ov_acc, sizeof(double) * kk, hipMemcpyDeviceToHost);
     if (e == hipSuccess && o->mass) e = hipMemcpy(o->mass, c->d_ov_acc + kk, sizeof(double) * (size_t)K, hipMemcpyDeviceToHost);
     if (e == hipSuccess && (o->count || o->skipped)) e = hipMemcpy(cnt.data(), c->d_ov_acc + overlap_acc_doubles(K), sizeof(unsigned long long) * cnt.size(), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) { c->err = who + hipGetErrorString(e); return DPMM_EHIP; }
+    if (e != hipSuccess) { c->err = std::string(fn) + ": " + hipGetErrorString(e); return DPMM_EHIP; }
     if (o->count) for (int k = 0; k < K; ++k) o->count[k] = fold_replicated(cnt, (size_t)K + 1, (size_t)k);
     if (o->skipped) o->skipped[0] = fold_replicated(cnt, (size_t)K + 1, (size_t)K);
     return DPMM_OK;
@@ -4555,9 +4599,15 @@ static size_t batchstats_part_doubles(int64_t len, int K, int D, size_t *off_s, 
     batchstats_chunks(len, K, D, &kg, &nchunk, &chunk);
     const size_t most = (size_t)std::max(1, BATCHSTATS_PARTIAL_BLOCKS / (kg * npairs));
     const size_t ck = std::min<size_t>(most, (size_t)std::max<int64_t>(1, (len + 2047) / 2048)) * (size_t)kg;      // (chunks, cluster) at most
-    if (off_s) *off_s = ck * (size_t)npairs * 4096;
-    if (off_n) *off_n = ck * (size_t)npairs * 4096 + ck * (size_t)nb * 64;
+    *off_s = ck * (size_t)npairs * 4096;
+    *off_n = ck * (size_t)npairs * 4096 + ck * (size_t)nb * 64;
     return ck * ((size_t)npairs * 4096 + (size_t)nb * 64 + 1);
+}
+// one range of P points: its two floats per point and its chunk partials, grown; the offsets of the partials' parts
+static int batchstats_range_buffers(dpmm_ctx *c, int64_t P, size_t *off_s, size_t *off_n) {
+    const size_t part = sizeof(double) * batchstats_part_doubles(std::min<int64_t>(P, c->n), c->K, c->D, off_s, off_n);
+    if (int rc = grow(c, c->d_bs_ms, sizeof(float2) * (size_t)P, "dpmm_score_points", "maxima and sums of the batch statistics")) return rc;
+    return grow(c, c->d_bs_part, part, "dpmm_score_points", "chunk partials of the batch statistics");
 }
 
 int dpmm_batchstats_begin(dpmm_ctx *c, int mode, int use_floor, float min_logdens) {
@@ -4575,61 +4625,46 @@ int dpmm_batchstats_begin(dpmm_ctx *c, int mode, int use_floor, float min_logden
     if (c->n > 0) {      // one range's floats and partials: sized as dpmm_batchstats_accumulate will find them unless the table budget changes in between
         int rstep = 0;
         int64_t P = 0;
+        size_t off_s = 0, off_n = 0;
         if (int rc = score_table_slab(c, &rstep, &P)) return rc;
-        if (int rc = grow(c, c->d_bs_ms, sizeof(float2) * (size_t)P, "dpmm_score_points", "maxima and sums of dpmm_batchstats_begin")) return rc;
-        const size_t part = sizeof(double) * batchstats_part_doubles(std::min<int64_t>(P, c->n), K, D, nullptr, nullptr);
-        if (int rc = grow(c, c->d_bs_part, part, "dpmm_score_points", "chunk partials of dpmm_batchstats_begin")) return rc;
+        if (int rc = batchstats_range_buffers(c, P, &off_s, &off_n)) return rc;
     }
     HIPCHK(c, hipMemsetAsync(c->d_bs_acc, 0, state, c->stream));
     c->bs = AccSession{true, K, mode, use_floor ? 1 : 0, min_logdens, c->pred_gen};
-    c->bs_use_tail = 0; c->bs_min_tail = 0.f; c->bs_accumulated = false;
     return DPMM_OK;
 }
 
 // include/dpmm_hip_typicality.h: the calibrated floor of the accumulation just begun
 int dpmm_batchstats_set_min_tail(dpmm_ctx *c, int use, float min_tail) {
-    static const char *fn = "dpmm_batchstats_set_min_tail";
-    if (!c) return tensor_no_ctx(fn);
-    const std::string who = std::string(fn) + ": ";
-    if (!c->bs.active) return fail(c, DPMM_ESTATE, who + "needs dpmm_batchstats_begin first");
-    if (c->bs_accumulated) return fail(c, DPMM_ESTATE, who + "belongs between dpmm_batchstats_begin and the first dpmm_batchstats_accumulate");
-    if (use && !(min_tail > 0.f && min_tail <= 1.f)) return fail(c, DPMM_EINVAL, who + "min_tail must lie in (0, 1]");
-    c->bs_use_tail = use ? 1 : 0;
-    c->bs_min_tail = use ? min_tail : 0.f;
-    return DPMM_OK;
+    return set_second_floor(c, &dpmm_ctx::bs, "dpmm_batchstats", "dpmm_batchstats_set_min_tail", use, min_tail,
+                            min_tail > 0.f && min_tail <= 1.f ? nullptr : "min_tail must lie in (0, 1]");
 }
 
 int dpmm_batchstats_accumulate(dpmm_ctx *c, int64_t n_valid) {
     static const char *fn = "dpmm_batchstats_accumulate";
-    if (!c) return tensor_no_ctx(fn);
-    c->miss_counted = false;      // (as score_points)
+    bool empty = false;
+    if (int rc = acc_front(c, &dpmm_ctx::bs, "dpmm_batchstats_begin", fn, n_valid, nullptr, ACC_DENSE, &empty)) return rc;
+    if (empty) return DPMM_OK;
     const std::string who = std::string(fn) + ": ";
-    if (int rc = session_check(c, c->bs, "dpmm_batchstats_begin", fn)) return rc;
-    if (n_valid < 0 || n_valid > c->n) return fail(c, DPMM_EINVAL, who + "n_valid must be in 0..n_local");
-    HIPCHK(c, hipSetDevice(c->device));
-    if (n_valid == 0) return DPMM_OK;
-    if (!c->have_points || !c->have_params || !c->dX) return fail(c, DPMM_ESTATE, who + "needs points and parameters");
     const int K = c->K, D = c->D;
     size_t off_s = 0, off_n = 0;
     TableWalk w;
     if (int rc = walk_open(c, fn, WALK_MISS_OPTION, &w, [&](int64_t P) -> int {
-            if (P >> 31) return fail(c, DPMM_EINVAL, who + "a range of the table must hold fewer than 2^31 points: lower DPMM_OPT_SCORE_TABLE_MB");
-            const size_t part = sizeof(double) * batchstats_part_doubles(std::min<int64_t>(P, c->n), K, D, &off_s, &off_n);
-            if (int rc = grow(c, c->d_bs_ms, sizeof(float2) * (size_t)P, "dpmm_score_points", "maxima and sums of dpmm_batchstats_accumulate")) return rc;
-            return grow(c, c->d_bs_part, part, "dpmm_score_points", "chunk partials of dpmm_batchstats_accumulate");
+            if (P >> 31) return fail(c, DPMM_EINVAL, who + RANGE_TOO_LONG);
+            return batchstats_range_buffers(c, P, &off_s, &off_n);
         })) return rc;
-    if (c->bs_use_tail) {
+    if (c->bs.use2) {
         if (int rc = grow(c, c->d_bs_tail, sizeof(float) * (size_t)w.P, "dpmm_score_points", "tails of dpmm_batchstats_accumulate")) return rc;
         if (int rc = typ_begin(c, w.P, fn)) return rc;
     }
-    c->bs_accumulated = true;
+    c->bs.accumulated = true;
     return walk_ranges(c, w, n_valid, fn, [&](int64_t p0, int64_t, int64_t nv) -> int {
-        if (c->bs_use_tail) if (int rc = typ_range(c, w.P, p0, nv, nullptr, nullptr, c->d_bs_tail, fn)) return rc;
+        if (c->bs.use2) if (int rc = typ_range(c, w.P, p0, nv, nullptr, nullptr, c->d_bs_tail, fn)) return rc;
         BatchStatsArgs a{};
         a.table = c->d_score_table; a.stride = w.P; a.rstep = w.rstep; a.n = nv; a.K = K; a.D = D; a.nb = (D + 63) / 64;
         a.X = c->dX + p0 * c->ldx; a.ldx = c->ldx;
         a.soft = c->bs.mode == DPMM_BATCHSTATS_SOFT; a.use_floor = c->bs.floor; a.min_logdens = c->bs.min_logdens;
-        a.use_tail = c->bs_use_tail; a.min_tail = c->bs_min_tail; a.tail = c->bs_use_tail ? c->d_bs_tail.get() : nullptr;
+        a.use_tail = c->bs.use2; a.min_tail = c->bs.min2; a.tail = c->bs.use2 ? c->d_bs_tail.get() : nullptr;
         batchstats_chunks(a.n, K, D, &a.kgroup, &a.nchunk, &a.chunk);
         if ((size_t)a.nchunk * (size_t)std::min(a.kgroup, K) * (size_t)(a.nb * (a.nb + 1) / 2) * 4096 > off_s)
             return fail(c, DPMM_EHIP, who + "internal: more chunks than the partial buffer holds");
@@ -4645,11 +4680,7 @@ int dpmm_batchstats_accumulate(dpmm_ctx *c, int64_t n_valid) {
 
 int dpmm_batchstats_read(dpmm_ctx *c, const dpmm_batchstats_out *o) {
     static const char *fn = "dpmm_batchstats_read";
-    if (!c) return tensor_no_ctx(fn);
-    const std::string who = std::string(fn) + ": ";
-    if (!o) return fail(c, DPMM_EINVAL, who + "out is null");
-    if (!c->bs.active) return fail(c, DPMM_ESTATE, who + "needs dpmm_batchstats_begin first");
-    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = read_front(c, &dpmm_ctx::bs, "dpmm_batchstats_begin", fn, o)) return rc;
     const int K = c->bs.K;
     const size_t D = (size_t)c->D, Kz = (size_t)K;
     hipError_t e = sync_stream(c, c->stream);
@@ -4664,6 +4695,18 @@ static int holdout_check_dst(dpmm_ctx *c, const char *fn, float *points, int64_t
     if (cap <= 0) return DPMM_OK;
     if (int rc = check_device_extent(c, fn, "dst_points", points, (uint64_t)cap * (uint64_t)c->D * sizeof(float), sizeof(float))) return rc;
     return check_device_extent(c, fn, "dst_index", index, (uint64_t)cap * sizeof(int64_t), sizeof(int64_t));
+}
+// one range of P points: the ballots, class counts and first slots of its workgroups, grown; entries (count data): their entry counts and
+// first entry offsets too
+static int holdout_range_buffers(dpmm_ctx *c, int64_t P, bool entries) {
+    const size_t groups = (size_t)holdout_groups(std::min<int64_t>(P, c->n));
+    if (int rc = grow(c, c->d_ho_ballot, sizeof(unsigned long long) * groups * (HOLDOUT_THREADS / 64), "dpmm_score_points", "ballots of the held-out points")) return rc;
+    if (int rc = grow(c, c->d_ho_count, sizeof(unsigned) * groups * HOLDOUT_STATE, "dpmm_score_points", "workgroup counts of the held-out points")) return rc;
+    if (entries) {
+        if (int rc = grow(c, c->d_ch_ent, sizeof(unsigned long long) * groups, "dpmm_score_points", "workgroup entry counts of the held-out points")) return rc;
+        if (int rc = grow(c, c->d_ch_eoff, sizeof(int64_t) * groups, "dpmm_score_points", "workgroup entry offsets of the held-out points")) return rc;
+    }
+    return grow(c, c->d_ho_off, sizeof(int64_t) * groups, "dpmm_score_points", "workgroup slots of the held-out points");
 }
 
 int dpmm_holdout_begin(dpmm_ctx *c, int use_floor, float min_logdens, int use_tail, float min_tail, float *dst_points, int64_t *dst_index, int64_t cap) {
@@ -4680,43 +4723,34 @@ int dpmm_holdout_begin(dpmm_ctx *c, int use_floor, float min_logdens, int use_ta
     if (int rc = holdout_check_dst(c, fn, dst_points, dst_index, cap)) return rc;
     if (int rc = grow(c, c->d_ho_state, sizeof(unsigned long long) * HOLDOUT_STATE, "dpmm_score_points", "counters of dpmm_holdout_begin")) return rc;
     HIPCHK(c, hipMemsetAsync(c->d_ho_state, 0, sizeof(unsigned long long) * HOLDOUT_STATE, c->stream));
-    c->ho = AccSession{true, c->K, 0, use_floor ? 1 : 0, min_logdens, c->pred_gen};
-    c->ho_use_tail = use_tail ? 1 : 0; c->ho_min_tail = use_tail ? min_tail : 0.f;
+    c->ho = AccSession{true, c->K, 0, use_floor ? 1 : 0, min_logdens, c->pred_gen, use_tail ? 1 : 0, use_tail ? min_tail : 0.f};
     c->ho_points = dst_points; c->ho_index = dst_index; c->ho_cap = cap;
     return DPMM_OK;
 }
 
 int dpmm_holdout_accumulate(dpmm_ctx *c, int64_t lo, int64_t n_valid) {
     static const char *fn = "dpmm_holdout_accumulate";
-    if (!c) return tensor_no_ctx(fn);
-    c->miss_counted = false;      // (as score_points)
+    bool empty = false;
+    if (int rc = acc_front(c, &dpmm_ctx::ho, "dpmm_holdout_begin", fn, n_valid, &lo, ACC_DENSE, &empty)) return rc;
+    if (empty) return DPMM_OK;
     const std::string who = std::string(fn) + ": ";
-    if (int rc = session_check(c, c->ho, "dpmm_holdout_begin", fn)) return rc;
-    if (n_valid < 0 || n_valid > c->n) return fail(c, DPMM_EINVAL, who + "n_valid must be in 0..n_local");
-    if (lo < 0 || lo > ((int64_t)1 << 62) - n_valid) return fail(c, DPMM_EINVAL, who + "global indices must lie in 0..2^62");
-    HIPCHK(c, hipSetDevice(c->device));
-    if (n_valid == 0) return DPMM_OK;
-    if (!c->have_points || !c->have_params || !c->dX) return fail(c, DPMM_ESTATE, who + "needs points and parameters");
     if (int rc = holdout_check_dst(c, fn, c->ho_points, c->ho_index, c->ho_cap)) return rc;      // (the caller may have freed it since the begin)
     TableWalk w;
     if (int rc = walk_open(c, fn, WALK_MISS_OPTION, &w, [&](int64_t P) -> int {
-            if (P >> 31) return fail(c, DPMM_EINVAL, who + "a range of the table must hold fewer than 2^31 points: lower DPMM_OPT_SCORE_TABLE_MB");
-            const size_t groups = (size_t)holdout_groups(std::min<int64_t>(P, c->n));
-            if (int rc = grow(c, c->d_ho_ballot, sizeof(unsigned long long) * groups * (HOLDOUT_THREADS / 64), "dpmm_score_points", "ballots of dpmm_holdout_accumulate")) return rc;
-            if (int rc = grow(c, c->d_ho_count, sizeof(unsigned) * groups * HOLDOUT_STATE, "dpmm_score_points", "workgroup counts of dpmm_holdout_accumulate")) return rc;
-            return grow(c, c->d_ho_off, sizeof(int64_t) * groups, "dpmm_score_points", "workgroup slots of dpmm_holdout_accumulate");
+            if (P >> 31) return fail(c, DPMM_EINVAL, who + RANGE_TOO_LONG);
+            return holdout_range_buffers(c, P, false);
         })) return rc;
-    if (c->ho_use_tail) {
+    if (c->ho.use2) {
         if (int rc = grow(c, c->d_bs_tail, sizeof(float) * (size_t)w.P, "dpmm_score_points", "tails of dpmm_holdout_accumulate")) return rc;
         if (int rc = typ_begin(c, w.P, fn)) return rc;
     }
     return walk_ranges(c, w, n_valid, fn, [&](int64_t p0, int64_t, int64_t nv) -> int {
-        if (c->ho_use_tail) if (int rc = typ_range(c, w.P, p0, nv, nullptr, nullptr, c->d_bs_tail, fn)) return rc;
+        if (c->ho.use2) if (int rc = typ_range(c, w.P, p0, nv, nullptr, nullptr, c->d_bs_tail, fn)) return rc;
         HoldoutArgs a{};
         a.table = c->d_score_table; a.stride = w.P; a.rstep = w.rstep; a.n = nv; a.K = c->K; a.D = c->D;
         a.X = c->dX + p0 * c->ldx; a.ldx = c->ldx;
         a.use_floor = c->ho.floor; a.min_logdens = c->ho.min_logdens;
-        a.use_tail = c->ho_use_tail; a.min_tail = c->ho_min_tail; a.tail = c->ho_use_tail ? c->d_bs_tail.get() : nullptr;
+        a.use_tail = c->ho.use2; a.min_tail = c->ho.min2; a.tail = c->ho.use2 ? c->d_bs_tail.get() : nullptr;
         a.index0 = lo + p0;
         a.ballot = c->d_ho_ballot; a.wgcount = c->d_ho_count; a.wgoff = c->d_ho_off; a.state = c->d_ho_state;
         a.dst_points = c->ho_points; a.dst_index = c->ho_index; a.cap = c->ho_cap;
@@ -4726,11 +4760,7 @@ int dpmm_holdout_accumulate(dpmm_ctx *c, int64_t lo, int64_t n_valid) {
 
 int dpmm_holdout_read(dpmm_ctx *c, const dpmm_holdout_out *o) {
     static const char *fn = "dpmm_holdout_read";
-    if (!c) return tensor_no_ctx(fn);
-    const std::string who = std::string(fn) + ": ";
-    if (!o) return fail(c, DPMM_EINVAL, who + "out is null");
-    if (!c->ho.active) return fail(c, DPMM_ESTATE, who + "needs dpmm_holdout_begin first");
-    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = read_front(c, &dpmm_ctx::ho, "dpmm_holdout_begin", fn, o)) return rc;
     unsigned long long h[HOLDOUT_STATE] = {0, 0, 0, 0};
     hipError_t e = sync_stream(c, c->stream);
     if (e == hipSuccess) e = hipMemcpy(h, c->d_ho_state, sizeof(h), hipMemcpyDeviceToHost);
@@ -4745,12 +4775,14 @@ int dpmm_holdout_read(dpmm_ctx *c, const dpmm_holdout_out *o) {
 
 // ---- include/dpmm_hip_countstats.h: per-cluster count statistics of a batch under the Multinomial model, sum_i w_ik (1, x_i) (countstats.hip)
 static size_t countstats_acc_doubles(int K, int D) { return (size_t)K * ((size_t)D + 1); }
-// doubles of the chunk partials of a range of at most `len` points: rows of dp doubles | one weight per row
-static size_t countstats_part_doubles(const dpmm_ctx *c, int64_t len) {
+// one range of P points: its two floats per point and its chunk partials -- rows of dp doubles | one weight per row -- grown; the partials' bytes
+static int countstats_range_buffers(dpmm_ctx *c, int64_t P, size_t *part) {
     int kg = 0, nchunk = 0;
     int64_t chunk = 0, dp = 0;
-    countstats_chunks(len, c->K, c->D, c->x_sparse ? 1 : 0, &kg, &nchunk, &chunk, &dp);
-    return (size_t)nchunk * (size_t)kg * ((size_t)dp + 1);
+    countstats_chunks(std::min<int64_t>(P, c->n), c->K, c->D, c->x_sparse ? 1 : 0, &kg, &nchunk, &chunk, &dp);
+    *part = sizeof(double) * (size_t)nchunk * (size_t)kg * ((size_t)dp + 1);
+    if (int rc = grow(c, c->d_cs_ms, sizeof(float2) * (size_t)P, "dpmm_score_points", "maxima and sums of the count statistics")) return rc;
+    return grow(c, c->d_cs_part, *part, "dpmm_score_points", "chunk partials of the count statistics");
 }
 
 int dpmm_countstats_begin(dpmm_ctx *c, int mode, int use_floor, float min_logdens) {
@@ -4768,78 +4800,52 @@ int dpmm_countstats_begin(dpmm_ctx *c, int mode, int use_floor, float min_logden
     if (c->n > 0) {      // one range's floats and partials: sized as dpmm_countstats_accumulate will find them unless the table budget or the store changes in between
         int rstep = 0;
         int64_t P = 0;
+        size_t part = 0;
         if (int rc = score_table_slab(c, &rstep, &P)) return rc;
-        if (int rc = grow(c, c->d_cs_ms, sizeof(float2) * (size_t)P, "dpmm_score_points", "maxima and sums of dpmm_countstats_begin")) return rc;
-        const size_t part = sizeof(double) * countstats_part_doubles(c, std::min<int64_t>(P, c->n));
-        if (int rc = grow(c, c->d_cs_part, part, "dpmm_score_points", "chunk partials of dpmm_countstats_begin")) return rc;
+        if (int rc = countstats_range_buffers(c, P, &part)) return rc;
     }
     HIPCHK(c, hipMemsetAsync(c->d_cs_acc, 0, state, c->stream));
     c->cs = AccSession{true, K, mode, use_floor ? 1 : 0, min_logdens, c->pred_gen};
-    c->cs_use_pc = 0; c->cs_min_pc = 0.f; c->cs_accumulated = false;
     return DPMM_OK;
 }
 
-// The live point store as the count kernels name it, and whether its buffers are there
-static int count_store(const dpmm_ctx *c) { return c->x_sparse ? COUNTSTATS_SPARSE : c->x_u8 ? COUNTSTATS_U8 : COUNTSTATS_F32; }
-static bool count_store_ready(const dpmm_ctx *c, int store) {
-    const bool have = store == COUNTSTATS_SPARSE ? (bool)c->d_cp : store == COUNTSTATS_U8 ? (bool)c->dX8 : (bool)c->dX;
-    return c->have_points && c->have_params && have && !(store == COUNTSTATS_SPARSE && c->nnz > 0 && (!c->d_ri || !c->d_val));
-}
 // t_i of the points p0 .. p0 + nv - 1 into d_cs_tot (one range), for the floor per count
 static hipError_t count_totals_range(dpmm_ctx *c, int store, int64_t p0, int64_t nv) {
     CountTotalsArgs t{};
-    t.n = nv; t.D = c->D; t.store = store; t.tot = c->d_cs_tot;
-    if (store == COUNTSTATS_SPARSE) { t.cp = c->d_cp + p0; t.val = c->d_val; }
-    else if (store == COUNTSTATS_U8) { t.X8 = c->dX8 + p0 * c->ld8; t.ld8 = c->ld8; }
-    else { t.X = c->dX + p0 * c->ldx; t.ldx = c->ldx; }
+    t.n = nv; t.D = c->D; t.tot = c->d_cs_tot;
+    count_points(c, store, p0, t);
     return launch_countstats_totals(t, c->stream);
 }
 
 // include/dpmm_hip_countholdout.h: the floor per count of the accumulation just begun
 int dpmm_countstats_set_per_count(dpmm_ctx *c, int use, float min_logdens_per_count) {
-    static const char *fn = "dpmm_countstats_set_per_count";
-    if (!c) return tensor_no_ctx(fn);
-    const std::string who = std::string(fn) + ": ";
-    if (!c->cs.active) return fail(c, DPMM_ESTATE, who + "needs dpmm_countstats_begin first");
-    if (c->cs_accumulated) return fail(c, DPMM_ESTATE, who + "belongs between dpmm_countstats_begin and the first dpmm_countstats_accumulate");
-    if (use && min_logdens_per_count != min_logdens_per_count) return fail(c, DPMM_EINVAL, who + "min_logdens_per_count must not be NaN");
-    c->cs_use_pc = use ? 1 : 0;
-    c->cs_min_pc = use ? min_logdens_per_count : 0.f;
-    return DPMM_OK;
+    return set_second_floor(c, &dpmm_ctx::cs, "dpmm_countstats", "dpmm_countstats_set_per_count", use, min_logdens_per_count,
+                            min_logdens_per_count == min_logdens_per_count ? nullptr : "min_logdens_per_count must not be NaN");
 }
 
 int dpmm_countstats_accumulate(dpmm_ctx *c, int64_t n_valid) {
     static const char *fn = "dpmm_countstats_accumulate";
-    if (!c) return tensor_no_ctx(fn);
-    c->miss_counted = false;      // (as score_points)
+    bool empty = false;
+    if (int rc = acc_front(c, &dpmm_ctx::cs, "dpmm_countstats_begin", fn, n_valid, nullptr, ACC_COUNTS, &empty)) return rc;
+    if (empty) return DPMM_OK;
     const std::string who = std::string(fn) + ": ";
-    if (int rc = session_check(c, c->cs, "dpmm_countstats_begin", fn)) return rc;
-    if (n_valid < 0 || n_valid > c->n) return fail(c, DPMM_EINVAL, who + "n_valid must be in 0..n_local");
-    HIPCHK(c, hipSetDevice(c->device));
-    if (n_valid == 0) return DPMM_OK;
     const int store = count_store(c);
-    if (!count_store_ready(c, store)) return fail(c, DPMM_ESTATE, who + "needs points and parameters");
     const int K = c->K, D = c->D;
     size_t part = 0;
     TableWalk w;
     if (int rc = walk_open(c, fn, WALK_MISS_NEVER, &w, [&](int64_t P) -> int {
-            if (P >> 31) return fail(c, DPMM_EINVAL, who + "a range of the table must hold fewer than 2^31 points: lower DPMM_OPT_SCORE_TABLE_MB");
-            part = sizeof(double) * countstats_part_doubles(c, std::min<int64_t>(P, c->n));
-            if (int rc = grow(c, c->d_cs_ms, sizeof(float2) * (size_t)P, "dpmm_score_points", "maxima and sums of dpmm_countstats_accumulate")) return rc;
-            return grow(c, c->d_cs_part, part, "dpmm_score_points", "chunk partials of dpmm_countstats_accumulate");
+            if (P >> 31) return fail(c, DPMM_EINVAL, who + RANGE_TOO_LONG);
+            return countstats_range_buffers(c, P, &part);
         })) return rc;
-    if (c->cs_use_pc) if (int rc = grow(c, c->d_cs_tot, sizeof(double) * (size_t)w.P, "dpmm_score_points", "totals of dpmm_countstats_accumulate")) return rc;
-    c->cs_accumulated = true;
+    if (c->cs.use2) if (int rc = grow(c, c->d_cs_tot, sizeof(double) * (size_t)w.P, "dpmm_score_points", "totals of dpmm_countstats_accumulate")) return rc;
+    c->cs.accumulated = true;
     return walk_ranges(c, w, n_valid, fn, [&](int64_t p0, int64_t, int64_t nv) -> int {
-        if (c->cs_use_pc) if (int rc = table_result(c, fn, count_totals_range(c, store, p0, nv))) return rc;
+        if (c->cs.use2) if (int rc = table_result(c, fn, count_totals_range(c, store, p0, nv))) return rc;
         CountStatsArgs a{};
         a.table = c->d_score_table; a.stride = w.P; a.rstep = w.rstep; a.n = nv; a.K = K; a.D = D;
-        a.store = store;
-        if (store == COUNTSTATS_SPARSE) { a.cp = c->d_cp + p0; a.ri = c->d_ri; a.val = c->d_val; }
-        else if (store == COUNTSTATS_U8) { a.X8 = c->dX8 + p0 * c->ld8; a.ld8 = c->ld8; }
-        else { a.X = c->dX + p0 * c->ldx; a.ldx = c->ldx; }
+        count_points(c, store, p0, a);
         a.soft = c->cs.mode == DPMM_BATCHSTATS_SOFT; a.use_floor = c->cs.floor; a.min_logdens = c->cs.min_logdens;
-        a.use_pc = c->cs_use_pc; a.min_pc = c->cs_min_pc; a.tot = c->cs_use_pc ? c->d_cs_tot.get() : nullptr;
+        a.use_pc = c->cs.use2; a.min_pc = c->cs.min2; a.tot = c->cs.use2 ? c->d_cs_tot.get() : nullptr;
         countstats_chunks(a.n, K, D, store == COUNTSTATS_SPARSE, &a.kgroup, &a.nchunk, &a.chunk, &a.dp);
         if (sizeof(double) * (size_t)a.nchunk * (size_t)a.kgroup * ((size_t)a.dp + 1) > part)
             return fail(c, DPMM_EHIP, who + "internal: more chunks than the partial buffer holds");
@@ -4854,11 +4860,7 @@ int dpmm_countstats_accumulate(dpmm_ctx *c, int64_t n_valid) {
 
 int dpmm_countstats_read(dpmm_ctx *c, const dpmm_countstats_out *o) {
     static const char *fn = "dpmm_countstats_read";
-    if (!c) return tensor_no_ctx(fn);
-    const std::string who = std::string(fn) + ": ";
-    if (!o) return fail(c, DPMM_EINVAL, who + "out is null");
-    if (!c->cs.active) return fail(c, DPMM_ESTATE, who + "needs dpmm_countstats_begin first");
-    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = read_front(c, &dpmm_ctx::cs, "dpmm_countstats_begin", fn, o)) return rc;
     const int K = c->cs.K;
     const size_t D = (size_t)c->D, Kz = (size_t)K;
     hipError_t e = sync_stream(c, c->stream);
@@ -4867,7 +4869,7 @@ int dpmm_countstats_read(dpmm_ctx *c, const dpmm_countstats_out *o) {
     return stats_counters_read(c, fn, e, c->d_cs_acc + countstats_acc_doubles(K, (int)D), K, o->count, o->skipped, o->held_out, o->incomplete);
 }
 
-// ---- include/dpmm_hip_countholdout.h: the held-out points of a batch of count data, compacted into the caller's device memory (countholdout.hip)
+// ---- include/dpmm_hip_countholdout.h: the held-out points of a batch of count data, compacted into the caller's device memory (holdout.hip)
 // kind of a destination: 0 count only, 1 rows of Float32 (dense stores), 2 compressed sparse columns
 static int countholdout_kind(const dpmm_countholdout_dst &d) { return d.cap <= 0 ? 0 : d.colptr ? 2 : 1; }
 static int countholdout_check_dst(dpmm_ctx *c, const char *fn, const dpmm_countholdout_dst &d) {
@@ -4899,24 +4901,18 @@ int dpmm_countholdout_begin(dpmm_ctx *c, int use_floor, float min_logdens, int u
     HIPCHK(c, hipMemsetAsync(c->d_ch_state, 0, sizeof(unsigned long long) * COUNTHOLDOUT_STATE, c->stream));
     HIPCHK(c, hipMemsetAsync(c->d_ch_state + 5, 0xFF, sizeof(unsigned long long) * 2, c->stream));      // stored, stored entries: COUNTHOLDOUT_UNSET
     if (countholdout_kind(d) == 2) HIPCHK(c, hipMemsetAsync(d.colptr, 0, sizeof(int64_t), c->stream));    // slot 0
-    c->ch = AccSession{true, c->K, 0, use_floor ? 1 : 0, min_logdens, c->pred_gen};
-    c->ch_use_pc = use_per_count ? 1 : 0; c->ch_min_pc = use_per_count ? min_logdens_per_count : 0.f;
+    c->ch = AccSession{true, c->K, 0, use_floor ? 1 : 0, min_logdens, c->pred_gen, use_per_count ? 1 : 0, use_per_count ? min_logdens_per_count : 0.f};
     c->ch_dst = d;
     return DPMM_OK;
 }
 
 int dpmm_countholdout_accumulate(dpmm_ctx *c, int64_t lo, int64_t n_valid) {
     static const char *fn = "dpmm_countholdout_accumulate";
-    if (!c) return tensor_no_ctx(fn);
-    c->miss_counted = false;      // (as score_points)
+    bool empty = false;
+    if (int rc = acc_front(c, &dpmm_ctx::ch, "dpmm_countholdout_begin", fn, n_valid, &lo, ACC_COUNTS, &empty)) return rc;
+    if (empty) return DPMM_OK;
     const std::string who = std::string(fn) + ": ";
-    if (int rc = session_check(c, c->ch, "dpmm_countholdout_begin", fn)) return rc;
-    if (n_valid < 0 || n_valid > c->n) return fail(c, DPMM_EINVAL, who + "n_valid must be in 0..n_local");
-    if (lo < 0 || lo > ((int64_t)1 << 62) - n_valid) return fail(c, DPMM_EINVAL, who + "global indices must lie in 0..2^62");
-    HIPCHK(c, hipSetDevice(c->device));
-    if (n_valid == 0) return DPMM_OK;
     const int store = count_store(c);
-    if (!count_store_ready(c, store)) return fail(c, DPMM_ESTATE, who + "needs points and parameters");
     const int kind = countholdout_kind(c->ch_dst);
     if (kind != 0 && (kind == 2) != (store == COUNTSTATS_SPARSE))
         return fail(c, DPMM_ESTATE, who + (store == COUNTSTATS_SPARSE ? "the sparse store is live and dpmm_countholdout_begin was given the dense destination dst_points"
@@ -4924,25 +4920,17 @@ int dpmm_countholdout_accumulate(dpmm_ctx *c, int64_t lo, int64_t n_valid) {
     if (int rc = countholdout_check_dst(c, fn, c->ch_dst)) return rc;      // (the caller may have freed it since the begin)
     TableWalk w;
     if (int rc = walk_open(c, fn, WALK_MISS_NEVER, &w, [&](int64_t P) -> int {
-            if (P >> 31) return fail(c, DPMM_EINVAL, who + "a range of the table must hold fewer than 2^31 points: lower DPMM_OPT_SCORE_TABLE_MB");
-            const size_t groups = (size_t)holdout_groups(std::min<int64_t>(P, c->n));
-            if (int rc = grow(c, c->d_ho_ballot, sizeof(unsigned long long) * groups * (HOLDOUT_THREADS / 64), "dpmm_score_points", "ballots of dpmm_countholdout_accumulate")) return rc;
-            if (int rc = grow(c, c->d_ho_count, sizeof(unsigned) * groups * HOLDOUT_STATE, "dpmm_score_points", "workgroup counts of dpmm_countholdout_accumulate")) return rc;
-            if (int rc = grow(c, c->d_ch_ent, sizeof(unsigned long long) * groups, "dpmm_score_points", "workgroup entry counts of dpmm_countholdout_accumulate")) return rc;
-            if (int rc = grow(c, c->d_ch_eoff, sizeof(int64_t) * groups, "dpmm_score_points", "workgroup entry offsets of dpmm_countholdout_accumulate")) return rc;
-            return grow(c, c->d_ho_off, sizeof(int64_t) * groups, "dpmm_score_points", "workgroup slots of dpmm_countholdout_accumulate");
+            if (P >> 31) return fail(c, DPMM_EINVAL, who + RANGE_TOO_LONG);
+            return holdout_range_buffers(c, P, true);
         })) return rc;
-    if (c->ch_use_pc) if (int rc = grow(c, c->d_cs_tot, sizeof(double) * (size_t)w.P, "dpmm_score_points", "totals of dpmm_countholdout_accumulate")) return rc;
+    if (c->ch.use2) if (int rc = grow(c, c->d_cs_tot, sizeof(double) * (size_t)w.P, "dpmm_score_points", "totals of dpmm_countholdout_accumulate")) return rc;
     return walk_ranges(c, w, n_valid, fn, [&](int64_t p0, int64_t, int64_t nv) -> int {
-        if (c->ch_use_pc) if (int rc = table_result(c, fn, count_totals_range(c, store, p0, nv))) return rc;
+        if (c->ch.use2) if (int rc = table_result(c, fn, count_totals_range(c, store, p0, nv))) return rc;
         CountHoldoutArgs a{};
         a.table = c->d_score_table; a.stride = w.P; a.rstep = w.rstep; a.n = nv; a.K = c->K; a.D = c->D;
-        a.store = store;
-        if (store == COUNTSTATS_SPARSE) { a.cp = c->d_cp + p0; a.ri = c->d_ri; a.val = c->d_val; }
-        else if (store == COUNTSTATS_U8) { a.X8 = c->dX8 + p0 * c->ld8; a.ld8 = c->ld8; }
-        else { a.X = c->dX + p0 * c->ldx; a.ldx = c->ldx; }
+        count_points(c, store, p0, a);
         a.use_floor = c->ch.floor; a.min_logdens = c->ch.min_logdens;
-        a.use_pc = c->ch_use_pc; a.min_pc = c->ch_min_pc; a.tot = c->ch_use_pc ? c->d_cs_tot.get() : nullptr;
+        a.use_pc = c->ch.use2; a.min_pc = c->ch.min2; a.tot = c->ch.use2 ? c->d_cs_tot.get() : nullptr;
         a.index0 = lo + p0;
         a.ballot = c->d_ho_ballot; a.wgcount = c->d_ho_count; a.wgent = c->d_ch_ent; a.wgoff = c->d_ho_off; a.wgeoff = c->d_ch_eoff; a.state = c->d_ch_state;
         a.dst_points = c->ch_dst.points; a.dst_colptr = c->ch_dst.colptr; a.dst_rowval = c->ch_dst.rowval; a.dst_val = c->ch_dst.val; a.dst_index = c->ch_dst.index;
@@ -4953,11 +4941,7 @@ int dpmm_countholdout_accumulate(dpmm_ctx *c, int64_t lo, int64_t n_valid) {
 
 int dpmm_countholdout_read(dpmm_ctx *c, const dpmm_countholdout_out *o) {
     static const char *fn = "dpmm_countholdout_read";
-    if (!c) return tensor_no_ctx(fn);
-    const std::string who = std::string(fn) + ": ";
-    if (!o) return fail(c, DPMM_EINVAL, who + "out is null");
-    if (!c->ch.active) return fail(c, DPMM_ESTATE, who + "needs dpmm_countholdout_begin first");
-    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = read_front(c, &dpmm_ctx::ch, "dpmm_countholdout_begin", fn, o)) return rc;
     unsigned long long h[COUNTHOLDOUT_STATE] = {0, 0, 0, 0, 0, 0, 0, 0};
     hipError_t e = sync_stream(c, c->stream);
     if (e == hipSuccess) e = hipMemcpy(h, c->d_ch_state, sizeof(h), hipMemcpyDeviceToHost);

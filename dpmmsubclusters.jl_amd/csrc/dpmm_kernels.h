@@ -327,11 +327,22 @@ hipError_t launch_batchstats_range(const BatchStatsArgs &a, hipStream_t s);
 constexpr int HOLDOUT_THREADS = 256;             // points per workgroup of the class and gather passes
 constexpr int HOLDOUT_STATE = 4;                 // running totals: held out | skipped | incomplete | taking part
 inline int64_t holdout_groups(int64_t n) { return (n + HOLDOUT_THREADS - 1) / HOLDOUT_THREADS; }
-struct HoldoutArgs {
+// the compaction of a range, whatever the prior: all that the scan and the row gather see
+struct HoldoutCompact {
+    int64_t n;           // points of the range that are classified, below 2^31
+    int64_t index0;      // global index of the range's first point
+    unsigned long long *ballot;     // [4 * holdout_groups(n)] bit l of word j: point 64 j + l is held out
+    unsigned *wgcount;              // [holdout_groups(n)][HOLDOUT_STATE] the classes of the workgroup's points, counted
+    int64_t *wgoff;                 // [holdout_groups(n)] slot of the workgroup's first held-out point
+    unsigned long long *state;      // [HOLDOUT_STATE] running totals: read, then advanced, by the scan (count data: [COUNTHOLDOUT_STATE])
+    float *dst_points;              // [cap][D] (rows: NIW and the dense count stores)
+    int64_t *dst_index;             // [cap]
+    int64_t cap;
+};
+struct HoldoutArgs : HoldoutCompact {
     const float *table;
     int64_t stride;      // floats between two rows of the table
     int rstep;           // cluster k is row k * rstep
-    int64_t n;           // points of the range that are classified, below 2^31
     int K, D;
     const float *X;      // [n][ldx], the range's first point
     int64_t ldx;
@@ -340,14 +351,6 @@ struct HoldoutArgs {
     int use_tail;
     float min_tail;
     const float *tail;   // [n], read only if use_tail
-    int64_t index0;      // global index of the range's first point
-    unsigned long long *ballot;     // [4 * holdout_groups(n)] bit l of word j: point 64 j + l is held out
-    unsigned *wgcount;              // [holdout_groups(n)][HOLDOUT_STATE] the classes of the workgroup's points, counted
-    int64_t *wgoff;                 // [holdout_groups(n)] slot of the workgroup's first held-out point
-    unsigned long long *state;      // [HOLDOUT_STATE] running totals: read, then advanced, by the scan
-    float *dst_points;              // [cap][D]
-    int64_t *dst_index;             // [cap]
-    int64_t cap;
 };
 hipError_t launch_holdout_range(const HoldoutArgs &a, hipStream_t s);
 // ---- per-cluster count statistics of the Multinomial prior (countstats.hip; include/dpmm_hip_countstats.h): one range of the score table,
@@ -401,16 +404,15 @@ struct CountTotalsArgs {
     double *tot;         // [n]
 };
 hipError_t launch_countstats_totals(const CountTotalsArgs &a, hipStream_t s);
-// ---- held-out points of count data (countholdout.hip; include/dpmm_hip_countholdout.h): one range of the score table, n points from table
+// ---- held-out points of count data (holdout.hip; include/dpmm_hip_countholdout.h): one range of the score table, n points from table
 // column 0 and from whichever point store is live; the points the rule of countstats_device.h holds out are appended to the caller's buffers
 // in increasing index -- rows of Float32 for the dense stores, compressed sparse columns for the sparse one
 constexpr int COUNTHOLDOUT_STATE = 8;            // running totals: held out | skipped | incomplete | taking part | held-out entries | stored | stored entries | unused
 constexpr unsigned long long COUNTHOLDOUT_UNSET = ~0ull;      // stored / stored entries while every held-out point so far has fitted
-struct CountHoldoutArgs {
+struct CountHoldoutArgs : HoldoutCompact {      // state: [5], [6] are written by the one boundary workgroup of the sparse gather
     const float *table;
     int64_t stride;      // floats between two rows of the table
     int rstep;           // cluster k is row k * rstep
-    int64_t n;           // points of the range that are classified, below 2^31
     int K, D;
     int store;           // as CountStatsArgs
     const float *X;
@@ -425,19 +427,12 @@ struct CountHoldoutArgs {
     int use_pc;
     float min_pc;
     const double *tot;
-    int64_t index0;      // global index of the range's first point
-    unsigned long long *ballot;     // [4 * holdout_groups(n)] bit l of word j: point 64 j + l is held out
-    unsigned *wgcount;              // [holdout_groups(n)][HOLDOUT_STATE] the classes of the workgroup's points, counted
     unsigned long long *wgent;      // [holdout_groups(n)] stored entries of the workgroup's held-out points (sparse store; else 0)
-    int64_t *wgoff;                 // [holdout_groups(n)] slot of the workgroup's first held-out point
     int64_t *wgeoff;                // [holdout_groups(n)] entry offset of the workgroup's first held-out point
-    unsigned long long *state;      // [COUNTHOLDOUT_STATE] running totals: read, then advanced, by the scan; [5], [6] by the one boundary workgroup
-    float *dst_points;              // dense stores: [cap][D]
     int64_t *dst_colptr;            // sparse store: [cap + 1]
     int32_t *dst_rowval;            // [entry_cap]
     float *dst_val;                 // [entry_cap]
-    int64_t *dst_index;             // [cap]
-    int64_t cap, entry_cap;
+    int64_t entry_cap;
 };
 hipError_t launch_countholdout_range(const CountHoldoutArgs &a, hipStream_t s);
 // ---- missing features (missing.hip; include/dpmm_hip_missing.h): one range of the score table, n points from table column 0 and from X

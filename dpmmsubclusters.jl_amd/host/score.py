@@ -161,6 +161,22 @@ def _count_floors(min_logdens, min_logdens_per_count):
     return out
 
 
+# What the two priors do not share in `statistics` / `absorb` / `held_out` / `grow` and their `*_counts` twins: the worker's methods
+# (stats + "_begin" ..., set_second, holdout + "_begin" ...), the floors' validator and the name of the second one, the conjugate update and
+# the graft of host/absorb.py with the rows of the posterior a graft takes, the result tuple, and the words of the messages.  The
+# `set_predictive_*` call is the one `_predictive_args` names.
+_Family = collections.namedtuple("_Family", "stats set_second holdout floors floor2 absorb graft post_keys result noun by held wrong_prior")
+_FAMILY = {
+    _priors.PRIOR_NIW: _Family("batchstats", "batchstats_set_min_tail", "holdout", _floors, "min_tail", _absorb.niw_absorb, _absorb.niw_graft,
+                               _absorb.POST_KEYS, BatchStatistics, "batch", "by their tail", "held-out points",
+                               "{what} is for the NIW prior and dense points: the Multinomial prior and sparse stores are out of scope here "
+                               "-- a Multinomial model has {what}_counts"),
+    _priors.PRIOR_MULT: _Family("countstats", "countstats_set_per_count", "countholdout", _count_floors, "min_logdens_per_count",
+                                _absorb.dirichlet_absorb, _absorb.dirichlet_graft, ("alpha",), CountStatistics, "count", "per count",
+                                "held-out count points", "{what} is for the Multinomial prior: an NIW model has {base}"),
+}
+
+
 class _Stages:
     """The staging of a Predictor's short slab as host/points.py asks for it -- "host", "dev", "csc" -- kept on the Predictor as
     `_host_stage`, `_dev_stage`, `_csc_stage`; suffix "_in": the D_in-wide ones of dense data that is projected on the way in."""
@@ -526,21 +542,42 @@ class Predictor:
             raise RuntimeError("this Predictor is closed")
         if self.kind != _priors.PRIOR_NIW:
             raise ValueError("statistics are for the NIW prior: a Multinomial model has count_statistics / absorb_counts")
+        return self._statistics(data, assign, min_logdens, min_tail)
+
+    def _statistics(self, data, assign, floor, second):
+        """`statistics` and `count_statistics` behind their prior checks: begin, the second floor, the walk, read, the prior's tuple."""
+        f = _FAMILY[self.kind]
         if assign not in ASSIGN_MODES:
             raise ValueError('assign must be "hard" or "soft"')
-        min_logdens, min_tail = _floors(min_logdens, min_tail)
+        floor, second = f.floors(floor, second)
         wk = self._wk
-        if not hasattr(wk, "batchstats_begin"):
-            raise RuntimeError("this Predictor's worker cannot accumulate batch statistics (no dpmm_batchstats_begin)")
-        if min_tail is not None and not hasattr(wk, "batchstats_set_min_tail"):
-            raise RuntimeError("this Predictor's worker cannot hold points out by their tail (no dpmm_batchstats_set_min_tail)")
+        if not hasattr(wk, f.stats + "_begin"):
+            raise RuntimeError(f"this Predictor's worker cannot accumulate {f.noun} statistics (no dpmm_{f.stats}_begin)")
+        if second is not None and not hasattr(wk, f.set_second):
+            raise RuntimeError(f"this Predictor's worker cannot hold points out {f.by} (no dpmm_{f.set_second})")
         opened = self._open(data)
-        wk.batchstats_begin(ASSIGN_MODES[assign], min_logdens)
-        if min_tail is not None:
-            wk.batchstats_set_min_tail(min_tail)
-        self._walk(opened, [], lambda views, lo, hi: wk.batchstats_accumulate(hi - lo))
-        r = wk.batchstats_read()
-        return BatchStatistics(r["N"], r["sums"], r["S"], r["count"], int(r["skipped"][0]), int(r["incomplete"][0]), int(r["held_out"][0]))
+        getattr(wk, f.stats + "_begin")(ASSIGN_MODES[assign], floor)
+        if second is not None:
+            getattr(wk, f.set_second)(second)
+        self._walk(opened, [], lambda views, lo, hi: getattr(wk, f.stats + "_accumulate")(hi - lo))
+        r = getattr(wk, f.stats + "_read")()
+        return f.result(**{k: int(r[k][0]) if k in ("skipped", "incomplete", "held_out") else r[k] for k in f.result._fields})
+
+    def _absorb_statistics(self, stats):
+        """`absorb` and `absorb_counts` behind their statistics: the conjugate update, the weights re-formed, one reload."""
+        if not stats.N.sum() > 0:
+            return stats
+        self.post, self.points_count = _FAMILY[self.kind].absorb(self.post, self.points_count, stats)
+        w = self.points_count + self.alpha
+        self.weights = (w / w.sum()).astype(np.float32)
+        self._reload()
+        self._sampler_set = False            # the sampler's tables are those of the old posterior
+        return stats
+
+    def _reload(self):
+        """The predictive parameters of `self.post` and `self.weights` into the worker."""
+        which, args = self._predictive_args()
+        getattr(self._wk, "set_predictive_" + which)(*args)
 
     def absorb(self, data, assign="hard", min_logdens=None, min_tail=None):
         """Folds `data` into the model and returns the `BatchStatistics` it absorbed (see `statistics` for the arguments).
@@ -551,35 +588,30 @@ class Predictor:
         begun before (`overlap`, `exemplars` pieces at the binding level) is refused afterwards.  Statistics with N.sum() == 0 change
         nothing.  No new cluster is created: points far from every cluster are either absorbed by the nearest one or, with
         `min_logdens` or `min_tail`, held out and counted.  `held_out` collects those points and `grow` turns them into new clusters."""
-        stats = self.statistics(data, assign=assign, min_logdens=min_logdens, min_tail=min_tail)
-        if not stats.N.sum() > 0:
-            return stats
-        self.post, self.points_count = _absorb.niw_absorb(self.post, self.points_count, stats)
-        w = self.points_count + self.alpha
-        self.weights = (w / w.sum()).astype(np.float32)
-        which, args = self._predictive_args()
-        self._wk.set_predictive_niw(*args)
-        self._sampler_set = False            # the sampler's tables are those of the old posterior
-        return stats
+        return self._absorb_statistics(self.statistics(data, assign=assign, min_logdens=min_logdens, min_tail=min_tail))
 
     # ---- held-out points and new clusters (include/dpmm_hip_holdout.h, host/absorb.py)
+    def _capture_front(self, kind, data, floor, second, caps, what):
+        """What `_capture` and `_capture_counts` check before they set their destination up: (worker, the opened data, the two floors)."""
+        if self._wk is None:
+            raise RuntimeError("this Predictor is closed")
+        f = _FAMILY[kind]
+        if self.kind != kind:
+            raise ValueError(f.wrong_prior.format(what=what, base=what[:-7]))
+        floor, second = f.floors(floor, second)
+        if floor is None and second is None:
+            raise ValueError(f"{what} needs a floor: min_logdens or {f.floor2}")
+        for name, v in caps.items():
+            if v != int(v) or int(v) < 0:
+                raise ValueError(f"{name} must be a non-negative integer")
+        if not hasattr(self._wk, f.holdout + "_begin"):
+            raise RuntimeError(f"this Predictor's worker cannot collect {f.held} (no dpmm_{f.holdout}_begin)")
+        return self._wk, self._open(data), floor, second
+
     def _capture(self, data, min_logdens, min_tail, max_points, what):
         """The held-out points of `data` as the GPU compacted them: (points (stored, D) float32 tensor, index (stored,) int64 tensor, the
         worker's counters, the torch device of device data or None)."""
-        if self._wk is None:
-            raise RuntimeError("this Predictor is closed")
-        if self.kind != _priors.PRIOR_NIW:
-            raise ValueError(f"{what} is for the NIW prior and dense points: the Multinomial prior and sparse stores are out of scope here "
-                             f"-- a Multinomial model has {what}_counts")
-        min_logdens, min_tail = _floors(min_logdens, min_tail)
-        if min_logdens is None and min_tail is None:
-            raise ValueError(f"{what} needs a floor: min_logdens or min_tail")
-        if max_points != int(max_points) or int(max_points) < 0:
-            raise ValueError("max_points must be a non-negative integer")
-        wk = self._wk
-        if not hasattr(wk, "holdout_begin"):
-            raise RuntimeError("this Predictor's worker cannot collect held-out points (no dpmm_holdout_begin)")
-        opened = self._open(data)
+        wk, opened, min_logdens, min_tail = self._capture_front(_priors.PRIOR_NIW, data, min_logdens, min_tail, dict(max_points=max_points), what)
         n, dev = opened[0], opened[1]
         import torch
         cap = min(int(max_points), n)
@@ -654,34 +686,38 @@ class Predictor:
             raise ValueError("min_points must be at least 1")
         points, index, r, _ = self._capture(data, min_logdens, min_tail, max_points, "grow")
         import torch
-        total, K0 = r["total"], self.K
+        total = r["total"]
         finite = torch.isfinite(points).all(1)
         dropped = int(points.shape[0] - int(finite.sum()))
         if dropped:
             points, index = points[finite], index[finite]
+        return self._grow_from(points.T if points.shape[0] else None, index, dropped, total, hyper, alpha, iters, min_points, seed, fit_kw, "grow")
+
+    def _grow_from(self, points, index, dropped, total, hyper, alpha, iters, min_points, seed, fit_kw, what):
+        """The end of `grow` and `grow_counts`: `points` (None: there are none) and `index`, the captured points already cut to the
+        finite ones, are clustered by the sub-fit, and its clusters of at least min_points points are grafted behind the model's."""
         none = np.zeros(0, np.int64)
-        if points.shape[0] == 0:
+        if points is None:
             return Growth(0, none, none, none, dropped, total, None)
+        f, K0 = _FAMILY[self.kind], self.K
         from . import api as _api
-        res = _api.fit(points.T, hyper, alpha, iters=int(iters), seed=seed, verbose=False, **fit_kw)
+        res = _api.fit(points, hyper, alpha, iters=int(iters), seed=seed, verbose=False, **fit_kw)
         model, lab = res[8], res[0]
         lab = (lab.cpu().numpy() if hasattr(lab, "cpu") else np.asarray(lab)).astype(np.int64)
         s = model.sampler
         sizes = np.bincount(lab - 1, minlength=s.K)
-        if len(sizes) != s.K or len(lab) != points.shape[0]:
-            raise RuntimeError("grow: the sub-fit's labels do not match its clusters")
+        if len(sizes) != s.K or len(lab) != index.shape[0]:
+            raise RuntimeError(f"{what}: the sub-fit's labels do not match its clusters")
         keep = np.flatnonzero(sizes >= min_points)
         dropped += int(sizes.sum() - sizes[keep].sum())
         if len(keep) == 0:
             return Growth(0, none, none, none, dropped, total, model)
-        new_post = {k: np.asarray(s.post[k])[3 * keep] for k in _absorb.POST_KEYS}
-        post, count = _absorb.niw_graft(self.post, self.points_count, new_post, sizes[keep])
+        post, count = f.graft(self.post, self.points_count, {k: np.asarray(s.post[k])[3 * keep] for k in f.post_keys}, sizes[keep])
         w = count + self.alpha
         old = self.post, self.points_count, self.weights, self.K
         self.post, self.points_count, self.weights, self.K = post, count, (w / w.sum()).astype(np.float32), len(count)
         try:
-            which, args = self._predictive_args()
-            self._wk.set_predictive_niw(*args)             # ONCE, with the new K
+            self._reload()                                 # ONCE, with the new K
         except Exception:
             self.post, self.points_count, self.weights, self.K = old
             raise
@@ -717,21 +753,7 @@ class Predictor:
             raise RuntimeError("this Predictor is closed")
         if self.kind != _priors.PRIOR_MULT:
             raise ValueError("count_statistics are for the Multinomial prior: an NIW model has statistics / absorb")
-        if assign not in ASSIGN_MODES:
-            raise ValueError('assign must be "hard" or "soft"')
-        min_logdens, per_count = _count_floors(min_logdens, min_logdens_per_count)
-        wk = self._wk
-        if not hasattr(wk, "countstats_begin"):
-            raise RuntimeError("this Predictor's worker cannot accumulate count statistics (no dpmm_countstats_begin)")
-        if per_count is not None and not hasattr(wk, "countstats_set_per_count"):
-            raise RuntimeError("this Predictor's worker cannot hold points out per count (no dpmm_countstats_set_per_count)")
-        opened = self._open(data)
-        wk.countstats_begin(ASSIGN_MODES[assign], min_logdens)
-        if per_count is not None:
-            wk.countstats_set_per_count(per_count)
-        self._walk(opened, [], lambda views, lo, hi: wk.countstats_accumulate(hi - lo))
-        r = wk.countstats_read()
-        return CountStatistics(r["N"], r["sums"], r["count"], int(r["skipped"][0]), int(r["incomplete"][0]), int(r["held_out"][0]))
+        return self._statistics(data, assign, min_logdens, min_logdens_per_count)
 
     def absorb_counts(self, data, assign="hard", min_logdens=None, min_logdens_per_count=None):
         """Folds count `data` into a Multinomial model and returns the `CountStatistics` it absorbed (see `count_statistics`).
@@ -742,35 +764,14 @@ class Predictor:
         afterwards.  Statistics with N.sum() == 0 change nothing.  No new cluster is created: points far from every cluster are absorbed
         by the nearest one or, with a floor, held out and counted; `held_out_counts` collects those and `grow_counts` turns them into new
         clusters."""
-        stats = self.count_statistics(data, assign=assign, min_logdens=min_logdens, min_logdens_per_count=min_logdens_per_count)
-        if not stats.N.sum() > 0:
-            return stats
-        self.post, self.points_count = _absorb.dirichlet_absorb(self.post, self.points_count, stats)
-        w = self.points_count + self.alpha
-        self.weights = (w / w.sum()).astype(np.float32)
-        which, args = self._predictive_args()
-        self._wk.set_predictive_mult(*args)
-        self._sampler_set = False            # the alias tables of `sample` are those of the old posterior
-        return stats
+        return self._absorb_statistics(self.count_statistics(data, assign=assign, min_logdens=min_logdens, min_logdens_per_count=min_logdens_per_count))
 
     # ---- held-out count points and new clusters (include/dpmm_hip_countholdout.h, host/absorb.py)
     def _capture_counts(self, data, min_logdens, min_logdens_per_count, max_points, max_entries, what):
         """The held-out points of count `data` as the GPU compacted them: (sparse?, the destination tensors cut to what was stored, the
         worker's counters, the Points description of `data`)."""
-        if self._wk is None:
-            raise RuntimeError("this Predictor is closed")
-        if self.kind != _priors.PRIOR_MULT:
-            raise ValueError(f"{what} is for the Multinomial prior: an NIW model has {what[:-7]}")
-        min_logdens, per_count = _count_floors(min_logdens, min_logdens_per_count)
-        if min_logdens is None and per_count is None:
-            raise ValueError(f"{what} needs a floor: min_logdens or min_logdens_per_count")
-        for name, v in (("max_points", max_points), ("max_entries", max_entries)):
-            if v != int(v) or int(v) < 0:
-                raise ValueError(f"{name} must be a non-negative integer")
-        wk = self._wk
-        if not hasattr(wk, "countholdout_begin"):
-            raise RuntimeError("this Predictor's worker cannot collect held-out count points (no dpmm_countholdout_begin)")
-        opened = self._open(data)
+        wk, opened, min_logdens, per_count = self._capture_front(_priors.PRIOR_MULT, data, min_logdens, min_logdens_per_count,
+                                                                 dict(max_points=max_points, max_entries=max_entries), what)
         n = opened[0]
         pts = _points.describe(data)
         sparse = pts.is_sparse and hasattr(wk, "upload_points_csc")          # (a worker without the sparse upload is given dense rows)
@@ -876,7 +877,7 @@ class Predictor:
             raise ValueError("min_points must be at least 1")
         sparse, got, r, _ = self._capture_counts(data, min_logdens, min_logdens_per_count, max_points, max_entries, "grow_counts")
         import torch
-        total, K0 = r["total"], self.K
+        total = r["total"]
         index = got["index"]
         stored = int(index.shape[0])
         if sparse:                                         # a value that is not finite drops its column
@@ -895,40 +896,13 @@ class Predictor:
         dropped = int(stored - int(finite.sum()))
         if dropped:
             index = index[finite]
-        none = np.zeros(0, np.int64)
         if index.shape[0] == 0:
-            return Growth(0, none, none, none, dropped, total, None)
-        if sparse:
+            points = None
+        elif sparse:
             points = torch.sparse_csc_tensor(colptr.to(torch.int32), rowval, val, size=(self.D, int(index.shape[0])))
         else:
             points = (got["points"][finite] if dropped else got["points"]).T
-        from . import api as _api
-        res = _api.fit(points, hyper, alpha, iters=int(iters), seed=seed, verbose=False, **fit_kw)
-        model, lab = res[8], res[0]
-        lab = (lab.cpu().numpy() if hasattr(lab, "cpu") else np.asarray(lab)).astype(np.int64)
-        s = model.sampler
-        sizes = np.bincount(lab - 1, minlength=s.K)
-        if len(sizes) != s.K or len(lab) != index.shape[0]:
-            raise RuntimeError("grow_counts: the sub-fit's labels do not match its clusters")
-        keep = np.flatnonzero(sizes >= min_points)
-        dropped += int(sizes.sum() - sizes[keep].sum())
-        if len(keep) == 0:
-            return Growth(0, none, none, none, dropped, total, model)
-        post, count = _absorb.dirichlet_graft(self.post, self.points_count, {"alpha": np.asarray(s.post["alpha"])[3 * keep]}, sizes[keep])
-        w = count + self.alpha
-        old = self.post, self.points_count, self.weights, self.K
-        self.post, self.points_count, self.weights, self.K = post, count, (w / w.sum()).astype(np.float32), len(count)
-        try:
-            which, args = self._predictive_args()
-            self._wk.set_predictive_mult(*args)            # ONCE, with the new K
-        except Exception:
-            self.post, self.points_count, self.weights, self.K = old
-            raise
-        self._sampler_set = False                          # the alias tables of `sample` are those of the old K
-        new_id = np.zeros(s.K, np.int64)
-        new_id[keep] = K0 + 1 + np.arange(len(keep))
-        kept = new_id[lab - 1] > 0
-        return Growth(len(keep), sizes[keep].astype(np.int64), index.cpu().numpy()[kept], new_id[lab - 1][kept], dropped, total, model)
+        return self._grow_from(points, index, dropped, total, hyper, alpha, iters, min_points, seed, fit_kw, "grow_counts")
 
     # ---- a fixed split of the features (host/condition.py, include/dpmm_hip_regress.h)
     def _refuse_conditioning(self, what):

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Times Predictor.held_out_counts (host/score.py, csrc/countholdout.hip) and prints one JSON line.
+"""Times Predictor.held_out_counts (host/score.py, csrc/holdout.hip) and prints one JSON line.
 
   N = 1e6, K = 32, 0.1 %, 1 % and 10 % of the documents novel (all their counts on features every cluster gives little mass):
     dense    D = 1000, small integer counts on the device as Float32: the worker keeps its lossless byte copy

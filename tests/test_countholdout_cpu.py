@@ -1,6 +1,6 @@
 """CPU-side checks of the held-out count points and of Multinomial model growth (include/dpmm_hip_countholdout.h, host/score.py:
 Predictor.held_out_counts / grow_counts, host/absorb.py: dirichlet_graft): the header compiles as C, its functions are bound, exported and
-built from csrc/countholdout.hip with the shared class function; `dirichlet_graft` by hand; the numpy class rule of
+built from csrc/holdout.hip with the shared class function; `dirichlet_graft` by hand; the numpy class rule of
 tests/tools/countholdout_ref.py on hand-made points; the prior's alpha through `save` / `load`; the argument checks over a stand-in worker
 (tests/fake_worker.py, subclassed here) whose rule is "the first feature exceeds 100"."""
 import ctypes
@@ -59,9 +59,9 @@ def test_header_compiles_as_c_and_is_bound_exported_and_built(pkg, host):
         assert callable(getattr(binding.Worker, name)), name
     csrc = os.path.join(ROOT, "dpmmsubclusters.jl_amd", "csrc")
     mk = open(os.path.join(csrc, "Makefile")).read()
-    assert "build/countholdout.o" in re.search(r"^OBJS\s*=(.*)$", mk, flags=re.M).group(1).split()
+    assert "build/holdout.o" in re.search(r"^OBJS\s*=(.*)$", mk, flags=re.M).group(1).split()
     assert "../../include/dpmm_hip_countholdout.h" in re.search(r"^build/dpmm_api\.o:(.*)$", mk, flags=re.M).group(1).split()
-    hip = re.sub(r"//[^\n]*", "", open(os.path.join(csrc, "countholdout.hip")).read())
+    hip = re.sub(r"//[^\n]*", "", open(os.path.join(csrc, "holdout.hip")).read())
     assert "cs_class(" in hip and "cs_mark_gaps(" in hip and "bs_table_passes(" in hip and '#include "countstats_device.h"' in hip
     assert "atomic" not in hip and "asm" not in hip and "__ballot(" in hip and "__popcll(" in hip
     assert "cs_class(" in re.sub(r"//[^\n]*", "", open(os.path.join(csrc, "countstats.hip")).read())      # one rule, one piece of code

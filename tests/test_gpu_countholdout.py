@@ -1,4 +1,4 @@
-"""GPU tests of include/dpmm_hip_countholdout.h (csrc/countholdout.hip, csrc/countstats_device.h) and of host/score.py's
+"""GPU tests of include/dpmm_hip_countholdout.h (csrc/holdout.hip, csrc/countstats_device.h) and of host/score.py's
 Predictor.held_out_counts / grow_counts and the floor per count of count_statistics.
 
 The reference is the library's own `score_samples` on the same data and Predictor with the class rule in numpy Float64
@@ -463,3 +463,37 @@ def test_a_failing_reload_leaves_the_predictor_as_it_was(host, binding):
             p.grow_counts(X, min_logdens_per_count=GFPC, seed=0)
         assert post_bytes(p) == before and Failing.loads == 2
         assert p.count_statistics(X, min_logdens_per_count=GFPC).held_out == 2 * GNEW     # the worker still serves the old model
+
+
+# ------------------------------------------------------------------------------------------------ a range of more than 256 workgroups
+def test_a_range_of_more_than_256_workgroups(host, binding):
+    """One range of n = 256 * 256 + 257 points of the Float32 store: 258 workgroups, so a thread of the one scan workgroup owns two of them.
+    Novel documents lie on both sides of the piece boundaries 65535 | 65536 and 65791 | 65792, at both ends and at every 997th point; one
+    floor, the floor per count.  The expected set is the class rule on `score_samples` of the same Predictor, under the precondition of `check`."""
+    D, K, n = 5, 1, 256 * 256 + 257
+    planted = sorted({0, 65535, 65536, 65791, 65792, n - 1} | set(range(500, n, 997)))      # ... and one in most threads' pieces
+    nan_at = 40000
+    post = posterior(D, K)
+    _, fpc = floors(post)
+    a = post["alpha"][0].astype(np.float64)
+    X = np.random.default_rng(13).multinomial(12, a / a.sum(), size=n).astype(np.float32)
+    X[planted] = 0
+    X[planted, D - 3:] = 4
+    X[nan_at, 0] = np.nan
+    X = np.ascontiguousarray(X.T)                                                  # (D, n)
+    with open_predictor(host, post, cap=1 << 17, no_u8=True, binding=binding) as p:      # one short slab, one range
+        ld = as_np(p.score_samples(X))
+        h = p.held_out_counts(X, min_logdens_per_count=fpc, max_points=n)
+    c = R.classes(ld, X, None, fpc)
+    pc = c["complete"] & (c["t"] > 0) & np.isfinite(ld)
+    assert (np.abs(ld[pc].astype(np.float64) / c["t"][pc] - fpc) > 1e-3 * abs(fpc)).all()
+    want = np.flatnonzero(c["held"]).astype(np.int64)
+    assert c["held"][planted].all() and not c["held"][nan_at]
+    print(f"n = {n}: held out {h.total} (reference {len(want)}), skipped {h.skipped}, incomplete {h.incomplete}")
+    assert as_np(h.index).dtype == np.int64 and np.array_equal(as_np(h.index), want)
+    got = as_np(h.points)
+    assert got.dtype == np.float32 and np.ascontiguousarray(got).tobytes() == np.ascontiguousarray(X[:, want]).tobytes()
+    assert (h.total, h.total_entries) == (len(want), D * len(want))
+    assert (h.skipped, h.incomplete) == (int(c["skipped"].sum()), int(c["incomplete"].sum())) and h.skipped == 1
+    with open_predictor(host, post, cap=1024, no_u8=True, binding=binding) as p:         # 65 slabs: the same bytes
+        assert signature(p.held_out_counts(X, min_logdens_per_count=fpc, max_points=n)) == signature(h)

@@ -329,3 +329,35 @@ def test_grow_appends_the_blob_as_a_third_cluster(host):
             r.grow(data, min_tail=T)
         g = r.grow(data, min_tail=T, prior=host.niw_hyperparams(1.0, np.zeros(GD), GD + 3.0, np.eye(GD)))
         assert g.added == 1 and r.K == 3
+
+
+# ------------------------------------------------------------------------------------------------ a range of more than 256 workgroups
+def test_a_range_of_more_than_256_workgroups(host):
+    """One range of n = 256 * 256 + 257 points: 258 workgroups, so a thread of the one scan workgroup owns two of them.  Far points lie on
+    both sides of the piece boundaries 65535 | 65536 and 65791 | 65792, at both ends and at every 997th point; one floor, min_tail = 1e-4.  The expected set comes
+    from `typicality` and `score_samples` of the same Predictor, under the precondition of `case`: no tail within relative 1e-3 of t."""
+    D, K, n = 5, 1, 256 * 256 + 257
+    planted = sorted({0, 65535, 65536, 65791, 65792, n - 1} | set(range(500, n, 997)))      # ... and one in most threads' pieces
+    nan_row = 40000
+    rng = np.random.default_rng(7)
+    X = rng.standard_normal((n, D)).astype(np.float32)
+    X[planted] = (100.0 + 5.0 * rng.standard_normal((len(planted), D))).astype(np.float32)
+    X[nan_row] = np.nan
+    data = torch.from_numpy(X).to(DEV).T
+    path = model_file(D, K)
+    with host.Predictor.load(path, device=0, capacity=1 << 17) as p:            # one short slab, one range
+        tail = as_np(p.typicality(data).tail)
+        ld = as_np(p.score_samples(data))
+        h = p.held_out(data, min_tail=T, max_points=n)
+    ok = np.isfinite(tail)
+    assert np.all(np.abs(tail[ok] - T) > 1e-3 * T), "a tail too close to the floor: another seed"
+    with np.errstate(invalid="ignore"):
+        held = tail < np.float32(T)
+    want = np.flatnonzero(held).astype(np.int64)
+    assert held[planted].all() and not held[nan_row]
+    print(f"n = {n}: held out {h.total} (reference {len(want)}), skipped {h.skipped}, incomplete {h.incomplete}")
+    assert as_np(h.index).dtype == np.int64 and np.array_equal(as_np(h.index), want)
+    assert np.ascontiguousarray(as_np(h.points)).tobytes() == np.ascontiguousarray(X[want].T).tobytes()
+    assert (h.total, h.skipped, h.incomplete) == (len(want), int((~np.isfinite(ld)).sum()), 0) and h.skipped == 1
+    with host.Predictor.load(path, device=0, capacity=1024) as p:               # 65 slabs: the same bytes
+        assert bits(p.held_out(data, min_tail=T, max_points=n)) == bits(h)
