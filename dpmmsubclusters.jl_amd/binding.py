@@ -320,6 +320,14 @@ ABI_REGRESS = [
     ("dpmm_regress_points_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, _c_i64p]),
 ]
 REGRESS_MAX_TARGETS = 256    # DPMM_REGRESS_MAX_TARGETS
+# include/dpmm_hip_regress_draw.h: draws of the targets from their conditional law (additive; bound next to ABI)
+_REGRESS_DRAW_TAIL = _IMPUTE_DRAW_TAIL + [_c_i64p]
+ABI_REGRESS_DRAW = [
+    ("dpmm_set_regression_factor", ctypes.c_int, [ctypes.c_void_p, _c_f64p]),
+    ("dpmm_regress_draw_points", ctypes.c_int, [ctypes.c_void_p, _c_f32p] + _REGRESS_DRAW_TAIL),
+    ("dpmm_regress_draw_points_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p] + _REGRESS_DRAW_TAIL),
+]
+REGRESS_MAX_DRAWS = 1 << 26  # DPMM_REGRESS_MAX_DRAWS
 
 HOST_ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int)   # dpmm_host_allreduce_fn
 
@@ -401,7 +409,7 @@ def load_library():
         except Exception:  # pragma: no cover  (torch is optional for single-GPU use)
             pass
         lib = ctypes.CDLL(p)
-        for name, res, args in ABI + ABI_TENSOR + ABI_SCORE + ABI_RANK + ABI_OVERLAP + ABI_BATCHSTATS + ABI_COUNTSTATS + ABI_TYPICALITY + ABI_EXPLAIN + ABI_HOLDOUT + ABI_COUNTHOLDOUT + ABI_TRACE + ABI_MISSING + ABI_IMPUTE + ABI_REGRESS + ABI_CSC + ABI_SAMPLE + ABI_PROJECT:
+        for name, res, args in ABI + ABI_TENSOR + ABI_SCORE + ABI_RANK + ABI_OVERLAP + ABI_BATCHSTATS + ABI_COUNTSTATS + ABI_TYPICALITY + ABI_EXPLAIN + ABI_HOLDOUT + ABI_COUNTHOLDOUT + ABI_TRACE + ABI_MISSING + ABI_IMPUTE + ABI_REGRESS + ABI_REGRESS_DRAW + ABI_CSC + ABI_SAMPLE + ABI_PROJECT:
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -911,6 +919,39 @@ class Worker:
             assert mean.dtype == np.float32 and (std is None or std.dtype == np.float32) and (labels is None or labels.dtype == np.int64)
             fn, ptr = self._lib.dpmm_regress_points, lambda a: None if a is None or a.size == 0 else ctypes.c_void_p(a.ctypes.data)
         self._chk(fn(self._h, ptr(mean), ptr(std), int(mean.shape[1]), ptr(labels), _p(skipped, _c_i64p)))
+        return int(skipped[0])
+
+    # ---- draws of the targets (include/dpmm_hip_regress_draw.h)
+    def set_regression_factor(self, W):
+        """dpmm_set_regression_factor: W (K, D_t, D_t) Float64, upper triangular with W W' = (A_MM)^-1, for the tables of set_regression
+        in force."""
+        W = np.ascontiguousarray(W, np.float64)
+        Dt = getattr(self, "_regress_Dt", None)
+        assert Dt is not None and W.shape == (self.K, Dt, Dt), "set_regression_factor: set_regression first, W (K, D_t, D_t)"
+        self._chk(self._lib.dpmm_set_regression_factor(self._h, _p(W, _c_f64p)))
+
+    def regress_draw_points_into(self, out, seed, i0, draw0=0, comp=None):
+        """dpmm_regress_draw_points[_device] into storage the caller made: out (n, ndraws, w >= D_t) float32, C-contiguous -- the draws of
+        a point side by side: ld = ndraws * w, draw_stride = w -- a numpy array (host variant) or a torch tensor on this worker's GPU (device
+        variant); the draws are draw0 .. draw0 + ndraws - 1 of the points with global indices i0 .. i0 + n - 1.  comp: None or an
+        (ndraws, n) int32 array / tensor of the same kind for the drawn clusters (0-based, -1: the point took no part).  Returns the number
+        of points that took no part."""
+        dev = hasattr(out, "data_ptr")
+        nd, w = int(out.shape[1]), int(out.shape[2])
+        assert int(out.shape[0]) == self.n and nd >= 1 and w >= self._regress_Dt and (out.is_contiguous() if dev else out.flags.c_contiguous)
+        if comp is not None:
+            assert hasattr(comp, "data_ptr") == dev and tuple(comp.shape) == (nd, self.n) and (comp.is_contiguous() if dev else comp.flags.c_contiguous)
+        skipped = np.zeros(1, np.int64)
+        if dev:
+            import torch
+            assert out.dtype == torch.float32 and (comp is None or comp.dtype == torch.int32)
+            torch.cuda.current_stream(out.device).synchronize()
+            fn, op = self._lib.dpmm_regress_draw_points_device, ctypes.c_void_p(out.data_ptr() if out.numel() else None)
+            cp = comp.data_ptr() if comp is not None and comp.numel() else None
+        else:
+            assert out.dtype == np.float32 and (comp is None or comp.dtype == np.int32)
+            fn, op, cp = self._lib.dpmm_regress_draw_points, _p(out, _c_f32p), comp.ctypes.data if comp is not None and comp.size else None
+        self._chk(fn(self._h, op, nd * w, w, ctypes.c_void_p(cp), ctypes.c_uint64(int(seed)), int(i0), int(draw0), nd, _p(skipped, _c_i64p)))
         return int(skipped[0])
 
     # ---- exemplars (include/dpmm_hip_rank.h)

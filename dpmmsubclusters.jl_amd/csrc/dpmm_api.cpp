@@ -21,6 +21,7 @@
 #include "../../include/dpmm_hip_missing.h"
 #include "../../include/dpmm_hip_impute.h"
 #include "../../include/dpmm_hip_regress.h"
+#include "../../include/dpmm_hip_regress_draw.h"
 #include "../../include/dpmm_hip_sample.h"
 #include "../../include/dpmm_hip_project.h"
 
@@ -226,6 +227,12 @@ struct dpmm_ctx {
     DevBuf<float> d_reg_bt, d_reg_c, d_reg_v;
     DevBuf<double> d_reg_hd;
     DevBuf<unsigned> d_reg_skip;
+    // draws of the targets (include/dpmm_hip_regress_draw.h): cluster k's image B_k' on top of W_k', allocated by dpmm_set_regression_factor;
+    // in force while reg_factor is set and the regression tables are (dpmm_set_regression clears it)
+    bool reg_factor = false;
+    DevBuf<float> d_reg_bw;
+    DevBuf<int32_t> d_reg_kc;          // [batch][P] drawn clusters and scales of a batch of draws of one range (at most 16 MiB together),
+    DevBuf<float> d_reg_sc;            // allocated by the first dpmm_regress_draw_points
     // drawing points (include/dpmm_hip_sample.h): the sampler's tables (dpmm_set_sampler_*) and what a call needs beside its outputs
     // (cluster and tile starts; sparse: 4 bytes per point of counts and the scan's tile totals), allocated on first use
     DevBuf<float> d_sm_m, d_sm_At, d_sm_df;
@@ -4231,6 +4238,7 @@ int dpmm_set_regression(dpmm_ctx *c, int Dt, const double *B, const double *cc, 
     HIPCHK(c, hipSetDevice(c->device));
     const size_t K = (size_t)c->K, D = (size_t)c->D, Tp = (size_t)regress_pitch(Dt);
     c->reg_gen = 0;      // (a failure below leaves no tables in force)
+    c->reg_factor = false;      // (the factor's image holds a copy of the matrices that are about to be replaced)
     if (int rc = grow(c, c->d_reg_bt, sizeof(float) * K * D * Tp, fn, "regression matrices")) return rc;
     if (int rc = grow(c, c->d_reg_c, sizeof(float) * K * Tp, fn, "regression offsets")) return rc;
     if (int rc = grow(c, c->d_reg_v, sizeof(float) * K * Tp, fn, "regression variances")) return rc;
@@ -4334,6 +4342,129 @@ int dpmm_regress_points(dpmm_ctx *c, float *mean, float *std, int64_t ld, int64_
 }
 int dpmm_regress_points_device(dpmm_ctx *c, float *d_mean, float *d_std, int64_t ld, int64_t *d_labels, int64_t *skipped) {
     return regress_points(c, d_mean, d_std, ld, d_labels, skipped, true, "dpmm_regress_points_device");
+}
+
+// ---- include/dpmm_hip_regress_draw.h: draws of the targets, range by range (regress_draw.hip) -------------------------------------------
+int dpmm_set_regression_factor(dpmm_ctx *c, const double *W) {
+    static const char *fn = "dpmm_set_regression_factor";
+    if (!c) return tensor_no_ctx(fn);
+    const std::string who = std::string(fn) + ": ";
+    if (c->prior != DPMM_PRIOR_NIW) return fail(c, DPMM_EINVAL, who + "the regression is that of the NIW prior's Student-t predictive");
+    if (!W) return fail(c, DPMM_EINVAL, who + "null table");
+    if (!c->predictive || c->reg_gen == 0 || c->reg_gen != c->pred_gen) return fail(c, DPMM_ESTATE, who + "needs dpmm_set_regression for the predictive parameters in force");
+    const size_t K = (size_t)c->K, D = (size_t)c->D, Dt = (size_t)c->reg_Dt, Tp = (size_t)regress_pitch(c->reg_Dt), R = D + Dt;
+    if (R > 256) return fail(c, DPMM_EINVAL, who + "D_o + D_t > 256");
+    HIPCHK(c, hipSetDevice(c->device));
+    c->reg_factor = false;      // (a failure below leaves no factor in force)
+    if (int rc = grow(c, c->d_reg_bw, sizeof(float) * K * R * Tp, fn, "regression matrices and factors")) return rc;
+    // each value rounded to Float32 once; W transposed to rows [D, D + D_t) of cluster k's image, zeros below the diagonal and in the pad
+    std::vector<float> wt(K * Dt * Tp, 0.f);
+    for (size_t k = 0; k < K; ++k)
+        for (size_t d = 0; d < Dt; ++d)
+            for (size_t a = d; a < Dt; ++a) wt[(k * Dt + a) * Tp + d] = (float)W[(k * Dt + d) * Dt + a];
+    HIPCHK(c, sync_stream(c, c->stream));
+    HIPCHK(c, hipMemcpy2D(c->d_reg_bw, sizeof(float) * R * Tp, c->d_reg_bt, sizeof(float) * D * Tp, sizeof(float) * D * Tp, K, hipMemcpyDeviceToDevice));
+    HIPCHK(c, hipMemcpy2D(c->d_reg_bw + D * Tp, sizeof(float) * R * Tp, wt.data(), sizeof(float) * Dt * Tp, sizeof(float) * Dt * Tp, K, hipMemcpyHostToDevice));
+    c->reg_factor = true;
+    return DPMM_OK;
+}
+
+// Per range: the table once, then the draws -- into the caller's device memory, or in batches of draws through the staging block
+// ([batch][np][D_t] floats, then [batch][np] components).
+static int regress_draw_points(dpmm_ctx *c, float *out, int64_t ld, int64_t draw_stride, int32_t *comp, uint64_t seed, int64_t i0, int64_t draw0,
+                               int64_t ndraws, int64_t *skipped, bool device, const char *fn) {
+    if (!c) return tensor_no_ctx(fn);
+    c->miss_counted = false;      // (as score_points)
+    const std::string who = std::string(fn) + ": ";
+    if (c->prior != DPMM_PRIOR_NIW) return fail(c, DPMM_EINVAL, who + "the regression is that of the NIW prior's Student-t predictive");
+    if (!c->predictive) return fail(c, DPMM_ESTATE, who + "needs dpmm_set_predictive_niw first");
+    if (c->reg_gen == 0 || c->reg_gen != c->pred_gen) return fail(c, DPMM_ESTATE, who + "needs dpmm_set_regression for the predictive parameters in force");
+    if (!c->reg_factor) return fail(c, DPMM_ESTATE, who + "needs dpmm_set_regression_factor for the regression tables in force");
+    const int64_t Dt = c->reg_Dt, n = c->n;
+    if (ndraws < 1 || draw0 < 0 || draw0 > DPMM_REGRESS_MAX_DRAWS || ndraws > DPMM_REGRESS_MAX_DRAWS - draw0)
+        return fail(c, DPMM_EINVAL, who + "draw0 >= 0, ndraws >= 1 and draw0 + ndraws <= DPMM_REGRESS_MAX_DRAWS are needed");
+    if (i0 < 0 || (i0 >> 62)) return fail(c, DPMM_EINVAL, who + "i0 out of range");
+    if (ld < Dt) return fail(c, DPMM_EINVAL, who + "ld < D_t");
+    if ((ld >> 40) || draw_stride < 0 || (draw_stride >> 37)) return fail(c, DPMM_EINVAL, who + "ld / draw_stride out of range");
+    const bool interleaved = draw_stride >= Dt && draw_stride <= ld / ndraws;
+    if (!interleaved && (unsigned __int128)draw_stride < (unsigned __int128)n * (unsigned __int128)ld)
+        return fail(c, DPMM_EINVAL, who + "the draws overlap: draw_stride >= n_local * ld (stacked) or D_t <= draw_stride <= ld / ndraws (interleaved) is needed");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (skipped) skipped[0] = 0;
+    if (n == 0) return DPMM_OK;
+    if (!c->have_points || !c->have_params || !c->dX) return fail(c, DPMM_ESTATE, who + "needs points and parameters");
+    if (!out) return fail(c, DPMM_EINVAL, who + "out is null");
+    const int64_t width = std::min(ld, draw_stride);
+    if (device) {
+        const uint64_t words = (uint64_t)(ndraws - 1) * (uint64_t)draw_stride + (uint64_t)(n - 1) * (uint64_t)ld + (uint64_t)width;
+        if (int rc = check_device_extent(c, fn, "d_out", out, words * sizeof(float), sizeof(float))) return rc;
+        if (comp) if (int rc = check_device_extent(c, fn, "d_comp", comp, (uint64_t)ndraws * (uint64_t)n * sizeof(int32_t), sizeof(int32_t))) return rc;
+    }
+    TableWalk tw;
+    if (int rc = walk_open(c, fn, WALK_MISS_NEVER, &tw)) return rc;
+    const int64_t P = tw.P;
+    const size_t tiles = (size_t)((P + 31) / 32);
+    if (int rc = grow(c, c->d_reg_skip, sizeof(unsigned) * tiles, fn, "counts of the regression pass")) return rc;
+    HIPCHK(c, hipMemsetAsync(c->d_reg_skip, 0, sizeof(unsigned) * tiles, c->stream));
+    // the draws of a range in batches: 16 MiB of components and scales at most, and (host variant) 64 MiB of staged draws; one draw at least
+    int64_t batch = std::max<int64_t>(1, std::min<int64_t>(ndraws, ((int64_t)16 << 20) / (8 * P)));
+    if (!device) {
+        batch = std::max<int64_t>(1, std::min<int64_t>(batch, ((int64_t)64 << 20) / ((int64_t)sizeof(float) * P * Dt)));
+        if (int rc = grow(c, c->d_score_out, (size_t)batch * (size_t)P * (sizeof(float) * (size_t)Dt + sizeof(int32_t)), fn, "staging of the outputs")) return rc;
+    }
+    if (int rc = grow(c, c->d_reg_kc, sizeof(int32_t) * (size_t)batch * (size_t)P, fn, "components of a batch of draws")) return rc;
+    if (int rc = grow(c, c->d_reg_sc, sizeof(float) * (size_t)batch * (size_t)P, fn, "scales of a batch of draws")) return rc;
+    if (int rc = walk_ranges(c, tw, n, fn, [&](int64_t p0, int64_t np, int64_t) -> int {
+            RegressDrawArgs a{};
+            a.kc = c->d_reg_kc; a.sc = c->d_reg_sc;
+            a.table = c->d_score_table; a.stride = P; a.n = np; a.K = c->K; a.D = c->D; a.Dt = (int)Dt; a.Tp = regress_pitch((int)Dt);
+            a.X = c->dX + p0 * c->ldx; a.ldx = c->ldx;
+            a.Bw = c->d_reg_bw; a.c = c->d_reg_c; a.hd = c->d_reg_hd;
+            a.seed = seed; a.i0 = i0 + p0;
+            for (int64_t j0 = 0; j0 < ndraws; j0 += batch) {
+                const int64_t nb = std::min(batch, ndraws - j0);
+                a.draw0 = draw0 + j0; a.ndraws = (int)nb;
+                a.skip = j0 == 0 ? c->d_reg_skip.get() : nullptr;      // a point is counted once per call
+                if (device) {
+                    a.out = out + j0 * draw_stride + p0 * ld; a.ld = ld; a.draw_stride = draw_stride;
+                    a.comp = comp ? comp + j0 * n + p0 : nullptr; a.comp_stride = n;
+                } else {
+                    a.out = reinterpret_cast<float *>(c->d_score_out.get()); a.ld = Dt; a.draw_stride = np * Dt;
+                    a.comp = comp ? reinterpret_cast<int32_t *>(a.out + batch * P * Dt) : nullptr; a.comp_stride = np;
+                }
+                if (int rc = table_result(c, fn, launch_regress_draw_range(a, c->stream))) return rc;
+                if (!device) {
+                    for (int64_t jd = 0; jd < nb; ++jd)
+                        HIPCHK(c, hipMemcpy2DAsync(out + (j0 + jd) * draw_stride + p0 * ld, sizeof(float) * (size_t)ld, a.out + jd * np * Dt, sizeof(float) * (size_t)Dt,
+                                                   sizeof(float) * (size_t)Dt, (size_t)np, hipMemcpyDeviceToHost, c->stream));
+                    if (comp) HIPCHK(c, hipMemcpy2DAsync(comp + j0 * n + p0, sizeof(int32_t) * (size_t)n, a.comp, sizeof(int32_t) * (size_t)np, sizeof(int32_t) * (size_t)np,
+                                                         (size_t)nb, hipMemcpyDeviceToHost, c->stream));
+                    HIPCHK(c, sync_stream(c, c->stream));      // the staging block is rewritten by the next batch
+                    if (width > Dt)
+                        for (int64_t jd = j0; jd < j0 + nb; ++jd)
+                            for (int64_t i = p0; i < p0 + np; ++i) memset(out + jd * draw_stride + i * ld + Dt, 0, sizeof(float) * (size_t)(width - Dt));
+                }
+            }
+            return DPMM_OK;
+        })) return rc;
+    HIPCHK(c, sync_stream(c, c->stream));
+    if (skipped) {
+        std::vector<unsigned> cnt(tiles);
+        HIPCHK(c, hipMemcpy(cnt.data(), c->d_reg_skip, sizeof(unsigned) * tiles, hipMemcpyDeviceToHost));
+        int64_t total = 0;
+        for (unsigned v : cnt) total += v;
+        skipped[0] = total;
+    }
+    return DPMM_OK;
+}
+
+int dpmm_regress_draw_points(dpmm_ctx *c, float *out, int64_t ld, int64_t draw_stride, int32_t *comp, uint64_t seed, int64_t i0, int64_t draw0, int64_t ndraws,
+                             int64_t *skipped) {
+    return regress_draw_points(c, out, ld, draw_stride, comp, seed, i0, draw0, ndraws, skipped, false, "dpmm_regress_draw_points");
+}
+int dpmm_regress_draw_points_device(dpmm_ctx *c, float *d_out, int64_t ld, int64_t draw_stride, int32_t *d_comp, uint64_t seed, int64_t i0, int64_t draw0,
+                                    int64_t ndraws, int64_t *skipped) {
+    return regress_draw_points(c, d_out, ld, draw_stride, d_comp, seed, i0, draw0, ndraws, skipped, true, "dpmm_regress_draw_points_device");
 }
 
 // ---- include/dpmm_hip_rank.h: exemplars, the m most and least typical points of every cluster (rank.hip) -----------------------------------

@@ -19,6 +19,8 @@ enum : uint32_t { STREAM_SWEEP = 0, STREAM_INIT = 1, STREAM_SPLIT = 2, STREAM_RE
 enum : uint32_t { STREAM_SAMPLE_NORMAL = 40, STREAM_SAMPLE_CHI = 41, STREAM_SAMPLE_MULT = 42 };
 // Drawing the missing features of a point (missing.hip; include/dpmm_hip_impute.h states the keying): component, normals, chi^2.
 enum : uint32_t { STREAM_IMPUTE_COMP = 43, STREAM_IMPUTE_NORMAL = 44, STREAM_IMPUTE_CHI = 45 };
+// Drawing the targets of a regression (regress_draw.hip; include/dpmm_hip_regress_draw.h states the keying): component, normals, chi^2.
+enum : uint32_t { STREAM_REGRESS_COMP = 46, STREAM_REGRESS_NORMAL = 47, STREAM_REGRESS_CHI = 48 };
 
 struct Philox4 {
     uint32_t v[4];

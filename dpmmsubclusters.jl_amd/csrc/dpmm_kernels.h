@@ -478,6 +478,34 @@ struct RegressArgs {
     unsigned *skip;              // [ceil(n / 32)] points of tile j that take no part, ADDED to word j
 };
 hipError_t launch_regress_range(const RegressArgs &a, hipStream_t s);
+// ---- draws of the targets (regress_draw.hip; include/dpmm_hip_regress_draw.h): one range of the score table, n points from table column 0
+// and from X, the draws draw0 .. draw0 + ndraws - 1 of each
+constexpr int64_t REGRESS_DRAW_MAX = 67108864;      // DPMM_REGRESS_MAX_DRAWS
+struct RegressDrawArgs {
+    const float *table;          // as RegressArgs
+    int64_t stride;
+    int64_t n;
+    int K, D;
+    int Dt, Tp;
+    const float *X;
+    int64_t ldx;
+    const float *Bw;             // [K][D + Dt][Tp]: rows [0, D) of cluster k are RegressArgs::Bt[k]; row D + a is W_k[.][a] (Bw[k][D + a][d] = W_k[d][a]),
+                                 // zero below the diagonal of W (a < d) and in the pad (d >= Dt)
+    const float *c;              // [K][Tp], zero in the pad
+    const double *hd;            // [K][2]: h_k, df_k
+    float *out;                  // element (jd, i, f) at out[jd * draw_stride + i * ld + f], f < min(ld, draw_stride); columns [Dt, ..) are written as 0
+    int64_t ld, draw_stride;
+    int32_t *comp;               // null, or element (jd, i) at comp[jd * comp_stride + i]
+    int64_t comp_stride;
+    uint64_t seed;
+    int64_t i0;                  // global index of the range's first point
+    int64_t draw0;
+    int ndraws;
+    unsigned *skip;              // as RegressArgs, or null: not counted by this launch
+    int32_t *kc;                 // scratch [ndraws][n]: the drawn cluster (-1: the point's row of the table takes no part) and
+    float *sc;                   // the scale s of every (draw, point), written by the first kernel of the launch and read by the second
+};
+hipError_t launch_regress_draw_range(const RegressDrawArgs &a, hipStream_t s);
 // ---- calibrated outlier scores (typicality.hip; include/dpmm_hip_typicality.h): one range of the score table, n points from table column 0:
 // the label and the class of every point, q = |R_k (x - m_k)|^2 for its own cluster k in Float32, the tail of q in Float64
 struct TypicalityArgs {

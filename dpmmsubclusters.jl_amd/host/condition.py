@@ -75,12 +75,14 @@ def table_constant(logdet, df, w, D):
     return gammaln(0.5 * (df + D)) - gammaln(0.5 * df) - 0.5 * D * np.log(df * np.pi) - 0.5 * logdet + np.log(w)
 
 
-def regression_tables(m, R, given, targets):
+def regression_tables(m, R, given, targets, factor=False):
     """(B (K, D_t, D_o), c (K, D_t), V (K, D_t)) in Float64 from the predictive parameters m (K, D), R (K, D, D) or (K, D D) upper triangular
     with Sigma^-1 = R'R, over the features of one model: `given` and `targets` index it, disjoint.  Features in neither are marginalised
     away first -- the precision of the sub-model over given + targets is the inverse of that block of Sigma -- then, with A that precision,
         B = -(A_MM)^-1 A_MO,   c = m_M - B m_O,   V = diag((A_MM)^-1)
-    by Cholesky of A_MM."""
+    by Cholesky of A_MM = L L'.  factor=True: (B, c, V, W) with W = (L^-1)' (K, D_t, D_t), upper triangular, W W' = (A_MM)^-1 -- what a
+    draw from the conditional law multiplies its normals with (include/dpmm_hip_regress_draw.h):
+        x_M = c + B x_O + sqrt((df + q) / g) W n,   n ~ N(0, I),  g ~ chi^2(df + D_o)."""
     m = np.asarray(m, np.float64)
     K, D = m.shape
     R = np.asarray(R, np.float64).reshape(K, D, D)
@@ -102,4 +104,6 @@ def regression_tables(m, R, given, targets):
     c = m[:, M] - np.einsum("kij,kj->ki", B, m[:, O])
     V = np.einsum("kii->ki", Ainv).copy()
     assert B.shape == (K, Dt, Do)
+    if factor:
+        return B, c, V, np.ascontiguousarray(Li.transpose(0, 2, 1))
     return B, c, V

@@ -80,6 +80,12 @@ Regression = collections.namedtuple("Regression", "mean std labels skipped")
 Regression.__doc__ = """What `Regressor.predict` returns: mean (D_t, n) float32, std the same or None, labels (n,) int64 1-based -- tensors on the
 data's device for a device tensor, else numpy arrays -- and skipped, an int: the points whose mean and std columns are NaN."""
 
+RegressionDraws = collections.namedtuple("RegressionDraws", "values components labels skipped")
+RegressionDraws.__doc__ = """What `Regressor.sample` returns: values (draws, D_t, n) float32, draw j of the targets of every point; components
+(draws, n) int32, the 0-based cluster each draw came from (-1: the point took no part), or None; labels (n,) int64 1-based, the marginal
+model's -- tensors on the data's device for a device tensor, else numpy arrays -- and skipped, an int: the points whose columns are NaN in
+every draw."""
+
 ASSIGN_MODES = {"hard": binding.BATCHSTATS_HARD, "soft": binding.BATCHSTATS_SOFT}
 
 
@@ -1195,16 +1201,24 @@ class Regressor:
             self.marginal.close()
             raise
 
-    def tables(self):
-        """(B (K, D_t, D_o), c (K, D_t), V (K, D_t), h (K,), df (K,)) in Float64 for the model as it stands."""
+    def _joint_parameters(self):
+        """(m (K, D_o + D_t), R (K, (D_o + D_t)^2) upper triangular, Sigma^-1 = R'R) of the joint predictive over given + targets, in that
+        order: the Float32 values a worker would be handed, widened to Float64 -- what the tables are formed from."""
         mg = self.marginal
         sub = Predictor.__new__(Predictor)      # only the conversion of host/priors.py is used: no worker
         sub.kind, sub.D, sub.K, sub.post, sub.weights = mg.kind, self.D_o + self.D_t, mg.K, self._sub_post, mg.weights
+        m, R = sub._predictive_args()[1][:2]
+        return np.asarray(m, np.float32).astype(np.float64), np.asarray(R, np.float32).astype(np.float64)
+
+    def tables(self, factor=False):
+        """(B (K, D_t, D_o), c (K, D_t), V (K, D_t), h (K,), df (K,)) in Float64 for the model as it stands; factor=True: W (K, D_t, D_t),
+        upper triangular with W W' = (A_MM)^-1, as a sixth entry."""
+        mg = self.marginal
         f32 = lambda a: np.asarray(a, np.float32).astype(np.float64)      # noqa: E731  (what the worker receives)
-        m, R, _, _, _ = (f32(a) for a in sub._predictive_args()[1])
-        B, c, V = _condition.regression_tables(m, R, range(self.D_o), range(self.D_o, self.D_o + self.D_t))
+        m, R = self._joint_parameters()
+        B, c, V, *W = _condition.regression_tables(m, R, range(self.D_o), range(self.D_o, self.D_o + self.D_t), factor=factor)
         _, _, logdet, df, w = (f32(a) for a in mg._predictive_args()[1])
-        return B, c, V, _condition.table_constant(logdet, df, w, self.D_o), df
+        return (B, c, V, _condition.table_constant(logdet, df, w, self.D_o), df) + tuple(W)
 
     def _refresh(self):
         """The worker's tables are those of the marginal model's posterior as it stands (absorb replaces `post` and reloads the worker)."""
@@ -1215,9 +1229,12 @@ class Regressor:
             return
         if not hasattr(mg._wk, "set_regression"):
             raise RuntimeError("this Regressor's worker cannot regress (no dpmm_set_regression)")
-        B, c, V, h, df = self.tables()
+        draws = hasattr(mg._wk, "set_regression_factor")      # (a worker without it predicts; `sample` says what is missing)
+        B, c, V, h, df, *W = self.tables(factor=draws)
         self._no_var = bool(np.any(df + self.D_o <= 2))
         mg._wk.set_regression(B, c, V, h)
+        if draws:
+            mg._wk.set_regression_factor(W[0])
         self._tables_for = mg.post
 
     def close(self):
@@ -1253,6 +1270,45 @@ class Regressor:
         out = mg._walk(mg._open(data), spec, evaluate)
         return Regression(out["mean"].T, out["std"].T if return_std else None, out["labels"], total[0])
 
+    def sample(self, data, draws=1, seed=0, return_components=False):
+        """`RegressionDraws(values, components, labels, skipped)`: `draws` DRAWS of the targets of every point of `data` (D_o rows in the
+        order of `given`, every input kind `predict` takes) from their law given the given features under the fitted mixture
+        (include/dpmm_hip_regress_draw.h): a cluster k ~ p_ik, then that cluster's conditional Student-t.  Where `predict` gives one
+        number per target -- a mean that can lie between the modes, where no data is -- the draws keep the modes and how the targets move
+        together: joint intervals, quantiles, P(target a > target b), completions of a table.  values (draws, D_t, n) float32, the
+        orientation of `impute(draws=m)`.  Draw j of point i depends on (seed, i = its position in `data`, j, the point, the model) alone
+        -- not on `capacity`, not on `draws`: the first draws of a longer run are those of a shorter one.  A point that takes no part
+        (see `predict`) has NaN in every draw and component -1, and is counted once in `skipped`.  The draws of a slab come from one
+        evaluation of the table; the labels cost a second one."""
+        mg = self.marginal
+        self._refresh()
+        m, seed = int(draws), int(seed)
+        if m < 1 or m != draws or m > binding.REGRESS_MAX_DRAWS:
+            raise ValueError(f"draws must be an integer in 1..{binding.REGRESS_MAX_DRAWS}")
+        if seed < 0 or seed >> 64:
+            raise ValueError("seed must be in 0..2^64 - 1")
+        wk, cap = mg._wk, mg.capacity
+        if not hasattr(wk, "regress_draw_points_into") or not hasattr(wk, "set_regression_factor"):
+            raise RuntimeError("this Regressor's worker cannot draw the targets (no dpmm_regress_draw_points)")
+        opened = mg._open(data)
+        n, new = opened[0], opened[2]
+        comp = new(m, (n,), "int32") if return_components else None
+        stage = new(m, (cap,), "int32") if n else None            # the ABI's comp is [m][capacity]: one slab's, then sliced in
+        total = [0]
+
+        def evaluate(views, lo, hi):
+            sk = wk.regress_draw_points_into(views["draws"], seed, lo, comp=stage)      # the global index of a point is its position in `data`
+            wk.score_points_into({"labels": views["labels"]})
+            if hi - lo < cap:                    # (the padding of a short slab is zeros, as in `predict`: not ours if it took no part)
+                sk -= int((stage[0, hi - lo:] < 0).sum())
+            total[0] += sk
+            if comp is not None:
+                comp[:, lo:hi] = stage[:, :hi - lo]
+        out = mg._walk(opened, [("draws", (m, self.D_t), "float32"), ("labels", (), "int64")], evaluate)      # (n, m, D_t): ld = m D_t, draw_stride = D_t
+        vals = out["draws"]
+        vals = vals.permute(1, 2, 0) if hasattr(vals, "permute") else vals.transpose(1, 2, 0)
+        return RegressionDraws(vals, comp, out["labels"], total[0])
+
 
 def regress(dp_model, data, given, targets=None, return_std=False, **kw):
     """Mixture regression from the features `given` to `targets` (opens a Predictor and its Regressor, runs, closes): see `Regressor`;
@@ -1261,6 +1317,16 @@ def regress(dp_model, data, given, targets=None, return_std=False, **kw):
     with Predictor(dp_model, worker_factory=factory, **kw) as p:
         with p.regressor(given, targets, worker_factory=factory) as r:
             return r.predict(data, return_std=return_std)
+
+
+def regress_sample(dp_model, data, given, targets=None, draws=1, seed=0, **kw):
+    """Draws of the features `targets` given the features `given` (opens a Predictor and its Regressor, draws, closes): see
+    `Regressor.sample`; `data` has the rows of `given`; kw: return_components, capacity, device, worker_factory."""
+    factory = kw.pop("worker_factory", None)
+    comps = kw.pop("return_components", False)
+    with Predictor(dp_model, worker_factory=factory, **kw) as p:
+        with p.regressor(given, targets, worker_factory=factory) as r:
+            return r.sample(data, draws=draws, seed=seed, return_components=comps)
 
 
 def score_samples(dp_model, data, **kw):
