@@ -328,6 +328,15 @@ ABI_REGRESS_DRAW = [
     ("dpmm_regress_draw_points_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p] + _REGRESS_DRAW_TAIL),
 ]
 REGRESS_MAX_DRAWS = 1 << 26  # DPMM_REGRESS_MAX_DRAWS
+# include/dpmm_hip_regress_cdf.h: conditional CDF and quantiles of the targets (additive; bound next to ABI)
+ABI_REGRESS_CDF = [
+    ("dpmm_regress_cdf_points", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, _c_i64p]),
+    ("dpmm_regress_cdf_points_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, _c_i64p]),
+    ("dpmm_set_regression_levels", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _c_f64p, _c_f64p]),
+    ("dpmm_regress_quantile_points", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, _c_i64p]),
+    ("dpmm_regress_quantile_points_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, _c_i64p]),
+]
+REGRESS_MAX_LEVELS = 16      # DPMM_REGRESS_MAX_LEVELS
 
 HOST_ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int)   # dpmm_host_allreduce_fn
 
@@ -409,7 +418,7 @@ def load_library():
         except Exception:  # pragma: no cover  (torch is optional for single-GPU use)
             pass
         lib = ctypes.CDLL(p)
-        for name, res, args in ABI + ABI_TENSOR + ABI_SCORE + ABI_RANK + ABI_OVERLAP + ABI_BATCHSTATS + ABI_COUNTSTATS + ABI_TYPICALITY + ABI_EXPLAIN + ABI_HOLDOUT + ABI_COUNTHOLDOUT + ABI_TRACE + ABI_MISSING + ABI_IMPUTE + ABI_REGRESS + ABI_REGRESS_DRAW + ABI_CSC + ABI_SAMPLE + ABI_PROJECT:
+        for name, res, args in ABI + ABI_TENSOR + ABI_SCORE + ABI_RANK + ABI_OVERLAP + ABI_BATCHSTATS + ABI_COUNTSTATS + ABI_TYPICALITY + ABI_EXPLAIN + ABI_HOLDOUT + ABI_COUNTHOLDOUT + ABI_TRACE + ABI_MISSING + ABI_IMPUTE + ABI_REGRESS + ABI_REGRESS_DRAW + ABI_REGRESS_CDF + ABI_CSC + ABI_SAMPLE + ABI_PROJECT:
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -952,6 +961,48 @@ class Worker:
             assert out.dtype == np.float32 and (comp is None or comp.dtype == np.int32)
             fn, op, cp = self._lib.dpmm_regress_draw_points, _p(out, _c_f32p), comp.ctypes.data if comp is not None and comp.size else None
         self._chk(fn(self._h, op, nd * w, w, ctypes.c_void_p(cp), ctypes.c_uint64(int(seed)), int(i0), int(draw0), nd, _p(skipped, _c_i64p)))
+        return int(skipped[0])
+
+    # ---- conditional CDF and quantiles of the targets (include/dpmm_hip_regress_cdf.h)
+    def _regress_cdf_call(self, name, arrays, lead, tail):
+        """The host or the device variant of `name` for `arrays` (numpy arrays or tensors of this worker's GPU, None allowed): (fn, ptr)."""
+        given = [a for a in arrays if a is not None]
+        dev = hasattr(given[0], "data_ptr")
+        assert all(hasattr(a, "data_ptr") == dev for a in given), name + ": numpy arrays or tensors, not both"
+        assert all(int(a.shape[0]) == self.n and (a.is_contiguous() if dev else a.flags.c_contiguous) for a in given)
+        if dev:
+            import torch
+            assert all(a.dtype == (torch.int64 if a is tail else torch.float32) for a in given)
+            torch.cuda.current_stream(lead.device).synchronize()
+            return getattr(self._lib, name + "_device"), lambda a: None if a is None or a.numel() == 0 else ctypes.c_void_p(a.data_ptr())
+        assert all(a.dtype == (np.int64 if a is tail else np.float32) for a in given)
+        return getattr(self._lib, name), lambda a: None if a is None or a.size == 0 else ctypes.c_void_p(a.ctypes.data)
+
+    def regress_cdf_points_into(self, y, cdf, sf=None, labels=None):
+        """dpmm_regress_cdf_points[_device] into storage the caller made: y, cdf and sf C-contiguous (n, ld >= D_t) float32, labels (n,) int64
+        -- numpy arrays (host variant) or torch tensors on this worker's GPU (device variant); sf and labels may be None.  Returns the
+        number of points that took no part."""
+        fn, ptr = self._regress_cdf_call("dpmm_regress_cdf_points", (y, cdf, sf, labels), cdf, labels)
+        assert sf is None or tuple(sf.shape) == tuple(cdf.shape)
+        skipped = np.zeros(1, np.int64)
+        self._chk(fn(self._h, ptr(y), int(y.shape[1]), ptr(cdf), ptr(sf), int(cdf.shape[1]), ptr(labels), _p(skipped, _c_i64p)))
+        return int(skipped[0])
+
+    def set_regression_levels(self, levels, z):
+        """dpmm_set_regression_levels: L strictly increasing levels inside (0, 1) and z (K, L) Float64, z[k, q] the level's quantile of
+        t_{df_k + D}, for the tables of set_regression in force."""
+        levels, z = np.ascontiguousarray(levels, np.float64), np.ascontiguousarray(z, np.float64)
+        assert levels.ndim == 1 and z.shape == (self.K, len(levels)), "set_regression_levels: levels (L,), z (K, L)"
+        self._chk(self._lib.dpmm_set_regression_levels(self._h, len(levels), _p(levels, _c_f64p), _p(z, _c_f64p)))
+        self._regress_L = len(levels)
+
+    def regress_quantile_points_into(self, out, labels=None):
+        """dpmm_regress_quantile_points[_device] into storage the caller made: out (n, L, ld >= D_t) float32 C-contiguous, labels (n,) int64
+        or None -- numpy arrays or torch tensors on this worker's GPU.  Returns the number of points that took no part."""
+        fn, ptr = self._regress_cdf_call("dpmm_regress_quantile_points", (out, labels), out, labels)
+        assert int(out.shape[1]) == self._regress_L
+        skipped = np.zeros(1, np.int64)
+        self._chk(fn(self._h, ptr(out), int(out.shape[2]), ptr(labels), _p(skipped, _c_i64p)))
         return int(skipped[0])
 
     # ---- exemplars (include/dpmm_hip_rank.h)

@@ -22,6 +22,7 @@
 #include "../../include/dpmm_hip_impute.h"
 #include "../../include/dpmm_hip_regress.h"
 #include "../../include/dpmm_hip_regress_draw.h"
+#include "../../include/dpmm_hip_regress_cdf.h"
 #include "../../include/dpmm_hip_sample.h"
 #include "../../include/dpmm_hip_project.h"
 
@@ -45,6 +46,7 @@
 
 #include "dpmm_kernels.h"
 #include "project_image.h"
+#include "typicality_math.h"      // typ_log_beta, for the density constants of dpmm_set_regression_levels
 #include "dev_mem.h"      // DevBuf / PinBuf: every buffer below is a member or a local of these and is never freed by hand
 
 namespace dpmm {      // test hook in front of every kernel launch (dpmm_kernels.h DPMM_LAUNCH, dpmm_debug_set_prelaunch_hook)
@@ -233,6 +235,11 @@ struct dpmm_ctx {
     DevBuf<float> d_reg_bw;
     DevBuf<int32_t> d_reg_kc;          // [batch][P] drawn clusters and scales of a batch of draws of one range (at most 16 MiB together),
     DevBuf<float> d_reg_sc;            // allocated by the first dpmm_regress_draw_points
+    // conditional quantiles (include/dpmm_hip_regress_cdf.h): levels [L], z [K][L], log densities at 0 [K], made by dpmm_set_regression_levels
+    // for the parameter set reg_lev_gen (0: none; dpmm_set_regression clears it)
+    unsigned long long reg_lev_gen = 0;
+    int reg_L = 0;
+    DevBuf<double> d_reg_lev;
     // drawing points (include/dpmm_hip_sample.h): the sampler's tables (dpmm_set_sampler_*) and what a call needs beside its outputs
     // (cluster and tile starts; sparse: 4 bytes per point of counts and the scan's tile totals), allocated on first use
     DevBuf<float> d_sm_m, d_sm_At, d_sm_df;
@@ -4239,6 +4246,7 @@ int dpmm_set_regression(dpmm_ctx *c, int Dt, const double *B, const double *cc, 
     const size_t K = (size_t)c->K, D = (size_t)c->D, Tp = (size_t)regress_pitch(Dt);
     c->reg_gen = 0;      // (a failure below leaves no tables in force)
     c->reg_factor = false;      // (the factor's image holds a copy of the matrices that are about to be replaced)
+    c->reg_lev_gen = 0;         // (the levels' z belong to the tables that are about to be replaced)
     if (int rc = grow(c, c->d_reg_bt, sizeof(float) * K * D * Tp, fn, "regression matrices")) return rc;
     if (int rc = grow(c, c->d_reg_c, sizeof(float) * K * Tp, fn, "regression offsets")) return rc;
     if (int rc = grow(c, c->d_reg_v, sizeof(float) * K * Tp, fn, "regression variances")) return rc;
@@ -4465,6 +4473,150 @@ int dpmm_regress_draw_points(dpmm_ctx *c, float *out, int64_t ld, int64_t draw_s
 int dpmm_regress_draw_points_device(dpmm_ctx *c, float *d_out, int64_t ld, int64_t draw_stride, int32_t *d_comp, uint64_t seed, int64_t i0, int64_t draw0,
                                     int64_t ndraws, int64_t *skipped) {
     return regress_draw_points(c, d_out, ld, draw_stride, d_comp, seed, i0, draw0, ndraws, skipped, true, "dpmm_regress_draw_points_device");
+}
+
+// ---- include/dpmm_hip_regress_cdf.h: conditional CDF and quantiles of the targets, range by range (regress_cdf.hip) --------------------------
+int dpmm_set_regression_levels(dpmm_ctx *c, int L, const double *levels, const double *z) {
+    static const char *fn = "dpmm_set_regression_levels";
+    if (!c) return tensor_no_ctx(fn);
+    const std::string who = std::string(fn) + ": ";
+    if (c->prior != DPMM_PRIOR_NIW) return fail(c, DPMM_EINVAL, who + "the regression is that of the NIW prior's Student-t predictive");
+    if (L < 1 || L > DPMM_REGRESS_MAX_LEVELS) return fail(c, DPMM_EINVAL, who + "L must be in 1.." + std::to_string(DPMM_REGRESS_MAX_LEVELS));
+    if (!levels || !z) return fail(c, DPMM_EINVAL, who + "null table");
+    if (!c->predictive || c->reg_gen == 0 || c->reg_gen != c->pred_gen) return fail(c, DPMM_ESTATE, who + "needs dpmm_set_regression for the predictive parameters in force");
+    const size_t K = (size_t)c->K;
+    for (int q = 0; q < L; ++q) {
+        if (!(levels[q] > 0.0 && levels[q] < 1.0)) return fail(c, DPMM_EINVAL, who + "a level outside (0, 1)");
+        if (q && !(levels[q] > levels[q - 1])) return fail(c, DPMM_EINVAL, who + "the levels must be strictly increasing");
+    }
+    for (size_t j = 0; j < K * (size_t)L; ++j)
+        if (!std::isfinite(z[j])) return fail(c, DPMM_EINVAL, who + "a z that is not finite");
+    HIPCHK(c, hipSetDevice(c->device));
+    c->reg_lev_gen = 0;      // (a failure below leaves no levels in force)
+    std::vector<double> img((size_t)L + K * (size_t)L + K);
+    std::copy(levels, levels + L, img.begin());
+    std::copy(z, z + K * (size_t)L, img.begin() + L);
+    for (size_t k = 0; k < K; ++k) {      // log of the density of t_nu at 0: -log B(nu / 2, 1 / 2) - log(nu) / 2
+        const double nu = (double)c->h_miss_cst[k * MISS_CST] + (double)c->D;
+        img[(size_t)L + K * (size_t)L + k] = -typ_log_beta(0.5 * nu, 0.5) - 0.5 * std::log(nu);
+    }
+    if (int rc = grow(c, c->d_reg_lev, sizeof(double) * img.size(), fn, "regression levels")) return rc;
+    HIPCHK(c, sync_stream(c, c->stream));
+    HIPCHK(c, hipMemcpy(c->d_reg_lev, img.data(), sizeof(double) * img.size(), hipMemcpyHostToDevice));
+    c->reg_L = L;
+    c->reg_lev_gen = c->pred_gen;
+    return DPMM_OK;
+}
+
+// Both calls: y null and L >= 1: the quantiles, out [n][L][ld]; else the CDF of y into out (cdf) and sf.  Host variants go through the
+// staging block: per range y in, then the outputs dense (D_t apart) and copied row by row.
+static int regress_cdf_points(dpmm_ctx *c, const float *y, int64_t ldy, float *out, float *sf, int64_t ld, int64_t *labels, int64_t *skipped, bool quant,
+                              bool device, const char *fn) {
+    if (!c) return tensor_no_ctx(fn);
+    c->miss_counted = false;      // (as score_points)
+    const std::string who = std::string(fn) + ": ";
+    if (c->prior != DPMM_PRIOR_NIW) return fail(c, DPMM_EINVAL, who + "the regression is that of the NIW prior's Student-t predictive");
+    if (!c->predictive) return fail(c, DPMM_ESTATE, who + "needs dpmm_set_predictive_niw first");
+    if (c->reg_gen == 0 || c->reg_gen != c->pred_gen) return fail(c, DPMM_ESTATE, who + "needs dpmm_set_regression for the predictive parameters in force");
+    if (quant && (c->reg_lev_gen == 0 || c->reg_lev_gen != c->pred_gen)) return fail(c, DPMM_ESTATE, who + "needs dpmm_set_regression_levels for the regression tables in force");
+    const int64_t Dt = c->reg_Dt, L = quant ? c->reg_L : 1;
+    if (ld < Dt || (!quant && ldy < Dt)) return fail(c, DPMM_EINVAL, who + "ld < D_t");
+    if ((ld >> 36) || (!quant && (ldy >> 40))) return fail(c, DPMM_EINVAL, who + "ld out of range");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (skipped) skipped[0] = 0;
+    if (c->n == 0) return DPMM_OK;
+    if (!c->have_points || !c->have_params || !c->dX) return fail(c, DPMM_ESTATE, who + "needs points and parameters");
+    if (!out) return fail(c, DPMM_EINVAL, who + (quant ? "out is null" : "cdf is null"));
+    if (!quant && !y) return fail(c, DPMM_EINVAL, who + "y is null");
+    const uint64_t n = (uint64_t)c->n;
+    if (device) {
+        if (!quant) if (int rc = check_device_extent(c, fn, "d_y", y, n * (uint64_t)ldy * sizeof(float), sizeof(float))) return rc;
+        if (int rc = check_device_extent(c, fn, quant ? "d_out" : "d_cdf", out, n * (uint64_t)L * (uint64_t)ld * sizeof(float), sizeof(float))) return rc;
+        if (sf) if (int rc = check_device_extent(c, fn, "d_sf", sf, n * (uint64_t)ld * sizeof(float), sizeof(float))) return rc;
+        if (labels) if (int rc = check_device_extent(c, fn, "d_labels", labels, n * sizeof(int64_t), sizeof(int64_t))) return rc;
+    }
+    TableWalk w;
+    if (int rc = walk_open(c, fn, WALK_MISS_NEVER, &w)) return rc;
+    const int64_t P = w.P;
+    const size_t tiles = (size_t)((P + 31) / 32);
+    if (int rc = grow(c, c->d_reg_skip, sizeof(unsigned) * tiles, fn, "counts of the regression pass")) return rc;
+    HIPCHK(c, hipMemsetAsync(c->d_reg_skip, 0, sizeof(unsigned) * tiles, c->stream));
+    // staging (host variants): [P] labels, then blocks of [P][L][D_t] floats: the output, sf, y
+    const size_t blk = sizeof(float) * (size_t)P * (size_t)L * (size_t)Dt;
+    char *st = nullptr;
+    if (!device) {
+        if (int rc = grow(c, c->d_score_out, sizeof(int64_t) * (size_t)P + 3 * blk, "dpmm_score_points", "staging of the outputs")) return rc;
+        st = c->d_score_out;
+    }
+    float *const s_out = reinterpret_cast<float *>(st + sizeof(int64_t) * (size_t)P), *const s_sf = reinterpret_cast<float *>(st + sizeof(int64_t) * (size_t)P + blk),
+                *const s_y = reinterpret_cast<float *>(st + sizeof(int64_t) * (size_t)P + 2 * blk);
+    const double *lev = c->d_reg_lev;
+    if (int rc = walk_ranges(c, w, c->n, fn, [&](int64_t p0, int64_t np, int64_t) -> int {
+            int64_t *lab = !labels ? nullptr : device ? labels + p0 : reinterpret_cast<int64_t *>(st);
+            const int64_t sld = device ? ld : Dt;
+            float *o = device ? out + p0 * L * ld : s_out;
+            hipError_t e;
+            if (quant) {
+                RegressQuantileArgs a{};
+                a.table = c->d_score_table; a.stride = P; a.n = np; a.K = c->K; a.D = c->D; a.Dt = (int)Dt; a.Tp = regress_pitch((int)Dt);
+                a.X = c->dX + p0 * c->ldx; a.ldx = c->ldx;
+                a.Bt = c->d_reg_bt; a.c = c->d_reg_c; a.V = c->d_reg_v; a.hd = c->d_reg_hd;
+                a.levels = lev; a.z = lev + L; a.lc = lev + L + (int64_t)c->K * L; a.L = (int)L;
+                a.out = o; a.ld = sld; a.labels = lab; a.skip = c->d_reg_skip;
+                e = launch_regress_quantile_range(a, c->stream);
+            } else {
+                RegressCdfArgs a{};
+                a.table = c->d_score_table; a.stride = P; a.n = np; a.K = c->K; a.D = c->D; a.Dt = (int)Dt; a.Tp = regress_pitch((int)Dt);
+                a.X = c->dX + p0 * c->ldx; a.ldx = c->ldx;
+                a.Bt = c->d_reg_bt; a.c = c->d_reg_c; a.V = c->d_reg_v; a.hd = c->d_reg_hd;
+                if (device) { a.y = y + p0 * ldy; a.ldy = ldy; }
+                else {
+                    HIPCHK(c, hipMemcpy2DAsync(s_y, sizeof(float) * (size_t)Dt, y + p0 * ldy, sizeof(float) * (size_t)ldy, sizeof(float) * (size_t)Dt, (size_t)np,
+                                               hipMemcpyHostToDevice, c->stream));
+                    a.y = s_y; a.ldy = Dt;
+                }
+                a.cdf = o; a.sf = !sf ? nullptr : device ? sf + p0 * ld : s_sf; a.ld = sld; a.labels = lab; a.skip = c->d_reg_skip;
+                e = launch_regress_cdf_range(a, c->stream);
+            }
+            if (int rc = table_result(c, fn, e)) return rc;
+            if (device) return DPMM_OK;
+            for (int j = 0; j < 2; ++j) {
+                float *dst = j == 0 ? out : sf;
+                if (!dst) continue;
+                HIPCHK(c, hipMemcpy2DAsync(dst + p0 * L * ld, sizeof(float) * (size_t)ld, j == 0 ? s_out : s_sf, sizeof(float) * (size_t)Dt, sizeof(float) * (size_t)Dt,
+                                           (size_t)(np * L), hipMemcpyDeviceToHost, c->stream));
+            }
+            if (labels) HIPCHK(c, hipMemcpyAsync(labels + p0, st, sizeof(int64_t) * (size_t)np, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, sync_stream(c, c->stream));      // the staging block is rewritten by the next range
+            if (ld > Dt)
+                for (int64_t r = p0 * L; r < (p0 + np) * L; ++r) {
+                    memset(out + r * ld + Dt, 0, sizeof(float) * (size_t)(ld - Dt));
+                    if (sf) memset(sf + r * ld + Dt, 0, sizeof(float) * (size_t)(ld - Dt));
+                }
+            return DPMM_OK;
+        })) return rc;
+    HIPCHK(c, sync_stream(c, c->stream));
+    if (skipped) {
+        std::vector<unsigned> cnt(tiles);
+        HIPCHK(c, hipMemcpy(cnt.data(), c->d_reg_skip, sizeof(unsigned) * tiles, hipMemcpyDeviceToHost));
+        int64_t total = 0;
+        for (unsigned v : cnt) total += v;
+        skipped[0] = total;
+    }
+    return DPMM_OK;
+}
+
+int dpmm_regress_cdf_points(dpmm_ctx *c, const float *y, int64_t ldy, float *cdf, float *sf, int64_t ld, int64_t *labels, int64_t *skipped) {
+    return regress_cdf_points(c, y, ldy, cdf, sf, ld, labels, skipped, false, false, "dpmm_regress_cdf_points");
+}
+int dpmm_regress_cdf_points_device(dpmm_ctx *c, const float *d_y, int64_t ldy, float *d_cdf, float *d_sf, int64_t ld, int64_t *d_labels, int64_t *skipped) {
+    return regress_cdf_points(c, d_y, ldy, d_cdf, d_sf, ld, d_labels, skipped, false, true, "dpmm_regress_cdf_points_device");
+}
+int dpmm_regress_quantile_points(dpmm_ctx *c, float *out, int64_t ld, int64_t *labels, int64_t *skipped) {
+    return regress_cdf_points(c, nullptr, 0, out, nullptr, ld, labels, skipped, true, false, "dpmm_regress_quantile_points");
+}
+int dpmm_regress_quantile_points_device(dpmm_ctx *c, float *d_out, int64_t ld, int64_t *d_labels, int64_t *skipped) {
+    return regress_cdf_points(c, nullptr, 0, d_out, nullptr, ld, d_labels, skipped, true, true, "dpmm_regress_quantile_points_device");
 }
 
 // ---- include/dpmm_hip_rank.h: exemplars, the m most and least typical points of every cluster (rank.hip) -----------------------------------

@@ -506,6 +506,49 @@ struct RegressDrawArgs {
     float *sc;                   // the scale s of every (draw, point), written by the first kernel of the launch and read by the second
 };
 hipError_t launch_regress_draw_range(const RegressDrawArgs &a, hipStream_t s);
+// ---- conditional CDF and quantiles of the targets (regress_cdf.hip; include/dpmm_hip_regress_cdf.h): one range of the score table, n points
+// from table column 0 and from X; table .. hd, labels and skip as RegressArgs
+constexpr int REGRESS_MAX_LEVELS = 16;    // DPMM_REGRESS_MAX_LEVELS
+struct RegressCdfArgs {
+    const float *table;
+    int64_t stride;
+    int64_t n;
+    int K, D;
+    int Dt, Tp;
+    const float *X;
+    int64_t ldx;
+    const float *Bt;
+    const float *c, *V;
+    const double *hd;
+    const float *y;              // [n][ldy] the observed targets of the range's points
+    int64_t ldy;
+    float *cdf, *sf;             // [n][ld]; sf null: not asked for
+    int64_t ld;
+    int64_t *labels;
+    unsigned *skip;
+};
+hipError_t launch_regress_cdf_range(const RegressCdfArgs &a, hipStream_t s);
+struct RegressQuantileArgs {
+    const float *table;
+    int64_t stride;
+    int64_t n;
+    int K, D;
+    int Dt, Tp;
+    const float *X;
+    int64_t ldx;
+    const float *Bt;
+    const float *c, *V;
+    const double *hd;
+    const double *levels;        // [L], increasing
+    const double *z;             // [K][L]: the level's quantile of t_{df_k + D}
+    const double *lc;            // [K]: log of the density of t_{df_k + D} at 0
+    int L;
+    float *out;                  // element (i, q, d) at out[(i * L + q) * ld + d]; columns [Dt, ld) are written as 0
+    int64_t ld;
+    int64_t *labels;
+    unsigned *skip;
+};
+hipError_t launch_regress_quantile_range(const RegressQuantileArgs &a, hipStream_t s);
 // ---- calibrated outlier scores (typicality.hip; include/dpmm_hip_typicality.h): one range of the score table, n points from table column 0:
 // the label and the class of every point, q = |R_k (x - m_k)|^2 for its own cluster k in Float32, the tail of q in Float64
 struct TypicalityArgs {

@@ -107,3 +107,106 @@ def regression_tables(m, R, given, targets, factor=False):
     if factor:
         return B, c, V, np.ascontiguousarray(Li.transpose(0, 2, 1))
     return B, c, V
+
+
+# ---- the quantiles of a Student-t (include/dpmm_hip_regress_cdf.h: the table z of dpmm_set_regression_levels), in the library's own
+# arithmetic: the incomplete beta function by the continued fraction csrc/typicality_math.h evaluates, a safeguarded Newton solve on it
+def _beta_cf(a, b, x):
+    """The continued fraction of I_x(a, b) (modified Lentz), elementwise in Float64."""
+    tiny = 1e-300
+    qab, qap, qam = a + b, a + 1.0, a - 1.0
+    c = np.ones_like(x)
+    d = 1.0 - qab * x / qap
+    d = 1.0 / np.where(np.abs(d) < tiny, tiny, d)
+    h = d.copy()
+    live = np.ones(x.shape, bool)
+    for m in range(1, 20001):
+        m2 = 2.0 * m
+        for aa in (m * (b - m) * x / ((qam + m2) * (a + m2)), -(a + m) * (qab + m) * x / ((a + m2) * (qap + m2))):
+            d = 1.0 + aa * d
+            d = 1.0 / np.where(np.abs(d) < tiny, tiny, d)
+            c = 1.0 + aa / c
+            c = np.where(np.abs(c) < tiny, tiny, c)
+            delta = d * c
+            h = np.where(live, h * delta, h)
+        live = live & (np.abs(delta - 1.0) >= 2.5e-16)
+        if not live.any():
+            break
+    return h
+
+
+def _log_beta(a, b):
+    """log B(a, b) as csrc/typicality_math.h forms it: for a >= 32 the two large terms are never formed -- lgamma(a + b) - lgamma(a) comes
+    from the Stirling series of the difference -- so that nu = 1e7 costs no digits."""
+    a, b = np.broadcast_arrays(np.asarray(a, np.float64), np.asarray(b, np.float64))
+    tail = lambda z: (1.0 / z) * (1.0 / 12.0 - (1.0 / z) ** 2 * (1.0 / 360.0 - (1.0 / z) ** 2 * (1.0 / 1260.0 - (1.0 / z) ** 2 * (1.0 / 1680.0))))      # noqa: E731
+    big = a >= 32.0
+    ab = np.where(big, a, 32.0)
+    d = (ab - 0.5) * np.log1p(b / ab) + b * np.log(ab + b) - b + (tail(ab + b) - tail(ab))
+    return np.where(big, gammaln(b) - d, gammaln(a) + gammaln(b) - gammaln(a + b))
+
+
+def student_t_tail(t, nu):
+    """P(|T| > |t|) for T ~ t_nu = I_{nu / (nu + t^2)}(nu / 2, 1 / 2), elementwise in Float64 (t, nu broadcast), evaluated on the side
+    of the incomplete beta function whose continued fraction converges fast."""
+    t, nu = np.broadcast_arrays(np.asarray(t, np.float64), np.asarray(nu, np.float64))
+    q = t * t
+    a, b = 0.5 * nu, np.full(nu.shape, 0.5)
+    out = np.ones(q.shape)
+    pos = (q > 0) & np.isfinite(q)
+    out[np.isinf(q)] = 0.0
+    if pos.any():
+        qq, aa, bb, nn = q[pos], a[pos], b[pos], nu[pos]
+        x, xc = nn / (nn + qq), qq / (nn + qq)
+        lpre = aa * -np.log1p(qq / nn) + bb * (np.log(qq) - np.log(nn + qq)) - _log_beta(aa, bb)
+        low = x < (aa + 1.0) / (aa + bb + 2.0)
+        res = np.empty(qq.shape)
+        if low.any():
+            res[low] = np.exp(lpre[low]) * _beta_cf(aa[low], bb[low], x[low]) / aa[low]
+        if (~low).any():
+            res[~low] = np.maximum(0.0, 1.0 - np.exp(lpre[~low]) * _beta_cf(bb[~low], aa[~low], xc[~low]) / bb[~low])
+        out[pos] = res
+    return out
+
+
+def student_t_pdf(t, nu):
+    """The density of t_nu at t, elementwise in Float64."""
+    t, nu = np.asarray(t, np.float64), np.asarray(nu, np.float64)
+    return np.exp(-_log_beta(0.5 * nu, 0.5) - 0.5 * np.log(nu) - 0.5 * (nu + 1) * np.log1p(t * t / nu))
+
+
+def student_t_ppf(levels, nu):
+    """z (K, L) Float64: z[k, q] the quantile of t_{nu_k} at levels[q], 0 < level < 1.  Exactly 0 at level 1 / 2 and antisymmetric:
+    the quantile at a level above 1 / 2 is minus the one at 1 - level.  Solved on the lower tail, where tail / 2 = level does not cancel:
+    Newton on the half tail from inside a bracket found by doubling, the midpoint whenever a step leaves the bracket."""
+    levels = np.atleast_1d(np.asarray(levels, np.float64))
+    nu = np.atleast_1d(np.asarray(nu, np.float64))
+    if levels.ndim != 1 or nu.ndim != 1 or not np.all((levels > 0) & (levels < 1)) or not np.all(nu > 0):
+        raise ValueError("student_t_ppf: levels inside (0, 1) and nu > 0 are needed")
+    upper = levels > 0.5
+    nu_all = nu
+    nu, where = np.unique(nu_all, return_inverse=True)      # (clusters share a handful of df: each is solved once)
+    p = np.broadcast_to(np.where(upper, 1.0 - levels, levels)[None, :], (len(nu), len(levels))).copy()      # <= 1 / 2: the lower tail's mass
+    n2 = np.broadcast_to(nu[:, None], p.shape).copy()
+    half = lambda t: 0.5 * student_t_tail(t, n2)      # noqa: E731  (P(T < -t), decreasing in t >= 0)
+    lo, hi = np.zeros(p.shape), np.ones(p.shape)
+    for _ in range(1100):
+        far = half(hi) > p
+        if not far.any():
+            break
+        lo, hi = np.where(far, hi, lo), np.where(far, 2.0 * hi, hi)
+    t = 0.5 * (lo + hi)
+    for _ in range(80):                                     # Newton doubles the digits; the tail itself is good to about 1e-15
+        f = half(t) - p
+        lo, hi = np.where(f > 0, t, lo), np.where(f > 0, hi, t)
+        with np.errstate(all="ignore"):
+            step = t + f / student_t_pdf(t, n2)
+        nxt = np.where((step > lo) & (step < hi), step, 0.5 * (lo + hi))
+        done = np.abs(nxt - t) <= 1e-14 * np.abs(t)
+        t = nxt
+        if done.all():
+            break
+    t = t[where.reshape(-1)]
+    z = np.where(upper[None, :], t, -t)
+    z[:, levels == 0.5] = 0.0
+    return z

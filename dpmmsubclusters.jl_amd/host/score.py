@@ -86,6 +86,16 @@ RegressionDraws.__doc__ = """What `Regressor.sample` returns: values (draws, D_t
 model's -- tensors on the data's device for a device tensor, else numpy arrays -- and skipped, an int: the points whose columns are NaN in
 every draw."""
 
+ConditionalCDF = collections.namedtuple("ConditionalCDF", "cdf sf labels skipped")
+ConditionalCDF.__doc__ = """What `Regressor.cdf` returns: cdf and sf (D_t, n) float32, P(target <= y) and P(target > y) given the given features,
+each summed from the side that does not cancel; labels (n,) int64 1-based, the marginal model's -- tensors on the data's device for a
+device tensor, else numpy arrays -- and skipped, an int: the points whose columns are NaN."""
+
+RegressionQuantiles = collections.namedtuple("RegressionQuantiles", "values levels labels skipped")
+RegressionQuantiles.__doc__ = """What `Regressor.quantile` returns: values (L, D_t, n) float32, values[q, d, i] the y at which the conditional CDF
+of target d of point i reaches levels[q] (the orientation of `sample`'s draws); levels, a tuple of floats as asked for; labels and skipped
+as `ConditionalCDF`."""
+
 ASSIGN_MODES = {"hard": binding.BATCHSTATS_HARD, "soft": binding.BATCHSTATS_SOFT}
 
 
@@ -1236,6 +1246,7 @@ class Regressor:
         if draws:
             mg._wk.set_regression_factor(W[0])
         self._tables_for = mg.post
+        self._levels_for = None      # (dpmm_set_regression invalidates the levels of `quantile`)
 
     def close(self):
         self.marginal.close()
@@ -1310,6 +1321,102 @@ class Regressor:
         return RegressionDraws(vals, comp, out["labels"], total[0])
 
 
+    # ---- calibrated probabilities (include/dpmm_hip_regress_cdf.h)
+    def _cdf_worker(self, what):
+        self._refresh()
+        wk = self.marginal._wk
+        if not all(hasattr(wk, f) for f in ("regress_cdf_points_into", "set_regression_levels", "regress_quantile_points_into")):
+            raise RuntimeError(f"this Regressor's worker cannot give {what} (no dpmm_regress_cdf_points)")
+        return wk
+
+    def cdf(self, data, y):
+        """`ConditionalCDF(cdf, sf, labels, skipped)`: for every point of `data` (D_o rows in the order of `given`, every input kind
+        `predict` takes) and every target d, the probability under the fitted mixture that the target lies at or below the observed
+        y[d, i], and above it: F = sum_k p_ik T_{df_k + D_o}((y - mu_ikd) / sigma_ikd), the mixture of the clusters' conditional Student-t
+        laws -- exact where `std` describes a bimodal law badly, and needing no draws.  y: a (D_t, n) numpy array or torch tensor of any
+        real dtype in the order of `targets` (on the data's device if `data` is a device tensor; host data takes an array or a CPU tensor), converted to float32 slab by slab.
+        cdf and sf are each summed in Float64 from the side of every component that does not cancel, so a value 40 standard deviations
+        out has sf = 1e-30, not 0 (Float32: below 2^-150 a value is returned as 0).  A NaN in y gives NaN in that entry only, -Inf / +Inf give exactly 0 / 1; a point that takes no
+        part (see `predict`) has NaN columns and is counted in `skipped`.  Needs no df + D_o > 2."""
+        mg = self.marginal
+        wk, cap = self._cdf_worker("the conditional CDF"), mg.capacity
+        opened = mg._open(data)
+        n, dev, new = opened[0], opened[1], opened[2]
+        y_dev = getattr(y, "device", None) if hasattr(y, "data_ptr") else None
+        if y_dev is not None and dev is None and y_dev.type == "cpu":      # host data: a CPU tensor is as good as an array
+            import torch
+            y, y_dev = (y if y.dtype in (torch.float32, torch.float64) else y.to(torch.float32)).numpy(), None
+        if y_dev is None:
+            y = np.asarray(y)
+            if y.dtype.kind not in "fiub":
+                raise TypeError("y must hold real numbers")
+        if tuple(y.shape) != (self.D_t, n):
+            raise ValueError(f"y must be (D_t, n) = ({self.D_t}, {n}), in the order of `targets`")
+        if (dev is None) != (y_dev is None) or (dev is not None and y_dev != dev):
+            raise ValueError("y must live where the data lives: host memory (a numpy array or a CPU tensor) for host data, the data's device for a device tensor")
+        ys = new(cap, (self.D_t,), "float32") if n else None
+        total = [0]
+
+        def evaluate(views, lo, hi):
+            m = hi - lo
+            if dev is not None:
+                import torch
+                ys[:m] = y[:, lo:hi].T.to(torch.float32)
+            else:
+                ys[:m] = y[:, lo:hi].T
+            ys[m:] = 0
+            sk = wk.regress_cdf_points_into(ys, views["cdf"], views["sf"], views["labels"])
+            if m < cap:                          # (the padding of a short slab is zeros, as in `predict`: not ours if it took no part)
+                pad = views["cdf"][m:]
+                sk -= int((pad[:, 0] != pad[:, 0]).sum())
+            total[0] += sk
+        out = mg._walk(opened, [("cdf", (self.D_t,), "float32"), ("sf", (self.D_t,), "float32"), ("labels", (), "int64")], evaluate)
+        return ConditionalCDF(out["cdf"].T, out["sf"].T, out["labels"], total[0])
+
+    def quantile(self, data, levels=(0.05, 0.5, 0.95)):
+        """`RegressionQuantiles(values, levels, labels, skipped)`: values[q, d, i] is the y at which the conditional CDF of target d of
+        point i (see `cdf`) reaches levels[q] -- medians and prediction intervals without draws.  levels: 1 to 16 numbers strictly
+        inside (0, 1), in any order.  A point that could belong to one cluster only gets that cluster's Student-t quantile (level 0.5:
+        the bits of `predict`'s mean); otherwise a safeguarded Newton solve on the mixture CDF runs on the GPU, to the Float32 value at
+        which the CDF crosses the level.  Values are non-decreasing in the level, and a value depends on (the point, the model, the
+        level) alone.  Skipped points as in `cdf`."""
+        mg = self.marginal
+        wk, cap = self._cdf_worker("conditional quantiles"), mg.capacity
+        lv = np.atleast_1d(np.asarray(levels, np.float64))
+        if lv.ndim != 1 or not 1 <= len(lv) <= binding.REGRESS_MAX_LEVELS:
+            raise ValueError(f"levels: 1 to {binding.REGRESS_MAX_LEVELS} numbers")
+        if not np.all((lv > 0) & (lv < 1)):
+            raise ValueError("levels must lie strictly inside (0, 1)")
+        inc, back = np.unique(lv, return_inverse=True)      # the worker solves them in increasing order
+        key = (tuple(inc), self._tables_for)
+        if getattr(self, "_levels_for", None) is None or self._levels_for[0] != key[0] or self._levels_for[1] is not key[1]:
+            df = np.asarray(mg._predictive_args()[1][3], np.float32).astype(np.float64)      # (what the worker holds, as `tables` widens it)
+            wk.set_regression_levels(inc, _condition.student_t_ppf(inc, df + self.D_o))
+            self._levels_for = key
+        L = len(inc)
+        total = [0]
+
+        def evaluate(views, lo, hi):
+            sk = wk.regress_quantile_points_into(views["values"], views["labels"])
+            if hi - lo < cap:
+                pad = views["values"][hi - lo:]
+                sk -= int((pad[:, 0, 0] != pad[:, 0, 0]).sum())
+            total[0] += sk
+        out = mg._walk(mg._open(data), [("values", (L, self.D_t), "float32"), ("labels", (), "int64")], evaluate)
+        vals = out["values"]
+        vals = vals.permute(1, 2, 0) if hasattr(vals, "permute") else vals.transpose(1, 2, 0)
+        vals = vals[back.tolist()] if hasattr(vals, "permute") else vals[back]
+        return RegressionQuantiles(vals, tuple(float(v) for v in lv), out["labels"], total[0])
+
+    def interval(self, data, level=0.9):
+        """(lower, upper), each (D_t, n): the central prediction interval of every target at coverage `level`, 0 < level < 1 -- `quantile`
+        at (1 - level) / 2 and (1 + level) / 2."""
+        if not 0.0 < float(level) < 1.0:
+            raise ValueError("level must lie strictly inside (0, 1)")
+        q = self.quantile(data, ((1.0 - float(level)) / 2.0, (1.0 + float(level)) / 2.0))
+        return q.values[0], q.values[1]
+
+
 def regress(dp_model, data, given, targets=None, return_std=False, **kw):
     """Mixture regression from the features `given` to `targets` (opens a Predictor and its Regressor, runs, closes): see `Regressor`;
     `data` has the rows of `given`; kw: capacity, device, worker_factory."""
@@ -1327,6 +1434,24 @@ def regress_sample(dp_model, data, given, targets=None, draws=1, seed=0, **kw):
     with Predictor(dp_model, worker_factory=factory, **kw) as p:
         with p.regressor(given, targets, worker_factory=factory) as r:
             return r.sample(data, draws=draws, seed=seed, return_components=comps)
+
+
+def regress_cdf(dp_model, data, y, given, targets=None, **kw):
+    """Conditional CDF of the observed `targets` y given the features `given` (opens a Predictor and its Regressor, runs, closes): see
+    `Regressor.cdf`; `data` has the rows of `given`, y those of `targets`; kw: capacity, device, worker_factory."""
+    factory = kw.pop("worker_factory", None)
+    with Predictor(dp_model, worker_factory=factory, **kw) as p:
+        with p.regressor(given, targets, worker_factory=factory) as r:
+            return r.cdf(data, y)
+
+
+def regress_quantile(dp_model, data, given, targets=None, levels=(0.05, 0.5, 0.95), **kw):
+    """Conditional quantiles of the features `targets` given the features `given` (opens a Predictor and its Regressor, runs, closes):
+    see `Regressor.quantile`; kw: capacity, device, worker_factory."""
+    factory = kw.pop("worker_factory", None)
+    with Predictor(dp_model, worker_factory=factory, **kw) as p:
+        with p.regressor(given, targets, worker_factory=factory) as r:
+            return r.quantile(data, levels)
 
 
 def score_samples(dp_model, data, **kw):
