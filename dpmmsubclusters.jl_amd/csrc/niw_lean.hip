@@ -444,11 +444,15 @@ __device__ __forceinline__ void niw_lean_body(NiwSweepArgs A, uint32_t *__restri
                 { LSTAMP(t1); s1 = t1; }
 #endif
                 // the last four features of "this lane's point" (the tail screens' operand), as niw_sweep_direct_kernel takes them
+                // (D <= 48: block 3 is padding and features D-4 .. D-1 sit in block 2 -- launch-uniform; x3 below stays block 3, the partner of
+                //  the bf16 bottom screen's fragment 5, a zero fragment there)
                 const int src = ci + 16 * A.tail_g;
+                const bool tb_last = A.ldx > 48;
 #pragma unroll
                 for (int n = 0; n < 4; ++n) {
+                    const f32x4 xl = tb_last ? x[n][3] : x[n][2];
                     f32x4 v;
-                    v.x = __shfl(x[n][3].x, src); v.y = __shfl(x[n][3].y, src); v.z = __shfl(x[n][3].z, src); v.w = __shfl(x[n][3].w, src);
+                    v.x = __shfl(xl.x, src); v.y = __shfl(xl.y, src); v.z = __shfl(xl.z, src); v.w = __shfl(xl.w, src);
                     if (g == n) xt = v;
                 }
 #pragma unroll

@@ -663,14 +663,26 @@ __global__ __launch_bounds__(256, (NB <= 8 ? 2 : 1)) void niw_sweep_kernel(NiwSw
             }
             STAMP(s2);
             const float my_thr = valid ? aref - A.screen_margin : INFINITY;
+            // The block of 16 features that holds the LAST ones, D-4 .. D-1 (a tail record exists for D a multiple of 4 only: ldx = D).  NB is 8
+            // for every D in 65 .. 128 and 16 beyond, so for D <= 16·(NB − 1), block NB − 1 is padding -- zeros in x, in the means and in R: the
+            // tail records' features sit in block tb, and so does the last non-empty row block of R.  (Reading block NB - 1 there compared the
+            // clusters' tail means with zeros instead of the points: clusters were excluded by how far their means lie from the ORIGIN.)
+            const int tb = (int)((A.ldx - 1) >> 4);
+            f32x4 xl[NG];
+#pragma unroll
+            for (int n = 0; n < NG; ++n) {
+                xl[n] = x[n][NB - 1];
+#pragma unroll
+                for (int t = 0; t < NB - 1; ++t) if (t == tb) xl[n] = x[n][t];
+            }
             f32x4 xt = (f32x4){0.f, 0.f, 0.f, 0.f};
             {
                 const int src = ci + 16 * A.tail_g;
 #pragma unroll
                 for (int n = 0; n < NG; ++n) {
                     f32x4 v;
-                    v.x = __shfl(x[n][NB - 1].x, src); v.y = __shfl(x[n][NB - 1].y, src);
-                    v.z = __shfl(x[n][NB - 1].z, src); v.w = __shfl(x[n][NB - 1].w, src);
+                    v.x = __shfl(xl[n].x, src); v.y = __shfl(xl[n].y, src);
+                    v.z = __shfl(xl[n].z, src); v.w = __shfl(xl[n].w, src);
                     if (g == n) xt = v;                        // owner lane 16 n + ci holds point (n, ci)
                 }
             }
@@ -710,13 +722,14 @@ __global__ __launch_bounds__(256, (NB <= 8 ? 2 : 1)) void niw_sweep_kernel(NiwSw
                     uint32_t sb = __builtin_amdgcn_readfirstlane(survm[w2]);
                     for (; sb; sb &= sb - 1u) {
                         const int k = (w2 << 5) + __builtin_ctz(sb);
-                        const f32x4 a4 = *reinterpret_cast<const f32x4 *>(A.Rp + (size_t)(3 * k) * C::MATSZ + (size_t)(C::NP - 1) * 256 + lane * 4);
-                        const f32x4 m4 = *reinterpret_cast<const f32x4 *>(A.mup + (size_t)(3 * k) * C::DP + 16 * (NB - 1) + 4 * g);
+                        // (the diagonal fragment of row block tb: the blocks to its right are padding, so rows 16 tb .. need block tb's features only)
+                        const f32x4 a4 = *reinterpret_cast<const f32x4 *>(A.Rp + (size_t)(3 * k) * C::MATSZ + (size_t)(tb * NB - (tb * (tb - 1)) / 2) * 256 + lane * 4);
+                        const f32x4 m4 = *reinterpret_cast<const f32x4 *>(A.mup + (size_t)(3 * k) * C::DP + 16 * tb + 4 * g);
                         const float ck = A.cst[3 * k];
                         bool skip = true;
 #pragma unroll
                         for (int n = 0; n < NG; ++n) {
-                            const f32x4 zz = x[n][NB - 1] - m4;
+                            const f32x4 zz = xl[n] - m4;
                             f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                             for (int jj = 0; jj < 4; ++jj) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[jj], zz[jj], acc, 0, 0, 0);
@@ -1092,14 +1105,20 @@ __global__ __launch_bounds__(256, OCC) void niw_sweep_direct_kernel(NiwSweepArgs
     const bool compact = !FAST && !tab_lds && A.lds_rows > 0 && !A.scratch_by_tile;
     uint8_t *slot_of = reinterpret_cast<uint8_t *>(lds_tab + (size_t)4 * A.lds_rows * WPTS + (A.screen_lds ? (size_t)K * (256 + 16) : 0)) +
                        (size_t)(tid >> 6) * ((K + 3) & ~3);
-    // screen operands of all K clusters (last fragment pair 1 KiB + last 16 means), staged once per workgroup
+    // The block of 16 features that holds the LAST ones: NB - 1 at NB = 1, 2, but NB is 4 for every D in 33 .. 64 and for D <= 48 block 3 is
+    // padding (zeros in x, in the means and in R) -- the tail records' features D-4 .. D-1 and the last non-empty row block of R sit in block 2.
+    // tb_last is launch-uniform.  (Reading block 3 there compared the clusters' tail means with zeros instead of the points.)  The bf16 bottom
+    // screen keeps fragment 5 = block row 3 with block 3 of x: a zero fragment for D <= 48, which excludes nothing and is sound.
+    const bool tb_last = NB != 4 || A.ldx > 16 * (NB - 1);
+    const int tb = tb_last ? NB - 1 : NB - 2, ptb = tb * NB - (tb * (tb - 1)) / 2;      // ptb: the diagonal fragment of row block tb
+    // screen operands of all K clusters (the diagonal fragment of row block tb, 1 KiB, + block tb's 16 means), staged once per workgroup
     float *scrA = lds_tab + (size_t)4 * A.lds_rows * WPTS;
     float *scrM = scrA + (size_t)K * 256;
     if (A.screen_lds) {
         for (int e = tid; e < K * 64; e += 256)
-            reinterpret_cast<f32x4 *>(scrA)[e] = *reinterpret_cast<const f32x4 *>(A.Rp + ((size_t)(3 * (e >> 6)) * NP + (NP - 1)) * 256 + (e & 63) * 4);
+            reinterpret_cast<f32x4 *>(scrA)[e] = *reinterpret_cast<const f32x4 *>(A.Rp + ((size_t)(3 * (e >> 6)) * NP + ptb) * 256 + (e & 63) * 4);
         for (int e = tid; e < K * 4; e += 256)
-            reinterpret_cast<f32x4 *>(scrM)[e] = *reinterpret_cast<const f32x4 *>(A.mup + (size_t)(3 * (e >> 2)) * DP + 16 * (NB - 1) + 4 * (e & 3));
+            reinterpret_cast<f32x4 *>(scrM)[e] = *reinterpret_cast<const f32x4 *>(A.mup + (size_t)(3 * (e >> 2)) * DP + 16 * tb + 4 * (e & 3));
         __syncthreads();
     }
 
@@ -1412,9 +1431,10 @@ __global__ __launch_bounds__(256, OCC) void niw_sweep_direct_kernel(NiwSweepArgs
                 const int src = ci + 16 * A.tail_g;
 #pragma unroll
                 for (int n = 0; n < NG; ++n) {
+                    const f32x4 xl = tb_last ? x[n][NB - 1] : x[n][NB > 1 ? NB - 2 : 0];
                     f32x4 v;
-                    v.x = __shfl(x[n][NB - 1].x, src); v.y = __shfl(x[n][NB - 1].y, src);
-                    v.z = __shfl(x[n][NB - 1].z, src); v.w = __shfl(x[n][NB - 1].w, src);
+                    v.x = __shfl(xl.x, src); v.y = __shfl(xl.y, src);
+                    v.z = __shfl(xl.z, src); v.w = __shfl(xl.w, src);
                     if (g == n) { xt = v; my_best = bestn[n]; }
                 }
             }
@@ -1459,7 +1479,7 @@ __global__ __launch_bounds__(256, OCC) void niw_sweep_direct_kernel(NiwSweepArgs
                 if (xr1 >= 0) ev[xr1 >> 5] |= 1u << (xr1 & 31);
             }
             const float margin = A.screen_margin;
-            constexpr int LASTP = NP - 1, LB = NB - 1;
+            constexpr int LB = NB - 1;      // (the bf16 bottom screen's block: see tb)
             STAMP(r1a);
             STAMP(r1b);
             // candidates = clusters that are neither references nor provably far; each gets the MFMA screen
@@ -1470,12 +1490,12 @@ __global__ __launch_bounds__(256, OCC) void niw_sweep_direct_kernel(NiwSweepArgs
                     a = *reinterpret_cast<const f32x4 *>(scrA + (size_t)k * 256 + lane * 4);
                     m4 = *reinterpret_cast<const f32x4 *>(scrM + (size_t)k * 16 + 4 * g);
                 } else {
-                    a = *reinterpret_cast<const f32x4 *>(A.Rp + ((size_t)(3 * k) * NP + LASTP) * 256 + lane * 4);
-                    m4 = *reinterpret_cast<const f32x4 *>(A.mup + (size_t)(3 * k) * DP + 16 * LB + 4 * g);
+                    a = *reinterpret_cast<const f32x4 *>(A.Rp + ((size_t)(3 * k) * NP + ptb) * 256 + lane * 4);
+                    m4 = *reinterpret_cast<const f32x4 *>(A.mup + (size_t)(3 * k) * DP + 16 * tb + 4 * g);
                 }
                 f32x4 zz[NG];
 #pragma unroll
-                for (int n = 0; n < NG; ++n) { acc[n] = (f32x4){0.f, 0.f, 0.f, 0.f}; zz[n] = x[n][LB] - m4; }
+                for (int n = 0; n < NG; ++n) { acc[n] = (f32x4){0.f, 0.f, 0.f, 0.f}; zz[n] = (tb_last ? x[n][LB] : x[n][NB > 1 ? NB - 2 : 0]) - m4; }
 #pragma unroll
                 for (int jj = 0; jj < 4; ++jj)
 #pragma unroll
@@ -1559,7 +1579,7 @@ __global__ __launch_bounds__(256, OCC) void niw_sweep_direct_kernel(NiwSweepArgs
                             const u32x4_t *Rb0 = reinterpret_cast<const u32x4_t *>(refb_records(A.tail, K));
                             auto loadk = [&](int k, u32x4_t &a, f32x4 &m4, float &ck) {
                                 a = Rb0[(size_t)k * (REFB_WORDS / 4) + 64 * 5 + lane];
-                                m4 = A.screen_lds ? *reinterpret_cast<const f32x4 *>(scrM + (size_t)k * 16 + 4 * g)
+                                m4 = (A.screen_lds && tb_last) ? *reinterpret_cast<const f32x4 *>(scrM + (size_t)k * 16 + 4 * g)
                                                   : *reinterpret_cast<const f32x4 *>(A.mup + (size_t)(3 * k) * DP + 16 * LB + 4 * g);
                                 ck = cst_of(k);
                             };

@@ -6,6 +6,7 @@ the same seeded inputs.  Tolerances (fp32 contraction on the matrix cores vs the
   draw given the GPU's own table: bit-exact (same exp_det / scan arithmetic)
   N counts and all relabel bookkeeping: bit-exact; sum x, sum xx' vs Float64 oracle: rtol 1e-12
       (the statistics kernels at their edge shapes, EXACTLY, on integer-valued data: tests/test_gpu_niw_stats_shapes.py)
+  routes by K outside D 33…64: tests/test_gpu_niw_routes.py
 """
 import numpy as np
 import pytest
