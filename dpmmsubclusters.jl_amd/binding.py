@@ -337,6 +337,14 @@ ABI_REGRESS_CDF = [
     ("dpmm_regress_quantile_points_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, _c_i64p]),
 ]
 REGRESS_MAX_LEVELS = 16      # DPMM_REGRESS_MAX_LEVELS
+# include/dpmm_hip_recommend.h: the m unseen features of largest next-count probability (Multinomial; additive; bound next to ABI)
+_RECOMMEND_ARGS = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, _c_i64p]
+ABI_RECOMMEND = [
+    ("dpmm_set_recommend", ctypes.c_int, [ctypes.c_void_p, _c_f64p]),
+    ("dpmm_recommend_points", ctypes.c_int, _RECOMMEND_ARGS),
+    ("dpmm_recommend_points_device", ctypes.c_int, _RECOMMEND_ARGS),
+]
+RECOMMEND_MAX_TOP = SCORE_MAX_TOP      # DPMM_RECOMMEND_MAX_TOP
 
 HOST_ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int)   # dpmm_host_allreduce_fn
 
@@ -418,7 +426,7 @@ def load_library():
         except Exception:  # pragma: no cover  (torch is optional for single-GPU use)
             pass
         lib = ctypes.CDLL(p)
-        for name, res, args in ABI + ABI_TENSOR + ABI_SCORE + ABI_RANK + ABI_OVERLAP + ABI_BATCHSTATS + ABI_COUNTSTATS + ABI_TYPICALITY + ABI_EXPLAIN + ABI_HOLDOUT + ABI_COUNTHOLDOUT + ABI_TRACE + ABI_MISSING + ABI_IMPUTE + ABI_REGRESS + ABI_REGRESS_DRAW + ABI_REGRESS_CDF + ABI_CSC + ABI_SAMPLE + ABI_PROJECT:
+        for name, res, args in ABI + ABI_TENSOR + ABI_SCORE + ABI_RANK + ABI_OVERLAP + ABI_BATCHSTATS + ABI_COUNTSTATS + ABI_TYPICALITY + ABI_EXPLAIN + ABI_HOLDOUT + ABI_COUNTHOLDOUT + ABI_TRACE + ABI_MISSING + ABI_IMPUTE + ABI_REGRESS + ABI_REGRESS_DRAW + ABI_REGRESS_CDF + ABI_RECOMMEND + ABI_CSC + ABI_SAMPLE + ABI_PROJECT:
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -928,6 +936,35 @@ class Worker:
             assert mean.dtype == np.float32 and (std is None or std.dtype == np.float32) and (labels is None or labels.dtype == np.int64)
             fn, ptr = self._lib.dpmm_regress_points, lambda a: None if a is None or a.size == 0 else ctypes.c_void_p(a.ctypes.data)
         self._chk(fn(self._h, ptr(mean), ptr(std), int(mean.shape[1]), ptr(labels), _p(skipped, _c_i64p)))
+        return int(skipped[0])
+
+    # ---- next-count probabilities (include/dpmm_hip_recommend.h)
+    def set_recommend(self, theta):
+        """dpmm_set_recommend: theta (K, D) in Float64, the clusters' next-count probabilities, for the predictive parameters in force."""
+        theta = np.ascontiguousarray(theta, np.float64)
+        assert theta.shape == (self.K, self.D), "set_recommend: theta (K, D)"
+        self._chk(self._lib.dpmm_set_recommend(self._h, _p(theta, _c_f64p)))
+
+    def recommend_points_into(self, views, m, exclude_seen=True):
+        """dpmm_recommend_points[_device] into storage the caller made: `views` maps `features` (n, ld >= m) int32, `prob` (n, ld) float32
+        and, if asked for, `labels` (n,) int64 to C-contiguous numpy arrays (host variant) or torch tensors on this worker's GPU (device
+        variant).  Returns the number of points that took no part."""
+        features, prob, labels = views["features"], views["prob"], views.get("labels")
+        dev = hasattr(features, "data_ptr")
+        outs = [a for a in (features, prob, labels) if a is not None]
+        assert all(hasattr(a, "data_ptr") == dev for a in outs), "recommend_points_into: numpy arrays or tensors, not both"
+        assert all(int(a.shape[0]) == self.n and (a.is_contiguous() if dev else a.flags.c_contiguous) for a in outs)
+        assert len(features.shape) == 2 and tuple(prob.shape) == tuple(features.shape)
+        skipped = np.zeros(1, np.int64)
+        if dev:
+            import torch
+            assert features.dtype == torch.int32 and prob.dtype == torch.float32 and (labels is None or labels.dtype == torch.int64)
+            torch.cuda.current_stream(features.device).synchronize()
+            fn, ptr = self._lib.dpmm_recommend_points_device, lambda a: None if a is None or a.numel() == 0 else ctypes.c_void_p(a.data_ptr())
+        else:
+            assert features.dtype == np.int32 and prob.dtype == np.float32 and (labels is None or labels.dtype == np.int64)
+            fn, ptr = self._lib.dpmm_recommend_points, lambda a: None if a is None or a.size == 0 else ctypes.c_void_p(a.ctypes.data)
+        self._chk(fn(self._h, int(m), 1 if exclude_seen else 0, ptr(features), ptr(prob), int(features.shape[1]), ptr(labels), _p(skipped, _c_i64p)))
         return int(skipped[0])
 
     # ---- draws of the targets (include/dpmm_hip_regress_draw.h)

@@ -23,6 +23,7 @@
 #include "../../include/dpmm_hip_regress.h"
 #include "../../include/dpmm_hip_regress_draw.h"
 #include "../../include/dpmm_hip_regress_cdf.h"
+#include "../../include/dpmm_hip_recommend.h"
 #include "../../include/dpmm_hip_sample.h"
 #include "../../include/dpmm_hip_project.h"
 
@@ -240,6 +241,11 @@ struct dpmm_ctx {
     unsigned long long reg_lev_gen = 0;
     int reg_L = 0;
     DevBuf<double> d_reg_lev;
+    // next-count probabilities (include/dpmm_hip_recommend.h): the padded Float32 image of theta, made by dpmm_set_recommend for the parameter
+    // set rec_gen (0: none); the per-tile counts of the points that take no part, of one range, allocated by the first dpmm_recommend_points
+    unsigned long long rec_gen = 0;
+    DevBuf<float> d_rec_theta;
+    DevBuf<unsigned> d_rec_skip;
     // drawing points (include/dpmm_hip_sample.h): the sampler's tables (dpmm_set_sampler_*) and what a call needs beside its outputs
     // (cluster and tile starts; sparse: 4 bytes per point of counts and the scan's tile totals), allocated on first use
     DevBuf<float> d_sm_m, d_sm_At, d_sm_df;
@@ -5150,6 +5156,103 @@ int dpmm_countstats_read(dpmm_ctx *c, const dpmm_countstats_out *o) {
     if (e == hipSuccess && o->N) e = hipMemcpy(o->N, c->d_cs_acc, sizeof(double) * Kz, hipMemcpyDeviceToHost);
     if (e == hipSuccess && o->sums) e = hipMemcpy(o->sums, c->d_cs_acc + Kz, sizeof(double) * Kz * D, hipMemcpyDeviceToHost);
     return stats_counters_read(c, fn, e, c->d_cs_acc + countstats_acc_doubles(K, (int)D), K, o->count, o->skipped, o->held_out, o->incomplete);
+}
+
+// ---- include/dpmm_hip_recommend.h: the m unseen features of largest next-count probability, range by range (recommend.hip) ---------------
+int dpmm_set_recommend(dpmm_ctx *c, const double *theta) {
+    static const char *fn = "dpmm_set_recommend";
+    if (!c) return tensor_no_ctx(fn);
+    const std::string who = std::string(fn) + ": ";
+    if (c->prior != DPMM_PRIOR_MULT) return fail(c, DPMM_EINVAL, who + "the next-count probabilities are those of the Multinomial prior: an NIW ctx has dpmm_set_regression");
+    if (!theta) return fail(c, DPMM_EINVAL, who + "null table");
+    if (!c->predictive) return fail(c, DPMM_ESTATE, who + "needs dpmm_set_predictive_mult first");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t K = (size_t)c->K, Kp = K + (K & 1), D = (size_t)c->D, Dp = (size_t)recommend_pitch(c->D);
+    c->rec_gen = 0;      // (a failure below leaves no table in force)
+    if (int rc = grow(c, c->d_rec_theta, sizeof(float) * Kp * Dp, fn, "next-count probabilities")) return rc;
+    std::vector<float> img(Kp * Dp, 0.f);      // each value rounded to Float32 once; zeros in the pad
+    for (size_t k = 0; k < K; ++k)
+        for (size_t d = 0; d < D; ++d) img[k * Dp + d] = (float)theta[k * D + d];
+    HIPCHK(c, sync_stream(c, c->stream));
+    HIPCHK(c, hipMemcpy(c->d_rec_theta, img.data(), sizeof(float) * img.size(), hipMemcpyHostToDevice));
+    c->rec_gen = c->pred_gen;
+    return DPMM_OK;
+}
+
+static int recommend_points(dpmm_ctx *c, int m, int exclude_seen, int32_t *features, float *prob, int64_t ld, int64_t *labels, int64_t *skipped, bool device,
+                            const char *fn) {
+    if (!c) return tensor_no_ctx(fn);
+    c->miss_counted = false;      // (as score_points)
+    const std::string who = std::string(fn) + ": ";
+    if (c->prior != DPMM_PRIOR_MULT) return fail(c, DPMM_EINVAL, who + "the next-count probabilities are those of the Multinomial prior: an NIW ctx has dpmm_regress_points");
+    if (!c->predictive) return fail(c, DPMM_ESTATE, who + "needs dpmm_set_predictive_mult first");
+    if (c->rec_gen == 0 || c->rec_gen != c->pred_gen) return fail(c, DPMM_ESTATE, who + "needs dpmm_set_recommend for the predictive parameters in force");
+    const int top = std::min(c->D, DPMM_RECOMMEND_MAX_TOP);
+    if (m < 1 || m > top) return fail(c, DPMM_EINVAL, who + "m must be in 1.." + std::to_string(top));
+    if (ld < m) return fail(c, DPMM_EINVAL, who + "ld < m");
+    if (ld >> 40) return fail(c, DPMM_EINVAL, who + "ld out of range");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (skipped) skipped[0] = 0;
+    if (c->n == 0) return DPMM_OK;
+    const int store = count_store(c);
+    if (!count_store_ready(c, store)) return fail(c, DPMM_ESTATE, who + "needs points and parameters");
+    if (!features || !prob) return fail(c, DPMM_EINVAL, who + (features ? "prob is null" : "features is null"));
+    const uint64_t n = (uint64_t)c->n;
+    if (device) {
+        if (int rc = check_device_extent(c, fn, "d_features", features, n * (uint64_t)ld * sizeof(int32_t), sizeof(int32_t))) return rc;
+        if (int rc = check_device_extent(c, fn, "d_prob", prob, n * (uint64_t)ld * sizeof(float), sizeof(float))) return rc;
+        if (labels) if (int rc = check_device_extent(c, fn, "d_labels", labels, n * sizeof(int64_t), sizeof(int64_t))) return rc;
+    }
+    TableWalk w;
+    if (int rc = walk_open(c, fn, WALK_MISS_NEVER, &w)) return rc;
+    const int64_t P = w.P;
+    const size_t tiles = (size_t)((P + 31) / 32);
+    if (int rc = grow(c, c->d_rec_skip, sizeof(unsigned) * tiles, fn, "counts of the recommendation pass")) return rc;
+    HIPCHK(c, hipMemsetAsync(c->d_rec_skip, 0, sizeof(unsigned) * tiles, c->stream));
+    // the rows: in the caller's device memory ld words apart; staged (host variant) dense, m apart, and copied row by row
+    const int64_t sld = device ? ld : m;
+    OutStage<3> out{{{features, sizeof(int32_t) * (size_t)sld}, {prob, sizeof(float) * (size_t)sld}, {labels, sizeof(int64_t)}}, device};
+    if (!device) {
+        if (int rc = grow(c, c->d_score_out, out.layout((size_t)P), "dpmm_score_points", "staging of the outputs")) return rc;
+        out.buf = c->d_score_out;
+    }
+    if (int rc = walk_ranges(c, w, c->n, fn, [&](int64_t p0, int64_t np, int64_t) -> int {
+            RecommendArgs a{};
+            a.table = c->d_score_table; a.stride = P; a.rstep = w.rstep; a.n = np; a.K = c->K; a.Kp = c->K + (c->K & 1); a.D = c->D; a.Dp = recommend_pitch(c->D);
+            count_points(c, store, p0, a);
+            a.theta = c->d_rec_theta; a.m = m; a.exclude = exclude_seen ? 1 : 0;
+            a.features = out.at<int32_t>(0, p0); a.prob = out.at<float>(1, p0); a.ld = sld; a.labels = out.at<int64_t>(2, p0); a.skip = c->d_rec_skip;
+            if (int rc = table_result(c, fn, launch_recommend_range(a, c->stream))) return rc;
+            if (device) return DPMM_OK;
+            HIPCHK(c, hipMemcpy2DAsync(features + p0 * ld, sizeof(int32_t) * (size_t)ld, out.buf + out.col[0].off, sizeof(int32_t) * (size_t)m, sizeof(int32_t) * (size_t)m,
+                                       (size_t)np, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipMemcpy2DAsync(prob + p0 * ld, sizeof(float) * (size_t)ld, out.buf + out.col[1].off, sizeof(float) * (size_t)m, sizeof(float) * (size_t)m, (size_t)np,
+                                       hipMemcpyDeviceToHost, c->stream));
+            if (labels) HIPCHK(c, hipMemcpyAsync(labels + p0, out.buf + out.col[2].off, sizeof(int64_t) * (size_t)np, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, sync_stream(c, c->stream));      // the staging block is rewritten by the next range
+            if (ld > m)
+                for (int64_t i = p0; i < p0 + np; ++i) {
+                    memset(features + i * ld + m, 0, sizeof(int32_t) * (size_t)(ld - m));
+                    memset(prob + i * ld + m, 0, sizeof(float) * (size_t)(ld - m));
+                }
+            return DPMM_OK;
+        })) return rc;
+    HIPCHK(c, sync_stream(c, c->stream));
+    if (skipped) {
+        std::vector<unsigned> cnt(tiles);
+        HIPCHK(c, hipMemcpy(cnt.data(), c->d_rec_skip, sizeof(unsigned) * tiles, hipMemcpyDeviceToHost));
+        int64_t total = 0;
+        for (unsigned v : cnt) total += v;
+        skipped[0] = total;
+    }
+    return DPMM_OK;
+}
+
+int dpmm_recommend_points(dpmm_ctx *c, int m, int exclude_seen, int32_t *features, float *prob, int64_t ld, int64_t *labels, int64_t *skipped) {
+    return recommend_points(c, m, exclude_seen, features, prob, ld, labels, skipped, false, "dpmm_recommend_points");
+}
+int dpmm_recommend_points_device(dpmm_ctx *c, int m, int exclude_seen, int32_t *d_features, float *d_prob, int64_t ld, int64_t *d_labels, int64_t *skipped) {
+    return recommend_points(c, m, exclude_seen, d_features, d_prob, ld, d_labels, skipped, true, "dpmm_recommend_points_device");
 }
 
 // ---- include/dpmm_hip_countholdout.h: the held-out points of a batch of count data, compacted into the caller's device memory (holdout.hip)

@@ -478,6 +478,35 @@ struct RegressArgs {
     unsigned *skip;              // [ceil(n / 32)] points of tile j that take no part, ADDED to word j
 };
 hipError_t launch_regress_range(const RegressArgs &a, hipStream_t s);
+// ---- top-m next-count probabilities (recommend.hip; include/dpmm_hip_recommend.h): one range of the score table, n points from table
+// column 0 and from whichever count store is live
+constexpr int RECOMMEND_MAX_TOP = 16;     // DPMM_RECOMMEND_MAX_TOP
+inline int64_t recommend_pitch(int D) { return 32 * (((int64_t)D + 31) / 32); }
+struct RecommendArgs {
+    const float *table;
+    int64_t stride;      // floats between two rows of the table
+    int rstep;           // cluster k is row k * rstep
+    int64_t n;
+    int K, Kp;           // Kp = K rounded up to even
+    int D;
+    int64_t Dp;          // recommend_pitch(D)
+    int store;           // as CountStatsArgs, the pointers at the range's first point (X, X8, cp) / the whole entry arrays (ri, val)
+    const float *X;
+    int64_t ldx;
+    const uint8_t *X8;
+    int64_t ld8;
+    const int64_t *cp;
+    const uint16_t *ri;
+    const float *val;
+    const float *theta;  // [Kp][Dp], zero in the pad
+    int m, exclude;      // 1 <= m <= min(D, RECOMMEND_MAX_TOP); exclude: the features a point has seen are no candidates
+    int32_t *features;   // [n][ld] rows of the range's points, 0-based, -1 behind the candidates
+    float *prob;         // [n][ld], NaN behind the candidates
+    int64_t ld;
+    int64_t *labels;     // [n] or null
+    unsigned *skip;      // [ceil(n / 32)] points of tile j that take no part, ADDED to word j
+};
+hipError_t launch_recommend_range(const RecommendArgs &a, hipStream_t s);
 // ---- draws of the targets (regress_draw.hip; include/dpmm_hip_regress_draw.h): one range of the score table, n points from table column 0
 // and from X, the draws draw0 .. draw0 + ndraws - 1 of each
 constexpr int64_t REGRESS_DRAW_MAX = 67108864;      // DPMM_REGRESS_MAX_DRAWS

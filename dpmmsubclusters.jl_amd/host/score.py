@@ -96,6 +96,12 @@ RegressionQuantiles.__doc__ = """What `Regressor.quantile` returns: values (L, D
 of target d of point i reaches levels[q] (the orientation of `sample`'s draws); levels, a tuple of floats as asked for; labels and skipped
 as `ConditionalCDF`."""
 
+Recommendation = collections.namedtuple("Recommendation", "features prob labels skipped")
+Recommendation.__doc__ = """What `Predictor.recommend` returns: features (n, m) int32, 0-based, the m candidates of largest next-count probability,
+largest first, ties to the lower index, -1 where a point has fewer than m candidates; prob (n, m) float32, their probabilities, NaN
+there; labels (n,) int64 1-based, what `predict_labels` gives -- tensors on the data's device for a device tensor, else numpy arrays --
+and skipped, an int: the points that are -1 / NaN throughout."""
+
 ASSIGN_MODES = {"hard": binding.BATCHSTATS_HARD, "soft": binding.BATCHSTATS_SOFT}
 
 
@@ -274,6 +280,7 @@ class Predictor:
         self._csc_stage = None           # capacity + 1 offsets on the device, for the short slab of a sparse_csc tensor
         self._out_stage = {}             # outputs of a short slab: name -> array / tensor of `capacity` rows
         self._sampler_set = False        # the sampler's tables are formed and uploaded by the first sample()
+        self._recommend_set = False      # ... and the next-count probabilities by the first recommend()
 
     def _predictive_args(self):
         """("niw" | "mult", the arguments of the worker's set_predictive_*) for `self.post` and `self.weights`."""
@@ -588,6 +595,7 @@ class Predictor:
         self.weights = (w / w.sum()).astype(np.float32)
         self._reload()
         self._sampler_set = False            # the sampler's tables are those of the old posterior
+        self._recommend_set = False          # ... and so are the next-count probabilities
         return stats
 
     def _reload(self):
@@ -738,6 +746,7 @@ class Predictor:
             self.post, self.points_count, self.weights, self.K = old
             raise
         self._sampler_set = False                          # the sampler's tables are those of the old K
+        self._recommend_set = False                        # ... and so are the next-count probabilities
         new_id = np.zeros(s.K, np.int64)
         new_id[keep] = K0 + 1 + np.arange(len(keep))
         kept = new_id[lab - 1] > 0
@@ -1089,6 +1098,47 @@ class Predictor:
                                      nzval=nzval.data_ptr(), nnz_extent=nnz)
         labels = torch.repeat_interleave(torch.arange(1, self.K + 1, dtype=torch.int64, device=dev), torch.as_tensor(n_k, device=dev), output_size=n)
         return torch.sparse_csc_tensor(colptr, rowval, nzval, size=(D, n)), labels
+
+    # ---- the features a count point is expected to get next (include/dpmm_hip_recommend.h)
+    def recommend(self, data, m, exclude_seen=True):
+        """`Recommendation(features, prob, labels, skipped)`: for every point of count `data` the m features the fitted Multinomial mixture
+        expects next, among those the point does not hold yet (exclude_seen=True) or among all D (False), 1 <= m <= min(D, 16).
+
+        Under cluster k one more count falls on feature d with probability theta_kd = alpha'_kd / sum_d alpha'_kd -- the `theta` of
+        `sampler_tables`, formed in Float64 -- and under the mixture with r_id = sum_k p_ik theta_kd, p_ik what `predict` returns.  A feature
+        is SEEN by a point when its value there is not 0 (a stored entry that is not 0 for sparse data).  features holds the m candidates
+        of largest r, largest first, ties to the lower index, 0-based as `explain` returns them; a point with fewer than m candidates has
+        -1 / NaN behind them; a point with a NaN or no finite entry in its row of the table is -1 / NaN throughout and counted in
+        `skipped`.  labels are those of `predict_labels`, from the same pass.  `data` is whatever `predict` takes for a Multinomial model
+        and is read from the store the worker keeps it in -- Float32, bytes, sparse columns up to D = 65536 -- nothing is densified, and
+        nothing of size n D or n K exists anywhere.  prob lies within (K + 2) 2^-24 of the Float64 value, relatively; the bits do not
+        depend on `capacity`.  After `absorb_counts` and `grow_counts` the answer is that of the updated model."""
+        if self._wk is None:
+            raise RuntimeError("this Predictor is closed")
+        if self.kind != _priors.PRIOR_MULT:
+            raise ValueError("recommend is for the Multinomial prior: an NIW model has regressor, which predicts features from given ones")
+        m = int(m)
+        top = min(self.D, binding.RECOMMEND_MAX_TOP)
+        if not 1 <= m <= top:
+            raise ValueError(f"m must be in 1..{top}")
+        wk = self._wk
+        if not hasattr(wk, "recommend_points_into"):
+            raise RuntimeError("this Predictor's worker cannot recommend (no dpmm_recommend_points)")
+        opened = self._open(data)
+        if not self._recommend_set:
+            a = np.asarray(self.post["alpha"], np.float64)
+            wk.set_recommend(a / a.sum(1, keepdims=True))
+            self._recommend_set = True
+        exclude_seen = bool(exclude_seen)
+        total = [0]
+
+        def evaluate(views, lo, hi):
+            sk = wk.recommend_points_into(views, m, exclude_seen)
+            if hi - lo < self.capacity:         # the padding of a short slab is empty points: they have candidates unless they take no part, and are not ours
+                sk -= int((views["features"][hi - lo:, 0] < 0).sum())
+            total[0] += sk
+        out = self._walk(opened, [("features", (m,), "int32"), ("prob", (m,), "float32"), ("labels", (), "int64")], evaluate)
+        return Recommendation(out["features"], out["prob"], out["labels"], total[0])
 
     # ---- slabs
     def _spec(self, labels, logdens, m, probs):
@@ -1452,6 +1502,13 @@ def regress_quantile(dp_model, data, given, targets=None, levels=(0.05, 0.5, 0.9
     with Predictor(dp_model, worker_factory=factory, **kw) as p:
         with p.regressor(given, targets, worker_factory=factory) as r:
             return r.quantile(data, levels)
+
+
+def recommend(dp_model, data, m, exclude_seen=True, **kw):
+    """`Predictor.recommend` in one call: the m features every count point of `data` is expected to get next under the fitted Multinomial
+    model (keywords: those of Predictor)."""
+    with Predictor(dp_model, **kw) as p:
+        return p.recommend(data, m, exclude_seen=exclude_seen)
 
 
 def score_samples(dp_model, data, **kw):
