@@ -3865,13 +3865,20 @@ static int walk_ranges(dpmm_ctx *c, const TableWalk &w, int64_t limit, const cha
     return DPMM_OK;
 }
 
-// ---- outputs of a table call: written into the caller's device memory, or staged on the device and copied back to the caller's host memory.
+// ---- the caller's arrays of a table call -- its outputs and, where a kernel reads one, a per-point input (`in`): used in place in the caller's
+// device memory, or staged on the device and copied back to (inputs: in from) the caller's host memory.
 // A column is the caller's pointer (null: not asked for) and its bytes per element; in the staging buffer the columns follow each other in
-// list order, each block 8-byte aligned.
+// list order, each block 8-byte aligned.  A pitched column has rows: an element is `rows` rows of `bytes` bytes, `pitch` bytes apart at the
+// caller's and dense in the staging buffer, and the words of the caller's rows behind `bytes` are written as zeros.
 struct OutCol {
     void *dst;
-    size_t bytes;
+    size_t bytes;        // per element, or per row of a pitched column
+    size_t pitch = 0;    // bytes between two rows at the caller's; 0: not pitched
+    size_t rows = 1;     // rows per element of a pitched column (L for the quantiles)
+    bool in = false;     // an input of the kernel: dst is read, by load()
     size_t off = 0;
+    size_t staged() const { return rows * bytes; }                      // bytes of an element in the staging buffer
+    size_t step() const { return rows * (pitch ? pitch : bytes); }      // and at the caller's
 };
 template <int N>
 struct OutStage {
@@ -3882,24 +3889,172 @@ struct OutStage {
     // bytes of the staging buffer for `count` elements per column
     size_t layout(size_t count) {
         size_t total = 0;
-        for (OutCol &q : col) { q.off = total; if (q.dst || every) total += (count * q.bytes + 7) & ~(size_t)7; }
+        for (OutCol &q : col) { q.off = total; if (q.dst || every) total += (count * q.staged() + 7) & ~(size_t)7; }
         return total;
     }
-    // where the kernel writes column i for the elements from e0 on (null: not at all)
+    // where the kernel writes (reads) column i for the elements from e0 on (null: not at all)
     template <class T>
     T *at(int i, int64_t e0) const {
         const OutCol &q = col[i];
-        if (device) return q.dst ? reinterpret_cast<T *>(static_cast<char *>(q.dst) + (size_t)e0 * q.bytes) : nullptr;
+        if (device) return q.dst ? reinterpret_cast<T *>(static_cast<char *>(q.dst) + (size_t)e0 * q.step()) : nullptr;
         return q.dst || every ? reinterpret_cast<T *>(buf + q.off) : nullptr;
     }
-    // host variant, behind the launch: `count` elements of every column asked for to the caller's element e0, in list order; then the wait,
-    // since the blocks are rewritten by the next range
-    hipError_t flush(dpmm_ctx *c, int64_t e0, size_t count) const {
+    // host variant, in front of the launch: `count` elements of every input column from the caller's element e0
+    hipError_t load(dpmm_ctx *c, int64_t e0, size_t count) const {
         hipError_t e = hipSuccess;
         for (const OutCol &q : col)
-            if (e == hipSuccess && q.dst) e = hipMemcpyAsync(static_cast<char *>(q.dst) + (size_t)e0 * q.bytes, buf + q.off, count * q.bytes, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = sync_stream(c, c->stream);
+            if (e == hipSuccess && q.dst && q.in)
+                e = hipMemcpy2DAsync(buf + q.off, q.bytes, static_cast<char *>(q.dst) + (size_t)e0 * q.step(), q.pitch ? q.pitch : q.bytes, q.bytes, count * q.rows,
+                                     hipMemcpyHostToDevice, c->stream);
         return e;
+    }
+    // host variant, behind the launch: `count` elements of every column asked for to the caller's element e0, in list order; then the wait,
+    // since the blocks are rewritten by the next range; then the zeros behind the rows of the pitched columns
+    hipError_t flush(dpmm_ctx *c, int64_t e0, size_t count) const {
+        hipError_t e = hipSuccess;
+        for (const OutCol &q : col) {
+            if (e != hipSuccess || !q.dst || q.in) continue;
+            char *dst = static_cast<char *>(q.dst) + (size_t)e0 * q.step();
+            if (q.pitch && q.pitch != q.bytes) e = hipMemcpy2DAsync(dst, q.pitch, buf + q.off, q.bytes, q.bytes, count * q.rows, hipMemcpyDeviceToHost, c->stream);
+            else e = hipMemcpyAsync(dst, buf + q.off, count * q.staged(), hipMemcpyDeviceToHost, c->stream);
+        }
+        if (e == hipSuccess) e = sync_stream(c, c->stream);
+        for (const OutCol &q : col)
+            if (e == hipSuccess && q.dst && !q.in && q.pitch > q.bytes)
+                for (size_t r = (size_t)e0 * q.rows; r < ((size_t)e0 + count) * q.rows; ++r) memset(static_cast<char *>(q.dst) + r * q.pitch + q.bytes, 0, q.pitch - q.bytes);
+        return e;
+    }
+};
+
+// ---- the points of a call that take no part, counted per 32-point tile of a range by the kernels (regress_device.h, recommend.hip): one
+// word per tile of a range of P points, ADDED to by the launches of every range
+static int skip_open(dpmm_ctx *c, DevBuf<unsigned> &buf, int64_t P, const char *fn, const char *what) {
+    const size_t bytes = sizeof(unsigned) * (size_t)((P + 31) / 32);
+    if (int rc = grow(c, buf, bytes, fn, what)) return rc;
+    HIPCHK(c, hipMemsetAsync(buf, 0, bytes, c->stream));
+    return DPMM_OK;
+}
+// behind the last range: the wait for the ctx stream, then the words added up into skipped[0] (null: not asked for)
+static int skip_close(dpmm_ctx *c, DevBuf<unsigned> &buf, int64_t P, int64_t *skipped) {
+    HIPCHK(c, sync_stream(c, c->stream));
+    if (!skipped) return DPMM_OK;
+    std::vector<unsigned> cnt((size_t)((P + 31) / 32));
+    HIPCHK(c, hipMemcpy(cnt.data(), buf, sizeof(unsigned) * cnt.size(), hipMemcpyDeviceToHost));
+    int64_t total = 0;
+    for (unsigned v : cnt) total += v;
+    skipped[0] = total;
+    return DPMM_OK;
+}
+
+// ---- what the calls of the mixture regression refuse first, in this order: no ctx, the prior, no predictive set, no tables for the set in
+// force, then what the call needs beside the tables
+enum RegressNeeds { REGRESS_TABLES, REGRESS_FACTOR, REGRESS_LEVELS };
+static int regress_front(dpmm_ctx *c, const char *fn, RegressNeeds needs) {
+    if (!c) return tensor_no_ctx(fn);
+    c->miss_counted = false;      // (as score_points)
+    const std::string who = std::string(fn) + ": ";
+    if (c->prior != DPMM_PRIOR_NIW) return fail(c, DPMM_EINVAL, who + "the regression is that of the NIW prior's Student-t predictive");
+    if (!c->predictive) return fail(c, DPMM_ESTATE, who + "needs dpmm_set_predictive_niw first");
+    if (c->reg_gen == 0 || c->reg_gen != c->pred_gen) return fail(c, DPMM_ESTATE, who + "needs dpmm_set_regression for the predictive parameters in force");
+    if (needs == REGRESS_FACTOR && !c->reg_factor) return fail(c, DPMM_ESTATE, who + "needs dpmm_set_regression_factor for the regression tables in force");
+    if (needs == REGRESS_LEVELS && (c->reg_lev_gen == 0 || c->reg_lev_gen != c->pred_gen))
+        return fail(c, DPMM_ESTATE, who + "needs dpmm_set_regression_levels for the regression tables in force");
+    return DPMM_OK;
+}
+// One range of the table (np points from point p0, rows P floats apart) and its points as the regression kernels take them
+static RegressTile regress_tile(dpmm_ctx *c, int64_t P, int64_t p0, int64_t np, int64_t *labels, unsigned *skip) {
+    RegressTile t{};
+    t.table = c->d_score_table; t.stride = P; t.n = np; t.K = c->K; t.D = c->D; t.Dt = c->reg_Dt; t.Tp = regress_pitch(c->reg_Dt);
+    t.X = c->dX + p0 * c->ldx; t.ldx = c->ldx;
+    t.c = c->d_reg_c; t.hd = c->d_reg_hd; t.labels = labels; t.skip = skip;
+    return t;
+}
+// the same fields of RegressCdfArgs and RegressQuantileArgs, which hold them flat (dpmm_kernels.h says why), and the tables beside them
+template <class Args>
+static Args regress_flat_args(dpmm_ctx *c, const RegressTile &t) {
+    Args a{};
+    a.table = t.table; a.stride = t.stride; a.n = t.n; a.K = t.K; a.D = t.D; a.Dt = t.Dt; a.Tp = t.Tp; a.X = t.X; a.ldx = t.ldx;
+    a.c = t.c; a.hd = t.hd; a.labels = t.labels; a.skip = t.skip;
+    a.Bt = c->d_reg_bt; a.V = c->d_reg_v;
+    return a;
+}
+
+// ---- draws of every point (include/dpmm_hip_impute.h, include/dpmm_hip_regress_draw.h): element (jd, i, f) of the caller's at
+// out[jd * draw_stride + i * ld + f], W floats of a row drawn (`wname` in the messages), the components at comp[jd * n_local + i].  Per
+// range the draws go into the caller's device memory, or in batches of draws through the staging block ([batch][np][W] floats, then
+// [batch][np] components), are copied back, and the words of the caller's rows behind W are written as zeros.
+struct DrawDest {       // where a launch writes the draws j0 .. j0 + nb - 1 of a range
+    float *out;
+    int64_t ld, draw_stride;
+    int32_t *comp;
+    int64_t comp_stride;
+};
+struct DrawBatch {
+    float *out;
+    int64_t ld, draw_stride;
+    int32_t *comp;
+    int64_t ndraws;
+    bool device;
+    int64_t W;
+    const char *wname;
+    int64_t batch = 0, P = 0;
+    // the refusals that need no device; cap: the draws a key holds, `capname` in the message
+    int check(dpmm_ctx *c, const char *fn, int64_t i0, int64_t draw0, int64_t cap, const char *capname) const {
+        const std::string who = std::string(fn) + ": ";
+        if (ndraws < 1 || draw0 < 0 || draw0 > cap || ndraws > cap - draw0)
+            return fail(c, DPMM_EINVAL, who + "draw0 >= 0, ndraws >= 1 and draw0 + ndraws <= " + capname + " are needed");
+        if (i0 < 0 || (i0 >> 62)) return fail(c, DPMM_EINVAL, who + "i0 out of range");
+        if (ld < W) return fail(c, DPMM_EINVAL, who + "ld < " + wname);
+        if ((ld >> 40) || draw_stride < 0 || (draw_stride >> 37)) return fail(c, DPMM_EINVAL, who + "ld / draw_stride out of range");
+        const bool interleaved = draw_stride >= W && draw_stride <= ld / ndraws;
+        if (!interleaved && (unsigned __int128)draw_stride < (unsigned __int128)c->n * (unsigned __int128)ld)
+            return fail(c, DPMM_EINVAL, who + "the draws overlap: draw_stride >= n_local * ld (stacked) or " + wname + " <= draw_stride <= ld / ndraws (interleaved) is needed");
+        return DPMM_OK;
+    }
+    // with points (n_local > 0): the state, the pointers and, device variant, their extents
+    int ready(dpmm_ctx *c, const char *fn) const {
+        const std::string who = std::string(fn) + ": ";
+        if (!c->have_points || !c->have_params || !c->dX) return fail(c, DPMM_ESTATE, who + "needs points and parameters");
+        if (!out) return fail(c, DPMM_EINVAL, who + "out is null");
+        if (!device) return DPMM_OK;
+        const uint64_t words = (uint64_t)(ndraws - 1) * (uint64_t)draw_stride + (uint64_t)(c->n - 1) * (uint64_t)ld + (uint64_t)std::min(ld, draw_stride);
+        if (int rc = check_device_extent(c, fn, "d_out", out, words * sizeof(float), sizeof(float))) return rc;
+        if (comp) if (int rc = check_device_extent(c, fn, "d_comp", comp, (uint64_t)ndraws * (uint64_t)c->n * sizeof(int32_t), sizeof(int32_t))) return rc;
+        return DPMM_OK;
+    }
+    // the draws of a batch for ranges of P_ points: `most` at most (what the call's own scratch per draw allows), host variant 64 MiB of
+    // staged draws, one draw at least; the staging block grown to hold them (`who`: the name in its out-of-memory message)
+    int size(dpmm_ctx *c, const char *who, int64_t P_, int64_t most) {
+        P = P_;
+        batch = std::max<int64_t>(1, std::min(ndraws, most));
+        if (device) return DPMM_OK;
+        batch = std::max<int64_t>(1, std::min<int64_t>(batch, ((int64_t)64 << 20) / ((int64_t)sizeof(float) * P * W)));
+        return grow(c, c->d_score_out, (size_t)batch * (size_t)P * (sizeof(float) * (size_t)W + sizeof(int32_t)), who, "staging of the outputs");
+    }
+    // one range (np points from point p0), batch by batch: launch(j0, nb, dest) -> int or hipError_t
+    template <class Launch>
+    int range(dpmm_ctx *c, const char *fn, int64_t p0, int64_t np, Launch launch) const {
+        const int64_t n = c->n, width = std::min(ld, draw_stride);
+        for (int64_t j0 = 0; j0 < ndraws; j0 += batch) {
+            const int64_t nb = std::min(batch, ndraws - j0);
+            DrawDest d{out + j0 * draw_stride + p0 * ld, ld, draw_stride, comp ? comp + j0 * n + p0 : nullptr, n};
+            if (!device) {
+                float *st = reinterpret_cast<float *>(c->d_score_out.get());
+                d = DrawDest{st, W, np * W, comp ? reinterpret_cast<int32_t *>(st + batch * P * W) : nullptr, np};
+            }
+            if (int rc = table_result(c, fn, launch(j0, nb, d))) return rc;
+            if (device) continue;
+            for (int64_t jd = 0; jd < nb; ++jd)
+                HIPCHK(c, hipMemcpy2DAsync(out + (j0 + jd) * draw_stride + p0 * ld, sizeof(float) * (size_t)ld, d.out + jd * np * W, sizeof(float) * (size_t)W,
+                                           sizeof(float) * (size_t)W, (size_t)np, hipMemcpyDeviceToHost, c->stream));
+            if (comp) HIPCHK(c, hipMemcpy2DAsync(comp + j0 * n + p0, sizeof(int32_t) * (size_t)n, d.comp, sizeof(int32_t) * (size_t)np, sizeof(int32_t) * (size_t)np,
+                                                 (size_t)nb, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, sync_stream(c, c->stream));      // the staging block is rewritten by the next batch
+            if (width > W)
+                for (int64_t jd = j0; jd < j0 + nb; ++jd)
+                    for (int64_t i = p0; i < p0 + np; ++i) memset(out + jd * draw_stride + i * ld + W, 0, sizeof(float) * (size_t)(width - W));
+        }
+        return DPMM_OK;
     }
 };
 }  // extern "C++"
@@ -4162,8 +4317,7 @@ static int impute_points(dpmm_ctx *c, float *out, int64_t ld, bool device, const
 int dpmm_impute_points(dpmm_ctx *c, float *out, int64_t ld) { return impute_points(c, out, ld, false, "dpmm_impute_points"); }
 int dpmm_impute_points_device(dpmm_ctx *c, float *d_out, int64_t ld) { return impute_points(c, d_out, ld, true, "dpmm_impute_points_device"); }
 
-// ---- include/dpmm_hip_impute.h: draws of the missing features.  Per range: the table once, list and patch, then the draws -- into the
-// caller's device memory, or in batches of draws through the staging block ([batch][np][D] floats, then [batch][np] components).
+// ---- include/dpmm_hip_impute.h: draws of the missing features.  Per range: the table once, list and patch, then the draws (DrawBatch).
 static int impute_draw_points(dpmm_ctx *c, float *out, int64_t ld, int64_t draw_stride, int32_t *comp, uint64_t seed, int64_t i0, int64_t draw0,
                               int64_t ndraws, bool device, const char *fn) {
     if (!c) return tensor_no_ctx(fn);
@@ -4171,61 +4325,23 @@ static int impute_draw_points(dpmm_ctx *c, float *out, int64_t ld, int64_t draw_
     const std::string who = std::string(fn) + ": ";
     if (c->prior != DPMM_PRIOR_NIW) return fail(c, DPMM_EINVAL, who + "the Multinomial prior has no missing features");
     if (!c->predictive) return fail(c, DPMM_ESTATE, who + "needs dpmm_set_predictive_niw first");
-    const int64_t D = c->D, n = c->n;
-    if (ndraws < 1 || draw0 < 0 || draw0 > DPMM_IMPUTE_MAX_DRAWS || ndraws > DPMM_IMPUTE_MAX_DRAWS - draw0)
-        return fail(c, DPMM_EINVAL, who + "draw0 >= 0, ndraws >= 1 and draw0 + ndraws <= DPMM_IMPUTE_MAX_DRAWS are needed");
-    if (i0 < 0 || (i0 >> 62)) return fail(c, DPMM_EINVAL, who + "i0 out of range");
-    if (ld < D) return fail(c, DPMM_EINVAL, who + "ld < D");
-    if ((ld >> 40) || draw_stride < 0 || (draw_stride >> 37)) return fail(c, DPMM_EINVAL, who + "ld / draw_stride out of range");
-    const bool interleaved = draw_stride >= D && draw_stride <= ld / ndraws;
-    if (!interleaved && (unsigned __int128)draw_stride < (unsigned __int128)n * (unsigned __int128)ld)
-        return fail(c, DPMM_EINVAL, who + "the draws overlap: draw_stride >= n_local * ld (stacked) or D <= draw_stride <= ld / ndraws (interleaved) is needed");
+    DrawBatch b{out, ld, draw_stride, comp, ndraws, device, c->D, "D"};
+    if (int rc = b.check(c, fn, i0, draw0, DPMM_IMPUTE_MAX_DRAWS, "DPMM_IMPUTE_MAX_DRAWS")) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    if (n == 0) return DPMM_OK;
-    if (!c->have_points || !c->have_params || !c->dX) return fail(c, DPMM_ESTATE, who + "needs points and parameters");
-    if (!out) return fail(c, DPMM_EINVAL, who + "out is null");
-    const int64_t width = std::min(ld, draw_stride);
-    if (device) {
-        const uint64_t words = (uint64_t)(ndraws - 1) * (uint64_t)draw_stride + (uint64_t)(n - 1) * (uint64_t)ld + (uint64_t)width;
-        if (int rc = check_device_extent(c, fn, "d_out", out, words * sizeof(float), sizeof(float))) return rc;
-        if (comp) if (int rc = check_device_extent(c, fn, "d_comp", comp, (uint64_t)ndraws * (uint64_t)n * sizeof(int32_t), sizeof(int32_t))) return rc;
-    }
+    if (c->n == 0) return DPMM_OK;
+    if (int rc = b.ready(c, fn)) return rc;
     TableWalk tw;
     if (int rc = walk_open(c, fn, WALK_MISS_ALWAYS, &tw)) return rc;
-    const int64_t P = tw.P;
-    int64_t batch = ndraws;
-    if (!device) {
-        batch = std::max<int64_t>(1, std::min<int64_t>(ndraws, ((int64_t)64 << 20) / ((int64_t)sizeof(float) * P * D)));
-        if (int rc = grow(c, c->d_score_out, (size_t)batch * (size_t)P * (sizeof(float) * (size_t)D + sizeof(int32_t)), "dpmm_score_points", "staging of the outputs")) return rc;
-    }
-    if (int rc = walk_ranges(c, tw, n, fn, [&](int64_t p0, int64_t np, int64_t) -> int {
-            MissArgs a = niw_range_args<MissArgs>(c, P, p0, np);
+    if (int rc = b.size(c, "dpmm_score_points", tw.P, ndraws)) return rc;
+    if (int rc = walk_ranges(c, tw, c->n, fn, [&](int64_t p0, int64_t np, int64_t) -> int {
+            MissArgs a = niw_range_args<MissArgs>(c, tw.P, p0, np);
             a.list = c->d_miss_list; a.cnt = c->d_miss_cnt;      // the list the walk's pass has just made of this range
-            for (int64_t j0 = 0; j0 < ndraws; j0 += batch) {
-                const int64_t nb = std::min(batch, ndraws - j0);
+            return b.range(c, fn, p0, np, [&](int64_t j0, int64_t nb, const DrawDest &d) {
                 MissDraw w{};
                 w.seed = seed; w.i0 = i0 + p0; w.draw0 = draw0 + j0; w.ndraws = (int)nb;
-                if (device) {
-                    w.out = out + j0 * draw_stride + p0 * ld; w.ld = ld; w.draw_stride = draw_stride;
-                    w.comp = comp ? comp + j0 * n + p0 : nullptr; w.comp_stride = n;
-                } else {
-                    w.out = reinterpret_cast<float *>(c->d_score_out.get()); w.ld = D; w.draw_stride = np * D;
-                    w.comp = comp ? reinterpret_cast<int32_t *>(w.out + batch * P * D) : nullptr; w.comp_stride = np;
-                }
-                if (int rc = table_result(c, fn, launch_miss_draw(a, w, 8 * c->cus, c->stream))) return rc;
-                if (!device) {
-                    for (int64_t jd = 0; jd < nb; ++jd)
-                        HIPCHK(c, hipMemcpy2DAsync(out + (j0 + jd) * draw_stride + p0 * ld, sizeof(float) * (size_t)ld, w.out + jd * np * D, sizeof(float) * (size_t)D,
-                                                   sizeof(float) * (size_t)D, (size_t)np, hipMemcpyDeviceToHost, c->stream));
-                    if (comp) HIPCHK(c, hipMemcpy2DAsync(comp + j0 * n + p0, sizeof(int32_t) * (size_t)n, w.comp, sizeof(int32_t) * (size_t)np, sizeof(int32_t) * (size_t)np,
-                                                         (size_t)nb, hipMemcpyDeviceToHost, c->stream));
-                    HIPCHK(c, sync_stream(c, c->stream));      // the staging block is rewritten by the next batch
-                    if (width > D)
-                        for (int64_t jd = j0; jd < j0 + nb; ++jd)
-                            for (int64_t i = p0; i < p0 + np; ++i) memset(out + jd * draw_stride + i * ld + D, 0, sizeof(float) * (size_t)(width - D));
-                }
-            }
-            return DPMM_OK;
+                w.out = d.out; w.ld = d.ld; w.draw_stride = d.draw_stride; w.comp = d.comp; w.comp_stride = d.comp_stride;
+                return launch_miss_draw(a, w, 8 * c->cus, c->stream);
+            });
         })) return rc;
     HIPCHK(c, sync_stream(c, c->stream));
     return DPMM_OK;
@@ -4283,12 +4399,8 @@ int dpmm_set_regression(dpmm_ctx *c, int Dt, const double *B, const double *cc, 
 }
 
 static int regress_points(dpmm_ctx *c, float *mean, float *sd, int64_t ld, int64_t *labels, int64_t *skipped, bool device, const char *fn) {
-    if (!c) return tensor_no_ctx(fn);
-    c->miss_counted = false;      // (as score_points)
+    if (int rc = regress_front(c, fn, REGRESS_TABLES)) return rc;
     const std::string who = std::string(fn) + ": ";
-    if (c->prior != DPMM_PRIOR_NIW) return fail(c, DPMM_EINVAL, who + "the regression is that of the NIW prior's Student-t predictive");
-    if (!c->predictive) return fail(c, DPMM_ESTATE, who + "needs dpmm_set_predictive_niw first");
-    if (c->reg_gen == 0 || c->reg_gen != c->pred_gen) return fail(c, DPMM_ESTATE, who + "needs dpmm_set_regression for the predictive parameters in force");
     const int64_t Dt = c->reg_Dt;
     if (ld < Dt) return fail(c, DPMM_EINVAL, who + "ld < D_t");
     if (ld >> 40) return fail(c, DPMM_EINVAL, who + "ld out of range");
@@ -4306,49 +4418,24 @@ static int regress_points(dpmm_ctx *c, float *mean, float *sd, int64_t ld, int64
     }
     TableWalk w;
     if (int rc = walk_open(c, fn, WALK_MISS_NEVER, &w)) return rc;
-    const int64_t P = w.P;
-    const size_t tiles = (size_t)((P + 31) / 32);
-    if (int rc = grow(c, c->d_reg_skip, sizeof(unsigned) * tiles, fn, "counts of the regression pass")) return rc;
-    HIPCHK(c, hipMemsetAsync(c->d_reg_skip, 0, sizeof(unsigned) * tiles, c->stream));
-    // the rows: in the caller's device memory ld floats apart; staged (host variant) dense, D_t apart, and copied row by row
-    const int64_t sld = device ? ld : Dt;
-    OutStage<3> out{{{mean, sizeof(float) * (size_t)sld}, {sd, sizeof(float) * (size_t)sld}, {labels, sizeof(int64_t)}}, device};
+    if (int rc = skip_open(c, c->d_reg_skip, w.P, fn, "counts of the regression pass")) return rc;
+    // the rows: in the caller's device memory ld floats apart; staged (host variant) dense, D_t apart
+    const size_t row = sizeof(float) * (size_t)Dt, pitch = sizeof(float) * (size_t)ld;
+    OutStage<3> out{{{mean, row, pitch}, {sd, row, pitch}, {labels, sizeof(int64_t)}}, device};
     if (!device) {
-        if (int rc = grow(c, c->d_score_out, out.layout((size_t)P), "dpmm_score_points", "staging of the outputs")) return rc;
+        if (int rc = grow(c, c->d_score_out, out.layout((size_t)w.P), "dpmm_score_points", "staging of the outputs")) return rc;
         out.buf = c->d_score_out;
     }
-    if (int rc = walk_ranges(c, w, c->n, fn, [&](int64_t p0, int64_t np, int64_t) -> int {
+    if (int rc = walk_ranges(c, w, c->n, fn, [&](int64_t p0, int64_t np, int64_t) {
             RegressArgs a{};
-            a.table = c->d_score_table; a.stride = P; a.n = np; a.K = c->K; a.D = c->D; a.Dt = (int)Dt; a.Tp = regress_pitch((int)Dt);
-            a.X = c->dX + p0 * c->ldx; a.ldx = c->ldx;
-            a.Bt = c->d_reg_bt; a.c = c->d_reg_c; a.V = c->d_reg_v; a.hd = c->d_reg_hd;
-            a.mean = out.at<float>(0, p0); a.std = out.at<float>(1, p0); a.ld = sld; a.labels = out.at<int64_t>(2, p0); a.skip = c->d_reg_skip;
-            if (int rc = table_result(c, fn, launch_regress_range(a, c->stream))) return rc;
-            if (device) return DPMM_OK;
-            for (int j = 0; j < 2; ++j) {
-                float *dst = j == 0 ? mean : sd;
-                if (!dst) continue;
-                HIPCHK(c, hipMemcpy2DAsync(dst + p0 * ld, sizeof(float) * (size_t)ld, out.buf + out.col[j].off, sizeof(float) * (size_t)Dt, sizeof(float) * (size_t)Dt, (size_t)np,
-                                           hipMemcpyDeviceToHost, c->stream));
-            }
-            if (labels) HIPCHK(c, hipMemcpyAsync(labels + p0, out.buf + out.col[2].off, sizeof(int64_t) * (size_t)np, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, sync_stream(c, c->stream));      // the staging block is rewritten by the next range
-            if (ld > Dt)
-                for (int64_t i = p0; i < p0 + np; ++i) {
-                    memset(mean + i * ld + Dt, 0, sizeof(float) * (size_t)(ld - Dt));
-                    if (sd) memset(sd + i * ld + Dt, 0, sizeof(float) * (size_t)(ld - Dt));
-                }
-            return DPMM_OK;
+            a.t = regress_tile(c, w.P, p0, np, out.at<int64_t>(2, p0), c->d_reg_skip);
+            a.Bt = c->d_reg_bt; a.V = c->d_reg_v;
+            a.mean = out.at<float>(0, p0); a.std = out.at<float>(1, p0); a.ld = device ? ld : Dt;
+            hipError_t e = launch_regress_range(a, c->stream);
+            if (e == hipSuccess && !device) e = out.flush(c, p0, (size_t)np);
+            return e;
         })) return rc;
-    HIPCHK(c, sync_stream(c, c->stream));
-    if (skipped) {
-        std::vector<unsigned> cnt(tiles);
-        HIPCHK(c, hipMemcpy(cnt.data(), c->d_reg_skip, sizeof(unsigned) * tiles, hipMemcpyDeviceToHost));
-        int64_t total = 0;
-        for (unsigned v : cnt) total += v;
-        skipped[0] = total;
-    }
-    return DPMM_OK;
+    return skip_close(c, c->d_reg_skip, w.P, skipped);
 }
 
 int dpmm_regress_points(dpmm_ctx *c, float *mean, float *std, int64_t ld, int64_t *labels, int64_t *skipped) {
@@ -4383,93 +4470,35 @@ int dpmm_set_regression_factor(dpmm_ctx *c, const double *W) {
     return DPMM_OK;
 }
 
-// Per range: the table once, then the draws -- into the caller's device memory, or in batches of draws through the staging block
-// ([batch][np][D_t] floats, then [batch][np] components).
+// Per range: the table once, then the draws (DrawBatch)
 static int regress_draw_points(dpmm_ctx *c, float *out, int64_t ld, int64_t draw_stride, int32_t *comp, uint64_t seed, int64_t i0, int64_t draw0,
                                int64_t ndraws, int64_t *skipped, bool device, const char *fn) {
-    if (!c) return tensor_no_ctx(fn);
-    c->miss_counted = false;      // (as score_points)
-    const std::string who = std::string(fn) + ": ";
-    if (c->prior != DPMM_PRIOR_NIW) return fail(c, DPMM_EINVAL, who + "the regression is that of the NIW prior's Student-t predictive");
-    if (!c->predictive) return fail(c, DPMM_ESTATE, who + "needs dpmm_set_predictive_niw first");
-    if (c->reg_gen == 0 || c->reg_gen != c->pred_gen) return fail(c, DPMM_ESTATE, who + "needs dpmm_set_regression for the predictive parameters in force");
-    if (!c->reg_factor) return fail(c, DPMM_ESTATE, who + "needs dpmm_set_regression_factor for the regression tables in force");
-    const int64_t Dt = c->reg_Dt, n = c->n;
-    if (ndraws < 1 || draw0 < 0 || draw0 > DPMM_REGRESS_MAX_DRAWS || ndraws > DPMM_REGRESS_MAX_DRAWS - draw0)
-        return fail(c, DPMM_EINVAL, who + "draw0 >= 0, ndraws >= 1 and draw0 + ndraws <= DPMM_REGRESS_MAX_DRAWS are needed");
-    if (i0 < 0 || (i0 >> 62)) return fail(c, DPMM_EINVAL, who + "i0 out of range");
-    if (ld < Dt) return fail(c, DPMM_EINVAL, who + "ld < D_t");
-    if ((ld >> 40) || draw_stride < 0 || (draw_stride >> 37)) return fail(c, DPMM_EINVAL, who + "ld / draw_stride out of range");
-    const bool interleaved = draw_stride >= Dt && draw_stride <= ld / ndraws;
-    if (!interleaved && (unsigned __int128)draw_stride < (unsigned __int128)n * (unsigned __int128)ld)
-        return fail(c, DPMM_EINVAL, who + "the draws overlap: draw_stride >= n_local * ld (stacked) or D_t <= draw_stride <= ld / ndraws (interleaved) is needed");
+    if (int rc = regress_front(c, fn, REGRESS_FACTOR)) return rc;
+    DrawBatch b{out, ld, draw_stride, comp, ndraws, device, c->reg_Dt, "D_t"};
+    if (int rc = b.check(c, fn, i0, draw0, DPMM_REGRESS_MAX_DRAWS, "DPMM_REGRESS_MAX_DRAWS")) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     if (skipped) skipped[0] = 0;
-    if (n == 0) return DPMM_OK;
-    if (!c->have_points || !c->have_params || !c->dX) return fail(c, DPMM_ESTATE, who + "needs points and parameters");
-    if (!out) return fail(c, DPMM_EINVAL, who + "out is null");
-    const int64_t width = std::min(ld, draw_stride);
-    if (device) {
-        const uint64_t words = (uint64_t)(ndraws - 1) * (uint64_t)draw_stride + (uint64_t)(n - 1) * (uint64_t)ld + (uint64_t)width;
-        if (int rc = check_device_extent(c, fn, "d_out", out, words * sizeof(float), sizeof(float))) return rc;
-        if (comp) if (int rc = check_device_extent(c, fn, "d_comp", comp, (uint64_t)ndraws * (uint64_t)n * sizeof(int32_t), sizeof(int32_t))) return rc;
-    }
+    if (c->n == 0) return DPMM_OK;
+    if (int rc = b.ready(c, fn)) return rc;
     TableWalk tw;
     if (int rc = walk_open(c, fn, WALK_MISS_NEVER, &tw)) return rc;
     const int64_t P = tw.P;
-    const size_t tiles = (size_t)((P + 31) / 32);
-    if (int rc = grow(c, c->d_reg_skip, sizeof(unsigned) * tiles, fn, "counts of the regression pass")) return rc;
-    HIPCHK(c, hipMemsetAsync(c->d_reg_skip, 0, sizeof(unsigned) * tiles, c->stream));
-    // the draws of a range in batches: 16 MiB of components and scales at most, and (host variant) 64 MiB of staged draws; one draw at least
-    int64_t batch = std::max<int64_t>(1, std::min<int64_t>(ndraws, ((int64_t)16 << 20) / (8 * P)));
-    if (!device) {
-        batch = std::max<int64_t>(1, std::min<int64_t>(batch, ((int64_t)64 << 20) / ((int64_t)sizeof(float) * P * Dt)));
-        if (int rc = grow(c, c->d_score_out, (size_t)batch * (size_t)P * (sizeof(float) * (size_t)Dt + sizeof(int32_t)), fn, "staging of the outputs")) return rc;
-    }
-    if (int rc = grow(c, c->d_reg_kc, sizeof(int32_t) * (size_t)batch * (size_t)P, fn, "components of a batch of draws")) return rc;
-    if (int rc = grow(c, c->d_reg_sc, sizeof(float) * (size_t)batch * (size_t)P, fn, "scales of a batch of draws")) return rc;
-    if (int rc = walk_ranges(c, tw, n, fn, [&](int64_t p0, int64_t np, int64_t) -> int {
+    if (int rc = skip_open(c, c->d_reg_skip, P, fn, "counts of the regression pass")) return rc;
+    if (int rc = b.size(c, fn, P, ((int64_t)16 << 20) / (8 * P))) return rc;      // 16 MiB of components and scales at most
+    if (int rc = grow(c, c->d_reg_kc, sizeof(int32_t) * (size_t)b.batch * (size_t)P, fn, "components of a batch of draws")) return rc;
+    if (int rc = grow(c, c->d_reg_sc, sizeof(float) * (size_t)b.batch * (size_t)P, fn, "scales of a batch of draws")) return rc;
+    if (int rc = walk_ranges(c, tw, c->n, fn, [&](int64_t p0, int64_t np, int64_t) -> int {
             RegressDrawArgs a{};
-            a.kc = c->d_reg_kc; a.sc = c->d_reg_sc;
-            a.table = c->d_score_table; a.stride = P; a.n = np; a.K = c->K; a.D = c->D; a.Dt = (int)Dt; a.Tp = regress_pitch((int)Dt);
-            a.X = c->dX + p0 * c->ldx; a.ldx = c->ldx;
-            a.Bw = c->d_reg_bw; a.c = c->d_reg_c; a.hd = c->d_reg_hd;
+            a.kc = c->d_reg_kc; a.sc = c->d_reg_sc; a.Bw = c->d_reg_bw;
             a.seed = seed; a.i0 = i0 + p0;
-            for (int64_t j0 = 0; j0 < ndraws; j0 += batch) {
-                const int64_t nb = std::min(batch, ndraws - j0);
+            return b.range(c, fn, p0, np, [&](int64_t j0, int64_t nb, const DrawDest &d) {
+                a.t = regress_tile(c, P, p0, np, nullptr, j0 == 0 ? c->d_reg_skip.get() : nullptr);      // a point is counted once per call
                 a.draw0 = draw0 + j0; a.ndraws = (int)nb;
-                a.skip = j0 == 0 ? c->d_reg_skip.get() : nullptr;      // a point is counted once per call
-                if (device) {
-                    a.out = out + j0 * draw_stride + p0 * ld; a.ld = ld; a.draw_stride = draw_stride;
-                    a.comp = comp ? comp + j0 * n + p0 : nullptr; a.comp_stride = n;
-                } else {
-                    a.out = reinterpret_cast<float *>(c->d_score_out.get()); a.ld = Dt; a.draw_stride = np * Dt;
-                    a.comp = comp ? reinterpret_cast<int32_t *>(a.out + batch * P * Dt) : nullptr; a.comp_stride = np;
-                }
-                if (int rc = table_result(c, fn, launch_regress_draw_range(a, c->stream))) return rc;
-                if (!device) {
-                    for (int64_t jd = 0; jd < nb; ++jd)
-                        HIPCHK(c, hipMemcpy2DAsync(out + (j0 + jd) * draw_stride + p0 * ld, sizeof(float) * (size_t)ld, a.out + jd * np * Dt, sizeof(float) * (size_t)Dt,
-                                                   sizeof(float) * (size_t)Dt, (size_t)np, hipMemcpyDeviceToHost, c->stream));
-                    if (comp) HIPCHK(c, hipMemcpy2DAsync(comp + j0 * n + p0, sizeof(int32_t) * (size_t)n, a.comp, sizeof(int32_t) * (size_t)np, sizeof(int32_t) * (size_t)np,
-                                                         (size_t)nb, hipMemcpyDeviceToHost, c->stream));
-                    HIPCHK(c, sync_stream(c, c->stream));      // the staging block is rewritten by the next batch
-                    if (width > Dt)
-                        for (int64_t jd = j0; jd < j0 + nb; ++jd)
-                            for (int64_t i = p0; i < p0 + np; ++i) memset(out + jd * draw_stride + i * ld + Dt, 0, sizeof(float) * (size_t)(width - Dt));
-                }
-            }
-            return DPMM_OK;
+                a.out = d.out; a.ld = d.ld; a.draw_stride = d.draw_stride; a.comp = d.comp; a.comp_stride = d.comp_stride;
+                return launch_regress_draw_range(a, c->stream);
+            });
         })) return rc;
-    HIPCHK(c, sync_stream(c, c->stream));
-    if (skipped) {
-        std::vector<unsigned> cnt(tiles);
-        HIPCHK(c, hipMemcpy(cnt.data(), c->d_reg_skip, sizeof(unsigned) * tiles, hipMemcpyDeviceToHost));
-        int64_t total = 0;
-        for (unsigned v : cnt) total += v;
-        skipped[0] = total;
-    }
-    return DPMM_OK;
+    return skip_close(c, c->d_reg_skip, P, skipped);
 }
 
 int dpmm_regress_draw_points(dpmm_ctx *c, float *out, int64_t ld, int64_t draw_stride, int32_t *comp, uint64_t seed, int64_t i0, int64_t draw0, int64_t ndraws,
@@ -4514,17 +4543,12 @@ int dpmm_set_regression_levels(dpmm_ctx *c, int L, const double *levels, const d
     return DPMM_OK;
 }
 
-// Both calls: y null and L >= 1: the quantiles, out [n][L][ld]; else the CDF of y into out (cdf) and sf.  Host variants go through the
-// staging block: per range y in, then the outputs dense (D_t apart) and copied row by row.
+// Both calls: quant: the quantiles, out [n][L][ld]; else the CDF of y into out (cdf) and sf.  Host variants go through the staging block:
+// per range y in, then the outputs dense (D_t apart).
 static int regress_cdf_points(dpmm_ctx *c, const float *y, int64_t ldy, float *out, float *sf, int64_t ld, int64_t *labels, int64_t *skipped, bool quant,
                               bool device, const char *fn) {
-    if (!c) return tensor_no_ctx(fn);
-    c->miss_counted = false;      // (as score_points)
+    if (int rc = regress_front(c, fn, quant ? REGRESS_LEVELS : REGRESS_TABLES)) return rc;
     const std::string who = std::string(fn) + ": ";
-    if (c->prior != DPMM_PRIOR_NIW) return fail(c, DPMM_EINVAL, who + "the regression is that of the NIW prior's Student-t predictive");
-    if (!c->predictive) return fail(c, DPMM_ESTATE, who + "needs dpmm_set_predictive_niw first");
-    if (c->reg_gen == 0 || c->reg_gen != c->pred_gen) return fail(c, DPMM_ESTATE, who + "needs dpmm_set_regression for the predictive parameters in force");
-    if (quant && (c->reg_lev_gen == 0 || c->reg_lev_gen != c->pred_gen)) return fail(c, DPMM_ESTATE, who + "needs dpmm_set_regression_levels for the regression tables in force");
     const int64_t Dt = c->reg_Dt, L = quant ? c->reg_L : 1;
     if (ld < Dt || (!quant && ldy < Dt)) return fail(c, DPMM_EINVAL, who + "ld < D_t");
     if ((ld >> 36) || (!quant && (ldy >> 40))) return fail(c, DPMM_EINVAL, who + "ld out of range");
@@ -4543,73 +4567,34 @@ static int regress_cdf_points(dpmm_ctx *c, const float *y, int64_t ldy, float *o
     }
     TableWalk w;
     if (int rc = walk_open(c, fn, WALK_MISS_NEVER, &w)) return rc;
-    const int64_t P = w.P;
-    const size_t tiles = (size_t)((P + 31) / 32);
-    if (int rc = grow(c, c->d_reg_skip, sizeof(unsigned) * tiles, fn, "counts of the regression pass")) return rc;
-    HIPCHK(c, hipMemsetAsync(c->d_reg_skip, 0, sizeof(unsigned) * tiles, c->stream));
-    // staging (host variants): [P] labels, then blocks of [P][L][D_t] floats: the output, sf, y
-    const size_t blk = sizeof(float) * (size_t)P * (size_t)L * (size_t)Dt;
-    char *st = nullptr;
+    if (int rc = skip_open(c, c->d_reg_skip, w.P, fn, "counts of the regression pass")) return rc;
+    // the rows: in the caller's device memory ld (ldy) floats apart, L rows a point; staged (host variants) dense, D_t apart
+    const size_t row = sizeof(float) * (size_t)Dt, pitch = sizeof(float) * (size_t)ld;
+    OutStage<4> st{{{out, row, pitch, (size_t)L}, {sf, row, pitch}, {labels, sizeof(int64_t)}, {const_cast<float *>(y), row, sizeof(float) * (size_t)ldy, 1, true}}, device};
     if (!device) {
-        if (int rc = grow(c, c->d_score_out, sizeof(int64_t) * (size_t)P + 3 * blk, "dpmm_score_points", "staging of the outputs")) return rc;
-        st = c->d_score_out;
+        if (int rc = grow(c, c->d_score_out, st.layout((size_t)w.P), "dpmm_score_points", "staging of the outputs")) return rc;
+        st.buf = c->d_score_out;
     }
-    float *const s_out = reinterpret_cast<float *>(st + sizeof(int64_t) * (size_t)P), *const s_sf = reinterpret_cast<float *>(st + sizeof(int64_t) * (size_t)P + blk),
-                *const s_y = reinterpret_cast<float *>(st + sizeof(int64_t) * (size_t)P + 2 * blk);
     const double *lev = c->d_reg_lev;
-    if (int rc = walk_ranges(c, w, c->n, fn, [&](int64_t p0, int64_t np, int64_t) -> int {
-            int64_t *lab = !labels ? nullptr : device ? labels + p0 : reinterpret_cast<int64_t *>(st);
-            const int64_t sld = device ? ld : Dt;
-            float *o = device ? out + p0 * L * ld : s_out;
-            hipError_t e;
+    if (int rc = walk_ranges(c, w, c->n, fn, [&](int64_t p0, int64_t np, int64_t) {
+            const RegressTile t = regress_tile(c, w.P, p0, np, st.at<int64_t>(2, p0), c->d_reg_skip);
+            hipError_t e = device ? hipSuccess : st.load(c, p0, (size_t)np);
+            if (e != hipSuccess) return e;
             if (quant) {
-                RegressQuantileArgs a{};
-                a.table = c->d_score_table; a.stride = P; a.n = np; a.K = c->K; a.D = c->D; a.Dt = (int)Dt; a.Tp = regress_pitch((int)Dt);
-                a.X = c->dX + p0 * c->ldx; a.ldx = c->ldx;
-                a.Bt = c->d_reg_bt; a.c = c->d_reg_c; a.V = c->d_reg_v; a.hd = c->d_reg_hd;
+                RegressQuantileArgs a = regress_flat_args<RegressQuantileArgs>(c, t);
                 a.levels = lev; a.z = lev + L; a.lc = lev + L + (int64_t)c->K * L; a.L = (int)L;
-                a.out = o; a.ld = sld; a.labels = lab; a.skip = c->d_reg_skip;
+                a.out = st.at<float>(0, p0); a.ld = device ? ld : Dt;
                 e = launch_regress_quantile_range(a, c->stream);
             } else {
-                RegressCdfArgs a{};
-                a.table = c->d_score_table; a.stride = P; a.n = np; a.K = c->K; a.D = c->D; a.Dt = (int)Dt; a.Tp = regress_pitch((int)Dt);
-                a.X = c->dX + p0 * c->ldx; a.ldx = c->ldx;
-                a.Bt = c->d_reg_bt; a.c = c->d_reg_c; a.V = c->d_reg_v; a.hd = c->d_reg_hd;
-                if (device) { a.y = y + p0 * ldy; a.ldy = ldy; }
-                else {
-                    HIPCHK(c, hipMemcpy2DAsync(s_y, sizeof(float) * (size_t)Dt, y + p0 * ldy, sizeof(float) * (size_t)ldy, sizeof(float) * (size_t)Dt, (size_t)np,
-                                               hipMemcpyHostToDevice, c->stream));
-                    a.y = s_y; a.ldy = Dt;
-                }
-                a.cdf = o; a.sf = !sf ? nullptr : device ? sf + p0 * ld : s_sf; a.ld = sld; a.labels = lab; a.skip = c->d_reg_skip;
+                RegressCdfArgs a = regress_flat_args<RegressCdfArgs>(c, t);
+                a.y = st.at<float>(3, p0); a.ldy = device ? ldy : Dt;
+                a.cdf = st.at<float>(0, p0); a.sf = st.at<float>(1, p0); a.ld = device ? ld : Dt;
                 e = launch_regress_cdf_range(a, c->stream);
             }
-            if (int rc = table_result(c, fn, e)) return rc;
-            if (device) return DPMM_OK;
-            for (int j = 0; j < 2; ++j) {
-                float *dst = j == 0 ? out : sf;
-                if (!dst) continue;
-                HIPCHK(c, hipMemcpy2DAsync(dst + p0 * L * ld, sizeof(float) * (size_t)ld, j == 0 ? s_out : s_sf, sizeof(float) * (size_t)Dt, sizeof(float) * (size_t)Dt,
-                                           (size_t)(np * L), hipMemcpyDeviceToHost, c->stream));
-            }
-            if (labels) HIPCHK(c, hipMemcpyAsync(labels + p0, st, sizeof(int64_t) * (size_t)np, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, sync_stream(c, c->stream));      // the staging block is rewritten by the next range
-            if (ld > Dt)
-                for (int64_t r = p0 * L; r < (p0 + np) * L; ++r) {
-                    memset(out + r * ld + Dt, 0, sizeof(float) * (size_t)(ld - Dt));
-                    if (sf) memset(sf + r * ld + Dt, 0, sizeof(float) * (size_t)(ld - Dt));
-                }
-            return DPMM_OK;
+            if (e == hipSuccess && !device) e = st.flush(c, p0, (size_t)np);
+            return e;
         })) return rc;
-    HIPCHK(c, sync_stream(c, c->stream));
-    if (skipped) {
-        std::vector<unsigned> cnt(tiles);
-        HIPCHK(c, hipMemcpy(cnt.data(), c->d_reg_skip, sizeof(unsigned) * tiles, hipMemcpyDeviceToHost));
-        int64_t total = 0;
-        for (unsigned v : cnt) total += v;
-        skipped[0] = total;
-    }
-    return DPMM_OK;
+    return skip_close(c, c->d_reg_skip, w.P, skipped);
 }
 
 int dpmm_regress_cdf_points(dpmm_ctx *c, const float *y, int64_t ldy, float *cdf, float *sf, int64_t ld, int64_t *labels, int64_t *skipped) {
@@ -5205,47 +5190,25 @@ static int recommend_points(dpmm_ctx *c, int m, int exclude_seen, int32_t *featu
     }
     TableWalk w;
     if (int rc = walk_open(c, fn, WALK_MISS_NEVER, &w)) return rc;
-    const int64_t P = w.P;
-    const size_t tiles = (size_t)((P + 31) / 32);
-    if (int rc = grow(c, c->d_rec_skip, sizeof(unsigned) * tiles, fn, "counts of the recommendation pass")) return rc;
-    HIPCHK(c, hipMemsetAsync(c->d_rec_skip, 0, sizeof(unsigned) * tiles, c->stream));
-    // the rows: in the caller's device memory ld words apart; staged (host variant) dense, m apart, and copied row by row
-    const int64_t sld = device ? ld : m;
-    OutStage<3> out{{{features, sizeof(int32_t) * (size_t)sld}, {prob, sizeof(float) * (size_t)sld}, {labels, sizeof(int64_t)}}, device};
+    if (int rc = skip_open(c, c->d_rec_skip, w.P, fn, "counts of the recommendation pass")) return rc;
+    // the rows: in the caller's device memory ld words apart; staged (host variant) dense, m apart
+    OutStage<3> out{{{features, sizeof(int32_t) * (size_t)m, sizeof(int32_t) * (size_t)ld}, {prob, sizeof(float) * (size_t)m, sizeof(float) * (size_t)ld},
+                     {labels, sizeof(int64_t)}}, device};
     if (!device) {
-        if (int rc = grow(c, c->d_score_out, out.layout((size_t)P), "dpmm_score_points", "staging of the outputs")) return rc;
+        if (int rc = grow(c, c->d_score_out, out.layout((size_t)w.P), "dpmm_score_points", "staging of the outputs")) return rc;
         out.buf = c->d_score_out;
     }
-    if (int rc = walk_ranges(c, w, c->n, fn, [&](int64_t p0, int64_t np, int64_t) -> int {
+    if (int rc = walk_ranges(c, w, c->n, fn, [&](int64_t p0, int64_t np, int64_t) {
             RecommendArgs a{};
-            a.table = c->d_score_table; a.stride = P; a.rstep = w.rstep; a.n = np; a.K = c->K; a.Kp = c->K + (c->K & 1); a.D = c->D; a.Dp = recommend_pitch(c->D);
+            a.table = c->d_score_table; a.stride = w.P; a.rstep = w.rstep; a.n = np; a.K = c->K; a.Kp = c->K + (c->K & 1); a.D = c->D; a.Dp = recommend_pitch(c->D);
             count_points(c, store, p0, a);
             a.theta = c->d_rec_theta; a.m = m; a.exclude = exclude_seen ? 1 : 0;
-            a.features = out.at<int32_t>(0, p0); a.prob = out.at<float>(1, p0); a.ld = sld; a.labels = out.at<int64_t>(2, p0); a.skip = c->d_rec_skip;
-            if (int rc = table_result(c, fn, launch_recommend_range(a, c->stream))) return rc;
-            if (device) return DPMM_OK;
-            HIPCHK(c, hipMemcpy2DAsync(features + p0 * ld, sizeof(int32_t) * (size_t)ld, out.buf + out.col[0].off, sizeof(int32_t) * (size_t)m, sizeof(int32_t) * (size_t)m,
-                                       (size_t)np, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipMemcpy2DAsync(prob + p0 * ld, sizeof(float) * (size_t)ld, out.buf + out.col[1].off, sizeof(float) * (size_t)m, sizeof(float) * (size_t)m, (size_t)np,
-                                       hipMemcpyDeviceToHost, c->stream));
-            if (labels) HIPCHK(c, hipMemcpyAsync(labels + p0, out.buf + out.col[2].off, sizeof(int64_t) * (size_t)np, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, sync_stream(c, c->stream));      // the staging block is rewritten by the next range
-            if (ld > m)
-                for (int64_t i = p0; i < p0 + np; ++i) {
-                    memset(features + i * ld + m, 0, sizeof(int32_t) * (size_t)(ld - m));
-                    memset(prob + i * ld + m, 0, sizeof(float) * (size_t)(ld - m));
-                }
-            return DPMM_OK;
+            a.features = out.at<int32_t>(0, p0); a.prob = out.at<float>(1, p0); a.ld = device ? ld : m; a.labels = out.at<int64_t>(2, p0); a.skip = c->d_rec_skip;
+            hipError_t e = launch_recommend_range(a, c->stream);
+            if (e == hipSuccess && !device) e = out.flush(c, p0, (size_t)np);
+            return e;
         })) return rc;
-    HIPCHK(c, sync_stream(c, c->stream));
-    if (skipped) {
-        std::vector<unsigned> cnt(tiles);
-        HIPCHK(c, hipMemcpy(cnt.data(), c->d_rec_skip, sizeof(unsigned) * tiles, hipMemcpyDeviceToHost));
-        int64_t total = 0;
-        for (unsigned v : cnt) total += v;
-        skipped[0] = total;
-    }
-    return DPMM_OK;
+    return skip_close(c, c->d_rec_skip, w.P, skipped);
 }
 
 int dpmm_recommend_points(dpmm_ctx *c, int m, int exclude_seen, int32_t *features, float *prob, int64_t ld, int64_t *labels, int64_t *skipped) {

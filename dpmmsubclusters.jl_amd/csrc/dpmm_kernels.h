@@ -461,7 +461,8 @@ hipError_t launch_miss_patch(const MissArgs &a, bool impute, int max_grid, hipSt
 // ---- mixture regression (regress.hip; include/dpmm_hip_regress.h): one range of the score table, n points from table column 0 and from X
 constexpr int REGRESS_MAX_TARGETS = 256;  // DPMM_REGRESS_MAX_TARGETS
 inline int regress_pitch(int Dt) { return 32 * ((Dt + 31) / 32); }
-struct RegressArgs {
+// what the kernels of regress.hip and regress_draw.hip share (regress_device.h)
+struct RegressTile {
     const float *table;          // entry (k, i) at table[k * stride + i] (NIW: one row per cluster)
     int64_t stride;
     int64_t n;
@@ -469,13 +470,21 @@ struct RegressArgs {
     int Dt, Tp;                  // targets; Tp = regress_pitch(Dt)
     const float *X;              // [n][ldx], the range's first point
     int64_t ldx;
-    const float *Bt;             // [K][D][Tp]: Bt[k][e][d] = B_k[d][e], zero in the pad (d >= Dt)
-    const float *c, *V;          // [K][Tp], zero in the pad
+    const float *c;              // [K][Tp], zero in the pad
     const double *hd;            // [K][2]: h_k, df_k
-    float *mean, *std;           // [n][ld] rows of the range's points; std null: not asked for
-    int64_t ld;
     int64_t *labels;             // [n] or null
     unsigned *skip;              // [ceil(n / 32)] points of tile j that take no part, ADDED to word j
+};
+// the shapes the launchers of regress.hip and regress_draw.hip refuse; ld: floats between two rows of its outputs
+inline bool regress_tile_ok(const RegressTile &t, int64_t ld) {
+    return t.K >= 1 && t.D >= 1 && t.Dt >= 1 && t.Tp % 32 == 0 && t.Tp >= t.Dt && ld >= t.Dt && !(((t.n + 31) / 32) >> 31);
+}
+struct RegressArgs {
+    RegressTile t;
+    const float *Bt;             // [K][D][Tp]: Bt[k][e][d] = B_k[d][e], zero in the pad (d >= Dt)
+    const float *V;              // [K][Tp], zero in the pad
+    float *mean, *std;           // [n][ld] rows of the range's points; std null: not asked for
+    int64_t ld;
 };
 hipError_t launch_regress_range(const RegressArgs &a, hipStream_t s);
 // ---- top-m next-count probabilities (recommend.hip; include/dpmm_hip_recommend.h): one range of the score table, n points from table
@@ -511,17 +520,9 @@ hipError_t launch_recommend_range(const RecommendArgs &a, hipStream_t s);
 // and from X, the draws draw0 .. draw0 + ndraws - 1 of each
 constexpr int64_t REGRESS_DRAW_MAX = 67108864;      // DPMM_REGRESS_MAX_DRAWS
 struct RegressDrawArgs {
-    const float *table;          // as RegressArgs
-    int64_t stride;
-    int64_t n;
-    int K, D;
-    int Dt, Tp;
-    const float *X;
-    int64_t ldx;
+    RegressTile t;               // labels: not written; skip null: not counted by this launch
     const float *Bw;             // [K][D + Dt][Tp]: rows [0, D) of cluster k are RegressArgs::Bt[k]; row D + a is W_k[.][a] (Bw[k][D + a][d] = W_k[d][a]),
                                  // zero below the diagonal of W (a < d) and in the pad (d >= Dt)
-    const float *c;              // [K][Tp], zero in the pad
-    const double *hd;            // [K][2]: h_k, df_k
     float *out;                  // element (jd, i, f) at out[jd * draw_stride + i * ld + f], f < min(ld, draw_stride); columns [Dt, ..) are written as 0
     int64_t ld, draw_stride;
     int32_t *comp;               // null, or element (jd, i) at comp[jd * comp_stride + i]
@@ -530,13 +531,13 @@ struct RegressDrawArgs {
     int64_t i0;                  // global index of the range's first point
     int64_t draw0;
     int ndraws;
-    unsigned *skip;              // as RegressArgs, or null: not counted by this launch
     int32_t *kc;                 // scratch [ndraws][n]: the drawn cluster (-1: the point's row of the table takes no part) and
     float *sc;                   // the scale s of every (draw, point), written by the first kernel of the launch and read by the second
 };
 hipError_t launch_regress_draw_range(const RegressDrawArgs &a, hipStream_t s);
 // ---- conditional CDF and quantiles of the targets (regress_cdf.hip; include/dpmm_hip_regress_cdf.h): one range of the score table, n points
-// from table column 0 and from X; table .. hd, labels and skip as RegressArgs
+// from table column 0 and from X; table .. hd, labels and skip as RegressTile and RegressArgs.  The two structs keep these fields flat and in this
+// order: the kernels of regress_cdf.hip sit at the register limit, and are compiled exactly as they were
 constexpr int REGRESS_MAX_LEVELS = 16;    // DPMM_REGRESS_MAX_LEVELS
 struct RegressCdfArgs {
     const float *table;

@@ -1,7 +1,7 @@
 // regress_cdf.hip -- conditional CDF and quantiles of every target (include/dpmm_hip_regress_cdf.h): from a range of the score table and the
 // range's points to F_id(y) = sum_k p_ik T_nu_k((y - mu_ikd) / sigma_ikd) at given y, and to the y at which F_id reaches given levels.
 //
-// Both kernels keep the tile of regress_kernel (regress.hip): 32 points per workgroup, one wave per 32 targets, the points staged transposed
+// Both kernels keep the tile of regress_kernel (regress.hip, regress_device.h), in statements of their own (see regress_device.h): 32 points per workgroup, one wave per 32 targets, the points staged transposed
 // in LDS, the row of the table walked with score_device.h (p_ik has the bits `probs` holds), clusters whose p is 0 for the whole tile left
 // out, mu_ikd the SAME Float32 chain (accumulator started from c, v_mfma_f32_32x32x2_f32 in increasing e), q_ik recovered from the table
 // entry as regress_kernel's STD branch does, and the results leave through the wave-private LDS tile as 128-byte segments.
