@@ -766,6 +766,40 @@ class Worker:
         self._chk(self._lib.dpmm_sample_points_device(self._h, ctypes.byref(req)))
         return int(nnz.value) if first else None
 
+    # ---- the point calls (`*_into`): one marshaller for the storage their callers make
+    def _marshal(self, call, arrays):
+        """What every `*_into` method does with its arrays.  call: the C entry's base name; arrays: (name, array or None, dtype name,
+        per_point) each -- numpy arrays (host variant) or torch tensors on this worker's GPU (device variant), never both, C-contiguous, of
+        that dtype and, if per_point, with n as the leading extent.  Synchronises the tensors' current stream once.  Returns (fn, ptr, dev):
+        `call` or `call_device`, ptr[name] the address of every array listed -- None for None and for an empty one: every entry returns at
+        n_local == 0 before it reads through a pointer (csrc/dpmm_api.cpp), and with points a null it needs is its own DPMM_EINVAL -- and
+        whether it is the device variant."""
+        dev, first, ptr = False, None, {}
+        for name, a, dt, per in arrays:             # (one pass: this runs once per slab of every served batch)
+            ptr[name] = None
+            if a is None:
+                continue
+            tensor = hasattr(a, "data_ptr")
+            if first is None:
+                dev, first = tensor, a
+            assert tensor == dev, call + ": numpy arrays or tensors, not both"
+            if dev:
+                import torch
+                assert a.is_contiguous() and a.dtype == getattr(torch, dt) and (not per or a.shape[0] == self.n), name
+                if a.numel():
+                    ptr[name] = a.data_ptr()
+            else:
+                assert a.flags.c_contiguous and a.dtype == dt and (not per or a.shape[0] == self.n), name
+                if a.size:
+                    ptr[name] = a.ctypes.data
+        if dev:
+            torch.cuda.current_stream(first.device).synchronize()
+        return getattr(self._lib, call + ("_device" if dev else "")), ptr, dev
+
+    _SCORE_OUTS = dict(labels="int64", logdens="float32", top_idx="int64", top_prob="float32", probs="float32")
+    _EXPLAIN_OUTS = dict(labels="int64", mahalanobis="float32", tail="float32", residual="float32", zscore="float32", feature_tail="float32",
+                         features="int32")
+
     def score_points_raw(self, device, labels=0, logdens=0, m=0, top_idx=0, top_prob=0, probs=0):
         """dpmm_score_points[_device] on plain addresses (integers; 0 = not asked for)."""
         out = ScoreOut(labels or None, logdens or None, int(m), top_idx or None, top_prob or None, probs or None)
@@ -775,18 +809,8 @@ class Worker:
     def score_points_into(self, outs, m=0):
         """dpmm_score_points[_device] into storage the caller made: `outs` maps `labels` / `logdens` / `top_idx` / `top_prob` / `probs` to
         contiguous numpy arrays (host variant) or torch tensors on this worker's GPU (device variant) with n rows each."""
-        ptr, on_device = {}, None
-        for name, a in outs.items():
-            dev = hasattr(a, "data_ptr")
-            if on_device is None:
-                on_device = dev
-            assert dev == on_device, "score_points_into: numpy arrays or tensors, not both"
-            assert a.is_contiguous() if dev else a.flags.c_contiguous, name
-            ptr[name] = (a.data_ptr() if a.numel() else 0) if dev else (a.ctypes.data if a.size else 0)
-        if on_device:
-            import torch
-            torch.cuda.current_stream(next(iter(outs.values())).device).synchronize()
-        self.score_points_raw(bool(on_device), m=int(m), **ptr)
+        _, ptr, dev = self._marshal("dpmm_score_points", [(name, a, self._SCORE_OUTS[name], True) for name, a in outs.items()])
+        self.score_points_raw(dev, m=int(m), **ptr)
 
     def score_points(self, labels=False, logdens=False, m=0, top_idx=None, top_prob=None, probs=False, device=None):
         """The outputs asked for, of the ctx's n points: a dict with `labels` (n,) int64, `logdens` (n,) float32, `top_idx` (n, m) int64,
@@ -816,19 +840,9 @@ class Worker:
     def typicality_points_into(self, outs):
         """dpmm_typicality_points[_device] into storage the caller made: `outs` maps `labels` / `mahalanobis` / `tail` to contiguous numpy
         arrays (host variant) or torch tensors on this worker's GPU (device variant) with n entries each; returns (skipped, incomplete)."""
-        ptr, on_device = {}, None
-        for name, a in outs.items():
-            dev = hasattr(a, "data_ptr")
-            if on_device is None:
-                on_device = dev
-            assert dev == on_device, "typicality_points_into: numpy arrays or tensors, not both"
-            assert a.is_contiguous() if dev else a.flags.c_contiguous, name
-            ptr[name] = (a.data_ptr() if a.numel() else 0) if dev else (a.ctypes.data if a.size else 0)
-        if on_device:
-            import torch
-            torch.cuda.current_stream(next(iter(outs.values())).device).synchronize()
+        _, ptr, dev = self._marshal("dpmm_typicality_points", [(name, a, self._EXPLAIN_OUTS[name], True) for name, a in outs.items()])
         cnt = np.zeros(2, np.int64)
-        self.typicality_points_raw(bool(on_device), skipped=cnt[0:].ctypes.data, incomplete=cnt[1:].ctypes.data, **ptr)
+        self.typicality_points_raw(dev, skipped=cnt.ctypes.data, incomplete=cnt.ctypes.data + 8, **ptr)
         return int(cnt[0]), int(cnt[1])
 
     # ---- per-feature explanations (include/dpmm_hip_explain.h)
@@ -844,22 +858,14 @@ class Worker:
         """dpmm_explain_points[_device] into storage the caller made: `outs` maps `labels` / `mahalanobis` / `tail` (n entries each) and
         `residual` / `zscore` / `feature_tail` / `features` ((n, ld) each, one ld for all, features int32 and only with top > 0) to contiguous
         numpy arrays (host variant) or torch tensors on this worker's GPU (device variant); returns (skipped, incomplete)."""
-        ptr, on_device, ld = {}, None, 0
-        for name, a in outs.items():
-            dev = hasattr(a, "data_ptr")
-            if on_device is None:
-                on_device = dev
-            assert dev == on_device, "explain_points_into: numpy arrays or tensors, not both"
-            assert a.is_contiguous() if dev else a.flags.c_contiguous, name
-            if name in ("residual", "zscore", "feature_tail", "features"):
-                assert len(a.shape) == 2 and ld in (0, a.shape[1]), name
-                ld = int(a.shape[1])
-            ptr[name] = (a.data_ptr() if a.numel() else 0) if dev else (a.ctypes.data if a.size else 0)
-        if on_device:
-            import torch
-            torch.cuda.current_stream(next(iter(outs.values())).device).synchronize()
+        ld = 0
+        for name in ("residual", "zscore", "feature_tail", "features"):
+            if name in outs:
+                assert len(outs[name].shape) == 2 and ld in (0, outs[name].shape[1]), name
+                ld = int(outs[name].shape[1])
+        _, ptr, dev = self._marshal("dpmm_explain_points", [(name, a, self._EXPLAIN_OUTS[name], True) for name, a in outs.items()])
         cnt = np.zeros(2, np.int64)
-        self.explain_points_raw(bool(on_device), top=top, ld=ld, skipped=cnt[0:].ctypes.data, incomplete=cnt[1:].ctypes.data, **ptr)
+        self.explain_points_raw(dev, top=top, ld=ld, skipped=cnt.ctypes.data, incomplete=cnt.ctypes.data + 8, **ptr)
         return int(cnt[0]), int(cnt[1])
 
     # ---- missing features (include/dpmm_hip_missing.h)
@@ -872,18 +878,9 @@ class Worker:
     def impute_points_into(self, out):
         """dpmm_impute_points[_device] into storage the caller made: a C-contiguous (n, ld >= D) float32 numpy array (host variant) or
         torch tensor on this worker's GPU (device variant)."""
-        dev = hasattr(out, "data_ptr")
-        assert tuple(out.shape)[0] == self.n and out.shape[1] >= self.D and (out.is_contiguous() if dev else out.flags.c_contiguous)
-        if self.n == 0:
-            return
-        if dev:
-            import torch
-            assert out.dtype == torch.float32
-            torch.cuda.current_stream(out.device).synchronize()
-            self._chk(self._lib.dpmm_impute_points_device(self._h, ctypes.c_void_p(out.data_ptr()), int(out.shape[1])))
-        else:
-            assert out.dtype == np.float32
-            self._chk(self._lib.dpmm_impute_points(self._h, _p(out, _c_f32p), int(out.shape[1])))
+        assert len(out.shape) == 2 and out.shape[1] >= self.D
+        fn, p, _ = self._marshal("dpmm_impute_points", [("out", out, "float32", True)])
+        self._chk(fn(self._h, ctypes.cast(p["out"], fn.argtypes[1]), int(out.shape[1])))
 
     # ---- draws of the missing features (include/dpmm_hip_impute.h)
     def impute_draws_into(self, out, seed, i0, draw0=0, comp=None):
@@ -891,22 +888,11 @@ class Worker:
         point side by side: ld = ndraws * w, draw_stride = w -- a numpy array (host variant) or a torch tensor on this worker's GPU (device
         variant); the draws are draw0 .. draw0 + ndraws - 1 of the points with global indices i0 .. i0 + n - 1.  comp: None or an
         (ndraws, n) int32 array / tensor of the same kind for the drawn clusters (0-based, -1 off the marginalised points)."""
-        dev = hasattr(out, "data_ptr")
         nd, w = int(out.shape[1]), int(out.shape[2])
-        assert int(out.shape[0]) == self.n and nd >= 1 and w >= self.D and (out.is_contiguous() if dev else out.flags.c_contiguous)
-        if comp is not None:
-            assert hasattr(comp, "data_ptr") == dev and tuple(comp.shape) == (nd, self.n) and (comp.is_contiguous() if dev else comp.flags.c_contiguous)
-        if self.n == 0:
-            return
-        if dev:
-            import torch
-            assert out.dtype == torch.float32 and (comp is None or comp.dtype == torch.int32)
-            torch.cuda.current_stream(out.device).synchronize()
-            fn, op, cp = self._lib.dpmm_impute_draw_points_device, ctypes.c_void_p(out.data_ptr()), comp.data_ptr() if comp is not None else None
-        else:
-            assert out.dtype == np.float32 and (comp is None or comp.dtype == np.int32)
-            fn, op, cp = self._lib.dpmm_impute_draw_points, _p(out, _c_f32p), comp.ctypes.data if comp is not None else None
-        self._chk(fn(self._h, op, nd * w, w, ctypes.c_void_p(cp), ctypes.c_uint64(int(seed)), int(i0), int(draw0), nd))
+        assert nd >= 1 and w >= self.D and (comp is None or tuple(comp.shape) == (nd, self.n))
+        fn, p, _ = self._marshal("dpmm_impute_draw_points", [("out", out, "float32", True), ("comp", comp, "int32", False)])
+        dest = ctypes.cast(p["out"], fn.argtypes[1])
+        self._chk(fn(self._h, dest, nd * w, w, p["comp"], ctypes.c_uint64(int(seed)), int(i0), int(draw0), nd))
 
     # ---- mixture regression (include/dpmm_hip_regress.h)
     def set_regression(self, B, c, V, h):
@@ -921,21 +907,11 @@ class Worker:
         """dpmm_regress_points[_device] into storage the caller made: mean and std C-contiguous (n, ld >= D_t) float32, labels (n,) int64
         -- numpy arrays (host variant) or torch tensors on this worker's GPU (device variant); std and labels may be None.  Returns the
         number of points that took no part."""
-        dev = hasattr(mean, "data_ptr")
-        outs = [a for a in (mean, std, labels) if a is not None]
-        assert all(hasattr(a, "data_ptr") == dev for a in outs), "regress_points_into: numpy arrays or tensors, not both"
-        assert all(int(a.shape[0]) == self.n and (a.is_contiguous() if dev else a.flags.c_contiguous) for a in outs)
         assert std is None or tuple(std.shape) == tuple(mean.shape)
+        fn, p, _ = self._marshal("dpmm_regress_points",
+                                 [("mean", mean, "float32", True), ("std", std, "float32", True), ("labels", labels, "int64", True)])
         skipped = np.zeros(1, np.int64)
-        if dev:
-            import torch
-            assert mean.dtype == torch.float32 and (std is None or std.dtype == torch.float32) and (labels is None or labels.dtype == torch.int64)
-            torch.cuda.current_stream(mean.device).synchronize()
-            fn, ptr = self._lib.dpmm_regress_points_device, lambda a: None if a is None or a.numel() == 0 else ctypes.c_void_p(a.data_ptr())
-        else:
-            assert mean.dtype == np.float32 and (std is None or std.dtype == np.float32) and (labels is None or labels.dtype == np.int64)
-            fn, ptr = self._lib.dpmm_regress_points, lambda a: None if a is None or a.size == 0 else ctypes.c_void_p(a.ctypes.data)
-        self._chk(fn(self._h, ptr(mean), ptr(std), int(mean.shape[1]), ptr(labels), _p(skipped, _c_i64p)))
+        self._chk(fn(self._h, p["mean"], p["std"], int(mean.shape[1]), p["labels"], _p(skipped, _c_i64p)))
         return int(skipped[0])
 
     # ---- next-count probabilities (include/dpmm_hip_recommend.h)
@@ -950,21 +926,12 @@ class Worker:
         and, if asked for, `labels` (n,) int64 to C-contiguous numpy arrays (host variant) or torch tensors on this worker's GPU (device
         variant).  Returns the number of points that took no part."""
         features, prob, labels = views["features"], views["prob"], views.get("labels")
-        dev = hasattr(features, "data_ptr")
-        outs = [a for a in (features, prob, labels) if a is not None]
-        assert all(hasattr(a, "data_ptr") == dev for a in outs), "recommend_points_into: numpy arrays or tensors, not both"
-        assert all(int(a.shape[0]) == self.n and (a.is_contiguous() if dev else a.flags.c_contiguous) for a in outs)
         assert len(features.shape) == 2 and tuple(prob.shape) == tuple(features.shape)
+        fn, p, _ = self._marshal("dpmm_recommend_points",
+                                 [("features", features, "int32", True), ("prob", prob, "float32", True), ("labels", labels, "int64", True)])
         skipped = np.zeros(1, np.int64)
-        if dev:
-            import torch
-            assert features.dtype == torch.int32 and prob.dtype == torch.float32 and (labels is None or labels.dtype == torch.int64)
-            torch.cuda.current_stream(features.device).synchronize()
-            fn, ptr = self._lib.dpmm_recommend_points_device, lambda a: None if a is None or a.numel() == 0 else ctypes.c_void_p(a.data_ptr())
-        else:
-            assert features.dtype == np.int32 and prob.dtype == np.float32 and (labels is None or labels.dtype == np.int64)
-            fn, ptr = self._lib.dpmm_recommend_points, lambda a: None if a is None or a.size == 0 else ctypes.c_void_p(a.ctypes.data)
-        self._chk(fn(self._h, int(m), 1 if exclude_seen else 0, ptr(features), ptr(prob), int(features.shape[1]), ptr(labels), _p(skipped, _c_i64p)))
+        self._chk(fn(self._h, int(m), 1 if exclude_seen else 0, p["features"], p["prob"], int(features.shape[1]), p["labels"],
+                     _p(skipped, _c_i64p)))
         return int(skipped[0])
 
     # ---- draws of the targets (include/dpmm_hip_regress_draw.h)
@@ -982,47 +949,24 @@ class Worker:
         variant); the draws are draw0 .. draw0 + ndraws - 1 of the points with global indices i0 .. i0 + n - 1.  comp: None or an
         (ndraws, n) int32 array / tensor of the same kind for the drawn clusters (0-based, -1: the point took no part).  Returns the number
         of points that took no part."""
-        dev = hasattr(out, "data_ptr")
         nd, w = int(out.shape[1]), int(out.shape[2])
-        assert int(out.shape[0]) == self.n and nd >= 1 and w >= self._regress_Dt and (out.is_contiguous() if dev else out.flags.c_contiguous)
-        if comp is not None:
-            assert hasattr(comp, "data_ptr") == dev and tuple(comp.shape) == (nd, self.n) and (comp.is_contiguous() if dev else comp.flags.c_contiguous)
+        assert nd >= 1 and w >= self._regress_Dt and (comp is None or tuple(comp.shape) == (nd, self.n))
+        fn, p, _ = self._marshal("dpmm_regress_draw_points", [("out", out, "float32", True), ("comp", comp, "int32", False)])
         skipped = np.zeros(1, np.int64)
-        if dev:
-            import torch
-            assert out.dtype == torch.float32 and (comp is None or comp.dtype == torch.int32)
-            torch.cuda.current_stream(out.device).synchronize()
-            fn, op = self._lib.dpmm_regress_draw_points_device, ctypes.c_void_p(out.data_ptr() if out.numel() else None)
-            cp = comp.data_ptr() if comp is not None and comp.numel() else None
-        else:
-            assert out.dtype == np.float32 and (comp is None or comp.dtype == np.int32)
-            fn, op, cp = self._lib.dpmm_regress_draw_points, _p(out, _c_f32p), comp.ctypes.data if comp is not None and comp.size else None
-        self._chk(fn(self._h, op, nd * w, w, ctypes.c_void_p(cp), ctypes.c_uint64(int(seed)), int(i0), int(draw0), nd, _p(skipped, _c_i64p)))
+        dest = ctypes.cast(p["out"], fn.argtypes[1])
+        self._chk(fn(self._h, dest, nd * w, w, p["comp"], ctypes.c_uint64(int(seed)), int(i0), int(draw0), nd, _p(skipped, _c_i64p)))
         return int(skipped[0])
 
     # ---- conditional CDF and quantiles of the targets (include/dpmm_hip_regress_cdf.h)
-    def _regress_cdf_call(self, name, arrays, lead, tail):
-        """The host or the device variant of `name` for `arrays` (numpy arrays or tensors of this worker's GPU, None allowed): (fn, ptr)."""
-        given = [a for a in arrays if a is not None]
-        dev = hasattr(given[0], "data_ptr")
-        assert all(hasattr(a, "data_ptr") == dev for a in given), name + ": numpy arrays or tensors, not both"
-        assert all(int(a.shape[0]) == self.n and (a.is_contiguous() if dev else a.flags.c_contiguous) for a in given)
-        if dev:
-            import torch
-            assert all(a.dtype == (torch.int64 if a is tail else torch.float32) for a in given)
-            torch.cuda.current_stream(lead.device).synchronize()
-            return getattr(self._lib, name + "_device"), lambda a: None if a is None or a.numel() == 0 else ctypes.c_void_p(a.data_ptr())
-        assert all(a.dtype == (np.int64 if a is tail else np.float32) for a in given)
-        return getattr(self._lib, name), lambda a: None if a is None or a.size == 0 else ctypes.c_void_p(a.ctypes.data)
-
     def regress_cdf_points_into(self, y, cdf, sf=None, labels=None):
         """dpmm_regress_cdf_points[_device] into storage the caller made: y, cdf and sf C-contiguous (n, ld >= D_t) float32, labels (n,) int64
         -- numpy arrays (host variant) or torch tensors on this worker's GPU (device variant); sf and labels may be None.  Returns the
         number of points that took no part."""
-        fn, ptr = self._regress_cdf_call("dpmm_regress_cdf_points", (y, cdf, sf, labels), cdf, labels)
         assert sf is None or tuple(sf.shape) == tuple(cdf.shape)
+        fn, p, _ = self._marshal("dpmm_regress_cdf_points", [("y", y, "float32", True), ("cdf", cdf, "float32", True), ("sf", sf, "float32", True),
+                                                             ("labels", labels, "int64", True)])
         skipped = np.zeros(1, np.int64)
-        self._chk(fn(self._h, ptr(y), int(y.shape[1]), ptr(cdf), ptr(sf), int(cdf.shape[1]), ptr(labels), _p(skipped, _c_i64p)))
+        self._chk(fn(self._h, p["y"], int(y.shape[1]), p["cdf"], p["sf"], int(cdf.shape[1]), p["labels"], _p(skipped, _c_i64p)))
         return int(skipped[0])
 
     def set_regression_levels(self, levels, z):
@@ -1036,10 +980,10 @@ class Worker:
     def regress_quantile_points_into(self, out, labels=None):
         """dpmm_regress_quantile_points[_device] into storage the caller made: out (n, L, ld >= D_t) float32 C-contiguous, labels (n,) int64
         or None -- numpy arrays or torch tensors on this worker's GPU.  Returns the number of points that took no part."""
-        fn, ptr = self._regress_cdf_call("dpmm_regress_quantile_points", (out, labels), out, labels)
         assert int(out.shape[1]) == self._regress_L
+        fn, p, _ = self._marshal("dpmm_regress_quantile_points", [("out", out, "float32", True), ("labels", labels, "int64", True)])
         skipped = np.zeros(1, np.int64)
-        self._chk(fn(self._h, ptr(out), int(out.shape[2]), ptr(labels), _p(skipped, _c_i64p)))
+        self._chk(fn(self._h, p["out"], int(out.shape[2]), p["labels"], _p(skipped, _c_i64p)))
         return int(skipped[0])
 
     # ---- exemplars (include/dpmm_hip_rank.h)

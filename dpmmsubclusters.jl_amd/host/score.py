@@ -199,6 +199,48 @@ _FAMILY = {
 }
 
 
+def _need(wk, message, *methods):
+    """`wk` if it has every one of `methods` -- a stand-in worker may lack a call -- else RuntimeError(message)."""
+    if not all(hasattr(wk, f) for f in methods):
+        raise RuntimeError(message)
+    return wk
+
+
+# The short-slab rule of `Predictor._walk`: the worker scores the zero padding of a short slab too, and the padding is not ours.  A call
+# marks a row that took no part in one of its outputs -- NaN in the first element of a float row, a negative first element of an integer
+# row -- and _first_nan(name) / _first_negative(name) give absent(views, rows): how many of `rows` of views[name] carry the mark.
+def _first_nan(name):
+    def absent(views, rows):
+        a = views[name][rows]
+        a = a.reshape(a.shape[0], -1)[:, 0]
+        return int((a != a).sum())
+    return absent
+
+
+def _first_negative(name):
+    def absent(views, rows):
+        a = views[name][rows]
+        return int((a.reshape(a.shape[0], -1)[:, 0] < 0).sum())
+    return absent
+
+
+class _CompStage:
+    """The drawn clusters of a draw call.  The ABI's comp is [m][capacity], one slab's: the call writes `stage`, and slice_in(lo, hi) slices the
+    slab's points into `comp` (m, n).  wanted=False: no comp; always=True: the stage exists without comp too (it tells who took no part)."""
+
+    def __init__(self, opened, m, capacity, wanted, always=False):
+        n, new = opened[0], opened[2]
+        self.comp = new(m, (n,), "int32") if wanted else None
+        self.stage = new(m, (capacity,), "int32") if n and (wanted or always) else None
+
+    def slice_in(self, lo, hi):
+        if self.comp is not None and self.stage is not None:
+            self.comp[:, lo:hi] = self.stage[:, :hi - lo]
+
+    def absent(self, views, rows):
+        return int((self.stage[0, rows] < 0).sum())
+
+
 class _Stages:
     """The staging of a Predictor's short slab as host/points.py asks for it -- "host", "dev", "csc" -- kept on the Predictor as
     `_host_stage`, `_dev_stage`, `_csc_stage`; suffix "_in": the D_in-wide ones of dense data that is projected on the way in."""
@@ -405,24 +447,12 @@ class Predictor:
         if self.kind != _priors.PRIOR_NIW:
             raise ValueError("typicality is for the NIW prior: the Multinomial predictive has no closed-form tail")
         on = self._gaps_option(gaps, "typicality")
-        wk = self._wk
-        if not hasattr(wk, "typicality_points_into"):
-            raise RuntimeError("this Predictor's worker cannot score typicality (no dpmm_typicality_points)")
-        total = [0, 0]
-
-        def evaluate(views, lo, hi):
-            sk, inc = wk.typicality_points_into(views)
-            if hi - lo < self.capacity:
-                # the short slab: the worker scored its padding too -- equal points with finite features, so never incomplete and all of
-                # one class, which the first of them shows
-                q0 = float(views["mahalanobis"][hi - lo])
-                if q0 != q0:
-                    sk -= self.capacity - (hi - lo)
-            total[0] += sk
-            total[1] += inc
+        wk = _need(self._wk, "this Predictor's worker cannot score typicality (no dpmm_typicality_points)", "typicality_points_into")
         spec = [("labels", (), "int64"), ("mahalanobis", (), "float32"), ("tail", (), "float32")]
-        out = self._with_gaps(on, lambda: self._walk(self._open(data), spec, evaluate))
-        return Typicality(out["labels"], out["mahalanobis"], out["tail"], total[0], total[1])
+        # (the padding of a short slab is equal points with finite features: skipped or not, never incomplete)
+        out, (sk, inc) = self._with_gaps(on, lambda: self._walk(self._open(data), spec, lambda views, lo, hi: wk.typicality_points_into(views),
+                                                                absent=_first_nan("mahalanobis")))
+        return Typicality(out["labels"], out["mahalanobis"], out["tail"], sk, inc)
 
     # ---- per-feature explanations (include/dpmm_hip_explain.h)
     def explain(self, data, top=None, gaps="incomplete"):
@@ -463,26 +493,15 @@ class Predictor:
             if m != top or not 1 <= m <= min(self.D, binding.EXPLAIN_MAX_TOP):
                 raise ValueError(f"top must be None or an integer in 1..{min(self.D, binding.EXPLAIN_MAX_TOP)}")
         on = self._gaps_option(gaps, "explain")
-        wk = self._wk
-        if not hasattr(wk, "explain_points_into"):
-            raise RuntimeError("this Predictor's worker cannot explain points (no dpmm_explain_points)")
-        total = [0, 0]
-
-        def evaluate(views, lo, hi):
-            sk, inc = wk.explain_points_into(views, top=m)
-            if hi - lo < self.capacity:
-                # the short slab: the padding is of one class, which its first point shows (as `typicality`)
-                q0 = float(views["mahalanobis"][hi - lo])
-                if q0 != q0:
-                    sk -= self.capacity - (hi - lo)
-            total[0] += sk
-            total[1] += inc
+        wk = _need(self._wk, "this Predictor's worker cannot explain points (no dpmm_explain_points)", "explain_points_into")
         width = (m or self.D,)
         spec = [("labels", (), "int64"), ("mahalanobis", (), "float32"), ("tail", (), "float32"), ("residual", width, "float32"),
                 ("zscore", width, "float32"), ("feature_tail", width, "float32")] + ([("features", width, "int32")] if m else [])
-        out = self._with_gaps(on, lambda: self._walk(self._open(data), spec, evaluate))
+        # (the padding of a short slab: as `typicality`, never incomplete)
+        out, (sk, inc) = self._with_gaps(on, lambda: self._walk(self._open(data), spec, lambda views, lo, hi: wk.explain_points_into(views, top=m),
+                                                                absent=_first_nan("mahalanobis")))
         rows = [out[name] if m else out[name].T for name in ("residual", "zscore", "feature_tail")]
-        return Explanation(out["labels"], out["mahalanobis"], out["tail"], rows[0], rows[1], rows[2], out["features"] if m else None, total[0], total[1])
+        return Explanation(out["labels"], out["mahalanobis"], out["tail"], rows[0], rows[1], rows[2], out["features"] if m else None, sk, inc)
 
     # ---- exemplars (include/dpmm_hip_rank.h)
     def exemplars(self, data, m, which="both"):
@@ -508,9 +527,7 @@ class Predictor:
         mask = {"typical": binding.RANK_TYPICAL, "fringe": binding.RANK_FRINGE, "both": binding.RANK_TYPICAL | binding.RANK_FRINGE}.get(which)
         if mask is None:
             raise ValueError('which must be "typical", "fringe" or "both"')
-        wk = self._wk
-        if not hasattr(wk, "rank_begin"):
-            raise RuntimeError("this Predictor's worker cannot rank points (no dpmm_rank_begin)")
+        wk = _need(self._wk, "this Predictor's worker cannot rank points (no dpmm_rank_begin)", "rank_begin")
         opened = self._open(data)
         wk.rank_begin(m, mask)
         self._walk(opened, [], lambda views, lo, hi: wk.rank_accumulate(lo, hi - lo))
@@ -534,9 +551,7 @@ class Predictor:
         result into the agglomerative hierarchy of the clusters."""
         if self._wk is None:
             raise RuntimeError("this Predictor is closed")
-        wk = self._wk
-        if not hasattr(wk, "overlap_begin"):
-            raise RuntimeError("this Predictor's worker cannot accumulate the cluster overlap (no dpmm_overlap_begin)")
+        wk = _need(self._wk, "this Predictor's worker cannot accumulate the cluster overlap (no dpmm_overlap_begin)", "overlap_begin")
         opened = self._open(data)
         wk.overlap_begin()
         self._walk(opened, [], lambda views, lo, hi: wk.overlap_accumulate(hi - lo))
@@ -573,11 +588,9 @@ class Predictor:
         if assign not in ASSIGN_MODES:
             raise ValueError('assign must be "hard" or "soft"')
         floor, second = f.floors(floor, second)
-        wk = self._wk
-        if not hasattr(wk, f.stats + "_begin"):
-            raise RuntimeError(f"this Predictor's worker cannot accumulate {f.noun} statistics (no dpmm_{f.stats}_begin)")
-        if second is not None and not hasattr(wk, f.set_second):
-            raise RuntimeError(f"this Predictor's worker cannot hold points out {f.by} (no dpmm_{f.set_second})")
+        wk = _need(self._wk, f"this Predictor's worker cannot accumulate {f.noun} statistics (no dpmm_{f.stats}_begin)", f.stats + "_begin")
+        if second is not None:
+            _need(wk, f"this Predictor's worker cannot hold points out {f.by} (no dpmm_{f.set_second})", f.set_second)
         opened = self._open(data)
         getattr(wk, f.stats + "_begin")(ASSIGN_MODES[assign], floor)
         if second is not None:
@@ -628,8 +641,7 @@ class Predictor:
         for name, v in caps.items():
             if v != int(v) or int(v) < 0:
                 raise ValueError(f"{name} must be a non-negative integer")
-        if not hasattr(self._wk, f.holdout + "_begin"):
-            raise RuntimeError(f"this Predictor's worker cannot collect {f.held} (no dpmm_{f.holdout}_begin)")
+        _need(self._wk, f"this Predictor's worker cannot collect {f.held} (no dpmm_{f.holdout}_begin)", f.holdout + "_begin")
         return self._wk, self._open(data), floor, second
 
     def _capture(self, data, min_logdens, min_tail, max_points, what):
@@ -978,10 +990,9 @@ class Predictor:
             return self._impute_draws(data, draws, seed, return_components)
         if return_components:
             raise ValueError("return_components is for draws=m: the mean imputation mixes all clusters")
-        if not hasattr(wk, "impute_points_into"):
-            raise RuntimeError("this Predictor's worker cannot impute points (no dpmm_impute_points)")
-        out = self._walk(self._open(data, refuse_projected="impute"), [("impute", (self.D,), "float32")],
-                         lambda views, lo, hi: wk.impute_points_into(views["impute"]), counts=True)
+        _need(wk, "this Predictor's worker cannot impute points (no dpmm_impute_points)", "impute_points_into")
+        out, _ = self._walk(self._open(data, refuse_projected="impute"), [("impute", (self.D,), "float32")],
+                            lambda views, lo, hi: wk.impute_points_into(views["impute"]), counts=True)
         return out["impute"].T
 
     def _impute_draws(self, data, draws, seed, return_components):
@@ -990,21 +1001,16 @@ class Predictor:
             raise ValueError(f"draws must be None or an integer in 1..{binding.IMPUTE_MAX_DRAWS}")
         if seed < 0 or seed >> 64:
             raise ValueError("seed must be in 0..2^64 - 1")
-        wk, cap = self._wk, self.capacity
-        if not hasattr(wk, "impute_draws_into"):
-            raise RuntimeError("this Predictor's worker cannot draw missing features (no dpmm_impute_draw_points)")
+        wk = _need(self._wk, "this Predictor's worker cannot draw missing features (no dpmm_impute_draw_points)", "impute_draws_into")
         opened = self._open(data, refuse_projected="impute")
-        n, new = opened[0], opened[2]
-        comp = new(m, (n,), "int32") if return_components else None
-        stage = new(m, (cap,), "int32") if return_components and n else None      # the ABI's comp is [m][capacity]: one slab's, then sliced in
+        cs = _CompStage(opened, m, self.capacity, return_components)
 
         def evaluate(views, lo, hi):
-            wk.impute_draws_into(views["draws"], seed, lo, comp=stage)             # the global index of a point is its position in `data`
-            if stage is not None:
-                comp[:, lo:hi] = stage[:, :hi - lo]
-        out = self._walk(opened, [("draws", (m, self.D), "float32")], evaluate, counts=True)["draws"]      # (n, m, D): ld = m D, draw_stride = D
+            wk.impute_draws_into(views["draws"], seed, lo, comp=cs.stage)          # the global index of a point is its position in `data`
+            cs.slice_in(lo, hi)
+        out = self._walk(opened, [("draws", (m, self.D), "float32")], evaluate, counts=True)[0]["draws"]      # (n, m, D): ld = m D, draw_stride = D
         res = out.permute(1, 2, 0) if hasattr(out, "permute") else out.transpose(1, 2, 0)
-        return (res, comp) if return_components else res
+        return (res, cs.comp) if return_components else res
 
     # ---- drawing points (include/dpmm_hip_sample.h)
     def sampler_tables(self):
@@ -1063,8 +1069,7 @@ class Predictor:
             if sparse:
                 raise ValueError("sparse output is for the Multinomial prior")
         wk, cap, D = self._wk, self.capacity, self.D
-        if not hasattr(wk, "sample_points_raw"):
-            raise RuntimeError("this Predictor's worker cannot draw points (no dpmm_sample_points_device)")
+        _need(wk, "this Predictor's worker cannot draw points (no dpmm_sample_points_device)", "sample_points_raw")
         import torch
         if not self._sampler_set:
             t = self.sampler_tables()
@@ -1121,24 +1126,17 @@ class Predictor:
         top = min(self.D, binding.RECOMMEND_MAX_TOP)
         if not 1 <= m <= top:
             raise ValueError(f"m must be in 1..{top}")
-        wk = self._wk
-        if not hasattr(wk, "recommend_points_into"):
-            raise RuntimeError("this Predictor's worker cannot recommend (no dpmm_recommend_points)")
+        wk = _need(self._wk, "this Predictor's worker cannot recommend (no dpmm_recommend_points)", "recommend_points_into")
         opened = self._open(data)
         if not self._recommend_set:
             a = np.asarray(self.post["alpha"], np.float64)
             wk.set_recommend(a / a.sum(1, keepdims=True))
             self._recommend_set = True
         exclude_seen = bool(exclude_seen)
-        total = [0]
-
-        def evaluate(views, lo, hi):
-            sk = wk.recommend_points_into(views, m, exclude_seen)
-            if hi - lo < self.capacity:         # the padding of a short slab is empty points: they have candidates unless they take no part, and are not ours
-                sk -= int((views["features"][hi - lo:, 0] < 0).sum())
-            total[0] += sk
-        out = self._walk(opened, [("features", (m,), "int32"), ("prob", (m,), "float32"), ("labels", (), "int64")], evaluate)
-        return Recommendation(out["features"], out["prob"], out["labels"], total[0])
+        # (the padding of a short slab is empty points: they have candidates unless they take no part)
+        out, (sk, _) = self._walk(opened, [("features", (m,), "int32"), ("prob", (m,), "float32"), ("labels", (), "int64")],
+                                  lambda views, lo, hi: wk.recommend_points_into(views, m, exclude_seen), absent=_first_negative("features"))
+        return Recommendation(out["features"], out["prob"], out["labels"], sk)
 
     # ---- slabs
     def _spec(self, labels, logdens, m, probs):
@@ -1191,14 +1189,19 @@ class Predictor:
                 pts.padded(lo, hi, cap, stages).upload(wk, 0, cap, projected)
         return n, dev, new, upload
 
-    def _walk(self, opened, spec, evaluate, counts=False):
+    def _walk(self, opened, spec, evaluate, counts=False, absent=None):
         """The one walk over opened data in slabs of `capacity` points: every slab is uploaded and `evaluate(views, lo, hi)` called with its
         outputs as `spec` lists them -- slices of the result for a full slab, the staging outputs the Predictor keeps for the short one, whose
-        first hi - lo rows are then copied.  Sets `missing_counts` (the worker is asked under "marginalize", or if `counts`); returns the results."""
+        first hi - lo rows are then copied.  Sets `missing_counts` (the worker is asked under "marginalize", or if `counts`).
+        absent: the call counts -- `evaluate` returns what the worker reported, skipped or (skipped, incomplete) -- and the walk owns the
+        sums: the worker scored the zero padding of a short slab too, which is not ours, so absent(views, rows), how many of `rows` took no
+        part, is counted over the padded rows and taken off `skipped`.  Returns (results, (skipped, incomplete)); without `absent` nothing is
+        counted and the pair is (0, 0)."""
         n, dev, new, upload = opened
         wk, cap = self._wk, self.capacity
         out = {name: new(n, tail, dt) for name, tail, dt in spec}
         total = np.zeros(2, np.int64)
+        took = [0, 0]
         for lo in range(0, n, cap):
             hi = min(n, lo + cap)
             full = hi - lo == cap
@@ -1213,18 +1216,23 @@ class Predictor:
                     if b is None or tuple(b.shape[1:]) != tail or (dev is not None and b.device != dev):
                         b = self._out_stage[(key, name)] = new(cap, tail, dt)
                     views[name] = b
-            evaluate(views, lo, hi)
+            got = evaluate(views, lo, hi)
+            if absent is not None:
+                for i, c in enumerate(got if isinstance(got, tuple) else (got,)):
+                    took[i] += c
+                if not full:
+                    took[0] -= absent(views, slice(hi - lo, cap))
             if counts or self.missing == "marginalize":
                 total += np.asarray(wk.score_missing_counts(), np.int64)
             if not full:
                 for name, _, _ in spec:
                     out[name][lo:hi] = views[name][:hi - lo]
         self.missing_counts = (int(total[0]), int(total[1]))
-        return out
+        return out, tuple(took)
 
     def _run(self, data, labels=False, logdens=False, m=0, probs=False):
         wk = self._wk
-        return self._walk(self._open(data), self._spec(labels, logdens, m, probs), lambda views, lo, hi: wk.score_points_into(views, m=m))
+        return self._walk(self._open(data), self._spec(labels, logdens, m, probs), lambda views, lo, hi: wk.score_points_into(views, m=m))[0]
 
 
 class Regressor:
@@ -1287,8 +1295,7 @@ class Regressor:
             raise RuntimeError("this Regressor is closed")
         if self._tables_for is mg.post:
             return
-        if not hasattr(mg._wk, "set_regression"):
-            raise RuntimeError("this Regressor's worker cannot regress (no dpmm_set_regression)")
+        _need(mg._wk, "this Regressor's worker cannot regress (no dpmm_set_regression)", "set_regression")
         draws = hasattr(mg._wk, "set_regression_factor")      # (a worker without it predicts; `sample` says what is missing)
         B, c, V, h, df, *W = self.tables(factor=draws)
         self._no_var = bool(np.any(df + self.D_o <= 2))
@@ -1319,17 +1326,10 @@ class Regressor:
             raise ValueError("return_std needs df + D_o > 2 for every cluster: a conditional law has no variance")
         wk = mg._wk
         spec = [("mean", (self.D_t,), "float32")] + ([("std", (self.D_t,), "float32")] if return_std else []) + [("labels", (), "int64")]
-        total = [0]
-
-        def evaluate(views, lo, hi):
-            sk = wk.regress_points_into(views["mean"], views.get("std"), views["labels"])
-            if hi - lo < mg.capacity:           # the padding of a short slab is zeros: points that take part, but if they did not, not ours
-                pad = views["mean"][hi - lo:]
-                bad = pad[:, 0] != pad[:, 0]
-                sk -= int(bad.sum())
-            total[0] += sk
-        out = mg._walk(mg._open(data), spec, evaluate)
-        return Regression(out["mean"].T, out["std"].T if return_std else None, out["labels"], total[0])
+        # (the padding of a short slab is zeros: points that take part, but if they did not, not ours)
+        out, (sk, _) = mg._walk(mg._open(data), spec, lambda views, lo, hi: wk.regress_points_into(views["mean"], views.get("std"), views["labels"]),
+                                absent=_first_nan("mean"))
+        return Regression(out["mean"].T, out["std"].T if return_std else None, out["labels"], sk)
 
     def sample(self, data, draws=1, seed=0, return_components=False):
         """`RegressionDraws(values, components, labels, skipped)`: `draws` DRAWS of the targets of every point of `data` (D_o rows in the
@@ -1348,36 +1348,26 @@ class Regressor:
             raise ValueError(f"draws must be an integer in 1..{binding.REGRESS_MAX_DRAWS}")
         if seed < 0 or seed >> 64:
             raise ValueError("seed must be in 0..2^64 - 1")
-        wk, cap = mg._wk, mg.capacity
-        if not hasattr(wk, "regress_draw_points_into") or not hasattr(wk, "set_regression_factor"):
-            raise RuntimeError("this Regressor's worker cannot draw the targets (no dpmm_regress_draw_points)")
+        wk = _need(mg._wk, "this Regressor's worker cannot draw the targets (no dpmm_regress_draw_points)", "regress_draw_points_into", "set_regression_factor")
         opened = mg._open(data)
-        n, new = opened[0], opened[2]
-        comp = new(m, (n,), "int32") if return_components else None
-        stage = new(m, (cap,), "int32") if n else None            # the ABI's comp is [m][capacity]: one slab's, then sliced in
-        total = [0]
+        cs = _CompStage(opened, m, mg.capacity, return_components, always=True)      # (a component of -1 is the mark of a point that took no part)
 
         def evaluate(views, lo, hi):
-            sk = wk.regress_draw_points_into(views["draws"], seed, lo, comp=stage)      # the global index of a point is its position in `data`
+            sk = wk.regress_draw_points_into(views["draws"], seed, lo, comp=cs.stage)      # the global index of a point is its position in `data`
             wk.score_points_into({"labels": views["labels"]})
-            if hi - lo < cap:                    # (the padding of a short slab is zeros, as in `predict`: not ours if it took no part)
-                sk -= int((stage[0, hi - lo:] < 0).sum())
-            total[0] += sk
-            if comp is not None:
-                comp[:, lo:hi] = stage[:, :hi - lo]
-        out = mg._walk(opened, [("draws", (m, self.D_t), "float32"), ("labels", (), "int64")], evaluate)      # (n, m, D_t): ld = m D_t, draw_stride = D_t
+            cs.slice_in(lo, hi)
+            return sk
+        out, (sk, _) = mg._walk(opened, [("draws", (m, self.D_t), "float32"), ("labels", (), "int64")], evaluate, absent=cs.absent)      # (n, m, D_t): ld = m D_t, draw_stride = D_t
         vals = out["draws"]
         vals = vals.permute(1, 2, 0) if hasattr(vals, "permute") else vals.transpose(1, 2, 0)
-        return RegressionDraws(vals, comp, out["labels"], total[0])
+        return RegressionDraws(vals, cs.comp, out["labels"], sk)
 
 
     # ---- calibrated probabilities (include/dpmm_hip_regress_cdf.h)
     def _cdf_worker(self, what):
         self._refresh()
-        wk = self.marginal._wk
-        if not all(hasattr(wk, f) for f in ("regress_cdf_points_into", "set_regression_levels", "regress_quantile_points_into")):
-            raise RuntimeError(f"this Regressor's worker cannot give {what} (no dpmm_regress_cdf_points)")
-        return wk
+        return _need(self.marginal._wk, f"this Regressor's worker cannot give {what} (no dpmm_regress_cdf_points)", "regress_cdf_points_into",
+                     "set_regression_levels", "regress_quantile_points_into")
 
     def cdf(self, data, y):
         """`ConditionalCDF(cdf, sf, labels, skipped)`: for every point of `data` (D_o rows in the order of `given`, every input kind
@@ -1404,8 +1394,7 @@ class Regressor:
             raise ValueError(f"y must be (D_t, n) = ({self.D_t}, {n}), in the order of `targets`")
         if (dev is None) != (y_dev is None) or (dev is not None and y_dev != dev):
             raise ValueError("y must live where the data lives: host memory (a numpy array or a CPU tensor) for host data, the data's device for a device tensor")
-        ys = new(cap, (self.D_t,), "float32") if n else None
-        total = [0]
+        ys = new(cap, (self.D_t,), "float32") if n else None      # y of one slab, point-major as the worker reads it, zeros behind the slab's points
 
         def evaluate(views, lo, hi):
             m = hi - lo
@@ -1415,13 +1404,10 @@ class Regressor:
             else:
                 ys[:m] = y[:, lo:hi].T
             ys[m:] = 0
-            sk = wk.regress_cdf_points_into(ys, views["cdf"], views["sf"], views["labels"])
-            if m < cap:                          # (the padding of a short slab is zeros, as in `predict`: not ours if it took no part)
-                pad = views["cdf"][m:]
-                sk -= int((pad[:, 0] != pad[:, 0]).sum())
-            total[0] += sk
-        out = mg._walk(opened, [("cdf", (self.D_t,), "float32"), ("sf", (self.D_t,), "float32"), ("labels", (), "int64")], evaluate)
-        return ConditionalCDF(out["cdf"].T, out["sf"].T, out["labels"], total[0])
+            return wk.regress_cdf_points_into(ys, views["cdf"], views["sf"], views["labels"])
+        out, (sk, _) = mg._walk(opened, [("cdf", (self.D_t,), "float32"), ("sf", (self.D_t,), "float32"), ("labels", (), "int64")], evaluate,
+                                absent=_first_nan("cdf"))
+        return ConditionalCDF(out["cdf"].T, out["sf"].T, out["labels"], sk)
 
     def quantile(self, data, levels=(0.05, 0.5, 0.95)):
         """`RegressionQuantiles(values, levels, labels, skipped)`: values[q, d, i] is the y at which the conditional CDF of target d of
@@ -1431,7 +1417,7 @@ class Regressor:
         which the CDF crosses the level.  Values are non-decreasing in the level, and a value depends on (the point, the model, the
         level) alone.  Skipped points as in `cdf`."""
         mg = self.marginal
-        wk, cap = self._cdf_worker("conditional quantiles"), mg.capacity
+        wk = self._cdf_worker("conditional quantiles")
         lv = np.atleast_1d(np.asarray(levels, np.float64))
         if lv.ndim != 1 or not 1 <= len(lv) <= binding.REGRESS_MAX_LEVELS:
             raise ValueError(f"levels: 1 to {binding.REGRESS_MAX_LEVELS} numbers")
@@ -1444,19 +1430,12 @@ class Regressor:
             wk.set_regression_levels(inc, _condition.student_t_ppf(inc, df + self.D_o))
             self._levels_for = key
         L = len(inc)
-        total = [0]
-
-        def evaluate(views, lo, hi):
-            sk = wk.regress_quantile_points_into(views["values"], views["labels"])
-            if hi - lo < cap:
-                pad = views["values"][hi - lo:]
-                sk -= int((pad[:, 0, 0] != pad[:, 0, 0]).sum())
-            total[0] += sk
-        out = mg._walk(mg._open(data), [("values", (L, self.D_t), "float32"), ("labels", (), "int64")], evaluate)
+        out, (sk, _) = mg._walk(mg._open(data), [("values", (L, self.D_t), "float32"), ("labels", (), "int64")],
+                                lambda views, lo, hi: wk.regress_quantile_points_into(views["values"], views["labels"]), absent=_first_nan("values"))
         vals = out["values"]
         vals = vals.permute(1, 2, 0) if hasattr(vals, "permute") else vals.transpose(1, 2, 0)
         vals = vals[back.tolist()] if hasattr(vals, "permute") else vals[back]
-        return RegressionQuantiles(vals, tuple(float(v) for v in lv), out["labels"], total[0])
+        return RegressionQuantiles(vals, tuple(float(v) for v in lv), out["labels"], sk)
 
     def interval(self, data, level=0.9):
         """(lower, upper), each (D_t, n): the central prediction interval of every target at coverage `level`, 0 < level < 1 -- `quantile`
