@@ -228,6 +228,22 @@ ABI_EXPLAIN = [
 EXPLAIN_MAX_TOP = 16                   # DPMM_EXPLAIN_MAX_TOP
 
 
+class ExplainGroupsOut(ctypes.Structure):
+    """dpmm_explain_groups_out (include/dpmm_hip_explain_groups.h): host or device addresses (the two counters always host), 0 / None = not
+    asked for; ld, the entries between two points' rows."""
+    _fields_ = [("labels", ctypes.c_void_p), ("mahalanobis", ctypes.c_void_p), ("tail", ctypes.c_void_p), ("skipped", ctypes.c_void_p),
+                ("incomplete", ctypes.c_void_p), ("group_mahalanobis", ctypes.c_void_p), ("group_tail", ctypes.c_void_p), ("ld", ctypes.c_int64)]
+
+
+# include/dpmm_hip_explain_groups.h: the conditional distance and tail of every group of features of a point (additive; bound next to ABI)
+ABI_EXPLAIN_GROUPS = [
+    ("dpmm_set_explain_groups", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, _c_i64p, ctypes.POINTER(ctypes.c_int32), _c_f64p]),
+    ("dpmm_explain_groups_points", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ExplainGroupsOut)]),
+    ("dpmm_explain_groups_points_device", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ExplainGroupsOut)]),
+]
+EXPLAIN_MAX_GROUPS = 64                # DPMM_EXPLAIN_MAX_GROUPS
+
+
 class HoldoutOut(ctypes.Structure):
     """dpmm_holdout_out (include/dpmm_hip_holdout.h): host addresses, 0 / None = not asked for."""
     _fields_ = [("total", ctypes.c_void_p), ("stored", ctypes.c_void_p), ("skipped", ctypes.c_void_p), ("incomplete", ctypes.c_void_p),
@@ -426,7 +442,7 @@ def load_library():
         except Exception:  # pragma: no cover  (torch is optional for single-GPU use)
             pass
         lib = ctypes.CDLL(p)
-        for name, res, args in ABI + ABI_TENSOR + ABI_SCORE + ABI_RANK + ABI_OVERLAP + ABI_BATCHSTATS + ABI_COUNTSTATS + ABI_TYPICALITY + ABI_EXPLAIN + ABI_HOLDOUT + ABI_COUNTHOLDOUT + ABI_TRACE + ABI_MISSING + ABI_IMPUTE + ABI_REGRESS + ABI_REGRESS_DRAW + ABI_REGRESS_CDF + ABI_RECOMMEND + ABI_CSC + ABI_SAMPLE + ABI_PROJECT:
+        for name, res, args in ABI + ABI_TENSOR + ABI_SCORE + ABI_RANK + ABI_OVERLAP + ABI_BATCHSTATS + ABI_COUNTSTATS + ABI_TYPICALITY + ABI_EXPLAIN + ABI_EXPLAIN_GROUPS + ABI_HOLDOUT + ABI_COUNTHOLDOUT + ABI_TRACE + ABI_MISSING + ABI_IMPUTE + ABI_REGRESS + ABI_REGRESS_DRAW + ABI_REGRESS_CDF + ABI_RECOMMEND + ABI_CSC + ABI_SAMPLE + ABI_PROJECT:
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -866,6 +882,41 @@ class Worker:
         _, ptr, dev = self._marshal("dpmm_explain_points", [(name, a, self._EXPLAIN_OUTS[name], True) for name, a in outs.items()])
         cnt = np.zeros(2, np.int64)
         self.explain_points_raw(dev, top=top, ld=ld, skipped=cnt.ctypes.data, incomplete=cnt.ctypes.data + 8, **ptr)
+        return int(cnt[0]), int(cnt[1])
+
+    # ---- explanations by groups of features (include/dpmm_hip_explain_groups.h)
+    _EXPLAIN_GROUPS_OUTS = dict(labels="int64", mahalanobis="float32", tail="float32", group_mahalanobis="float32", group_tail="float32")
+
+    def set_explain_groups(self, groups, W):
+        """dpmm_set_explain_groups: `groups`, a sequence of sequences of 0-based feature indices (increasing inside a group), and W, the
+        Float64 rows of the lower triangles of the factors L^-1 packed per cluster and group as the header says (what
+        host/condition.py's `group_factors` returns), for the predictive parameters in force."""
+        sizes = [len(g) for g in groups]
+        offsets = _i64(np.concatenate([[0], np.cumsum(sizes)]))
+        features = np.ascontiguousarray(np.concatenate([np.asarray(g, np.int64).ravel() for g in groups]) if sizes else np.zeros(0), np.int32)
+        W = np.ascontiguousarray(W, np.float64).ravel()
+        assert W.size == self.K * sum(s * (s + 1) // 2 for s in sizes), "set_explain_groups: W holds K sum s (s + 1) / 2 values"
+        self._chk(self._lib.dpmm_set_explain_groups(self._h, len(sizes), _p(offsets, _c_i64p), _p(features, ctypes.POINTER(ctypes.c_int32)), _p(W, _c_f64p)))
+
+    def explain_groups_points_raw(self, device, ld=0, labels=0, mahalanobis=0, tail=0, skipped=0, incomplete=0, group_mahalanobis=0, group_tail=0):
+        """dpmm_explain_groups_points[_device] on plain addresses (integers; 0 = not asked for); skipped, incomplete: host addresses."""
+        out = ExplainGroupsOut(labels or None, mahalanobis or None, tail or None, skipped or None, incomplete or None, group_mahalanobis or None,
+                               group_tail or None, int(ld))
+        fn = self._lib.dpmm_explain_groups_points_device if device else self._lib.dpmm_explain_groups_points
+        self._chk(fn(self._h, ctypes.byref(out)))
+
+    def explain_groups_points_into(self, outs):
+        """dpmm_explain_groups_points[_device] into storage the caller made: `outs` maps `labels` / `mahalanobis` / `tail` (n entries each)
+        and `group_mahalanobis` / `group_tail` ((n, ld >= G) each, one ld for both) to contiguous numpy arrays (host variant) or torch
+        tensors on this worker's GPU (device variant); returns (skipped, incomplete)."""
+        ld = 0
+        for name in ("group_mahalanobis", "group_tail"):
+            if name in outs:
+                assert len(outs[name].shape) == 2 and ld in (0, outs[name].shape[1]), name
+                ld = int(outs[name].shape[1])
+        _, ptr, dev = self._marshal("dpmm_explain_groups_points", [(name, a, self._EXPLAIN_GROUPS_OUTS[name], True) for name, a in outs.items()])
+        cnt = np.zeros(2, np.int64)
+        self.explain_groups_points_raw(dev, ld=ld, skipped=cnt.ctypes.data, incomplete=cnt.ctypes.data + 8, **ptr)
         return int(cnt[0]), int(cnt[1])
 
     # ---- missing features (include/dpmm_hip_missing.h)

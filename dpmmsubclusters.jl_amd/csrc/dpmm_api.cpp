@@ -15,6 +15,7 @@
 #include "../../include/dpmm_hip_countstats.h"
 #include "../../include/dpmm_hip_typicality.h"
 #include "../../include/dpmm_hip_explain.h"
+#include "../../include/dpmm_hip_explain_groups.h"
 #include "../../include/dpmm_hip_holdout.h"
 #include "../../include/dpmm_hip_countholdout.h"
 #include "../../include/dpmm_hip_trace.h"
@@ -178,6 +179,14 @@ struct dpmm_ctx {
     // call and made from the parameter set exp_gen (0: none)
     DevBuf<float> d_exp_rr, d_exp_a;
     unsigned long long exp_gen = 0;
+    // explanation by groups (include/dpmm_hip_explain_groups.h): the Float32 image of W, the descriptors (goff [G + 1], then gfeat) and the
+    // groups' first words, allocated by dpmm_set_explain_groups and made for the parameter set exg_gen (0: none)
+    unsigned long long exg_gen = 0;
+    int exg_G = 0;
+    int64_t exg_wstep = 0;
+    DevBuf<float> d_exg_w;
+    DevBuf<int32_t> d_exg_desc;
+    DevBuf<int64_t> d_exg_gw;
     // held-out points (include/dpmm_hip_holdout.h): ballots, class counts and first slots of the workgroups of one range; the running totals;
     // the caller's destination as dpmm_holdout_begin took it.  With a tail floor the tails of a range go through d_bs_tail, as batchstats' do.
     DevBuf<unsigned long long> d_ho_ballot, d_ho_state;
@@ -4279,6 +4288,150 @@ static int explain_points(dpmm_ctx *c, const dpmm_explain_out *o, bool device, c
 
 int dpmm_explain_points(dpmm_ctx *c, const dpmm_explain_out *out) { return explain_points(c, out, false, "dpmm_explain_points"); }
 int dpmm_explain_points_device(dpmm_ctx *c, const dpmm_explain_out *out) { return explain_points(c, out, true, "dpmm_explain_points_device"); }
+
+// ---- include/dpmm_hip_explain_groups.h: behind the typicality pass of every range, q_G and its tail for every group (explain_group.hip) ----
+static_assert(DPMM_EXPLAIN_MAX_GROUPS == EXPLAIN_MAX_GROUPS, "header / kernel limits out of sync");
+int dpmm_set_explain_groups(dpmm_ctx *c, int32_t G, const int64_t *offsets, const int32_t *features, const double *W) {
+    static const char *fn = "dpmm_set_explain_groups";
+    if (!c) return tensor_no_ctx(fn);
+    const std::string who = std::string(fn) + ": ";
+    if (c->prior != DPMM_PRIOR_NIW) return fail(c, DPMM_EINVAL, who + "the explanation is that of the NIW prior's Student-t predictive; the Multinomial predictive has no closed-form tail");
+    if (G < 1 || G > DPMM_EXPLAIN_MAX_GROUPS) return fail(c, DPMM_EINVAL, who + "G must be in 1.." + std::to_string(DPMM_EXPLAIN_MAX_GROUPS));
+    if (!offsets) return fail(c, DPMM_EINVAL, who + "offsets is null");
+    if (!features) return fail(c, DPMM_EINVAL, who + "features is null");
+    if (!W) return fail(c, DPMM_EINVAL, who + "W is null");
+    if (!c->predictive) return fail(c, DPMM_ESTATE, who + "needs dpmm_set_predictive_niw first");
+    const int64_t D = c->D;
+    if (offsets[0] != 0) return fail(c, DPMM_EINVAL, who + "offsets[0] must be 0");
+    for (int j = 0; j < G; ++j)
+        if (offsets[j + 1] <= offsets[j] || offsets[j + 1] > D)
+            return fail(c, DPMM_EINVAL, who + "offsets must increase strictly (no empty group) and end at D at most, group " + std::to_string(j));
+    std::vector<char> seen((size_t)D, 0);
+    for (int j = 0; j < G; ++j)
+        for (int64_t e = offsets[j]; e < offsets[j + 1]; ++e) {
+            const int64_t f = features[e];
+            if (f < 0 || f >= D) return fail(c, DPMM_EINVAL, who + "features out of 0..D-1 in group " + std::to_string(j));
+            if (e > offsets[j] && f <= features[e - 1]) return fail(c, DPMM_EINVAL, who + "features must increase strictly inside group " + std::to_string(j));
+            if (seen[(size_t)f]) return fail(c, DPMM_EINVAL, who + "features: feature " + std::to_string(f) + " is in two groups");
+            seen[(size_t)f] = 1;
+        }
+    // the images: descriptors, first words, and per cluster and group the columns of W padded to explain_group_pitch(s) rows, rounded once
+    const size_t K = (size_t)c->K, total = (size_t)offsets[G];
+    std::vector<int32_t> desc((size_t)G + 1 + total);
+    std::vector<int64_t> gw((size_t)G);
+    size_t wstep = 0, tri = 0;
+    for (int j = 0; j < G; ++j) {
+        const size_t s = (size_t)(offsets[j + 1] - offsets[j]);
+        desc[(size_t)j] = (int32_t)offsets[j];
+        gw[(size_t)j] = (int64_t)wstep;
+        wstep += s * (size_t)explain_group_pitch((int)s);
+        tri += s * (s + 1) / 2;
+    }
+    desc[(size_t)G] = (int32_t)total;
+    for (size_t e = 0; e < total; ++e) desc[(size_t)G + 1 + e] = features[e];
+    std::vector<float> img(K * wstep, 0.f);
+    for (size_t k = 0; k < K; ++k) {
+        const double *src = W + k * tri;
+        for (int j = 0; j < G; ++j) {
+            const size_t s = (size_t)(offsets[j + 1] - offsets[j]), sp = (size_t)explain_group_pitch((int)s);
+            float *dst = img.data() + k * wstep + (size_t)gw[(size_t)j];
+            for (size_t r = 0; r < s; ++r)
+                for (size_t cc = 0; cc <= r; ++cc) {
+                    const double w = *src++;
+                    if (!std::isfinite(w) || !std::isfinite((float)w)) return fail(c, DPMM_EINVAL, who + "W holds a value that is not finite (in Float32), cluster " + std::to_string(k) + " group " + std::to_string(j));
+                    dst[cc * sp + r] = (float)w;
+                }
+        }
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    c->exg_gen = 0;      // (a failure below leaves no tables in force)
+    if (int rc = grow(c, c->d_exg_w, sizeof(float) * img.size(), fn, "group tables")) return rc;
+    if (int rc = grow(c, c->d_exg_desc, sizeof(int32_t) * desc.size(), fn, "group descriptors")) return rc;
+    if (int rc = grow(c, c->d_exg_gw, sizeof(int64_t) * gw.size(), fn, "group descriptors")) return rc;
+    HIPCHK(c, sync_stream(c, c->stream));
+    HIPCHK(c, hipMemcpy(c->d_exg_w, img.data(), sizeof(float) * img.size(), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->d_exg_desc, desc.data(), sizeof(int32_t) * desc.size(), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->d_exg_gw, gw.data(), sizeof(int64_t) * gw.size(), hipMemcpyHostToDevice));
+    c->exg_G = G; c->exg_wstep = (int64_t)wstep;
+    c->exg_gen = c->pred_gen;
+    return DPMM_OK;
+}
+
+static int explain_groups_points(dpmm_ctx *c, const dpmm_explain_groups_out *o, bool device, const char *fn) {
+    if (!c) return tensor_no_ctx(fn);
+    c->miss_counted = false;      // (as score_points)
+    const std::string who = std::string(fn) + ": ";
+    if (!o) return fail(c, DPMM_EINVAL, who + "out is null");
+    if (c->prior != DPMM_PRIOR_NIW) return fail(c, DPMM_EINVAL, who + "the explanation is that of the NIW prior's Student-t predictive; the Multinomial predictive has no closed-form tail");
+    const bool rows = o->group_mahalanobis || o->group_tail;
+    if (!o->labels && !o->mahalanobis && !o->tail && !o->skipped && !o->incomplete && !rows) return fail(c, DPMM_EINVAL, who + "every output pointer is null");
+    if (!c->predictive) return fail(c, DPMM_ESTATE, who + "needs dpmm_set_predictive_niw first");
+    if (c->exg_gen == 0 || c->exg_gen != c->pred_gen) return fail(c, DPMM_ESTATE, who + "needs dpmm_set_explain_groups for the predictive parameters in force");
+    const int64_t width = c->exg_G;
+    if (rows && o->ld < width) return fail(c, DPMM_EINVAL, who + "ld < G");
+    if (rows && (o->ld >> 31)) return fail(c, DPMM_EINVAL, who + "ld out of range (below 2^31)");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (o->skipped) o->skipped[0] = 0;
+    if (o->incomplete) o->incomplete[0] = 0;
+    if (c->n == 0) return DPMM_OK;
+    if (!c->have_points || !c->have_params || !c->dX) return fail(c, DPMM_ESTATE, who + "needs points and parameters");
+    const uint64_t n = (uint64_t)c->n, ld = rows ? (uint64_t)o->ld : 0;
+    if (ld && n > (UINT64_MAX / sizeof(int64_t)) / ld) return fail(c, DPMM_EINVAL, who + "n_local * ld out of range");      // (the extents below cannot wrap)
+    if (device) {
+        if (o->labels) if (int rc = check_device_extent(c, fn, "labels", o->labels, sizeof(int64_t) * n, sizeof(int64_t))) return rc;
+        if (o->mahalanobis) if (int rc = check_device_extent(c, fn, "mahalanobis", o->mahalanobis, sizeof(float) * n, sizeof(float))) return rc;
+        if (o->tail) if (int rc = check_device_extent(c, fn, "tail", o->tail, sizeof(float) * n, sizeof(float))) return rc;
+        if (o->group_mahalanobis) if (int rc = check_device_extent(c, fn, "group_mahalanobis", o->group_mahalanobis, sizeof(float) * n * ld, sizeof(float))) return rc;
+        if (o->group_tail) if (int rc = check_device_extent(c, fn, "group_tail", o->group_tail, sizeof(float) * n * ld, sizeof(float))) return rc;
+    }
+    TableWalk w;
+    if (int rc = walk_open(c, fn, WALK_MISS_OPTION, &w)) return rc;
+    if (int rc = typ_begin(c, w.P, fn)) return rc;
+    if (rows) if (int rc = explain_params(c)) return rc;      // (the row-major factors of explain.hip)
+    HIPCHK(c, hipMemsetAsync(c->d_typ_cnt, 0, 3 * sizeof(unsigned long long), c->stream));
+    // the rows: as explain_points -- in the caller's device memory ld entries apart; staged (host variant) dense and copied row by row
+    const uint64_t sld = device ? ld : (uint64_t)width;
+    OutStage<5> out{{{o->labels, sizeof(int64_t)}, {o->mahalanobis, sizeof(float)}, {o->tail, sizeof(float)}, {o->group_mahalanobis, sizeof(float) * sld},
+                     {o->group_tail, sizeof(float) * sld}}, device};
+    if (!device) {
+        if (int rc = grow(c, c->d_score_out, out.layout((size_t)w.P), "dpmm_score_points", "staging of the outputs")) return rc;
+        out.buf = c->d_score_out;
+    }
+    if (int rc = walk_ranges(c, w, c->n, fn, [&](int64_t p0, int64_t np, int64_t) -> int {
+            if (int rc = typ_range(c, w.P, p0, np, out.at<int64_t>(0, p0), out.at<float>(1, p0), out.at<float>(2, p0), fn)) return rc;
+            if (rows) {
+                ExplainGroupArgs a{};
+                a.n = np; a.K = c->K; a.D = c->D; a.G = c->exg_G;
+                a.X = c->dX + p0 * c->ldx; a.ldx = c->ldx;
+                const TypicalityArgs t = niw_range_args<TypicalityArgs>(c, w.P, p0, np);      // (the copies and the means the typicality pass has just read)
+                a.Rt = t.Rt; a.mu = t.mu; a.mu_step = t.mu_step; a.cst = t.cst;
+                a.Rr = c->d_exp_rr; a.cls = c->d_typ_cls;
+                a.goff = c->d_exg_desc; a.gfeat = c->d_exg_desc + (c->exg_G + 1); a.gw = c->d_exg_gw; a.W = c->d_exg_w; a.wstep = c->exg_wstep;
+                a.group_q = out.at<float>(3, p0); a.group_tail = out.at<float>(4, p0); a.ld = (int64_t)sld;
+                if (int rc = table_result(c, fn, launch_explain_group_range(a, 32 * c->cus, c->stream))) return rc;
+            }
+            if (device) return DPMM_OK;
+            for (int i = 3; i < 5; ++i) {      // (then the three vectors and the wait, by flush)
+                OutCol &q = out.col[i];
+                if (!q.dst) continue;
+                HIPCHK(c, hipMemcpy2DAsync(static_cast<char *>(q.dst) + (size_t)p0 * ld * 4, (size_t)ld * 4, out.buf + q.off, (size_t)width * 4, (size_t)width * 4, (size_t)np,
+                                           hipMemcpyDeviceToHost, c->stream));
+                q.dst = nullptr;
+            }
+            const int rc = table_result(c, fn, out.flush(c, p0, (size_t)np));
+            out.col[3].dst = o->group_mahalanobis; out.col[4].dst = o->group_tail;
+            return rc;
+        })) return rc;
+    HIPCHK(c, sync_stream(c, c->stream));
+    unsigned long long h[3] = {0, 0, 0};
+    HIPCHK(c, hipMemcpy(h, c->d_typ_cnt, sizeof(h), hipMemcpyDeviceToHost));
+    if (o->skipped) o->skipped[0] = (int64_t)h[0];
+    if (o->incomplete) o->incomplete[0] = (int64_t)h[1];
+    return DPMM_OK;
+}
+
+int dpmm_explain_groups_points(dpmm_ctx *c, const dpmm_explain_groups_out *out) { return explain_groups_points(c, out, false, "dpmm_explain_groups_points"); }
+int dpmm_explain_groups_points_device(dpmm_ctx *c, const dpmm_explain_groups_out *out) { return explain_groups_points(c, out, true, "dpmm_explain_groups_points_device"); }
 
 static int impute_points(dpmm_ctx *c, float *out, int64_t ld, bool device, const char *fn) {
     if (!c) return tensor_no_ctx(fn);

@@ -629,6 +629,32 @@ struct ExplainArgs {
 hipError_t launch_explain_params(const float *Rpk, int64_t step, float *Rr, float *a, int K, int D, hipStream_t s);      // Rpk: as launch_miss_transpose
 hipError_t launch_explain_range(const ExplainArgs &a, int max_grid, hipStream_t s);
 hipError_t launch_explain_gap_range(const ExplainArgs &a, int max_grid, hipStream_t s);      // explain_gap.hip: behind launch_explain_range, a.list != null
+// ---- explanation by groups of features (explain_group.hip; include/dpmm_hip_explain_groups.h): behind launch_typicality_range of the same
+// range: for a scored point and every group q_G = |W g_G|^2 and the tail of its F statistic
+constexpr int EXPLAIN_MAX_GROUPS = 64;    // DPMM_EXPLAIN_MAX_GROUPS
+constexpr int explain_group_pitch(int s) { return 64 * ((s + 63) / 64); }      // rows a column of a group's W is padded to
+struct ExplainGroupArgs {
+    int64_t n;
+    int K, D, G;
+    const float *X;              // [n][ldx], the range's first point
+    int64_t ldx;
+    const float *Rt;             // as ExplainArgs
+    const float *Rr;
+    const float *mu;
+    int64_t mu_step;
+    const double *cst;
+    const int32_t *cls;          // [n] the class words launch_typicality_range wrote for this range
+    const int32_t *goff;         // [G + 1] group j holds the entries goff[j] .. goff[j + 1] - 1 of gfeat
+    const int32_t *gfeat;        // [goff[G]] 0-based features, below D
+    const int64_t *gw;           // [G] the first word of group j inside a cluster's image of W
+    const float *W;              // [K][wstep]: group j's column c at W + k * wstep + gw[j] + c * explain_group_pitch(s_j), entry r the
+                                 // Float32 W_rc, zero above the diagonal (r < c) and in the pad (r >= s_j)
+    int64_t wstep;
+    float *group_q;              // [n][ld] or null
+    float *group_tail;           // [n][ld] or null
+    int64_t ld;                  // >= G
+};
+hipError_t launch_explain_group_range(const ExplainGroupArgs &a, int max_grid, hipStream_t s);
 // draws of the missing features (include/dpmm_hip_impute.h) behind launch_miss_list and launch_miss_patch(a, false, ..) of the same range
 constexpr int64_t MISS_DRAW_MAX = (int64_t)1 << 26;      // draw indices: 64 Philox blocks each in a 32-bit block number
 struct MissDraw {

@@ -109,6 +109,62 @@ def regression_tables(m, R, given, targets, factor=False):
     return B, c, V
 
 
+def check_groups(groups, D, most):
+    """`groups` of `Predictor.explain_groups` -- a sequence of index sequences, or a dict name -> indices -- as (names or None, list of
+    sorted lists of distinct 0-based indices below D): 1 .. `most` groups, none empty, pairwise disjoint; ValueError otherwise."""
+    names = None
+    if isinstance(groups, dict):
+        names, groups = tuple(groups.keys()), list(groups.values())
+    try:
+        groups = [list(g) for g in groups]
+    except TypeError:
+        raise ValueError("groups must be a sequence of sequences of feature indices, or a dict name -> indices") from None
+    if not 1 <= len(groups) <= most:
+        raise ValueError(f"groups must hold between 1 and {most} groups")
+    out, seen = [], set()
+    for j, g in enumerate(groups):
+        what = f"group {names[j]!r}" if names is not None else f"group {j}"
+        try:
+            idx = [int(f) for f in g]
+            same = all(i == f for i, f in zip(idx, g))
+        except (TypeError, ValueError):
+            raise ValueError(f"{what} must be a sequence of integer feature indices") from None
+        if not same:
+            raise ValueError(f"{what} must be a sequence of integer feature indices")
+        if not idx:
+            raise ValueError(f"{what} is empty")
+        if min(idx) < 0 or max(idx) >= D:
+            raise ValueError(f"{what} must lie in 0..{D - 1}")
+        if len(set(idx)) != len(idx):
+            raise ValueError(f"{what} repeats a feature")
+        if seen & set(idx):
+            raise ValueError(f"{what} overlaps an earlier group in {sorted(seen & set(idx))}")
+        seen |= set(idx)
+        out.append(sorted(idx))
+    return names, out
+
+
+def group_factors(R, groups, packed=True):
+    """The tables of include/dpmm_hip_explain_groups.h in Float64 from the predictive factors R (K, D, D) or (K, D D), upper triangular
+    with Sigma^-1 = A = R'R -- the Float32 values the worker holds, widened: the exact A is defined from these.  For every cluster and every
+    group G (a sorted list of feature indices) A_GG = L L' by Cholesky and W = L^-1, lower triangular, so that q_G = |W g_G|^2.
+    packed=True: (K, T) -- per cluster group after group, per group the rows of the lower triangle, row r holding columns 0 .. r.
+    packed=False: a list of (K, s, s) arrays, one per group."""
+    R = np.asarray(R)
+    K = R.shape[0]
+    D = int(round(np.sqrt(R.size // K)))
+    R = np.triu(R.astype(np.float32).astype(np.float64).reshape(K, D, D))
+    A = np.einsum("kji,kjl->kil", R, R)
+    Ws = []
+    for g in groups:
+        G = np.asarray(g, np.int64)
+        L = np.linalg.cholesky(A[:, G[:, None], G[None, :]])
+        Ws.append(np.tril(np.linalg.inv(L)))
+    if not packed:
+        return Ws
+    return np.concatenate([W[:, np.tril_indices(W.shape[1])[0], np.tril_indices(W.shape[1])[1]] for W in Ws], axis=1)
+
+
 # ---- the quantiles of a Student-t (include/dpmm_hip_regress_cdf.h: the table z of dpmm_set_regression_levels), in the library's own
 # arithmetic: the incomplete beta function by the continued fraction csrc/typicality_math.h evaluates, a safeguarded Newton solve on it
 def _beta_cf(a, b, x):

@@ -59,6 +59,11 @@ Explanation.__doc__ = """What `Predictor.explain` returns: labels, mahalanobis, 
 feature_tail float32 -- (D, n) in feature order with features None, or with top=m (n, m) and features (n, m) int32, 0-based, the m features of
 largest |zscore|, largest first -- tensors on the data's device for a device tensor, else numpy arrays."""
 
+GroupExplanation = collections.namedtuple("GroupExplanation", "labels mahalanobis tail group_mahalanobis group_tail names sizes skipped incomplete")
+GroupExplanation.__doc__ = """What `Predictor.explain_groups` returns: labels, mahalanobis, tail, skipped, incomplete as `Typicality`;
+group_mahalanobis, group_tail (G, n) float32 in the order of `groups` -- `.T` views of point-major memory, tensors on the data's device for
+a device tensor, else numpy arrays; names, the keys of a dict of groups (None for a sequence); sizes, a tuple of the G group sizes."""
+
 HeldOut = collections.namedtuple("HeldOut", "points index total skipped incomplete")
 HeldOut.__doc__ = """What `Predictor.held_out` returns: points (D, stored) float32 -- a view of the (stored, D) buffer the GPU wrote -- and index
 (stored,) int64, 0-based positions in `data`, increasing -- tensors on the data's device for a device tensor, else numpy arrays; total, the
@@ -323,6 +328,7 @@ class Predictor:
         self._out_stage = {}             # outputs of a short slab: name -> array / tensor of `capacity` rows
         self._sampler_set = False        # the sampler's tables are formed and uploaded by the first sample()
         self._recommend_set = False      # ... and the next-count probabilities by the first recommend()
+        self._groups_set = None          # ... and the group tables by explain_groups(): the groups they were made for
 
     def _predictive_args(self):
         """("niw" | "mult", the arguments of the worker's set_predictive_*) for `self.post` and `self.weights`."""
@@ -503,6 +509,52 @@ class Predictor:
         rows = [out[name] if m else out[name].T for name in ("residual", "zscore", "feature_tail")]
         return Explanation(out["labels"], out["mahalanobis"], out["tail"], rows[0], rows[1], rows[2], out["features"] if m else None, sk, inc)
 
+    # ---- explanations by groups of features (include/dpmm_hip_explain_groups.h)
+    def explain_groups(self, data, groups):
+        """WHICH GROUP of features makes a point atypical of the cluster it is given: a `GroupExplanation` tuple, computed on the GPU.
+
+        `explain` conditions one feature on all the others.  Features often come in blocks -- the parts of a concatenated embedding, the
+        channels of a sensor, the one-hot columns of a variable, the lags of a series -- and inside a correlated block every feature is
+        explained away by its block-mates while the block as a whole can be impossible.  Under the point's own Student-t predictive the
+        law of a block G of s features given the other D - s is again a Student-t in closed form.  With the notation of `explain`
+        (A = R_k' R_k, g = A z, q = mahalanobis[i], df = df_k):
+
+          labels, mahalanobis, tail, skipped, incomplete    the values and classes of `typicality(data)`, bit for bit;
+          group_mahalanobis   q_G = g_G' A_GG^-1 g_G, the squared length of the conditional residual x_G - E[x_G | the other features, k]
+                              in the conditional metric; q - q_G is the squared distance of the other features under their marginal;
+          group_tail          P(F >= f_G / s) for f_G = q_G (df + D - s) / (df + q - q_G), F ~ F(s, df + D - s), evaluated in Float64 and
+                              rounded once: uniform on (0, 1) for points of the cluster, whatever the other features are, and comparable
+                              across groups of different sizes, clusters and D.  A group of one feature gives `explain`'s feature_tail,
+                              the group of all features gives `tail`.
+        groups: a sequence of sequences of 0-based feature indices, or a dict name -> indices (`names` then holds the keys, in order):
+        1 .. 64 groups, none empty, pairwise disjoint, not necessarily covering all features; the indices of a group are sorted on the way
+        in.  Anything else is a ValueError before the GPU is touched.  Both arrays are (G, n) float32 in the order of `groups`, `.T` views of
+        point-major memory as `explain` returns.  Skipped and incomplete points (see `typicality`) have NaN in both; on a
+        missing="marginalize" Predictor a point with gaps is incomplete here.
+        The per-cluster tables (the inverse Cholesky factors of A_GG, Float64 on the host, `condition.group_factors`) are formed by the
+        first call and again after `absorb`, `grow` or for other groups.  Float32 arithmetic from the Float32 x, m, R the worker holds;
+        include/dpmm_hip_explain_groups.h states the error bounds.  With a projection the indices are those of the PROJECTED space.
+        NIW only.  No result depends on `capacity`, the cut into uploads or the table budget, to the bit."""
+        if self._wk is None:
+            raise RuntimeError("this Predictor is closed")
+        if self.kind != _priors.PRIOR_NIW:
+            raise ValueError("explain_groups is for the NIW prior: the Multinomial predictive has no closed-form tail")
+        names, idx = _condition.check_groups(groups, self.D, binding.EXPLAIN_MAX_GROUPS)
+        wk = _need(self._wk, "this Predictor's worker cannot explain groups (no dpmm_explain_groups_points)", "set_explain_groups", "explain_groups_points_into")
+        opened = self._open(data)
+        key = tuple(tuple(g) for g in idx)
+        if self._groups_set != key:
+            R = np.asarray(self._predictive_args()[1][1], np.float32)      # what the worker was given
+            wk.set_explain_groups(idx, _condition.group_factors(R, idx))
+            self._groups_set = key
+        width = (len(idx),)
+        spec = [("labels", (), "int64"), ("mahalanobis", (), "float32"), ("tail", (), "float32"), ("group_mahalanobis", width, "float32"),
+                ("group_tail", width, "float32")]
+        # (the padding of a short slab: as `typicality`, never incomplete)
+        out, (sk, inc) = self._walk(opened, spec, lambda views, lo, hi: wk.explain_groups_points_into(views), absent=_first_nan("mahalanobis"))
+        return GroupExplanation(out["labels"], out["mahalanobis"], out["tail"], out["group_mahalanobis"].T, out["group_tail"].T, names,
+                                tuple(len(g) for g in idx), sk, inc)
+
     # ---- exemplars (include/dpmm_hip_rank.h)
     def exemplars(self, data, m, which="both"):
         """The m most and the m least typical points of every cluster, selected on the GPU: an `Exemplars` tuple.
@@ -615,6 +667,7 @@ class Predictor:
         """The predictive parameters of `self.post` and `self.weights` into the worker."""
         which, args = self._predictive_args()
         getattr(self._wk, "set_predictive_" + which)(*args)
+        self._groups_set = None              # the group tables are those of the old parameters
 
     def absorb(self, data, assign="hard", min_logdens=None, min_tail=None):
         """Folds `data` into the model and returns the `BatchStatistics` it absorbed (see `statistics` for the arguments).
@@ -1524,6 +1577,13 @@ def explain(dp_model, data, top=None, **kw):
     gaps = kw.pop("gaps", "incomplete")
     with Predictor(dp_model, **kw) as p:
         return p.explain(data, top=top, gaps=gaps)
+
+
+def explain_groups(dp_model, data, groups, **kw):
+    """`Predictor.explain_groups` in one call: which group of features makes every point of `data` atypical of its cluster, a
+    `GroupExplanation` tuple; kw: capacity, device, worker_factory, missing."""
+    with Predictor(dp_model, **kw) as p:
+        return p.explain_groups(data, groups)
 
 
 def held_out(dp_model, data, **kw):
