@@ -362,6 +362,24 @@ ABI_RECOMMEND = [
 ]
 RECOMMEND_MAX_TOP = SCORE_MAX_TOP      # DPMM_RECOMMEND_MAX_TOP
 
+
+class CountExplainOut(ctypes.Structure):
+    """dpmm_count_explain_out (include/dpmm_hip_count_explain.h): host or device addresses (the two counters always host), 0 / None = not
+    asked for; ld, the entries between two points' rows."""
+    _fields_ = [("top", ctypes.c_int), ("side", ctypes.c_int), ("ld", ctypes.c_int64), ("features", ctypes.c_void_p), ("count", ctypes.c_void_p),
+                ("expected", ctypes.c_void_p), ("residual", ctypes.c_void_p), ("feature_tail", ctypes.c_void_p), ("labels", ctypes.c_void_p),
+                ("total", ctypes.c_void_p), ("skipped", ctypes.c_void_p), ("incomplete", ctypes.c_void_p)]
+
+
+# include/dpmm_hip_count_explain.h: the features that put a count point out, with exact binomial tails (Multinomial; additive; bound next to ABI)
+ABI_COUNT_EXPLAIN = [
+    ("dpmm_set_count_explain", ctypes.c_int, [ctypes.c_void_p, _c_f64p, _c_f64p, ctypes.POINTER(ctypes.c_int32)]),
+    ("dpmm_count_explain_points", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(CountExplainOut)]),
+    ("dpmm_count_explain_points_device", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(CountExplainOut)]),
+]
+COUNT_EXPLAIN_MAX_TOP = SCORE_MAX_TOP      # DPMM_COUNT_EXPLAIN_MAX_TOP
+COUNT_EXPLAIN_SIDES = {"both": 0, "over": 1, "under": 2}      # DPMM_COUNT_EXPLAIN_BOTH / _OVER / _UNDER
+
 HOST_ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int)   # dpmm_host_allreduce_fn
 
 # dpmm_set_option keys (include/dpmm_hip.h)
@@ -442,7 +460,7 @@ def load_library():
         except Exception:  # pragma: no cover  (torch is optional for single-GPU use)
             pass
         lib = ctypes.CDLL(p)
-        for name, res, args in ABI + ABI_TENSOR + ABI_SCORE + ABI_RANK + ABI_OVERLAP + ABI_BATCHSTATS + ABI_COUNTSTATS + ABI_TYPICALITY + ABI_EXPLAIN + ABI_EXPLAIN_GROUPS + ABI_HOLDOUT + ABI_COUNTHOLDOUT + ABI_TRACE + ABI_MISSING + ABI_IMPUTE + ABI_REGRESS + ABI_REGRESS_DRAW + ABI_REGRESS_CDF + ABI_RECOMMEND + ABI_CSC + ABI_SAMPLE + ABI_PROJECT:
+        for name, res, args in ABI + ABI_TENSOR + ABI_SCORE + ABI_RANK + ABI_OVERLAP + ABI_BATCHSTATS + ABI_COUNTSTATS + ABI_TYPICALITY + ABI_EXPLAIN + ABI_EXPLAIN_GROUPS + ABI_HOLDOUT + ABI_COUNTHOLDOUT + ABI_TRACE + ABI_MISSING + ABI_IMPUTE + ABI_REGRESS + ABI_REGRESS_DRAW + ABI_REGRESS_CDF + ABI_RECOMMEND + ABI_COUNT_EXPLAIN + ABI_CSC + ABI_SAMPLE + ABI_PROJECT:
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -984,6 +1002,33 @@ class Worker:
         self._chk(fn(self._h, int(m), 1 if exclude_seen else 0, p["features"], p["prob"], int(features.shape[1]), p["labels"],
                      _p(skipped, _c_i64p)))
         return int(skipped[0])
+
+    # ---- the features that put a count point out (include/dpmm_hip_count_explain.h)
+    def set_count_explain(self, log_theta, log1m_theta, order):
+        """dpmm_set_count_explain: log theta and log1p(-theta), (K, D) Float64 each, and order (K, D) int32, every cluster's features with
+        log1p(-theta) non-decreasing, ties to the lower index -- for the predictive parameters in force."""
+        lth, l1m = np.ascontiguousarray(log_theta, np.float64), np.ascontiguousarray(log1m_theta, np.float64)
+        order = np.ascontiguousarray(order, np.int32)
+        assert lth.shape == l1m.shape == order.shape == (self.K, self.D), "set_count_explain: three (K, D) tables"
+        self._chk(self._lib.dpmm_set_count_explain(self._h, _p(lth, _c_f64p), _p(l1m, _c_f64p), _p(order, ctypes.POINTER(ctypes.c_int32))))
+
+    _COUNT_EXPLAIN_OUTS = dict(features="int32", count="float32", expected="float32", residual="float32", feature_tail="float32", labels="int64",
+                               total="float64")
+
+    def count_explain_points_into(self, views, top, side="both"):
+        """dpmm_count_explain_points[_device] into storage the caller made: `views` maps `features` (n, ld >= top) int32 and `count`,
+        `expected`, `residual`, `feature_tail` (n, ld) float32 -- one ld for the five -- and, if asked for, `labels` (n,) int64 and `total`
+        (n,) float64 to C-contiguous numpy arrays (host variant) or torch tensors on this worker's GPU (device variant).  Returns
+        (skipped, incomplete)."""
+        ld = int(views["features"].shape[1])
+        for name in ("features", "count", "expected", "residual", "feature_tail"):
+            assert len(views[name].shape) == 2 and int(views[name].shape[1]) == ld, name
+        fn, p, _ = self._marshal("dpmm_count_explain_points", [(name, views.get(name), dt, True) for name, dt in self._COUNT_EXPLAIN_OUTS.items()])
+        cnt = np.zeros(2, np.int64)
+        out = CountExplainOut(int(top), COUNT_EXPLAIN_SIDES[side], ld, p["features"], p["count"], p["expected"], p["residual"], p["feature_tail"], p["labels"],
+                              p["total"], cnt.ctypes.data, cnt.ctypes.data + 8)
+        self._chk(fn(self._h, ctypes.byref(out)))
+        return int(cnt[0]), int(cnt[1])
 
     # ---- draws of the targets (include/dpmm_hip_regress_draw.h)
     def set_regression_factor(self, W):

@@ -55,17 +55,7 @@ constexpr int CS_SP_WAVE = 1792;         // features (doubles of LDS) of a wave 
 constexpr int CS_SP_WG = 4 * CS_SP_WAVE; // ... of its workgroup: 56 KB
 constexpr int CS_SP_SCAN = 128;          // columns up to this length are scanned from their start, longer ones bisected
 
-// t_i, the Float64 total of a point's values, for the floor per count: one wave per point.  Lane l adds entries l, l + 64, .. in order, then
-// a fixed butterfly combines the lanes (every lane ends with the same sum): a function of the point alone, exact for integer data.
-template <typename T>
-__device__ __forceinline__ double cs_wave_total(const T *v, int64_t len, int lane) {
-    double t = 0.;
-    for (int64_t e = lane; e < len; e += 64) t += (double)v[e];
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) t += __shfl_xor(t, o);
-    return t;
-}
-
+// (t_i, the Float64 total of a point's values: cs_wave_total of countstats_device.h)
 __global__ __launch_bounds__(CS_THREADS) void countstats_totals_kernel(CountTotalsArgs A) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     constexpr int WAVES = CS_THREADS / 64;

@@ -47,4 +47,16 @@ __device__ __forceinline__ void cs_class(bool valid, bool nan_seen, float m, flo
     part = scored && !held && !incomplete;
 }
 
+// t_i, the Float64 total of a point's values, for the floor per count (countstats.hip) and the binomial law of a feature
+// (count_explain.hip): one wave per point.  Lane l adds entries l, l + 64, .. in order, then
+// a fixed butterfly combines the lanes (every lane ends with the same sum): a function of the point alone, exact for integer data.
+template <typename T>
+__device__ __forceinline__ double cs_wave_total(const T *v, int64_t len, int lane) {
+    double t = 0.;
+    for (int64_t e = lane; e < len; e += 64) t += (double)v[e];
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) t += __shfl_xor(t, o);
+    return t;
+}
+
 }  // namespace dpmm

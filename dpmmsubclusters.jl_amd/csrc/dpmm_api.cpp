@@ -25,6 +25,7 @@
 #include "../../include/dpmm_hip_regress_draw.h"
 #include "../../include/dpmm_hip_regress_cdf.h"
 #include "../../include/dpmm_hip_recommend.h"
+#include "../../include/dpmm_hip_count_explain.h"
 #include "../../include/dpmm_hip_sample.h"
 #include "../../include/dpmm_hip_project.h"
 
@@ -255,6 +256,14 @@ struct dpmm_ctx {
     unsigned long long rec_gen = 0;
     DevBuf<float> d_rec_theta;
     DevBuf<unsigned> d_rec_skip;
+    // surprising features (include/dpmm_hip_count_explain.h): log theta and log1p(-theta), [K][D] each, and the order, [K][D], made by
+    // dpmm_set_count_explain for the parameter set cex_gen (0: none); the per-tile counts of the skipped and the incomplete points of one range
+    unsigned long long cex_gen = 0;
+    DevBuf<double> d_cex_log;
+    DevBuf<int32_t> d_cex_order;
+    DevBuf<unsigned> d_cex_skip, d_cex_inc;
+    DevBuf<double> d_cex_tot;      // ... and their totals and 0-based labels, for the tail kernel
+    DevBuf<int32_t> d_cex_lab;
     // drawing points (include/dpmm_hip_sample.h): the sampler's tables (dpmm_set_sampler_*) and what a call needs beside its outputs
     // (cluster and tile starts; sparse: 4 bytes per point of counts and the scan's tile totals), allocated on first use
     DevBuf<float> d_sm_m, d_sm_At, d_sm_df;
@@ -5370,6 +5379,109 @@ int dpmm_recommend_points(dpmm_ctx *c, int m, int exclude_seen, int32_t *feature
 int dpmm_recommend_points_device(dpmm_ctx *c, int m, int exclude_seen, int32_t *d_features, float *d_prob, int64_t ld, int64_t *d_labels, int64_t *skipped) {
     return recommend_points(c, m, exclude_seen, d_features, d_prob, ld, d_labels, skipped, true, "dpmm_recommend_points_device");
 }
+
+// ---- include/dpmm_hip_count_explain.h: the features that put a count point out, range by range (count_explain.hip) ----------------------
+int dpmm_set_count_explain(dpmm_ctx *c, const double *log_theta, const double *log1m_theta, const int32_t *order) {
+    static const char *fn = "dpmm_set_count_explain";
+    if (!c) return tensor_no_ctx(fn);
+    const std::string who = std::string(fn) + ": ";
+    if (c->prior != DPMM_PRIOR_MULT) return fail(c, DPMM_EINVAL, who + "the binomial law of a feature is that of the Multinomial prior: an NIW ctx has dpmm_explain_points");
+    if (!log_theta || !log1m_theta || !order) return fail(c, DPMM_EINVAL, who + "null table");
+    if (!c->predictive) return fail(c, DPMM_ESTATE, who + "needs dpmm_set_predictive_mult first");
+    const size_t K = (size_t)c->K, D = (size_t)c->D;
+    // the kernel indexes the tables with what `order` holds and ends its walk on what the order promises: both are checked here
+    std::vector<char> seen(D);
+    for (size_t k = 0; k < K; ++k) {
+        std::fill(seen.begin(), seen.end(), 0);
+        for (size_t j = 0; j < D; ++j) {
+            const double a = log_theta[k * D + j], b = log1m_theta[k * D + j];
+            if (!(a <= 0.) || !(b <= 0.)) return fail(c, DPMM_EINVAL, who + "a logarithm of a probability is above 0 or NaN");
+            const int32_t d = order[k * D + j];
+            if (d < 0 || (size_t)d >= D || seen[(size_t)d]) return fail(c, DPMM_EINVAL, who + "order is no permutation of the features");
+            seen[(size_t)d] = 1;
+            if (j > 0) {
+                const int32_t p = order[k * D + j - 1];
+                const double lp = log1m_theta[k * D + (size_t)p], ld = log1m_theta[k * D + (size_t)d];
+                if (!(lp < ld || (lp == ld && p < d))) return fail(c, DPMM_EINVAL, who + "order does not follow log1m_theta (non-decreasing, ties to the lower index)");
+            }
+        }
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    c->cex_gen = 0;      // (a failure below leaves no table in force)
+    if (int rc = grow(c, c->d_cex_log, sizeof(double) * 2 * K * D, fn, "logarithms of the feature probabilities")) return rc;
+    if (int rc = grow(c, c->d_cex_order, sizeof(int32_t) * K * D, fn, "order of the feature probabilities")) return rc;
+    HIPCHK(c, sync_stream(c, c->stream));
+    HIPCHK(c, hipMemcpy(c->d_cex_log, log_theta, sizeof(double) * K * D, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->d_cex_log + K * D, log1m_theta, sizeof(double) * K * D, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->d_cex_order, order, sizeof(int32_t) * K * D, hipMemcpyHostToDevice));
+    c->cex_gen = c->pred_gen;
+    return DPMM_OK;
+}
+
+static int count_explain_points(dpmm_ctx *c, const dpmm_count_explain_out *o, bool device, const char *fn) {
+    if (!c) return tensor_no_ctx(fn);
+    c->miss_counted = false;      // (as score_points)
+    const std::string who = std::string(fn) + ": ";
+    if (c->prior != DPMM_PRIOR_MULT) return fail(c, DPMM_EINVAL, who + "the binomial law of a feature is that of the Multinomial prior: an NIW ctx has dpmm_explain_points");
+    if (!o) return fail(c, DPMM_EINVAL, who + "null out");
+    if (!c->predictive) return fail(c, DPMM_ESTATE, who + "needs dpmm_set_predictive_mult first");
+    if (c->cex_gen == 0 || c->cex_gen != c->pred_gen) return fail(c, DPMM_ESTATE, who + "needs dpmm_set_count_explain for the predictive parameters in force");
+    const int cap = std::min(c->D, DPMM_COUNT_EXPLAIN_MAX_TOP), top = o->top;
+    const int64_t ld = o->ld;
+    if (top < 1 || top > cap) return fail(c, DPMM_EINVAL, who + "top must be in 1.." + std::to_string(cap));
+    if (o->side < DPMM_COUNT_EXPLAIN_BOTH || o->side > DPMM_COUNT_EXPLAIN_UNDER) return fail(c, DPMM_EINVAL, who + "side must be DPMM_COUNT_EXPLAIN_BOTH, _OVER or _UNDER");
+    if (ld < top) return fail(c, DPMM_EINVAL, who + "ld < top");
+    if (ld >> 40) return fail(c, DPMM_EINVAL, who + "ld out of range");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (o->skipped) o->skipped[0] = 0;
+    if (o->incomplete) o->incomplete[0] = 0;
+    if (c->n == 0) return DPMM_OK;
+    const int store = count_store(c);
+    if (!count_store_ready(c, store)) return fail(c, DPMM_ESTATE, who + "needs points and parameters");
+    struct { const char *name; void *p; size_t word; } rows[5] = {{"features", o->features, sizeof(int32_t)}, {"count", o->count, sizeof(float)}, {"expected", o->expected, sizeof(float)},
+                                                                   {"residual", o->residual, sizeof(float)}, {"feature_tail", o->feature_tail, sizeof(float)}};
+    for (const auto &r : rows)
+        if (!r.p) return fail(c, DPMM_EINVAL, who + r.name + " is null");
+    const uint64_t n = (uint64_t)c->n;
+    if (device) {
+        for (const auto &r : rows)
+            if (int rc = check_device_extent(c, fn, (std::string("d_") + r.name).c_str(), r.p, n * (uint64_t)ld * r.word, r.word)) return rc;
+        if (o->labels) if (int rc = check_device_extent(c, fn, "d_labels", o->labels, n * sizeof(int64_t), sizeof(int64_t))) return rc;
+        if (o->total) if (int rc = check_device_extent(c, fn, "d_total", o->total, n * sizeof(double), sizeof(double))) return rc;
+    }
+    TableWalk w;
+    if (int rc = walk_open(c, fn, WALK_MISS_NEVER, &w)) return rc;
+    if (int rc = skip_open(c, c->d_cex_skip, w.P, fn, "counts of the skipped points")) return rc;
+    if (int rc = skip_open(c, c->d_cex_inc, w.P, fn, "counts of the incomplete points")) return rc;
+    if (int rc = grow(c, c->d_cex_tot, sizeof(double) * (size_t)w.P, fn, "totals of the points")) return rc;
+    if (int rc = grow(c, c->d_cex_lab, sizeof(int32_t) * (size_t)w.P, fn, "labels of the points")) return rc;
+    // the rows: in the caller's device memory ld words apart; staged (host variant) dense, top apart
+    const size_t rb = sizeof(float) * (size_t)top, pb = sizeof(float) * (size_t)ld;      // (the five arrays have 4-byte words)
+    OutStage<7> out{{{o->features, rb, pb}, {o->count, rb, pb}, {o->expected, rb, pb}, {o->residual, rb, pb}, {o->feature_tail, rb, pb}, {o->labels, sizeof(int64_t)},
+                     {o->total, sizeof(double)}}, device};
+    if (!device) {
+        if (int rc = grow(c, c->d_score_out, out.layout((size_t)w.P), fn, "staging of the outputs")) return rc;
+        out.buf = c->d_score_out;
+    }
+    const size_t KD = (size_t)c->K * (size_t)c->D;
+    if (int rc = walk_ranges(c, w, c->n, fn, [&](int64_t p0, int64_t np, int64_t) {
+            CountExplainArgs a{};
+            a.table = c->d_score_table; a.stride = w.P; a.rstep = w.rstep; a.n = np; a.K = c->K; a.D = c->D;
+            count_points(c, store, p0, a);
+            a.lth = c->d_cex_log; a.l1m = c->d_cex_log + KD; a.order = c->d_cex_order; a.top = top; a.side = o->side;
+            a.features = out.at<int32_t>(0, p0); a.count = out.at<float>(1, p0); a.expected = out.at<float>(2, p0); a.residual = out.at<float>(3, p0);
+            a.feature_tail = out.at<float>(4, p0); a.ld = device ? ld : top; a.labels = out.at<int64_t>(5, p0); a.total = out.at<double>(6, p0);
+            a.skip = c->d_cex_skip; a.incomplete = c->d_cex_inc; a.tot = c->d_cex_tot; a.lab = c->d_cex_lab;
+            hipError_t e = launch_count_explain_range(a, c->stream);
+            if (e == hipSuccess && !device) e = out.flush(c, p0, (size_t)np);
+            return e;
+        })) return rc;
+    if (int rc = skip_close(c, c->d_cex_skip, w.P, o->skipped)) return rc;
+    return skip_close(c, c->d_cex_inc, w.P, o->incomplete);
+}
+
+int dpmm_count_explain_points(dpmm_ctx *c, const dpmm_count_explain_out *out) { return count_explain_points(c, out, false, "dpmm_count_explain_points"); }
+int dpmm_count_explain_points_device(dpmm_ctx *c, const dpmm_count_explain_out *out) { return count_explain_points(c, out, true, "dpmm_count_explain_points_device"); }
 
 // ---- include/dpmm_hip_countholdout.h: the held-out points of a batch of count data, compacted into the caller's device memory (holdout.hip)
 // kind of a destination: 0 count only, 1 rows of Float32 (dense stores), 2 compressed sparse columns

@@ -516,6 +516,43 @@ struct RecommendArgs {
     unsigned *skip;      // [ceil(n / 32)] points of tile j that take no part, ADDED to word j
 };
 hipError_t launch_recommend_range(const RecommendArgs &a, hipStream_t s);
+// ---- top-m surprising features of a count point (count_explain.hip; include/dpmm_hip_count_explain.h): one range of the score table, n
+// points from table column 0 and from whichever count store is live
+constexpr int COUNT_EXPLAIN_MAX_TOP = 16; // DPMM_COUNT_EXPLAIN_MAX_TOP
+constexpr int COUNT_EXPLAIN_TILE = 32;    // points of a wave: one counter word each in `skip` and `incomplete`
+enum { COUNT_EXPLAIN_BOTH = 0, COUNT_EXPLAIN_OVER = 1, COUNT_EXPLAIN_UNDER = 2 };      // DPMM_COUNT_EXPLAIN_*
+struct CountExplainArgs {
+    const float *table;
+    int64_t stride;      // floats between two rows of the table
+    int rstep;           // cluster k is row k * rstep
+    int64_t n;
+    int K, D;
+    int store;           // as CountStatsArgs, the pointers at the range's first point (X, X8, cp) / the whole entry arrays (ri, val)
+    const float *X;
+    int64_t ldx;
+    const uint8_t *X8;
+    int64_t ld8;
+    const int64_t *cp;
+    const uint16_t *ri;
+    const float *val;
+    const double *lth;   // [K][D] log theta
+    const double *l1m;   // [K][D] log1p(-theta)
+    const int32_t *order;// [K][D] the features of cluster k with l1m non-decreasing (theta non-increasing), ties to the lower index
+    int top, side;       // 1 <= top <= min(D, COUNT_EXPLAIN_MAX_TOP); side: COUNT_EXPLAIN_*
+    int32_t *features;   // [n][ld] rows of the range's points, 0-based, -1 behind the candidates
+    float *count;        // [n][ld] each, NaN behind the candidates
+    float *expected;
+    float *residual;
+    float *feature_tail;
+    int64_t ld;
+    int64_t *labels;     // [n] or null
+    double *total;       // [n] or null: t_i, NaN for a skipped point
+    double *tot;         // [n] the ctx's own copy of total, and the 0-based labels: what the tail kernel reads
+    int32_t *lab;
+    unsigned *skip;      // [ceil(n / COUNT_EXPLAIN_TILE)] skipped points of tile j, ADDED to word j
+    unsigned *incomplete;// ... and incomplete ones
+};
+hipError_t launch_count_explain_range(const CountExplainArgs &a, hipStream_t s);
 // ---- draws of the targets (regress_draw.hip; include/dpmm_hip_regress_draw.h): one range of the score table, n points from table column 0
 // and from X, the draws draw0 .. draw0 + ndraws - 1 of each
 constexpr int64_t REGRESS_DRAW_MAX = 67108864;      // DPMM_REGRESS_MAX_DRAWS

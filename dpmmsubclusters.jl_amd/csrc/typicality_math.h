@@ -75,4 +75,15 @@ TYP_HD double typ_tail(double q, double df, int D, int *trips) {
     return t < 0.0 ? 0.0 : t;
 }
 
+// The general I_x(a, b) for a, b > 0 and 0 < x < 1 (count_explain.hip: the binomial tails of include/dpmm_hip_count_explain.h).  The caller
+// hands over x AND xc = 1 - x, each formed without cancellation, and their logarithms lx, lxc -- it has them from its tables; a caller
+// without passes log(x), log(xc).  The same two sides as typ_tail: the fraction that converges fast is the one that is evaluated.
+TYP_HD double typ_inc_beta(double a, double b, double x, double xc, double lx, double lxc, int *trips) {
+    if (trips) *trips = 0;
+    const double lpre = a * lx + b * lxc - typ_log_beta(a, b);
+    if (x < (a + 1.0) / (a + b + 2.0)) return exp(lpre) * typ_beta_cf(a, b, x, trips) / a;
+    const double t = 1.0 - exp(lpre) * typ_beta_cf(b, a, xc, trips) / b;
+    return t < 0.0 ? 0.0 : t;
+}
+
 }  // namespace dpmm

@@ -107,6 +107,14 @@ largest first, ties to the lower index, -1 where a point has fewer than m candid
 there; labels (n,) int64 1-based, what `predict_labels` gives -- tensors on the data's device for a device tensor, else numpy arrays --
 and skipped, an int: the points that are -1 / NaN throughout."""
 
+CountExplanation = collections.namedtuple("CountExplanation", "features count expected residual feature_tail labels total skipped incomplete")
+CountExplanation.__doc__ = """What `Predictor.explain_counts` returns: features (n, top) int32, 0-based, the candidates of largest |residual|, largest
+first, ties to the lower index, -1 where a point has fewer than `top` candidates; count, expected, residual, feature_tail (n, top) float32:
+the point's count of the feature, t theta, the signed binomial deviance residual and the exact one-sided binomial tail on the side of the
+deviation, NaN there; labels (n,) int64 1-based, what `predict_labels` gives; total (n,) float64, the points' totals t, NaN for a skipped
+point -- tensors on the data's device for a device tensor, else numpy arrays -- and skipped, incomplete, ints: the points that are -1 / NaN
+throughout."""
+
 ASSIGN_MODES = {"hard": binding.BATCHSTATS_HARD, "soft": binding.BATCHSTATS_SOFT}
 
 
@@ -328,6 +336,7 @@ class Predictor:
         self._out_stage = {}             # outputs of a short slab: name -> array / tensor of `capacity` rows
         self._sampler_set = False        # the sampler's tables are formed and uploaded by the first sample()
         self._recommend_set = False      # ... and the next-count probabilities by the first recommend()
+        self._count_explain_set = False  # ... and the logarithms and the order of theta by the first explain_counts()
         self._groups_set = None          # ... and the group tables by explain_groups(): the groups they were made for
 
     def _predictive_args(self):
@@ -661,6 +670,7 @@ class Predictor:
         self._reload()
         self._sampler_set = False            # the sampler's tables are those of the old posterior
         self._recommend_set = False          # ... and so are the next-count probabilities
+        self._count_explain_set = False      # ... and the tables of explain_counts
         return stats
 
     def _reload(self):
@@ -812,6 +822,7 @@ class Predictor:
             raise
         self._sampler_set = False                          # the sampler's tables are those of the old K
         self._recommend_set = False                        # ... and so are the next-count probabilities
+        self._count_explain_set = False                    # ... and the tables of explain_counts
         new_id = np.zeros(s.K, np.int64)
         new_id[keep] = K0 + 1 + np.arange(len(keep))
         kept = new_id[lab - 1] > 0
@@ -1191,6 +1202,70 @@ class Predictor:
                                   lambda views, lo, hi: wk.recommend_points_into(views, m, exclude_seen), absent=_first_negative("features"))
         return Recommendation(out["features"], out["prob"], out["labels"], sk)
 
+    # ---- the features that put a count point out (include/dpmm_hip_count_explain.h)
+    def count_explain_tables(self):
+        """(log theta, log1p(-theta), order): the (K, D) tables `explain_counts` hands to the worker.  theta = alpha' / sum(alpha') in Float64
+        (the `theta` of `sampler_tables`); order (K, D) int32: every cluster's features with log1p(-theta) non-decreasing -- theta
+        non-increasing -- equal values in increasing index order.  Sorting by the logarithm the kernel reads, not by theta, makes the
+        promise the sparse walk ends on hold whatever log1p rounds to."""
+        a = np.asarray(self.post["alpha"], np.float64)
+        theta = a / a.sum(1, keepdims=True)
+        with np.errstate(divide="ignore"):
+            lth, l1m = np.log(theta), np.log1p(-theta)
+        return lth, l1m, np.argsort(l1m, axis=1, kind="stable").astype(np.int32)
+
+    def explain_counts(self, data, top, side="both"):
+        """WHICH features put a count point out of the cluster it is given: a `CountExplanation` tuple, computed on the GPU.
+
+        `score_samples`, `count_statistics(min_logdens_per_count=...)` and `held_out_counts` say THAT a document, basket or play-list is
+        unusual.  Under the plug-in predictive `predict` scores and `sample` draws from, Multinomial(t, theta_k) with k the point's label,
+        t its total and theta_k = alpha'_k / sum(alpha'_k), the count x of feature d is Binomial(t, theta_kd).  Per point the `top`
+        features, 1 <= top <= min(D, 16), of largest |residual|:
+
+          residual      sign(x - t theta) sqrt(g), g = 2 [x log(x / (t theta)) + (t - x) log((t - x) / (t (1 - theta)))] the binomial deviance,
+                        Float64, rounded to Float32 once.  The deviance, not a Pearson z-score, ranks: exp(-g / 2) is the Chernoff bound of
+                        the tail, while a z-score puts every rare feature that occurs once above a common one at four times its expectation;
+          count, expected    x and t theta;
+          feature_tail  the exact one-sided binomial tail on the side of the deviation, P(X >= x) over, P(X <= x) under, 1 at x = t theta
+                        (agreement to 2^-40): a regularised incomplete beta function in Float64, rounded once.  For values that are no
+                        integers the continuous extension, no probability statement;
+          features      0-based, largest |residual| as returned first, ties to the lower index; -1 / NaN behind the candidates.
+        side: "both" ranks all D features, "over" those with x > t theta, "under" those with x < t theta.  A point with a NaN or no finite
+        entry in its row of the table is `skipped` (total NaN); one with a value that is not finite or negative, or with t = 0, is
+        `incomplete`; both are -1 / NaN throughout.  `data` is whatever `predict` takes for a Multinomial model and is read from the store
+        the worker keeps it in -- Float32, bytes, sparse columns up to D = 65536 (work proportional to the point's entries) -- nothing is
+        densified and nothing of size n D or n K exists.  include/dpmm_hip_count_explain.h states the error bounds; the bits do not depend
+        on `capacity`.  After `absorb_counts` and `grow_counts` the answer is that of the updated model."""
+        if self._wk is None:
+            raise RuntimeError("this Predictor is closed")
+        if self.kind != _priors.PRIOR_MULT:
+            raise ValueError("explain_counts is for the Multinomial prior: an NIW model has explain")
+        if self.projection is not None:
+            raise ValueError("explain_counts is refused for a model with a projection: its features are mixtures of the source features")
+        m = int(top)
+        cap = min(self.D, binding.COUNT_EXPLAIN_MAX_TOP)
+        if m != top or not 1 <= m <= cap:
+            raise ValueError(f"top must be an integer in 1..{cap}")
+        if side not in binding.COUNT_EXPLAIN_SIDES:
+            raise ValueError('side must be "both", "over" or "under"')
+        wk = _need(self._wk, "this Predictor's worker cannot explain count points (no dpmm_count_explain_points)", "count_explain_points_into")
+        opened = self._open(data)
+        if not self._count_explain_set:
+            wk.set_count_explain(*self.count_explain_tables())
+            self._count_explain_set = True
+        cap_n = self.capacity
+
+        def evaluate(views, lo, hi):
+            sk, inc = wk.count_explain_points_into(views, m, side)
+            if hi - lo < cap_n:      # the padding of a short slab is empty points: incomplete (t = 0) unless their row is skipped (total NaN)
+                tot = views["total"][hi - lo:]
+                inc -= int((tot == tot).sum())
+            return sk, inc
+        spec = [("features", (m,), "int32")] + [(name, (m,), "float32") for name in ("count", "expected", "residual", "feature_tail")] + \
+               [("labels", (), "int64"), ("total", (), "float64")]
+        out, (sk, inc) = self._walk(opened, spec, evaluate, absent=_first_nan("total"))
+        return CountExplanation(out["features"], out["count"], out["expected"], out["residual"], out["feature_tail"], out["labels"], out["total"], sk, inc)
+
     # ---- slabs
     def _spec(self, labels, logdens, m, probs):
         spec = []
@@ -1541,6 +1616,13 @@ def recommend(dp_model, data, m, exclude_seen=True, **kw):
     model (keywords: those of Predictor)."""
     with Predictor(dp_model, **kw) as p:
         return p.recommend(data, m, exclude_seen=exclude_seen)
+
+
+def explain_counts(dp_model, data, top, side="both", **kw):
+    """`Predictor.explain_counts` in one call: the `top` features that put every count point of `data` out of its cluster under the fitted
+    Multinomial model (keywords: those of Predictor)."""
+    with Predictor(dp_model, **kw) as p:
+        return p.explain_counts(data, top, side=side)
 
 
 def score_samples(dp_model, data, **kw):
