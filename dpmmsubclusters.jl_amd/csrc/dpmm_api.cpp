@@ -3885,15 +3885,19 @@ static int walk_ranges(dpmm_ctx *c, const TableWalk &w, int64_t limit, const cha
 
 // ---- the caller's arrays of a table call -- its outputs and, where a kernel reads one, a per-point input (`in`): used in place in the caller's
 // device memory, or staged on the device and copied back to (inputs: in from) the caller's host memory.
-// A column is the caller's pointer (null: not asked for) and its bytes per element; in the staging buffer the columns follow each other in
-// list order, each block 8-byte aligned.  A pitched column has rows: an element is `rows` rows of `bytes` bytes, `pitch` bytes apart at the
-// caller's and dense in the staging buffer, and the words of the caller's rows behind `bytes` are written as zeros.
+// A column is the caller's pointer (null: not asked for), the argument's name in the messages, the size of its words and its bytes per
+// element; in the staging buffer the columns follow each other in list order, each block 8-byte aligned.  A pitched column has rows: an
+// element is `rows` rows of `bytes` bytes, `pitch` bytes apart at the caller's and dense in the staging buffer, and the words of the caller's
+// rows behind `bytes` are written as zeros -- or, with `keep`, left as they are (host variant; the device variant's are the kernel's affair).
 struct OutCol {
     void *dst;
+    const char *name;
+    size_t word;         // the alignment asked of dst
     size_t bytes;        // per element, or per row of a pitched column
     size_t pitch = 0;    // bytes between two rows at the caller's; 0: not pitched
     size_t rows = 1;     // rows per element of a pitched column (L for the quantiles)
     bool in = false;     // an input of the kernel: dst is read, by load()
+    bool keep = false;   // flush writes nothing behind the rows
     size_t off = 0;
     size_t staged() const { return rows * bytes; }                      // bytes of an element in the staging buffer
     size_t step() const { return rows * (pitch ? pitch : bytes); }      // and at the caller's
@@ -3909,6 +3913,20 @@ struct OutStage {
         size_t total = 0;
         for (OutCol &q : col) { q.off = total; if (q.dst || every) total += (count * q.staged() + 7) & ~(size_t)7; }
         return total;
+    }
+    // device variant: `count` elements from every pointer given are device memory of the ctx's device, refused in list order
+    int check(dpmm_ctx *c, const char *fn, uint64_t count) const {
+        if (device)
+            for (const OutCol &q : col)
+                if (q.dst) if (int rc = check_device_extent(c, fn, q.name, q.dst, count * q.step(), q.word)) return rc;
+        return DPMM_OK;
+    }
+    // host variant: the ctx's staging block grown to ranges of P points
+    int open(dpmm_ctx *c, int64_t P) {
+        if (device) return DPMM_OK;
+        if (int rc = grow(c, c->d_score_out, layout((size_t)P), "dpmm_score_points", "staging of the outputs")) return rc;
+        buf = c->d_score_out;
+        return DPMM_OK;
     }
     // where the kernel writes (reads) column i for the elements from e0 on (null: not at all)
     template <class T>
@@ -3927,7 +3945,7 @@ struct OutStage {
         return e;
     }
     // host variant, behind the launch: `count` elements of every column asked for to the caller's element e0, in list order; then the wait,
-    // since the blocks are rewritten by the next range; then the zeros behind the rows of the pitched columns
+    // since the blocks are rewritten by the next range; then the zeros behind the rows of the pitched columns that do not keep theirs
     hipError_t flush(dpmm_ctx *c, int64_t e0, size_t count) const {
         hipError_t e = hipSuccess;
         for (const OutCol &q : col) {
@@ -3938,7 +3956,7 @@ struct OutStage {
         }
         if (e == hipSuccess) e = sync_stream(c, c->stream);
         for (const OutCol &q : col)
-            if (e == hipSuccess && q.dst && !q.in && q.pitch > q.bytes)
+            if (e == hipSuccess && q.dst && !q.in && !q.keep && q.pitch > q.bytes)
                 for (size_t r = (size_t)e0 * q.rows; r < ((size_t)e0 + count) * q.rows; ++r) memset(static_cast<char *>(q.dst) + r * q.pitch + q.bytes, 0, q.pitch - q.bytes);
         return e;
     }
@@ -4091,22 +4109,13 @@ static int score_points(dpmm_ctx *c, const dpmm_score_out *o, bool device, const
     HIPCHK(c, hipSetDevice(c->device));
     if (c->n == 0) return DPMM_OK;
     if (!c->have_points || !c->have_params) return fail(c, DPMM_ESTATE, who + "needs points and parameters");
-    const uint64_t n = (uint64_t)c->n, K = (uint64_t)c->K, m = (uint64_t)o->m;
-    if (device) {
-        if (o->labels) if (int rc = check_device_extent(c, fn, "labels", o->labels, sizeof(int64_t) * n, sizeof(int64_t))) return rc;
-        if (o->logdens) if (int rc = check_device_extent(c, fn, "logdens", o->logdens, sizeof(float) * n, sizeof(float))) return rc;
-        if (o->top_idx) if (int rc = check_device_extent(c, fn, "top_idx", o->top_idx, sizeof(int64_t) * n * m, sizeof(int64_t))) return rc;
-        if (o->top_prob) if (int rc = check_device_extent(c, fn, "top_prob", o->top_prob, sizeof(float) * n * m, sizeof(float))) return rc;
-        if (o->probs) if (int rc = check_device_extent(c, fn, "probs", o->probs, sizeof(float) * n * K, sizeof(float))) return rc;
-    }
+    const size_t K = (size_t)c->K, m = (size_t)o->m;
+    OutStage<5> out{{{o->labels, "labels", 8, sizeof(int64_t)}, {o->logdens, "logdens", 4, sizeof(float)}, {o->top_idx, "top_idx", 8, sizeof(int64_t) * m},
+                     {o->top_prob, "top_prob", 4, sizeof(float) * m}, {o->probs, "probs", 4, sizeof(float) * K}}, device};
+    if (int rc = out.check(c, fn, (uint64_t)c->n)) return rc;
     TableWalk w;
     if (int rc = walk_open(c, fn, WALK_MISS_OPTION, &w)) return rc;
-    OutStage<5> out{{{o->labels, sizeof(int64_t)}, {o->logdens, sizeof(float)}, {o->top_idx, sizeof(int64_t) * m}, {o->top_prob, sizeof(float) * m},
-                     {o->probs, sizeof(float) * K}}, device};
-    if (!device) {
-        if (int rc = grow(c, c->d_score_out, out.layout((size_t)w.P), "dpmm_score_points", "staging of the outputs")) return rc;
-        out.buf = c->d_score_out;
-    }
+    if (int rc = out.open(c, w.P)) return rc;
     if (int rc = walk_ranges(c, w, c->n, fn, [&](int64_t p0, int64_t np, int64_t) {
             ScoreArgs a{};
             a.table = c->d_score_table; a.stride = w.P; a.rstep = w.rstep; a.n = np; a.K = c->K; a.m = o->m;
@@ -4155,53 +4164,8 @@ static int typ_range(dpmm_ctx *c, int64_t P, int64_t p0, int64_t np, int64_t *la
     return table_result(c, fn, launch_typicality_range(a, 32 * c->cus, c->stream));
 }
 
-static int typicality_points(dpmm_ctx *c, const dpmm_typicality_out *o, bool device, const char *fn) {
-    if (!c) return tensor_no_ctx(fn);
-    c->miss_counted = false;      // (as score_points)
-    const std::string who = std::string(fn) + ": ";
-    if (!o) return fail(c, DPMM_EINVAL, who + "out is null");
-    if (c->prior != DPMM_PRIOR_NIW) return fail(c, DPMM_EINVAL, who + "the tail is that of the NIW prior's Student-t predictive; the Multinomial predictive has no closed-form tail");
-    if (!o->labels && !o->mahalanobis && !o->tail && !o->skipped && !o->incomplete) return fail(c, DPMM_EINVAL, who + "every output pointer is null");
-    if (!c->predictive) return fail(c, DPMM_ESTATE, who + "needs dpmm_set_predictive_niw first");
-    HIPCHK(c, hipSetDevice(c->device));
-    if (o->skipped) o->skipped[0] = 0;
-    if (o->incomplete) o->incomplete[0] = 0;
-    if (c->n == 0) return DPMM_OK;
-    if (!c->have_points || !c->have_params || !c->dX) return fail(c, DPMM_ESTATE, who + "needs points and parameters");
-    const uint64_t n = (uint64_t)c->n;
-    if (device) {
-        if (o->labels) if (int rc = check_device_extent(c, fn, "labels", o->labels, sizeof(int64_t) * n, sizeof(int64_t))) return rc;
-        if (o->mahalanobis) if (int rc = check_device_extent(c, fn, "mahalanobis", o->mahalanobis, sizeof(float) * n, sizeof(float))) return rc;
-        if (o->tail) if (int rc = check_device_extent(c, fn, "tail", o->tail, sizeof(float) * n, sizeof(float))) return rc;
-    }
-    TableWalk w;
-    if (int rc = walk_open(c, fn, WALK_MISS_OPTION, &w)) return rc;
-    if (int rc = typ_begin(c, w.P, fn)) return rc;
-    HIPCHK(c, hipMemsetAsync(c->d_typ_cnt, 0, 3 * sizeof(unsigned long long), c->stream));
-    const bool gaps = w.miss && c->opt_typ_gaps != 0;      // (without a list nothing new runs)
-    OutStage<3> out{{{o->labels, sizeof(int64_t)}, {o->mahalanobis, sizeof(float)}, {o->tail, sizeof(float)}}, device};
-    if (!device) {
-        if (int rc = grow(c, c->d_score_out, out.layout((size_t)w.P), "dpmm_score_points", "staging of the outputs")) return rc;
-        out.buf = c->d_score_out;
-    }
-    if (int rc = walk_ranges(c, w, c->n, fn, [&](int64_t p0, int64_t np, int64_t) -> int {
-            if (int rc = typ_range(c, w.P, p0, np, out.at<int64_t>(0, p0), out.at<float>(1, p0), out.at<float>(2, p0), fn, gaps)) return rc;
-            return device ? DPMM_OK : table_result(c, fn, out.flush(c, p0, (size_t)np));
-        })) return rc;
-    HIPCHK(c, sync_stream(c, c->stream));
-    unsigned long long h[3] = {0, 0, 0};
-    HIPCHK(c, hipMemcpy(h, c->d_typ_cnt, sizeof(h), hipMemcpyDeviceToHost));
-    if (o->skipped) o->skipped[0] = (int64_t)h[0];
-    if (o->incomplete) o->incomplete[0] = (int64_t)(h[1] - h[2]);      // (h[2]: scored with gaps, 0 without the option)
-    return DPMM_OK;
-}
-
-int dpmm_typicality_points(dpmm_ctx *c, const dpmm_typicality_out *out) { return typicality_points(c, out, false, "dpmm_typicality_points"); }
-int dpmm_typicality_points_device(dpmm_ctx *c, const dpmm_typicality_out *out) { return typicality_points(c, out, true, "dpmm_typicality_points_device"); }
-
-// ---- include/dpmm_hip_explain.h: behind the typicality pass of every range, the per-feature residuals, z-scores and tails (explain.hip) ----
-// The device copies explain.hip reads beside miss_params' -- the row-major factors Rr and the diagonals a of R'R -- are those of the
-// predictive set in force afterwards.  Called behind miss_params (typ_begin), which has checked the prior and the parameters.
+// The device copies explain.hip and explain_group.hip read beside miss_params' -- the row-major factors Rr and the diagonals a of R'R -- are
+// those of the predictive set in force afterwards.  Called behind miss_params (typ_begin), which has checked the prior and the parameters.
 static int explain_params(dpmm_ctx *c) {
     if (c->exp_gen == c->pred_gen) return DPMM_OK;
     const size_t K = (size_t)c->K, D = (size_t)c->D, Dp = (size_t)miss_pitch(c->D);
@@ -4214,85 +4178,124 @@ static int explain_params(dpmm_ctx *c) {
     return DPMM_OK;
 }
 
-static int explain_points(dpmm_ctx *c, const dpmm_explain_out *o, bool device, const char *fn) {
+// ---- what typicality_points, explain_points and explain_groups_points share around their walk
+extern "C++" {
+// What the three refuse first, in this order: no ctx, no out, the prior (`what`: the name in the message of what the call computes), own(0),
+// every output pointer null (rows: a row output of the call's own is given), own(1), no predictive set, own(2); then skipped and incomplete
+// zeroed and, with points, the state.  own(at) -> int: the call's own refusals at that place.  The caller returns behind it where n_local = 0.
+template <class Out, class Own>
+static int typ_front(dpmm_ctx *c, const char *fn, const Out *o, const char *what, bool rows, Own own) {
     if (!c) return tensor_no_ctx(fn);
     c->miss_counted = false;      // (as score_points)
     const std::string who = std::string(fn) + ": ";
     if (!o) return fail(c, DPMM_EINVAL, who + "out is null");
-    if (c->prior != DPMM_PRIOR_NIW) return fail(c, DPMM_EINVAL, who + "the explanation is that of the NIW prior's Student-t predictive; the Multinomial predictive has no closed-form tail");
-    const int cap = std::min(c->D, DPMM_EXPLAIN_MAX_TOP);
-    if (o->top < 0 || o->top > cap) return fail(c, DPMM_EINVAL, who + "top must be in 0.." + std::to_string(cap));
-    if (o->top == 0 && o->features) return fail(c, DPMM_EINVAL, who + "features given with top = 0");
-    const bool rows = o->residual || o->zscore || o->feature_tail || o->features;
+    if (c->prior != DPMM_PRIOR_NIW)
+        return fail(c, DPMM_EINVAL, who + "the " + what + " is that of the NIW prior's Student-t predictive; the Multinomial predictive has no closed-form tail");
+    if (int rc = own(0)) return rc;
     if (!o->labels && !o->mahalanobis && !o->tail && !o->skipped && !o->incomplete && !rows) return fail(c, DPMM_EINVAL, who + "every output pointer is null");
-    const int64_t width = o->top ? o->top : c->D;
-    if (rows && o->ld < width) return fail(c, DPMM_EINVAL, who + "ld < " + (o->top ? "top" : "D"));
-    if (rows && (o->ld >> 31)) return fail(c, DPMM_EINVAL, who + "ld out of range (below 2^31)");
+    if (int rc = own(1)) return rc;
     if (!c->predictive) return fail(c, DPMM_ESTATE, who + "needs dpmm_set_predictive_niw first");
+    if (int rc = own(2)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     if (o->skipped) o->skipped[0] = 0;
     if (o->incomplete) o->incomplete[0] = 0;
-    if (c->n == 0) return DPMM_OK;
-    if (!c->have_points || !c->have_params || !c->dX) return fail(c, DPMM_ESTATE, who + "needs points and parameters");
-    const uint64_t n = (uint64_t)c->n, ld = rows ? (uint64_t)o->ld : 0;
-    if (ld && n > (UINT64_MAX / sizeof(int64_t)) / ld) return fail(c, DPMM_EINVAL, who + "n_local * ld out of range");      // (the extents below cannot wrap)
-    if (device) {
-        if (o->labels) if (int rc = check_device_extent(c, fn, "labels", o->labels, sizeof(int64_t) * n, sizeof(int64_t))) return rc;
-        if (o->mahalanobis) if (int rc = check_device_extent(c, fn, "mahalanobis", o->mahalanobis, sizeof(float) * n, sizeof(float))) return rc;
-        if (o->tail) if (int rc = check_device_extent(c, fn, "tail", o->tail, sizeof(float) * n, sizeof(float))) return rc;
-        if (o->residual) if (int rc = check_device_extent(c, fn, "residual", o->residual, sizeof(float) * n * ld, sizeof(float))) return rc;
-        if (o->zscore) if (int rc = check_device_extent(c, fn, "zscore", o->zscore, sizeof(float) * n * ld, sizeof(float))) return rc;
-        if (o->feature_tail) if (int rc = check_device_extent(c, fn, "feature_tail", o->feature_tail, sizeof(float) * n * ld, sizeof(float))) return rc;
-        if (o->features) if (int rc = check_device_extent(c, fn, "features", o->features, sizeof(int32_t) * n * ld, sizeof(int32_t))) return rc;
-    }
-    TableWalk w;
-    if (int rc = walk_open(c, fn, WALK_MISS_OPTION, &w)) return rc;
-    if (int rc = typ_begin(c, w.P, fn)) return rc;
+    if (c->n > 0 && (!c->have_points || !c->have_params || !c->dX)) return fail(c, DPMM_ESTATE, who + "needs points and parameters");
+    return DPMM_OK;
+}
+// the range typ_range has just classified as the kernels of the row outputs take it (ExplainArgs, ExplainGroupArgs): the copies and the means
+// the typicality pass has read, the row-major factors, the class words
+template <class Args>
+static Args explain_range_args(dpmm_ctx *c, int64_t P, int64_t p0, int64_t np) {
+    const TypicalityArgs t = niw_range_args<TypicalityArgs>(c, P, p0, np);
+    Args a{};
+    a.n = t.n; a.K = t.K; a.D = t.D; a.X = t.X; a.ldx = t.ldx; a.Rt = t.Rt; a.mu = t.mu; a.mu_step = t.mu_step; a.cst = t.cst;
+    a.Rr = c->d_exp_rr; a.cls = c->d_typ_cls;
+    return a;
+}
+}  // extern "C++"
+// behind the extents: the walk opened, the scratch of the pass, with row outputs the copies explain.hip reads, the three counters cleared
+static int typ_open(dpmm_ctx *c, const char *fn, TableWalk *w, bool rows) {
+    if (int rc = walk_open(c, fn, WALK_MISS_OPTION, w)) return rc;
+    if (int rc = typ_begin(c, w->P, fn)) return rc;
     if (rows) if (int rc = explain_params(c)) return rc;
     HIPCHK(c, hipMemsetAsync(c->d_typ_cnt, 0, 3 * sizeof(unsigned long long), c->stream));
+    return DPMM_OK;
+}
+// behind the last range: the wait for the ctx stream, then the counters into skipped[0] and incomplete[0] (null: not asked for)
+static int typ_counters(dpmm_ctx *c, int64_t *skipped, int64_t *incomplete) {
+    HIPCHK(c, sync_stream(c, c->stream));
+    unsigned long long h[3] = {0, 0, 0};
+    HIPCHK(c, hipMemcpy(h, c->d_typ_cnt, sizeof(h), hipMemcpyDeviceToHost));
+    if (skipped) skipped[0] = (int64_t)h[0];
+    if (incomplete) incomplete[0] = (int64_t)(h[1] - h[2]);      // (h[2]: scored with gaps, 0 where no call passes the list)
+    return DPMM_OK;
+}
+
+static int typicality_points(dpmm_ctx *c, const dpmm_typicality_out *o, bool device, const char *fn) {
+    if (int rc = typ_front(c, fn, o, "tail", false, [](int) { return DPMM_OK; })) return rc;
+    if (c->n == 0) return DPMM_OK;
+    OutStage<3> out{{{o->labels, "labels", 8, sizeof(int64_t)}, {o->mahalanobis, "mahalanobis", 4, sizeof(float)}, {o->tail, "tail", 4, sizeof(float)}}, device};
+    if (int rc = out.check(c, fn, (uint64_t)c->n)) return rc;
+    TableWalk w;
+    if (int rc = typ_open(c, fn, &w, false)) return rc;
+    if (int rc = out.open(c, w.P)) return rc;
     const bool gaps = w.miss && c->opt_typ_gaps != 0;      // (without a list nothing new runs)
-    // the rows: in the caller's device memory ld entries apart; staged (host variant) dense, `width` apart, and copied row by row, so that the
-    // words of the caller's rows behind `width` are not touched
-    const uint64_t sld = device ? ld : (uint64_t)width;
-    OutStage<7> out{{{o->labels, sizeof(int64_t)}, {o->mahalanobis, sizeof(float)}, {o->tail, sizeof(float)}, {o->residual, sizeof(float) * sld},
-                     {o->zscore, sizeof(float) * sld}, {o->feature_tail, sizeof(float) * sld}, {o->features, sizeof(int32_t) * sld}}, device};
-    if (!device) {
-        if (int rc = grow(c, c->d_score_out, out.layout((size_t)w.P), "dpmm_score_points", "staging of the outputs")) return rc;
-        out.buf = c->d_score_out;
-    }
+    if (int rc = walk_ranges(c, w, c->n, fn, [&](int64_t p0, int64_t np, int64_t) -> int {
+            if (int rc = typ_range(c, w.P, p0, np, out.at<int64_t>(0, p0), out.at<float>(1, p0), out.at<float>(2, p0), fn, gaps)) return rc;
+            return device ? DPMM_OK : table_result(c, fn, out.flush(c, p0, (size_t)np));
+        })) return rc;
+    return typ_counters(c, o->skipped, o->incomplete);
+}
+
+int dpmm_typicality_points(dpmm_ctx *c, const dpmm_typicality_out *out) { return typicality_points(c, out, false, "dpmm_typicality_points"); }
+int dpmm_typicality_points_device(dpmm_ctx *c, const dpmm_typicality_out *out) { return typicality_points(c, out, true, "dpmm_typicality_points_device"); }
+
+// ---- include/dpmm_hip_explain.h: behind the typicality pass of every range, the per-feature residuals, z-scores and tails (explain.hip) ----
+static int explain_points(dpmm_ctx *c, const dpmm_explain_out *o, bool device, const char *fn) {
+    const std::string who = std::string(fn) + ": ";
+    const bool rows = o && (o->residual || o->zscore || o->feature_tail || o->features);
+    int64_t width = 0;
+    if (int rc = typ_front(c, fn, o, "explanation", rows, [&](int at) -> int {
+            if (at == 0) {
+                const int cap = std::min(c->D, DPMM_EXPLAIN_MAX_TOP);
+                if (o->top < 0 || o->top > cap) return fail(c, DPMM_EINVAL, who + "top must be in 0.." + std::to_string(cap));
+                if (o->top == 0 && o->features) return fail(c, DPMM_EINVAL, who + "features given with top = 0");
+                width = o->top ? o->top : c->D;
+            }
+            if (at == 1 && rows) {
+                if (o->ld < width) return fail(c, DPMM_EINVAL, who + "ld < " + (o->top ? "top" : "D"));
+                if (o->ld >> 31) return fail(c, DPMM_EINVAL, who + "ld out of range (below 2^31)");
+            }
+            return DPMM_OK;
+        })) return rc;
+    if (c->n == 0) return DPMM_OK;
+    const uint64_t n = (uint64_t)c->n, ld = rows ? (uint64_t)o->ld : 0;
+    if (ld && n > (UINT64_MAX / sizeof(int64_t)) / ld) return fail(c, DPMM_EINVAL, who + "n_local * ld out of range");      // (the extents below cannot wrap)
+    // the rows: in the caller's memory ld entries apart, the words behind `width` left as they are; staged (host variant) dense, `width` apart
+    // (`1, false, true`: one row a point, an output, keep)
+    const size_t rb = 4 * (size_t)width, pb = 4 * (size_t)ld;      // (4-byte entries all)
+    OutStage<7> out{{{o->labels, "labels", 8, sizeof(int64_t)}, {o->mahalanobis, "mahalanobis", 4, sizeof(float)}, {o->tail, "tail", 4, sizeof(float)},
+                     {o->residual, "residual", 4, rb, pb, 1, false, true}, {o->zscore, "zscore", 4, rb, pb, 1, false, true},
+                     {o->feature_tail, "feature_tail", 4, rb, pb, 1, false, true}, {o->features, "features", 4, rb, pb, 1, false, true}}, device};
+    if (int rc = out.check(c, fn, n)) return rc;
+    TableWalk w;
+    if (int rc = typ_open(c, fn, &w, rows)) return rc;
+    if (int rc = out.open(c, w.P)) return rc;
+    const bool gaps = w.miss && c->opt_typ_gaps != 0;      // (without a list nothing new runs)
     if (int rc = walk_ranges(c, w, c->n, fn, [&](int64_t p0, int64_t np, int64_t) -> int {
             if (int rc = typ_range(c, w.P, p0, np, out.at<int64_t>(0, p0), out.at<float>(1, p0), out.at<float>(2, p0), fn, gaps)) return rc;
             if (rows) {
-                ExplainArgs a{};
-                a.n = np; a.K = c->K; a.D = c->D;
-                a.X = c->dX + p0 * c->ldx; a.ldx = c->ldx;
-                const TypicalityArgs t = niw_range_args<TypicalityArgs>(c, w.P, p0, np);      // (the copies and the means the typicality pass has just read)
-                a.Rt = t.Rt; a.mu = t.mu; a.mu_step = t.mu_step; a.cst = t.cst;
-                a.Rr = c->d_exp_rr; a.a = c->d_exp_a; a.cls = c->d_typ_cls;
+                ExplainArgs a = explain_range_args<ExplainArgs>(c, w.P, p0, np);
+                a.a = c->d_exp_a;
                 a.residual = out.at<float>(3, p0); a.zscore = out.at<float>(4, p0); a.feature_tail = out.at<float>(5, p0); a.features = out.at<int32_t>(6, p0);
-                a.top = o->top; a.ld = (int64_t)sld;
+                a.top = o->top; a.ld = device ? (int64_t)ld : width;
                 if (gaps) { a.list = c->d_miss_list; a.list_cnt = c->d_miss_cnt; }
                 if (int rc = table_result(c, fn, launch_explain_range(a, 32 * c->cus, c->stream))) return rc;
                 if (gaps) if (int rc = table_result(c, fn, launch_explain_gap_range(a, 32 * c->cus, c->stream))) return rc;
             }
-            if (device) return DPMM_OK;
-            for (int i = 3; i < 7; ++i) {      // (4-byte entries all; then the three vectors and the wait, by flush)
-                OutCol &q = out.col[i];
-                if (!q.dst) continue;
-                HIPCHK(c, hipMemcpy2DAsync(static_cast<char *>(q.dst) + (size_t)p0 * ld * 4, (size_t)ld * 4, out.buf + q.off, (size_t)width * 4, (size_t)width * 4, (size_t)np,
-                                           hipMemcpyDeviceToHost, c->stream));
-                q.dst = nullptr;
-            }
-            const int rc = table_result(c, fn, out.flush(c, p0, (size_t)np));
-            out.col[3].dst = o->residual; out.col[4].dst = o->zscore; out.col[5].dst = o->feature_tail; out.col[6].dst = o->features;
-            return rc;
+            return device ? DPMM_OK : table_result(c, fn, out.flush(c, p0, (size_t)np));
         })) return rc;
-    HIPCHK(c, sync_stream(c, c->stream));
-    unsigned long long h[3] = {0, 0, 0};
-    HIPCHK(c, hipMemcpy(h, c->d_typ_cnt, sizeof(h), hipMemcpyDeviceToHost));
-    if (o->skipped) o->skipped[0] = (int64_t)h[0];
-    if (o->incomplete) o->incomplete[0] = (int64_t)(h[1] - h[2]);      // (h[2]: scored with gaps, 0 without the option)
-    return DPMM_OK;
+    return typ_counters(c, o->skipped, o->incomplete);
 }
 
 int dpmm_explain_points(dpmm_ctx *c, const dpmm_explain_out *out) { return explain_points(c, out, false, "dpmm_explain_points"); }
@@ -4367,76 +4370,39 @@ int dpmm_set_explain_groups(dpmm_ctx *c, int32_t G, const int64_t *offsets, cons
 }
 
 static int explain_groups_points(dpmm_ctx *c, const dpmm_explain_groups_out *o, bool device, const char *fn) {
-    if (!c) return tensor_no_ctx(fn);
-    c->miss_counted = false;      // (as score_points)
     const std::string who = std::string(fn) + ": ";
-    if (!o) return fail(c, DPMM_EINVAL, who + "out is null");
-    if (c->prior != DPMM_PRIOR_NIW) return fail(c, DPMM_EINVAL, who + "the explanation is that of the NIW prior's Student-t predictive; the Multinomial predictive has no closed-form tail");
-    const bool rows = o->group_mahalanobis || o->group_tail;
-    if (!o->labels && !o->mahalanobis && !o->tail && !o->skipped && !o->incomplete && !rows) return fail(c, DPMM_EINVAL, who + "every output pointer is null");
-    if (!c->predictive) return fail(c, DPMM_ESTATE, who + "needs dpmm_set_predictive_niw first");
-    if (c->exg_gen == 0 || c->exg_gen != c->pred_gen) return fail(c, DPMM_ESTATE, who + "needs dpmm_set_explain_groups for the predictive parameters in force");
-    const int64_t width = c->exg_G;
-    if (rows && o->ld < width) return fail(c, DPMM_EINVAL, who + "ld < G");
-    if (rows && (o->ld >> 31)) return fail(c, DPMM_EINVAL, who + "ld out of range (below 2^31)");
-    HIPCHK(c, hipSetDevice(c->device));
-    if (o->skipped) o->skipped[0] = 0;
-    if (o->incomplete) o->incomplete[0] = 0;
+    const bool rows = o && (o->group_mahalanobis || o->group_tail);
+    if (int rc = typ_front(c, fn, o, "explanation", rows, [&](int at) -> int {
+            if (at != 2) return DPMM_OK;
+            if (c->exg_gen == 0 || c->exg_gen != c->pred_gen) return fail(c, DPMM_ESTATE, who + "needs dpmm_set_explain_groups for the predictive parameters in force");
+            if (rows && o->ld < c->exg_G) return fail(c, DPMM_EINVAL, who + "ld < G");
+            if (rows && (o->ld >> 31)) return fail(c, DPMM_EINVAL, who + "ld out of range (below 2^31)");
+            return DPMM_OK;
+        })) return rc;
     if (c->n == 0) return DPMM_OK;
-    if (!c->have_points || !c->have_params || !c->dX) return fail(c, DPMM_ESTATE, who + "needs points and parameters");
+    const int64_t width = c->exg_G;
     const uint64_t n = (uint64_t)c->n, ld = rows ? (uint64_t)o->ld : 0;
     if (ld && n > (UINT64_MAX / sizeof(int64_t)) / ld) return fail(c, DPMM_EINVAL, who + "n_local * ld out of range");      // (the extents below cannot wrap)
-    if (device) {
-        if (o->labels) if (int rc = check_device_extent(c, fn, "labels", o->labels, sizeof(int64_t) * n, sizeof(int64_t))) return rc;
-        if (o->mahalanobis) if (int rc = check_device_extent(c, fn, "mahalanobis", o->mahalanobis, sizeof(float) * n, sizeof(float))) return rc;
-        if (o->tail) if (int rc = check_device_extent(c, fn, "tail", o->tail, sizeof(float) * n, sizeof(float))) return rc;
-        if (o->group_mahalanobis) if (int rc = check_device_extent(c, fn, "group_mahalanobis", o->group_mahalanobis, sizeof(float) * n * ld, sizeof(float))) return rc;
-        if (o->group_tail) if (int rc = check_device_extent(c, fn, "group_tail", o->group_tail, sizeof(float) * n * ld, sizeof(float))) return rc;
-    }
+    // the rows: as explain_points -- ld entries apart, the words behind the G entries left as they are; staged (host variant) dense
+    const size_t rb = sizeof(float) * (size_t)width, pb = sizeof(float) * (size_t)ld;
+    OutStage<5> out{{{o->labels, "labels", 8, sizeof(int64_t)}, {o->mahalanobis, "mahalanobis", 4, sizeof(float)}, {o->tail, "tail", 4, sizeof(float)},
+                     {o->group_mahalanobis, "group_mahalanobis", 4, rb, pb, 1, false, true}, {o->group_tail, "group_tail", 4, rb, pb, 1, false, true}}, device};
+    if (int rc = out.check(c, fn, n)) return rc;
     TableWalk w;
-    if (int rc = walk_open(c, fn, WALK_MISS_OPTION, &w)) return rc;
-    if (int rc = typ_begin(c, w.P, fn)) return rc;
-    if (rows) if (int rc = explain_params(c)) return rc;      // (the row-major factors of explain.hip)
-    HIPCHK(c, hipMemsetAsync(c->d_typ_cnt, 0, 3 * sizeof(unsigned long long), c->stream));
-    // the rows: as explain_points -- in the caller's device memory ld entries apart; staged (host variant) dense and copied row by row
-    const uint64_t sld = device ? ld : (uint64_t)width;
-    OutStage<5> out{{{o->labels, sizeof(int64_t)}, {o->mahalanobis, sizeof(float)}, {o->tail, sizeof(float)}, {o->group_mahalanobis, sizeof(float) * sld},
-                     {o->group_tail, sizeof(float) * sld}}, device};
-    if (!device) {
-        if (int rc = grow(c, c->d_score_out, out.layout((size_t)w.P), "dpmm_score_points", "staging of the outputs")) return rc;
-        out.buf = c->d_score_out;
-    }
+    if (int rc = typ_open(c, fn, &w, rows)) return rc;      // (the row-major factors of explain.hip)
+    if (int rc = out.open(c, w.P)) return rc;
     if (int rc = walk_ranges(c, w, c->n, fn, [&](int64_t p0, int64_t np, int64_t) -> int {
             if (int rc = typ_range(c, w.P, p0, np, out.at<int64_t>(0, p0), out.at<float>(1, p0), out.at<float>(2, p0), fn)) return rc;
             if (rows) {
-                ExplainGroupArgs a{};
-                a.n = np; a.K = c->K; a.D = c->D; a.G = c->exg_G;
-                a.X = c->dX + p0 * c->ldx; a.ldx = c->ldx;
-                const TypicalityArgs t = niw_range_args<TypicalityArgs>(c, w.P, p0, np);      // (the copies and the means the typicality pass has just read)
-                a.Rt = t.Rt; a.mu = t.mu; a.mu_step = t.mu_step; a.cst = t.cst;
-                a.Rr = c->d_exp_rr; a.cls = c->d_typ_cls;
+                ExplainGroupArgs a = explain_range_args<ExplainGroupArgs>(c, w.P, p0, np);
+                a.G = c->exg_G;
                 a.goff = c->d_exg_desc; a.gfeat = c->d_exg_desc + (c->exg_G + 1); a.gw = c->d_exg_gw; a.W = c->d_exg_w; a.wstep = c->exg_wstep;
-                a.group_q = out.at<float>(3, p0); a.group_tail = out.at<float>(4, p0); a.ld = (int64_t)sld;
+                a.group_q = out.at<float>(3, p0); a.group_tail = out.at<float>(4, p0); a.ld = device ? (int64_t)ld : width;
                 if (int rc = table_result(c, fn, launch_explain_group_range(a, 32 * c->cus, c->stream))) return rc;
             }
-            if (device) return DPMM_OK;
-            for (int i = 3; i < 5; ++i) {      // (then the three vectors and the wait, by flush)
-                OutCol &q = out.col[i];
-                if (!q.dst) continue;
-                HIPCHK(c, hipMemcpy2DAsync(static_cast<char *>(q.dst) + (size_t)p0 * ld * 4, (size_t)ld * 4, out.buf + q.off, (size_t)width * 4, (size_t)width * 4, (size_t)np,
-                                           hipMemcpyDeviceToHost, c->stream));
-                q.dst = nullptr;
-            }
-            const int rc = table_result(c, fn, out.flush(c, p0, (size_t)np));
-            out.col[3].dst = o->group_mahalanobis; out.col[4].dst = o->group_tail;
-            return rc;
+            return device ? DPMM_OK : table_result(c, fn, out.flush(c, p0, (size_t)np));
         })) return rc;
-    HIPCHK(c, sync_stream(c, c->stream));
-    unsigned long long h[3] = {0, 0, 0};
-    HIPCHK(c, hipMemcpy(h, c->d_typ_cnt, sizeof(h), hipMemcpyDeviceToHost));
-    if (o->skipped) o->skipped[0] = (int64_t)h[0];
-    if (o->incomplete) o->incomplete[0] = (int64_t)h[1];
-    return DPMM_OK;
+    return typ_counters(c, o->skipped, o->incomplete);
 }
 
 int dpmm_explain_groups_points(dpmm_ctx *c, const dpmm_explain_groups_out *out) { return explain_groups_points(c, out, false, "dpmm_explain_groups_points"); }
@@ -4454,23 +4420,19 @@ static int impute_points(dpmm_ctx *c, float *out, int64_t ld, bool device, const
     if (c->n == 0) return DPMM_OK;
     if (!c->have_points || !c->have_params || !c->dX) return fail(c, DPMM_ESTATE, who + "needs points and parameters");
     if (!out) return fail(c, DPMM_EINVAL, who + "out is null");
-    if (device) if (int rc = check_device_extent(c, fn, "d_out", out, (uint64_t)c->n * (uint64_t)ld * sizeof(float), sizeof(float))) return rc;
+    // the rows: in the caller's device memory ld floats apart; staged (host variant) dense, D apart
+    OutStage<1> st{{{out, "d_out", 4, sizeof(float) * (size_t)c->D, sizeof(float) * (size_t)ld}}, device};
+    if (int rc = st.check(c, fn, (uint64_t)c->n)) return rc;
     TableWalk w;
     if (int rc = walk_open(c, fn, WALK_MISS_ALWAYS, &w)) return rc;
     w.miss = false;      // the consumer patches: the rows the imputation is written behind are copied first
-    const int64_t P = w.P, D = c->D;
-    if (!device) if (int rc = grow(c, c->d_score_out, sizeof(float) * (size_t)P * (size_t)D, "dpmm_score_points", "staging of the outputs")) return rc;
+    if (int rc = st.open(c, w.P)) return rc;
     if (int rc = walk_ranges(c, w, c->n, fn, [&](int64_t p0, int64_t np, int64_t) -> int {
-            float *rows = device ? out + p0 * ld : reinterpret_cast<float *>(c->d_score_out.get());
-            const int64_t ldr = device ? ld : D;
+            float *rows = st.at<float>(0, p0);
+            const int64_t ldr = device ? ld : c->D;
             HIPCHK(c, launch_points_readback(rows, ldr, c->dX + p0 * c->ldx, c->ldx, nullptr, 0, np, c->D, c->stream));
-            if (int rc = miss_range(c, P, p0, np, rows, ldr, fn)) return rc;
-            if (!device) {
-                HIPCHK(c, hipMemcpy2DAsync(out + p0 * ld, sizeof(float) * (size_t)ld, rows, sizeof(float) * (size_t)D, sizeof(float) * (size_t)D, (size_t)np, hipMemcpyDeviceToHost, c->stream));
-                HIPCHK(c, sync_stream(c, c->stream));      // the staging block is rewritten by the next range
-                if (ld > D) for (int64_t i = p0; i < p0 + np; ++i) memset(out + i * ld + D, 0, sizeof(float) * (size_t)(ld - D));
-            }
-            return DPMM_OK;
+            if (int rc = miss_range(c, w.P, p0, np, rows, ldr, fn)) return rc;
+            return device ? DPMM_OK : table_result(c, fn, st.flush(c, p0, (size_t)np));
         })) return rc;
     HIPCHK(c, sync_stream(c, c->stream));
     return DPMM_OK;
@@ -4572,22 +4534,14 @@ static int regress_points(dpmm_ctx *c, float *mean, float *sd, int64_t ld, int64
     if (c->n == 0) return DPMM_OK;
     if (!c->have_points || !c->have_params || !c->dX) return fail(c, DPMM_ESTATE, who + "needs points and parameters");
     if (!mean) return fail(c, DPMM_EINVAL, who + "mean is null");
-    const uint64_t n = (uint64_t)c->n;
-    if (device) {
-        if (int rc = check_device_extent(c, fn, "d_mean", mean, n * (uint64_t)ld * sizeof(float), sizeof(float))) return rc;
-        if (sd) if (int rc = check_device_extent(c, fn, "d_std", sd, n * (uint64_t)ld * sizeof(float), sizeof(float))) return rc;
-        if (labels) if (int rc = check_device_extent(c, fn, "d_labels", labels, n * sizeof(int64_t), sizeof(int64_t))) return rc;
-    }
+    // the rows: in the caller's device memory ld floats apart; staged (host variant) dense, D_t apart
+    const size_t row = sizeof(float) * (size_t)Dt, pitch = sizeof(float) * (size_t)ld;
+    OutStage<3> out{{{mean, "d_mean", 4, row, pitch}, {sd, "d_std", 4, row, pitch}, {labels, "d_labels", 8, sizeof(int64_t)}}, device};
+    if (int rc = out.check(c, fn, (uint64_t)c->n)) return rc;
     TableWalk w;
     if (int rc = walk_open(c, fn, WALK_MISS_NEVER, &w)) return rc;
     if (int rc = skip_open(c, c->d_reg_skip, w.P, fn, "counts of the regression pass")) return rc;
-    // the rows: in the caller's device memory ld floats apart; staged (host variant) dense, D_t apart
-    const size_t row = sizeof(float) * (size_t)Dt, pitch = sizeof(float) * (size_t)ld;
-    OutStage<3> out{{{mean, row, pitch}, {sd, row, pitch}, {labels, sizeof(int64_t)}}, device};
-    if (!device) {
-        if (int rc = grow(c, c->d_score_out, out.layout((size_t)w.P), "dpmm_score_points", "staging of the outputs")) return rc;
-        out.buf = c->d_score_out;
-    }
+    if (int rc = out.open(c, w.P)) return rc;
     if (int rc = walk_ranges(c, w, c->n, fn, [&](int64_t p0, int64_t np, int64_t) {
             RegressArgs a{};
             a.t = regress_tile(c, w.P, p0, np, out.at<int64_t>(2, p0), c->d_reg_skip);
@@ -4720,37 +4674,30 @@ static int regress_cdf_points(dpmm_ctx *c, const float *y, int64_t ldy, float *o
     if (!c->have_points || !c->have_params || !c->dX) return fail(c, DPMM_ESTATE, who + "needs points and parameters");
     if (!out) return fail(c, DPMM_EINVAL, who + (quant ? "out is null" : "cdf is null"));
     if (!quant && !y) return fail(c, DPMM_EINVAL, who + "y is null");
-    const uint64_t n = (uint64_t)c->n;
-    if (device) {
-        if (!quant) if (int rc = check_device_extent(c, fn, "d_y", y, n * (uint64_t)ldy * sizeof(float), sizeof(float))) return rc;
-        if (int rc = check_device_extent(c, fn, quant ? "d_out" : "d_cdf", out, n * (uint64_t)L * (uint64_t)ld * sizeof(float), sizeof(float))) return rc;
-        if (sf) if (int rc = check_device_extent(c, fn, "d_sf", sf, n * (uint64_t)ld * sizeof(float), sizeof(float))) return rc;
-        if (labels) if (int rc = check_device_extent(c, fn, "d_labels", labels, n * sizeof(int64_t), sizeof(int64_t))) return rc;
-    }
+    // the rows: in the caller's device memory ld (ldy) floats apart, L rows a point; staged (host variants) dense, D_t apart.  y (null with
+    // quant) comes first: its extent is the first one checked
+    const size_t row = sizeof(float) * (size_t)Dt, pitch = sizeof(float) * (size_t)ld;
+    OutStage<4> st{{{const_cast<float *>(y), "d_y", 4, row, sizeof(float) * (size_t)ldy, 1, true}, {out, quant ? "d_out" : "d_cdf", 4, row, pitch, (size_t)L},
+                    {sf, "d_sf", 4, row, pitch}, {labels, "d_labels", 8, sizeof(int64_t)}}, device};
+    if (int rc = st.check(c, fn, (uint64_t)c->n)) return rc;
     TableWalk w;
     if (int rc = walk_open(c, fn, WALK_MISS_NEVER, &w)) return rc;
     if (int rc = skip_open(c, c->d_reg_skip, w.P, fn, "counts of the regression pass")) return rc;
-    // the rows: in the caller's device memory ld (ldy) floats apart, L rows a point; staged (host variants) dense, D_t apart
-    const size_t row = sizeof(float) * (size_t)Dt, pitch = sizeof(float) * (size_t)ld;
-    OutStage<4> st{{{out, row, pitch, (size_t)L}, {sf, row, pitch}, {labels, sizeof(int64_t)}, {const_cast<float *>(y), row, sizeof(float) * (size_t)ldy, 1, true}}, device};
-    if (!device) {
-        if (int rc = grow(c, c->d_score_out, st.layout((size_t)w.P), "dpmm_score_points", "staging of the outputs")) return rc;
-        st.buf = c->d_score_out;
-    }
+    if (int rc = st.open(c, w.P)) return rc;
     const double *lev = c->d_reg_lev;
     if (int rc = walk_ranges(c, w, c->n, fn, [&](int64_t p0, int64_t np, int64_t) {
-            const RegressTile t = regress_tile(c, w.P, p0, np, st.at<int64_t>(2, p0), c->d_reg_skip);
+            const RegressTile t = regress_tile(c, w.P, p0, np, st.at<int64_t>(3, p0), c->d_reg_skip);
             hipError_t e = device ? hipSuccess : st.load(c, p0, (size_t)np);
             if (e != hipSuccess) return e;
             if (quant) {
                 RegressQuantileArgs a = regress_flat_args<RegressQuantileArgs>(c, t);
                 a.levels = lev; a.z = lev + L; a.lc = lev + L + (int64_t)c->K * L; a.L = (int)L;
-                a.out = st.at<float>(0, p0); a.ld = device ? ld : Dt;
+                a.out = st.at<float>(1, p0); a.ld = device ? ld : Dt;
                 e = launch_regress_quantile_range(a, c->stream);
             } else {
                 RegressCdfArgs a = regress_flat_args<RegressCdfArgs>(c, t);
-                a.y = st.at<float>(3, p0); a.ldy = device ? ldy : Dt;
-                a.cdf = st.at<float>(0, p0); a.sf = st.at<float>(1, p0); a.ld = device ? ld : Dt;
+                a.y = st.at<float>(0, p0); a.ldy = device ? ldy : Dt;
+                a.cdf = st.at<float>(1, p0); a.sf = st.at<float>(2, p0); a.ld = device ? ld : Dt;
                 e = launch_regress_cdf_range(a, c->stream);
             }
             if (e == hipSuccess && !device) e = st.flush(c, p0, (size_t)np);
@@ -4775,11 +4722,12 @@ int dpmm_regress_quantile_points_device(dpmm_ctx *c, float *d_out, int64_t ld, i
 // ---- include/dpmm_hip_rank.h: exemplars, the m most and least typical points of every cluster (rank.hip) -----------------------------------
 static size_t rank_keys_words(int K) { return (size_t)2 * (size_t)K * RANK_SLOTS; }
 static size_t rank_count_words(int K) { return (size_t)RANK_REPL * (size_t)(K + 1); }
-// the outputs of dpmm_rank_read in the order of its staging block: idx | idx | score | score | count | skipped (launch_rank_read writes all six)
+// the outputs of dpmm_rank_read in the order of dpmm_rank_out, one element per column: the whole array (launch_rank_read writes all six)
 static OutStage<6> rank_out_stage(const dpmm_rank_out &o, int K, int m, bool device) {
     const size_t km = (size_t)K * (size_t)m;
-    return {{{o.typ_idx, sizeof(int64_t) * km}, {o.fringe_idx, sizeof(int64_t) * km}, {o.typ_score, sizeof(float) * km}, {o.fringe_score, sizeof(float) * km},
-             {o.count, sizeof(int64_t) * (size_t)K}, {o.skipped, sizeof(int64_t)}}, device, true};
+    return {{{o.typ_idx, "typ_idx", 8, sizeof(int64_t) * km}, {o.typ_score, "typ_score", 4, sizeof(float) * km}, {o.fringe_idx, "fringe_idx", 8, sizeof(int64_t) * km},
+             {o.fringe_score, "fringe_score", 4, sizeof(float) * km}, {o.count, "count", 8, sizeof(int64_t) * (size_t)K}, {o.skipped, "skipped", 8, sizeof(int64_t)}},
+            device, true};
 }
 
 int dpmm_rank_begin(dpmm_ctx *c, int m, int which) {
@@ -4846,19 +4794,11 @@ static int rank_read(dpmm_ctx *c, const dpmm_rank_out *o, bool device, const cha
     if (!c->rank_active) return fail(c, DPMM_ESTATE, who + "needs dpmm_rank_begin first");
     HIPCHK(c, hipSetDevice(c->device));
     const int K = c->rank_K, m = c->rank_m;
-    const uint64_t km = (uint64_t)K * (uint64_t)m;
-    if (device) {
-        if (o->typ_idx) if (int rc = check_device_extent(c, fn, "typ_idx", o->typ_idx, sizeof(int64_t) * km, sizeof(int64_t))) return rc;
-        if (o->typ_score) if (int rc = check_device_extent(c, fn, "typ_score", o->typ_score, sizeof(float) * km, sizeof(float))) return rc;
-        if (o->fringe_idx) if (int rc = check_device_extent(c, fn, "fringe_idx", o->fringe_idx, sizeof(int64_t) * km, sizeof(int64_t))) return rc;
-        if (o->fringe_score) if (int rc = check_device_extent(c, fn, "fringe_score", o->fringe_score, sizeof(float) * km, sizeof(float))) return rc;
-        if (o->count) if (int rc = check_device_extent(c, fn, "count", o->count, sizeof(int64_t) * (uint64_t)K, sizeof(int64_t))) return rc;
-        if (o->skipped) if (int rc = check_device_extent(c, fn, "skipped", o->skipped, sizeof(int64_t), sizeof(int64_t))) return rc;
-    }
-    OutStage<6> out = rank_out_stage(*o, K, m, device);      // one element per column: the whole array
+    OutStage<6> out = rank_out_stage(*o, K, m, device);
+    if (int rc = out.check(c, fn, 1)) return rc;
     out.layout(1);
     out.buf = c->d_rank_out;      // (dpmm_rank_begin sized it)
-    const RankOut r{out.at<int64_t>(0, 0), out.at<float>(2, 0), out.at<int64_t>(1, 0), out.at<float>(3, 0), out.at<int64_t>(4, 0), out.at<int64_t>(5, 0)};
+    const RankOut r{out.at<int64_t>(0, 0), out.at<float>(1, 0), out.at<int64_t>(2, 0), out.at<float>(3, 0), out.at<int64_t>(4, 0), out.at<int64_t>(5, 0)};
     const unsigned long long *keys = c->d_rank_state, *count = keys + rank_keys_words(K);
     hipError_t e = launch_rank_read(keys, count, K, m, c->rank_which, r, c->stream);
     if (e == hipSuccess) e = device ? sync_stream(c, c->stream) : out.flush(c, 0, 1);
@@ -5344,22 +5284,14 @@ static int recommend_points(dpmm_ctx *c, int m, int exclude_seen, int32_t *featu
     const int store = count_store(c);
     if (!count_store_ready(c, store)) return fail(c, DPMM_ESTATE, who + "needs points and parameters");
     if (!features || !prob) return fail(c, DPMM_EINVAL, who + (features ? "prob is null" : "features is null"));
-    const uint64_t n = (uint64_t)c->n;
-    if (device) {
-        if (int rc = check_device_extent(c, fn, "d_features", features, n * (uint64_t)ld * sizeof(int32_t), sizeof(int32_t))) return rc;
-        if (int rc = check_device_extent(c, fn, "d_prob", prob, n * (uint64_t)ld * sizeof(float), sizeof(float))) return rc;
-        if (labels) if (int rc = check_device_extent(c, fn, "d_labels", labels, n * sizeof(int64_t), sizeof(int64_t))) return rc;
-    }
+    // the rows: in the caller's device memory ld words apart; staged (host variant) dense, m apart
+    const size_t rb = 4 * (size_t)m, pb = 4 * (size_t)ld;      // (4-byte words both)
+    OutStage<3> out{{{features, "d_features", 4, rb, pb}, {prob, "d_prob", 4, rb, pb}, {labels, "d_labels", 8, sizeof(int64_t)}}, device};
+    if (int rc = out.check(c, fn, (uint64_t)c->n)) return rc;
     TableWalk w;
     if (int rc = walk_open(c, fn, WALK_MISS_NEVER, &w)) return rc;
     if (int rc = skip_open(c, c->d_rec_skip, w.P, fn, "counts of the recommendation pass")) return rc;
-    // the rows: in the caller's device memory ld words apart; staged (host variant) dense, m apart
-    OutStage<3> out{{{features, sizeof(int32_t) * (size_t)m, sizeof(int32_t) * (size_t)ld}, {prob, sizeof(float) * (size_t)m, sizeof(float) * (size_t)ld},
-                     {labels, sizeof(int64_t)}}, device};
-    if (!device) {
-        if (int rc = grow(c, c->d_score_out, out.layout((size_t)w.P), "dpmm_score_points", "staging of the outputs")) return rc;
-        out.buf = c->d_score_out;
-    }
+    if (int rc = out.open(c, w.P)) return rc;
     if (int rc = walk_ranges(c, w, c->n, fn, [&](int64_t p0, int64_t np, int64_t) {
             RecommendArgs a{};
             a.table = c->d_score_table; a.stride = w.P; a.rstep = w.rstep; a.n = np; a.K = c->K; a.Kp = c->K + (c->K & 1); a.D = c->D; a.Dp = recommend_pitch(c->D);
@@ -5438,31 +5370,20 @@ static int count_explain_points(dpmm_ctx *c, const dpmm_count_explain_out *o, bo
     if (c->n == 0) return DPMM_OK;
     const int store = count_store(c);
     if (!count_store_ready(c, store)) return fail(c, DPMM_ESTATE, who + "needs points and parameters");
-    struct { const char *name; void *p; size_t word; } rows[5] = {{"features", o->features, sizeof(int32_t)}, {"count", o->count, sizeof(float)}, {"expected", o->expected, sizeof(float)},
-                                                                   {"residual", o->residual, sizeof(float)}, {"feature_tail", o->feature_tail, sizeof(float)}};
-    for (const auto &r : rows)
-        if (!r.p) return fail(c, DPMM_EINVAL, who + r.name + " is null");
-    const uint64_t n = (uint64_t)c->n;
-    if (device) {
-        for (const auto &r : rows)
-            if (int rc = check_device_extent(c, fn, (std::string("d_") + r.name).c_str(), r.p, n * (uint64_t)ld * r.word, r.word)) return rc;
-        if (o->labels) if (int rc = check_device_extent(c, fn, "d_labels", o->labels, n * sizeof(int64_t), sizeof(int64_t))) return rc;
-        if (o->total) if (int rc = check_device_extent(c, fn, "d_total", o->total, n * sizeof(double), sizeof(double))) return rc;
-    }
+    // the rows: in the caller's device memory ld words apart; staged (host variant) dense, top apart
+    const size_t rb = sizeof(float) * (size_t)top, pb = sizeof(float) * (size_t)ld;      // (the five arrays have 4-byte words)
+    OutStage<7> out{{{o->features, "d_features", 4, rb, pb}, {o->count, "d_count", 4, rb, pb}, {o->expected, "d_expected", 4, rb, pb}, {o->residual, "d_residual", 4, rb, pb},
+                     {o->feature_tail, "d_feature_tail", 4, rb, pb}, {o->labels, "d_labels", 8, sizeof(int64_t)}, {o->total, "d_total", 8, sizeof(double)}}, device};
+    for (int i = 0; i < 5; ++i)
+        if (!out.col[i].dst) return fail(c, DPMM_EINVAL, who + (out.col[i].name + 2) + " is null");      // (the field's name: without the d_)
+    if (int rc = out.check(c, fn, (uint64_t)c->n)) return rc;
     TableWalk w;
     if (int rc = walk_open(c, fn, WALK_MISS_NEVER, &w)) return rc;
     if (int rc = skip_open(c, c->d_cex_skip, w.P, fn, "counts of the skipped points")) return rc;
     if (int rc = skip_open(c, c->d_cex_inc, w.P, fn, "counts of the incomplete points")) return rc;
     if (int rc = grow(c, c->d_cex_tot, sizeof(double) * (size_t)w.P, fn, "totals of the points")) return rc;
     if (int rc = grow(c, c->d_cex_lab, sizeof(int32_t) * (size_t)w.P, fn, "labels of the points")) return rc;
-    // the rows: in the caller's device memory ld words apart; staged (host variant) dense, top apart
-    const size_t rb = sizeof(float) * (size_t)top, pb = sizeof(float) * (size_t)ld;      // (the five arrays have 4-byte words)
-    OutStage<7> out{{{o->features, rb, pb}, {o->count, rb, pb}, {o->expected, rb, pb}, {o->residual, rb, pb}, {o->feature_tail, rb, pb}, {o->labels, sizeof(int64_t)},
-                     {o->total, sizeof(double)}}, device};
-    if (!device) {
-        if (int rc = grow(c, c->d_score_out, out.layout((size_t)w.P), fn, "staging of the outputs")) return rc;
-        out.buf = c->d_score_out;
-    }
+    if (int rc = out.open(c, w.P)) return rc;
     const size_t KD = (size_t)c->K * (size_t)c->D;
     if (int rc = walk_ranges(c, w, c->n, fn, [&](int64_t p0, int64_t np, int64_t) {
             CountExplainArgs a{};
